@@ -1,13 +1,18 @@
 #!/usr/bin/env python3
 """bench.py -- decode throughput of the HIP path on llama2-7B-shaped synthetic fp32 weights.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus 1 --steps K --warmup W --full
   python bench.py --gpus N ...          (N > 1 without a launcher: this script starts the N ranks itself)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 N = 1: one decode step = one forward() (infer.rs:8-53) + greedy sample, chained on the device,
-starting at pos 0 like generate() (BOS, then the Rama-BPE ids of 'once upon a time').  Two modes of
-the SAME entry points are timed in one run:
+starting at pos 0 like generate() (BOS, then the Rama-BPE ids of 'once upon a time').  A plain run
+sets up, settles and warms up, times the K steps of the headline mode (parity mode unless --mode
+leaves it out), writes the last step's logits and the generation's tokens with --dump-outputs, and
+prints the line.  Everything else described here -- the other modes, per-kernel times and the
+roofline, the CPU baseline and every check against the oracle, the other shapes -- runs with --full.
+Two modes of the SAME entry points are timed in a --full run:
   * parity mode (`value`): every op in the reference CPU path's own rounding order, on the model's
     chain-order weight copy (csrc/chain.hpp) -- logits bit-identical to engine/src/device/cpu.rs, the
     only way to stay within north_star's 1e-4 over a 200-token generation at llama2-7B depth (checked
@@ -23,7 +28,8 @@ every sequence by one token (rama_amd/pipeline.py, csrc/pipe.hip).
 
 Prints ONE JSON line (see the driver contract): whole-job tokens/s, `roofline` for the dominant kernel
 (W1|W3 SwiGLU matvec, 43 % of the bytes) and `cpu_baseline` (the oracle -- the C restatement of the
-reference CPU path -- timed at full depth on the host cores, rank 0, N = 1 only).
+reference CPU path -- timed at full depth on the host cores, rank 0, N = 1 only); at N = 1 the last
+two are null without --full.
 """
 from __future__ import annotations
 
@@ -79,6 +85,13 @@ def parse(argv=None):
                          "N = 1 only; the default 0 is generate()'s own start (BOS + prompt)")
     ap.add_argument("--cpu-tokens", type=int, default=16, help="tokens of the CPU baseline's sample (the first one warms up); every mode's logits are compared with the oracle's at each of them")
     ap.add_argument("--rank-timeout", type=float, default=900.0, help="seconds the self-started ranks of --gpus N may take")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: everything beyond the headline as well -- the other modes of --mode, per-kernel times and the roofline, -r 1, prefill, "
+                         "generation_200, by_position, bar mode, trait_ops_path, the other shapes, cpu_baseline and every oracle check (the --no-* "
+                         "switches apply); without it a run times the headline mode alone")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="N = 1: after the timed steps write what they computed -- the last step's logits and the generation's tokens -- "
+                         "as DIR/<name>.npy (float32 / float64)")
     return ap.parse_args(argv)
 
 
@@ -244,6 +257,16 @@ def cpu_baseline(shape_name, n_tokens, check_engines=None):
                      + f" + classifier, {n} tokens after 1 warm-up = positions 1-{n} (BOS + prompt from position 0: the short-context best case of the CPU path too); oracle/rama_oracle.c "
                      f"(C restatement of engine/src/device/cpu.rs), OpenMP threads={threads}"}
     return out, {m: c for m, c in chk.items() if c["checked_positions"]}
+
+
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs: {name: array} -> out_dir/<name>.npy, float32 stays float32, anything else is written as float64"""
+    import numpy as np
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in outputs.items():
+        a = np.asarray(a)
+        np.save(d / f"{name}.npy", a if a.dtype == np.float32 else a.astype(np.float64))
 
 
 def time_decode(eng, dev, seq, steps, warmup, pos0, prompt, temperature=0.0, settle_s=0.0):
@@ -500,9 +523,10 @@ MODE_TEXT = {
 }
 
 
-def run_shape(dev, name, steps, warmup, pos0, graph, modes, kprof, sampled=False, settle_s=0.0, gen_head=None):
+def run_shape(dev, name, steps, warmup, pos0, graph, modes, kprof, sampled=False, settle_s=0.0, gen_head=None, keep_outputs=None):
     """the requested modes of one shape on one resident model -> (cfg, model, bytes, {mode: {...}});
-    sampled: also time the head mode with the README's `-r 1` (Device::sample's top-p path, on the device)"""
+    sampled: also time the head mode with the README's `-r 1` (Device::sample's top-p path, on the device);
+    keep_outputs: for this mode, `outputs` = what its timed steps computed (the last step's logits, the generation's tokens)"""
     import rama_amd
     d, h, L, H, V, seq, shared = SHAPES[name]
     cfg = rama_amd.Config(d, h, L, H, H, V, seq, shared)
@@ -527,6 +551,9 @@ def run_shape(dev, name, steps, warmup, pos0, graph, modes, kprof, sampled=False
              "frac_of_8TBps": round(bytes_["token"] * tok_s / 1e9 / HBM_PEAK_GBPS, 4),
              "positions": f"{pos0 + warmup}..{pos0 + warmup + steps - 1}" + (" (wrapping at seq_len)" if pos0 + warmup + steps > seq else ""),
              "tokens": tokens}
+        if mode == keep_outputs:      # read before anything else runs on this engine
+            import numpy as np
+            r["outputs"] = {"logits": eng.logits(), "tokens": np.asarray(tokens, dtype=np.float64)}
         if sampled and mode in sampled:
             # BASELINE config 3 as the README ran it: `-r 1` (README.md:80-83) = temperature 1, topp 0.9 (main.rs:48-50), Device::sample
             # (cpu.rs:155-179) on the device inside the chained loop.  Synthetic logits are flat: every entry is a top-p candidate, the worst case.
@@ -605,9 +632,17 @@ def single_gpu(args, local_rank):
     dev = rama_amd.Hip(local_rank)
     modes = {"all": ["fast", "tol", "parity"], "both": ["fast", "parity"]}.get(args.mode, [args.mode])
     head = "parity" if "parity" in modes else modes[-1]
+    if not args.full:      # a plain run: the headline mode's timed steps and nothing else
+        modes = [head]
+        for k_ in ("no_cpu_baseline", "no_kprof", "no_prefill", "no_other_configs", "no_sampled", "no_by_position", "no_generation_200", "no_trait_ops"):
+            setattr(args, k_, True)
     cfg, model, bytes_, res = run_shape(dev, args.config, args.steps, args.warmup, args.pos0, args.graph, modes, not args.no_kprof,
                                         sampled=() if args.no_sampled else (head,), settle_s=args.settle_s,
-                                        gen_head=None if (args.no_generation_200 or args.pos0) else head)
+                                        gen_head=None if (args.no_generation_200 or args.pos0) else head,
+                                        keep_outputs=head if args.dump_outputs else None)
+    outputs = res[head].pop("outputs", None)
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs)
     d, h, L, H, V, seq, shared = SHAPES[args.config]
     for m_ in modes:
         if m_ != "fast" and "fast" in res:
@@ -710,7 +745,7 @@ def single_gpu(args, local_rank):
     }
     if r.get("generation_200"):
         line["generation_200"] = r["generation_200"]      # the headline mode over the README's whole generation (positions 0..199): first use, cold, settled
-    full = parity_200pos() if args.config == "llama2-7B" else None
+    full = parity_200pos() if (args.full and args.config == "llama2-7B") else None
     for m_ in modes:
         block = {k: v for k, v in res[m_].items() if k != "tokens"}
         if m_ in check:
@@ -752,8 +787,10 @@ def single_gpu(args, local_rank):
     bw = (line.get("bar_mode") or {}).get("whole_context_vs_oracle")
     if bw:
         quoted[bw["source"]] = bw.get("library")
-    line["profiles_quoted"] = quoted
-    line["profile_matches_build"] = bool(quoted) and not lib.get("stale_build") and all(v is not None and v == lib["src_sha16"] for v in quoted.values())
+    if args.full:      # a plain run quotes no committed file
+        line["profiles_quoted"] = quoted
+        line["profile_matches_build"] = bool(quoted) and not lib.get("stale_build") and all(v is not None and v == lib["src_sha16"] for v in quoted.values())
+    line["full"] = bool(args.full)
     print(json.dumps(line), flush=True)
     dev.close()
 
@@ -833,6 +870,9 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    if args.dump_outputs and (args.gpus > 1 or os.environ.get("RAMA_FORCE_PIPELINE")):
+        print("bench.py: --dump-outputs is implemented for the single-GPU path (--gpus 1) only", file=sys.stderr)
+        raise SystemExit(2)
     if args.gpus > 1 and not os.environ.get("RAMA_BENCH_SKIP_DEVICE_CHECK"):
         # N ranks need N visible devices: say so HERE, before anything touches a GPU (counting devices does not initialise one), instead of letting the ranks
         # fail one by one inside RCCL's bootstrap

@@ -1,6 +1,7 @@
 """Host-side string code: the C++ tokenizer (rama_amd/csrc/host/tokenizer.hpp)
 against the Python restatement of bpe.rs (oracle/tokenizer.py) on synthetic vocabularies (CPU),
 and -- marked gpu -- the engine CLI's printed text against oracle generate() + decode."""
+import gzip
 import os
 import random
 import struct
@@ -17,7 +18,7 @@ from tests.helpers import GOLDEN, load_case
 REPO = Path(__file__).resolve().parent.parent
 TOOL = REPO / "rama_amd" / "bin" / "tokenizer_tool"
 ENGINE = REPO / "rama_amd" / "bin" / "engine"
-REF_TOK = Path("/root/reference/engine/tokenizer.bin")
+REF_TOK_GZ = GOLDEN / "tokenizer.bin.gz"      # the reference's 32 000-entry tokenizer.bin, gzipped
 
 
 def write_tokenizer(path, entries):
@@ -108,11 +109,12 @@ def test_trim_is_unicode_white_space(tmp_path):
     assert run_tool(p, len(entries), "encode", "\u3000\u00a0").returncode == 101          # trims to nothing
 
 
-@pytest.mark.skipif(not REF_TOK.exists(), reason="reference tokenizer.bin only exists in the build container")
-def test_reference_tokenizer_prompt_ids():
+def test_reference_tokenizer_prompt_ids(tmp_path):
     """'once upon a time' -> [10646, 2501, 263, 931] (no sentencepiece dummy prefix)"""
-    assert run_tool(REF_TOK, 32000, "encode", "once upon a time").stdout.split() == ["10646", "2501", "263", "931"]
-    assert Tokenizer(REF_TOK, 32000).encode("once upon a time") == [10646, 2501, 263, 931]
+    tok = tmp_path / "tokenizer.bin"
+    tok.write_bytes(gzip.decompress(REF_TOK_GZ.read_bytes()))
+    assert run_tool(tok, 32000, "encode", "once upon a time").stdout.split() == ["10646", "2501", "263", "931"]
+    assert Tokenizer(tok, 32000).encode("once upon a time") == [10646, 2501, 263, 931]
 
 
 # ------------------------------------------------------------------ the CLI on the GPU
