@@ -219,6 +219,22 @@ int  rama_decode_batch_tokens(rama_ctx *ctx, int32_t *out_host, int max_per_seq,
 /* tokens `from`.. that sequence `seq` of the chained batch has produced SO FAR, without touching the stream (a host-visible
  * ring per sequence, as rama_decode_stream_poll): a server hands each request its tokens as they appear. */
 int  rama_decode_batch_stream_poll(rama_ctx *ctx, int seq, int from, int32_t *out_tokens_host, int max_tokens, int *n_ready);
+/* The chained batch with sampling and forced prompts (the server's requests: each samples by default and has its own prompt).
+ * Sequence i runs generate()'s loop (mod.rs:169-206) from its own (token, position):
+ *   next = pos < n_forced ? forced[pos] : Device::sample(logits, temperature, topp, u)
+ * -- the absolute-position rule of rama_decode_begin, so sequences that all start at (1, 0) with their prompts give exactly the
+ * reference's generations; temperature 0 is the argmax, a sample with no kept entry gives token 0 as in rama_decode_steps.  Every
+ * step ends in the batched top-p sampler (rama_sample_topp_batch_dev); forced and temperature-0 rows skip its sorting work.
+ * The records and forced lists are copied to the device here; rama_decode_batch_steps / _tokens / _stream_poll drive the chain
+ * as they drive rama_decode_batch_begin's, and a step in graph mode is still one hipGraph replay.  Same restrictions as
+ * rama_decode_batch_begin (fast mode: RAMA_EUNSUP otherwise; 1..128 sequences), and vocab_size <= 32768 (RAMA_EUNSUP).
+ * RAMA_EINVAL, the previous chain untouched, for temperature < 0, topp outside [0, 1], u outside [0, 1), n_forced < 0 or a
+ * forced token outside the vocabulary. */
+typedef struct { float temperature, topp, u; const int32_t *forced; int32_t n_forced; } rama_seq_sampling;
+int  rama_decode_batch_begin_sampled(rama_ctx *ctx, const rama_config *cfg, const rama_weights *w,
+                                     const rama_run_state *states, const int32_t *tokens_host,
+                                     const int32_t *positions_host, int n_seq, int max_steps,
+                                     const rama_seq_sampling *per_seq);
 
 /* Layer-pipeline stage variants (no reference counterpart: the reference is single-device).
  * The token id is read from / written to DEVICE memory, so a stage boundary is one RCCL
@@ -301,6 +317,14 @@ int  rama_generate_greedy(rama_ctx *ctx, const rama_config *cfg, const rama_weig
  * -1 when no probability exceeds the cutoff (the reference's index arithmetic underflows there). */
 int  rama_sample_topp_dev(rama_ctx *ctx, const float *logits, size_t n, float temperature, float topp,
                           float u, int32_t *result_dev);
+/* rama_sample_topp_dev for n_rows (1..128) rows at once: row r is logits + r * ld (ld >= n floats) with its own
+ * temperature_host[r], topp_host[r], u_host[r]; result_dev[r] is bit for bit what rama_sample_topp_dev gives for that row
+ * (-1: nothing kept).  Rows are sampled side by side in the same launches (one workgroup per row for the running sums; n >
+ * 32768: the single-row launches row by row).  Scratch is sized on the first call for the largest (rows, n) seen.
+ * RAMA_EINVAL for temperature < 0, topp outside [0, 1] or u outside [0, 1). */
+int  rama_sample_topp_batch_dev(rama_ctx *ctx, const float *logits, size_t ld, size_t n, int n_rows,
+                                const float *temperature_host, const float *topp_host, const float *u_host,
+                                int32_t *result_dev);
 /* Sampler of the chained decode loop (rama_decode_steps): temperature 0 (default) = argmax. */
 int  rama_decode_sampler(rama_ctx *ctx, float temperature, float topp, float u);
 /* generate() (mod.rs:169-206) for any temperature, chained on the device: no per-token host round

@@ -30,6 +30,11 @@ pub struct rama_run_state {
     pub q: *mut f32, pub k: *mut f32, pub v: *mut f32, pub att: *mut f32, pub logits: *mut f32,
     pub key_cache: *mut f32, pub value_cache: *mut f32,
 }
+/// one sequence's sampler and forced prompt of the sampled chained batch (rama_decode_batch_begin_sampled)
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct rama_seq_sampling {
+    pub temperature: f32, pub topp: f32, pub u: f32, pub forced: *const i32, pub n_forced: i32,
+}
 
 extern "C" {
     pub fn rama_ctx_create(device: c_int, stream: *mut c_void, out: *mut *mut rama_ctx) -> c_int;
@@ -72,6 +77,9 @@ extern "C" {
                              n_seq: c_int) -> c_int;
     pub fn rama_decode_batch_begin(ctx: *mut rama_ctx, cfg: *const rama_config, w: *const rama_weights, states: *const rama_run_state,
                                    tokens_host: *const i32, positions_host: *const i32, n_seq: c_int, max_steps: c_int) -> c_int;
+    pub fn rama_decode_batch_begin_sampled(ctx: *mut rama_ctx, cfg: *const rama_config, w: *const rama_weights, states: *const rama_run_state,
+                                           tokens_host: *const i32, positions_host: *const i32, n_seq: c_int, max_steps: c_int,
+                                           per_seq: *const rama_seq_sampling) -> c_int;
     pub fn rama_decode_batch_steps(ctx: *mut rama_ctx, n_steps: c_int) -> c_int;
     pub fn rama_decode_batch_tokens(ctx: *mut rama_ctx, out_host: *mut i32, max_per_seq: c_int, n_per_seq: *mut c_int) -> c_int;
     pub fn rama_generate(ctx: *mut rama_ctx, cfg: *const rama_config, w: *const rama_weights,
@@ -123,6 +131,8 @@ extern "C" {
     pub fn rama_argmax_dev(ctx: *mut rama_ctx, logits: *const f32, n: usize, result_dev: *mut i32) -> c_int;
     pub fn rama_sample_topp_dev(ctx: *mut rama_ctx, logits: *const f32, n: usize, temperature: f32, topp: f32, u: f32,
                                 result_dev: *mut i32) -> c_int;
+    pub fn rama_sample_topp_batch_dev(ctx: *mut rama_ctx, logits: *const f32, ld: usize, n: usize, n_rows: c_int, temperature_host: *const f32,
+                                      topp_host: *const f32, u_host: *const f32, result_dev: *mut i32) -> c_int;
     pub fn rama_generate_greedy(ctx: *mut rama_ctx, cfg: *const rama_config, w: *const rama_weights, s: *mut rama_run_state,
                                 prompt_tokens_host: *const i32, n_prompt: c_int, steps: c_int, out_tokens_host: *mut i32) -> c_int;
     pub fn rama_decode_begin(ctx: *mut rama_ctx, token: c_int, pos: c_int, forced_tokens_host: *const i32, n_forced: c_int) -> c_int;

@@ -47,6 +47,11 @@ class rama_stage(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("layer_begin", "layer_end", "do_embed", "do_cls")]
 
 
+class rama_seq_sampling(C.Structure):
+    """one sequence's sampler and forced prompt of the sampled chained batch (rama_decode_batch_begin_sampled)"""
+    _fields_ = [("temperature", C.c_float), ("topp", C.c_float), ("u", C.c_float), ("forced", C.POINTER(C.c_int32)), ("n_forced", C.c_int32)]
+
+
 class rama_pipe_plan(C.Structure):
     _fields_ = [("n_seq", C.c_int32), ("n_pos", C.c_int32), ("wrap", C.c_int32), ("prompt", C.POINTER(C.c_int32)), ("n_prompt", C.c_int32),
                 ("temperature", C.c_float), ("topp", C.c_float), ("u", C.c_float), ("out_tokens_dev", C.c_void_p)]
@@ -100,6 +105,8 @@ SIGNATURES = {
     "rama_prefill": (_int, [_vp, _cfgp, _wp, _sp, i32p, _int, _int]),
     "rama_decode_batch": (_int, [_vp, _cfgp, _wp, _sp, i32p, i32p, _int]),
     "rama_decode_batch_begin": (_int, [_vp, _cfgp, _wp, _sp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _int, _int]),
+    "rama_decode_batch_begin_sampled": (_int, [_vp, _cfgp, _wp, _sp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _int, _int,
+                                                C.POINTER(rama_seq_sampling)]),
     "rama_decode_batch_steps": (_int, [_vp, _int]),
     "rama_decode_batch_tokens": (_int, [_vp, C.POINTER(C.c_int32), _int, C.POINTER(_int)]),
     "rama_forward_stage_devtok": (_int, [_vp, _cfgp, _wp, _sp, _vp, _int, _stp]),
@@ -107,6 +114,7 @@ SIGNATURES = {
     "rama_generate_greedy": (_int, [_vp, _cfgp, _wp, _sp, i32p, _int, _int, i32p]),
     "rama_generate": (_int, [_vp, _cfgp, _wp, _sp, i32p, _int, _int, C.c_float, C.c_float, C.c_float, i32p]),
     "rama_sample_topp_dev": (_int, [_vp, _vp, _sz, C.c_float, C.c_float, C.c_float, _vp]),
+    "rama_sample_topp_batch_dev": (_int, [_vp, _vp, _sz, _sz, _int, f32p, f32p, f32p, _vp]),
     "rama_decode_sampler": (_int, [_vp, C.c_float, C.c_float, C.c_float]),
     "rama_decode_begin": (_int, [_vp, _int, _int, i32p, _int]),
     "rama_decode_steps": (_int, [_vp, _cfgp, _wp, _sp, _int]),

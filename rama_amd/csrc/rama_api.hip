@@ -154,6 +154,15 @@ struct rama_ctx {
     int tune_attn_u = 8;                    // cache rows per lane and round in the split-T attention (8 | 16; 16 measured no faster)
     int tune_topp_sort = 1;                 // 0: ranks through global memory (topp_rank_global_kernel) for every vocabulary size
     int tune_topp_keep_sums = 0;            // 1: the scan sampler also writes its running sums to global memory (tests)
+    // the batched top-p sampler (rama_sample_topp_batch_dev, the sampled chained batch; topp_sort.hpp ROWS kernels): one scratch slice
+    // per row, sized by the op's first call or by rama_decode_batch_begin_sampled -- never inside a step, which may be captured
+    struct ToppBatchScratch {
+        int rows = 0; size_t rstride = 0;  // rows x rstride entries per slice array
+        float* keys = nullptr; int* vals = nullptr; float* bp = nullptr; int* bi = nullptr;
+        unsigned long long* rk = nullptr; unsigned long long* bm = nullptr;
+        int* bcount = nullptr; ToppStats* stats = nullptr; int* m = nullptr;     // rows x kToppRowBlocks, rows x kToppRowBlocks, rows
+        ToppRow* rows_dev = nullptr;       // [kMfMaxTok] rama_sample_topp_batch_dev's (T, topp, u) per row, written by a launch
+    } tb;
     int tune_split_pos = -1;               // attention runs split-T (+ combine launch) from this position on; -1 = by model size
     int tune_resid_r2 = 2;                 // Wo / W2 under geometry 3: 0 = 4-row workgroups, 1 = 2 rows x 8 waves (+0.45 %),
                                            // 2 = additionally 16 waves for rows wider than 8192 floats (W2: +1.15 % more), 3 = 16 waves x 4 chunks
@@ -236,6 +245,10 @@ struct rama_ctx {
         int* ring_dev = nullptr;
         rama_config cfg{}; rama_weights w{};
         hipGraphExec_t exec = nullptr; hipGraph_t graph = nullptr; int graph_bucket = -1;
+        // rama_decode_batch_begin_sampled: a step ends in the batched top-p sampler instead of argmax_batch_kernel
+        bool sampled = false;
+        ToppRow* rows = nullptr;           // [kMfMaxTok] every sequence's (T, topp, u, forced list)
+        int* forced = nullptr; size_t forced_cap = 0;      // the forced lists, one after the other
     } bc;
 };
 
@@ -383,6 +396,9 @@ int rama_ctx_destroy(rama_ctx* c) {
     hipFree(c->topp_bp); hipFree(c->topp_bi); hipFree(c->topp_bcount); hipFree(c->topp_racc);
     hipFree(c->topp_rk); hipFree(c->topp_bm); hipFree(c->topp_approx); hipFree(c->topp_dist); hipFree(c->topp_stats);
     hipFree(c->bc.toks); hipFree(c->bc.seqs); hipFree(c->bc.out); if (c->bc.ring) hipHostFree(c->bc.ring);
+    hipFree(c->bc.rows); hipFree(c->bc.forced);
+    hipFree(c->tb.keys); hipFree(c->tb.vals); hipFree(c->tb.bp); hipFree(c->tb.bi); hipFree(c->tb.rk); hipFree(c->tb.bm);
+    hipFree(c->tb.bcount); hipFree(c->tb.stats); hipFree(c->tb.m); hipFree(c->tb.rows_dev);
     hipHostFree(c->pinned_int); hipHostFree(c->pinned_tok);
     hipEventDestroy(c->t0); hipEventDestroy(c->t1);
     if (c->own_stream) hipStreamDestroy(c->stream);
@@ -1886,6 +1902,106 @@ int rama_sample_topp_dev(rama_ctx* c, const float* logits, size_t n, float tempe
     return enqueue_sample(c, ap, temperature, topp, u);
 }
 
+// ---- the batched top-p sampler: many rows per launch (topp_sort.hpp ROWS kernels), the parallelism from the rows -- no waits between
+// workgroups (topp_pick_dist_kernel's hand-offs need all its workgroups resident: not at 128 rows), the pick one workgroup per row
+static bool topp_params_ok(float temperature, float topp, float u) {
+    return temperature >= 0.0f && topp >= 0.0f && topp <= 1.0f && u >= 0.0f && u < 1.0f;      // (false for NaN)
+}
+// slices for `rows` rows of n <= 32768 logits; called outside any stream capture
+static int ensure_topp_batch(rama_ctx* c, int rows, int n) {
+    auto& t = c->tb;
+    size_t rs = ((size_t)n + kToppBlock - 1) / kToppBlock * kToppBlock;      // >= n and >= the blocks' slots of either block size
+    if (rows <= t.rows && rs <= t.rstride) return 0;
+    if (set_device(c)) return 1;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    drop_graph(c);                                                 // a captured chained step holds the old slices
+    rows = std::max(rows, t.rows); rs = std::max(rs, t.rstride);
+    for (void** q : {(void**)&t.keys, (void**)&t.vals, (void**)&t.bp, (void**)&t.bi, (void**)&t.rk, (void**)&t.bm, (void**)&t.bcount, (void**)&t.stats, (void**)&t.m}) {
+        hipFree(*q); *q = nullptr;
+    }
+    t.rows = 0; t.rstride = 0;
+    const size_t e = (size_t)rows * rs;
+    HIPCHK(hipMalloc(&t.keys, sizeof(float) * e)); HIPCHK(hipMalloc(&t.vals, sizeof(int) * e));
+    HIPCHK(hipMalloc(&t.bp, sizeof(float) * e)); HIPCHK(hipMalloc(&t.bi, sizeof(int) * e));
+    HIPCHK(hipMalloc(&t.rk, sizeof(unsigned long long) * e)); HIPCHK(hipMalloc(&t.bm, sizeof(unsigned long long) * e));
+    HIPCHK(hipMalloc(&t.bcount, sizeof(int) * rows * kToppRowBlocks)); HIPCHK(hipMalloc(&t.stats, sizeof(ToppStats) * rows * kToppRowBlocks));
+    HIPCHK(hipMalloc(&t.m, sizeof(int) * rows));
+    if (!t.rows_dev) HIPCHK(hipMalloc(&t.rows_dev, sizeof(ToppRow) * kMfMaxTok));
+    t.rows = rows; t.rstride = rs;
+    return 0;
+}
+// every row's (T, topp, u) by value: the launch takes a copy, so no host staging buffer has to outlive the call
+struct ToppRowsArg { float temperature[kMfMaxTok], topp[kMfMaxTok], u[kMfMaxTok]; };
+__global__ void topp_rows_kernel(ToppRowsArg a, ToppRow* rows, int n_rows) {
+    const int r = threadIdx.x;
+    if (r < n_rows) rows[r] = ToppRow{a.temperature[r], a.topp[r], a.u[r], 0, nullptr};
+}
+// the sampler over n_rows rows of n <= 32768 logits (row r at logits + r ld); fin says where the picks go.  The statistics, the block
+// sorts and the ranking are the single-row sampler's launches for the same n (enqueue_sample_launches at the default tuning), so every
+// sampled row gets its bits; the running sums are topp_pick_scan_kernel's, one workgroup per row.
+static int enqueue_topp_batch(rama_ctx* c, const ToppRow* rows, int n_rows, const float* logits, size_t ld, int n, ToppBatchParams fin) {
+    auto& t = c->tb;
+    REQUIRE(n > 1 && n <= kToppBlock * kToppMaxBlocks && n_rows <= t.rows && (size_t)n <= t.rstride, RAMA_EINVAL, "top-p batch sampler: scratch not prepared");
+    ToppSortParams sp{};
+    sp.logits = logits; sp.n = n;
+    sp.bp = t.bp; sp.bi = t.bi; sp.bcount = t.bcount; sp.keys = t.keys; sp.vals = t.vals; sp.m = t.m;
+    sp.rows = rows; sp.seqs = fin.seqs; sp.ld = ld; sp.rstride = t.rstride;
+    if (n <= kToppBlock) {                                         // one block: its own statistics and sort, the in-LDS ranking
+        sp.nblk = 1;
+        hipLaunchKernelGGL((topp_blocksort_kernel<false, true>), dim3(1, 1, n_rows), dim3(1024), 0, c->stream, sp);
+        LAUNCHCHK();
+        hipLaunchKernelGGL((topp_rank_kernel<kToppMaxBlocks, true>), dim3(kToppBlock / kRankThreads, 1, n_rows), dim3(kRankThreads), 0, c->stream, sp);
+        LAUNCHCHK();
+    } else {                                                       // the small-block path: statistics per 1024 logits, 1024-entry sorts, pairs, scatter
+        // (pair width OB = 2 as the single-row path: 4 and 8 -- fewer atomics, wider workgroups -- measured 3 % and 44 % slower at 128 rows)
+        constexpr int BS = 1024, OB = 2;
+        sp.rk = t.rk; sp.bm = t.bm;
+        sp.nblk = (n + BS - 1) / BS;
+        const int nstat = (n + 1023) / 1024;
+        hipLaunchKernelGGL(topp_stats_kernel<true>, dim3(nstat, 1, n_rows), dim3(1024), 0, c->stream, sp, t.stats);
+        LAUNCHCHK();
+        hipLaunchKernelGGL((topp_blocksort_bs_kernel<BS, true>), dim3(sp.nblk, 1, n_rows), dim3(BS), 0, c->stream, sp, (const ToppStats*)t.stats, nstat);
+        LAUNCHCHK();
+        hipLaunchKernelGGL((topp_rank_pairs_bs_kernel<BS, OB, true>), dim3(sp.nblk, (sp.nblk + OB - 1) / OB, n_rows), dim3(BS / 2), 0, c->stream, sp);
+        LAUNCHCHK();
+        hipLaunchKernelGGL((topp_rank_scatter_bs_kernel<BS, true>), dim3((sp.nblk * BS + 1023) / 1024, 1, n_rows), dim3(1024), 0, c->stream, sp);
+        LAUNCHCHK();
+    }
+    fin.rows = rows; fin.logits = logits; fin.ld = ld; fin.n = n;
+    fin.keys = t.keys; fin.vals = t.vals; fin.m = t.m; fin.rstride = t.rstride;
+    hipLaunchKernelGGL(topp_pick_batch_kernel, dim3(n_rows), dim3(1024), 0, c->stream, fin);
+    LAUNCHCHK();
+    return 0;
+}
+
+int rama_sample_topp_batch_dev(rama_ctx* c, const float* logits, size_t ld, size_t n, int n_rows, const float* temperature_host,
+                               const float* topp_host, const float* u_host, int32_t* result_dev) {
+    RAMA_ENTER(c);
+    REQUIRE(c && logits && temperature_host && topp_host && u_host && result_dev, RAMA_EINVAL, "sample_topp_batch_dev: NULL argument");
+    REQUIRE(n > 1 && n < (1u << 30) && ld >= n && n_rows >= 1 && n_rows <= kMfMaxTok, RAMA_EINVAL, "sample_topp_batch_dev: 1..128 rows of n > 1 logits, ld >= n");
+    for (int r = 0; r < n_rows; r++)
+        REQUIRE(topp_params_ok(temperature_host[r], topp_host[r], u_host[r]), RAMA_EINVAL, "sample_topp_batch_dev: temperature >= 0, topp in [0,1], u in [0,1)");
+    if (set_device(c)) return 1;
+    if (n > (size_t)kToppBlock * kToppMaxBlocks) {
+        // beyond one workgroup's LDS the single-row sampler ranks through global memory and picks with a staged ripple: row by row
+        for (int r = 0; r < n_rows; r++) {
+            if (temperature_host[r] != 0.0f) { int rc = ensure_topp_scratch(c, (int)n); if (rc) return rc; }
+            ArgmaxParams ap{};
+            ap.logits = logits + (size_t)r * ld; ap.n = (int)n; ap.result = (int*)result_dev + r;
+            int rc = enqueue_sample_launches(c, ap, temperature_host[r], topp_host[r], u_host[r]); if (rc) return rc;
+        }
+        return 0;
+    }
+    int rc = ensure_topp_batch(c, n_rows, (int)n); if (rc) return rc;
+    ToppRowsArg a{};
+    for (int r = 0; r < n_rows; r++) { a.temperature[r] = temperature_host[r]; a.topp[r] = topp_host[r]; a.u[r] = u_host[r]; }
+    hipLaunchKernelGGL(topp_rows_kernel, dim3(1), dim3(kMfMaxTok), 0, c->stream, a, c->tb.rows_dev, n_rows);
+    LAUNCHCHK();
+    ToppBatchParams fin{};
+    fin.result = (int*)result_dev;
+    return enqueue_topp_batch(c, c->tb.rows_dev, n_rows, logits, ld, (int)n, fin);
+}
+
 int rama_decode_sampler(rama_ctx* c, float temperature, float topp, float u) {
     RAMA_ENTER(c);
     REQUIRE(c, RAMA_EINVAL, "ctx is NULL");
@@ -2454,9 +2570,10 @@ __global__ __launch_bounds__(1024) void argmax_batch_kernel(BatchArgmaxParams p)
     }
 }
 
-int rama_decode_batch_begin(rama_ctx* c, const rama_config* cfg, const rama_weights* w, const rama_run_state* states,
-                            const int32_t* tokens_host, const int32_t* pos_host, int n_seq, int max_steps) {
-    RAMA_ENTER(c);
+// per_seq == nullptr: the greedy chain (argmax_batch_kernel); else every step ends in the batched top-p sampler.  Every argument is
+// checked before anything of the previous chain is touched.
+static int batch_begin(rama_ctx* c, const rama_config* cfg, const rama_weights* w, const rama_run_state* states,
+                       const int32_t* tokens_host, const int32_t* pos_host, int n_seq, int max_steps, const rama_seq_sampling* per_seq) {
     REQUIRE(c && states && tokens_host && pos_host, RAMA_EINVAL, "decode_batch_begin: NULL argument");
     REQUIRE(n_seq >= 1 && n_seq <= kMfMaxTok, RAMA_EINVAL, "decode_batch_begin: 1..128 sequences");
     REQUIRE(max_steps >= 1 && max_steps <= (1 << 20), RAMA_EINVAL, "decode_batch_begin: bad max_steps");
@@ -2475,6 +2592,18 @@ int rama_decode_batch_begin(rama_ctx* c, const rama_config* cfg, const rama_weig
         REQUIRE(pos_host[i] >= 0 && pos_host[i] + max_steps <= cfg->seq_len, RAMA_EINVAL, "decode_batch_begin: position + max_steps beyond seq_len");
         for (int j = 0; j < i; j++) REQUIRE(states[j].key_cache != states[i].key_cache, RAMA_EINVAL, "decode_batch_begin: two sequences share a run state");
         pmax = std::max(pmax, pos_host[i]);
+    }
+    size_t n_forced_all = 0;
+    if (per_seq) {
+        REQUIRE(cfg->vocab_size <= kToppBlock * kToppMaxBlocks, RAMA_EUNSUP, "decode_batch_begin_sampled: vocab_size above 32768");
+        for (int i = 0; i < n_seq; i++) {
+            const rama_seq_sampling& q = per_seq[i];
+            REQUIRE(topp_params_ok(q.temperature, q.topp, q.u), RAMA_EINVAL, "decode_batch_begin_sampled: temperature >= 0, topp in [0,1], u in [0,1)");
+            REQUIRE(q.n_forced >= 0 && (q.n_forced == 0 || q.forced), RAMA_EINVAL, "decode_batch_begin_sampled: bad forced list");
+            for (int k = 0; k < q.n_forced; k++)
+                REQUIRE(q.forced[k] >= 0 && q.forced[k] < cfg->vocab_size, RAMA_EINVAL, "decode_batch_begin_sampled: forced token outside the vocabulary");
+            n_forced_all += (size_t)q.n_forced;
+        }
     }
     HIPCHK(hipStreamSynchronize(c->stream));
     auto& bc = c->bc;
@@ -2496,11 +2625,60 @@ int rama_decode_batch_begin(rama_ctx* c, const rama_config* cfg, const rama_weig
     }
     HIPCHK(hipMemcpyAsync(bc.toks, c->pinned_tok, sizeof(int) * n_seq, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(bc.seqs, slots, sizeof(SeqSlot) * n_seq, hipMemcpyHostToDevice, c->stream));
+    bc.sampled = per_seq != nullptr;
+    if (per_seq) {
+        // the sampling records and the forced lists go to the device once; a step reads them there
+        if (!bc.rows) HIPCHK(hipMalloc(&bc.rows, sizeof(ToppRow) * kMfMaxTok));
+        if (bc.forced_cap < n_forced_all) {
+            hipFree(bc.forced); bc.forced = nullptr; bc.forced_cap = 0;
+            HIPCHK(hipMalloc(&bc.forced, sizeof(int) * n_forced_all));
+            bc.forced_cap = n_forced_all;
+        }
+        ToppRow rows[kMfMaxTok];
+        size_t at = 0;
+        for (int i = 0; i < n_seq; i++) {
+            const rama_seq_sampling& q = per_seq[i];
+            rows[i] = ToppRow{q.temperature, q.topp, q.u, q.n_forced, q.n_forced ? bc.forced + at : nullptr};
+            if (q.n_forced) HIPCHK(hipMemcpy(bc.forced + at, q.forced, sizeof(int) * q.n_forced, hipMemcpyHostToDevice));
+            at += (size_t)q.n_forced;
+        }
+        HIPCHK(hipMemcpy(bc.rows, rows, sizeof(ToppRow) * n_seq, hipMemcpyHostToDevice));
+        rc = ensure_topp_batch(c, n_seq, cfg->vocab_size); if (rc) return rc;
+    }
     HIPCHK(hipStreamSynchronize(c->stream));
     bc.n_seq = n_seq; bc.pos_max = pmax; bc.steps_done = 0; bc.cfg = *cfg; bc.w = *w;
     if (c->tune_tiled) { rc = rama_internal_model_ensure(c, w, 2); if (rc) return rc; }
     BatchScratch b{};
     return ensure_batch_scratch(c, cfg, true, &b);
+}
+
+int rama_decode_batch_begin(rama_ctx* c, const rama_config* cfg, const rama_weights* w, const rama_run_state* states,
+                            const int32_t* tokens_host, const int32_t* pos_host, int n_seq, int max_steps) {
+    RAMA_ENTER(c);
+    return batch_begin(c, cfg, w, states, tokens_host, pos_host, n_seq, max_steps, nullptr);
+}
+
+int rama_decode_batch_begin_sampled(rama_ctx* c, const rama_config* cfg, const rama_weights* w, const rama_run_state* states,
+                                    const int32_t* tokens_host, const int32_t* pos_host, int n_seq, int max_steps,
+                                    const rama_seq_sampling* per_seq) {
+    RAMA_ENTER(c);
+    REQUIRE(per_seq, RAMA_EINVAL, "decode_batch_begin_sampled: per_seq is NULL");
+    return batch_begin(c, cfg, w, states, tokens_host, pos_host, n_seq, max_steps, per_seq);
+}
+
+// what ends a chained batch step: one argmax per sequence, or the batched top-p sampler (forced / temperature-0 rows included)
+static int enqueue_batch_finish(rama_ctx* c, const BatchScratch& b) {
+    auto& bc = c->bc;
+    const int V = bc.cfg.vocab_size;
+    if (!bc.sampled) {
+        BatchArgmaxParams ap{b.LG, V, bc.toks, bc.seqs, bc.out, bc.out_cap, bc.ring_dev};
+        hipLaunchKernelGGL(argmax_batch_kernel, dim3(bc.n_seq), dim3(1024), 0, c->stream, ap);
+        LAUNCHCHK();
+        return 0;
+    }
+    ToppBatchParams fin{};
+    fin.toks = bc.toks; fin.seqs = bc.seqs; fin.out = bc.out; fin.out_cap = bc.out_cap; fin.ring = bc.ring_dev;
+    return enqueue_topp_batch(c, bc.rows, bc.n_seq, b.LG, (size_t)V, V, fin);
 }
 
 int rama_decode_batch_steps(rama_ctx* c, int n_steps) {
@@ -2517,18 +2695,16 @@ int rama_decode_batch_steps(rama_ctx* c, int n_steps) {
     for (int i = 0; i < n_steps; i++) {
         // the score buffers are sized by the longest context: one graph per bucket of 256 timesteps
         const int tmax = bc.pos_max + 1, bucket = (tmax + 255) / 256;
-        BatchArgmaxParams ap{b.LG, cfg->vocab_size, bc.toks, bc.seqs, bc.out, bc.out_cap, bc.ring_dev};
         if (!c->graph_mode) {
             rc = enqueue_batch_pass(c, cfg, &bc.w, b, bc.n_seq, bucket * 256); if (rc) return rc;
-            hipLaunchKernelGGL(argmax_batch_kernel, dim3(bc.n_seq), dim3(1024), 0, c->stream, ap);
-            LAUNCHCHK();
+            rc = enqueue_batch_finish(c, b); if (rc) return rc;
         } else {
             if (bc.graph_bucket != bucket) {
                 if (bc.exec) { hipGraphExecDestroy(bc.exec); bc.exec = nullptr; }
                 if (bc.graph) { hipGraphDestroy(bc.graph); bc.graph = nullptr; }
                 HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
                 rc = enqueue_batch_pass(c, cfg, &bc.w, b, bc.n_seq, bucket * 256);
-                if (!rc) { hipLaunchKernelGGL(argmax_batch_kernel, dim3(bc.n_seq), dim3(1024), 0, c->stream, ap); }
+                if (!rc) rc = enqueue_batch_finish(c, b);
                 const hipError_t e = hipStreamEndCapture(c->stream, &bc.graph);
                 if (rc) return rc;
                 HIPCHK(e);

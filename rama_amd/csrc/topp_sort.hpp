@@ -33,6 +33,7 @@ __device__ unsigned long long g_topp_stamps[64];
 constexpr int kToppBlock = 2048;        // logits per sorting workgroup
 constexpr int kToppMaxBlocks = 16;      // => n <= 32768 on the LDS-rank path; larger vocabularies rank through global memory (topp_rank_global_kernel)
 
+struct ToppRow;
 struct ToppSortParams {
     const float* logits; int n;
     float temperature, topp;
@@ -48,7 +49,32 @@ struct ToppSortParams {
     unsigned long long* bm;             // [nblk * BS] mass of a block's entries up to and including each one (the block sort's output)
     float* approx;                      // [n] out: the mass in front of every entry of the whole order (what topp_pick_dist_kernel predicts binades from)
     unsigned* epoch;                    // the pick launch's hand-off tag (topp_pick.hpp), advanced by the scatter launch
+    // the batched sampler (ROWS = true instances below): see topp_row_view
+    const ToppRow* rows; const SeqSlot* seqs; size_t ld, rstride;
 };
+// The batched sampler (rama_sample_topp_batch_dev; the sampled chained batch).  The kernels below instantiated with ROWS = true
+// run row blockIdx.z of a launch: its logits at row * ld, its scratch slices (bp bi rk bm keys vals) at row * rstride, its
+// bcount / statistics at row * kToppRowBlocks, its m at row, its (T, topp) from rows[row].  Nothing else changes, so a row
+// gets the bits the single-row launches give.  A row at temperature 0 -- or, in the chain (seqs set), on a forced step:
+// position < n_forced -- leaves every launch at once; topp_pick_batch_kernel takes its argmax or forced token instead.
+struct ToppRow { float temperature, topp, u; int n_forced; const int* forced; };
+constexpr int kToppRowBlocks = 64;      // >= the blocks of 32768 logits at the smallest block size (1024)
+__device__ __forceinline__ bool topp_row_sampled(const ToppRow& r, const SeqSlot* seqs, int row) {
+    return r.temperature != 0.0f && !(seqs && seqs[row].pos < r.n_forced);
+}
+// false: the row takes no part in this launch (uniform over the workgroup)
+__device__ __forceinline__ bool topp_row_view(ToppSortParams& p) {
+    const int row = blockIdx.z;
+    const ToppRow r = p.rows[row];
+    if (!topp_row_sampled(r, p.seqs, row)) return false;
+    const size_t o = (size_t)row * p.rstride;
+    p.logits += (size_t)row * p.ld; p.temperature = r.temperature; p.topp = r.topp;
+    p.bp += o; p.bi += o; p.keys += o; p.vals += o;
+    if (p.rk) p.rk += o;
+    if (p.bm) p.bm += o;
+    p.bcount += (size_t)row * kToppRowBlocks; p.m += row;
+    return true;
+}
 // Probability mass as a 48-bit fixed-point number, unit 2^-47, truncated: integer sums are exact in any order, so the mass in front of an
 // entry -- gathered from 32 blocks by atomics -- is the same number however the adds arrive, and differs from the real-number sum by less
 // than 2^-47 per entry.  p <= 1 (the softmax sum contains the maximum's exp(0) = 1), so a sum over the whole list stays below 2^48.
@@ -80,11 +106,12 @@ __device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v,
 
 // BIG: n > 32768 -- the softmax statistics loop over the logits instead of holding them in registers (same
 // per-thread order: ascending i = tid + 1024 k, then the wave tree, then the 16-wave tree)
-template <bool BIG>
+template <bool BIG, bool ROWS = false>
 __global__ __launch_bounds__(1024) void topp_blocksort_kernel(ToppSortParams p) {
     __shared__ float s_r[16];
     __shared__ unsigned long long s_k[2][kToppBlock];
     __shared__ int s_n;
+    if constexpr (ROWS) { if (!topp_row_view(p)) return; }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const bool scale = p.temperature < 1.0f;                       // cpu.rs:170-172: T > 1 has no effect
     TOPP_STAMP(0);
@@ -232,8 +259,10 @@ __device__ __forceinline__ unsigned lane_xor_u32(unsigned v) {
 //                              order in every workgroup: the same bits), keeps and sorts its slice -- 55 stages, 45 of them inside a
 //                              wave by DPP moves / lane swaps -- and leaves the block's running mass
 struct ToppStats { float mx, sum; };
+template <bool ROWS = false>
 __global__ __launch_bounds__(1024) void topp_stats_kernel(ToppSortParams p, ToppStats* st) {
     __shared__ float s_r[16];
+    if constexpr (ROWS) { if (!topp_row_view(p)) return; st += (size_t)blockIdx.z * kToppRowBlocks; }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const bool scale = p.temperature < 1.0f;                       // cpu.rs:170-172: T > 1 has no effect
     const int i = blockIdx.x * 1024 + tid;
@@ -272,11 +301,12 @@ __device__ __forceinline__ void lane_stage(unsigned long long& A, bool desc) {
     const bool lower = (threadIdx.x & J) == 0;
     A = ((oa > A) == (lower == desc)) ? oa : A;
 }
-template <int BS>
+template <int BS, bool ROWS = false>
 __global__ __launch_bounds__(BS) void topp_blocksort_bs_kernel(ToppSortParams p, const ToppStats* st, int nstat) {
     __shared__ unsigned long long s_k[2][BS];
     __shared__ unsigned long long s_w[BS / 64];
     __shared__ int s_n;
+    if constexpr (ROWS) { if (!topp_row_view(p)) return; st += (size_t)blockIdx.z * kToppRowBlocks; }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const bool scale = p.temperature < 1.0f;
     if (tid == 0) s_n = 0;
@@ -338,11 +368,12 @@ __global__ __launch_bounds__(BS) void topp_blocksort_bs_kernel(ToppSortParams p,
 // the pair-wise ranking for blocks of BS entries: a workgroup of BS / 2 threads takes block b against OB other blocks at once.  Besides the
 // COUNT of block o's entries that precede an entry it looks up their MASS (the block's running mass at that place) and adds both to the
 // entry's accumulator in one 64-bit integer atomic: count << 48 | mass.
-template <int BS, int OB>
+template <int BS, int OB, bool ROWS = false>
 __global__ __launch_bounds__(BS / 2) void topp_rank_pairs_bs_kernel(ToppSortParams p) {
     constexpr int NT = BS / 2;
     __shared__ unsigned s_o[OB * BS];
     __shared__ unsigned long long s_m[OB * BS];
+    if constexpr (ROWS) { if (!topp_row_view(p)) return; }
     const int tid = threadIdx.x;
     const int b = blockIdx.x, o0 = blockIdx.y * OB;
     const int cb = p.bcount[b];
@@ -398,8 +429,9 @@ __global__ __launch_bounds__(BS / 2) void topp_rank_pairs_bs_kernel(ToppSortPara
     if (tid + NT < cb && a1) atomicAdd(&p.rk[(size_t)b * BS + NT + tid], a1);
 }
 // place = own place in the block + the count; the mass in front of the entry = the accumulated mass + the own block's mass before it
-template <int BS>
+template <int BS, bool ROWS = false>
 __global__ __launch_bounds__(1024) void topp_rank_scatter_bs_kernel(ToppSortParams p) {
+    if constexpr (ROWS) { if (!topp_row_view(p)) return; }
     const int g = blockIdx.x * 1024 + threadIdx.x;
     const int b = g / BS, s = g % BS;
     if (g == 0) {
@@ -427,9 +459,10 @@ __global__ __launch_bounds__(1024) void topp_rank_scatter_bs_kernel(ToppSortPara
 // Blocks are index ranges, so among equal probabilities an entry of an earlier block comes first:
 // the rank needs the other blocks' PROBABILITIES only -- all of them fit in one workgroup's LDS.
 constexpr int kRankThreads = 1024;
-template <int NB>
+template <int NB, bool ROWS = false>
 __global__ __launch_bounds__(kRankThreads) void topp_rank_kernel(ToppSortParams p) {
     __shared__ unsigned s_p[NB * kToppBlock];                      // 128 KB: every block's sorted probability bits
+    if constexpr (ROWS) { if (!topp_row_view(p)) return; }
     const int tid = threadIdx.x;
     TOPP_STAMP(8);
     const int g = blockIdx.x * kRankThreads + tid;
@@ -811,6 +844,74 @@ __device__ __forceinline__ void topp_pick_scan_body(const ToppParams& p, const A
 __global__ __launch_bounds__(1024) void topp_pick_scan_kernel(ToppParams p, ArgmaxParams fin) {
     __shared__ ScanShared sh;
     topp_pick_scan_body(p, fin, sh);
+}
+
+// ---- the batched sampler's last launch: one workgroup per row (no waits between workgroups).  A sampled row runs the pick of
+// topp_pick_scan_kernel on its slices; a row at temperature 0 takes the argmax (cpu.rs:163-167: ties to the LAST index); a forced
+// row (the chain) takes forced[pos].  Then either result[row] = the index (-1: nothing kept) or the chain's step ends as in
+// argmax_batch_kernel: token = next (-1 -> 0, as finish_step), pos += 1, out / ring.
+struct ToppBatchParams {
+    const ToppRow* rows;
+    const float* logits; size_t ld; int n;
+    float* keys; int* vals; int* m; size_t rstride;
+    int* result;                                  // rama_sample_topp_batch_dev: [rows] the picks
+    int* toks; SeqSlot* seqs; int* out; int out_cap; int* ring;      // the chained batch (seqs set)
+};
+__device__ __forceinline__ int topp_row_argmax(const float* lg, int n, float* s_v, int* s_i) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float bv = -INFINITY; int bi = -1;
+    for (int i0 = tid; i0 < n; i0 += 8 * 1024) {                  // ascending per thread: "replace unless strictly smaller" keeps the last maximum
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) v[u] = lg[min(i0 + u * 1024, n - 1)];
+#pragma unroll
+        for (int u = 0; u < 8; u++)
+            if (i0 + u * 1024 < n && !(bv > v[u])) { bv = v[u]; bi = i0 + u * 1024; }
+    }
+    const float wm = wave_max(bv);
+    const int wi = wave_max_i(bv == wm ? bi : -1);
+    if (lane == 0) { s_v[wave] = wm; s_i[wave] = wi; }
+    __syncthreads();
+    float v = s_v[0]; int idx = s_i[0];
+    for (int w = 1; w < 16; w++) {
+        const float ov = s_v[w]; const int oi = s_i[w];
+        if (oi >= 0 && (idx < 0 || ov > v || (ov == v && oi > idx))) { v = ov; idx = oi; }
+    }
+    return idx < 0 ? 0 : idx;
+}
+__global__ __launch_bounds__(1024) void topp_pick_batch_kernel(ToppBatchParams p) {
+    __shared__ ScanShared sh;
+    __shared__ float s_v[16];
+    __shared__ int s_i[16];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const ToppRow r = p.rows[row];
+    const int pos = p.seqs ? p.seqs[row].pos : 0;
+    int idx;
+    if (p.seqs && pos < r.n_forced) idx = r.forced[pos];          // uniform branches: the row's mode
+    else if (r.temperature == 0.0f) idx = topp_row_argmax(p.logits + (size_t)row * p.ld, p.n, s_v, s_i);
+    else {
+        const size_t o = (size_t)row * p.rstride;
+        ToppParams tp{};
+        tp.logits = p.logits + (size_t)row * p.ld; tp.n = p.n; tp.temperature = r.temperature; tp.topp = r.topp; tp.u = r.u;
+        tp.keys = p.keys + o; tp.vals = p.vals + o; tp.m = p.m + row;
+        ArgmaxParams fin{};
+        fin.result = &s_i[0];                                      // finish_step's raw pick (-1: nothing kept)
+        topp_pick_scan_body(tp, fin, sh);
+        __syncthreads();
+        idx = s_i[0];
+    }
+    __syncthreads();                                               // every wave has read the position before it moves on
+    if (tid != 0) return;
+    if (!p.seqs) { p.result[row] = idx; return; }
+    const int next = idx < 0 ? 0 : idx;
+    p.toks[row] = next;
+    p.seqs[row].pos = pos + 1;
+    const int k = p.seqs[row].pad;                                 // tokens this sequence has produced so far
+    if (k < p.out_cap) {
+        p.out[(size_t)row * p.out_cap + k] = next;
+        if (p.ring) __hip_atomic_store(p.ring + (size_t)row * p.out_cap + k, next + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    p.seqs[row].pad = k + 1;
 }
 
 }  // namespace rama

@@ -8,7 +8,8 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from ._lib import check, rama_config, rama_run_state, rama_stage, rama_weights
+from ._lib import check, rama_config, rama_run_state, rama_seq_sampling, rama_stage, rama_weights
+from .sampler_const import TOPP_U_CPU
 from .transformer import Config, Hip
 
 KERNEL_IDS = dict(qkv=0, attn=1, wo=2, w13=3, w2=4, cls=5, norm=6, sample=7)
@@ -206,19 +207,73 @@ def decode_batch(engines: Sequence["Engine"], tokens: Sequence[int], positions: 
                                           states, toks, poss, len(engines)), "rama_decode_batch")
 
 
-def decode_batch_chained(engines: Sequence["Engine"], tokens: Sequence[int], positions: Sequence[int], n_steps: int, on_token=None):
-    """n_steps greedy decode steps of up to 128 independent sequences chained on the device (rama_decode_batch_begin /
+def _per_seq(v, n: int, what: str) -> list:
+    """a scalar for every sequence, or one value per sequence"""
+    if np.ndim(v) == 0:
+        return [v] * n
+    v = list(v)
+    if len(v) != n:
+        raise ValueError(f"{what}: {len(v)} values for {n} sequences")
+    return v
+
+
+def sample_topp_batch(device: Hip, logits, temperature=1.0, topp=0.9, u=TOPP_U_CPU, n_rows: Optional[int] = None,
+                      n: Optional[int] = None, ld: Optional[int] = None):
+    """Device::sample for many rows at once on the device (rama_sample_topp_batch_dev) -> one token id per row (-1: nothing
+    kept).  `logits` is a host array [rows, n] (uploaded for the call) or a device pointer (int) to n_rows rows of n floats,
+    ld floats apart (default n).  temperature, topp and u are scalars or one value per row."""
+    owned = None
+    if isinstance(logits, np.ndarray):
+        a = np.ascontiguousarray(logits, dtype=np.float32)
+        a = a.reshape(1, -1) if a.ndim == 1 else a
+        n_rows, n, ld = a.shape[0], a.shape[1], a.shape[1]
+        owned = device.allocate(a)
+        ptr = owned.ptr
+    else:
+        if n_rows is None or n is None:
+            raise ValueError("sample_topp_batch: a device pointer needs n_rows and n")
+        ptr, ld = int(logits), ld if ld is not None else n
+    T = (C.c_float * n_rows)(*_per_seq(temperature, n_rows, "temperature"))
+    P = (C.c_float * n_rows)(*_per_seq(topp, n_rows, "topp"))
+    U = (C.c_float * n_rows)(*_per_seq(u, n_rows, "u"))
+    res = device.alloc(n_rows)
+    try:
+        check(device.lib.rama_sample_topp_batch_dev(device.ctx, ptr, ld, n, n_rows, T, P, U, res.ptr), "rama_sample_topp_batch_dev")
+        return [int(v) for v in device.download(res).view(np.int32)]
+    finally:
+        res.free()
+        if owned is not None:
+            owned.free()
+
+
+def decode_batch_chained(engines: Sequence["Engine"], tokens: Sequence[int], positions: Sequence[int], n_steps: int, on_token=None,
+                         temperature=0.0, topp=0.9, u=TOPP_U_CPU, prompts=None):
+    """n_steps decode steps of up to 128 independent sequences chained on the device (rama_decode_batch_begin /
     _steps / _tokens): -> per sequence the n_steps tokens it produced.  engines[i]'s caches are advanced.
     on_token(sequence, index, token), when given, is called for every token as it appears in the host-visible rings
-    (rama_decode_batch_stream_poll) while the steps run."""
+    (rama_decode_batch_stream_poll) while the steps run.
+    temperature, topp, u (scalars or one per sequence) and prompts (None or one token list per sequence, forced by absolute
+    position as in generate()) select the sampled chain (rama_decode_batch_begin_sampled); with the defaults every step
+    is the greedy chain's argmax."""
     assert 1 <= len(engines) == len(tokens) == len(positions) <= 128
     e0 = engines[0]
     L = e0.device.lib
-    states = (rama_run_state * len(engines))(*[e.state for e in engines])
-    toks = (C.c_int32 * len(engines))(*tokens)
-    poss = (C.c_int32 * len(engines))(*positions)
-    check(L.rama_decode_batch_begin(e0.device.ctx, C.byref(e0.model.ccfg), C.byref(e0.model.weights), states, toks, poss,
-                                    len(engines), max(n_steps, 1)), "rama_decode_batch_begin")
+    ns = len(engines)
+    states = (rama_run_state * ns)(*[e.state for e in engines])
+    toks = (C.c_int32 * ns)(*tokens)
+    poss = (C.c_int32 * ns)(*positions)
+    Ts, Ps, Us = _per_seq(temperature, ns, "temperature"), _per_seq(topp, ns, "topp"), _per_seq(u, ns, "u")
+    prompts = [list(p) for p in prompts] if prompts is not None else [[] for _ in range(ns)]
+    if len(prompts) != ns:
+        raise ValueError(f"prompts: {len(prompts)} lists for {ns} sequences")
+    if all(t == 0.0 for t in Ts) and not any(prompts):
+        check(L.rama_decode_batch_begin(e0.device.ctx, C.byref(e0.model.ccfg), C.byref(e0.model.weights), states, toks, poss,
+                                        ns, max(n_steps, 1)), "rama_decode_batch_begin")
+    else:
+        forced = [(C.c_int32 * max(len(p), 1))(*p) for p in prompts]
+        per = (rama_seq_sampling * ns)(*[rama_seq_sampling(Ts[i], Ps[i], Us[i], forced[i], len(prompts[i])) for i in range(ns)])
+        check(L.rama_decode_batch_begin_sampled(e0.device.ctx, C.byref(e0.model.ccfg), C.byref(e0.model.weights), states, toks,
+                                                poss, ns, max(n_steps, 1), per), "rama_decode_batch_begin_sampled")
     check(L.rama_decode_batch_steps(e0.device.ctx, n_steps), "rama_decode_batch_steps")
     if on_token is not None:
         import time
