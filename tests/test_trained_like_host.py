@@ -1,0 +1,199 @@
+"""CPU: the trained-like test data (tests/trained_like.py) has the properties the GPU tests rely on, and the comparator against
+the float64 forward is neither tighter than the fp32 reference nor blind to small planted faults."""
+import math
+
+import numpy as np
+import pytest
+
+from oracle import oracle as O
+
+from . import trained_like as T
+
+
+def _cfg(shared, dim=64, hidden=176, layers=2, heads=4, vocab=40, seq=24):
+    return O.Config(dim, hidden, layers, heads, heads, vocab, seq, shared)
+
+
+@pytest.mark.parametrize("shared", [True, False])
+def test_checkpoint_writer_round_trips(tmp_path, shared):
+    cfg = _cfg(shared)
+    w = T.trained_like_weights(cfg, "massive", 3)
+    p = tmp_path / "m.bin"
+    T.write_checkpoint(p, cfg, w)
+    raw = p.read_bytes()
+    hdr = np.frombuffer(raw[:28], "<i4")
+    assert hdr.tolist() == [cfg.dim, cfg.hidden_dim, cfg.n_layers, cfg.n_heads, cfg.n_kv_heads,
+                            cfg.vocab_size if shared else -cfg.vocab_size, cfg.seq_len]
+    n = sum(int(np.prod(s)) for _, s in O.weight_shapes(cfg))
+    assert len(raw) == 28 + 4 * n
+    cfg2, w2 = O.read_checkpoint(p)
+    assert cfg2 == cfg
+    for name, _ in O.weight_shapes(cfg):
+        assert w2[name].tobytes() == np.ascontiguousarray(w[name], np.float32).tobytes(), name
+    assert w2["wcls"].tobytes() == np.ascontiguousarray(w["wcls"], np.float32).tobytes()
+
+
+@pytest.mark.parametrize("dim", [288, 768, 2048, 4096])
+def test_tie_row_defeats_the_one_pass_sum(dim):
+    """every tail square is half an ulp of 4096: the sequential sum never moves, every group of 8 is a SEQ group, and from dim 2048 on
+    the walk list needs more than kFsCap items (the leader's fallback loop)"""
+    sq = (T.tie_row(dim) ** 2).astype(np.float32)
+    s32, s64 = T.seq_sum_f32(sq), float(np.sum(sq.astype(np.float64)))
+    assert s32 == np.float32(4096.0)
+    assert s64 - float(s32) == (dim - 1) * 2.0 ** -12
+    g = T.seq_groups(sq)
+    assert g["ties"] == dim - 1 and g["groups"] == dim // 8
+    assert (g["items"] > T.FS_CAP) == (dim >= 2048)
+    if dim == 4096:
+        assert (s64 - s32) / s64 > 2.0 ** -13
+        assert g["groups"] > 128
+
+
+@pytest.mark.parametrize("dim", [288, 768, 2048, 4096])
+def test_other_designated_rows(dim):
+    rows = T.designated_rows(dim)
+    assert not rows[T.TOK_ZERO].any()
+    sq = (rows[T.TOK_SUBNORMAL].astype(np.float32) ** 2).astype(np.float32)
+    assert (sq > 0).all() and (sq < np.finfo(np.float32).tiny).all()
+    assert 0 < T.seq_sum_f32(sq) < np.finfo(np.float32).tiny
+    big = rows[T.TOK_LARGE]
+    sq = (big * big).astype(np.float32)
+    assert np.isfinite(sq).all() and np.isfinite(T.seq_sum_f32(sq)) and sq.min() >= 1e32
+    z = T.seq_groups(np.zeros(dim, np.float32))
+    assert z["groups"] == dim // 8
+
+
+def test_massive_weights_have_their_shape():
+    cfg = _cfg(False, dim=288, hidden=768, heads=6, vocab=64, seq=16)
+    w = T.trained_like_weights(cfg, "massive", 5)
+    emb = w["token_embedding_table"]
+    med = np.median(np.abs(emb[8:]))
+    for c in T.massive_channels(cfg.dim):
+        r = np.abs(emb[8:, c]) / med
+        assert 300 <= np.median(r) <= 3600, (c, np.median(r))
+    assert T.massive_channels(cfg.dim)[1] % 16 == 0
+    g = w["rms_att_weight"]
+    assert (g.max(axis=1) >= 10).all() and (g.min(axis=1) <= 1e-3).all()
+    assert 0.7 < np.median(g) < 1.4
+    # heavy tails: kurtosis of t(4) is infinite; far above the normal's 3 on any sample
+    x = w["wv"].reshape(-1).astype(np.float64)
+    assert np.mean(x ** 4) / np.mean(x ** 2) ** 2 > 6
+    assert abs(x.std() - 0.02) < 0.004
+
+
+def test_sink_weights_reach_large_scores():
+    """sink kind: the largest |score| of the live heads reaches 30 .. 100 (float64 forward, last layer), head 0 is dead (all scores 0),
+    head 1 nearly flat"""
+    cfg = O.Config(512, 512, 2, 4, 4, 64, 16, False)      # head size 128
+    w = T.trained_like_weights(cfg, "sink", 2)
+    f = O.Oracle(cfg, w)
+    best = flat = 0.0
+    for pos, tok in enumerate([1, 7, 9, 11, 13, 17, 19, 23]):
+        f.forward_f64(tok, pos)
+        sc = f.s["att"].reshape(cfg.n_heads, cfg.seq_len)[:, :pos + 1]
+        assert not sc[0].any()
+        flat = max(flat, float(np.abs(sc[1]).max()))
+        best = max(best, float(np.abs(sc[2:]).max()))
+    assert flat < 0.5, flat
+    assert 30 <= best <= 300, best
+
+
+@pytest.mark.parametrize("sink_at", ["first", "boundary", "last"])
+def test_sink_caches_put_the_tail_at_half_ulps(sink_at):
+    """the prefilled caches give every live head one probability ~1 and a tail with exp(s - max) in [2^-25, 2^-24]: the fp32 sum of
+    the exponentials stays within 2^-13 of 1.0 (inside seq_sum_predict's margin at a binade edge), and from 1 025 terms on every
+    group of eight is a SEQ group of seqsum_fast.hpp: more items than kFsCap"""
+    cfg = O.Config(256, 256, 2, 4, 4, 32, 1100, False)
+    w = T.trained_like_weights(cfg, "sink", 4)
+    pos = 1099
+    at = {"first": 0, "boundary": 256, "last": pos - 1}[sink_at]
+    kc, vc = T.sink_caches(cfg, w, 9, pos, at)
+    f = O.Oracle(cfg, w)
+    f.s["key_cache"][:] = kc; f.s["value_cache"][:] = vc
+    f.forward_f64(9, pos)
+    sc = f.s["att"].reshape(cfg.n_heads, cfg.seq_len)[:, :pos + 1].astype(np.float64)
+    assert not sc[0].any()                                  # the dead head
+    for hh in range(2, cfg.n_heads):
+        e = np.exp(sc[hh] - sc[hh].max()).astype(np.float32)
+        assert int(np.argmax(sc[hh])) == at
+        tail = np.delete(e, [at, pos])
+        assert (tail <= 2.0 ** -23.9).all() and np.mean(tail >= 2.0 ** -25.1) > 0.99
+        s = float(T.seq_sum_f32(e))
+        assert 1.0 <= s < 1.0 + 2.0 ** -13
+        if at == 0:
+            assert T.seq_groups(e)["items"] > T.FS_CAP
+
+
+# ------------------------------------------------------------------ the comparator
+
+def _forward_ops(cfg, w, st, token, pos, att_len=None, drop_block=None):
+    """infer.rs:8-53 from the oracle's 1:1 ops, with two optional planted faults: the attention over att_len positions instead of
+    pos + 1, and a matvec (W1 of the last layer) that skips the 16 input columns starting at drop_block"""
+    d, h, hs = cfg.dim, cfg.hidden_dim, cfg.head_size
+    s = st
+    O.copy_from_slice(s["x"], np.ascontiguousarray(w["token_embedding_table"][token]), d)
+    pr = np.ascontiguousarray(w["freq_cis_real"][pos]); pi = np.ascontiguousarray(w["freq_cis_imag"][pos])
+    scratch = O.Oracle(cfg, {k: v for k, v in w.items()})
+    for l in range(cfg.n_layers):
+        O.rmsnorm(s["xb"], s["x"], np.ascontiguousarray(w["rms_att_weight"][l]), d)
+        O.matmul(s["q"], np.ascontiguousarray(w["wq"][l]), s["xb"], d, d)
+        O.matmul(s["k"], np.ascontiguousarray(w["wk"][l]), s["xb"], d, d)
+        O.matmul(s["v"], np.ascontiguousarray(w["wv"][l]), s["xb"], d, d)
+        for hh in range(cfg.n_heads):
+            q = s["q"][hh * hs:(hh + 1) * hs].copy(); k = s["k"][hh * hs:(hh + 1) * hs].copy()
+            O.apply_position(q, k, pr, pi, hs)
+            s["q"][hh * hs:(hh + 1) * hs] = q; s["k"][hh * hs:(hh + 1) * hs] = k
+        lo = l * cfg.seq_len * d
+        s["key_cache"][lo + pos * d:lo + (pos + 1) * d] = s["k"]
+        s["value_cache"][lo + pos * d:lo + (pos + 1) * d] = s["v"]
+        for name in ("q", "key_cache", "value_cache", "att", "xb"):
+            scratch.s[name][:] = s[name]
+        scratch.multi_head_attention(l, pos if att_len is None else att_len - 1)
+        s["xb"][:] = scratch.s["xb"]; s["att"][:] = scratch.s["att"]
+        O.matmul(s["xb2"], np.ascontiguousarray(w["wo"][l]), s["xb"], d, d)
+        s["x"][:] = s["x"] + s["xb2"]
+        O.rmsnorm(s["xb"], s["x"], np.ascontiguousarray(w["rms_ffn_weight"][l]), d)
+        w1 = np.ascontiguousarray(w["w1"][l])
+        if drop_block is not None and l == cfg.n_layers - 1:
+            w1 = w1.copy(); w1[:, drop_block:drop_block + 16] = 0.0
+        O.matmul(s["hb"], w1, s["xb"], d, h)
+        O.matmul(s["hb2"], np.ascontiguousarray(w["w3"][l]), s["xb"], d, h)
+        O.sinu(s["hb"], h)
+        s["hb"][:] = s["hb"] * s["hb2"]
+        O.matmul(s["xb"], np.ascontiguousarray(w["w2"][l]), s["hb"], h, d)
+        s["x"][:] = s["x"] + s["xb"]
+    s["xb"][:] = s["x"]
+    O.rmsnorm(s["x"], s["xb"], np.ascontiguousarray(w["rms_final_weight"]), d)
+    O.matmul(s["logits"], np.ascontiguousarray(w["wcls"]), s["x"], d, cfg.vocab_size)
+
+
+@pytest.mark.parametrize("kind", T.KINDS)
+def test_comparator_accepts_the_reference_and_rejects_planted_faults(kind):
+    cfg = O.Config(288, 768, 2, 6, 6, 96, 64, False)
+    w = T.trained_like_weights(cfg, kind, 6)
+    toks = [1, T.TOK_TIE, T.TOK_ZERO, T.TOK_SUBNORMAL, T.TOK_LARGE, 7, 9, 11, 13, 15]
+    o, f = O.Oracle(cfg, w), O.Oracle(cfg, w)
+    ops = {k: np.zeros_like(v) for k, v in o.s.items()}
+    att_fault = {k: np.zeros_like(v) for k, v in o.s.items()}
+    blk_fault = {k: np.zeros_like(v) for k, v in o.s.items()}
+    caught_att = caught_blk = 0
+    for pos, tok in enumerate(toks):
+        o.forward(tok, pos); f.forward_f64(tok, pos)
+        _forward_ops(cfg, w, ops, tok, pos)
+        for k in ("logits", "x", "xb", "hb", "q", "key_cache", "value_cache", "att"):
+            assert ops[k].tobytes() == o.s[k].tobytes(), (pos, k)       # the op composition is the reference's forward
+        Ov, F = T.state_view(o.s, cfg, pos), T.state_view(f.s, cfg, pos, f64=True)
+        assert T.assert_f64_bound(Ov, Ov, F, f"{kind} pos {pos}") <= 1.0 / T.F64_A + 1e-12
+        if pos == 0 or tok == T.TOK_LARGE:      # (a residual of 1e17: anything O(1) in it is below fp32's resolution, faults included)
+            continue
+        _forward_ops(cfg, w, att_fault, tok, pos, att_len=pos)
+        _forward_ops(cfg, w, blk_fault, tok, pos, drop_block=16 * 5)
+        for bad, what in ((att_fault, "att"), (blk_fault, "blk")):
+            res = T.f64_bound(T.state_view(bad, cfg, pos), Ov, F)
+            hit = any(e > b for k, (e, b) in res.items() if k in ("logits", "x", "xb", "hb"))
+            if what == "att":
+                caught_att += hit
+            else:
+                caught_blk += hit
+    assert caught_att == len(toks) - 2, caught_att
+    assert caught_blk == len(toks) - 2, caught_blk
