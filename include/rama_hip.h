@@ -404,6 +404,58 @@ int  rama_set_tuning(rama_ctx *ctx, const char *key, int value);
  * evaluate it, elementwise: the bit-exactness test's handle on it */
 int  rama_ref_expf(rama_ctx *ctx, float *o, const float *x, size_t n);
 
+/* ---------------------------------------------------------------- Q8_0 models (llama2.c version-2 checkpoints)
+ * The Q8 forward is rama's forward (parity mode's exact norms, RoPE, attention, SiLU and residual adds) with every
+ * Device::matmul replaced by llama2.c runq.c's quantized product:
+ *   quantize(x, GS), per group: scale = max|x| / 127.0f; q = (int8) C round(x / scale) (halves away from zero), clamped to
+ *     [-127, 127]; scale == 0 gives q = 0; denormals kept.
+ *   matmul, row i: val = +0.0f; for g in order: ival = sum_k xq * Wq (exact int32); val = val + ((float)ival * Ws[i][g]) * xs[g]
+ *     (three separately rounded fp32 operations).
+ * Activations are quantized where runq.c does it: the attention-norm output (shared by Wq, Wk, Wv), the attention output
+ * (Wo), the FFN-norm output (W1, W3), SiLU * gate (W2) and the final-norm output (classifier).  The token table is
+ * dequantized once at load (q * s) and embeddings are read from that fp32 copy; the KV cache stays fp32.  This is NOT
+ * runq.c end to end: its rmsnorm and RoPE round differently from cpu.rs, whose order rama keeps. */
+typedef struct rama_q8_model rama_q8_model;
+/* device pointers; x_s = the fp32 scales of tensor x, one per group of group_size consecutive values (row-major).
+ * Per-layer tensors are stacked over layers as in the file; wcls == tok when the classifier is shared. */
+typedef struct {
+    int32_t group_size;
+    const float *token_embedding_table;            /* fp32 [vocab, dim], dequantized from tok / tok_s */
+    const float *rms_att_weight, *rms_ffn_weight, *rms_final_weight;
+    const float *freq_cis_real, *freq_cis_imag;    /* [seq_len, head_size / 2], computed at load */
+    const int8_t *tok, *wq, *wk, *wv, *wo, *w1, *w2, *w3, *wcls;
+    const float *tok_s, *wq_s, *wk_s, *wv_s, *wo_s, *w1_s, *w2_s, *w3_s, *wcls_s;
+} rama_q8_weights;
+/* A version-2 "ak42" file (export.py version2_export): 256-byte header (magic, version, 7 ints, shared-classifier byte,
+ * group size), the fp32 norms (attention, FFN, final), then per quantized tensor its int8 values and its fp32 scales:
+ * tok_embeddings, wq, wk, wv, wo, w1, w2, w3 (each over all layers), output unless shared.
+ * RAMA_EIO: the size does not match the header; RAMA_EUNSUP: not version 2, a group size that does not divide dim and
+ * hidden_dim, n_kv_heads != n_heads. */
+int  rama_q8_model_load(rama_ctx *ctx, const char *path, rama_q8_model **out);
+/* rama_model_synth's fp32 weights (same hash fill and tags), generated tensor by tensor through a bounded scratch and
+ * quantized by export.py quantize_q80's rule (scale = max|w| / 127, torch.round: halves to even).  RoPE tables as
+ * rama_model_synth computes them without given tables. */
+int  rama_q8_model_synth(rama_ctx *ctx, const rama_config *cfg, int group_size, uint64_t seed, rama_q8_model **out);
+int  rama_q8_model_config(const rama_q8_model *m, rama_config *cfg);
+int  rama_q8_model_weights(const rama_q8_model *m, rama_q8_weights *w);
+size_t rama_q8_model_bytes(const rama_q8_model *m);     /* bytes streamed per token: int8 values + scales + fp32 norms */
+int  rama_q8_model_free(rama_ctx *ctx, rama_q8_model *m);
+/* the op-level entries: quantize(x, n) -> q[n], s[n / group_size] (RAMA_EINVAL unless group_size divides n), and
+ * o[d] = matmul(xq, wq) for wq [d, n] with scales ws [d, n / group_size] */
+int  rama_q8_quantize(rama_ctx *ctx, const float *x, size_t n, int group_size, int8_t *q, float *s);
+int  rama_q8_matmul(rama_ctx *ctx, float *o, const int8_t *wq, const float *ws, const int8_t *xq, const float *xs,
+                    size_t n, size_t d, int group_size);
+/* rama_forward for a Q8 model: the same run-state buffers (logits, the cache rows of `pos`, x).  The int8 activation
+ * scratch belongs to the context and is sized on the first call (outside any capture).  Graph mode: one graph per
+ * (run state, attention variant), kept apart from the fp32 graphs; rama_state_free drops the Q8 graphs of the state it frees
+ * and rama_q8_model_free those of every Q8 model. */
+int  rama_q8_forward(rama_ctx *ctx, const rama_config *cfg, const rama_q8_weights *w, rama_run_state *s, int token, int pos);
+/* generate() (mod.rs:169-206) over a Q8 model, chained on the device as rama_generate: BOS at 0, forced prompt, then
+ * Device::sample (argmax at temperature 0, else the device top-p sampler with draw u).  Graph mode: a step is one replay. */
+int  rama_q8_generate(rama_ctx *ctx, const rama_config *cfg, const rama_q8_weights *w, rama_run_state *s,
+                      const int32_t *prompt_tokens_host, int n_prompt, int steps, float temperature, float topp, float u,
+                      int32_t *out_tokens_host);
+
 /* ---------------------------------------------------------------- measurement
  * HIP events on the context's stream (the stream the kernels are launched on). */
 int  rama_timer_start(rama_ctx *ctx);

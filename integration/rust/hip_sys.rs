@@ -35,6 +35,18 @@ pub struct rama_run_state {
 pub struct rama_seq_sampling {
     pub temperature: f32, pub topp: f32, pub u: f32, pub forced: *const i32, pub n_forced: i32,
 }
+#[repr(C)] pub struct rama_q8_model { _p: [u8; 0] }
+/// a Q8_0 (llama2.c version-2) model as device pointers; `x_s` = the fp32 scales of the int8 tensor `x`
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct rama_q8_weights {
+    pub group_size: i32,
+    pub token_embedding_table: *const f32, pub rms_att_weight: *const f32, pub rms_ffn_weight: *const f32,
+    pub rms_final_weight: *const f32, pub freq_cis_real: *const f32, pub freq_cis_imag: *const f32,
+    pub tok: *const i8, pub wq: *const i8, pub wk: *const i8, pub wv: *const i8, pub wo: *const i8,
+    pub w1: *const i8, pub w2: *const i8, pub w3: *const i8, pub wcls: *const i8,
+    pub tok_s: *const f32, pub wq_s: *const f32, pub wk_s: *const f32, pub wv_s: *const f32, pub wo_s: *const f32,
+    pub w1_s: *const f32, pub w2_s: *const f32, pub w3_s: *const f32, pub wcls_s: *const f32,
+}
 
 extern "C" {
     pub fn rama_ctx_create(device: c_int, stream: *mut c_void, out: *mut *mut rama_ctx) -> c_int;
@@ -156,6 +168,23 @@ extern "C" {
     pub fn rama_timer_stop(ctx: *mut rama_ctx, elapsed_ms: *mut f32) -> c_int;
     pub fn rama_kprof_enable(ctx: *mut rama_ctx, kernel_id: c_int, max_records: c_int) -> c_int;
     pub fn rama_kprof_read(ctx: *mut rama_ctx, n_launches: *mut c_int, total_ms: *mut f64) -> c_int;
+
+    // Q8_0 models (llama2.c version-2 checkpoints)
+    pub fn rama_q8_model_load(ctx: *mut rama_ctx, path: *const c_char, out: *mut *mut rama_q8_model) -> c_int;
+    pub fn rama_q8_model_synth(ctx: *mut rama_ctx, cfg: *const rama_config, group_size: c_int, seed: u64,
+                               out: *mut *mut rama_q8_model) -> c_int;
+    pub fn rama_q8_model_config(m: *const rama_q8_model, cfg: *mut rama_config) -> c_int;
+    pub fn rama_q8_model_weights(m: *const rama_q8_model, w: *mut rama_q8_weights) -> c_int;
+    pub fn rama_q8_model_bytes(m: *const rama_q8_model) -> usize;
+    pub fn rama_q8_model_free(ctx: *mut rama_ctx, m: *mut rama_q8_model) -> c_int;
+    pub fn rama_q8_quantize(ctx: *mut rama_ctx, x: *const f32, n: usize, group_size: c_int, q: *mut i8, s: *mut f32) -> c_int;
+    pub fn rama_q8_matmul(ctx: *mut rama_ctx, o: *mut f32, wq: *const i8, ws: *const f32, xq: *const i8, xs: *const f32,
+                          n: usize, d: usize, group_size: c_int) -> c_int;
+    pub fn rama_q8_forward(ctx: *mut rama_ctx, cfg: *const rama_config, w: *const rama_q8_weights, s: *mut rama_run_state,
+                           token: c_int, pos: c_int) -> c_int;
+    pub fn rama_q8_generate(ctx: *mut rama_ctx, cfg: *const rama_config, w: *const rama_q8_weights, s: *mut rama_run_state,
+                            prompt_tokens_host: *const i32, n_prompt: c_int, steps: c_int, temperature: f32, topp: f32, u: f32,
+                            out_tokens_host: *mut i32) -> c_int;
 }
 
 #[repr(C)] pub struct rama_pipe { _p: [u8; 0] }

@@ -43,6 +43,17 @@ class rama_run_state(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in S_FIELDS]
 
 
+Q8_TENSORS = ("tok", "wq", "wk", "wv", "wo", "w1", "w2", "w3", "wcls")
+
+
+class rama_q8_weights(C.Structure):
+    """include/rama_hip.h rama_q8_weights (device pointers; x_s = the scales of x)"""
+    _fields_ = ([("group_size", C.c_int32)] +
+                [(n, C.c_void_p) for n in ("token_embedding_table", "rms_att_weight", "rms_ffn_weight", "rms_final_weight",
+                                           "freq_cis_real", "freq_cis_imag")] +
+                [(n, C.c_void_p) for n in Q8_TENSORS] + [(n + "_s", C.c_void_p) for n in Q8_TENSORS])
+
+
 class rama_stage(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("layer_begin", "layer_end", "do_embed", "do_cls")]
 
@@ -141,6 +152,16 @@ SIGNATURES = {
     "rama_timer_stop": (_int, [_vp, C.POINTER(C.c_float)]),
     "rama_kprof_enable": (_int, [_vp, _int, _int]),
     "rama_kprof_read": (_int, [_vp, C.POINTER(_int), C.POINTER(C.c_double)]),
+    "rama_q8_model_load": (_int, [_vp, C.c_char_p, C.POINTER(_vp)]),
+    "rama_q8_model_synth": (_int, [_vp, _cfgp, _int, C.c_uint64, C.POINTER(_vp)]),
+    "rama_q8_model_config": (_int, [_vp, _cfgp]),
+    "rama_q8_model_weights": (_int, [_vp, C.POINTER(rama_q8_weights)]),
+    "rama_q8_model_bytes": (_sz, [_vp]),
+    "rama_q8_model_free": (_int, [_vp, _vp]),
+    "rama_q8_quantize": (_int, [_vp, _vp, _sz, _int, _vp, _vp]),
+    "rama_q8_matmul": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _int]),
+    "rama_q8_forward": (_int, [_vp, _cfgp, C.POINTER(rama_q8_weights), _sp, _int, _int]),
+    "rama_q8_generate": (_int, [_vp, _cfgp, C.POINTER(rama_q8_weights), _sp, i32p, _int, _int, C.c_float, C.c_float, C.c_float, i32p]),
 }
 
 _lib = None

@@ -8,6 +8,8 @@
 // RAMA_PATH=ops     forward() composed from the 1:1 Device ops (the drop-in path)
 // RAMA_PATH=fused   (default) rama_forward: five fused launches per layer
 // RAMA_PATH=chained the whole loop chained on the device, every token printed as it appears in the host-visible ring
+// A llama2.c version-2 (Q8_0, "ak42") checkpoint decodes through the Q8 entries (rama_q8_forward / rama_q8_generate):
+//                   fused = a forward per token + the device sampler, chained = rama_q8_generate; ops and RAMA_WORLD > 1 exit 2
 // RAMA_WORLD=N RAMA_RANK=r RAMA_PIPE_ID_FILE=path [RAMA_DEVICE=d]
 //                   layer pipeline over N processes, one GPU each (csrc/pipe.hip: RCCL send/recv of
 //                   x[dim] and the sampled token id).  Rank r loads layers [r*L/N, (r+1)*L/N) only;
@@ -145,8 +147,81 @@ static int run_pipeline_stage(const Args& args, int world, int rank) {
     return 0;
 }
 
+// ---- a version-2 (Q8_0) checkpoint: the same generate() loop over the Q8 forward (include/rama_hip.h)
+static int ak42_version(const std::string& path) {       // 0: not an ak42 file; else the version in its header
+    std::ifstream f(path, std::ios::binary);
+    uint32_t h[2] = {0, 0};
+    f.read(reinterpret_cast<char*>(h), sizeof h);
+    if (!f || h[0] != 0x616b3432u) return 0;
+    return (int)h[1];
+}
+
+static int run_q8(const Args& args, const std::string& path) {
+    if (const char* we = std::getenv("RAMA_WORLD")) {
+        if (std::atoi(we) > 1) { std::fprintf(stderr, "a Q8_0 (version-2) checkpoint runs on one GPU: RAMA_WORLD > 1 is not supported\n"); return 2; }
+    }
+    if (path != "fused" && path != "chained") {
+        std::fprintf(stderr, "a Q8_0 (version-2) checkpoint decodes with RAMA_PATH=fused or chained; '%s' is not supported\n", path.c_str());
+        return 2;
+    }
+    Hip device(0);
+    rama_q8_model* model = nullptr;
+    ck(rama_q8_model_load(device.ctx, args.model.c_str(), &model), "rama_q8_model_load");
+    rama_config c{};
+    rama_q8_weights w{};
+    ck(rama_q8_model_config(model, &c), "rama_q8_model_config");
+    ck(rama_q8_model_weights(model, &w), "rama_q8_model_weights");
+    rama_run_state s{};
+    ck(rama_state_create(device.ctx, &c, c.n_layers, &s), "rama_state_create");
+    Tokenizer tokenizer;
+    std::vector<size_t> prompt_tokens;
+    try {
+        tokenizer = Tokenizer::from_file(args.tokenizer, (size_t)c.vocab_size);
+        if (!args.prompt.empty()) prompt_tokens = tokenizer.encode(args.prompt);
+    } catch (const std::exception& e) { std::fprintf(stderr, "panic: %s\n", e.what()); return 101; }
+    const size_t steps = args.step;
+    if (steps > (size_t)c.seq_len) {
+        std::fprintf(stderr, "step %zu exceeds the checkpoint's seq_len %d\n", steps, c.seq_len);
+        return 1;
+    }
+    const auto start = std::chrono::steady_clock::now();
+    try {
+        if (path == "chained") {
+            std::vector<int32_t> pt(prompt_tokens.begin(), prompt_tokens.end()), out(steps ? steps : 1);
+            ck(rama_q8_generate(device.ctx, &c, &w, &s, pt.data(), (int)pt.size(), (int)steps, args.temperature, args.topp,
+                                device.topp_draw, out.data()), "rama_q8_generate");
+            for (size_t i = 0; i < steps; i++) std::cout << decode(tokenizer.vocab[(size_t)out[i]]);
+            std::cout.flush();
+        } else {
+            size_t token = 1, pos = 0;                                    // mod.rs:182-183
+            while (pos < steps) {
+                ck(rama_q8_forward(device.ctx, &c, &w, &s, (int)token, (int)pos), "rama_q8_forward");
+                int32_t nx = 0;
+                if (pos < prompt_tokens.size()) nx = (int32_t)prompt_tokens[pos];
+                else if (args.temperature == 0.0f) ck(rama_sample_argmax(device.ctx, s.logits, (size_t)c.vocab_size, &nx), "sample");
+                else ck(rama_sample_topp(device.ctx, s.logits, (size_t)c.vocab_size, args.temperature, args.topp, device.topp_draw, &nx), "sample");
+                std::cout << decode(tokenizer.vocab[(size_t)nx]);
+                std::cout.flush();
+                token = (size_t)nx;
+                pos += 1;
+            }
+        }
+    } catch (const std::exception& e) { std::fprintf(stderr, "\npanic: %s\n", e.what()); return 101; }
+    const double elapsed = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
+    std::printf("\n--------------------------------\n");
+    std::printf("elapsed: %lld.%03lld s, avg tok/s: %g\n", (long long)elapsed, (long long)(elapsed * 1000) % 1000,
+                (double)((float)(args.step - 1) / (float)elapsed));
+    rama_state_free(device.ctx, &s);
+    rama_q8_model_free(device.ctx, model);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     const Args args = parse(argc, argv);
+    if (ak42_version(args.model) == 2) {
+        const char* pe = std::getenv("RAMA_PATH");
+        return run_q8(args, pe ? pe : "fused");
+    }
     if (const char* we = std::getenv("RAMA_WORLD")) {
         const int world = std::atoi(we), rank = std::getenv("RAMA_RANK") ? std::atoi(std::getenv("RAMA_RANK")) : 0;
         if (world > 1 || std::getenv("RAMA_PIPE_ID_FILE")) {

@@ -508,7 +508,7 @@ extern "C" int rama_model_load_stage(rama_ctx* ctx, const char* path, const rama
     c.seq_len = hdr[6];
     if (hdr[0] == 0x616b3432) {   // "ak42": llama2.c v1/v2 header (export.py:132-260), which the engine cannot read
         munmap(map, sb.st_size);
-        return bad(RAMA_EUNSUP, "checkpoint is llama2.c v1/v2 (ak42 header); rama reads the v0 legacy format only");
+        return bad(RAMA_EUNSUP, "checkpoint is llama2.c v1/v2 (ak42 header); rama_model_load reads the v0 legacy format only (a version-2 Q8_0 file: rama_q8_model_load)");
     }
     if (c.dim <= 0 || c.hidden_dim <= 0 || c.n_layers <= 0 || c.n_heads <= 0 || c.vocab_size <= 0 || c.seq_len <= 0 ||
         c.dim % c.n_heads != 0) {
@@ -581,6 +581,19 @@ extern "C" int rama_model_load(rama_ctx* ctx, const char* path, rama_model** out
     return rama_model_load_stage(ctx, path, nullptr, out);
 }
 
+// model.py:41-47: cos/sin(t * 10000^(-2i/hs)) in double, rounded to fp32 -- the tables rama_model_synth makes when none are given
+// (and the Q8 models, whose files carry none)
+extern "C" void rama_internal_rope_tables(const rama_config* cfg, std::vector<float>* re, std::vector<float>* im) {
+    const size_t hs = cfg->dim / cfg->n_heads, S = cfg->seq_len;
+    re->assign(S * (hs / 2), 0.f); im->assign(S * (hs / 2), 0.f);
+    for (size_t t = 0; t < S; t++)
+        for (size_t i = 0; i < hs / 2; i++) {
+            double f = 1.0 / std::pow(10000.0, (double)(2 * i) / (double)hs);
+            (*re)[t * (hs / 2) + i] = (float)std::cos((double)t * f);
+            (*im)[t * (hs / 2) + i] = (float)std::sin((double)t * f);
+        }
+}
+
 extern "C" int rama_model_synth(rama_ctx* ctx, const rama_config* cfg, uint64_t seed, const rama_stage* stage,
                                 const float* rope_real_host, const float* rope_imag_host, rama_model** out) {
     if (!ctx || !cfg || !out) return bad(RAMA_EINVAL, "rama_model_synth: NULL argument");
@@ -610,7 +623,6 @@ extern "C" int rama_model_synth(rama_ctx* ctx, const rama_config* cfg, uint64_t 
     int rc = rama_alloc_f32(ctx, total, &m->blob);
     if (rc) { delete m; return rc; }
     size_t off = 0;
-    const size_t hs = cfg->dim / cfg->n_heads;
     for (auto& p : pieces) {
         float* dst = m->blob + off;
         *field(m->w, p.t.name) = dst;
@@ -620,14 +632,9 @@ extern "C" int rama_model_synth(rama_ctx* ctx, const rama_config* cfg, uint64_t 
         } else {
             const bool real = !strcmp(p.t.name, "freq_cis_real");
             const float* given = real ? rope_real_host : rope_imag_host;
-            std::vector<float> tab;
-            if (!given) {   // model.py:41-47: cos/sin(t * 10000^(-2i/hs))
-                tab.resize(p.n);
-                for (size_t t = 0; t < (size_t)cfg->seq_len; t++)
-                    for (size_t i = 0; i < hs / 2; i++) {
-                        double f = 1.0 / std::pow(10000.0, (double)(2 * i) / (double)hs);
-                        tab[t * (hs / 2) + i] = (float)(real ? std::cos((double)t * f) : std::sin((double)t * f));
-                    }
+            std::vector<float> tab, other;
+            if (!given) {
+                rama_internal_rope_tables(cfg, real ? &tab : &other, real ? &other : &tab);
                 given = tab.data();
             }
             rc = rama_copy_h2d_f32(ctx, dst, given, p.n);

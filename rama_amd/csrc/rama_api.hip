@@ -10,6 +10,7 @@
 #include "ref_order.hpp"
 #include "chain.hpp"
 #include "topp_pick.hpp"
+#include "q8.hpp"
 
 #include <hip/hip_ext.h>   // hipExtLaunchKernelGGL: start/stop events carried by the dispatch itself
 
@@ -163,6 +164,10 @@ struct rama_ctx {
         int* bcount = nullptr; ToppStats* stats = nullptr; int* m = nullptr;     // rows x kToppRowBlocks, rows x kToppRowBlocks, rows
         ToppRow* rows_dev = nullptr;       // [kMfMaxTok] rama_sample_topp_batch_dev's (T, topp, u) per row, written by a launch
     } tb;
+    // Q8 models (rama_q8_forward / rama_q8_generate): the int8 activations and their scales, sized by the first call; graphs of their own
+    int8_t* q8_xq = nullptr; float* q8_xs = nullptr; size_t q8_cap = 0;
+    struct Q8Graph { hipGraphExec_t exec = nullptr; hipGraph_t graph = nullptr; rama_config cfg{}; rama_q8_weights w{}; rama_run_state s{}; int variant = 0; int chained = 0; };
+    std::vector<Q8Graph> q8g;
     int tune_split_pos = -1;               // attention runs split-T (+ combine launch) from this position on; -1 = by model size
     int tune_resid_r2 = 2;                 // Wo / W2 under geometry 3: 0 = 4-row workgroups, 1 = 2 rows x 8 waves (+0.45 %),
                                            // 2 = additionally 16 waves for rows wider than 8192 floats (W2: +1.15 % more), 3 = 16 waves x 4 chunks
@@ -365,6 +370,22 @@ int rama_ctx_create(int device, void* hip_stream, rama_ctx** out) {
     return 0;
 }
 
+// the captured Q8 steps: all of them (s == NULL) or those over one run state
+static void drop_q8_graphs(rama_ctx* c, const rama_run_state* s) {
+    bool any = false;
+    for (auto& e : c->q8g) any = any || !s || !memcmp(&e.s, s, sizeof *s);
+    if (!any) return;
+    (void)hipStreamSynchronize(c->stream);
+    for (size_t i = 0; i < c->q8g.size();) {
+        auto& e = c->q8g[i];
+        if (s && memcmp(&e.s, s, sizeof *s)) { i++; continue; }
+        if (e.exec) hipGraphExecDestroy(e.exec);
+        if (e.graph) hipGraphDestroy(e.graph);
+        c->q8g.erase(c->q8g.begin() + (long)i);
+    }
+}
+extern "C" void rama_internal_drop_q8_graphs(rama_ctx* c) { if (c) drop_q8_graphs(c, nullptr); }      // q8_model.hip: a freed Q8 model's steps
+
 static void drop_graph(rama_ctx* c) {
     if (c->bc.exec) { hipGraphExecDestroy(c->bc.exec); c->bc.exec = nullptr; }
     if (c->bc.graph) { hipGraphDestroy(c->bc.graph); c->bc.graph = nullptr; }
@@ -379,6 +400,7 @@ static void drop_graph(rama_ctx* c) {
         if (e.g.graph) hipGraphDestroy(e.g.graph);
     }
     c->sg.clear();
+    drop_q8_graphs(c, nullptr);
 }
 
 extern "C" void rama_internal_drop_graphs(rama_ctx* c) { if (c) drop_graph(c); }      // model.hip: before a derived weight copy is freed
@@ -399,6 +421,7 @@ int rama_ctx_destroy(rama_ctx* c) {
     hipFree(c->bc.rows); hipFree(c->bc.forced);
     hipFree(c->tb.keys); hipFree(c->tb.vals); hipFree(c->tb.bp); hipFree(c->tb.bi); hipFree(c->tb.rk); hipFree(c->tb.bm);
     hipFree(c->tb.bcount); hipFree(c->tb.stats); hipFree(c->tb.m); hipFree(c->tb.rows_dev);
+    hipFree(c->q8_xq); hipFree(c->q8_xs);
     hipHostFree(c->pinned_int); hipHostFree(c->pinned_tok);
     hipEventDestroy(c->t0); hipEventDestroy(c->t1);
     if (c->own_stream) hipStreamDestroy(c->stream);
@@ -3380,7 +3403,258 @@ int rama_state_create(rama_ctx* c, const rama_config* cfg, int n_local_layers, r
 int rama_state_free(rama_ctx* c, rama_run_state* s) {
     RAMA_ENTER(c);
     REQUIRE(c && s, RAMA_EINVAL, "state_free: NULL argument");
+    drop_q8_graphs(c, s);          // the Q8 steps captured over this state (the fp32 graphs: rama_set_graph_mode(0) first, as documented)
     int rc = rama_free(c, s->x);   // x is the blob base
     memset(s, 0, sizeof *s);
     return rc;
+}
+
+// ---------------------------------------------------------------- Q8_0 models (q8.hpp, q8_model.hip)
+// The forward of a version-2 checkpoint: parity mode's exact norms, RoPE + cache append, attention, SiLU and residual adds,
+// with every matmul replaced by runq.c's quantized product (rama_hip.h).  Per layer: norm, quantize,
+// Wq|Wk|Wv, RoPE + cache rows, attention, quantize, Wo (+ residual), norm, quantize, W1|W3 (+ SiLU * gate), quantize, W2 (+ residual).
+
+static int launch_q8_quantize(rama_ctx* c, const float* x, int n, int gs, int8_t* q, float* s) {
+    const int groups = n / gs;
+    RAMA_LAUNCH(c, q8_quantize_kernel, dim3((groups + 3) / 4), dim3(256), 0, x, n, gs, q, s);
+    LAUNCHCHK();
+    return 0;
+}
+
+template <int EPI>
+static int launch_q8_matvec(rama_ctx* c, Q8MatParams& p) {
+    const int G = p.K / p.gs, nm = EPI == Q8EPI_SWIGLU ? 2 : p.nmat;
+    bool fast = q8_matvec_fast_ok(p.K, p.gs) && (size_t)kQ8Waves * 2 * G * sizeof(float) <= 64 * 1024 && aligned16(p.xq);
+    for (int m = 0; m < nm; m++) fast = fast && aligned16(p.w[m]);
+    if (fast) {
+        const int tasks = EPI == Q8EPI_SWIGLU ? p.rows : (p.nmat * p.rows + 1) / 2;
+        const size_t lds = (size_t)kQ8Waves * 2 * G * sizeof(float);
+        RAMA_LAUNCH(c, (q8_matvec_kernel<2, EPI>), dim3((tasks + kQ8Waves - 1) / kQ8Waves), dim3(kQ8Waves * 64), lds, p);
+    } else {
+        const int total = EPI == Q8EPI_SWIGLU ? p.rows : p.nmat * p.rows;
+        RAMA_LAUNCH(c, (q8_matvec_generic_kernel<EPI>), dim3((total + 255) / 256), dim3(256), 0, p);
+    }
+    LAUNCHCHK();
+    return 0;
+}
+
+int rama_q8_quantize(rama_ctx* c, const float* x, size_t n, int group_size, int8_t* q, float* s) {
+    RAMA_ENTER(c);
+    REQUIRE(c && x && q && s, RAMA_EINVAL, "q8_quantize: NULL argument");
+    REQUIRE(group_size > 0 && n > 0 && n % (size_t)group_size == 0 && n < ((size_t)1 << 31), RAMA_EINVAL, "q8_quantize: group_size must divide n");
+    if (set_device(c)) return 1;
+    RAMA_WRITES(c, s, n / group_size);
+    return launch_q8_quantize(c, x, (int)n, group_size, q, s);
+}
+
+int rama_q8_matmul(rama_ctx* c, float* o, const int8_t* wq, const float* ws, const int8_t* xq, const float* xs, size_t n, size_t d, int group_size) {
+    RAMA_ENTER(c);
+    REQUIRE(c && o && wq && ws && xq && xs, RAMA_EINVAL, "q8_matmul: NULL argument");
+    REQUIRE(group_size > 0 && n > 0 && d > 0 && n % (size_t)group_size == 0 && n < ((size_t)1 << 31) && d < ((size_t)1 << 31), RAMA_EINVAL,
+            "q8_matmul: group_size must divide n");
+    if (set_device(c)) return 1;
+    RAMA_WRITES(c, o, d);
+    Q8MatParams p{};
+    p.w[0] = wq; p.ws[0] = ws; p.o[0] = o; p.xq = xq; p.xs = xs; p.K = (int)n; p.rows = (int)d; p.gs = group_size; p.nmat = 1;
+    return launch_q8_matvec<Q8EPI_STORE>(c, p);
+}
+
+static int q8_check(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const rama_run_state* s) {
+    REQUIRE(c, RAMA_EINVAL, "ctx is NULL");
+    int rc = check_cfg(cfg); if (rc) return rc;
+    REQUIRE(w && s, RAMA_EINVAL, "q8 forward: NULL argument");
+    const int gs = w->group_size;
+    REQUIRE(gs > 0 && cfg->dim % gs == 0 && cfg->hidden_dim % gs == 0, RAMA_EINVAL, "q8 forward: group_size must divide dim and hidden_dim");
+    REQUIRE(w->token_embedding_table && w->rms_att_weight && w->rms_ffn_weight && w->rms_final_weight && w->freq_cis_real && w->freq_cis_imag &&
+            w->wq && w->wk && w->wv && w->wo && w->w1 && w->w2 && w->w3 && w->wcls && w->wq_s && w->wk_s && w->wv_s && w->wo_s && w->w1_s &&
+            w->w2_s && w->w3_s && w->wcls_s, RAMA_EINVAL, "q8 forward: missing weights");
+    REQUIRE(s->x && s->xb && s->hb && s->q && s->k && s->v && s->att && s->logits && s->key_cache && s->value_cache, RAMA_EINVAL,
+            "q8 forward: missing state buffer");
+    return 0;
+}
+
+// the int8 activations: one buffer of max(dim, hidden) values and as many scales (sized here, never inside a capture)
+static int ensure_q8_scratch(rama_ctx* c, const rama_config* cfg) {
+    const size_t need = (size_t)std::max(cfg->dim, cfg->hidden_dim);
+    if (need <= c->q8_cap) return 0;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    REQUIRE(hipStreamIsCapturing(c->stream, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone, RAMA_EINVAL,
+            "q8: the activation scratch is sized by the first call, which must not be captured");
+    HIPCHK(hipStreamSynchronize(c->stream));
+    drop_q8_graphs(c, nullptr);        // (they hold the scratch's addresses; nothing else reads it)
+    if (c->q8_xq) { HIPCHK(hipFree(c->q8_xq)); c->q8_xq = nullptr; }
+    if (c->q8_xs) { HIPCHK(hipFree(c->q8_xs)); c->q8_xs = nullptr; }
+    c->q8_cap = 0;
+    HIPCHK(hipMalloc(&c->q8_xq, (need + 15) / 16 * 16));
+    HIPCHK(hipMalloc(&c->q8_xs, need * sizeof(float)));
+    c->q8_cap = need;
+    return 0;
+}
+
+// the attention variant of a Q8 step: parity mode's exact attention, 16 waves per head from position 256, spread over the chip from "spread_pos"
+static int q8_variant(rama_ctx* c, int pos) {
+    c->long_attn = pos >= kLongAttnPos;
+    c->spread_attn = pos >= c->tune_spread_pos;
+    return c->spread_attn ? 2 : (c->long_attn ? 1 : 0);
+}
+
+static int q8_norm(rama_ctx* c, float* o, float* x, const float* gain, int n, float* copy_to) {
+    KTimer kt(c, RAMA_K_NORM);
+    if (rmsnorm_chain_ok(n)) return launch_rmsnorm_chain(c, o, x, gain, n, copy_to);
+    if (copy_to) {      // xb = x; x = rmsnorm(xb) (infer.rs:49-50)
+        hipLaunchKernelGGL(copy_kernel, dim3(ew_grid(n)), dim3(256), 0, c->stream, copy_to, (const float*)x, (size_t)n);
+        LAUNCHCHK();
+        return launch_rmsnorm_ref(c, o, copy_to, gain, n);
+    }
+    return launch_rmsnorm_ref(c, o, x, gain, n);
+}
+
+// one forward (token and position in the device cursor); embed = 0: x already holds the token's embedding (chained decode)
+static int enqueue_q8_stage(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, rama_run_state* s, bool embed) {
+    const int dim = cfg->dim, hidden = cfg->hidden_dim, hs = dim / cfg->n_heads, gs = w->group_size;
+    const size_t dd = (size_t)dim * dim, hd = (size_t)hidden * dim;
+    int8_t* xq = c->q8_xq; float* xs = c->q8_xs;
+    int rc;
+    if (embed) {
+        hipLaunchKernelGGL(embed_kernel, dim3((dim + 255) / 256), dim3(256), 0, c->stream, s->x, w->token_embedding_table, (const Ctl*)c->ctl, 0, dim);
+        LAUNCHCHK();
+    }
+    for (int l = 0; l < cfg->n_layers; l++) {
+        float* kc = s->key_cache + (size_t)l * cfg->seq_len * dim;
+        float* vc = s->value_cache + (size_t)l * cfg->seq_len * dim;
+        rc = q8_norm(c, s->xb, s->x, w->rms_att_weight + (size_t)l * dim, dim, nullptr); if (rc) return rc;          // infer.rs:19
+        rc = launch_q8_quantize(c, s->xb, dim, gs, xq, xs); if (rc) return rc;
+        {   // :20-23
+            KTimer kt(c, RAMA_K_QKV);
+            Q8MatParams p{};
+            p.w[0] = w->wq + l * dd; p.w[1] = w->wk + l * dd; p.w[2] = w->wv + l * dd;
+            p.ws[0] = w->wq_s + l * dd / gs; p.ws[1] = w->wk_s + l * dd / gs; p.ws[2] = w->wv_s + l * dd / gs;
+            p.o[0] = s->q; p.o[1] = s->k; p.o[2] = s->v;
+            p.xq = xq; p.xs = xs; p.K = dim; p.rows = dim; p.gs = gs; p.nmat = 3;
+            rc = launch_q8_matvec<Q8EPI_STORE>(c, p); if (rc) return rc;
+        }
+        hipLaunchKernelGGL(rope_ref_cursor_kernel, dim3((dim / 2 + 255) / 256), dim3(256), 0, c->stream, s->q, s->k, (const float*)s->v,
+                           w->freq_cis_real, w->freq_cis_imag, dim, hs, kc, vc, (const Ctl*)c->ctl);                  // :25-33
+        LAUNCHCHK();
+        {   // :34
+            KTimer kt(c, RAMA_K_ATTN);
+            if (attn_chain_ok(hs, cfg->seq_len))
+                rc = launch_attention_chain(c, s->xb, s->att, s->q, kc, vc, c->ctl, 0, dim, hs, cfg->seq_len, cfg->n_heads, c->long_attn, c->spread_attn);
+            else rc = launch_attention_ref(c, s->xb, s->att, s->q, kc, vc, c->ctl, 0, dim, hs, cfg->seq_len, cfg->n_heads);
+            if (rc) return rc;
+        }
+        rc = launch_q8_quantize(c, s->xb, dim, gs, xq, xs); if (rc) return rc;
+        {   // :35-37: x = x + Wo . xb
+            KTimer kt(c, RAMA_K_WO);
+            Q8MatParams p{};
+            p.w[0] = w->wo + l * dd; p.ws[0] = w->wo_s + l * dd / gs; p.o[0] = s->x;
+            p.xq = xq; p.xs = xs; p.K = dim; p.rows = dim; p.gs = gs; p.nmat = 1;
+            rc = launch_q8_matvec<Q8EPI_RESID>(c, p); if (rc) return rc;
+        }
+        rc = q8_norm(c, s->xb, s->x, w->rms_ffn_weight + (size_t)l * dim, dim, nullptr); if (rc) return rc;          // :39
+        rc = launch_q8_quantize(c, s->xb, dim, gs, xq, xs); if (rc) return rc;
+        {   // :41-45: hb = sinu(W1 . xb) * (W3 . xb)
+            KTimer kt(c, RAMA_K_W13);
+            Q8MatParams p{};
+            p.w[0] = w->w1 + l * hd; p.w[1] = w->w3 + l * hd; p.ws[0] = w->w1_s + l * hd / gs; p.ws[1] = w->w3_s + l * hd / gs;
+            p.o[0] = s->hb; p.xq = xq; p.xs = xs; p.K = dim; p.rows = hidden; p.gs = gs; p.nmat = 2;
+            rc = launch_q8_matvec<Q8EPI_SWIGLU>(c, p); if (rc) return rc;
+        }
+        rc = launch_q8_quantize(c, s->hb, hidden, gs, xq, xs); if (rc) return rc;
+        {   // :46-47: x = x + W2 . hb
+            KTimer kt(c, RAMA_K_W2);
+            Q8MatParams p{};
+            p.w[0] = w->w2 + l * hd; p.ws[0] = w->w2_s + l * hd / gs; p.o[0] = s->x;
+            p.xq = xq; p.xs = xs; p.K = hidden; p.rows = dim; p.gs = gs; p.nmat = 1;
+            rc = launch_q8_matvec<Q8EPI_RESID>(c, p); if (rc) return rc;
+        }
+    }
+    // :49-51: xb = x; x = rmsnorm(xb); logits = Wcls . x
+    rc = q8_norm(c, s->x, s->x, w->rms_final_weight, dim, s->xb); if (rc) return rc;
+    rc = launch_q8_quantize(c, s->x, dim, gs, xq, xs); if (rc) return rc;
+    KTimer kt(c, RAMA_K_CLS);
+    Q8MatParams p{};
+    p.w[0] = w->wcls; p.ws[0] = w->wcls_s; p.o[0] = s->logits;
+    p.xq = xq; p.xs = xs; p.K = dim; p.rows = cfg->vocab_size; p.gs = gs; p.nmat = 1;
+    return launch_q8_matvec<Q8EPI_STORE>(c, p);
+}
+
+// a chained step: the layers, then Device::sample (cursor advance, next token's embedding gather from the fp32 table)
+static int enqueue_q8_step(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, rama_run_state* s) {
+    int rc = enqueue_q8_stage(c, cfg, w, s, false);
+    if (rc) return rc;
+    ArgmaxParams ap{};
+    ap.logits = s->logits; ap.n = cfg->vocab_size;
+    ap.ctl = c->ctl; ap.forced = c->forced; ap.out = c->out; ap.out_cap = c->out_cap; ap.ring = c->ring_dev;
+    ap.emb = w->token_embedding_table; ap.x = s->x; ap.dim = cfg->dim;
+    return enqueue_sample(c, ap, c->samp_T, c->samp_topp, c->samp_u);
+}
+
+// eager, or replayed from the context's Q8 graph for (config, weights, state, attention variant, kind)
+static int run_q8(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, rama_run_state* s, int variant, int chained) {
+    auto enqueue = [&]() { return chained ? enqueue_q8_step(c, cfg, w, s) : enqueue_q8_stage(c, cfg, w, s, true); };
+    if (!c->graph_mode || c->kp.kernel_id >= 0) return enqueue();
+    rama_ctx::Q8Graph* hit = nullptr;
+    for (auto& e : c->q8g)
+        if (e.variant == variant && e.chained == chained && !memcmp(&e.cfg, cfg, sizeof *cfg) && !memcmp(&e.w, w, sizeof *w) && !memcmp(&e.s, s, sizeof *s)) { hit = &e; break; }
+    if (!hit) {
+        if (c->q8g.size() >= 16) {
+            HIPCHK(hipStreamSynchronize(c->stream));
+            for (auto& e : c->q8g) { if (e.exec) hipGraphExecDestroy(e.exec); if (e.graph) hipGraphDestroy(e.graph); }
+            c->q8g.clear();
+        }
+        rama_ctx::Q8Graph e;
+        HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+        const int rc = enqueue();
+        const hipError_t err = hipStreamEndCapture(c->stream, &e.graph);
+        if (rc) { if (e.graph) hipGraphDestroy(e.graph); return rc; }
+        HIPCHK(err);
+        HIPCHK(hipGraphInstantiate(&e.exec, e.graph, nullptr, nullptr, 0));
+        e.cfg = *cfg; e.w = *w; e.s = *s; e.variant = variant; e.chained = chained;
+        c->q8g.push_back(e);
+        hit = &c->q8g.back();
+    }
+    HIPCHK(hipGraphLaunch(hit->exec, c->stream));
+    return 0;
+}
+
+int rama_q8_forward(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, rama_run_state* s, int token, int pos) {
+    RAMA_ENTER(c);
+    int rc = q8_check(c, cfg, w, s); if (rc) return rc;
+    if (set_device(c)) return 1;
+    REQUIRE(pos >= 0 && pos < cfg->seq_len, RAMA_EINVAL, "q8_forward: pos outside [0, seq_len)");
+    REQUIRE(token >= 0 && token < cfg->vocab_size, RAMA_EINVAL, "q8_forward: token outside the vocabulary");
+    rc = ensure_q8_scratch(c, cfg); if (rc) return rc;
+    hipLaunchKernelGGL(set_ctl_kernel, dim3(1), dim3(1), 0, c->stream, c->ctl, token, pos, 0, 0);
+    LAUNCHCHK();
+    c->embedded_x = nullptr;
+    c->host_pos = -1;
+    return run_q8(c, cfg, w, s, q8_variant(c, pos), 0);
+}
+
+int rama_q8_generate(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, rama_run_state* s, const int32_t* prompt_host, int n_prompt,
+                     int steps, float temperature, float topp, float u, int32_t* out_host) {
+    RAMA_ENTER(c);
+    int rc = q8_check(c, cfg, w, s); if (rc) return rc;
+    REQUIRE(out_host, RAMA_EINVAL, "q8_generate: NULL argument");
+    if (set_device(c)) return 1;
+    rc = rama_decode_sampler(c, temperature, topp, u); if (rc) return rc;
+    REQUIRE(steps >= 0 && steps <= cfg->seq_len && steps <= c->out_cap, RAMA_EINVAL, "q8_generate: steps outside [0, seq_len]");
+    REQUIRE(n_prompt >= 0 && (n_prompt == 0 || prompt_host) && n_prompt <= c->forced_cap, RAMA_EINVAL, "q8_generate: bad prompt");
+    for (int i = 0; i < n_prompt; i++) REQUIRE(prompt_host[i] >= 0 && prompt_host[i] < cfg->vocab_size, RAMA_EINVAL, "q8_generate: prompt token outside the vocabulary");
+    rc = ensure_q8_scratch(c, cfg); if (rc) return rc;
+    if (c->samp_T != 0.0f) { rc = ensure_topp_scratch(c, cfg->vocab_size); if (rc) return rc; c->topp_dist_dirty = true; }
+    rc = rama_decode_begin(c, /*BOS*/ 1, 0, prompt_host, n_prompt); if (rc) return rc;
+    if (steps == 0) { int n = 0; return rama_decode_tokens(c, out_host, 0, &n); }
+    hipLaunchKernelGGL(embed_kernel, dim3((cfg->dim + 255) / 256), dim3(256), 0, c->stream, s->x, w->token_embedding_table, (const Ctl*)c->ctl, 0, cfg->dim);
+    LAUNCHCHK();
+    for (int i = 0; i < steps; i++) {
+        rc = run_q8(c, cfg, w, s, q8_variant(c, c->host_pos), 1);
+        if (rc) return rc;
+        c->host_pos++;
+    }
+    c->embedded_x = nullptr;
+    c->ring_hi = std::min(c->out_cap, c->ring_hi + steps);
+    int n = 0;
+    return rama_decode_tokens(c, out_host, steps, &n);
 }
