@@ -455,6 +455,21 @@ int  rama_q8_forward(rama_ctx *ctx, const rama_config *cfg, const rama_q8_weight
 int  rama_q8_generate(rama_ctx *ctx, const rama_config *cfg, const rama_q8_weights *w, rama_run_state *s,
                       const int32_t *prompt_tokens_host, int n_prompt, int steps, float temperature, float topp, float u,
                       int32_t *out_tokens_host);
+/* Q8 token batches: every weight pass is shared by up to 128 tokens (int8 matrix cores at group sizes 32 and multiples of
+ * 64, a bytewise kernel otherwise).  The scratch belongs to the context and is sized by the first call (outside any capture);
+ * these calls run eagerly in either graph mode.
+ * o[t * d + i] = row i of matmul(xq[t], wq) for n_tok token rows: xq [n_tok, n], xs [n_tok, n / group_size]; bit for bit
+ * n_tok calls of rama_q8_matmul */
+int  rama_q8_matmul_batch(rama_ctx *ctx, float *o, const int8_t *wq, const float *ws, const int8_t *xq, const float *xs,
+                          size_t n, size_t d, int group_size, int n_tok);
+/* the state n_tokens calls rama_q8_forward(tokens[i], pos0 + i) leave: cache rows pos0 .. pos0 + n - 1 of every layer,
+ * x and logits of the last position, bit for bit (the last position runs as rama_q8_forward) */
+int  rama_q8_prefill(rama_ctx *ctx, const rama_config *cfg, const rama_q8_weights *w, rama_run_state *s,
+                     const int32_t *tokens_host, int n_tokens, int pos0);
+/* one step of 1..128 independent sequences sharing every weight pass; states[i] afterwards holds what
+ * rama_q8_forward(tokens[i], positions[i]) would leave in its cache rows and logits (x / xb / q ... not maintained) */
+int  rama_q8_decode_batch(rama_ctx *ctx, const rama_config *cfg, const rama_q8_weights *w, const rama_run_state *states,
+                          const int32_t *tokens_host, const int32_t *positions_host, int n_seq);
 
 /* ---------------------------------------------------------------- measurement
  * HIP events on the context's stream (the stream the kernels are launched on). */

@@ -185,6 +185,12 @@ extern "C" {
     pub fn rama_q8_generate(ctx: *mut rama_ctx, cfg: *const rama_config, w: *const rama_q8_weights, s: *mut rama_run_state,
                             prompt_tokens_host: *const i32, n_prompt: c_int, steps: c_int, temperature: f32, topp: f32, u: f32,
                             out_tokens_host: *mut i32) -> c_int;
+    pub fn rama_q8_matmul_batch(ctx: *mut rama_ctx, o: *mut f32, wq: *const i8, ws: *const f32, xq: *const i8, xs: *const f32,
+                                n: usize, d: usize, group_size: c_int, n_tok: c_int) -> c_int;
+    pub fn rama_q8_prefill(ctx: *mut rama_ctx, cfg: *const rama_config, w: *const rama_q8_weights, s: *mut rama_run_state,
+                           tokens_host: *const i32, n_tokens: c_int, pos0: c_int) -> c_int;
+    pub fn rama_q8_decode_batch(ctx: *mut rama_ctx, cfg: *const rama_config, w: *const rama_q8_weights, states: *const rama_run_state,
+                                tokens_host: *const i32, positions_host: *const i32, n_seq: c_int) -> c_int;
 }
 
 #[repr(C)] pub struct rama_pipe { _p: [u8; 0] }

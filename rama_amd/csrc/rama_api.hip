@@ -11,6 +11,7 @@
 #include "chain.hpp"
 #include "topp_pick.hpp"
 #include "q8.hpp"
+#include "q8_batch.hpp"
 
 #include <hip/hip_ext.h>   // hipExtLaunchKernelGGL: start/stop events carried by the dispatch itself
 
@@ -168,6 +169,9 @@ struct rama_ctx {
     int8_t* q8_xq = nullptr; float* q8_xs = nullptr; size_t q8_cap = 0;
     struct Q8Graph { hipGraphExec_t exec = nullptr; hipGraph_t graph = nullptr; rama_config cfg{}; rama_q8_weights w{}; rama_run_state s{}; int variant = 0; int chained = 0; };
     std::vector<Q8Graph> q8g;
+    // Q8 token batches (rama_q8_prefill / rama_q8_decode_batch): row-major scratch for kQ8bMaxTok tokens, sized by the first call
+    // (never inside a capture; no graph holds it), see Q8BatchScratch
+    char* q8b_blob = nullptr; size_t q8b_cap = 0;
     int tune_split_pos = -1;               // attention runs split-T (+ combine launch) from this position on; -1 = by model size
     int tune_resid_r2 = 2;                 // Wo / W2 under geometry 3: 0 = 4-row workgroups, 1 = 2 rows x 8 waves (+0.45 %),
                                            // 2 = additionally 16 waves for rows wider than 8192 floats (W2: +1.15 % more), 3 = 16 waves x 4 chunks
@@ -421,7 +425,7 @@ int rama_ctx_destroy(rama_ctx* c) {
     hipFree(c->bc.rows); hipFree(c->bc.forced);
     hipFree(c->tb.keys); hipFree(c->tb.vals); hipFree(c->tb.bp); hipFree(c->tb.bi); hipFree(c->tb.rk); hipFree(c->tb.bm);
     hipFree(c->tb.bcount); hipFree(c->tb.stats); hipFree(c->tb.m); hipFree(c->tb.rows_dev);
-    hipFree(c->q8_xq); hipFree(c->q8_xs);
+    hipFree(c->q8_xq); hipFree(c->q8_xs); hipFree(c->q8b_blob);
     hipHostFree(c->pinned_int); hipHostFree(c->pinned_tok);
     hipEventDestroy(c->t0); hipEventDestroy(c->t1);
     if (c->own_stream) hipStreamDestroy(c->stream);
@@ -2267,6 +2271,17 @@ static int launch_gemm_chain(rama_ctx* c, GemmChainParams& p) {
 }
 constexpr int kGcMaxTok = 8 * kGcWaves;
 
+// parity mode's exact attention for a token batch: one workgroup of nw waves per (head, token) -- the RefAttnParams carry
+// tok_stride / att_stride and either p.pos_val + token or the sequence table
+static int launch_attention_chain_tokens(rama_ctx* c, const RefAttnParams& a, int n_heads, int nt, int nw, size_t lds) {
+    const dim3 grid(n_heads, nt);
+    if (nw == 4) hipLaunchKernelGGL((attention_chain_kernel<4>), grid, dim3(4 * 64), lds, c->stream, a);
+    else if (nw == 8) hipLaunchKernelGGL((attention_chain_kernel<8>), grid, dim3(8 * 64), lds, c->stream, a);
+    else hipLaunchKernelGGL((attention_chain_kernel<16>), grid, dim3(16 * 64), lds, c->stream, a);
+    LAUNCHCHK();
+    return 0;
+}
+
 // the layers of one pass of nt <= 16 tokens whose residual rows sit in b.X: consecutive positions p0.. of one sequence
 // (key_cache / value_cache its cache bases), or -- seqs != NULL -- token t of independent sequence t (device table)
 struct ChainBatch { float *X, *XN, *Q, *XB, *HB, *ATT; const float *cq, *ck, *cv, *co, *c13, *c2; int nw; size_t att_lds; };
@@ -2293,11 +2308,7 @@ static int chain_batch_layers(rama_ctx* c, const rama_config* cfg, const rama_we
             a.q = b.Q; a.kc = kc; a.vc = vc; a.att = b.ATT; a.xb = b.XB; a.ctl = nullptr; a.pos_val = p0;
             a.dim = dim; a.head_size = hs; a.seq_len = seq; a.tok_stride = dim; a.att_stride = H * seq;
             a.seqs = seqs; a.layer_off = layer_off;
-            const dim3 grid(H, nt);
-            if (b.nw == 4) hipLaunchKernelGGL((attention_chain_kernel<4>), grid, dim3(4 * 64), b.att_lds, c->stream, a);
-            else if (b.nw == 8) hipLaunchKernelGGL((attention_chain_kernel<8>), grid, dim3(8 * 64), b.att_lds, c->stream, a);
-            else hipLaunchKernelGGL((attention_chain_kernel<16>), grid, dim3(16 * 64), b.att_lds, c->stream, a);
-            LAUNCHCHK();
+            rc = launch_attention_chain_tokens(c, a, H, nt, b.nw, b.att_lds); if (rc) return rc;
         }
         {   // :35-37
             GemmChainParams p{};
@@ -3657,4 +3668,240 @@ int rama_q8_generate(rama_ctx* c, const rama_config* cfg, const rama_q8_weights*
     c->ring_hi = std::min(c->out_cap, c->ring_hi + steps);
     int n = 0;
     return rama_decode_tokens(c, out_host, steps, &n);
+}
+
+// ---------------------------------------------------------------- Q8_0 token batches (q8_batch.hpp)
+// rama_q8_prefill and rama_q8_decode_batch: enqueue_q8_stage over up to kQ8bMaxTok tokens per weight pass.  The batched exact
+// norm, the quantizer over T rows (a group never straddles a row), the batched product, RoPE + cache rows per token and parity
+// mode's attention on a (heads, tokens) grid: every token's bits are those of its own rama_q8_forward.
+
+template <int EPI>
+static int launch_q8_gemm(rama_ctx* c, const Q8BatchParams& p) {
+    const int nm = EPI == Q8EPI_SWIGLU ? 2 : p.nmat;
+    bool mf = q8_gemm_mfma_ok(p.K, p.gs) && aligned16(p.xq);
+    for (int m = 0; m < nm; m++) mf = mf && aligned16(p.w[m]);
+    const int G = p.K / p.gs;
+    const int total = EPI == Q8EPI_SWIGLU ? p.rows : p.nmat * p.rows;
+    const int tiles = (p.rows + 15) / 16, tasks = EPI == Q8EPI_SWIGLU ? tiles : p.nmat * tiles;
+    for (int t0 = 0; t0 < p.n_tok; t0 += kQ8bMaxTok) {
+        Q8BatchParams q = p;
+        q.n_tok = std::min(kQ8bMaxTok, p.n_tok - t0);
+        q.xq = p.xq + (size_t)t0 * p.K; q.xs = p.xs + (size_t)t0 * G;
+        for (int m = 0; m < 3; m++) if (q.o[m]) q.o[m] = p.o[m] + (size_t)t0 * p.ostride;
+        if (mf && q.n_tok <= 32 && (q.gs == 32 || q.gs == 64)) {      // few tokens: K split over the waves of a workgroup
+            constexpr int RT = EPI == Q8EPI_SWIGLU ? 2 : 1;
+#define RAMA_Q8S(NT_, G32_) RAMA_LAUNCH(c, (q8_gemm_ksplit_kernel<NT_, EPI, G32_>), dim3(tasks), dim3(kQ8sWaves * 64), q8s_lds_bytes(NT_, RT, G32_), q)
+            if (q.n_tok <= 16) { if (q.gs == 32) RAMA_Q8S(1, true); else RAMA_Q8S(1, false); }
+            else { if (q.gs == 32) RAMA_Q8S(2, true); else RAMA_Q8S(2, false); }
+#undef RAMA_Q8S
+        } else if (mf) {
+            const dim3 grid((tasks + kQ8bWaves - 1) / kQ8bWaves), block(kQ8bWaves * 64);
+#define RAMA_Q8G(NT_) do { if (q.gs == 32) RAMA_LAUNCH(c, (q8_gemm_mfma_kernel<NT_, EPI, true>), grid, block, 0, q); \
+                           else RAMA_LAUNCH(c, (q8_gemm_mfma_kernel<NT_, EPI, false>), grid, block, 0, q); } while (0)
+            if (q.n_tok <= 16) RAMA_Q8G(1);
+            else if (q.n_tok <= 32) RAMA_Q8G(2);
+            else if (q.n_tok <= 64) RAMA_Q8G(4);
+            else RAMA_Q8G(8);
+#undef RAMA_Q8G
+        } else {
+            RAMA_LAUNCH(c, (q8_gemm_generic_kernel<EPI>), dim3((total + 255) / 256, q.n_tok), dim3(256), 0, q);
+        }
+        LAUNCHCHK();
+    }
+    return 0;
+}
+
+int rama_q8_matmul_batch(rama_ctx* c, float* o, const int8_t* wq, const float* ws, const int8_t* xq, const float* xs, size_t n, size_t d,
+                         int group_size, int n_tok) {
+    RAMA_ENTER(c);
+    REQUIRE(c && o && wq && ws && xq && xs, RAMA_EINVAL, "q8_matmul_batch: NULL argument");
+    REQUIRE(group_size > 0 && n > 0 && d > 0 && n % (size_t)group_size == 0 && n < ((size_t)1 << 31) && d < ((size_t)1 << 31), RAMA_EINVAL,
+            "q8_matmul_batch: group_size must divide n");
+    REQUIRE(n_tok >= 1, RAMA_EINVAL, "q8_matmul_batch: n_tok < 1");
+    if (set_device(c)) return 1;
+    RAMA_WRITES(c, o, d * (size_t)n_tok);
+    Q8BatchParams p{};
+    p.w[0] = wq; p.ws[0] = ws; p.o[0] = o; p.xq = xq; p.xs = xs;
+    p.K = (int)n; p.rows = (int)d; p.gs = group_size; p.nmat = 1; p.n_tok = n_tok; p.ostride = (int)d;
+    return launch_q8_gemm<Q8EPI_STORE>(c, p);
+}
+
+// the batch path's scratch, row-major per token (T = kQ8bMaxTok): X residual rows, XN their norms, Q / Kr / V, XB attention
+// output, HB, ATT score rows [T][n_heads][seq_len], LG logits [T][vocab]; the int8 activations [T][max(dim, hidden)] and their
+// scales; token ids; the sequence table
+struct Q8BatchScratch { float *X, *XN, *Q, *Kr, *V, *XB, *HB, *ATT, *LG; int8_t* xq; float* xs; int* toks; SeqSlot* seqs; int nw; size_t att_lds; };
+
+// the shapes the batch path takes: those whose single-token forward runs parity mode's chain norm and chain attention
+static bool q8_batch_ok(const rama_config* cfg) {
+    const int hs = cfg->dim / cfg->n_heads;
+    if (!rmsnorm_chain_ok((size_t)cfg->dim) || !attn_chain_ok(hs, cfg->seq_len) || cfg->dim % 4) return false;
+    return attn_chain_lds_floats(hs, cfg->seq_len, attn_chain_waves(hs, false)) * sizeof(float) + 16 <= kAttnChainMaxLds;
+}
+
+static int ensure_q8_batch_scratch(rama_ctx* c, const rama_config* cfg, int gs, Q8BatchScratch* b) {
+    const size_t T = kQ8bMaxTok, dim = (size_t)cfg->dim, hidden = (size_t)cfg->hidden_dim, mx = std::max(dim, hidden);
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    const size_t sz[13] = {T * dim * 4, T * dim * 4, T * dim * 4, T * dim * 4, T * dim * 4, T * dim * 4, T * hidden * 4,
+                           T * (size_t)cfg->n_heads * cfg->seq_len * 4, T * (size_t)cfg->vocab_size * 4, T * mx, T * (mx / gs) * 4, T * sizeof(int),
+                           T * sizeof(SeqSlot)};
+    size_t off[13], need = 0;
+    for (int i = 0; i < 13; i++) { off[i] = need; need += up(sz[i]); }
+    if (need > c->q8b_cap) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        REQUIRE(hipStreamIsCapturing(c->stream, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone, RAMA_EINVAL,
+                "q8 batch: the scratch is sized by the first call, which must not be captured");
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (c->q8b_blob) { HIPCHK(hipFree(c->q8b_blob)); c->q8b_blob = nullptr; }
+        c->q8b_cap = 0;
+        HIPCHK(hipMalloc(&c->q8b_blob, need));
+        c->q8b_cap = need;
+    }
+    char* base = c->q8b_blob;
+    float** f[9] = {&b->X, &b->XN, &b->Q, &b->Kr, &b->V, &b->XB, &b->HB, &b->ATT, &b->LG};
+    for (int i = 0; i < 9; i++) *f[i] = reinterpret_cast<float*>(base + off[i]);
+    b->xq = reinterpret_cast<int8_t*>(base + off[9]);
+    b->xs = reinterpret_cast<float*>(base + off[10]);
+    b->toks = reinterpret_cast<int*>(base + off[11]);
+    b->seqs = reinterpret_cast<SeqSlot*>(base + off[12]);
+    const int hs = cfg->dim / cfg->n_heads;
+    b->nw = attn_chain_waves(hs, false);
+    b->att_lds = attn_chain_lds_floats(hs, cfg->seq_len, b->nw) * sizeof(float) + 16;
+    return 0;
+}
+
+// the layers for nt tokens whose embeddings sit in b.X: consecutive positions p0.. of one sequence (key_cache / value_cache
+// its caches), or -- seqs != NULL -- token t of independent sequence t (device table)
+static int q8_batch_layers(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const Q8BatchScratch& b, int nt, int p0,
+                           float* key_cache, float* value_cache, const SeqSlot* seqs) {
+    const int dim = cfg->dim, hidden = cfg->hidden_dim, hs = dim / cfg->n_heads, H = cfg->n_heads, seq = cfg->seq_len, gs = w->group_size;
+    const size_t dd = (size_t)dim * dim, hd = (size_t)hidden * dim;
+    int rc;
+    for (int l = 0; l < cfg->n_layers; l++) {
+        const size_t layer_off = (size_t)l * seq * dim;
+        float* kc = key_cache ? key_cache + layer_off : nullptr;
+        float* vc = value_cache ? value_cache + layer_off : nullptr;
+        rc = launch_rmsnorm_chain(c, b.XN, b.X, w->rms_att_weight + (size_t)l * dim, dim, nullptr, nt, dim); if (rc) return rc;    // infer.rs:19
+        rc = launch_q8_quantize(c, b.XN, nt * dim, gs, b.xq, b.xs); if (rc) return rc;
+        {   // :20-23
+            Q8BatchParams p{};
+            p.w[0] = w->wq + l * dd; p.w[1] = w->wk + l * dd; p.w[2] = w->wv + l * dd;
+            p.ws[0] = w->wq_s + l * dd / gs; p.ws[1] = w->wk_s + l * dd / gs; p.ws[2] = w->wv_s + l * dd / gs;
+            p.o[0] = b.Q; p.o[1] = b.Kr; p.o[2] = b.V;
+            p.xq = b.xq; p.xs = b.xs; p.K = dim; p.rows = dim; p.gs = gs; p.nmat = 3; p.n_tok = nt; p.ostride = dim;
+            rc = launch_q8_gemm<Q8EPI_STORE>(c, p); if (rc) return rc;
+        }
+        hipLaunchKernelGGL(q8_rope_batch_kernel, dim3((dim / 2 + 255) / 256, nt), dim3(256), 0, c->stream, b.Q, b.Kr, (const float*)b.V,
+                           w->freq_cis_real, w->freq_cis_imag, dim, hs, kc, vc, p0, seqs, layer_off);                    // :25-33
+        LAUNCHCHK();
+        {   // :34, one workgroup per (head, token)
+            RefAttnParams a{};
+            a.q = b.Q; a.kc = kc; a.vc = vc; a.att = b.ATT; a.xb = b.XB; a.ctl = nullptr; a.pos_val = p0;
+            a.dim = dim; a.head_size = hs; a.seq_len = seq; a.tok_stride = dim; a.att_stride = H * seq;
+            a.seqs = seqs; a.layer_off = layer_off;
+            rc = launch_attention_chain_tokens(c, a, H, nt, b.nw, b.att_lds); if (rc) return rc;
+        }
+        rc = launch_q8_quantize(c, b.XB, nt * dim, gs, b.xq, b.xs); if (rc) return rc;
+        {   // :35-37: x = x + Wo . xb
+            Q8BatchParams p{};
+            p.w[0] = w->wo + l * dd; p.ws[0] = w->wo_s + l * dd / gs; p.o[0] = b.X;
+            p.xq = b.xq; p.xs = b.xs; p.K = dim; p.rows = dim; p.gs = gs; p.nmat = 1; p.n_tok = nt; p.ostride = dim;
+            rc = launch_q8_gemm<Q8EPI_RESID>(c, p); if (rc) return rc;
+        }
+        rc = launch_rmsnorm_chain(c, b.XN, b.X, w->rms_ffn_weight + (size_t)l * dim, dim, nullptr, nt, dim); if (rc) return rc;    // :39
+        rc = launch_q8_quantize(c, b.XN, nt * dim, gs, b.xq, b.xs); if (rc) return rc;
+        {   // :41-45: hb = sinu(W1 . xb) * (W3 . xb)
+            Q8BatchParams p{};
+            p.w[0] = w->w1 + l * hd; p.w[1] = w->w3 + l * hd; p.ws[0] = w->w1_s + l * hd / gs; p.ws[1] = w->w3_s + l * hd / gs;
+            p.o[0] = b.HB; p.xq = b.xq; p.xs = b.xs; p.K = dim; p.rows = hidden; p.gs = gs; p.nmat = 2; p.n_tok = nt; p.ostride = hidden;
+            rc = launch_q8_gemm<Q8EPI_SWIGLU>(c, p); if (rc) return rc;
+        }
+        rc = launch_q8_quantize(c, b.HB, nt * hidden, gs, b.xq, b.xs); if (rc) return rc;
+        {   // :46-47: x = x + W2 . hb
+            Q8BatchParams p{};
+            p.w[0] = w->w2 + l * hd; p.ws[0] = w->w2_s + l * hd / gs; p.o[0] = b.X;
+            p.xq = b.xq; p.xs = b.xs; p.K = hidden; p.rows = dim; p.gs = gs; p.nmat = 1; p.n_tok = nt; p.ostride = dim;
+            rc = launch_q8_gemm<Q8EPI_RESID>(c, p); if (rc) return rc;
+        }
+    }
+    return 0;
+}
+
+int rama_q8_prefill(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, rama_run_state* s, const int32_t* tokens_host, int n_tokens, int pos0) {
+    RAMA_ENTER(c);
+    REQUIRE(c && tokens_host, RAMA_EINVAL, "q8_prefill: NULL argument");
+    int rc = q8_check(c, cfg, w, s); if (rc) return rc;
+    REQUIRE(n_tokens >= 1 && pos0 >= 0 && pos0 <= cfg->seq_len - n_tokens, RAMA_EINVAL, "q8_prefill: positions outside [0, seq_len)");
+    for (int i = 0; i < n_tokens; i++) REQUIRE(tokens_host[i] >= 0 && tokens_host[i] < cfg->vocab_size, RAMA_EINVAL, "q8_prefill: token outside the vocabulary");
+    if (set_device(c)) return 1;
+    rc = ensure_q8_scratch(c, cfg); if (rc) return rc;
+    // the last position runs as rama_q8_forward (x and logits); a batched pass of one token costs more than a forward (4.7 against
+    // 3.8 ms at llama2-7B), so batches start at two tokens
+    const int n_batch = q8_batch_ok(cfg) && n_tokens >= 3 ? n_tokens - 1 : 0;
+    if (n_batch > 0) {
+        Q8BatchScratch b{};
+        rc = ensure_q8_batch_scratch(c, cfg, w->group_size, &b); if (rc) return rc;
+        c->embedded_x = nullptr; c->host_pos = -1;
+        for (int c0 = 0; c0 < n_batch; c0 += kQ8bMaxTok) {
+            const int nt = std::min(kQ8bMaxTok, n_batch - c0);
+            HIPCHK(hipStreamSynchronize(c->stream));              // the pinned staging buffer is free again
+            memcpy(c->pinned_tok, tokens_host + c0, sizeof(int) * nt);
+            HIPCHK(hipMemcpyAsync(b.toks, c->pinned_tok, sizeof(int) * nt, hipMemcpyHostToDevice, c->stream));
+            hipLaunchKernelGGL(embed_rows_kernel, dim3((cfg->dim + 255) / 256, nt), dim3(256), 0, c->stream, b.X, w->token_embedding_table,
+                               (const int*)b.toks, nt, cfg->dim);
+            LAUNCHCHK();
+            rc = q8_batch_layers(c, cfg, w, b, nt, pos0 + c0, s->key_cache, s->value_cache, nullptr); if (rc) return rc;
+        }
+    }
+    for (int i = n_batch; i < n_tokens; i++) { rc = rama_q8_forward(c, cfg, w, s, tokens_host[i], pos0 + i); if (rc) return rc; }
+    return 0;
+}
+
+int rama_q8_decode_batch(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const rama_run_state* states,
+                         const int32_t* tokens_host, const int32_t* positions_host, int n_seq) {
+    RAMA_ENTER(c);
+    REQUIRE(c && states && tokens_host && positions_host, RAMA_EINVAL, "q8_decode_batch: NULL argument");
+    REQUIRE(n_seq >= 1 && n_seq <= kQ8bMaxTok, RAMA_EINVAL, "q8_decode_batch: 1..128 sequences per call");
+    for (int i = 0; i < n_seq; i++) {
+        int rc = q8_check(c, cfg, w, &states[i]); if (rc) return rc;
+        REQUIRE(tokens_host[i] >= 0 && tokens_host[i] < cfg->vocab_size, RAMA_EINVAL, "q8_decode_batch: token outside the vocabulary");
+        REQUIRE(positions_host[i] >= 0 && positions_host[i] < cfg->seq_len, RAMA_EINVAL, "q8_decode_batch: position outside [0, seq_len)");
+        for (int j = 0; j < i; j++)
+            REQUIRE(states[j].key_cache != states[i].key_cache && states[j].value_cache != states[i].value_cache && states[j].logits != states[i].logits,
+                    RAMA_EINVAL, "q8_decode_batch: two sequences share a run state");
+    }
+    if (set_device(c)) return 1;
+    int rc = ensure_q8_scratch(c, cfg); if (rc) return rc;
+    if (!q8_batch_ok(cfg) || n_seq == 1) {      // see rama_q8_prefill: one rama_q8_forward per sequence (and for a single one)
+        for (int i = 0; i < n_seq; i++) {
+            rama_run_state si = states[i];
+            rc = rama_q8_forward(c, cfg, w, &si, tokens_host[i], positions_host[i]); if (rc) return rc;
+        }
+        return 0;
+    }
+    const int dim = cfg->dim, V = cfg->vocab_size, gs = w->group_size;
+    Q8BatchScratch b{};
+    rc = ensure_q8_batch_scratch(c, cfg, gs, &b); if (rc) return rc;
+    c->embedded_x = nullptr; c->host_pos = -1;
+    // ids and the sequence table go through pinned staging (the source arrays are the caller's)
+    HIPCHK(hipStreamSynchronize(c->stream));
+    SeqSlot* slots = reinterpret_cast<SeqSlot*>(c->pinned_tok + kMfMaxTok);
+    for (int i = 0; i < n_seq; i++) {
+        c->pinned_tok[i] = tokens_host[i];
+        slots[i].kc = states[i].key_cache; slots[i].vc = states[i].value_cache; slots[i].pos = positions_host[i]; slots[i].pad = 0;
+    }
+    HIPCHK(hipMemcpyAsync(b.toks, c->pinned_tok, sizeof(int) * n_seq, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(b.seqs, slots, sizeof(SeqSlot) * n_seq, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(embed_rows_kernel, dim3((dim + 255) / 256, n_seq), dim3(256), 0, c->stream, b.X, w->token_embedding_table, (const int*)b.toks, n_seq, dim);
+    LAUNCHCHK();
+    rc = q8_batch_layers(c, cfg, w, b, n_seq, 0, nullptr, nullptr, b.seqs); if (rc) return rc;
+    // infer.rs:49-51 per sequence: x = rmsnorm(x), logits = Wcls . x
+    rc = launch_rmsnorm_chain(c, b.XN, b.X, w->rms_final_weight, dim, nullptr, n_seq, dim); if (rc) return rc;
+    rc = launch_q8_quantize(c, b.XN, n_seq * dim, gs, b.xq, b.xs); if (rc) return rc;
+    Q8BatchParams p{};
+    p.w[0] = w->wcls; p.ws[0] = w->wcls_s; p.o[0] = b.LG;
+    p.xq = b.xq; p.xs = b.xs; p.K = dim; p.rows = V; p.gs = gs; p.nmat = 1; p.n_tok = n_seq; p.ostride = V;
+    rc = launch_q8_gemm<Q8EPI_STORE>(c, p); if (rc) return rc;
+    for (int i = 0; i < n_seq; i++)
+        HIPCHK(hipMemcpyAsync(states[i].logits, b.LG + (size_t)i * V, sizeof(float) * V, hipMemcpyDeviceToDevice, c->stream));
+    return 0;
 }

@@ -97,6 +97,19 @@ class Q8Engine:
     def logits(self) -> np.ndarray:
         return self.buffer("logits", self.cfg.vocab_size)
 
+    def prefill(self, tokens, pos0: int = 0):
+        """the prompt positions pos0 .. pos0 + len(tokens) - 1 in shared weight passes (rama_q8_prefill): the caches, x and
+        logits rama_q8_forward would leave after them"""
+        toks = _tokens(tokens, self.cfg.vocab_size, "prefill")
+        if not toks:
+            raise ValueError("prefill: no tokens")
+        pos0 = int(pos0)
+        if pos0 < 0 or pos0 + len(toks) > self.cfg.seq_len:
+            raise ValueError(f"prefill: positions {pos0} .. {pos0 + len(toks) - 1} outside [0, {self.cfg.seq_len})")
+        arr = (C.c_int32 * len(toks))(*toks)
+        check(self.device.lib.rama_q8_prefill(self.device.ctx, C.byref(self.model.ccfg), C.byref(self.model.weights),
+                                              C.byref(self.state), arr, len(toks), pos0), "rama_q8_prefill")
+
     def generate(self, prompt_tokens, steps: int, temperature: float = 0.0, topp: float = 0.9, u: float = TOPP_U_CPU):
         """generate() chained on the device (rama_q8_generate); u defaults to the reference's constant draw"""
         pt = (C.c_int32 * max(len(prompt_tokens), 1))(*prompt_tokens)
@@ -116,3 +129,38 @@ class Q8Engine:
         if self.state.x:        # (rama_state_free drops the Q8 steps captured over this state; the context's graph mode stays)
             check(self.device.lib.rama_state_free(self.device.ctx, C.byref(self.state)))
             self.state = rama_run_state()
+
+
+MAX_BATCH = 128
+
+
+def _tokens(tokens, vocab_size: int, what: str) -> list:
+    out = [int(t) for t in tokens]
+    bad = [t for t in out if not 0 <= t < vocab_size]
+    if bad:
+        raise ValueError(f"{what}: token {bad[0]} outside the vocabulary [0, {vocab_size})")
+    return out
+
+
+def decode_batch(engines, tokens, positions):
+    """one decode step of up to 128 independent sequences over one Q8Model, sharing every weight pass (rama_q8_decode_batch):
+    engines[i]'s caches and logits() become what engines[i].forward(tokens[i], positions[i]) would leave"""
+    engines = list(engines)
+    n = len(engines)
+    if not 1 <= n <= MAX_BATCH:
+        raise ValueError(f"decode_batch: {n} sequences, not 1..{MAX_BATCH}")
+    if len(tokens) != n or len(positions) != n:
+        raise ValueError(f"decode_batch: {len(tokens)} tokens and {len(positions)} positions for {n} sequences")
+    e0 = engines[0]
+    if any(e.model is not e0.model for e in engines):
+        raise ValueError("decode_batch: the engines do not share one Q8Model")
+    if len({id(e) for e in engines}) != n:
+        raise ValueError("decode_batch: an engine appears twice")
+    toks = _tokens(tokens, e0.cfg.vocab_size, "decode_batch")
+    poss = [int(p) for p in positions]
+    bad = [p for p in poss if not 0 <= p < e0.cfg.seq_len]
+    if bad:
+        raise ValueError(f"decode_batch: position {bad[0]} outside [0, {e0.cfg.seq_len})")
+    states = (rama_run_state * n)(*[e.state for e in engines])
+    check(e0.device.lib.rama_q8_decode_batch(e0.device.ctx, C.byref(e0.model.ccfg), C.byref(e0.model.weights), states,
+                                             (C.c_int32 * n)(*toks), (C.c_int32 * n)(*poss), n), "rama_q8_decode_batch")
