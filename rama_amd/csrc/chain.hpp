@@ -434,7 +434,9 @@ __device__ __forceinline__ bool seq_sum_lds_fast_r(const float* a, int n, FastSu
     float v[R];
 #pragma unroll
     for (int k = 0; k < R; k++) { const int i = (int)threadIdx.x * R + k; const float t = a[scan_slot(min(i, n - 1))]; v[k] = i < n ? t : 0.0f; }
-    return seq_sum_fast<NW, R>(v, fs, out);
+    // groups of eight wholly behind the list's end stay off the walk list
+    const int nreal = min(max((n - (int)threadIdx.x * R + 7) >> 3, 0), R / 8);
+    return seq_sum_fast<NW, R>(v, fs, out, nreal);
 }
 template <int NW>
 __device__ __forceinline__ bool seq_sum_lds_fast(const float* a, int n, FastSumShared<NW>& fs, float* out) {

@@ -59,8 +59,12 @@ __device__ __forceinline__ void seq_sum_fast_prepare(FastSumShared<NW>& fs) {
 
 // a[k] = term tid * R + k of the list (terms behind its end: 0.0f -- they change nothing); all NW waves of the workgroup call it, after
 // seq_sum_fast_prepare.  *out = the sequential sum when true is returned (the same value and verdict in every thread).
+// nreal: this thread's groups from nreal on lie wholly behind the list's end (zero padding).  They put nothing on the walk list and leave
+// an open run open: s + 0.0f is s for every s >= +0.  Without it a short list on many threads -- 768 terms on 256 threads of 8 -- whose
+// sum sits exactly on a binade edge (or is zero) makes a SEQ group of each of its 160 padding groups and overflows the list on padding
+// alone.  The default keeps every group (the leader workgroups, whose lists fill their threads).
 template <int NW, int R>
-__device__ __forceinline__ bool seq_sum_fast(const float (&a)[R], FastSumShared<NW>& fs, float* out) {
+__device__ __forceinline__ bool seq_sum_fast(const float (&a)[R], FastSumShared<NW>& fs, float* out, int nreal = R / 8) {
     RAMA_NO_CONTRACT
     static_assert(R % 8 == 0 && R >= 8 && R <= 64, "whole groups of 8 terms, a 32-bit group mask");
     constexpr int G = R / 8;
@@ -119,16 +123,17 @@ __device__ __forceinline__ bool seq_sum_fast(const float (&a)[R], FastSumShared<
             // both ends in binade E with 2^-12 to spare: lob - 2048 keeps the exponent iff the sum is >= 2^E (1 + 2^-12), hib + 2048 iff
             // it is < 2^(E+1) (1 - 2^-13).  (A zero estimate wraps to an exponent of 511: not safe; nan / inf: E = 255.)
             const bool safe = (((lob - 2048u) ^ (hib + 2048u)) >> 23) == 0u && E >= 32 && E <= 253;
-            const bool sp = !safe || tie;
+            const bool real = g < nreal;                           // (false: padding behind the list's end -- nothing below changes)
+            const bool sp = real && (!safe || tie);
             const bool cont = open && !sp && E == eprev;           // this group continues the run in front of it
-            const bool closes_prev = open && !cont;                // ... or ends it (a SEQ group, or a MAP group of another binade)
+            const bool closes_prev = real && open && !cont;        // ... or ends it (a SEQ group, or a MAP group of another binade)
             if (g > 0) { cl |= closes_prev ? (1u << (g - 1)) : 0u; cnt += closes_prev ? 1 : 0; }
             offc[g] = cnt;
             cnt += sp ? 8 : 0;
-            acc = cont ? acc + seg : seg;
-            run[g] = acc; eg[g] = E;
+            acc = real ? (cont ? acc + seg : seg) : acc;
+            run[g] = acc; eg[g] = real ? E : eprev;                // (a run left open in front of the padding closes behind the last group with its own sum and binade)
             m |= sp ? (1u << g) : 0u;
-            open = !sp; eprev = E; P = Phi;
+            open = real ? !sp : open; eprev = real ? E : eprev; P = Phi;
         }
         if (open) { cl |= 1u << (G - 1); }
         // (the place of a run item: behind everything counted up to the group AFTER its last one -- offc[g + 1] - 1, or cnt for the last run)

@@ -5,7 +5,7 @@
 * quantize_q80(): export.py's weight rule -- the same scale, torch.round (halves to even).
 * matmul(): vectorised over rows, sequential over groups in np.float32: val = val + ((float)ival * ws) * xs.
 * Q8Ref.forward(): infer.rs:8-53 composed from the oracle's per-op functions, every matmul replaced by the above.
-* read_v2(): the llama2.c version-2 file (export.py version2_export).
+* read_v2() / write_v2(): the llama2.c version-2 file (export.py version2_export) and its inverse.
 """
 from __future__ import annotations
 
@@ -95,6 +95,39 @@ def read_v2(path):
     return cfg, gs, shared, norms, t
 
 
+def write_v2(path, cfg: dict, gs: int, shared: bool, norms: dict, t: dict):
+    """the inverse of read_v2: 256-byte header (magic, version, 7 ints, the shared-classifier byte at 36, the group size at 37, zeros),
+    the fp32 norms, then every quantized tensor as int8 values followed by its scales -- per-layer tensors layer by layer, as
+    export.py writes them -- and no wcls when the classifier is shared"""
+    dim, hidden, L, V = cfg["dim"], cfg["hidden_dim"], cfg["n_layers"], cfg["vocab_size"]
+    assert bool(cfg["shared_weight"]) == bool(shared) and dim % gs == 0 and hidden % gs == 0
+    hdr = bytearray(256)
+    hdr[0:4] = np.array([MAGIC], "<u4").tobytes()
+    hdr[4:8] = np.array([2], "<i4").tobytes()
+    hdr[8:36] = np.array([dim, hidden, L, cfg["n_heads"], cfg["n_kv_heads"], V, cfg["seq_len"]], "<i4").tobytes()
+    hdr[36] = int(bool(shared))
+    hdr[37:41] = np.array([gs], "<i4").tobytes()
+    sizes = dict(tok=V * dim, wq=L * dim * dim, wk=L * dim * dim, wv=L * dim * dim, wo=L * dim * dim, w1=L * hidden * dim,
+                 w2=L * dim * hidden, w3=L * hidden * dim, wcls=V * dim)
+    with open(path, "wb") as f:
+        f.write(bytes(hdr))
+        for name, n in (("rms_att_weight", L * dim), ("rms_ffn_weight", L * dim), ("rms_final_weight", dim)):
+            a = np.ascontiguousarray(norms[name], "<f4").reshape(-1)
+            assert a.size == n, (name, a.size, n)
+            f.write(a.tobytes())
+        for name in TENSORS:
+            if name == "wcls" and shared:
+                continue
+            q, s = t[name]
+            q, s = np.ascontiguousarray(q, np.int8).reshape(-1), np.ascontiguousarray(s, "<f4").reshape(-1)
+            assert q.size == sizes[name] and s.size * gs == q.size, (name, q.size, s.size)
+            parts = 1 if name in ("tok", "wcls") else L
+            n = q.size // parts
+            for i in range(parts):
+                f.write(q[i * n:(i + 1) * n].tobytes())
+                f.write(s[i * (n // gs):(i + 1) * (n // gs)].tobytes())
+
+
 def oracle_config(cfg: dict) -> O.Config:
     return O.Config(**cfg)
 
@@ -116,43 +149,51 @@ class Q8Ref:
         self._cs = O.OracleState(*[O._p(self.s[n]) for n in O._S_FIELDS])
         self._cc = c.c()
 
+    # the two data-dependent ops as hooks: the host tests plant a fault in a subclass and show the comparison helpers see it
+    quantize = staticmethod(quantize)
+    rmsnorm = staticmethod(O.rmsnorm)
+
     def _mm(self, name, layer, xq, xs, rows, K):
         q, s = self.t[name]
         per, G = rows * K, rows * K // self.gs
         return matmul(xq, xs, q[layer * per:(layer + 1) * per], s[layer * G:(layer + 1) * G], self.gs)
 
-    def forward(self, token: int, pos: int) -> np.ndarray:
+    def forward(self, token: int, pos: int, rope_stop=None) -> np.ndarray:
+        """rope_stop = l: return after layer l's RoPE with that layer's query and key in s["q"] / s["k"] and nothing of layer l
+        appended to the caches (sink_caches_q8 builds layer l's keys for that query); None: the whole forward"""
         c, s, gs = self.c, self.s, self.gs
         d, h, hs = c.dim, c.hidden_dim, c.head_size
         x = s["x"]
         x[:] = self.emb[token]
         for l in range(c.n_layers):
-            O.rmsnorm(s["xb"], x, np.ascontiguousarray(self.norms["rms_att_weight"][l * d:(l + 1) * d]), d)
-            xq, xs = quantize(s["xb"], gs)
+            self.rmsnorm(s["xb"], x, np.ascontiguousarray(self.norms["rms_att_weight"][l * d:(l + 1) * d]), d)
+            xq, xs = self.quantize(s["xb"], gs)
             s["q"][:] = self._mm("wq", l, xq, xs, d, d)
             s["k"][:] = self._mm("wk", l, xq, xs, d, d)
             s["v"][:] = self._mm("wv", l, xq, xs, d, d)
             for hh in range(c.n_heads):
                 O.apply_position(s["q"][hh * hs:(hh + 1) * hs], s["k"][hh * hs:(hh + 1) * hs], self.fr[pos], self.fi[pos], hs)
+            if rope_stop == l:
+                return None
             base = (l * c.seq_len + pos) * d
             s["key_cache"][base:base + d] = s["k"]
             s["value_cache"][base:base + d] = s["v"]
             O.lib().oracle_multi_head_attention(C.byref(self._cc), C.byref(self._cs), l, pos)
-            xq, xs = quantize(s["xb"], gs)
+            xq, xs = self.quantize(s["xb"], gs)
             s["xb2"][:] = self._mm("wo", l, xq, xs, d, d)
             O.array_add(x, s["xb2"], d)
-            O.rmsnorm(s["xb"], x, np.ascontiguousarray(self.norms["rms_ffn_weight"][l * d:(l + 1) * d]), d)
-            xq, xs = quantize(s["xb"], gs)
+            self.rmsnorm(s["xb"], x, np.ascontiguousarray(self.norms["rms_ffn_weight"][l * d:(l + 1) * d]), d)
+            xq, xs = self.quantize(s["xb"], gs)
             s["hb"][:] = self._mm("w1", l, xq, xs, h, d)
             s["hb2"][:] = self._mm("w3", l, xq, xs, h, d)
             O.sinu(s["hb"], h)
             O.array_mult(s["hb"], s["hb2"], h)
-            xq, xs = quantize(s["hb"], gs)
+            xq, xs = self.quantize(s["hb"], gs)
             s["xb"][:] = self._mm("w2", l, xq, xs, d, h)
             O.array_add(x, s["xb"], d)
         s["xb"][:] = x
-        O.rmsnorm(x, s["xb"], self.norms["rms_final_weight"], d)
-        xq, xs = quantize(x, gs)
+        self.rmsnorm(x, s["xb"], self.norms["rms_final_weight"], d)
+        xq, xs = self.quantize(x, gs)
         s["logits"][:] = self._mm("wcls", 0, xq, xs, c.vocab_size, d)
         return s["logits"]
 

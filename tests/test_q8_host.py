@@ -92,3 +92,32 @@ def test_matmul_definition_order_and_negative_zero():
     # a zero row starting from +0.0 stays +0.0
     z = R.matmul(xq, xs, np.zeros(64, np.int8), np.ones(2, np.float32), gs)
     assert z.view(np.uint32)[0] == 0
+
+
+# ------------------------------------------------------------------ write_v2, the inverse of read_v2
+
+@pytest.mark.parametrize("name,gs,shared", CASES)
+def test_write_v2_reproduces_the_exporters_file(golden_dir, tmp_path, name, gs, shared):
+    """the fixtures were written by the reference exporter: write_v2(*read_v2(file)) is the file, byte for byte"""
+    src = golden_dir / f"{name}.bin"
+    p = tmp_path / "again.bin"
+    R.write_v2(p, *R.read_v2(src))
+    assert p.read_bytes() == src.read_bytes()
+
+
+@pytest.mark.parametrize("shared", [True, False])
+def test_write_v2_round_trips_a_trained_like_model(tmp_path, shared):
+    from tests import trained_like as T
+    cfg = dict(dim=64, hidden_dim=192, n_layers=3, n_heads=4, n_kv_heads=4, vocab_size=40, seq_len=24, shared_weight=shared)
+    norms, t = T.trained_like_q8(cfg, "massive", 32, 3)
+    p = tmp_path / "m.bin"
+    R.write_v2(p, cfg, 32, shared, norms, t)
+    cfg2, gs2, shared2, norms2, t2 = R.read_v2(p)
+    assert cfg2 == cfg and gs2 == 32 and shared2 == shared
+    for k, v in norms.items():
+        assert norms2[k].tobytes() == v.tobytes(), k
+    for k in R.TENSORS:
+        assert np.array_equal(t2[k][0], t[k][0]) and t2[k][1].tobytes() == t[k][1].tobytes(), k
+    assert (t2["wcls"][0] is t2["tok"][0]) == shared
+    raw = p.read_bytes()
+    assert raw[36] == int(shared) and np.frombuffer(raw[37:41], "<i4")[0] == 32 and not any(raw[41:256])

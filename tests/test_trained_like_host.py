@@ -197,3 +197,206 @@ def test_comparator_accepts_the_reference_and_rejects_planted_faults(kind):
                 caught_blk += hit
     assert caught_att == len(toks) - 2, caught_att
     assert caught_blk == len(toks) - 2, caught_blk
+
+
+# ------------------------------------------------------------------ the Q8 twins: the conditions tests/test_hip_q8_trained_like.py rests on
+
+from tests import q8_ref as R                                                       # noqa: E402
+from tests.test_hip_q8 import check_state                                           # noqa: E402
+from tests.test_hip_q8_trained_like import GS, SEED, SINK_POS, SINK_TOKEN, MILD, quantized_equal   # noqa: E402
+from tests.test_hip_trained_like import SHAPES, TOKS                                # noqa: E402
+from oracle import synth as S                                                       # noqa: E402
+
+_q8 = {}
+
+
+def _q8_ref(shape, kind, cls=R.Q8Ref):
+    """a fresh Q8Ref (or a planted-fault subclass) of the GPU tests' case; the quantized tensors are built once"""
+    if (shape, kind) not in _q8:
+        d, h, L, H, V, seq = SHAPES[shape]
+        cfg = O.Config(d, h, L, H, H, V, seq, False)
+        _q8[(shape, kind)] = (T.cfg_dict(cfg), GS[shape]) + T.trained_like_q8(cfg, kind, GS[shape], SEED)
+    cfg, gs, norms, t = _q8[(shape, kind)]
+    return cls(cfg, gs, norms, t, S.rope_tables(cfg["seq_len"], cfg["dim"] // cfg["n_heads"]))
+
+
+@pytest.mark.parametrize("dim,gs", [(288, 32), (768, 32), (768, 64), (2048, 32), (2048, 64), (4096, 32), (4096, 64)])
+def test_designated_rows_survive_q8_quantization(dim, gs):
+    """after quantize_q80 AND dequantization (what Q8Ref.emb and the device's fp32 token table hold) the designated rows keep their
+    property: none had to be planted as (int8, scale) by hand.  The tie row's group 0 becomes [64, 0, ...] (2^-6 is 0.03 steps of
+    64 / 127) and its other groups are exact."""
+    tiny = np.finfo(np.float32).tiny
+    for tok, row in T.designated_rows(dim, SEED).items():
+        x = R.dequantize(*R.quantize_q80(row, gs), gs)
+        sq = (x * x).astype(np.float32)
+        if tok == T.TOK_ZERO:
+            assert not x.any()
+        elif tok == T.TOK_TIE:
+            assert x[0] == 64.0 and not x[1:gs].any() and np.array_equal(x[gs:], row[gs:])
+            assert T.seq_sum_f32(sq) == np.float32(4096.0)
+            items = T.seq_groups(sq)["items"]
+            assert items == dim and (items > T.FS_CAP) == (dim >= 2048)
+        elif tok == T.TOK_SUBNORMAL:
+            assert (sq > 0).all() and (sq < tiny).all() and 0 < T.seq_sum_f32(sq) < tiny
+        else:
+            assert np.isfinite(T.seq_sum_f32(sq)) and sq.min() >= 1e31
+
+
+def test_designated_rows_in_the_quantized_table():
+    """trained_like_q8's table, dequantized as Q8Ref does it, carries those rows"""
+    ref = _q8_ref("d768", "massive")
+    for tok, row in T.designated_rows(768, SEED).items():
+        want = R.dequantize(*R.quantize_q80(row, GS["d768"]), GS["d768"])
+        assert ref.emb[tok].tobytes() == want.tobytes(), tok
+
+
+class _Recording(R.Q8Ref):
+    """Q8Ref that notes, per rmsnorm call, the items its sum of squares puts on seqsum_fast's walk list"""
+    rec = None
+
+    def rmsnorm(self, o, x, w, n):
+        self.rec.append(T.seq_groups((x * x).astype(np.float32))["items"])
+        O.rmsnorm(o, x, w, n)
+
+
+@pytest.mark.parametrize("kind", T.KINDS)
+@pytest.mark.parametrize("shape", ["d288", "d768", "d2048"])
+def test_q8_forward_is_finite_and_only_the_tie_row_overflows_the_walk_list(shape, kind):
+    """Q8Ref.forward over TOKS gives finite logits; and the GPU tests' proof that the stand-alone norm fell back: at the position behind
+    TOKS, over the same caches, the tie token's forward has exactly one norm (layer 0's) whose list passes kFsCap from dim 2048 on and
+    a mild token's has none -- at 768 neither has.  (d4096, 35 s on a CPU: one overflowing norm for the tie token, none for the mild
+    one, both kinds; measured once and left out of the suite.)"""
+    ref = _q8_ref(shape, kind, _Recording)
+    for pos, tok in enumerate(TOKS):
+        ref.rec = []
+        assert np.isfinite(ref.forward(tok, pos)).all(), (shape, kind, pos)
+    over = {}
+    for tok in (MILD, T.TOK_TIE):
+        ref.rec = []
+        ref.forward(tok, len(TOKS))
+        over[tok] = sum(i > T.FS_CAP for i in ref.rec)
+    assert over[MILD] == 0 and over[T.TOK_TIE] == (1 if shape == "d2048" else 0), over
+
+
+@pytest.mark.parametrize("sink_at", [0, 256, SINK_POS - 1])
+def test_sink_caches_q8_put_the_tail_at_half_ulps(sink_at):
+    """the GPU tests' sink case (d2048 / sink / GS 64, position 1099): the last layer's softmax rows of the Q8 forward, recomputed from
+    its query and keys, have one exponential equal to 1.0 at the sink and the rest of the prefilled positions in [2^-25, 2^-24]; the
+    fp32 sum stays within 2^-13 of 1.0, and with the sink first every group of eight is a SEQ group: more items than kFsCap"""
+    ref = _q8_ref("d2048", "sink")
+    c, pos = ref.c, SINK_POS
+    T.sink_caches_q8(ref, SINK_TOKEN, pos, sink_at)
+    assert np.isfinite(ref.forward(SINK_TOKEN, pos)).all()
+    hs = c.head_size
+    q = ref.s["q"].reshape(c.n_heads, hs).astype(np.float64)
+    K = ref.s["key_cache"].reshape(c.n_layers, c.seq_len, c.n_heads, hs)[-1, :pos + 1].astype(np.float64)
+    sc = np.einsum("thd,hd->ht", K, q) / math.sqrt(hs)
+    assert not sc[0].any()                                  # the dead head
+    for hh in range(2, c.n_heads):
+        e = np.exp(sc[hh] - sc[hh].max()).astype(np.float32)
+        assert int(np.argmax(sc[hh])) == sink_at and e[sink_at] == 1.0
+        tail = np.delete(e, [sink_at, pos])
+        assert (tail <= 2.0 ** -23.9).all() and np.mean(tail >= 2.0 ** -25.1) > 0.99
+        assert 1.0 <= float(T.seq_sum_f32(e)) < 1.0 + 2.0 ** -13
+        if sink_at == 0:
+            assert T.seq_groups(e)["items"] > T.FS_CAP
+    # the probabilities the oracle's attention left agree with that picture: one of them ~1
+    att = ref.s["att"].reshape(c.n_heads, c.seq_len)[2:, :pos + 1]
+    assert (att.argmax(axis=1) == sink_at).all() and (att.max(axis=1) > 0.999).all()
+
+
+@pytest.mark.parametrize("gs", [32, 64, 128])
+def test_q8_vectors_are_as_harsh_as_the_gpu_test_says(gs):
+    """the share of one-element groups (one |q| = 127, every other |q| <= 1) on the R.quantize output: all groups of `every_group`
+    (measured 1.0 at the three group sizes; asserted >= 0.9), the massive channels' groups of `massive` (3 of n / gs; the 400 x group
+    may hold a |q| = 2: asserted >= 2), and what the other vectors are built for"""
+    n = 2048
+    q, s = R.quantize(T.q8_vector("every_group", n, gs), gs)
+    assert T.one_element_groups(q, gs) >= 0.9
+    q, s = R.quantize(T.q8_vector("massive", n, gs), gs)
+    assert 2 <= round(T.one_element_groups(q, gs) * (n // gs)) <= 3
+    for c in T.massive_channels(n)[1:]:
+        g = np.abs(q.reshape(-1, gs)[c // gs].astype(int))
+        assert g.max() == 127 and np.sort(g)[-2] <= 1
+    q, s = R.quantize(T.q8_vector("equal", n, gs), gs)
+    assert (np.abs(q.astype(int)) == 127).all() and s.max() / s.min() > 2.0 ** 40
+    x = T.q8_vector("tiny", n, gs)
+    q, s = R.quantize(x, gs)
+    tiny = np.finfo(np.float32).tiny
+    assert (s > 0).all() and (s < tiny).all() and (np.abs(x).reshape(-1, gs).max(axis=1)[0::2] == tiny).all()
+    assert (np.abs(x).reshape(-1, gs).max(axis=1)[1::2] < tiny).all() and np.count_nonzero(q) > 0.9 * n
+    x = T.q8_vector("fltmax", n, gs)
+    assert np.isfinite(x).all() and (np.abs(x).reshape(-1, gs).max(axis=1) == np.float32(T.FLT_MAX / 2)).all()
+    x = np.abs(T.q8_vector("large", n, gs))
+    assert x.min() >= 1e16 and x.max() <= 2.0001e17
+    # near_half: the fp32 quotients next to k + 0.5 on both sides (one ulp of the quotient away, two where the spacing of x is the
+    # coarser one) and, where a value gives it, k + 0.5 itself
+    x = T.q8_vector("near_half", n, gs).reshape(-1, gs)
+    scale = (np.abs(x).max(axis=1) / np.float32(127.0)).astype(np.float32)
+    r = np.abs((x / scale[:, None]).astype(np.float32))[:, 1:]
+    r = r[r > 0]
+    half = np.floor(r) + np.float32(0.5)
+    assert (np.abs(r - half) <= 2 * np.spacing(half)).all()
+    assert (r < half).sum() > n // 8 and (r > half).sum() > n // 8 and (r == half).sum() > 0
+    assert len(np.unique(np.floor(r))) > 100
+
+
+# ------------------------------------------------------------------ planted faults, seen by the GPU tests' own comparison helpers
+
+class _RefAsEngine:
+    """what check_state reads of a Q8Engine, served from a Q8Ref's state"""
+
+    def __init__(self, ref):
+        self.ref = ref
+
+    def logits(self):
+        return self.ref.s["logits"].copy()
+
+    def buffer(self, name, n, offset=0):
+        return self.ref.s[name][offset:offset + n].copy()
+
+
+class _PairwiseNorm(R.Q8Ref):
+    """the norm's sum of squares pairwise (numpy's float32 sum) instead of in index order"""
+
+    def rmsnorm(self, o, x, w, n):
+        ss = np.sum((x * x).astype(np.float32), dtype=np.float32)
+        v = np.float32(1.0) / np.sqrt(np.float32(ss / np.float32(n) + np.float32(1e-5)), dtype=np.float32)
+        o[:] = (w * (v * x).astype(np.float32)).astype(np.float32)
+
+
+def _quantize_by_reciprocal(x, gs):
+    """q8_ref.quantize with x * (1 / scale) in place of x / scale"""
+    x = np.ascontiguousarray(x, np.float32).reshape(-1, gs)
+    scale = (np.abs(x).max(axis=1) / np.float32(127.0)).astype(np.float32)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        inv = (np.float32(1.0) / scale).astype(np.float32)
+        r = (x * inv[:, None]).astype(np.float32).astype(np.float64)
+    q = np.sign(r) * np.floor(np.abs(r) + 0.5)
+    q = np.where(scale[:, None] == 0, 0.0, np.clip(np.nan_to_num(q), -127, 127))
+    return q.astype(np.int8).reshape(-1), scale
+
+
+def test_planted_pairwise_norm_sum_is_caught_on_the_tie_row():
+    """a forward whose norm sums pairwise passes check_state on a mild token and fails it on TOK_TIE at d2048 (sequential 4096.0,
+    pairwise 4096.5): the comparison the GPU tests make would see a norm kernel that left the reference's order"""
+    good, bad = _q8_ref("d2048", "massive"), _q8_ref("d2048", "massive", _PairwiseNorm)
+    good.forward(T.TOK_TIE, 0); bad.forward(T.TOK_TIE, 0)
+    check_state(_RefAsEngine(good), good, 0)
+    with pytest.raises(AssertionError):
+        check_state(_RefAsEngine(bad), good, 0)
+
+
+@pytest.mark.parametrize("gs", [32, 64, 128])
+def test_planted_reciprocal_quantizer_is_caught_on_the_near_half_vectors(gs):
+    """x * (1 / scale) in place of x / scale changes an int8 of the near-half vector (and none of a mild Gaussian one's scale):
+    quantized_equal, the GPU test's comparison, sees it"""
+    x = T.q8_vector("near_half", 2048, gs)
+    wq, ws = R.quantize(x, gs)
+    assert quantized_equal(wq, ws, wq, ws)
+    bq, bs = _quantize_by_reciprocal(x, gs)
+    assert same_scale_bits(bs, ws) and not quantized_equal(bq, bs, wq, ws) and (bq != wq).sum() >= 1
+
+
+def same_scale_bits(a, b):
+    return np.array_equal(a.view(np.uint32), b.view(np.uint32))

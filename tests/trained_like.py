@@ -218,6 +218,184 @@ def sink_caches(cfg: O.Config, w: dict, token: int, pos: int, sink_at: int, seed
     return kc.reshape(-1), vc.reshape(-1)
 
 
+# ------------------------------------------------------------------ the Q8 twins (tests/q8_ref.py)
+
+def cfg_dict(cfg) -> dict:
+    """O.Config -> the dict Q8Ref / write_v2 take"""
+    if isinstance(cfg, dict):
+        return dict(cfg)
+    return dict(dim=cfg.dim, hidden_dim=cfg.hidden_dim, n_layers=cfg.n_layers, n_heads=cfg.n_heads, n_kv_heads=cfg.n_kv_heads,
+                vocab_size=cfg.vocab_size, seq_len=cfg.seq_len, shared_weight=bool(cfg.shared_weight))
+
+
+def trained_like_q8(cfg, kind: str, gs: int, seed: int):
+    """-> (norms, t) for Q8Ref / write_v2: trained_like_weights quantized by export.py's rule (q8_ref.quantize_q80), every layer's
+    matrix on its own as synth_q8 does; tok and wcls are one pair when the classifier is shared.  The DESIGNATED rows survive the
+    round trip with their property (tests/test_trained_like_host.py): the tie row keeps its 64 and its tail (the tail values that share
+    the 64's group round to zero: still SEQ groups), the zero row is zero, the subnormal row stays non-zero with subnormal squares, the
+    large row stays finite in the sum."""
+    from . import q8_ref as R
+    c = O.Config(**cfg) if isinstance(cfg, dict) else cfg
+    w = trained_like_weights(c, kind, seed)
+    norms = {n: np.ascontiguousarray(w[n], np.float32).reshape(-1) for n in ("rms_att_weight", "rms_ffn_weight", "rms_final_weight")}
+    names = dict(tok="token_embedding_table")
+    t = {}
+    for name in R.TENSORS:
+        if name == "wcls" and c.shared_weight:
+            t["wcls"] = t["tok"]
+            continue
+        a = np.ascontiguousarray(w.pop(names.get(name, name)), np.float32)
+        if name in ("tok", "wcls"):
+            t[name] = R.quantize_q80(a, gs)
+        else:
+            parts = [R.quantize_q80(a[l], gs) for l in range(c.n_layers)]
+            t[name] = (np.concatenate([q for q, _ in parts]), np.concatenate([s_ for _, s_ in parts]))
+        del a
+    return norms, t
+
+
+def sink_caches_q8(ref, token: int, pos: int, sink_at: int, seed: int = 0, tail_every: int = 1):
+    """sink_caches for the Q8 model: `ref` is a Q8Ref (or a callable returning one); layer l's sink keys are built for the query the
+    Q8 forward forms in layer l over the layers below (Q8Ref.forward(..., rope_stop=l)).  The KV cache is fp32 in the Q8 model, so
+    sink_cache_layer serves unchanged.  ref's caches are left holding the result."""
+    ref = ref() if callable(ref) else ref
+    c = ref.c
+    rng = np.random.default_rng([seed, pos, sink_at])
+    L, T, d = c.n_layers, c.seq_len, c.dim
+    kc = np.zeros((L, T, d), np.float32)
+    vc = np.zeros((L, T, d), np.float32)
+    for l in range(L):
+        ref.s["key_cache"][:] = kc.reshape(-1)
+        ref.s["value_cache"][:] = vc.reshape(-1)
+        ref.forward(token, pos, rope_stop=l)
+        kl, vl = sink_cache_layer(ref.s["q"].copy(), ref.s["k"].copy(), c.n_heads, pos, sink_at, rng, tail_every)
+        kc[l, :pos] = kl
+        vc[l, :pos] = vl
+    ref.s["key_cache"][:] = kc.reshape(-1)
+    ref.s["value_cache"][:] = vc.reshape(-1)
+    return kc.reshape(-1), vc.reshape(-1)
+
+
+def one_element_groups(q, gs: int) -> float:
+    """the share of groups of an int8 vector in which one |q| is 127 and every other |q| <= 1 (a massive channel sets the scale)"""
+    a = np.sort(np.abs(np.asarray(q).reshape(-1, gs).astype(np.int32)), axis=1)
+    return float(np.mean((a[:, -1] == 127) & (a[:, -2] <= 1)))
+
+
+MASSIVE_MULTS = (400.0, 1500.0, 3000.0)
+FLT_MAX = float(np.finfo(np.float32).max)
+Q8_VECTORS = ("massive", "every_group", "equal", "tiny", "large", "fltmax", "near_half")
+
+
+def near_half_group(gs: int, top: np.float32, ks, rng) -> np.ndarray:
+    """one group with max |x| = top (scale = fl(top / 127)) whose other values sit where the quantizer's rounding decides: for each k
+    the fp32 values x around (k + 0.5) scale whose fp32 QUOTIENT fl(x / scale) is the largest below k + 0.5, k + 0.5 itself when some
+    x gives it, and the smallest above (one or two ulps of the quotient away).  Searched over the fp32 neighbours of fl((k + 0.5) scale) with numpy's correctly rounded fp32
+    division -- a float64 quotient would place them differently."""
+    top = np.float32(top)
+    scale = np.float32(top / np.float32(127.0))
+    out = [top]
+    for k in ks:
+        t = np.float32(k + 0.5)
+        x0 = np.float32(t * scale)
+        cand = [x0]
+        lo = hi = x0
+        for _ in range(6):
+            lo = np.nextafter(lo, np.float32(-np.inf)); hi = np.nextafter(hi, np.float32(np.inf))
+            cand += [lo, hi]
+        cand = np.sort(np.array(cand, np.float32))
+        r = (cand / scale).astype(np.float32)
+        pick = []
+        if (r < t).any():
+            pick.append(cand[r < t][-1])
+        if (r == t).any():
+            pick.append(cand[r == t][0])
+        if (r > t).any():
+            pick.append(cand[r > t][0])
+        for x in pick:
+            out.append(x if rng.random() < 0.5 else -x)
+    out = out[:gs]
+    g = np.zeros(gs, np.float32)
+    g[:len(out)] = out
+    return g
+
+
+def q8_vector(kind: str, n: int, gs: int, seed: int = 0) -> np.ndarray:
+    """one activation vector of n values (gs | n) that is hard on the Q8 activation quantizer and on the in-order group sum:
+
+    massive      N(0, 1) with the three massive_channels 400 / 1500 / 3000 times the median |x|: their groups' scales are set by one
+                 element and every other element of the group lands on 0 or +-1;
+    every_group  the same with one such element in EVERY group (rotating place and multiplier);
+    equal        every group all-equal in magnitude (mixed signs in every second group): all +-127, over 60 binades of scale;
+    tiny         groups whose max is the smallest normal over subnormal others, and groups whose max is a subnormal with the others
+                 eight times smaller: the scale itself is subnormal;
+    large        groups at 1e16 .. 2e17;
+    fltmax       groups whose max is FLT_MAX / 2;
+    near_half    near_half_group over many scales and every k of 0 .. 126."""
+    assert n % gs == 0 and kind in Q8_VECTORS, (kind, n, gs)
+    rng = np.random.default_rng([seed, Q8_VECTORS.index(kind), gs])
+    G = n // gs
+    sign = lambda shape: np.where(rng.random(shape) < 0.5, -1.0, 1.0)
+    if kind in ("massive", "every_group"):
+        x = rng.standard_normal(n).astype(np.float32)
+        med = float(np.median(np.abs(x)))
+        if kind == "massive":
+            where = list(zip(massive_channels(n), MASSIVE_MULTS))
+        else:
+            where = [(g * gs + (7 * g) % gs, MASSIVE_MULTS[g % 3]) for g in range(G)]
+        for c, mult in where:
+            x[c] = np.float32(sign(()) * mult * med)
+        return x
+    if kind == "equal":
+        mag = np.exp2(rng.uniform(-40.0, 20.0, G)) * rng.uniform(1.0, 2.0, G)
+        x = np.repeat(mag, gs).reshape(G, gs)
+        x[1::2] *= sign((len(x[1::2]), gs))
+        x[2::4] *= -1.0
+        return x.astype(np.float32).reshape(-1)
+    if kind == "tiny":
+        tiny = float(np.finfo(np.float32).tiny)
+        x = np.zeros((G, gs), np.float64)
+        for g in range(G):
+            if g % 2 == 0:      # max = the smallest normal, the others subnormal
+                x[g] = sign(gs) * rng.uniform(0.0, 1.0, gs) * tiny
+                x[g, (3 * g) % gs] = tiny * sign(())
+            else:               # max subnormal (2^-130 .. 2^-127), the others eight times smaller
+                m = tiny * 2.0 ** -int(rng.integers(1, 5))
+                x[g] = sign(gs) * rng.uniform(0.5, 1.0, gs) * m / 8.0
+                x[g, (5 * g) % gs] = m * sign(())
+        return x.astype(np.float32).reshape(-1)
+    if kind == "large":
+        return (sign(n) * rng.uniform(1e16, 2e17, n)).astype(np.float32)
+    if kind == "fltmax":
+        x = (sign((G, gs)) * rng.uniform(0.0, 0.5, (G, gs)) * FLT_MAX).astype(np.float32)
+        for g in range(G):
+            x[g, (11 * g) % gs] = np.float32(FLT_MAX / 2) * np.float32(sign(()))
+        return x.reshape(-1)
+    per = max(1, (gs - 1) // 3)
+    ks = [int(k) for k in rng.permutation(127)]
+    out = []
+    for g in range(G):
+        top = np.float32(127.0 * 0.0371 * 1.37 ** (g % 40) * rng.uniform(1.0, 1.3))
+        out.append(near_half_group(gs, top, [ks[(g * per + i) % 127] for i in range(per)], rng))
+    return np.concatenate(out)
+
+
+def q8_rows(n_tok: int, n: int, gs: int, seed: int = 0, kinds=Q8_VECTORS) -> np.ndarray:
+    """[n_tok, n]: row t is q8_vector(kinds[t % len(kinds)], seed + t // len(kinds))"""
+    return np.stack([q8_vector(kinds[t % len(kinds)], n, gs, seed + t // len(kinds)) for t in range(n_tok)])
+
+
+def harsh_q8_matrix(d: int, n: int, gs: int, seed: int = 0):
+    """(int8 values, scales) of a [d, n] Student-t matrix (std 0.02) with three columns x 20 and three rows x 300, quantized by
+    export.py's rule: the group terms of a row span many binades"""
+    from . import q8_ref as R
+    rng = np.random.default_rng([seed, d, n])
+    w = _student_t(rng, (d, n), 0.02)
+    w[:, rng.choice(n, 3, replace=False)] *= np.float32(20.0)
+    w[rng.choice(d, 3, replace=False), :] *= np.float32(300.0)
+    return R.quantize_q80(w, gs)
+
+
 # ------------------------------------------------------------------ sequential-sum properties (numpy)
 
 def seq_sum_f32(a) -> np.float32:
