@@ -358,7 +358,8 @@ int  rama_generate_stream(rama_ctx *ctx, const rama_config *cfg, const rama_weig
  * synchronises and drops every captured graph; free a run state only after that (or after rama_ctx_destroy). */
 int  rama_set_graph_mode(rama_ctx *ctx, int enabled);
 /* Modes and performance knobs.  The MODE keys change which of the reference's admissible roundings is reproduced; every other key leaves results
- * unchanged (parity mode: the same bits; fast mode: up to fp32 summation order).  Changing a key synchronises and drops captured graphs.
+ * unchanged (parity mode: the same bits; fast mode: up to fp32 summation order).  Changing a key synchronises and drops captured graphs, except
+ * the switches of the recorded 1:1 ops (last line below), "chain_views", "prefill", "prefill_attn" and "prefill_chain", which only store the value.
  * Measurements and history of every key: DESIGN.md appendix A.
  *
  * MODE
@@ -381,7 +382,7 @@ int  rama_set_graph_mode(rama_ctx *ctx, int enabled);
  *        32 = parity mode's attention, 64 = its exact norms; tools/tol_sweep.py)
  *
  * FAST MODE  (default in brackets)
- *   "geom" 0..3 [3] matvec workgroup geometry | "resid_r2" 0..3 [2] geometry of Wo / W2 | "solo" -1|0|1 [-1: rows <= 2048 floats] one wave per row group
+ *   "geom" 0..4 [3] matvec workgroup geometry (4: 8 rows x 8 waves) | "resid_r2" 0..3 [2] geometry of Wo / W2 | "solo" -1|0|1 [-1: rows <= 2048 floats] one wave per row group
  *   "w13i" 0|1 [1] W1|W3 from the row-interleaved copy | "fused" / "fused_solo" -1|0|1 [-1: dim <= 1024 / dim > 512] a whole stage as ONE launch (layer_fused.hpp)
  *   "merge" -1|0|1 [-1: dim <= 1024] attention + Wo as one launch | "split_pos" -1|N [-1: 256 when a head's K+V cache exceeds 1 MiB] split-T attention from N
  *   "attn_nsplit" 0..32 [0], "attn_waves" 16|8|4 [8], "attn_nt" 0|1 [1], "attn_u" 8|16 [8], "combine_v" 0|1 [1] : split-T geometry

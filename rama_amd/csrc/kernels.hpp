@@ -975,6 +975,59 @@ __global__ __launch_bounds__(1024) void argmax_kernel(ArgmaxParams p) {
     gather_next_embedding(p, &s_next);
 }
 
+// what ends a step of the chained batch decode (rama_decode_batch_steps): one workgroup per sequence.  In the global namespace, where it was
+// first defined: its symbol is the name it carries in the committed profiles and resource listings.
+}  // namespace rama
+struct BatchArgmaxParams { const float* logits; int n; int* toks; rama::SeqSlot* seqs; int* out; int out_cap; int* ring; };      // ring: host-visible copy of out, token + 1 (0: not yet)
+__global__ __launch_bounds__(1024) void argmax_batch_kernel(BatchArgmaxParams p) {
+    using namespace rama;
+    // Device::sample at temperature 0 per sequence (cpu.rs:163-167: the LAST maximal index), then mod.rs:196-203:
+    // token = next, pos += 1
+    __shared__ float s_v[16];
+    __shared__ int s_i[16];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* lg = p.logits + (size_t)b * p.n;
+    float bv = -INFINITY; int bi = -1;
+    const int n4 = p.n >> 2;                                      // rows of the logits slab are 16-byte aligned (n % 4 == 0)
+    const f4* l4 = reinterpret_cast<const f4*>(lg);
+    for (int i0 = tid; i0 < n4; i0 += 8 * 1024) {
+        f4 v[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) { const int i = i0 + u * 1024; v[u] = i < n4 ? l4[i] : f4{-INFINITY, -INFINITY, -INFINITY, -INFINITY}; }
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            const int i = i0 + u * 1024;
+            if (i < n4) {
+                if (!(bv > v[u].x)) { bv = v[u].x; bi = 4 * i; }
+                if (!(bv > v[u].y)) { bv = v[u].y; bi = 4 * i + 1; }
+                if (!(bv > v[u].z)) { bv = v[u].z; bi = 4 * i + 2; }
+                if (!(bv > v[u].w)) { bv = v[u].w; bi = 4 * i + 3; }
+            }
+        }
+    }
+    const float wm = wave_max(bv);
+    const int wi = wave_max_i(bv == wm ? bi : -1);
+    if (lane == 0) { s_v[wave] = wm; s_i[wave] = wi; }
+    __syncthreads();
+    if (tid == 0) {
+        float v = s_v[0]; int idx = s_i[0];
+        for (int w = 1; w < 16; w++) {
+            const float ov = s_v[w]; const int oi = s_i[w];
+            if (oi >= 0 && (idx < 0 || ov > v || (ov == v && oi > idx))) { v = ov; idx = oi; }
+        }
+        idx = idx < 0 ? 0 : idx;
+        p.toks[b] = idx;
+        p.seqs[b].pos += 1;
+        const int k = p.seqs[b].pad;                              // tokens this sequence has produced so far
+        if (k < p.out_cap) {
+            p.out[(size_t)b * p.out_cap + k] = idx;
+            if (p.ring) __hip_atomic_store(p.ring + (size_t)b * p.out_cap + k, idx + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+        p.seqs[b].pad = k + 1;
+    }
+}
+namespace rama {
+
 // ---------------------------------------------------------------- top-p sampling on the device
 // Device::sample for temperature != 0 (cpu.rs:168-178 + sample_top_q, infer.rs:55-85), without the
 // reference GPU path's 128 KB logits download per token (gpu.rs:153).  The ordering (softmax, cutoff,

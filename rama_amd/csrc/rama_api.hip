@@ -16,6 +16,7 @@
 #include <hip/hip_ext.h>   // hipExtLaunchKernelGGL: start/stop events carried by the dispatch itself
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -74,9 +75,21 @@ struct KProf {
     std::vector<hipEvent_t> ev;   // 2 per record
 };
 
-struct GraphCache {
-    hipGraphExec_t exec = nullptr;
+// a captured, instantiated graph: made by capture_graph, launched by replay_graph
+struct CapturedGraph {
     hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    bool handoff = false;              // [r6] the captured launches hand data over inside a kernel (a leader norm, attention+Wo, the one-launch stage): a REPLAY must mark
+                                       // the error word as worth reading too (rama_ctx::handoff_dirty is otherwise only set where such a launch is enqueued)
+};
+static void destroy_graph(CapturedGraph& g) {
+    if (g.exec) hipGraphExecDestroy(g.exec);
+    if (g.graph) hipGraphDestroy(g.graph);
+    g = CapturedGraph();
+}
+
+struct GraphCache {
+    CapturedGraph cg;
     // identity of what was captured
     rama_config cfg{};
     rama_weights w{};
@@ -84,8 +97,6 @@ struct GraphCache {
     bool valid = false;
     int steps = 1;                     // decode steps in the captured graph
     unsigned long long copies_gen = 0; // model.hip's generation of derived weight copies at capture: a graph holds their addresses, and ANOTHER context may free them
-    bool handoff = false;              // [r6] the captured launches hand data over inside a kernel (a leader norm, attention+Wo, the one-launch stage): a REPLAY must mark
-                                       // the error word as worth reading too (rama_ctx::handoff_dirty is otherwise only set where such a launch is enqueued)
 };
 
 struct rama_ctx {
@@ -167,7 +178,7 @@ struct rama_ctx {
     } tb;
     // Q8 models (rama_q8_forward / rama_q8_generate): the int8 activations and their scales, sized by the first call; graphs of their own
     int8_t* q8_xq = nullptr; float* q8_xs = nullptr; size_t q8_cap = 0;
-    struct Q8Graph { hipGraphExec_t exec = nullptr; hipGraph_t graph = nullptr; rama_config cfg{}; rama_q8_weights w{}; rama_run_state s{}; int variant = 0; int chained = 0; };
+    struct Q8Graph { CapturedGraph cg; rama_config cfg{}; rama_q8_weights w{}; rama_run_state s{}; int variant = 0; int chained = 0; };
     std::vector<Q8Graph> q8g;
     // Q8 token batches (rama_q8_prefill / rama_q8_decode_batch): row-major scratch for kQ8bMaxTok tokens, sized by the first call
     // (never inside a capture; no graph holds it), see Q8BatchScratch
@@ -253,7 +264,7 @@ struct rama_ctx {
         int* ring = nullptr;               // the same, host-pinned and device-mapped: token + 1, 0 = not produced yet (rama_decode_batch_stream_poll)
         int* ring_dev = nullptr;
         rama_config cfg{}; rama_weights w{};
-        hipGraphExec_t exec = nullptr; hipGraph_t graph = nullptr; int graph_bucket = -1;
+        CapturedGraph cg; int graph_bucket = -1;        // the step captured for contexts of up to 256 * graph_bucket timesteps
         // rama_decode_batch_begin_sampled: a step ends in the batched top-p sampler instead of argmax_batch_kernel
         bool sampled = false;
         ToppRow* rows = nullptr;           // [kMfMaxTok] every sequence's (T, topp, u, forced list)
@@ -383,26 +394,17 @@ static void drop_q8_graphs(rama_ctx* c, const rama_run_state* s) {
     for (size_t i = 0; i < c->q8g.size();) {
         auto& e = c->q8g[i];
         if (s && memcmp(&e.s, s, sizeof *s)) { i++; continue; }
-        if (e.exec) hipGraphExecDestroy(e.exec);
-        if (e.graph) hipGraphDestroy(e.graph);
+        destroy_graph(e.cg);
         c->q8g.erase(c->q8g.begin() + (long)i);
     }
 }
 extern "C" void rama_internal_drop_q8_graphs(rama_ctx* c) { if (c) drop_q8_graphs(c, nullptr); }      // q8_model.hip: a freed Q8 model's steps
 
 static void drop_graph(rama_ctx* c) {
-    if (c->bc.exec) { hipGraphExecDestroy(c->bc.exec); c->bc.exec = nullptr; }
-    if (c->bc.graph) { hipGraphDestroy(c->bc.graph); c->bc.graph = nullptr; }
+    destroy_graph(c->bc.cg);
     c->bc.graph_bucket = -1;
-    for (auto& g : c->gc) {
-        if (g.exec) hipGraphExecDestroy(g.exec);
-        if (g.graph) hipGraphDestroy(g.graph);
-        g = GraphCache();
-    }
-    for (auto& e : c->sg) {
-        if (e.g.exec) hipGraphExecDestroy(e.g.exec);
-        if (e.g.graph) hipGraphDestroy(e.g.graph);
-    }
+    for (auto& g : c->gc) { destroy_graph(g.cg); g = GraphCache(); }
+    for (auto& e : c->sg) destroy_graph(e.g.cg);
     c->sg.clear();
     drop_q8_graphs(c, nullptr);
 }
@@ -449,6 +451,30 @@ static int handoff_check(rama_ctx* c) {
         hipStreamSynchronize(c->stream);
         return fail(RAMA_EINVAL, perr >= 0x3000ull ? "one-launch stage: a hand-off timed out" : "attention+Wo launch: hand-off timed out", __FILE__, __LINE__);
     }
+    return 0;
+}
+
+// g = the launches `enqueue` puts on the stream, captured and instantiated (whatever g held goes first).  The capture always ends -- a stream
+// must never be left capturing --, and an error of `enqueue` comes before the capture's own status.  rama_ctx::handoff_dirty is saved and
+// cleared around the capture: what the enqueue sets is a property of the GRAPH (g.handoff), which replay_graph re-arms at every launch.
+template <class Enqueue>
+static int capture_graph(rama_ctx* c, CapturedGraph& g, Enqueue&& enqueue) {
+    destroy_graph(g);
+    HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+    const bool dirty_before = c->handoff_dirty;
+    c->handoff_dirty = false;
+    const int rc = enqueue();
+    hipError_t err = hipStreamEndCapture(c->stream, &g.graph);
+    g.handoff = c->handoff_dirty;
+    c->handoff_dirty = dirty_before;
+    if (rc) { destroy_graph(g); return rc; }
+    if (err == hipSuccess) err = hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0);
+    if (err != hipSuccess) { destroy_graph(g); return fail((int)err, "graph capture", __FILE__, __LINE__); }
+    return 0;
+}
+static int replay_graph(rama_ctx* c, const CapturedGraph& g) {
+    HIPCHK(hipGraphLaunch(g.exec, c->stream));
+    if (g.handoff) c->handoff_dirty = true;
     return 0;
 }
 
@@ -1683,29 +1709,18 @@ static int run_stage(rama_ctx* c, const rama_config* cfg, const rama_weights* w,
             size_t old = 0;
             for (size_t i = 1; i < c->sg.size(); i++) if (c->sg[i].used < c->sg[old].used) old = i;
             HIPCHK(hipStreamSynchronize(c->stream));
-            if (c->sg[old].g.exec) hipGraphExecDestroy(c->sg[old].g.exec);
-            if (c->sg[old].g.graph) hipGraphDestroy(c->sg[old].g.graph);
+            destroy_graph(c->sg[old].g.cg);
             c->sg.erase(c->sg.begin() + (long)old);
         }
         rama_ctx::StageGraph e;
-        const bool dirty_before = c->handoff_dirty;
-        c->handoff_dirty = false;
-        HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-        const int rc = enqueue_stage(c, cfg, w, s, st);
-        const hipError_t err = hipStreamEndCapture(c->stream, &e.g.graph);
-        e.g.handoff = c->handoff_dirty;
-        c->handoff_dirty = dirty_before;
-        if (rc) { if (e.g.graph) hipGraphDestroy(e.g.graph); return rc; }
-        HIPCHK(err);
-        HIPCHK(hipGraphInstantiate(&e.g.exec, e.g.graph, nullptr, nullptr, 0));
+        const int rc = capture_graph(c, e.g.cg, [&] { return enqueue_stage(c, cfg, w, s, st); });
+        if (rc) return rc;
         e.g.cfg = *cfg; e.g.w = *w; e.g.s = *s; e.g.valid = true; e.g.copies_gen = rama_internal_copies_generation(); e.st = *st; e.variant = variant;
         c->sg.push_back(e);
         hit = &c->sg.back();
     }
     hit->used = ++c->sg_clock;
-    HIPCHK(hipGraphLaunch(hit->g.exec, c->stream));
-    if (hit->g.handoff) c->handoff_dirty = true;
-    return 0;
+    return replay_graph(c, hit->g.cg);
 }
 
 static int check_stage(const rama_config* cfg, const rama_weights* w, const rama_run_state* s, const rama_stage* st) {
@@ -2092,6 +2107,29 @@ static int launch_mf(rama_ctx* c, MfParams& p, int pt) {
     return 0;
 }
 
+// n token ids -- and, with seqs_dev, the sequence table of n independent sequences: cache bases and position of each, nothing produced yet --
+// to the device through the context's pinned staging buffer: the caller's arrays may be gone before the copies run.  Synchronises first,
+// after which the pinned buffer is free again.
+static int stage_tokens(rama_ctx* c, int* toks_dev, const int32_t* tokens_host, int n, SeqSlot* seqs_dev = nullptr,
+                        const rama_run_state* states = nullptr, const int32_t* pos_host = nullptr) {
+    REQUIRE(n >= 1 && n <= kMfMaxTok, RAMA_EINVAL, "token batch: more tokens than the staging buffer holds");
+    HIPCHK(hipStreamSynchronize(c->stream));
+    memcpy(c->pinned_tok, tokens_host, sizeof(int) * n);
+    HIPCHK(hipMemcpyAsync(toks_dev, c->pinned_tok, sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
+    if (!seqs_dev) return 0;
+    SeqSlot* slots = reinterpret_cast<SeqSlot*>(c->pinned_tok + kMfMaxTok);
+    for (int i = 0; i < n; i++) { slots[i].kc = states[i].key_cache; slots[i].vc = states[i].value_cache; slots[i].pos = pos_host[i]; slots[i].pad = 0; }
+    HIPCHK(hipMemcpyAsync(seqs_dev, slots, sizeof(SeqSlot) * n, hipMemcpyHostToDevice, c->stream));
+    return 0;
+}
+
+// row i of the logits slab lg [n, V] to sequence i's run state
+static int copy_out_logits(rama_ctx* c, const rama_run_state* states, const float* lg, int n, int V) {
+    for (int i = 0; i < n; i++)
+        HIPCHK(hipMemcpyAsync(states[i].logits, lg + (size_t)i * V, sizeof(float) * V, hipMemcpyDeviceToDevice, c->stream));
+    return 0;
+}
+
 // p.w[0..n) = layer li of the given row-major tensors, or of their tile-order copies when the model has them all
 static void mf_weights(const rama_ctx* c, MfParams& p, int n, const float* const* base, size_t per_layer, size_t li) {
     const float* t[3] = {nullptr, nullptr, nullptr};
@@ -2123,8 +2161,7 @@ static int ensure_batch_scratch(rama_ctx* c, const rama_config* cfg, bool with_l
     if (need > c->pf_floats) {
         if (c->pf_blob) { HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipFree(c->pf_blob)); c->pf_blob = nullptr; }
         // the chained-batch graph has the old scratch pointers baked in: it must not be replayed on freed memory
-        if (c->bc.exec) { hipGraphExecDestroy(c->bc.exec); c->bc.exec = nullptr; }
-        if (c->bc.graph) { hipGraphDestroy(c->bc.graph); c->bc.graph = nullptr; }
+        destroy_graph(c->bc.cg);
         c->bc.graph_bucket = -1;
         if (set_device(c)) return 1;
         HIPCHK(hipMalloc(&c->pf_blob, need * sizeof(float)));
@@ -2382,9 +2419,7 @@ static int prefill_chain(rama_ctx* c, const rama_config* cfg, const rama_weights
     const int n_batch = n_tokens - 1;                             // the last position runs as forward()
     for (int c0 = 0; c0 < n_batch; c0 += kGcMaxTok) {
         const int nt = std::min(kGcMaxTok, n_batch - c0), p0 = pos0 + c0;
-        HIPCHK(hipStreamSynchronize(c->stream));                  // the pinned staging buffer is free again
-        memcpy(c->pinned_tok, tokens_host + c0, sizeof(int) * nt);
-        HIPCHK(hipMemcpyAsync(toks, c->pinned_tok, sizeof(int) * nt, hipMemcpyHostToDevice, c->stream));
+        rc = stage_tokens(c, toks, tokens_host + c0, nt); if (rc) return rc;
         hipLaunchKernelGGL(embed_rows_kernel, dim3((dim + 255) / 256, nt), dim3(256), 0, c->stream, X, w->token_embedding_table, (const int*)toks, nt, dim);
         LAUNCHCHK();
         rc = chain_batch_layers(c, cfg, w, cb, nt, p0, s->key_cache, s->value_cache, nullptr); if (rc) return rc;
@@ -2403,16 +2438,9 @@ static int decode_batch_chain(rama_ctx* c, const rama_config* cfg, const rama_we
     ChainScratch sc{};
     int rc = chain_batch_setup(c, cfg, w, true, &sc, done); if (rc || !*done) return rc;
     c->embedded_x = nullptr; c->host_pos = -1;
-    SeqSlot* slots = reinterpret_cast<SeqSlot*>(c->pinned_tok + kMfMaxTok);
     for (int c0 = 0; c0 < n_seq; c0 += kGcMaxTok) {
         const int nt = std::min(kGcMaxTok, n_seq - c0);
-        HIPCHK(hipStreamSynchronize(c->stream));                  // the pinned staging buffers are free again
-        for (int i = 0; i < nt; i++) {
-            c->pinned_tok[i] = tokens_host[c0 + i];
-            slots[i].kc = states[c0 + i].key_cache; slots[i].vc = states[c0 + i].value_cache; slots[i].pos = pos_host[c0 + i]; slots[i].pad = 0;
-        }
-        HIPCHK(hipMemcpyAsync(sc.toks, c->pinned_tok, sizeof(int) * nt, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(sc.seqs, slots, sizeof(SeqSlot) * nt, hipMemcpyHostToDevice, c->stream));
+        rc = stage_tokens(c, sc.toks, tokens_host + c0, nt, sc.seqs, states + c0, pos_host + c0); if (rc) return rc;
         hipLaunchKernelGGL(embed_rows_kernel, dim3((dim + 255) / 256, nt), dim3(256), 0, c->stream, sc.b.X, w->token_embedding_table, (const int*)sc.toks, nt, dim);
         LAUNCHCHK();
         rc = chain_batch_layers(c, cfg, w, sc.b, nt, 0, nullptr, nullptr, sc.seqs); if (rc) return rc;
@@ -2421,8 +2449,7 @@ static int decode_batch_chain(rama_ctx* c, const rama_config* cfg, const rama_we
         GemmChainParams p{};
         p.w[0] = sc.ccls; p.nmat = 1; p.K = dim; p.rows = V; p.x = sc.b.XN; p.xstride = dim; p.o[0] = sc.LG; p.ostride = V; p.n_tok = nt;
         rc = launch_gemm_chain<CEPI_STORE>(c, p); if (rc) return rc;
-        for (int i = 0; i < nt; i++)
-            HIPCHK(hipMemcpyAsync(states[c0 + i].logits, sc.LG + (size_t)i * V, sizeof(float) * V, hipMemcpyDeviceToDevice, c->stream));
+        rc = copy_out_logits(c, states + c0, sc.LG, nt, V); if (rc) return rc;
     }
     return 0;
 }
@@ -2460,11 +2487,7 @@ int rama_prefill(rama_ctx* c, const rama_config* cfg, const rama_weights* w, ram
     for (int c0 = 0; c0 < n_tokens; c0 += per_pass) {
         const int nt = std::min(per_pass, n_tokens - c0), p0 = pos0 + c0;
         last_nt = nt;
-        // the ids go through the context's pinned staging buffer: the caller's array may be gone
-        // before the copy runs
-        HIPCHK(hipStreamSynchronize(c->stream));
-        memcpy(c->pinned_tok, tokens_host + c0, sizeof(int) * nt);
-        HIPCHK(hipMemcpyAsync(b.toks, c->pinned_tok, sizeof(int) * nt, hipMemcpyHostToDevice, c->stream));
+        rc = stage_tokens(c, b.toks, tokens_host + c0, nt); if (rc) return rc;
         hipLaunchKernelGGL(embed_tile_kernel, dim3((dim / 4 + 255) / 256, nt), dim3(256), 0, c->stream, b.X, w->token_embedding_table, (const int*)b.toks, nt, dim);
         LAUNCHCHK();
         rc = run_layers_batched(c, cfg, w, b, nt, p0, s->key_cache, s->value_cache, false, p0 + nt, &nslab);
@@ -2536,74 +2559,16 @@ int rama_decode_batch(rama_ctx* c, const rama_config* cfg, const rama_weights* w
     if (c->tune_tiled) { rc = rama_internal_model_ensure(c, w, 2); if (rc) return rc; }
     rc = ensure_batch_scratch(c, cfg, true, &b); if (rc) return rc;
     c->embedded_x = nullptr; c->host_pos = -1;
-    // ids and the sequence table go through pinned staging (the source arrays are the caller's / locals)
-    HIPCHK(hipStreamSynchronize(c->stream));
-    SeqSlot* slots = reinterpret_cast<SeqSlot*>(c->pinned_tok + kMfMaxTok);
-    for (int i = 0; i < n_seq; i++) {
-        c->pinned_tok[i] = tokens_host[i];
-        slots[i].kc = states[i].key_cache; slots[i].vc = states[i].value_cache; slots[i].pos = pos_host[i]; slots[i].pad = 0;
-    }
-    HIPCHK(hipMemcpyAsync(b.toks, c->pinned_tok, sizeof(int) * n_seq, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(b.seqs, slots, sizeof(SeqSlot) * n_seq, hipMemcpyHostToDevice, c->stream));
+    rc = stage_tokens(c, b.toks, tokens_host, n_seq, b.seqs, states, pos_host); if (rc) return rc;
     rc = enqueue_batch_pass(c, cfg, w, b, n_seq, tmax);
     if (rc) return rc;
-    for (int i = 0; i < n_seq; i++)
-        HIPCHK(hipMemcpyAsync(states[i].logits, b.LG + (size_t)i * V, sizeof(float) * V, hipMemcpyDeviceToDevice, c->stream));
-    return 0;
+    return copy_out_logits(c, states, b.LG, n_seq, V);
 }
 
 // ---- the same pass CHAINED ON THE DEVICE: every sequence's (token, position) lives in device memory, a step ends with
 // one argmax per sequence that writes the next token and advances the position, and a step is one hipGraph replay --
 // no per-sequence download, no host round trip per step (rama_decode_batch costs one call and n_seq 4-byte downloads
 // per step when the tokens are fed back through the host).
-struct BatchArgmaxParams { const float* logits; int n; int* toks; SeqSlot* seqs; int* out; int out_cap; int* ring; };      // ring: host-visible copy of out, token + 1 (0: not yet)
-__global__ __launch_bounds__(1024) void argmax_batch_kernel(BatchArgmaxParams p) {
-    // Device::sample at temperature 0 per sequence (cpu.rs:163-167: the LAST maximal index), then mod.rs:196-203:
-    // token = next, pos += 1
-    __shared__ float s_v[16];
-    __shared__ int s_i[16];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* lg = p.logits + (size_t)b * p.n;
-    float bv = -INFINITY; int bi = -1;
-    const int n4 = p.n >> 2;                                      // rows of the logits slab are 16-byte aligned (n % 4 == 0)
-    const f4* l4 = reinterpret_cast<const f4*>(lg);
-    for (int i0 = tid; i0 < n4; i0 += 8 * 1024) {
-        f4 v[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) { const int i = i0 + u * 1024; v[u] = i < n4 ? l4[i] : f4{-INFINITY, -INFINITY, -INFINITY, -INFINITY}; }
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            const int i = i0 + u * 1024;
-            if (i < n4) {
-                if (!(bv > v[u].x)) { bv = v[u].x; bi = 4 * i; }
-                if (!(bv > v[u].y)) { bv = v[u].y; bi = 4 * i + 1; }
-                if (!(bv > v[u].z)) { bv = v[u].z; bi = 4 * i + 2; }
-                if (!(bv > v[u].w)) { bv = v[u].w; bi = 4 * i + 3; }
-            }
-        }
-    }
-    const float wm = wave_max(bv);
-    const int wi = wave_max_i(bv == wm ? bi : -1);
-    if (lane == 0) { s_v[wave] = wm; s_i[wave] = wi; }
-    __syncthreads();
-    if (tid == 0) {
-        float v = s_v[0]; int idx = s_i[0];
-        for (int w = 1; w < 16; w++) {
-            const float ov = s_v[w]; const int oi = s_i[w];
-            if (oi >= 0 && (idx < 0 || ov > v || (ov == v && oi > idx))) { v = ov; idx = oi; }
-        }
-        idx = idx < 0 ? 0 : idx;
-        p.toks[b] = idx;
-        p.seqs[b].pos += 1;
-        const int k = p.seqs[b].pad;                              // tokens this sequence has produced so far
-        if (k < p.out_cap) {
-            p.out[(size_t)b * p.out_cap + k] = idx;
-            if (p.ring) __hip_atomic_store(p.ring + (size_t)b * p.out_cap + k, idx + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-        p.seqs[b].pad = k + 1;
-    }
-}
-
 // per_seq == nullptr: the greedy chain (argmax_batch_kernel); else every step ends in the batched top-p sampler.  Every argument is
 // checked before anything of the previous chain is touched.
 static int batch_begin(rama_ctx* c, const rama_config* cfg, const rama_weights* w, const rama_run_state* states,
@@ -2652,13 +2617,7 @@ static int batch_begin(rama_ctx* c, const rama_config* cfg, const rama_weights* 
         bc.out_cap = max_steps;
     }
     memset(bc.ring, 0, sizeof(int) * (size_t)kMfMaxTok * bc.out_cap);      // (the stream was drained above: nothing is on its way)
-    SeqSlot* slots = reinterpret_cast<SeqSlot*>(c->pinned_tok + kMfMaxTok);
-    for (int i = 0; i < n_seq; i++) {
-        c->pinned_tok[i] = tokens_host[i];
-        slots[i].kc = states[i].key_cache; slots[i].vc = states[i].value_cache; slots[i].pos = pos_host[i]; slots[i].pad = 0;
-    }
-    HIPCHK(hipMemcpyAsync(bc.toks, c->pinned_tok, sizeof(int) * n_seq, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(bc.seqs, slots, sizeof(SeqSlot) * n_seq, hipMemcpyHostToDevice, c->stream));
+    rc = stage_tokens(c, bc.toks, tokens_host, n_seq, bc.seqs, states, pos_host); if (rc) return rc;
     bc.sampled = per_seq != nullptr;
     if (per_seq) {
         // the sampling records and the forced lists go to the device once; a step reads them there
@@ -2734,18 +2693,15 @@ int rama_decode_batch_steps(rama_ctx* c, int n_steps) {
             rc = enqueue_batch_finish(c, b); if (rc) return rc;
         } else {
             if (bc.graph_bucket != bucket) {
-                if (bc.exec) { hipGraphExecDestroy(bc.exec); bc.exec = nullptr; }
-                if (bc.graph) { hipGraphDestroy(bc.graph); bc.graph = nullptr; }
-                HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-                rc = enqueue_batch_pass(c, cfg, &bc.w, b, bc.n_seq, bucket * 256);
-                if (!rc) rc = enqueue_batch_finish(c, b);
-                const hipError_t e = hipStreamEndCapture(c->stream, &bc.graph);
+                bc.graph_bucket = -1;
+                rc = capture_graph(c, bc.cg, [&] {
+                    const int re = enqueue_batch_pass(c, cfg, &bc.w, b, bc.n_seq, bucket * 256);
+                    return re ? re : enqueue_batch_finish(c, b);
+                });
                 if (rc) return rc;
-                HIPCHK(e);
-                HIPCHK(hipGraphInstantiate(&bc.exec, bc.graph, nullptr, nullptr, 0));
                 bc.graph_bucket = bucket;
             }
-            HIPCHK(hipGraphLaunch(bc.exec, c->stream));
+            rc = replay_graph(c, bc.cg); if (rc) return rc;
         }
         bc.pos_max++; bc.steps_done++;
     }
@@ -2867,23 +2823,16 @@ int rama_decode_steps(rama_ctx* c, const rama_config* cfg, const rama_weights* w
             if (M > 1 && n_steps - i >= M && variant_at(c->host_pos + M - 1) == v) take = M;   // the variant changes at most once, monotonically
             GraphCache& g = c->gc[v + (take > 1 ? 4 : 0)];
             if (!same_capture(g, cfg, w, s) || g.steps != take) {
-                if (g.exec) hipGraphExecDestroy(g.exec);
-                if (g.graph) hipGraphDestroy(g.graph);
-                g = GraphCache();
-                const bool dirty_before = c->handoff_dirty;
-                c->handoff_dirty = false;
-                HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-                for (int k = 0; k < take && !rc; k++) rc = enqueue_decode_step(c, cfg, w, s);
-                hipError_t e = hipStreamEndCapture(c->stream, &g.graph);
-                g.handoff = c->handoff_dirty;
-                c->handoff_dirty = dirty_before;
+                g.valid = false;
+                rc = capture_graph(c, g.cg, [&] {
+                    int re = 0;
+                    for (int k = 0; k < take && !re; k++) re = enqueue_decode_step(c, cfg, w, s);
+                    return re;
+                });
                 if (rc) return rc;
-                HIPCHK(e);
-                HIPCHK(hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0));
                 g.cfg = *cfg; g.w = *w; g.s = *s; g.valid = true; g.copies_gen = rama_internal_copies_generation(); g.steps = take;
             }
-            HIPCHK(hipGraphLaunch(g.exec, c->stream));
-            if (g.handoff) c->handoff_dirty = true;
+            rc = replay_graph(c, g.cg); if (rc) return rc;
         } else {
             rc = enqueue_decode_step(c, cfg, w, s);
             if (rc) return rc;
@@ -3059,282 +3008,105 @@ int rama_generate_stream(rama_ctx* c, const rama_config* cfg, const rama_weights
     return 0;
 }
 
+// rama_set_tuning's keys, one row each: the member it stores, the values it takes -- a range, a short set, or a predicate with its wording --
+// and whether setting it synchronises the stream and drops the captured graphs (kStoreOnly: the switches of the recording 1:1 ops and of the
+// prompt path, which no captured launch depends on, only store).
+struct TuneKey {
+    const char* key;
+    int rama_ctx::* member;
+    bool drops;
+    int lo, hi;                  // lo..hi (hi = INT_MAX: no upper end) ...
+    int set[3]; int n_set;       // ... or, n_set > 0, one of set[0..n_set) ...
+    bool (*ok)(int); const char* ok_text;      // ... or whatever ok() takes, worded ok_text
+};
+constexpr bool kDrop = true, kStoreOnly = false;
+static constexpr TuneKey range(const char* key, int rama_ctx::* m, bool drops, int lo, int hi) { return {key, m, drops, lo, hi, {0, 0, 0}, 0, nullptr, nullptr}; }
+static constexpr TuneKey one_of(const char* key, int rama_ctx::* m, bool drops, int a, int b) { return {key, m, drops, 0, 0, {a, b, 0}, 2, nullptr, nullptr}; }
+static constexpr TuneKey one_of(const char* key, int rama_ctx::* m, bool drops, int a, int b, int c) { return {key, m, drops, 0, 0, {a, b, c}, 3, nullptr, nullptr}; }
+static constexpr TuneKey pred(const char* key, int rama_ctx::* m, bool drops, bool (*ok)(int), const char* text) { return {key, m, drops, 0, 0, {0, 0, 0}, 0, ok, text}; }
+static bool chain_resid_d_ok(int v) { return v == 0 || v == -1 || ((v / 100 == 1 || v / 100 == 2 || v / 100 == 4) && (v % 100 == 16 || v % 100 == 32)); }
+static bool chain_d_ok(int v) { return v == 0 || (v >= 116 && v <= 432); }
+static bool graph_steps_ok(int v) { return v == -1 || (v >= 1 && v <= 32); }
+
+static constexpr TuneKey kTuneKeys[] = {
+    range("ref_order", &rama_ctx::tune_ref_order, kDrop, 0, 3),      // (+ tune_tol, tune_bar: see rama_set_tuning)
+    range("lane_reduce", &rama_ctx::tune_lane_reduce, kDrop, 0, 2),
+    range("bar_pos", &rama_ctx::tune_bar_pos, kDrop, 0, INT_MAX),
+    range("tol_mask", &rama_ctx::tune_tol_mask, kDrop, 0, 127),
+    range("geom", &rama_ctx::tune_geom, kDrop, 0, 4),
+    range("resid_r2", &rama_ctx::tune_resid_r2, kDrop, 0, 3),
+    range("solo", &rama_ctx::tune_solo, kDrop, -1, 1),
+    range("w13i", &rama_ctx::tune_w13i, kDrop, 0, 1),
+    range("fused", &rama_ctx::tune_fused, kDrop, -1, 1),
+    range("fused_solo", &rama_ctx::tune_fused_solo, kDrop, -1, 1),
+    range("merge", &rama_ctx::tune_merge, kDrop, -1, 1),
+    range("split_pos", &rama_ctx::tune_split_pos, kDrop, -1, INT_MAX),
+    range("attn_nsplit", &rama_ctx::tune_attn_nsplit, kDrop, 0, 32),      // (+ attn_part goes: see rama_set_tuning)
+    one_of("attn_waves", &rama_ctx::tune_attn_waves, kDrop, 4, 8, 16),
+    range("attn_nt", &rama_ctx::tune_attn_nt, kDrop, 0, 1),
+    one_of("attn_u", &rama_ctx::tune_attn_u, kDrop, 8, 16),
+    range("combine_v", &rama_ctx::tune_combine_v, kDrop, 0, 1),
+    range("small_attn", &rama_ctx::tune_small_attn, kDrop, -1, 1),
+    one_of("small_attn_waves", &rama_ctx::tune_small_waves, kDrop, 4, 8),
+    range("small_attn_pos", &rama_ctx::tune_small_pos, kDrop, 0, INT_MAX),
+    pred("graph_steps", &rama_ctx::tune_graph_steps, kDrop, graph_steps_ok, "-1 or 1..32"),
+    range("prefill", &rama_ctx::tune_prefill, kStoreOnly, 0, 1),
+    one_of("prefill_tok", &rama_ctx::tune_prefill_tok, kDrop, 64, 128),
+    range("prefill_attn", &rama_ctx::tune_prefill_attn, kStoreOnly, 0, 1),
+    range("tiled", &rama_ctx::tune_tiled, kDrop, 0, 1),
+    range("norm_in_gemm", &rama_ctx::tune_norm_in_gemm, kDrop, 0, 1),
+    range("topp_sort", &rama_ctx::tune_topp_sort, kDrop, 0, 1),
+    range("topp_pairs", &rama_ctx::tune_topp_pairs, kDrop, 0, 1),
+    range("topp_dist", &rama_ctx::tune_topp_dist, kDrop, 0, 1),
+    one_of("topp_block", &rama_ctx::tune_topp_block, kDrop, 512, 1024, 2048),
+    range("topp_keep_sums", &rama_ctx::tune_topp_keep_sums, kDrop, 0, 1),
+    range("chain", &rama_ctx::tune_chain, kDrop, 0, 1),
+    pred("chain_d", &rama_ctx::tune_chain_d, kDrop, chain_d_ok, "0 or 100 W + D (116..432)"),
+    pred("chain_resid_d", &rama_ctx::tune_chain_resid_d, kDrop, chain_resid_d_ok, "-1, 0 or 100 W + D, W in {1, 2, 4}, D in {16, 32}"),
+    range("chain_lead_w", &rama_ctx::tune_chain_lead_w, kDrop, 0, 2),
+    range("chain_norm", &rama_ctx::tune_chain_norm, kDrop, 0, 1),
+    range("chain_lead", &rama_ctx::tune_chain_lead, kDrop, 0, 1),
+    range("chain_split", &rama_ctx::tune_chain_split, kDrop, 0, 1),
+    range("chain_views", &rama_ctx::tune_chain_views, kStoreOnly, 0, 1),
+    range("spread_pos", &rama_ctx::tune_spread_pos, kDrop, 64, 1 << 20),
+    range("attn_fv", &rama_ctx::tune_attn_fv, kDrop, 0, 1),
+    range("prefill_chain", &rama_ctx::tune_prefill_chain, kStoreOnly, 0, 1),
+    range("rope_batch", &rama_ctx::tune_rope_batch, kStoreOnly, 0, 1),
+    range("matmul_batch", &rama_ctx::tune_matmul_batch, kStoreOnly, 0, 1),
+    range("ew_batch", &rama_ctx::tune_ew_batch, kStoreOnly, 0, 1),
+    range("norm_fold", &rama_ctx::tune_norm_fold, kStoreOnly, 0, 1),
+    range("resid_fold", &rama_ctx::tune_resid_fold, kStoreOnly, 0, 1),
+    range("qkv_fold", &rama_ctx::tune_qkv_fold, kStoreOnly, 0, 1),
+};
+
+static bool tune_value_ok(const TuneKey& k, int v) {
+    if (k.ok) return k.ok(v);
+    if (!k.n_set) return v >= k.lo && v <= k.hi;
+    return std::find(k.set, k.set + k.n_set, v) != k.set + k.n_set;
+}
+static std::string tune_domain(const TuneKey& k) {
+    if (k.ok) return k.ok_text;
+    if (!k.n_set) return k.hi == INT_MAX ? ">= " + std::to_string(k.lo) : std::to_string(k.lo) + ".." + std::to_string(k.hi);
+    std::string d = std::to_string(k.set[0]);
+    for (int i = 1; i < k.n_set; i++) d += "|" + std::to_string(k.set[i]);
+    return d;
+}
+
+// a refused value leaves the setting, the stream and the graphs alone
 int rama_set_tuning(rama_ctx* c, const char* key, int value) {
     RAMA_ENTER(c);
     REQUIRE(c && key, RAMA_EINVAL, "set_tuning: NULL argument");
-    if (!strcmp(key, "split_pos")) {
-        REQUIRE(value >= -1, RAMA_EINVAL, "set_tuning: split_pos must be >= -1");
-        c->tune_split_pos = value;
-        hipStreamSynchronize(c->stream);
-        drop_graph(c);
-        return 0;
-    }
-    if (!strcmp(key, "resid_r2")) {
-        REQUIRE(value >= 0 && value <= 3, RAMA_EINVAL, "set_tuning: resid_r2 must be 0..3");
-        c->tune_resid_r2 = value;
-        hipStreamSynchronize(c->stream);
-        drop_graph(c);
-        return 0;
-    }
-    if (!strcmp(key, "prefill")) {
-        REQUIRE(value == 0 || value == 1, RAMA_EINVAL, "set_tuning: prefill must be 0 or 1");
-        c->tune_prefill = value;
-        return 0;
-    }
-    if (!strcmp(key, "fused") || !strcmp(key, "fused_solo")) {
-        REQUIRE(value >= -1 && value <= 1, RAMA_EINVAL, "set_tuning: fused / fused_solo must be -1, 0 or 1");
-        if (key[5]) c->tune_fused_solo = value; else c->tune_fused = value;
-        hipStreamSynchronize(c->stream);
-        drop_graph(c);
-        return 0;
-    }
-    if (!strcmp(key, "merge")) {
-        REQUIRE(value >= -1 && value <= 1, RAMA_EINVAL, "set_tuning: merge must be -1, 0 or 1");
-        c->tune_merge = value;
-        hipStreamSynchronize(c->stream);
-        drop_graph(c);
-        return 0;
-    }
-    if (!strcmp(key, "attn_nsplit") || !strcmp(key, "attn_nt")) {
-        const bool ns = !strcmp(key, "attn_nsplit");
-        REQUIRE(value >= 0 && value <= (ns ? 32 : 1), RAMA_EINVAL, "set_tuning: attn_nsplit must be 0..32, attn_nt 0 or 1");
+    const TuneKey* k = std::find_if(std::begin(kTuneKeys), std::end(kTuneKeys), [&](const TuneKey& e) { return !strcmp(key, e.key); });
+    REQUIRE(k != std::end(kTuneKeys), RAMA_EINVAL, "set_tuning: unknown key");
+    if (!tune_value_ok(*k, value)) return fail(RAMA_EINVAL, ("set_tuning: " + std::string(k->key) + " must be " + tune_domain(*k)).c_str(), __FILE__, __LINE__);
+    if (k->drops) {
         HIPCHK(hipStreamSynchronize(c->stream));
         drop_graph(c);
-        if (ns) { c->tune_attn_nsplit = value; if (c->attn_part) { hipFree(c->attn_part); c->attn_part = nullptr; c->attn_part_floats = 0; } }
-        else c->tune_attn_nt = value;
-        return 0;
     }
-    if (!strcmp(key, "small_attn_waves") || !strcmp(key, "small_attn_pos")) {
-        const bool wv = !strcmp(key, "small_attn_waves");
-        REQUIRE(wv ? (value == 4 || value == 8) : value >= 0, RAMA_EINVAL, "set_tuning: small_attn_waves must be 4 or 8, small_attn_pos >= 0");
-        HIPCHK(hipStreamSynchronize(c->stream));
-        drop_graph(c);
-        if (wv) c->tune_small_waves = value; else c->tune_small_pos = value;
-        return 0;
-    }
-    if (!strcmp(key, "combine_v")) {
-        REQUIRE(value == 0 || value == 1, RAMA_EINVAL, "set_tuning: combine_v must be 0 or 1");
-        HIPCHK(hipStreamSynchronize(c->stream));
-        drop_graph(c);
-        c->tune_combine_v = value;
-        return 0;
-    }
-    if (!strcmp(key, "norm_in_gemm")) {
-        REQUIRE(value == 0 || value == 1, RAMA_EINVAL, "set_tuning: norm_in_gemm must be 0 or 1");
-        c->tune_norm_in_gemm = value;
-        hipStreamSynchronize(c->stream);
-        drop_graph(c);
-        return 0;
-    }
-    if (!strcmp(key, "tiled")) {
-        REQUIRE(value == 0 || value == 1, RAMA_EINVAL, "set_tuning: tiled must be 0 or 1");
-        c->tune_tiled = value;
-        hipStreamSynchronize(c->stream);
-        drop_graph(c);
-        return 0;
-    }
-    if (!strcmp(key, "chain_lead")) {
-        REQUIRE(value == 0 || value == 1, RAMA_EINVAL, "set_tuning: chain_lead must be 0 or 1");
-        c->tune_chain_lead = value;
-        hipStreamSynchronize(c->stream);
-        drop_graph(c);
-        return 0;
-    }
-    if (!strcmp(key, "qkv_fold")) {
-        REQUIRE(value == 0 || value == 1, RAMA_EINVAL, "set_tuning: qkv_fold must be 0 or 1");
-        c->tune_qkv_fold = value;
-        return 0;
-    }
-    if (!strcmp(key, "resid_fold")) {
-        REQUIRE(value == 0 || value == 1, RAMA_EINVAL, "set_tuning: resid_fold must be 0 or 1");
-        c->tune_resid_fold = value;
-        return 0;
-    }
-    if (!strcmp(key, "norm_fold")) {
-        REQUIRE(value == 0 || value == 1, RAMA_EINVAL, "set_tuning: norm_fold must be 0 or 1");
-        c->tune_norm_fold = value;
-        return 0;
-    }
-    if (!strcmp(key, "chain_split")) {
-        REQUIRE(value == 0 || value == 1, RAMA_EINVAL, "set_tuning: chain_split must be 0 or 1");
-        c->tune_chain_split = value;
-        hipStreamSynchronize(c->stream);
-        drop_graph(c);
-        return 0;
-    }
-    if (!strcmp(key, "chain_lead_w")) {
-        REQUIRE(value >= 0 && value <= 2, RAMA_EINVAL, "set_tuning: chain_lead_w must be 0, 1 or 2");
-        c->tune_chain_lead_w = value;
-        hipStreamSynchronize(c->stream);
-        drop_graph(c);
-        return 0;
-    }
-    if (!strcmp(key, "chain_resid_d")) {
-        REQUIRE(value == 0 || value == -1 || ((value / 100 == 1 || value / 100 == 2 || value / 100 == 4) && (value % 100 == 16 || value % 100 == 32)), RAMA_EINVAL, "set_tuning: chain_resid_d must be -1, 0 or 100 W + D, W in {1, 2, 4}, D in {16, 32}");
-        c->tune_chain_resid_d = value;
-        hipStreamSynchronize(c->stream);
-        drop_graph(c);
-        return 0;
-    }
-    if (!strcmp(key, "ew_batch")) {
-        REQUIRE(value == 0 || value == 1, RAMA_EINVAL, "set_tuning: ew_batch must be 0 or 1");
-        c->tune_ew_batch = value;
-        return 0;
-    }
-    if (!strcmp(key, "matmul_batch")) {
-        REQUIRE(value == 0 || value == 1, RAMA_EINVAL, "set_tuning: matmul_batch must be 0 or 1");
-        c->tune_matmul_batch = value;
-        return 0;
-    }
-    if (!strcmp(key, "rope_batch")) {
-        REQUIRE(value == 0 || value == 1, RAMA_EINVAL, "set_tuning: rope_batch must be 0 or 1");
-        c->tune_rope_batch = value;
-        return 0;
-    }
-    if (!strcmp(key, "chain_views")) {
-        REQUIRE(value == 0 || value == 1, RAMA_EINVAL, "set_tuning: chain_views must be 0 or 1");
-        c->tune_chain_views = value;
-        return 0;
-    }
-    if (!strcmp(key, "chain_norm")) {
-        REQUIRE(value == 0 || value == 1, RAMA_EINVAL, "set_tuning: chain_norm must be 0 or 1");
-        c->tune_chain_norm = value;
-        hipStreamSynchronize(c->stream);
-        drop_graph(c);
-        return 0;
-    }
-    if (!strcmp(key, "prefill_chain")) {
-        REQUIRE(value == 0 || value == 1, RAMA_EINVAL, "set_tuning: prefill_chain must be 0 or 1");
-        c->tune_prefill_chain = value;
-        return 0;
-    }
-    if (!strcmp(key, "prefill_tok")) {
-        REQUIRE(value == 64 || value == 128, RAMA_EINVAL, "set_tuning: prefill_tok must be 64 or 128");
-        c->tune_prefill_tok = value;
-        hipStreamSynchronize(c->stream);
-        drop_graph(c);
-        return 0;
-    }
-    if (!strcmp(key, "prefill_attn")) {
-        REQUIRE(value == 0 || value == 1, RAMA_EINVAL, "set_tuning: prefill_attn must be 0 or 1");
-        c->tune_prefill_attn = value;
-        return 0;
-    }
-    if (!strcmp(key, "graph_steps")) {
-        REQUIRE(value == -1 || (value >= 1 && value <= 32), RAMA_EINVAL, "set_tuning: graph_steps must be -1 or 1..32");
-        HIPCHK(hipStreamSynchronize(c->stream));
-        drop_graph(c);
-        c->tune_graph_steps = value;
-        return 0;
-    }
-    if (!strcmp(key, "attn_u")) {
-        REQUIRE(value == 8 || value == 16, RAMA_EINVAL, "set_tuning: attn_u must be 8 or 16");
-        HIPCHK(hipStreamSynchronize(c->stream));
-        drop_graph(c);
-        c->tune_attn_u = value;
-        return 0;
-    }
-    if (!strcmp(key, "attn_waves")) {
-        REQUIRE(value == 16 || value == 8 || value == 4, RAMA_EINVAL, "set_tuning: attn_waves must be 16, 8 or 4");
-        HIPCHK(hipStreamSynchronize(c->stream));
-        drop_graph(c);
-        c->tune_attn_waves = value;
-        return 0;
-    }
-    if (!strcmp(key, "small_attn")) {
-        REQUIRE(value >= -1 && value <= 1, RAMA_EINVAL, "set_tuning: small_attn must be -1, 0 or 1");
-        c->tune_small_attn = value;
-        hipStreamSynchronize(c->stream);
-        drop_graph(c);
-        return 0;
-    }
-    if (!strcmp(key, "topp_block")) {
-        REQUIRE(value == 512 || value == 1024 || value == 2048, RAMA_EINVAL, "set_tuning: topp_block must be 512, 1024 or 2048");
-        c->tune_topp_block = value;
-        hipStreamSynchronize(c->stream);
-        drop_graph(c);
-        return 0;
-    }
-    if (!strcmp(key, "spread_pos")) {
-        REQUIRE(value >= 64 && value <= (1 << 20), RAMA_EINVAL, "set_tuning: spread_pos must be 64 .. 2^20");
-        c->tune_spread_pos = value;
-        hipStreamSynchronize(c->stream);
-        drop_graph(c);
-        return 0;
-    }
-    if (!strcmp(key, "attn_fv")) {
-        REQUIRE(value == 0 || value == 1, RAMA_EINVAL, "set_tuning: attn_fv must be 0 or 1");
-        c->tune_attn_fv = value;
-        hipStreamSynchronize(c->stream);
-        drop_graph(c);
-        return 0;
-    }
-    if (!strcmp(key, "topp_sort") || !strcmp(key, "topp_keep_sums") || !strcmp(key, "topp_pairs") || !strcmp(key, "topp_dist")) {
-        REQUIRE(value == 0 || value == 1, RAMA_EINVAL, "set_tuning: topp_sort / topp_keep_sums / topp_pairs / topp_dist must be 0 or 1");
-        if (!strcmp(key, "topp_sort")) c->tune_topp_sort = value; else if (!strcmp(key, "topp_pairs")) c->tune_topp_pairs = value;
-        else if (!strcmp(key, "topp_dist")) c->tune_topp_dist = value; else c->tune_topp_keep_sums = value;
-        hipStreamSynchronize(c->stream);
-        drop_graph(c);
-        return 0;
-    }
-    if (!strcmp(key, "w13i")) {
-        REQUIRE(value == 0 || value == 1, RAMA_EINVAL, "set_tuning: w13i must be 0 or 1");
-        c->tune_w13i = value;
-        hipStreamSynchronize(c->stream);
-        drop_graph(c);
-        return 0;
-    }
-    if (!strcmp(key, "solo")) {
-        REQUIRE(value >= -1 && value <= 1, RAMA_EINVAL, "set_tuning: solo must be -1, 0 or 1");
-        c->tune_solo = value;
-        hipStreamSynchronize(c->stream);
-        drop_graph(c);
-        return 0;
-    }
-    if (!strcmp(key, "ref_order")) {
-        REQUIRE(value >= 0 && value <= 3, RAMA_EINVAL, "set_tuning: ref_order must be 0, 1, 2 or 3");
-        c->tune_ref_order = value != 0; c->tune_tol = value == 2; c->tune_bar = value == 3;
-        hipStreamSynchronize(c->stream);
-        drop_graph(c);
-        return 0;
-    }
-    if (!strcmp(key, "bar_pos")) {
-        REQUIRE(value >= 0, RAMA_EINVAL, "set_tuning: bar_pos must be >= 0");
-        c->tune_bar_pos = value;
-        hipStreamSynchronize(c->stream);
-        drop_graph(c);
-        return 0;
-    }
-    if (!strcmp(key, "lane_reduce")) {
-        REQUIRE(value >= 0 && value <= 2, RAMA_EINVAL, "set_tuning: lane_reduce must be 0 (pairwise), 1 (strided) or 2 (sequential)");
-        c->tune_lane_reduce = value;
-        hipStreamSynchronize(c->stream);
-        drop_graph(c);
-        return 0;
-    }
-    if (!strcmp(key, "tol_mask")) {
-        REQUIRE(value >= 0 && value < 128, RAMA_EINVAL, "set_tuning: tol_mask must be 0..127");
-        c->tune_tol_mask = value;
-        hipStreamSynchronize(c->stream);
-        drop_graph(c);
-        return 0;
-    }
-    if (!strcmp(key, "chain") || !strcmp(key, "chain_d")) {
-        const bool cd = !strcmp(key, "chain_d");
-        REQUIRE(cd ? (value == 0 || (value >= 116 && value <= 432)) : (value == 0 || value == 1), RAMA_EINVAL, "set_tuning: chain must be 0 or 1, chain_d 0 or 100 W + D");
-        if (cd) c->tune_chain_d = value; else c->tune_chain = value;
-        hipStreamSynchronize(c->stream);
-        drop_graph(c);
-        return 0;
-    }
-    if (!strcmp(key, "geom")) {
-        REQUIRE(value >= 0 && value <= 4, RAMA_EINVAL, "set_tuning: geom must be 0..4");
-        c->tune_geom = value;
-        hipStreamSynchronize(c->stream);
-        drop_graph(c);
-        return 0;
-    }
-    return fail(RAMA_EINVAL, "set_tuning: unknown key", __FILE__, __LINE__);
+    c->*(k->member) = value;
+    if (k->member == &rama_ctx::tune_ref_order) { c->tune_ref_order = value != 0; c->tune_tol = value == 2; c->tune_bar = value == 3; }
+    if (k->member == &rama_ctx::tune_attn_nsplit && c->attn_part) { hipFree(c->attn_part); c->attn_part = nullptr; c->attn_part_floats = 0; }      // (sized by the slices per head)
+    return 0;
 }
 
 int rama_set_graph_mode(rama_ctx* c, int enabled) {
@@ -3611,22 +3383,17 @@ static int run_q8(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w,
     if (!hit) {
         if (c->q8g.size() >= 16) {
             HIPCHK(hipStreamSynchronize(c->stream));
-            for (auto& e : c->q8g) { if (e.exec) hipGraphExecDestroy(e.exec); if (e.graph) hipGraphDestroy(e.graph); }
+            for (auto& e : c->q8g) destroy_graph(e.cg);
             c->q8g.clear();
         }
         rama_ctx::Q8Graph e;
-        HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-        const int rc = enqueue();
-        const hipError_t err = hipStreamEndCapture(c->stream, &e.graph);
-        if (rc) { if (e.graph) hipGraphDestroy(e.graph); return rc; }
-        HIPCHK(err);
-        HIPCHK(hipGraphInstantiate(&e.exec, e.graph, nullptr, nullptr, 0));
+        const int rc = capture_graph(c, e.cg, enqueue);
+        if (rc) return rc;
         e.cfg = *cfg; e.w = *w; e.s = *s; e.variant = variant; e.chained = chained;
         c->q8g.push_back(e);
         hit = &c->q8g.back();
     }
-    HIPCHK(hipGraphLaunch(hit->exec, c->stream));
-    return 0;
+    return replay_graph(c, hit->cg);
 }
 
 int rama_q8_forward(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, rama_run_state* s, int token, int pos) {
@@ -3843,9 +3610,7 @@ int rama_q8_prefill(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* 
         c->embedded_x = nullptr; c->host_pos = -1;
         for (int c0 = 0; c0 < n_batch; c0 += kQ8bMaxTok) {
             const int nt = std::min(kQ8bMaxTok, n_batch - c0);
-            HIPCHK(hipStreamSynchronize(c->stream));              // the pinned staging buffer is free again
-            memcpy(c->pinned_tok, tokens_host + c0, sizeof(int) * nt);
-            HIPCHK(hipMemcpyAsync(b.toks, c->pinned_tok, sizeof(int) * nt, hipMemcpyHostToDevice, c->stream));
+            rc = stage_tokens(c, b.toks, tokens_host + c0, nt); if (rc) return rc;
             hipLaunchKernelGGL(embed_rows_kernel, dim3((cfg->dim + 255) / 256, nt), dim3(256), 0, c->stream, b.X, w->token_embedding_table,
                                (const int*)b.toks, nt, cfg->dim);
             LAUNCHCHK();
@@ -3882,15 +3647,7 @@ int rama_q8_decode_batch(rama_ctx* c, const rama_config* cfg, const rama_q8_weig
     Q8BatchScratch b{};
     rc = ensure_q8_batch_scratch(c, cfg, gs, &b); if (rc) return rc;
     c->embedded_x = nullptr; c->host_pos = -1;
-    // ids and the sequence table go through pinned staging (the source arrays are the caller's)
-    HIPCHK(hipStreamSynchronize(c->stream));
-    SeqSlot* slots = reinterpret_cast<SeqSlot*>(c->pinned_tok + kMfMaxTok);
-    for (int i = 0; i < n_seq; i++) {
-        c->pinned_tok[i] = tokens_host[i];
-        slots[i].kc = states[i].key_cache; slots[i].vc = states[i].value_cache; slots[i].pos = positions_host[i]; slots[i].pad = 0;
-    }
-    HIPCHK(hipMemcpyAsync(b.toks, c->pinned_tok, sizeof(int) * n_seq, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(b.seqs, slots, sizeof(SeqSlot) * n_seq, hipMemcpyHostToDevice, c->stream));
+    rc = stage_tokens(c, b.toks, tokens_host, n_seq, b.seqs, states, positions_host); if (rc) return rc;
     hipLaunchKernelGGL(embed_rows_kernel, dim3((dim + 255) / 256, n_seq), dim3(256), 0, c->stream, b.X, w->token_embedding_table, (const int*)b.toks, n_seq, dim);
     LAUNCHCHK();
     rc = q8_batch_layers(c, cfg, w, b, n_seq, 0, nullptr, nullptr, b.seqs); if (rc) return rc;
@@ -3901,7 +3658,5 @@ int rama_q8_decode_batch(rama_ctx* c, const rama_config* cfg, const rama_q8_weig
     p.w[0] = w->wcls; p.ws[0] = w->wcls_s; p.o[0] = b.LG;
     p.xq = b.xq; p.xs = b.xs; p.K = dim; p.rows = V; p.gs = gs; p.nmat = 1; p.n_tok = n_seq; p.ostride = V;
     rc = launch_q8_gemm<Q8EPI_STORE>(c, p); if (rc) return rc;
-    for (int i = 0; i < n_seq; i++)
-        HIPCHK(hipMemcpyAsync(states[i].logits, b.LG + (size_t)i * V, sizeof(float) * V, hipMemcpyDeviceToDevice, c->stream));
-    return 0;
+    return copy_out_logits(c, states, b.LG, n_seq, V);
 }

@@ -37,6 +37,22 @@ def test_rust_bindings_declare_every_header_symbol():
     assert len(declared) == len(set(declared))
 
 
+def test_tuning_key_table_matches_the_header():
+    """every key of rama_set_tuning's table (csrc/rama_api.hip kTuneKeys) is documented in the header's comment on
+    rama_set_tuning, and every key quoted there is in the table: 48 keys, none twice"""
+    src = (REPO / "rama_amd" / "csrc" / "rama_api.hip").read_text()
+    table = re.search(r"kTuneKeys\[\] = \{\n(.*?)\n\};", src, flags=re.S).group(1)
+    rows = [r for r in table.split("\n") if r.strip()]
+    keys = re.findall(r"^\s*(?:range|one_of|pred)\(\"([a-z0-9_]*)\",", table, flags=re.M)
+    assert len(keys) == len(rows), "a row of kTuneKeys the test cannot read"
+    assert len(keys) == 48 and len(set(keys)) == 48, sorted(k for k in keys if keys.count(k) > 1)
+    header = (REPO / "include" / "rama_hip.h").read_text()
+    doc = re.search(r"/\* Modes and performance knobs\..*?\*/\s*int\s+rama_set_tuning\(", header, flags=re.S).group(0)
+    assert doc.count("/*") == 1
+    documented = set(re.findall(r"\"([a-z0-9_]+)\"", doc))
+    assert documented == set(keys), documented ^ set(keys)
+
+
 def test_no_gpu_means_loud_failure():
     import torch
     if torch.cuda.is_available():
