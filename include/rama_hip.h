@@ -458,7 +458,7 @@ int  rama_q8_generate(rama_ctx *ctx, const rama_config *cfg, const rama_q8_weigh
                       int32_t *out_tokens_host);
 /* Q8 token batches: every weight pass is shared by up to 128 tokens (int8 matrix cores at group sizes 32 and multiples of
  * 64, a bytewise kernel otherwise).  The scratch belongs to the context and is sized by the first call (outside any capture);
- * these calls run eagerly in either graph mode.
+ * these calls run eagerly in either graph mode (the chained batch below captures its step).
  * o[t * d + i] = row i of matmul(xq[t], wq) for n_tok token rows: xq [n_tok, n], xs [n_tok, n / group_size]; bit for bit
  * n_tok calls of rama_q8_matmul */
 int  rama_q8_matmul_batch(rama_ctx *ctx, float *o, const int8_t *wq, const float *ws, const int8_t *xq, const float *xs,
@@ -471,6 +471,42 @@ int  rama_q8_prefill(rama_ctx *ctx, const rama_config *cfg, const rama_q8_weight
  * rama_q8_forward(tokens[i], positions[i]) would leave in its cache rows and logits (x / xb / q ... not maintained) */
 int  rama_q8_decode_batch(rama_ctx *ctx, const rama_config *cfg, const rama_q8_weights *w, const rama_run_state *states,
                           const int32_t *tokens_host, const int32_t *positions_host, int n_seq);
+
+/* rama_q8_decode_batch CHAINED ON THE DEVICE, with per-sequence sampling, forced prompts, step budgets and stop tokens.
+ * rama_q8_decode_batch_begin uploads every sequence's (token, position) and plan once; each step of
+ * rama_q8_decode_batch_steps is the batched pass followed by one pick per sequence on the device --
+ *   next = pos < n_forced ? forced[pos] : Device::sample(logits)      (a sample that keeps nothing gives token 0)
+ * -- so sequence i produces, bit for bit, the tokens rama_q8_generate / rama_q8_forward give it alone.  The logits stay in
+ * the context's scratch: states[i].logits is not written.  In graph mode a step is ONE hipGraph replay, and one captured
+ * graph serves the whole chain.
+ * A sequence is FINISHED once it has produced max_new tokens (forced ones included), or has just recorded a sampled token
+ * equal to stop_token (a forced token never stops it).  From then on it keeps its token and position, writes no more
+ * tokens, and its slot only rewrites its last cache row with the same bits; the other sequences run on.  per_seq == NULL:
+ * every sequence greedy, without stop token, max_steps tokens each.
+ * rama_q8_decode_batch_begin checks everything before it touches a running chain: RAMA_EINVAL for a bad record
+ * (temperature < 0, topp outside [0, 1], u outside [0, 1), NaN, n_forced < 0, max_new < 0, a token / forced token / stop
+ * token outside the vocabulary, position_i + min(max_new_i or max_steps, max_steps) > seq_len, a shared run state, n_seq
+ * outside 1..128) leaves the previous chain as it was.  RAMA_EUNSUP: a shape the Q8 token-batch pass does not take, or a
+ * plan that samples or forces on vocab_size > 32768.
+ * rama_q8_decode_batch_steps: RAMA_EINVAL beyond max_steps, and once the chain's model (rama_q8_model_free) or the run
+ * state of one of its sequences (rama_state_free) is gone.  rama_q8_prefill / rama_q8_decode_batch / rama_q8_forward on
+ * other run states between two calls are fine.
+ * rama_q8_decode_batch_tokens synchronises: sequence s's tokens at out_host[s * max_per_seq ..], its count in n_per_seq[s].
+ * rama_q8_decode_batch_stream_poll never touches the stream: tokens from.. of one sequence from its host-visible ring, and
+ * *finished (may be NULL) = 1 once the sequence has finished -- set after its last token is visible. */
+typedef struct {
+    float temperature, topp, u;                 /* Device::sample; temperature 0 = argmax */
+    const int32_t *forced; int32_t n_forced;    /* forced by ABSOLUTE position, as rama_decode_batch_begin_sampled */
+    int32_t max_new;                            /* tokens this sequence may produce, forced ones included; 0 = max_steps */
+    int32_t stop_token;                         /* -1 = none; a SAMPLED token equal to it is recorded, then the sequence is finished */
+} rama_q8_seq_plan;
+int  rama_q8_decode_batch_begin(rama_ctx *ctx, const rama_config *cfg, const rama_q8_weights *w, const rama_run_state *states,
+                                const int32_t *tokens_host, const int32_t *positions_host, int n_seq, int max_steps,
+                                const rama_q8_seq_plan *per_seq);
+int  rama_q8_decode_batch_steps(rama_ctx *ctx, int n_steps);
+int  rama_q8_decode_batch_tokens(rama_ctx *ctx, int32_t *out_host, int max_per_seq, int32_t *n_per_seq);
+int  rama_q8_decode_batch_stream_poll(rama_ctx *ctx, int seq, int from, int32_t *out_tokens_host, int max_tokens, int *n_ready,
+                                      int *finished);
 
 /* ---------------------------------------------------------------- measurement
  * HIP events on the context's stream (the stream the kernels are launched on). */

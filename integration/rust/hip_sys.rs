@@ -35,6 +35,11 @@ pub struct rama_run_state {
 pub struct rama_seq_sampling {
     pub temperature: f32, pub topp: f32, pub u: f32, pub forced: *const i32, pub n_forced: i32,
 }
+/// one sequence's sampler, forced prompt, step budget (0 = the chain's) and stop token (-1 = none) of the chained Q8 batch
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct rama_q8_seq_plan {
+    pub temperature: f32, pub topp: f32, pub u: f32, pub forced: *const i32, pub n_forced: i32, pub max_new: i32, pub stop_token: i32,
+}
 #[repr(C)] pub struct rama_q8_model { _p: [u8; 0] }
 /// a Q8_0 (llama2.c version-2) model as device pointers; `x_s` = the fp32 scales of the int8 tensor `x`
 #[repr(C)] #[derive(Clone, Copy)]
@@ -191,6 +196,13 @@ extern "C" {
                            tokens_host: *const i32, n_tokens: c_int, pos0: c_int) -> c_int;
     pub fn rama_q8_decode_batch(ctx: *mut rama_ctx, cfg: *const rama_config, w: *const rama_q8_weights, states: *const rama_run_state,
                                 tokens_host: *const i32, positions_host: *const i32, n_seq: c_int) -> c_int;
+    pub fn rama_q8_decode_batch_begin(ctx: *mut rama_ctx, cfg: *const rama_config, w: *const rama_q8_weights, states: *const rama_run_state,
+                                      tokens_host: *const i32, positions_host: *const i32, n_seq: c_int, max_steps: c_int,
+                                      per_seq: *const rama_q8_seq_plan) -> c_int;
+    pub fn rama_q8_decode_batch_steps(ctx: *mut rama_ctx, n_steps: c_int) -> c_int;
+    pub fn rama_q8_decode_batch_tokens(ctx: *mut rama_ctx, out_host: *mut i32, max_per_seq: c_int, n_per_seq: *mut i32) -> c_int;
+    pub fn rama_q8_decode_batch_stream_poll(ctx: *mut rama_ctx, seq: c_int, from: c_int, out_tokens_host: *mut i32, max_tokens: c_int,
+                                            n_ready: *mut c_int, finished: *mut c_int) -> c_int;
 }
 
 #[repr(C)] pub struct rama_pipe { _p: [u8; 0] }

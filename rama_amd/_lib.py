@@ -63,6 +63,12 @@ class rama_seq_sampling(C.Structure):
     _fields_ = [("temperature", C.c_float), ("topp", C.c_float), ("u", C.c_float), ("forced", C.POINTER(C.c_int32)), ("n_forced", C.c_int32)]
 
 
+class rama_q8_seq_plan(C.Structure):
+    """one sequence's sampler, forced prompt, step budget and stop token of the chained Q8 batch (rama_q8_decode_batch_begin)"""
+    _fields_ = [("temperature", C.c_float), ("topp", C.c_float), ("u", C.c_float), ("forced", C.POINTER(C.c_int32)), ("n_forced", C.c_int32),
+                ("max_new", C.c_int32), ("stop_token", C.c_int32)]
+
+
 class rama_pipe_plan(C.Structure):
     _fields_ = [("n_seq", C.c_int32), ("n_pos", C.c_int32), ("wrap", C.c_int32), ("prompt", C.POINTER(C.c_int32)), ("n_prompt", C.c_int32),
                 ("temperature", C.c_float), ("topp", C.c_float), ("u", C.c_float), ("out_tokens_dev", C.c_void_p)]
@@ -165,6 +171,10 @@ SIGNATURES = {
     "rama_q8_matmul_batch": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _int, _int]),
     "rama_q8_prefill": (_int, [_vp, _cfgp, C.POINTER(rama_q8_weights), _sp, i32p, _int, _int]),
     "rama_q8_decode_batch": (_int, [_vp, _cfgp, C.POINTER(rama_q8_weights), _sp, i32p, i32p, _int]),
+    "rama_q8_decode_batch_begin": (_int, [_vp, _cfgp, C.POINTER(rama_q8_weights), _sp, i32p, i32p, _int, _int, C.POINTER(rama_q8_seq_plan)]),
+    "rama_q8_decode_batch_steps": (_int, [_vp, _int]),
+    "rama_q8_decode_batch_tokens": (_int, [_vp, i32p, _int, i32p]),
+    "rama_q8_decode_batch_stream_poll": (_int, [_vp, _int, _int, i32p, _int, C.POINTER(_int), C.POINTER(_int)]),
 }
 
 _lib = None

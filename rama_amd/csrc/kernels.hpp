@@ -978,9 +978,41 @@ __global__ __launch_bounds__(1024) void argmax_kernel(ArgmaxParams p) {
 // what ends a step of the chained batch decode (rama_decode_batch_steps): one workgroup per sequence.  In the global namespace, where it was
 // first defined: its symbol is the name it carries in the committed profiles and resource listings.
 }  // namespace rama
-struct BatchArgmaxParams { const float* logits; int n; int* toks; rama::SeqSlot* seqs; int* out; int out_cap; int* ring; };      // ring: host-visible copy of out, token + 1 (0: not yet)
+// per-sequence ends of a chained batch (the Q8 chain, rama_q8_decode_batch_begin): one device table, so that a finish kernel carries one pointer
+struct BatchEnds {
+    int limit[128];                               // tokens a sequence may produce; a stop lowers it to what was produced
+    int stop[128];                                // the token whose sampling ends the sequence (-1: none)
+    int* done;                                    // [n_seq] host-visible: 1 once the sequence has finished
+};
+struct BatchArgmaxParams {
+    const float* logits; int n; int* toks; rama::SeqSlot* seqs; int* out; int out_cap; int* ring;      // ring: host-visible copy of out, token + 1 (0: not yet)
+    BatchEnds* ends;                              // NULL: none, every sequence runs on
+};
+// What ends a chained batch step for one sequence once the next token is known (thread 0 of its workgroup).  Without limits:
+// token = next, pos += 1, out / ring.  With limits a sequence that produces its last token -- the limit-th, or a sampled
+// (not forced) stop token -- records it and then KEEPS its token and position: the slot repeats the same forward in every
+// later step (the same cache row, the same bits), so no position runs on and no pass kernel needs a mask.
+__device__ __forceinline__ void batch_seq_advance(int b, int next, int pos, bool forced, int* toks, rama::SeqSlot* seqs, int* out, int out_cap,
+                                                  int* ring, BatchEnds* ends) {
+    const int k = seqs[b].pad;                                    // tokens this sequence has produced so far
+    if (k < out_cap) {
+        out[(size_t)b * out_cap + k] = next;
+        // the host may be polling this word while the chain runs on: one system-scope store
+        if (ring) __hip_atomic_store(ring + (size_t)b * out_cap + k, next + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    seqs[b].pad = k + 1;
+    if (ends && (k + 1 >= ends->limit[b] || (!forced && next == ends->stop[b]))) {
+        ends->limit[b] = k + 1;
+        __hip_atomic_store(ends->done + b, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);      // (after the ring word: who sees it set finds every token)
+        return;
+    }
+    toks[b] = next;
+    seqs[b].pos = pos + 1;
+}
+__device__ __forceinline__ bool batch_seq_finished(int b, const rama::SeqSlot* seqs, const BatchEnds* ends) { return ends && seqs[b].pad >= ends->limit[b]; }
 __global__ __launch_bounds__(1024) void argmax_batch_kernel(BatchArgmaxParams p) {
     using namespace rama;
+    if (batch_seq_finished(blockIdx.x, p.seqs, p.ends)) return;   // (uniform: the whole workgroup)
     // Device::sample at temperature 0 per sequence (cpu.rs:163-167: the LAST maximal index), then mod.rs:196-203:
     // token = next, pos += 1
     __shared__ float s_v[16];
@@ -1016,14 +1048,7 @@ __global__ __launch_bounds__(1024) void argmax_batch_kernel(BatchArgmaxParams p)
             if (oi >= 0 && (idx < 0 || ov > v || (ov == v && oi > idx))) { v = ov; idx = oi; }
         }
         idx = idx < 0 ? 0 : idx;
-        p.toks[b] = idx;
-        p.seqs[b].pos += 1;
-        const int k = p.seqs[b].pad;                              // tokens this sequence has produced so far
-        if (k < p.out_cap) {
-            p.out[(size_t)b * p.out_cap + k] = idx;
-            if (p.ring) __hip_atomic_store(p.ring + (size_t)b * p.out_cap + k, idx + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-        p.seqs[b].pad = k + 1;
+        batch_seq_advance(b, idx, p.seqs[b].pos, false, p.toks, p.seqs, p.out, p.out_cap, p.ring, p.ends);
     }
 }
 namespace rama {

@@ -19,7 +19,7 @@ extern "C" int rama_fill_synth(rama_ctx*, float*, size_t, uint64_t, uint64_t, ui
 extern "C" void* rama_internal_stream(rama_ctx* c);
 extern "C" int rama_internal_device(rama_ctx* c);
 extern "C" void rama_internal_rope_tables(const rama_config* cfg, std::vector<float>* re, std::vector<float>* im);   // model.hip
-extern "C" void rama_internal_drop_q8_graphs(rama_ctx* ctx);                                                         // rama_api.hip
+extern "C" void rama_internal_drop_q8_graphs(rama_ctx* ctx, const rama_q8_weights* freed);                                                      // rama_api.hip
 
 struct rama_q8_model {
     rama_config cfg{};
@@ -246,7 +246,7 @@ extern "C" int rama_q8_model_weights(const rama_q8_model* m, rama_q8_weights* w)
 extern "C" size_t rama_q8_model_bytes(const rama_q8_model* m) { return m ? m->streamed : 0; }
 extern "C" int rama_q8_model_free(rama_ctx* ctx, rama_q8_model* m) {
     if (!m) return 0;
-    if (ctx) { rama_sync(ctx); rama_internal_drop_q8_graphs(ctx); }      // captured Q8 steps hold the model's addresses (the fp32 graphs stay)
+    if (ctx) { rama_sync(ctx); rama_internal_drop_q8_graphs(ctx, &m->w); }      // captured Q8 steps hold the model's addresses (the fp32 graphs stay); a chained batch over it ends
     const int rc = m->blob ? rama_free(ctx, m->blob) : 0;
     delete m;
     return rc;

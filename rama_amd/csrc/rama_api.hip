@@ -180,8 +180,8 @@ struct rama_ctx {
     int8_t* q8_xq = nullptr; float* q8_xs = nullptr; size_t q8_cap = 0;
     struct Q8Graph { CapturedGraph cg; rama_config cfg{}; rama_q8_weights w{}; rama_run_state s{}; int variant = 0; int chained = 0; };
     std::vector<Q8Graph> q8g;
-    // Q8 token batches (rama_q8_prefill / rama_q8_decode_batch): row-major scratch for kQ8bMaxTok tokens, sized by the first call
-    // (never inside a capture; no graph holds it), see Q8BatchScratch
+    // Q8 token batches (rama_q8_prefill / rama_q8_decode_batch / the chained batch): row-major scratch for kQ8bMaxTok tokens, sized by
+    // the first call (never inside a capture; only the chained batch's step q8c.cg holds it, and goes when it moves), see Q8BatchScratch
     char* q8b_blob = nullptr; size_t q8b_cap = 0;
     int tune_split_pos = -1;               // attention runs split-T (+ combine launch) from this position on; -1 = by model size
     int tune_resid_r2 = 2;                 // Wo / W2 under geometry 3: 0 = 4-row workgroups, 1 = 2 rows x 8 waves (+0.45 %),
@@ -270,6 +270,26 @@ struct rama_ctx {
         ToppRow* rows = nullptr;           // [kMfMaxTok] every sequence's (T, topp, u, forced list)
         int* forced = nullptr; size_t forced_cap = 0;      // the forced lists, one after the other
     } bc;
+    // rama_q8_decode_batch_begin / _steps: the same for a Q8 model, with per-sequence ends (a step budget, a stop token).  A state of
+    // its own: the fp32 chain above neither sees nor shares any of it.
+    struct Q8Chain {
+        int n_seq = 0, max_steps = 0, out_cap = 0, steps_done = 0;      // out_cap: row stride of out / ring, >= every sequence's budget
+        bool live = false;                 // false once the model or a member's run state has been freed: rama_q8_decode_batch_steps refuses
+        int* toks = nullptr;               // [kMfMaxTok] the token each sequence feeds next
+        SeqSlot* seqs = nullptr;           // [kMfMaxTok] cache bases, position and tokens produced of every sequence
+        int* out = nullptr;                // [kMfMaxTok, out_cap] the tokens produced
+        int* ring = nullptr;               // the same, host-pinned and device-mapped: token + 1, 0 = not produced yet
+        int* ring_dev = nullptr;
+        BatchEnds* ends = nullptr;         // device: every sequence's budget (a stop lowers it) and stop token, and where `done` is
+        int* done = nullptr;               // [kMfMaxTok] host-pinned and device-mapped: 1 = the sequence has finished
+        int* done_dev = nullptr;
+        bool sampled = false;              // a step ends in the batched top-p sampler (a row samples, or is forced) instead of argmax_batch_kernel
+        ToppRow* rows = nullptr;           // [kMfMaxTok] every sequence's (T, topp, u, forced list)
+        int* forced = nullptr; size_t forced_cap = 0;
+        rama_config cfg{}; rama_q8_weights w{};
+        std::vector<rama_run_state> states;
+        CapturedGraph cg;                  // one step: nothing in its launch geometry depends on the positions
+    } q8c;
 };
 
 static int set_device(rama_ctx* c) { HIPCHK(hipSetDevice(c->device)); return 0; }
@@ -387,6 +407,11 @@ int rama_ctx_create(int device, void* hip_stream, rama_ctx** out) {
 
 // the captured Q8 steps: all of them (s == NULL) or those over one run state
 static void drop_q8_graphs(rama_ctx* c, const rama_run_state* s) {
+    // the chained batch's step: it goes with all Q8 graphs, and with a member's run state -- after which the chain is dead
+    bool member = false;
+    for (const auto& m : c->q8c.states) member = member || (s && m.key_cache == s->key_cache);
+    if (c->q8c.cg.exec && (!s || member)) { (void)hipStreamSynchronize(c->stream); destroy_graph(c->q8c.cg); }
+    if (member) c->q8c.live = false;
     bool any = false;
     for (auto& e : c->q8g) any = any || !s || !memcmp(&e.s, s, sizeof *s);
     if (!any) return;
@@ -398,7 +423,12 @@ static void drop_q8_graphs(rama_ctx* c, const rama_run_state* s) {
         c->q8g.erase(c->q8g.begin() + (long)i);
     }
 }
-extern "C" void rama_internal_drop_q8_graphs(rama_ctx* c) { if (c) drop_q8_graphs(c, nullptr); }      // q8_model.hip: a freed Q8 model's steps
+// q8_model.hip: a Q8 model (weights *freed) is about to go: the captured Q8 steps, and a chained batch over it is dead
+extern "C" void rama_internal_drop_q8_graphs(rama_ctx* c, const rama_q8_weights* freed) {
+    if (!c) return;
+    drop_q8_graphs(c, nullptr);
+    if (freed && c->q8c.n_seq > 0 && c->q8c.w.wq == freed->wq) c->q8c.live = false;
+}
 
 static void drop_graph(rama_ctx* c) {
     destroy_graph(c->bc.cg);
@@ -425,6 +455,9 @@ int rama_ctx_destroy(rama_ctx* c) {
     hipFree(c->topp_rk); hipFree(c->topp_bm); hipFree(c->topp_approx); hipFree(c->topp_dist); hipFree(c->topp_stats);
     hipFree(c->bc.toks); hipFree(c->bc.seqs); hipFree(c->bc.out); if (c->bc.ring) hipHostFree(c->bc.ring);
     hipFree(c->bc.rows); hipFree(c->bc.forced);
+    hipFree(c->q8c.toks); hipFree(c->q8c.seqs); hipFree(c->q8c.out); hipFree(c->q8c.ends); hipFree(c->q8c.rows); hipFree(c->q8c.forced);
+    if (c->q8c.ring) hipHostFree(c->q8c.ring);
+    if (c->q8c.done) hipHostFree(c->q8c.done);
     hipFree(c->tb.keys); hipFree(c->tb.vals); hipFree(c->tb.bp); hipFree(c->tb.bi); hipFree(c->tb.rk); hipFree(c->tb.bm);
     hipFree(c->tb.bcount); hipFree(c->tb.stats); hipFree(c->tb.m); hipFree(c->tb.rows_dev);
     hipFree(c->q8_xq); hipFree(c->q8_xs); hipFree(c->q8b_blob);
@@ -3518,6 +3551,7 @@ static int ensure_q8_batch_scratch(rama_ctx* c, const rama_config* cfg, int gs, 
         REQUIRE(hipStreamIsCapturing(c->stream, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone, RAMA_EINVAL,
                 "q8 batch: the scratch is sized by the first call, which must not be captured");
         HIPCHK(hipStreamSynchronize(c->stream));
+        destroy_graph(c->q8c.cg);          // (the chained batch's step holds the old scratch's addresses)
         if (c->q8b_blob) { HIPCHK(hipFree(c->q8b_blob)); c->q8b_blob = nullptr; }
         c->q8b_cap = 0;
         HIPCHK(hipMalloc(&c->q8b_blob, need));
@@ -3621,6 +3655,23 @@ int rama_q8_prefill(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* 
     return 0;
 }
 
+// One pass for the n_seq sequences of the device tables toks / seqs: embedding rows, every layer, the final norm, the quantizer and
+// the classifier as one more product into b.LG [n_seq, vocab]
+static int enqueue_q8_batch_pass(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const Q8BatchScratch& b, const int* toks,
+                                 const SeqSlot* seqs, int n_seq) {
+    const int dim = cfg->dim, V = cfg->vocab_size, gs = w->group_size;
+    hipLaunchKernelGGL(embed_rows_kernel, dim3((dim + 255) / 256, n_seq), dim3(256), 0, c->stream, b.X, w->token_embedding_table, toks, n_seq, dim);
+    LAUNCHCHK();
+    int rc = q8_batch_layers(c, cfg, w, b, n_seq, 0, nullptr, nullptr, seqs); if (rc) return rc;
+    // infer.rs:49-51 per sequence: x = rmsnorm(x), logits = Wcls . x
+    rc = launch_rmsnorm_chain(c, b.XN, b.X, w->rms_final_weight, dim, nullptr, n_seq, dim); if (rc) return rc;
+    rc = launch_q8_quantize(c, b.XN, n_seq * dim, gs, b.xq, b.xs); if (rc) return rc;
+    Q8BatchParams p{};
+    p.w[0] = w->wcls; p.ws[0] = w->wcls_s; p.o[0] = b.LG;
+    p.xq = b.xq; p.xs = b.xs; p.K = dim; p.rows = V; p.gs = gs; p.nmat = 1; p.n_tok = n_seq; p.ostride = V;
+    return launch_q8_gemm<Q8EPI_STORE>(c, p);
+}
+
 int rama_q8_decode_batch(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const rama_run_state* states,
                          const int32_t* tokens_host, const int32_t* positions_host, int n_seq) {
     RAMA_ENTER(c);
@@ -3643,20 +3694,194 @@ int rama_q8_decode_batch(rama_ctx* c, const rama_config* cfg, const rama_q8_weig
         }
         return 0;
     }
-    const int dim = cfg->dim, V = cfg->vocab_size, gs = w->group_size;
     Q8BatchScratch b{};
-    rc = ensure_q8_batch_scratch(c, cfg, gs, &b); if (rc) return rc;
+    rc = ensure_q8_batch_scratch(c, cfg, w->group_size, &b); if (rc) return rc;
     c->embedded_x = nullptr; c->host_pos = -1;
     rc = stage_tokens(c, b.toks, tokens_host, n_seq, b.seqs, states, positions_host); if (rc) return rc;
-    hipLaunchKernelGGL(embed_rows_kernel, dim3((dim + 255) / 256, n_seq), dim3(256), 0, c->stream, b.X, w->token_embedding_table, (const int*)b.toks, n_seq, dim);
-    LAUNCHCHK();
-    rc = q8_batch_layers(c, cfg, w, b, n_seq, 0, nullptr, nullptr, b.seqs); if (rc) return rc;
-    // infer.rs:49-51 per sequence: x = rmsnorm(x), logits = Wcls . x
-    rc = launch_rmsnorm_chain(c, b.XN, b.X, w->rms_final_weight, dim, nullptr, n_seq, dim); if (rc) return rc;
-    rc = launch_q8_quantize(c, b.XN, n_seq * dim, gs, b.xq, b.xs); if (rc) return rc;
-    Q8BatchParams p{};
-    p.w[0] = w->wcls; p.ws[0] = w->wcls_s; p.o[0] = b.LG;
-    p.xq = b.xq; p.xs = b.xs; p.K = dim; p.rows = V; p.gs = gs; p.nmat = 1; p.n_tok = n_seq; p.ostride = V;
-    rc = launch_q8_gemm<Q8EPI_STORE>(c, p); if (rc) return rc;
-    return copy_out_logits(c, states, b.LG, n_seq, V);
+    rc = enqueue_q8_batch_pass(c, cfg, w, b, b.toks, b.seqs, n_seq); if (rc) return rc;
+    return copy_out_logits(c, states, b.LG, n_seq, cfg->vocab_size);
+}
+
+// ---- the same pass CHAINED ON THE DEVICE (the Q8 counterpart of rama_decode_batch_begin / _steps): every sequence's (token, position)
+// lives in device memory, a step ends with argmax_batch_kernel or the batched top-p sampler, and -- new here -- a sequence ENDS on its
+// own: after `max_new` tokens or on a sampled stop token (kernels.hpp batch_seq_advance).  A finished slot repeats its last forward,
+// which rewrites one cache row with the same bits, so the pass needs no mask and one captured graph serves the whole chain: nothing in
+// the pass's launch geometry depends on the positions (score rows and attention LDS are sized by seq_len).
+
+// a sequence's budget: its own max_new (0: none) within the chain's max_steps
+static int q8_chain_limit(const rama_q8_seq_plan* per_seq, int i, int max_steps) {
+    return per_seq && per_seq[i].max_new > 0 ? std::min(per_seq[i].max_new, max_steps) : max_steps;
+}
+
+int rama_q8_decode_batch_begin(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const rama_run_state* states,
+                               const int32_t* tokens_host, const int32_t* positions_host, int n_seq, int max_steps,
+                               const rama_q8_seq_plan* per_seq) {
+    RAMA_ENTER(c);
+    // everything is checked before anything of a running chain is touched
+    REQUIRE(c && states && tokens_host && positions_host, RAMA_EINVAL, "q8_decode_batch_begin: NULL argument");
+    REQUIRE(n_seq >= 1 && n_seq <= kQ8bMaxTok, RAMA_EINVAL, "q8_decode_batch_begin: 1..128 sequences");
+    REQUIRE(max_steps >= 1 && max_steps <= (1 << 20), RAMA_EINVAL, "q8_decode_batch_begin: bad max_steps");
+    bool sampled = false;
+    size_t n_forced_all = 0;
+    int cap = 1;
+    for (int i = 0; i < n_seq; i++) {
+        int rc = q8_check(c, cfg, w, &states[i]); if (rc) return rc;
+        REQUIRE(tokens_host[i] >= 0 && tokens_host[i] < cfg->vocab_size, RAMA_EINVAL, "q8_decode_batch_begin: token outside the vocabulary");
+        for (int j = 0; j < i; j++)
+            REQUIRE(states[j].key_cache != states[i].key_cache && states[j].value_cache != states[i].value_cache, RAMA_EINVAL,
+                    "q8_decode_batch_begin: two sequences share a run state");
+        if (per_seq) {
+            const rama_q8_seq_plan& q = per_seq[i];
+            REQUIRE(topp_params_ok(q.temperature, q.topp, q.u), RAMA_EINVAL, "q8_decode_batch_begin: temperature >= 0, topp in [0,1], u in [0,1)");
+            REQUIRE(q.n_forced >= 0 && (q.n_forced == 0 || q.forced), RAMA_EINVAL, "q8_decode_batch_begin: bad forced list");
+            for (int k = 0; k < q.n_forced; k++)
+                REQUIRE(q.forced[k] >= 0 && q.forced[k] < cfg->vocab_size, RAMA_EINVAL, "q8_decode_batch_begin: forced token outside the vocabulary");
+            REQUIRE(q.max_new >= 0, RAMA_EINVAL, "q8_decode_batch_begin: max_new < 0");
+            REQUIRE(q.stop_token >= -1 && q.stop_token < cfg->vocab_size, RAMA_EINVAL, "q8_decode_batch_begin: stop token outside the vocabulary");
+            sampled = sampled || q.temperature != 0.0f || q.n_forced > 0;
+            n_forced_all += (size_t)q.n_forced;
+        }
+        const int limit = q8_chain_limit(per_seq, i, max_steps);
+        REQUIRE(positions_host[i] >= 0 && positions_host[i] <= cfg->seq_len - limit, RAMA_EINVAL,
+                "q8_decode_batch_begin: position + step budget beyond seq_len");
+        cap = std::max(cap, limit);
+    }
+    REQUIRE(q8_batch_ok(cfg), RAMA_EUNSUP, "q8_decode_batch_begin: a shape the Q8 token-batch pass does not take");
+    // argmax_batch_kernel reads 16-byte pieces of the logits rows: other vocabulary sizes end their steps in the sampler's launch
+    const bool use_sampler = sampled || cfg->vocab_size % 4 != 0;
+    REQUIRE(!use_sampler || (cfg->vocab_size > 1 && cfg->vocab_size <= kToppBlock * kToppMaxBlocks), RAMA_EUNSUP,
+            sampled ? "q8_decode_batch_begin: a sampled plan needs vocab_size <= 32768" : "q8_decode_batch_begin: vocab_size % 4 != 0 needs vocab_size <= 32768");
+    if (set_device(c)) return 1;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    auto& qc = c->q8c;
+    destroy_graph(qc.cg);
+    qc.n_seq = 0; qc.live = false; qc.states.clear();
+    // both scratches, the sampler's slices and the chain's tables: sized here, outside any capture
+    int rc = ensure_q8_scratch(c, cfg); if (rc) return rc;
+    Q8BatchScratch b{};
+    rc = ensure_q8_batch_scratch(c, cfg, w->group_size, &b); if (rc) return rc;
+    if (use_sampler) { rc = ensure_topp_batch(c, n_seq, cfg->vocab_size); if (rc) return rc; }
+    if (!qc.toks) {
+        HIPCHK(hipMalloc(&qc.toks, sizeof(int) * kQ8bMaxTok)); HIPCHK(hipMalloc(&qc.seqs, sizeof(SeqSlot) * kQ8bMaxTok));
+        HIPCHK(hipMalloc(&qc.ends, sizeof(BatchEnds)));
+        HIPCHK(hipMalloc(&qc.rows, sizeof(ToppRow) * kQ8bMaxTok));
+        HIPCHK(hipHostMalloc(&qc.done, sizeof(int) * kQ8bMaxTok, hipHostMallocMapped));
+        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&qc.done_dev), qc.done, 0));
+    }
+    if (qc.out_cap < cap) {
+        hipFree(qc.out); qc.out = nullptr; qc.out_cap = 0;
+        if (qc.ring) { hipHostFree(qc.ring); qc.ring = nullptr; }
+        HIPCHK(hipMalloc(&qc.out, sizeof(int) * (size_t)kQ8bMaxTok * cap));
+        HIPCHK(hipHostMalloc(&qc.ring, sizeof(int) * (size_t)kQ8bMaxTok * cap, hipHostMallocMapped));
+        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&qc.ring_dev), qc.ring, 0));
+        qc.out_cap = cap;
+    }
+    memset(qc.ring, 0, sizeof(int) * (size_t)kQ8bMaxTok * qc.out_cap);      // (the stream was drained above: nothing is on its way)
+    memset(qc.done, 0, sizeof(int) * kQ8bMaxTok);
+    if (qc.forced_cap < n_forced_all) {
+        hipFree(qc.forced); qc.forced = nullptr; qc.forced_cap = 0;
+        HIPCHK(hipMalloc(&qc.forced, sizeof(int) * n_forced_all));
+        qc.forced_cap = n_forced_all;
+    }
+    rc = stage_tokens(c, qc.toks, tokens_host, n_seq, qc.seqs, states, positions_host); if (rc) return rc;
+    static_assert(kQ8bMaxTok <= 128, "BatchEnds holds 128 sequences");
+    BatchEnds ends{};
+    ends.done = qc.done_dev;
+    ToppRow rows[kQ8bMaxTok];
+    size_t at = 0;
+    for (int i = 0; i < n_seq; i++) {
+        ends.limit[i] = q8_chain_limit(per_seq, i, max_steps);
+        ends.stop[i] = per_seq ? per_seq[i].stop_token : -1;
+        rows[i] = ToppRow{0.0f, 0.9f, 0.0f, 0, nullptr};
+        if (!per_seq) continue;
+        const rama_q8_seq_plan& q = per_seq[i];
+        rows[i] = ToppRow{q.temperature, q.topp, q.u, q.n_forced, q.n_forced ? qc.forced + at : nullptr};
+        if (q.n_forced) HIPCHK(hipMemcpy(qc.forced + at, q.forced, sizeof(int) * q.n_forced, hipMemcpyHostToDevice));
+        at += (size_t)q.n_forced;
+    }
+    HIPCHK(hipMemcpy(qc.ends, &ends, sizeof ends, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(qc.rows, rows, sizeof(ToppRow) * n_seq, hipMemcpyHostToDevice));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    qc.sampled = use_sampler; qc.cfg = *cfg; qc.w = *w; qc.states.assign(states, states + n_seq);
+    qc.max_steps = max_steps; qc.steps_done = 0; qc.n_seq = n_seq; qc.live = true;
+    return 0;
+}
+
+// one step: the pass over the chain's own tables, then what ends it
+static int enqueue_q8_chain_step(rama_ctx* c, const Q8BatchScratch& b) {
+    auto& qc = c->q8c;
+    const int V = qc.cfg.vocab_size;
+    int rc = enqueue_q8_batch_pass(c, &qc.cfg, &qc.w, b, qc.toks, qc.seqs, qc.n_seq); if (rc) return rc;
+    if (!qc.sampled) {
+        BatchArgmaxParams ap{b.LG, V, qc.toks, qc.seqs, qc.out, qc.out_cap, qc.ring_dev, qc.ends};
+        hipLaunchKernelGGL(argmax_batch_kernel, dim3(qc.n_seq), dim3(1024), 0, c->stream, ap);
+        LAUNCHCHK();
+        return 0;
+    }
+    ToppBatchParams fin{};
+    fin.toks = qc.toks; fin.seqs = qc.seqs; fin.out = qc.out; fin.out_cap = qc.out_cap; fin.ring = qc.ring_dev;
+    fin.ends = qc.ends;
+    return enqueue_topp_batch(c, qc.rows, qc.n_seq, b.LG, (size_t)V, V, fin);
+}
+
+int rama_q8_decode_batch_steps(rama_ctx* c, int n_steps) {
+    RAMA_ENTER(c);
+    REQUIRE(c && c->q8c.n_seq > 0, RAMA_EINVAL, "q8_decode_batch_steps: call rama_q8_decode_batch_begin first");
+    auto& qc = c->q8c;
+    REQUIRE(qc.live, RAMA_EINVAL, "q8_decode_batch_steps: the chain's model or one of its run states has been freed");
+    REQUIRE(n_steps >= 0 && n_steps <= qc.max_steps - qc.steps_done, RAMA_EINVAL, "q8_decode_batch_steps: more steps than rama_q8_decode_batch_begin allowed for");
+    if (set_device(c)) return 1;
+    // (neither grows here: rama_q8_decode_batch_begin sized them, and whoever grew them since for another shape dropped the step's graph)
+    int rc = ensure_q8_scratch(c, &qc.cfg); if (rc) return rc;
+    Q8BatchScratch b{};
+    rc = ensure_q8_batch_scratch(c, &qc.cfg, qc.w.group_size, &b); if (rc) return rc;
+    if (qc.sampled) { rc = ensure_topp_batch(c, qc.n_seq, qc.cfg.vocab_size); if (rc) return rc; }
+    c->embedded_x = nullptr; c->host_pos = -1;
+    const bool graphs = c->graph_mode && c->kp.kernel_id < 0;
+    for (int i = 0; i < n_steps; i++) {
+        if (!graphs) {
+            rc = enqueue_q8_chain_step(c, b); if (rc) return rc;
+        } else {
+            if (!qc.cg.exec) { rc = capture_graph(c, qc.cg, [&] { return enqueue_q8_chain_step(c, b); }); if (rc) return rc; }
+            rc = replay_graph(c, qc.cg); if (rc) return rc;
+        }
+        qc.steps_done++;
+    }
+    return 0;
+}
+
+int rama_q8_decode_batch_tokens(rama_ctx* c, int32_t* out_host, int max_per_seq, int32_t* n_per_seq) {
+    RAMA_ENTER(c);
+    REQUIRE(c && out_host && n_per_seq && c->q8c.n_seq > 0 && max_per_seq >= 0, RAMA_EINVAL, "q8_decode_batch_tokens: bad argument");
+    auto& qc = c->q8c;
+    if (set_device(c)) return 1;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    { const int rh = handoff_check(c); if (rh) return rh; }
+    SeqSlot slots[kQ8bMaxTok];
+    HIPCHK(hipMemcpy(slots, qc.seqs, sizeof(SeqSlot) * qc.n_seq, hipMemcpyDeviceToHost));
+    for (int s_ = 0; s_ < qc.n_seq; s_++) {
+        const int n = std::min(std::min(slots[s_].pad, qc.out_cap), max_per_seq);      // pad: the tokens the sequence has produced
+        if (n > 0) HIPCHK(hipMemcpy(out_host + (size_t)s_ * max_per_seq, qc.out + (size_t)s_ * qc.out_cap, sizeof(int) * n, hipMemcpyDeviceToHost));
+        n_per_seq[s_] = n;
+    }
+    return 0;
+}
+
+int rama_q8_decode_batch_stream_poll(rama_ctx* c, int seq, int from, int32_t* out_host, int max_tokens, int* n_ready, int* finished) {
+    RAMA_ENTER(c);
+    REQUIRE(c && n_ready && c->q8c.n_seq > 0 && c->q8c.ring && seq >= 0 && seq < c->q8c.n_seq && from >= 0 && max_tokens >= 0 && (max_tokens == 0 || out_host),
+            RAMA_EINVAL, "q8_decode_batch_stream_poll: bad argument");
+    const auto& qc = c->q8c;
+    // the finished word first: it is stored after the sequence's last ring word, so a set word means every token is there to be read
+    const int fin = __atomic_load_n(qc.done + seq, __ATOMIC_ACQUIRE);
+    const int* row = qc.ring + (size_t)seq * qc.out_cap;
+    int n = 0;
+    while (n < max_tokens && from + n < qc.out_cap) {
+        const int v = __atomic_load_n(row + from + n, __ATOMIC_ACQUIRE);
+        if (v == 0) break;
+        out_host[n++] = v - 1;
+    }
+    *n_ready = n;
+    if (finished) *finished = fin != 0;
+    return 0;
 }

@@ -856,6 +856,7 @@ struct ToppBatchParams {
     float* keys; int* vals; int* m; size_t rstride;
     int* result;                                  // rama_sample_topp_batch_dev: [rows] the picks
     int* toks; SeqSlot* seqs; int* out; int out_cap; int* ring;      // the chained batch (seqs set)
+    BatchEnds* ends;                              // ... with per-sequence ends (kernels.hpp; NULL: none)
 };
 __device__ __forceinline__ int topp_row_argmax(const float* lg, int n, float* s_v, int* s_i) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -884,10 +885,12 @@ __global__ __launch_bounds__(1024) void topp_pick_batch_kernel(ToppBatchParams p
     __shared__ float s_v[16];
     __shared__ int s_i[16];
     const int row = blockIdx.x, tid = threadIdx.x;
+    if (p.seqs && batch_seq_finished(row, p.seqs, p.ends)) return;      // (uniform: the whole workgroup)
     const ToppRow r = p.rows[row];
     const int pos = p.seqs ? p.seqs[row].pos : 0;
+    const bool forced = p.seqs && pos < r.n_forced;
     int idx;
-    if (p.seqs && pos < r.n_forced) idx = r.forced[pos];          // uniform branches: the row's mode
+    if (forced) idx = r.forced[pos];                              // uniform branches: the row's mode
     else if (r.temperature == 0.0f) idx = topp_row_argmax(p.logits + (size_t)row * p.ld, p.n, s_v, s_i);
     else {
         const size_t o = (size_t)row * p.rstride;
@@ -903,15 +906,7 @@ __global__ __launch_bounds__(1024) void topp_pick_batch_kernel(ToppBatchParams p
     __syncthreads();                                               // every wave has read the position before it moves on
     if (tid != 0) return;
     if (!p.seqs) { p.result[row] = idx; return; }
-    const int next = idx < 0 ? 0 : idx;
-    p.toks[row] = next;
-    p.seqs[row].pos = pos + 1;
-    const int k = p.seqs[row].pad;                                 // tokens this sequence has produced so far
-    if (k < p.out_cap) {
-        p.out[(size_t)row * p.out_cap + k] = next;
-        if (p.ring) __hip_atomic_store(p.ring + (size_t)row * p.out_cap + k, next + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    p.seqs[row].pad = k + 1;
+    batch_seq_advance(row, idx < 0 ? 0 : idx, pos, forced, p.toks, p.seqs, p.out, p.out_cap, p.ring, p.ends);
 }
 
 }  // namespace rama

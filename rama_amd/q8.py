@@ -164,3 +164,113 @@ def decode_batch(engines, tokens, positions):
     states = (rama_run_state * n)(*[e.state for e in engines])
     check(e0.device.lib.rama_q8_decode_batch(e0.device.ctx, C.byref(e0.model.ccfg), C.byref(e0.model.weights), states,
                                              (C.c_int32 * n)(*toks), (C.c_int32 * n)(*poss), n), "rama_q8_decode_batch")
+
+
+def _per_seq(v, n: int, what: str) -> list:
+    """a scalar for every sequence, or one value per sequence"""
+    if v is None or np.ndim(v) == 0:
+        return [v] * n
+    v = list(v)
+    if len(v) != n:
+        raise ValueError(f"decode_batch_chained: {len(v)} {what} values for {n} sequences")
+    return v
+
+
+def chain_plan(engines, tokens, positions, n_steps, temperature=0.0, topp=0.9, u=TOPP_U_CPU, prompts=None, max_new=None,
+               stop_tokens=None):
+    """the checked arguments of decode_batch_chained: (tokens, positions, per-sequence records as tuples (temperature, topp, u,
+    forced list, max_new, stop token)); ValueError for anything rama_q8_decode_batch_begin would refuse.  No library call."""
+    engines = list(engines)
+    n = len(engines)
+    what = "decode_batch_chained"
+    if not 1 <= n <= MAX_BATCH:
+        raise ValueError(f"{what}: {n} sequences, not 1..{MAX_BATCH}")
+    if len(tokens) != n or len(positions) != n:
+        raise ValueError(f"{what}: {len(tokens)} tokens and {len(positions)} positions for {n} sequences")
+    e0 = engines[0]
+    if any(e.model is not e0.model for e in engines):
+        raise ValueError(f"{what}: the engines do not share one Q8Model")
+    if len({id(e) for e in engines}) != n:
+        raise ValueError(f"{what}: an engine appears twice")
+    n_steps = int(n_steps)
+    if n_steps < 1:
+        raise ValueError(f"{what}: n_steps {n_steps} < 1")
+    V, S = e0.cfg.vocab_size, e0.cfg.seq_len
+    toks = _tokens(tokens, V, what)
+    poss = [int(p) for p in positions]
+    Ts, Ps, Us = (_per_seq(x, n, k) for x, k in ((temperature, "temperature"), (topp, "topp"), (u, "u")))
+    news, stops = _per_seq(max_new, n, "max_new"), _per_seq(stop_tokens, n, "stop_tokens")
+    prompts = [[] if p is None else _tokens(p, V, what + " prompt") for p in prompts] if prompts is not None else [[] for _ in range(n)]
+    if len(prompts) != n:
+        raise ValueError(f"{what}: {len(prompts)} prompts for {n} sequences")
+    plan = []
+    for i in range(n):
+        T, P, U = float(Ts[i]), float(Ps[i]), float(Us[i])
+        if not (T >= 0.0 and 0.0 <= P <= 1.0 and 0.0 <= U < 1.0):       # (false for NaN)
+            raise ValueError(f"{what}: sequence {i}: temperature >= 0, topp in [0, 1], u in [0, 1) -- not {T}, {P}, {U}")
+        new = 0 if news[i] is None else int(news[i])
+        if new < 0:
+            raise ValueError(f"{what}: sequence {i}: max_new {new} < 0")
+        stop = -1 if stops[i] is None else int(stops[i])
+        if not -1 <= stop < V:
+            raise ValueError(f"{what}: sequence {i}: stop token {stop} outside the vocabulary [0, {V})")
+        budget = min(new, n_steps) if new else n_steps
+        if not 0 <= poss[i] <= S - budget:
+            raise ValueError(f"{what}: sequence {i}: position {poss[i]} + {budget} steps outside [0, {S}]")
+        plan.append((T, P, U, prompts[i], new, stop))
+    return toks, poss, plan
+
+
+def decode_batch_chained(engines, tokens, positions, n_steps, temperature=0.0, topp=0.9, u=TOPP_U_CPU, prompts=None, max_new=None,
+                         stop_tokens=None, on_token=None):
+    """up to n_steps decode steps of up to 128 independent sequences over one Q8Model, chained on the device
+    (rama_q8_decode_batch_begin / _steps / _tokens) -> per sequence the tokens it produced; the lists may differ in length.
+    temperature, topp, u, max_new and stop_tokens are scalars or one value per sequence (None: no budget of its own / no
+    stop token); prompts is None or one token list per sequence, forced by absolute position as in generate().  A sequence
+    ends after max_new tokens or on a sampled stop token, which it still returns.  on_token(sequence, index, token), when
+    given, is fed from the host-visible rings (rama_q8_decode_batch_stream_poll) while the steps run, until every sequence
+    has set its finished word or the steps have run.  engines[i]'s caches are advanced; its logits() are not written."""
+    from ._lib import rama_q8_seq_plan
+    engines = list(engines)
+    toks, poss, plan = chain_plan(engines, tokens, positions, n_steps, temperature, topp, u, prompts, max_new, stop_tokens)
+    n, n_steps = len(engines), int(n_steps)
+    e0 = engines[0]
+    L, ctx = e0.device.lib, e0.device.ctx
+    states = (rama_run_state * n)(*[e.state for e in engines])
+    forced = [(C.c_int32 * max(len(p[3]), 1))(*p[3]) for p in plan]
+    per = (rama_q8_seq_plan * n)(*[rama_q8_seq_plan(p[0], p[1], p[2], forced[i], len(p[3]), p[4], p[5]) for i, p in enumerate(plan)])
+    check(L.rama_q8_decode_batch_begin(ctx, C.byref(e0.model.ccfg), C.byref(e0.model.weights), states, (C.c_int32 * n)(*toks),
+                                       (C.c_int32 * n)(*poss), n, n_steps, per), "rama_q8_decode_batch_begin")
+    check(L.rama_q8_decode_batch_steps(ctx, n_steps), "rama_q8_decode_batch_steps")
+    if on_token is not None:
+        import time
+        seen, done = [0] * n, [False] * n
+        buf = (C.c_int32 * 64)()
+        k, fin = C.c_int(), C.c_int()
+        ran = False                   # the stream has drained: one more sweep collects what is there
+        while not all(done):
+            progress = 0
+            for s_ in range(n):
+                if done[s_]:
+                    continue
+                # the finished word is read before the ring: once it is set, every token of the sequence is there
+                check(L.rama_q8_decode_batch_stream_poll(ctx, s_, seen[s_], buf, 64, C.byref(k), C.byref(fin)), "rama_q8_decode_batch_stream_poll")
+                for i in range(k.value):
+                    on_token(s_, seen[s_] + i, int(buf[i]))
+                seen[s_] += k.value
+                progress += k.value
+                done[s_] = bool(fin.value) and k.value < 64
+            if progress or all(done):
+                continue
+            if ran:
+                raise RuntimeError(f"decode_batch_chained: the steps have run but sequences {[i for i in range(n) if not done[i]]} have not finished")
+            q = L.rama_stream_query(ctx)
+            if q == 1:
+                time.sleep(0.0002)
+                continue
+            check(q, "rama_stream_query")
+            ran = True
+    out = (C.c_int32 * (n * n_steps))()
+    cnt = (C.c_int32 * n)()
+    check(L.rama_q8_decode_batch_tokens(ctx, out, n_steps, cnt), "rama_q8_decode_batch_tokens")
+    return [[int(out[s_ * n_steps + j]) for j in range(cnt[s_])] for s_ in range(n)]
