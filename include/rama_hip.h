@@ -508,6 +508,82 @@ int  rama_q8_decode_batch_tokens(rama_ctx *ctx, int32_t *out_host, int max_per_s
 int  rama_q8_decode_batch_stream_poll(rama_ctx *ctx, int seq, int from, int32_t *out_tokens_host, int max_tokens, int *n_ready,
                                       int *finished);
 
+/* THE SERVING CHAIN: continuous batching over a Q8 model.  A second, open-ended chain next to the one above,
+ * with a state of its own.  n_slots sequence slots (1..128) share weight passes of max_rows rows (n_slots <= max_rows <= 128).
+ * A slot is FREE, PROMPT (still ingesting its context), DECODE or DONE.  An admitted sequence brings a run state, its context
+ * tokens c[0..n) fed at positions 0..n-1 (the caller includes BOS), and a plan; its output is the SAMPLED tokens only.
+ * One step = one weight pass over max_rows rows, then one pick per slot that has logits.  The step's rows are decided ON THE
+ * DEVICE from the slot table, by the rule rama_q8_serve_plan_step states on the host:
+ *   1. every DECODE slot gets one row: its current token at its position;
+ *   2. every PROMPT slot gets one row: its next context position;
+ *   3. the rows left over go to PROMPT slots in ascending slot index, each taking as many further consecutive context
+ *      positions as it has left and as fit;
+ *   4. the rest are idle (position -1): they write nothing to any run state and nothing is read through their pointers.
+ * Rows are laid out by slot index, a slot's rows at consecutive positions, idle rows last.  Only a slot's last row of a step
+ * may carry logits, and only if it is a DECODE row or the final context position; those rows (<= n_slots) are gathered, and
+ * the final norm, the quantizer and the classifier run over n_slots rows.  After the pick a PROMPT slot that has just fed its
+ * final context position records its first token and becomes DECODE; a slot that records its max_new-th token or a sampled
+ * stop token becomes DONE, sets its host-visible finished word after its last ring word, and occupies no rows from then on.
+ * Slot i's tokens are, bit for bit, rama_q8_generate(prompt = c[1:], steps = n - 1 + max_new, T, topp, u)[n-1:] run on that
+ * sequence alone (for c[0] == 1), cut at the stop token; its cache rows 0..last are that run's, and nothing behind its last
+ * position is written -- whatever the chunking, the neighbours, max_rows and the graph mode.  In graph mode a step is one
+ * hipGraph replay and ONE captured graph serves the chain for its whole life, admissions included.
+ *
+ * rama_q8_serve_begin sizes everything outside any capture (tables, a context buffer of seq_len ints and a pinned admission
+ * record per slot, out / ring rows of max_new_cap tokens) and ends a previous serving chain.  RAMA_EUNSUP where
+ * rama_q8_decode_batch_begin gives it (a shape the Q8 token-batch pass does not take; vocab_size % 4 != 0 beyond 32768),
+ * RAMA_EINVAL for bad sizes.
+ * rama_q8_serve_admit: the slot must be FREE, or DONE as the host can already see it (the finished word; no synchronisation).
+ * Stream-ordered -- an async copy of the slot's own pinned record and a small launch that installs it -- so it works between
+ * any two rama_q8_serve_steps calls without draining the stream or touching the graph.  It resets the slot's ring row and
+ * finished word and bumps the slot's generation number.  Everything is checked first and a refusal leaves the chain as it was:
+ * RAMA_EINVAL for a busy slot, a token outside the vocabulary, temperature < 0 / topp outside [0, 1] / u outside [0, 1) / NaN,
+ * a stop token outside [-1, vocab_size), n_context < 1, max_new < 1, n_context + max_new > seq_len, max_new > max_new_cap, a
+ * run state that a live slot already uses; RAMA_EUNSUP for a sampled plan on vocab_size > 32768.
+ * rama_q8_serve_steps: no overall limit.  RAMA_EINVAL once the model (rama_q8_model_free) or the run state of an occupied slot
+ * (rama_state_free before the host could see the slot DONE) is gone.
+ * rama_q8_serve_poll never touches the stream: tokens from.. of the slot's occupant, *finished, and *generation (each may be
+ * NULL).  rama_q8_serve_tokens synchronises.  rama_q8_serve_stats synchronises: the counters the scheduler launch keeps on the
+ * device, the captures so far, the slot table, and the last step's row table.
+ * rama_q8_serve_plan_step is HOST-ONLY (no context, no GPU): the rule above as a pure function, rows_out[max_rows] and --
+ * slots_after may be NULL -- the successor states when no stop token is sampled.  The device scheduler produces exactly
+ * this table. */
+#define RAMA_SERVE_FREE   0
+#define RAMA_SERVE_PROMPT 1
+#define RAMA_SERVE_DECODE 2
+#define RAMA_SERVE_DONE   3
+typedef struct {
+    int32_t state;                              /* RAMA_SERVE_* */
+    int32_t n_context;
+    int32_t cursor;                             /* PROMPT: the next context position; DECODE: the position of the next row */
+    int32_t n_out;                              /* tokens produced */
+    int32_t max_new;
+} rama_q8_serve_slot;
+typedef struct { int32_t slot, pos, logits; } rama_q8_serve_row;      /* idle: slot -1, pos -1; logits: 1 if the row carries them */
+typedef struct {
+    float temperature, topp, u;                 /* Device::sample; temperature 0 = argmax */
+    int32_t max_new;                            /* >= 1 */
+    int32_t stop_token;                         /* -1 = none; a sampled token equal to it is recorded, then the slot is DONE */
+} rama_q8_serve_plan;
+typedef struct {
+    uint64_t steps, graph_captures, rows_decode, rows_prompt, rows_idle;
+    int32_t n_slots, max_rows;
+    rama_q8_serve_row last_rows[128];           /* the last step's row table (max_rows entries) */
+    rama_q8_serve_slot slots[128];              /* the slot table now */
+    int32_t generation[128];
+} rama_q8_serve_report;
+int  rama_q8_serve_begin(rama_ctx *ctx, const rama_config *cfg, const rama_q8_weights *w, int n_slots, int max_rows, int max_new_cap);
+int  rama_q8_serve_admit(rama_ctx *ctx, int slot, const rama_run_state *state, const int32_t *context_host, int n_context,
+                         const rama_q8_serve_plan *plan);
+int  rama_q8_serve_steps(rama_ctx *ctx, int n_steps);
+int  rama_q8_serve_poll(rama_ctx *ctx, int slot, int from, int32_t *out_tokens_host, int max_tokens, int *n_ready, int *finished,
+                        int *generation);
+int  rama_q8_serve_tokens(rama_ctx *ctx, int slot, int32_t *out_host, int max_tokens, int *n);
+int  rama_q8_serve_stats(rama_ctx *ctx, rama_q8_serve_report *out);
+int  rama_q8_serve_plan_step(const rama_q8_serve_slot *slots, int n_slots, int max_rows, rama_q8_serve_row *rows_out,
+                             rama_q8_serve_slot *slots_after);
+int  rama_q8_serve_end(rama_ctx *ctx);
+
 /* ---------------------------------------------------------------- measurement
  * HIP events on the context's stream (the stream the kernels are launched on). */
 int  rama_timer_start(rama_ctx *ctx);

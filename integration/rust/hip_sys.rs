@@ -40,6 +40,20 @@ pub struct rama_seq_sampling {
 pub struct rama_q8_seq_plan {
     pub temperature: f32, pub topp: f32, pub u: f32, pub forced: *const i32, pub n_forced: i32, pub max_new: i32, pub stop_token: i32,
 }
+/// a slot of the serving chain (state: 0 FREE, 1 PROMPT, 2 DECODE, 3 DONE), a row of a step (idle: slot -1, pos -1), an admission's plan,
+/// and what rama_q8_serve_stats reports
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct rama_q8_serve_slot { pub state: i32, pub n_context: i32, pub cursor: i32, pub n_out: i32, pub max_new: i32 }
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct rama_q8_serve_row { pub slot: i32, pub pos: i32, pub logits: i32 }
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct rama_q8_serve_plan { pub temperature: f32, pub topp: f32, pub u: f32, pub max_new: i32, pub stop_token: i32 }
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct rama_q8_serve_report {
+    pub steps: u64, pub graph_captures: u64, pub rows_decode: u64, pub rows_prompt: u64, pub rows_idle: u64,
+    pub n_slots: i32, pub max_rows: i32,
+    pub last_rows: [rama_q8_serve_row; 128], pub slots: [rama_q8_serve_slot; 128], pub generation: [i32; 128],
+}
 #[repr(C)] pub struct rama_q8_model { _p: [u8; 0] }
 /// a Q8_0 (llama2.c version-2) model as device pointers; `x_s` = the fp32 scales of the int8 tensor `x`
 #[repr(C)] #[derive(Clone, Copy)]
@@ -203,6 +217,19 @@ extern "C" {
     pub fn rama_q8_decode_batch_tokens(ctx: *mut rama_ctx, out_host: *mut i32, max_per_seq: c_int, n_per_seq: *mut i32) -> c_int;
     pub fn rama_q8_decode_batch_stream_poll(ctx: *mut rama_ctx, seq: c_int, from: c_int, out_tokens_host: *mut i32, max_tokens: c_int,
                                             n_ready: *mut c_int, finished: *mut c_int) -> c_int;
+    // the serving chain (continuous batching): slots admitted and finished while the chain runs
+    pub fn rama_q8_serve_begin(ctx: *mut rama_ctx, cfg: *const rama_config, w: *const rama_q8_weights, n_slots: c_int, max_rows: c_int,
+                               max_new_cap: c_int) -> c_int;
+    pub fn rama_q8_serve_admit(ctx: *mut rama_ctx, slot: c_int, state: *const rama_run_state, context_host: *const i32, n_context: c_int,
+                               plan: *const rama_q8_serve_plan) -> c_int;
+    pub fn rama_q8_serve_steps(ctx: *mut rama_ctx, n_steps: c_int) -> c_int;
+    pub fn rama_q8_serve_poll(ctx: *mut rama_ctx, slot: c_int, from: c_int, out_tokens_host: *mut i32, max_tokens: c_int,
+                              n_ready: *mut c_int, finished: *mut c_int, generation: *mut c_int) -> c_int;
+    pub fn rama_q8_serve_tokens(ctx: *mut rama_ctx, slot: c_int, out_host: *mut i32, max_tokens: c_int, n: *mut c_int) -> c_int;
+    pub fn rama_q8_serve_stats(ctx: *mut rama_ctx, out: *mut rama_q8_serve_report) -> c_int;
+    pub fn rama_q8_serve_plan_step(slots: *const rama_q8_serve_slot, n_slots: c_int, max_rows: c_int, rows_out: *mut rama_q8_serve_row,
+                                   slots_after: *mut rama_q8_serve_slot) -> c_int;
+    pub fn rama_q8_serve_end(ctx: *mut rama_ctx) -> c_int;
 }
 
 #[repr(C)] pub struct rama_pipe { _p: [u8; 0] }

@@ -69,6 +69,28 @@ class rama_q8_seq_plan(C.Structure):
                 ("max_new", C.c_int32), ("stop_token", C.c_int32)]
 
 
+class rama_q8_serve_slot(C.Structure):
+    """a slot of the serving chain as rama_q8_serve_plan_step and rama_q8_serve_stats see it (state: 0 FREE, 1 PROMPT, 2 DECODE, 3 DONE)"""
+    _fields_ = [(n, C.c_int32) for n in ("state", "n_context", "cursor", "n_out", "max_new")]
+
+
+class rama_q8_serve_row(C.Structure):
+    """a row of a serving step: its slot and position (-1, -1: idle), and whether it carries logits"""
+    _fields_ = [(n, C.c_int32) for n in ("slot", "pos", "logits")]
+
+
+class rama_q8_serve_plan(C.Structure):
+    """an admitted sequence's sampler, budget and stop token (rama_q8_serve_admit)"""
+    _fields_ = [("temperature", C.c_float), ("topp", C.c_float), ("u", C.c_float), ("max_new", C.c_int32), ("stop_token", C.c_int32)]
+
+
+class rama_q8_serve_report(C.Structure):
+    """what rama_q8_serve_stats fills in: the device counters, the slot table, the last step's row table"""
+    _fields_ = ([(n, C.c_uint64) for n in ("steps", "graph_captures", "rows_decode", "rows_prompt", "rows_idle")] +
+                [("n_slots", C.c_int32), ("max_rows", C.c_int32), ("last_rows", rama_q8_serve_row * 128),
+                 ("slots", rama_q8_serve_slot * 128), ("generation", C.c_int32 * 128)])
+
+
 class rama_pipe_plan(C.Structure):
     _fields_ = [("n_seq", C.c_int32), ("n_pos", C.c_int32), ("wrap", C.c_int32), ("prompt", C.POINTER(C.c_int32)), ("n_prompt", C.c_int32),
                 ("temperature", C.c_float), ("topp", C.c_float), ("u", C.c_float), ("out_tokens_dev", C.c_void_p)]
@@ -175,6 +197,14 @@ SIGNATURES = {
     "rama_q8_decode_batch_steps": (_int, [_vp, _int]),
     "rama_q8_decode_batch_tokens": (_int, [_vp, i32p, _int, i32p]),
     "rama_q8_decode_batch_stream_poll": (_int, [_vp, _int, _int, i32p, _int, C.POINTER(_int), C.POINTER(_int)]),
+    "rama_q8_serve_begin": (_int, [_vp, _cfgp, C.POINTER(rama_q8_weights), _int, _int, _int]),
+    "rama_q8_serve_admit": (_int, [_vp, _int, _sp, i32p, _int, C.POINTER(rama_q8_serve_plan)]),
+    "rama_q8_serve_steps": (_int, [_vp, _int]),
+    "rama_q8_serve_poll": (_int, [_vp, _int, _int, i32p, _int, C.POINTER(_int), C.POINTER(_int), C.POINTER(_int)]),
+    "rama_q8_serve_tokens": (_int, [_vp, _int, i32p, _int, C.POINTER(_int)]),
+    "rama_q8_serve_stats": (_int, [_vp, C.POINTER(rama_q8_serve_report)]),
+    "rama_q8_serve_plan_step": (_int, [C.POINTER(rama_q8_serve_slot), _int, _int, C.POINTER(rama_q8_serve_row), C.POINTER(rama_q8_serve_slot)]),
+    "rama_q8_serve_end": (_int, [_vp]),
 }
 
 _lib = None

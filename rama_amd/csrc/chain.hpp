@@ -1420,6 +1420,8 @@ __device__ __forceinline__ void attention_chain_body(RefAttnParams p, int h, int
 }
 template <int NW>
 __global__ __launch_bounds__(NW * 64) void attention_chain_kernel(RefAttnParams p) {
+    // an idle row of the serving chain's step (q8_serve.hpp): position -1, cache bases never read (uniform: the whole workgroup)
+    if (p.seqs && p.seqs[blockIdx.y].pos < 0) return;
     attention_chain_body<NW>(p, (int)blockIdx.x, (int)blockIdx.y, p.seq_len);
 }
 

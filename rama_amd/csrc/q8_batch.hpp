@@ -323,7 +323,7 @@ static inline bool q8_gemm_mfma_ok(int K, int gs) {
 
 // infer.rs:25-33 for a token batch: rope_ref_cursor_kernel's arithmetic over a (pairs, tokens) grid.  Token t sits at
 // position p0 + t with its cache rows in kc / vc, or -- seqs != NULL -- at seqs[t].pos with its caches at seqs[t].kc / .vc
-// + layer_off.  Q, Kr, V: [n_tok, dim]; the rotated k goes to Kr and the cache, v to the cache.
+// + layer_off (a negative position: the row is idle).  Q, Kr, V: [n_tok, dim]; the rotated k goes to Kr and the cache, v to the cache.
 __global__ void q8_rope_batch_kernel(float* Q, float* Kr, const float* V, const float* fr, const float* fi, int dim, int head_size,
                                      float* kc, float* vc, int p0, const SeqSlot* seqs, size_t layer_off) {
     RAMA_NO_CONTRACT
@@ -331,8 +331,11 @@ __global__ void q8_rope_batch_kernel(float* Q, float* Kr, const float* V, const 
     if (j >= dim / 2) return;
     int pos;
     float *kcb, *vcb;
-    if (seqs) { pos = seqs[t].pos; kcb = seqs[t].kc + layer_off; vcb = seqs[t].vc + layer_off; }
-    else { pos = p0 + t; kcb = kc; vcb = vc; }
+    if (seqs) {
+        pos = seqs[t].pos;
+        if (pos < 0) return;               // an idle row of the serving chain's step (q8_serve.hpp): nothing rotated, no cache row
+        kcb = seqs[t].kc + layer_off; vcb = seqs[t].vc + layer_off;
+    } else { pos = p0 + t; kcb = kc; vcb = vc; }
     float* q = Q + (size_t)t * dim;
     float* k = Kr + (size_t)t * dim;
     const float* v = V + (size_t)t * dim;

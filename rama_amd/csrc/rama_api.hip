@@ -12,6 +12,7 @@
 #include "topp_pick.hpp"
 #include "q8.hpp"
 #include "q8_batch.hpp"
+#include "q8_serve.hpp"
 
 #include <hip/hip_ext.h>   // hipExtLaunchKernelGGL: start/stop events carried by the dispatch itself
 
@@ -290,6 +291,25 @@ struct rama_ctx {
         std::vector<rama_run_state> states;
         CapturedGraph cg;                  // one step: nothing in its launch geometry depends on the positions
     } q8c;
+    // rama_q8_serve_begin / _admit / _steps: the serving chain (q8_serve.hpp), a state of its own next to the chain above
+    struct Q8Serve {
+        int n_slots = 0, max_rows = 0, out_cap = 0;       // n_slots 0: no serving chain
+        bool live = false;                 // false once the model or an occupied slot's run state has been freed: rama_q8_serve_steps refuses
+        bool sampler = false;              // a step runs the batched sampler's ordering launches (vocab_size <= 32768)
+        ServeTables t{};                   // the device tables (ring / done: the device addresses of the two below)
+        char* blob = nullptr;              // ... all of them, one allocation
+        char* stage = nullptr;             // device: one admission record per slot (a ServeSlot + seq_len tokens)
+        char* pinned = nullptr;            // host-pinned: the same, what rama_q8_serve_admit fills and copies from
+        size_t rec_bytes = 0;
+        int* ring = nullptr;               // [n_slots, out_cap] host-pinned and device-mapped: token + 1, 0 = not produced yet
+        int* done = nullptr;               // [n_slots] host-pinned and device-mapped: 1 = the slot's occupant has finished
+        rama_config cfg{}; rama_q8_weights w{};
+        std::vector<rama_run_state> states;   // per slot, the occupant's
+        std::vector<char> occupied;        // per slot: admitted, and not yet seen DONE by a call that frees the slot
+        std::vector<int> gen;
+        unsigned long long steps = 0, captures = 0;
+        CapturedGraph cg;                  // one step, for the chain's whole life: the tables' addresses, nothing of a sequence
+    } q8s;
 };
 
 static int set_device(rama_ctx* c) { HIPCHK(hipSetDevice(c->device)); return 0; }
@@ -412,6 +432,16 @@ static void drop_q8_graphs(rama_ctx* c, const rama_run_state* s) {
     for (const auto& m : c->q8c.states) member = member || (s && m.key_cache == s->key_cache);
     if (c->q8c.cg.exec && (!s || member)) { (void)hipStreamSynchronize(c->stream); destroy_graph(c->q8c.cg); }
     if (member) c->q8c.live = false;
+    // the serving chain: its step goes with all Q8 graphs (the next rama_q8_serve_steps captures again); the run state of a slot whose
+    // occupant the host cannot yet see DONE ends the chain -- a finished occupant's is its owner's again
+    auto& sv = c->q8s;
+    if (!s && sv.cg.exec) { (void)hipStreamSynchronize(c->stream); destroy_graph(sv.cg); }
+    for (int i = 0; s && i < sv.n_slots; i++) {
+        if (!sv.occupied[i] || sv.states[i].key_cache != s->key_cache) continue;
+        if (__atomic_load_n(sv.done + i, __ATOMIC_ACQUIRE)) { sv.occupied[i] = 0; continue; }
+        (void)hipStreamSynchronize(c->stream);
+        sv.live = false;
+    }
     bool any = false;
     for (auto& e : c->q8g) any = any || !s || !memcmp(&e.s, s, sizeof *s);
     if (!any) return;
@@ -428,6 +458,18 @@ extern "C" void rama_internal_drop_q8_graphs(rama_ctx* c, const rama_q8_weights*
     if (!c) return;
     drop_q8_graphs(c, nullptr);
     if (freed && c->q8c.n_seq > 0 && c->q8c.w.wq == freed->wq) c->q8c.live = false;
+    if (freed && c->q8s.n_slots > 0 && c->q8s.w.wq == freed->wq) c->q8s.live = false;
+}
+
+// the serving chain's allocations (rama_q8_serve_begin / _end, rama_ctx_destroy); the stream is idle
+static void serve_release(rama_ctx* c) {
+    auto& sv = c->q8s;
+    destroy_graph(sv.cg);
+    hipFree(sv.blob); hipFree(sv.stage);
+    if (sv.pinned) hipHostFree(sv.pinned);
+    if (sv.ring) hipHostFree(sv.ring);
+    if (sv.done) hipHostFree(sv.done);
+    sv = rama_ctx::Q8Serve();
 }
 
 static void drop_graph(rama_ctx* c) {
@@ -458,6 +500,7 @@ int rama_ctx_destroy(rama_ctx* c) {
     hipFree(c->q8c.toks); hipFree(c->q8c.seqs); hipFree(c->q8c.out); hipFree(c->q8c.ends); hipFree(c->q8c.rows); hipFree(c->q8c.forced);
     if (c->q8c.ring) hipHostFree(c->q8c.ring);
     if (c->q8c.done) hipHostFree(c->q8c.done);
+    serve_release(c);
     hipFree(c->tb.keys); hipFree(c->tb.vals); hipFree(c->tb.bp); hipFree(c->tb.bi); hipFree(c->tb.rk); hipFree(c->tb.bm);
     hipFree(c->tb.bcount); hipFree(c->tb.stats); hipFree(c->tb.m); hipFree(c->tb.rows_dev);
     hipFree(c->q8_xq); hipFree(c->q8_xs); hipFree(c->q8b_blob);
@@ -2014,13 +2057,14 @@ __global__ void topp_rows_kernel(ToppRowsArg a, ToppRow* rows, int n_rows) {
 // the sampler over n_rows rows of n <= 32768 logits (row r at logits + r ld); fin says where the picks go.  The statistics, the block
 // sorts and the ranking are the single-row sampler's launches for the same n (enqueue_sample_launches at the default tuning), so every
 // sampled row gets its bits; the running sums are topp_pick_scan_kernel's, one workgroup per row.
-static int enqueue_topp_batch(rama_ctx* c, const ToppRow* rows, int n_rows, const float* logits, size_t ld, int n, ToppBatchParams fin) {
+// (its ordering launches -- everything but the pick -- are enqueue_topp_batch_order: the serving chain ends its step in a pick of its own)
+static int enqueue_topp_batch_order(rama_ctx* c, const ToppRow* rows, int n_rows, const float* logits, size_t ld, int n, const SeqSlot* seqs) {
     auto& t = c->tb;
     REQUIRE(n > 1 && n <= kToppBlock * kToppMaxBlocks && n_rows <= t.rows && (size_t)n <= t.rstride, RAMA_EINVAL, "top-p batch sampler: scratch not prepared");
     ToppSortParams sp{};
     sp.logits = logits; sp.n = n;
     sp.bp = t.bp; sp.bi = t.bi; sp.bcount = t.bcount; sp.keys = t.keys; sp.vals = t.vals; sp.m = t.m;
-    sp.rows = rows; sp.seqs = fin.seqs; sp.ld = ld; sp.rstride = t.rstride;
+    sp.rows = rows; sp.seqs = seqs; sp.ld = ld; sp.rstride = t.rstride;
     if (n <= kToppBlock) {                                         // one block: its own statistics and sort, the in-LDS ranking
         sp.nblk = 1;
         hipLaunchKernelGGL((topp_blocksort_kernel<false, true>), dim3(1, 1, n_rows), dim3(1024), 0, c->stream, sp);
@@ -2042,6 +2086,11 @@ static int enqueue_topp_batch(rama_ctx* c, const ToppRow* rows, int n_rows, cons
         hipLaunchKernelGGL((topp_rank_scatter_bs_kernel<BS, true>), dim3((sp.nblk * BS + 1023) / 1024, 1, n_rows), dim3(1024), 0, c->stream, sp);
         LAUNCHCHK();
     }
+    return 0;
+}
+static int enqueue_topp_batch(rama_ctx* c, const ToppRow* rows, int n_rows, const float* logits, size_t ld, int n, ToppBatchParams fin) {
+    auto& t = c->tb;
+    { const int rc = enqueue_topp_batch_order(c, rows, n_rows, logits, ld, n, fin.seqs); if (rc) return rc; }
     fin.rows = rows; fin.logits = logits; fin.ld = ld; fin.n = n;
     fin.keys = t.keys; fin.vals = t.vals; fin.m = t.m; fin.rstride = t.rstride;
     hipLaunchKernelGGL(topp_pick_batch_kernel, dim3(n_rows), dim3(1024), 0, c->stream, fin);
@@ -3552,6 +3601,7 @@ static int ensure_q8_batch_scratch(rama_ctx* c, const rama_config* cfg, int gs, 
                 "q8 batch: the scratch is sized by the first call, which must not be captured");
         HIPCHK(hipStreamSynchronize(c->stream));
         destroy_graph(c->q8c.cg);          // (the chained batch's step holds the old scratch's addresses)
+        destroy_graph(c->q8s.cg);          // (and the serving chain's)
         if (c->q8b_blob) { HIPCHK(hipFree(c->q8b_blob)); c->q8b_blob = nullptr; }
         c->q8b_cap = 0;
         HIPCHK(hipMalloc(&c->q8b_blob, need));
@@ -3883,5 +3933,299 @@ int rama_q8_decode_batch_stream_poll(rama_ctx* c, int seq, int from, int32_t* ou
     }
     *n_ready = n;
     if (finished) *finished = fin != 0;
+    return 0;
+}
+
+// ---- THE SERVING CHAIN (q8_serve.hpp): continuous batching.  n_slots slots share passes of max_rows rows; a scheduler
+// launch builds every step's row table from the slot table on the device, a pick launch runs the slots' state machine, and an admission
+// is a stream-ordered copy + launch between two steps.  Nothing in a step's launch geometry depends on a sequence, so one captured graph
+// serves the chain for its whole life.
+
+// the scheduling rule on the host: the rows every slot gets in the next step (serve_schedule_kernel computes the same numbers by scans)
+static void serve_plan_counts(const rama_q8_serve_slot* slots, int n_slots, int max_rows, int* nrows) {
+    int left = max_rows;
+    for (int i = 0; i < n_slots; i++) {
+        nrows[i] = slots[i].state == RAMA_SERVE_DECODE || slots[i].state == RAMA_SERVE_PROMPT ? 1 : 0;
+        left -= nrows[i];
+    }
+    for (int i = 0; i < n_slots && left > 0; i++) {
+        if (slots[i].state != RAMA_SERVE_PROMPT) continue;
+        const int extra = std::min(slots[i].n_context - slots[i].cursor - 1, left);
+        nrows[i] += extra;
+        left -= extra;
+    }
+}
+
+int rama_q8_serve_plan_step(const rama_q8_serve_slot* slots, int n_slots, int max_rows, rama_q8_serve_row* rows_out, rama_q8_serve_slot* slots_after) {
+    REQUIRE(slots && rows_out, RAMA_EINVAL, "q8_serve_plan_step: NULL argument");
+    REQUIRE(n_slots >= 1 && n_slots <= kServeMaxSlots && max_rows >= n_slots && max_rows <= kQ8bMaxTok, RAMA_EINVAL,
+            "q8_serve_plan_step: 1 <= n_slots <= max_rows <= 128");
+    for (int i = 0; i < n_slots; i++) {
+        const rama_q8_serve_slot& s = slots[i];
+        REQUIRE(s.state >= RAMA_SERVE_FREE && s.state <= RAMA_SERVE_DONE, RAMA_EINVAL, "q8_serve_plan_step: bad slot state");
+        if (s.state == RAMA_SERVE_PROMPT)
+            REQUIRE(s.n_context >= 1 && s.cursor >= 0 && s.cursor < s.n_context && s.max_new >= 1, RAMA_EINVAL, "q8_serve_plan_step: bad PROMPT slot");
+        if (s.state == RAMA_SERVE_DECODE)
+            REQUIRE(s.cursor >= 0 && s.n_out >= 1 && s.n_out < s.max_new, RAMA_EINVAL, "q8_serve_plan_step: bad DECODE slot");
+    }
+    int nrows[kServeMaxSlots];
+    serve_plan_counts(slots, n_slots, max_rows, nrows);
+    int r = 0;
+    for (int i = 0; i < n_slots; i++) {
+        const rama_q8_serve_slot& s = slots[i];
+        const bool lg = s.state == RAMA_SERVE_DECODE || (s.state == RAMA_SERVE_PROMPT && s.cursor + nrows[i] == s.n_context);
+        for (int k = 0; k < nrows[i]; k++) rows_out[r++] = rama_q8_serve_row{i, s.cursor + k, lg && k == nrows[i] - 1 ? 1 : 0};
+        if (!slots_after) continue;
+        rama_q8_serve_slot a = s;
+        if (nrows[i]) {
+            a.cursor = s.cursor + nrows[i];
+            if (lg) {
+                a.n_out = s.n_out + 1;
+                a.state = a.n_out >= s.max_new ? RAMA_SERVE_DONE : RAMA_SERVE_DECODE;
+            }
+        }
+        slots_after[i] = a;
+    }
+    for (; r < max_rows; r++) rows_out[r] = rama_q8_serve_row{-1, -1, 0};
+    return 0;
+}
+
+int rama_q8_serve_end(rama_ctx* c) {
+    RAMA_ENTER(c);
+    REQUIRE(c, RAMA_EINVAL, "q8_serve_end: ctx is NULL");
+    if (!c->q8s.n_slots && !c->q8s.blob) return 0;
+    if (set_device(c)) return 1;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    serve_release(c);
+    return 0;
+}
+
+int rama_q8_serve_begin(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, int n_slots, int max_rows, int max_new_cap) {
+    RAMA_ENTER(c);
+    REQUIRE(c, RAMA_EINVAL, "ctx is NULL");
+    int rc = check_cfg(cfg); if (rc) return rc;
+    REQUIRE(w && w->group_size > 0 && cfg->dim % w->group_size == 0 && cfg->hidden_dim % w->group_size == 0, RAMA_EINVAL,
+            "q8_serve_begin: group_size must divide dim and hidden_dim");
+    REQUIRE(w->token_embedding_table && w->rms_att_weight && w->rms_ffn_weight && w->rms_final_weight && w->freq_cis_real && w->freq_cis_imag &&
+            w->wq && w->wk && w->wv && w->wo && w->w1 && w->w2 && w->w3 && w->wcls && w->wq_s && w->wk_s && w->wv_s && w->wo_s && w->w1_s &&
+            w->w2_s && w->w3_s && w->wcls_s, RAMA_EINVAL, "q8_serve_begin: missing weights");
+    REQUIRE(n_slots >= 1 && n_slots <= kServeMaxSlots && max_rows >= n_slots && max_rows <= kQ8bMaxTok, RAMA_EINVAL,
+            "q8_serve_begin: 1 <= n_slots <= max_rows <= 128");
+    REQUIRE(max_new_cap >= 1 && max_new_cap <= cfg->seq_len - 1, RAMA_EINVAL, "q8_serve_begin: max_new_cap outside [1, seq_len - 1]");
+    REQUIRE(q8_batch_ok(cfg), RAMA_EUNSUP, "q8_serve_begin: a shape the Q8 token-batch pass does not take");
+    const int V = cfg->vocab_size;
+    const bool sampler = V > 1 && V <= kToppBlock * kToppMaxBlocks;
+    REQUIRE(sampler || V % 4 == 0, RAMA_EUNSUP, "q8_serve_begin: vocab_size % 4 != 0 needs vocab_size <= 32768");
+    if (set_device(c)) return 1;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    serve_release(c);
+    // both scratches, the sampler's slices and the chain's tables: sized here, outside any capture
+    rc = ensure_q8_scratch(c, cfg); if (rc) return rc;
+    Q8BatchScratch b{};
+    rc = ensure_q8_batch_scratch(c, cfg, w->group_size, &b); if (rc) return rc;
+    if (sampler) { rc = ensure_topp_batch(c, n_slots, V); if (rc) return rc; }
+    auto& sv = c->q8s;
+    const size_t S = (size_t)cfg->seq_len, N = (size_t)n_slots, R = (size_t)max_rows, cap = (size_t)max_new_cap;
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    const size_t sz[9] = {N * sizeof(ServeSlot), N * S * sizeof(int), R * sizeof(SeqSlot), R * sizeof(int), N * sizeof(int), N * sizeof(int),
+                          N * sizeof(ToppRow), 4 * sizeof(unsigned long long), N * cap * sizeof(int)};
+    size_t off[9], need = 0;
+    for (int i = 0; i < 9; i++) { off[i] = need; need += up(sz[i]); }
+    HIPCHK(hipMalloc(&sv.blob, need));
+    HIPCHK(hipMemsetAsync(sv.blob, 0, need, c->stream));          // every slot FREE, the counters 0
+    sv.rec_bytes = up(sizeof(ServeSlot) + S * sizeof(int));
+    HIPCHK(hipMalloc(&sv.stage, N * sv.rec_bytes));
+    HIPCHK(hipHostMalloc(&sv.pinned, N * sv.rec_bytes, hipHostMallocDefault));
+    HIPCHK(hipHostMalloc(&sv.ring, sizeof(int) * N * cap, hipHostMallocMapped));
+    HIPCHK(hipHostMalloc(&sv.done, sizeof(int) * N, hipHostMallocMapped));
+    memset(sv.ring, 0, sizeof(int) * N * cap);
+    memset(sv.done, 0, sizeof(int) * N);
+    ServeTables& t = sv.t;
+    t.slots = reinterpret_cast<ServeSlot*>(sv.blob + off[0]); t.ctx = reinterpret_cast<int*>(sv.blob + off[1]);
+    t.rows = reinterpret_cast<SeqSlot*>(sv.blob + off[2]); t.row_tok = reinterpret_cast<int*>(sv.blob + off[3]);
+    t.nrows = reinterpret_cast<int*>(sv.blob + off[4]); t.lrow = reinterpret_cast<int*>(sv.blob + off[5]);
+    t.trow = reinterpret_cast<ToppRow*>(sv.blob + off[6]); t.counters = reinterpret_cast<unsigned long long*>(sv.blob + off[7]);
+    t.out = reinterpret_cast<int*>(sv.blob + off[8]);
+    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&t.ring), sv.ring, 0));
+    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&t.done), sv.done, 0));
+    t.seq_len = cfg->seq_len; t.n_slots = n_slots; t.max_rows = max_rows; t.out_cap = max_new_cap;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    sv.cfg = *cfg; sv.w = *w; sv.sampler = sampler;
+    sv.states.assign(N, rama_run_state{}); sv.occupied.assign(N, 0); sv.gen.assign(N, 0);
+    sv.steps = 0; sv.captures = 0;
+    sv.max_rows = max_rows; sv.out_cap = max_new_cap; sv.n_slots = n_slots; sv.live = true;
+    return 0;
+}
+
+// the slot's occupant is still on the device's hands: admitted, and its finished word not yet set
+static bool serve_slot_live(const rama_ctx::Q8Serve& sv, int slot) {
+    return sv.occupied[slot] && !__atomic_load_n(sv.done + slot, __ATOMIC_ACQUIRE);
+}
+
+int rama_q8_serve_admit(rama_ctx* c, int slot, const rama_run_state* state, const int32_t* context_host, int n_context, const rama_q8_serve_plan* plan) {
+    RAMA_ENTER(c);
+    REQUIRE(c && c->q8s.n_slots > 0, RAMA_EINVAL, "q8_serve_admit: call rama_q8_serve_begin first");
+    auto& sv = c->q8s;
+    // everything is checked before anything of the running chain is touched
+    REQUIRE(sv.live, RAMA_EINVAL, "q8_serve_admit: the chain's model or the run state of an occupied slot has been freed");
+    REQUIRE(state && context_host && plan, RAMA_EINVAL, "q8_serve_admit: NULL argument");
+    REQUIRE(slot >= 0 && slot < sv.n_slots, RAMA_EINVAL, "q8_serve_admit: no such slot");
+    int rc = q8_check(c, &sv.cfg, &sv.w, state); if (rc) return rc;
+    REQUIRE(!serve_slot_live(sv, slot), RAMA_EINVAL, "q8_serve_admit: the slot is busy");
+    const int V = sv.cfg.vocab_size;
+    REQUIRE(n_context >= 1, RAMA_EINVAL, "q8_serve_admit: n_context < 1");
+    REQUIRE(plan->max_new >= 1, RAMA_EINVAL, "q8_serve_admit: max_new < 1");
+    REQUIRE(plan->max_new <= sv.out_cap, RAMA_EINVAL, "q8_serve_admit: max_new beyond rama_q8_serve_begin's max_new_cap");
+    REQUIRE(n_context <= sv.cfg.seq_len - plan->max_new, RAMA_EINVAL, "q8_serve_admit: n_context + max_new beyond seq_len");
+    for (int i = 0; i < n_context; i++) REQUIRE(context_host[i] >= 0 && context_host[i] < V, RAMA_EINVAL, "q8_serve_admit: token outside the vocabulary");
+    REQUIRE(topp_params_ok(plan->temperature, plan->topp, plan->u), RAMA_EINVAL, "q8_serve_admit: temperature >= 0, topp in [0,1], u in [0,1)");
+    REQUIRE(plan->stop_token >= -1 && plan->stop_token < V, RAMA_EINVAL, "q8_serve_admit: stop token outside the vocabulary");
+    for (int j = 0; j < sv.n_slots; j++)
+        REQUIRE(j == slot || !serve_slot_live(sv, j) || (sv.states[j].key_cache != state->key_cache && sv.states[j].value_cache != state->value_cache),
+                RAMA_EINVAL, "q8_serve_admit: the run state is already in a live slot");
+    REQUIRE(plan->temperature == 0.0f || sv.sampler, RAMA_EUNSUP, "q8_serve_admit: a sampled plan needs vocab_size <= 32768");
+    if (set_device(c)) return 1;
+    // the slot's own pinned record: its previous copy has run (the occupant it installed has finished, or there was none)
+    char* rec = sv.pinned + (size_t)slot * sv.rec_bytes;
+    ServeSlot h{};
+    h.kc = state->key_cache; h.vc = state->value_cache;
+    h.state = kServePrompt; h.n_ctx = n_context; h.cursor = 0; h.tok = 0; h.n_out = 0;
+    h.max_new = plan->max_new; h.stop = plan->stop_token; h.gen = sv.gen[slot] + 1;
+    h.temperature = plan->temperature; h.topp = plan->topp; h.u = plan->u;
+    memcpy(rec, &h, sizeof h);
+    memcpy(rec + sizeof h, context_host, sizeof(int) * (size_t)n_context);
+    // (the device writes neither again for the previous occupant: it is DONE)
+    memset(sv.ring + (size_t)slot * sv.out_cap, 0, sizeof(int) * (size_t)sv.out_cap);
+    __atomic_store_n(sv.done + slot, 0, __ATOMIC_RELEASE);
+    char* dst = sv.stage + (size_t)slot * sv.rec_bytes;
+    HIPCHK(hipMemcpyAsync(dst, rec, sizeof h + sizeof(int) * (size_t)n_context, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(serve_install_kernel, dim3(1), dim3(256), 0, c->stream, sv.t, slot, reinterpret_cast<const ServeSlot*>(dst));
+    LAUNCHCHK();
+    sv.states[slot] = *state; sv.occupied[slot] = 1; sv.gen[slot]++;
+    return 0;
+}
+
+// one step: the scheduler, the pass over its row table, the logits of the rows that carry them, the pick and the slots' state machine
+static int enqueue_q8_serve_step(rama_ctx* c, const Q8BatchScratch& b) {
+    auto& sv = c->q8s;
+    const rama_config* cfg = &sv.cfg;
+    const rama_q8_weights* w = &sv.w;
+    const int dim = cfg->dim, V = cfg->vocab_size, gs = w->group_size, R = sv.max_rows, N = sv.n_slots;
+    hipLaunchKernelGGL(serve_schedule_kernel, dim3(1), dim3(kServeMaxSlots), 0, c->stream, sv.t);
+    LAUNCHCHK();
+    hipLaunchKernelGGL(embed_rows_kernel, dim3((dim + 255) / 256, R), dim3(256), 0, c->stream, b.X, w->token_embedding_table, (const int*)sv.t.row_tok, R, dim);
+    LAUNCHCHK();
+    int rc = q8_batch_layers(c, cfg, w, b, R, 0, nullptr, nullptr, sv.t.rows); if (rc) return rc;
+    // infer.rs:49-51 for the slots' logits rows only (b.Q is free here): x = rmsnorm(x), logits = Wcls . x
+    hipLaunchKernelGGL(serve_gather_kernel, dim3((dim + 255) / 256, N), dim3(256), 0, c->stream, b.Q, (const float*)b.X, (const int*)sv.t.lrow, dim);
+    LAUNCHCHK();
+    rc = launch_rmsnorm_chain(c, b.XN, b.Q, w->rms_final_weight, dim, nullptr, N, dim); if (rc) return rc;
+    rc = launch_q8_quantize(c, b.XN, N * dim, gs, b.xq, b.xs); if (rc) return rc;
+    Q8BatchParams p{};
+    p.w[0] = w->wcls; p.ws[0] = w->wcls_s; p.o[0] = b.LG;
+    p.xq = b.xq; p.xs = b.xs; p.K = dim; p.rows = V; p.gs = gs; p.nmat = 1; p.n_tok = N; p.ostride = V;
+    rc = launch_q8_gemm<Q8EPI_STORE>(c, p); if (rc) return rc;
+    ServePickParams fin{};
+    fin.t = sv.t; fin.logits = b.LG; fin.ld = (size_t)V; fin.n = V;
+    if (sv.sampler) {
+        rc = enqueue_topp_batch_order(c, sv.t.trow, N, b.LG, (size_t)V, V, nullptr); if (rc) return rc;
+        fin.keys = c->tb.keys; fin.vals = c->tb.vals; fin.m = c->tb.m; fin.rstride = c->tb.rstride;
+    }
+    hipLaunchKernelGGL(serve_pick_kernel, dim3(N), dim3(1024), 0, c->stream, fin);
+    LAUNCHCHK();
+    return 0;
+}
+
+int rama_q8_serve_steps(rama_ctx* c, int n_steps) {
+    RAMA_ENTER(c);
+    REQUIRE(c && c->q8s.n_slots > 0, RAMA_EINVAL, "q8_serve_steps: call rama_q8_serve_begin first");
+    auto& sv = c->q8s;
+    REQUIRE(sv.live, RAMA_EINVAL, "q8_serve_steps: the chain's model or the run state of an occupied slot has been freed");
+    REQUIRE(n_steps >= 0, RAMA_EINVAL, "q8_serve_steps: n_steps < 0");
+    if (set_device(c)) return 1;
+    // (neither grows here: rama_q8_serve_begin sized them, and whoever grew them since for another shape dropped the step's graph)
+    int rc = ensure_q8_scratch(c, &sv.cfg); if (rc) return rc;
+    Q8BatchScratch b{};
+    rc = ensure_q8_batch_scratch(c, &sv.cfg, sv.w.group_size, &b); if (rc) return rc;
+    if (sv.sampler) { rc = ensure_topp_batch(c, sv.n_slots, sv.cfg.vocab_size); if (rc) return rc; }
+    c->embedded_x = nullptr; c->host_pos = -1;
+    const bool graphs = c->graph_mode && c->kp.kernel_id < 0;
+    for (int i = 0; i < n_steps; i++) {
+        if (!graphs) {
+            rc = enqueue_q8_serve_step(c, b); if (rc) return rc;
+        } else {
+            if (!sv.cg.exec) {
+                rc = capture_graph(c, sv.cg, [&] { return enqueue_q8_serve_step(c, b); }); if (rc) return rc;
+                sv.captures++;
+            }
+            rc = replay_graph(c, sv.cg); if (rc) return rc;
+        }
+        sv.steps++;
+    }
+    return 0;
+}
+
+int rama_q8_serve_poll(rama_ctx* c, int slot, int from, int32_t* out_host, int max_tokens, int* n_ready, int* finished, int* generation) {
+    RAMA_ENTER(c);
+    REQUIRE(c && n_ready && c->q8s.n_slots > 0 && slot >= 0 && slot < c->q8s.n_slots && from >= 0 && max_tokens >= 0 && (max_tokens == 0 || out_host),
+            RAMA_EINVAL, "q8_serve_poll: bad argument");
+    const auto& sv = c->q8s;
+    // the finished word first: it is stored after the occupant's last ring word, so a set word means every token is there to be read
+    const int fin = __atomic_load_n(sv.done + slot, __ATOMIC_ACQUIRE);
+    const int* row = sv.ring + (size_t)slot * sv.out_cap;
+    int n = 0;
+    while (n < max_tokens && from + n < sv.out_cap) {
+        const int v = __atomic_load_n(row + from + n, __ATOMIC_ACQUIRE);
+        if (v == 0) break;
+        out_host[n++] = v - 1;
+    }
+    *n_ready = n;
+    if (finished) *finished = fin != 0;
+    if (generation) *generation = sv.gen[slot];
+    return 0;
+}
+
+int rama_q8_serve_tokens(rama_ctx* c, int slot, int32_t* out_host, int max_tokens, int* n_out) {
+    RAMA_ENTER(c);
+    REQUIRE(c && n_out && c->q8s.n_slots > 0 && slot >= 0 && slot < c->q8s.n_slots && max_tokens >= 0 && (max_tokens == 0 || out_host), RAMA_EINVAL,
+            "q8_serve_tokens: bad argument");
+    auto& sv = c->q8s;
+    if (set_device(c)) return 1;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    { const int rh = handoff_check(c); if (rh) return rh; }
+    ServeSlot s{};
+    HIPCHK(hipMemcpy(&s, sv.t.slots + slot, sizeof s, hipMemcpyDeviceToHost));
+    const int n = std::min(std::min(s.n_out, sv.out_cap), max_tokens);
+    if (n > 0) HIPCHK(hipMemcpy(out_host, sv.t.out + (size_t)slot * sv.out_cap, sizeof(int) * n, hipMemcpyDeviceToHost));
+    *n_out = n;
+    return 0;
+}
+
+int rama_q8_serve_stats(rama_ctx* c, rama_q8_serve_report* out) {
+    RAMA_ENTER(c);
+    REQUIRE(c && out && c->q8s.n_slots > 0, RAMA_EINVAL, "q8_serve_stats: bad argument");
+    auto& sv = c->q8s;
+    if (set_device(c)) return 1;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    { const int rh = handoff_check(c); if (rh) return rh; }
+    memset(out, 0, sizeof *out);
+    unsigned long long cnt[4];
+    ServeSlot slots[kServeMaxSlots];
+    SeqSlot rows[kQ8bMaxTok];
+    int lrow[kServeMaxSlots];
+    HIPCHK(hipMemcpy(cnt, sv.t.counters, sizeof cnt, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(slots, sv.t.slots, sizeof(ServeSlot) * sv.n_slots, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(rows, sv.t.rows, sizeof(SeqSlot) * sv.max_rows, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(lrow, sv.t.lrow, sizeof(int) * sv.n_slots, hipMemcpyDeviceToHost));
+    out->steps = cnt[0]; out->graph_captures = sv.captures; out->rows_decode = cnt[1]; out->rows_prompt = cnt[2]; out->rows_idle = cnt[3];
+    out->n_slots = sv.n_slots; out->max_rows = sv.max_rows;
+    for (int r = 0; r < sv.max_rows; r++) {
+        const bool on = cnt[0] > 0 && rows[r].pos >= 0;            // (before the first step the table holds nothing)
+        out->last_rows[r] = rama_q8_serve_row{on ? rows[r].pad : -1, on ? rows[r].pos : -1, on && lrow[rows[r].pad] == r ? 1 : 0};
+    }
+    for (int i = 0; i < sv.n_slots; i++) {
+        out->slots[i] = rama_q8_serve_slot{slots[i].state, slots[i].n_ctx, slots[i].cursor, slots[i].n_out, slots[i].max_new};
+        out->generation[i] = sv.gen[i];
+    }
     return 0;
 }

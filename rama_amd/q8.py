@@ -274,3 +274,269 @@ def decode_batch_chained(engines, tokens, positions, n_steps, temperature=0.0, t
     cnt = (C.c_int32 * n)()
     check(L.rama_q8_decode_batch_tokens(ctx, out, n_steps, cnt), "rama_q8_decode_batch_tokens")
     return [[int(out[s_ * n_steps + j]) for j in range(cnt[s_])] for s_ in range(n)]
+
+
+# ------------------------------------------------------------------ the serving chain: continuous batching (rama_q8_serve_*)
+
+SERVE_FREE, SERVE_PROMPT, SERVE_DECODE, SERVE_DONE = 0, 1, 2, 3
+
+
+def serve_sizes(cfg, n_slots, max_rows, max_new_cap):
+    """the checked sizes of a serving chain; ValueError for what rama_q8_serve_begin would refuse as a bad size.  No library call."""
+    n_slots, max_new_cap = int(n_slots), int(max_new_cap)
+    max_rows = n_slots if max_rows is None else int(max_rows)
+    if not 1 <= n_slots <= MAX_BATCH:
+        raise ValueError(f"Q8Server: {n_slots} slots, not 1..{MAX_BATCH}")
+    if not n_slots <= max_rows <= MAX_BATCH:
+        raise ValueError(f"Q8Server: max_rows {max_rows} outside [n_slots = {n_slots}, {MAX_BATCH}]")
+    if not 1 <= max_new_cap <= cfg.seq_len - 1:
+        raise ValueError(f"Q8Server: max_new_cap {max_new_cap} outside [1, seq_len - 1 = {cfg.seq_len - 1}]")
+    return n_slots, max_rows, max_new_cap
+
+
+def serve_plan(cfg, context, max_new, temperature=0.0, topp=0.9, u=TOPP_U_CPU, stop_token=None, max_new_cap=None):
+    """the checked arguments of Q8Server.submit: (context tokens, (temperature, topp, u, max_new, stop token)); ValueError for
+    everything rama_q8_serve_admit would refuse in them.  No library call."""
+    what = "Q8Server.submit"
+    V, S = cfg.vocab_size, cfg.seq_len
+    ctx = _tokens(context, V, what)
+    if not ctx:
+        raise ValueError(f"{what}: an empty context (the caller includes BOS)")
+    T, P, U = float(temperature), float(topp), float(u)
+    if not (T >= 0.0 and 0.0 <= P <= 1.0 and 0.0 <= U < 1.0):       # (false for NaN)
+        raise ValueError(f"{what}: temperature >= 0, topp in [0, 1], u in [0, 1) -- not {T}, {P}, {U}")
+    new = int(max_new)
+    if new < 1:
+        raise ValueError(f"{what}: max_new {new} < 1")
+    if max_new_cap is not None and new > int(max_new_cap):
+        raise ValueError(f"{what}: max_new {new} beyond the server's max_new_cap {int(max_new_cap)}")
+    if len(ctx) + new > S:
+        raise ValueError(f"{what}: {len(ctx)} context tokens + {new} new ones beyond seq_len {S}")
+    stop = -1 if stop_token is None else int(stop_token)
+    if not -1 <= stop < V:
+        raise ValueError(f"{what}: stop token {stop} outside the vocabulary [0, {V})")
+    if T != 0.0 and V > 32768:
+        raise ValueError(f"{what}: a sampled plan needs vocab_size <= 32768")
+    return ctx, (T, P, U, new, stop)
+
+
+def serve_plan_step(slots, max_rows):
+    """rama_q8_serve_plan_step, the scheduling rule as a pure host function: slots = (state, n_context, cursor, n_out, max_new)
+    tuples -> (rows [(slot, pos, logits)] * max_rows, the slots after the step when no stop token is sampled).  No GPU."""
+    from ._lib import load, rama_q8_serve_row, rama_q8_serve_slot
+    n = len(slots)
+    arr = (rama_q8_serve_slot * max(n, 1))(*[rama_q8_serve_slot(*[int(v) for v in s]) for s in slots])
+    rows = (rama_q8_serve_row * max(int(max_rows), 1))()
+    after = (rama_q8_serve_slot * max(n, 1))()
+    check(load().rama_q8_serve_plan_step(arr, n, int(max_rows), rows, after), "rama_q8_serve_plan_step")
+    return ([(r.slot, r.pos, r.logits) for r in rows[:int(max_rows)]],
+            [(a.state, a.n_context, a.cursor, a.n_out, a.max_new) for a in after[:n]])
+
+
+class Q8Server:
+    """continuous batching over one Q8Model (rama_q8_serve_begin / _admit / _steps / _poll): n_slots sequence slots share weight
+    passes of max_rows rows; a finished sequence frees its slot for the next queued request while the others run on, and a new
+    request's context is ingested in chunks next to the decoding slots.  Every request's tokens are those Q8Engine.generate gives
+    it alone.  One serving chain per device context at a time."""
+
+    def __init__(self, model: Q8Model, n_slots: int, max_rows=None, max_new_cap: int = 256):
+        self.n_slots, self.max_rows, self.max_new_cap = serve_sizes(model.cfg, n_slots, max_rows, max_new_cap)
+        self.model, self.device, self.cfg = model, model.device, model.cfg
+        L = self.device.lib
+        check(L.rama_q8_serve_begin(self.device.ctx, C.byref(model.ccfg), C.byref(model.weights), self.n_slots, self.max_rows,
+                                    self.max_new_cap), "rama_q8_serve_begin")
+        self._open = True
+        self._own = [None] * self.n_slots                 # the server's own engine of a slot, made on first use and reused
+        self._req = [None] * self.n_slots                 # the handle a slot serves
+        self._seen = [0] * self.n_slots
+        self._mirror = [(SERVE_FREE, 0, 0, 0, 0)] * self.n_slots      # the host's copy of the slot table (exact unless a stop token fell)
+        self._queue, self._results, self._finished, self._plans = [], {}, set(), {}
+        self._next = 0
+        self.planned = dict(steps=0, rows_decode=0, rows_prompt=0, rows_idle=0)      # the host plan's sums over the steps enqueued
+        self.last_rows = []                               # ... and its row table of the last one
+
+    # -- requests
+    def submit(self, context, max_new, temperature=0.0, topp=0.9, u=TOPP_U_CPU, stop_token=None, engine=None):
+        """queue a request -> its handle.  It is admitted at once if a slot is free, else when one finishes (step / run).
+        engine: the Q8Engine whose run state the sequence uses (default: one the server owns for the slot)."""
+        ctx, plan = serve_plan(self.cfg, context, max_new, temperature, topp, u, stop_token, self.max_new_cap)
+        if engine is not None and engine.model is not self.model:
+            raise ValueError("Q8Server.submit: the engine belongs to another Q8Model")
+        if engine is not None and any(e is engine for e in self._engines_in_use()):
+            raise ValueError("Q8Server.submit: the engine already serves a queued or running request")
+        h = self._next
+        self._next += 1
+        self._plans[h] = (ctx, plan, engine)
+        self._results[h] = []
+        self._queue.append(h)
+        self._admit()
+        return h
+
+    def _engines_in_use(self):
+        waiting = [self._plans[h][2] for h in self._queue]
+        running = [self._plans[h][2] for h in self._req if h is not None]
+        return [e for e in waiting + running if e is not None]
+
+    def _admit(self):
+        from ._lib import rama_q8_serve_plan
+        L, ctx = self.device.lib, self.device.ctx
+        for slot in range(self.n_slots):
+            if not self._queue:
+                return
+            if self._req[slot] is not None:
+                continue
+            h = self._queue[0]                             # (it leaves the queue once the library has taken it)
+            toks, (T, P, U, new, stop), eng = self._plans[h]
+            if eng is None:
+                if self._own[slot] is None:
+                    self._own[slot] = Q8Engine(self.device, self.model)
+                eng = self._own[slot]
+            rec = rama_q8_serve_plan(T, P, U, new, stop)
+            check(L.rama_q8_serve_admit(ctx, slot, C.byref(eng.state), (C.c_int32 * len(toks))(*toks), len(toks), C.byref(rec)),
+                  "rama_q8_serve_admit")
+            self._queue.pop(0)
+            self._req[slot], self._seen[slot] = h, 0
+            self._mirror[slot] = (SERVE_PROMPT, len(toks), 0, 0, new)
+
+    def _collect(self, on_token=None):
+        """what the rings hold: new tokens of every occupied slot; a finished occupant frees its slot"""
+        L, ctx = self.device.lib, self.device.ctx
+        buf = (C.c_int32 * 64)()
+        k, fin = C.c_int(), C.c_int()
+        early = False
+        for slot in range(self.n_slots):
+            h = self._req[slot]
+            if h is None:
+                continue
+            while True:
+                # the finished word is read before the ring: once it is set, every token of the occupant is there
+                check(L.rama_q8_serve_poll(ctx, slot, self._seen[slot], buf, 64, C.byref(k), C.byref(fin), None), "rama_q8_serve_poll")
+                for i in range(k.value):
+                    if on_token is not None:
+                        on_token(h, self._seen[slot] + i, int(buf[i]))
+                    self._results[h].append(int(buf[i]))
+                self._seen[slot] += k.value
+                if k.value < 64:
+                    break
+            if fin.value:
+                self._finished.add(h)
+                self._req[slot] = None
+                early = early or self._mirror[slot][0] != SERVE_DONE
+                self._mirror[slot] = (SERVE_DONE,) + tuple(self._mirror[slot][1:])
+        return early
+
+    def step(self, n: int = 1, on_token=None):
+        """collect what has arrived, admit queued requests into free slots, then enqueue n steps (asynchronous)"""
+        if self._collect(on_token):
+            self._resync()
+        self._admit()
+        self._count_and_enqueue(int(n))
+
+    def _count_and_enqueue(self, n):
+        for _ in range(n):
+            before = self._mirror
+            rows, self._mirror = serve_plan_step(before, self.max_rows)
+            self.last_rows = rows
+            dec = sum(1 for s, _, _ in rows if s >= 0 and before[s][0] == SERVE_DECODE)
+            used = sum(1 for s, _, _ in rows if s >= 0)
+            self.planned["steps"] += 1
+            self.planned["rows_decode"] += dec
+            self.planned["rows_prompt"] += used - dec
+            self.planned["rows_idle"] += self.max_rows - used
+        if n:
+            check(self.device.lib.rama_q8_serve_steps(self.device.ctx, n), "rama_q8_serve_steps")
+
+    def _resync(self):
+        """a stop token ended a sequence before its budget: the host's copy of the slot table is taken from the device again"""
+        st = self.stats()
+        self._mirror = [s if self._req[i] is not None or s[0] in (SERVE_FREE, SERVE_DONE) else (SERVE_DONE,) + s[1:] for i, s in enumerate(st["slots"])]
+
+    def _steps_to_next_finish(self):
+        """by the host plan: the steps until a slot finishes (requests waiting) or until all have (none waiting)"""
+        m, k = list(self._mirror), 0
+        live = lambda t: [s[0] in (SERVE_PROMPT, SERVE_DECODE) for s in t]
+        start = live(m)
+        while any(live(m)):
+            _, m = serve_plan_step(m, self.max_rows)
+            k += 1
+            if self._queue and live(m) != start:
+                break
+        return k
+
+    LOOKAHEAD = 2      # steps enqueued past a foreseen finish while requests wait: the admission then goes in behind running steps
+
+    def run(self, on_token=None):
+        """serve every submitted request to its end.  on_token(handle, index, token), when given, is fed from the host-visible
+        rings.  The steps up to the next finish the host plan foresees -- and, while requests wait, LOOKAHEAD more, so that the
+        device does not idle until the host has seen the finished word and admitted -- are enqueued at once; a DONE slot takes
+        no rows, and an admission is stream-ordered behind them, so the host plan stays exact.  A stop token that ends a sequence
+        earlier is seen at the next collection."""
+        import time
+        done_in = lambda t: {i for i in range(self.n_slots) if self._req[i] is not None and t[i][0] == SERVE_DONE}
+        while True:
+            if self._collect(on_token):
+                self._resync()
+            self._admit()
+            expect = done_in(self._mirror)                # finished by the plan, not yet seen
+            k = self._steps_to_next_finish()
+            if k == 0 and not expect:
+                if self._queue:
+                    raise RuntimeError("Q8Server.run: requests are waiting but no slot can take them")
+                return
+            if k:
+                after = self._after(k)
+                expect |= done_in(after)
+                live_on = any(s[0] in (SERVE_PROMPT, SERVE_DECODE) for s in after)
+                self._count_and_enqueue(k + (self.LOOKAHEAD if self._queue and live_on else 0))
+            while True:                       # until the slots the plan ends here have set their finished words
+                if self._collect(on_token):
+                    self._resync()
+                if all(self._req[i] is None for i in expect):
+                    break
+                q = self.device.lib.rama_stream_query(self.device.ctx)
+                if q == 1:
+                    time.sleep(0.0001)
+                    continue
+                check(q, "rama_stream_query")
+                self._collect(on_token)
+                if not all(self._req[i] is None for i in expect):
+                    raise RuntimeError(f"Q8Server.run: the steps have run but slots {[i for i in expect if self._req[i] is not None]} have not finished")
+                break
+
+    def _after(self, k):
+        m = list(self._mirror)
+        for _ in range(k):
+            _, m = serve_plan_step(m, self.max_rows)
+        return m
+
+    def finished(self, handle) -> bool:
+        return handle in self._finished
+
+    def poll(self, on_token=None):
+        """collect what the rings hold now (never touches the stream); on_token(handle, index, token) for every new token"""
+        if self._collect(on_token):
+            self._resync()
+
+    def result(self, handle):
+        """the tokens of request `handle` collected so far by run / step / poll (all of them once finished(handle))"""
+        return list(self._results[handle])
+
+    def stats(self):
+        """rama_q8_serve_stats (synchronises): the device's counters, the slot table, the last step's row table"""
+        from ._lib import rama_q8_serve_report
+        r = rama_q8_serve_report()
+        check(self.device.lib.rama_q8_serve_stats(self.device.ctx, C.byref(r)), "rama_q8_serve_stats")
+        return dict(steps=int(r.steps), graph_captures=int(r.graph_captures), rows_decode=int(r.rows_decode), rows_prompt=int(r.rows_prompt),
+                    rows_idle=int(r.rows_idle), n_slots=int(r.n_slots), max_rows=int(r.max_rows),
+                    last_rows=[(x.slot, x.pos, x.logits) for x in r.last_rows[:r.max_rows]],
+                    slots=[(s.state, s.n_context, s.cursor, s.n_out, s.max_new) for s in r.slots[:r.n_slots]],
+                    generation=[int(g) for g in r.generation[:r.n_slots]])
+
+    def close(self):
+        if self._open:
+            self._open = False
+            check(self.device.lib.rama_q8_serve_end(self.device.ctx), "rama_q8_serve_end")
+            for e in self._own:
+                if e is not None:
+                    e.free()
+            self._own = [None] * self.n_slots
