@@ -584,6 +584,33 @@ int  rama_q8_serve_plan_step(const rama_q8_serve_slot *slots, int n_slots, int m
                              rama_q8_serve_slot *slots_after);
 int  rama_q8_serve_end(rama_ctx *ctx);
 
+/* PROMPT CACHING for the serving chain.  Cache row t of a sequence is a function of tokens 0..t only, and its
+ * bits are the same whoever computed it (chunking, neighbours, max_rows, graph mode).  So rows computed once, by any sequence
+ * with the same first n tokens, are the rows this sequence would compute: copy them, start the cursor at n, and the tokens and
+ * cache rows are still those of rama_q8_generate on the sequence alone, bit for bit.
+ *
+ * rama_q8_serve_admit_at is rama_q8_serve_admit with the first n_cached positions taken as already present in `state`'s
+ * caches: rows 0..n_cached-1 of every layer are the rows of context[0..n_cached), written by work enqueued EARLIER on the
+ * context's stream (the caller's contract: a rama_q8_kv_fork, a rama_q8_prefill, an earlier occupant's steps).  The slot is
+ * installed PROMPT with cursor = n_cached and feeds context[n_cached..n_context).  The whole context is still passed and
+ * checked, and the slot's context buffer holds all of it.  0 <= n_cached <= n_context - 1: the final context position is
+ * always fed, its logits are needed.  n_cached == 0 is exactly rama_q8_serve_admit; every check of rama_q8_serve_admit
+ * applies, a bad n_cached is RAMA_EINVAL, a refusal leaves the chain as it was.  Stream-ordered, no synchronisation, the graph
+ * untouched, the slot's generation number goes up.
+ *
+ * rama_q8_kv_fork copies rows [0, n_rows) of every layer of src's key and value caches into each of dsts[0..n_dst) -- one
+ * launch that reads the source once and writes every destination.  1 <= n_dst <= 16, 0 <= n_rows <= seq_len; n_rows == 0 is a
+ * successful no-op.  Only cfg's dim, n_layers and seq_len and the states' key_cache / value_cache are used.  Stream-ordered on
+ * the context's stream, never synchronises, legal between any two rama_q8_serve_steps calls.  The source may belong to a live
+ * slot provided the copied rows lie below what earlier enqueued work has written (rows below a slot's cursor are never
+ * rewritten).  RAMA_EINVAL for a NULL argument or cache, n_dst or n_rows out of range, a destination whose caches overlap the
+ * source's or another destination's, and a destination that is in a live slot of the serving chain.  Cache bases that are not
+ * 16-byte aligned take a slower path with the same result. */
+int  rama_q8_serve_admit_at(rama_ctx *ctx, int slot, const rama_run_state *state, const int32_t *context_host, int n_context,
+                            int n_cached, const rama_q8_serve_plan *plan);
+int  rama_q8_kv_fork(rama_ctx *ctx, const rama_config *cfg, const rama_run_state *src, const rama_run_state *dsts, int n_dst,
+                     int n_rows);
+
 /* ---------------------------------------------------------------- measurement
  * HIP events on the context's stream (the stream the kernels are launched on). */
 int  rama_timer_start(rama_ctx *ctx);

@@ -222,6 +222,10 @@ extern "C" {
                                max_new_cap: c_int) -> c_int;
     pub fn rama_q8_serve_admit(ctx: *mut rama_ctx, slot: c_int, state: *const rama_run_state, context_host: *const i32, n_context: c_int,
                                plan: *const rama_q8_serve_plan) -> c_int;
+    pub fn rama_q8_serve_admit_at(ctx: *mut rama_ctx, slot: c_int, state: *const rama_run_state, context_host: *const i32, n_context: c_int,
+                                  n_cached: c_int, plan: *const rama_q8_serve_plan) -> c_int;
+    pub fn rama_q8_kv_fork(ctx: *mut rama_ctx, cfg: *const rama_config, src: *const rama_run_state, dsts: *const rama_run_state, n_dst: c_int,
+                           n_rows: c_int) -> c_int;
     pub fn rama_q8_serve_steps(ctx: *mut rama_ctx, n_steps: c_int) -> c_int;
     pub fn rama_q8_serve_poll(ctx: *mut rama_ctx, slot: c_int, from: c_int, out_tokens_host: *mut i32, max_tokens: c_int,
                               n_ready: *mut c_int, finished: *mut c_int, generation: *mut c_int) -> c_int;

@@ -199,6 +199,8 @@ SIGNATURES = {
     "rama_q8_decode_batch_stream_poll": (_int, [_vp, _int, _int, i32p, _int, C.POINTER(_int), C.POINTER(_int)]),
     "rama_q8_serve_begin": (_int, [_vp, _cfgp, C.POINTER(rama_q8_weights), _int, _int, _int]),
     "rama_q8_serve_admit": (_int, [_vp, _int, _sp, i32p, _int, C.POINTER(rama_q8_serve_plan)]),
+    "rama_q8_serve_admit_at": (_int, [_vp, _int, _sp, i32p, _int, _int, C.POINTER(rama_q8_serve_plan)]),
+    "rama_q8_kv_fork": (_int, [_vp, _cfgp, _sp, _sp, _int, _int]),
     "rama_q8_serve_steps": (_int, [_vp, _int]),
     "rama_q8_serve_poll": (_int, [_vp, _int, _int, i32p, _int, C.POINTER(_int), C.POINTER(_int), C.POINTER(_int)]),
     "rama_q8_serve_tokens": (_int, [_vp, _int, i32p, _int, C.POINTER(_int)]),

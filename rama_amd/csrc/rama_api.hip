@@ -13,6 +13,7 @@
 #include "q8.hpp"
 #include "q8_batch.hpp"
 #include "q8_serve.hpp"
+#include "q8_fork.hpp"
 
 #include <hip/hip_ext.h>   // hipExtLaunchKernelGGL: start/stop events carried by the dispatch itself
 
@@ -4062,7 +4063,10 @@ static bool serve_slot_live(const rama_ctx::Q8Serve& sv, int slot) {
     return sv.occupied[slot] && !__atomic_load_n(sv.done + slot, __ATOMIC_ACQUIRE);
 }
 
-int rama_q8_serve_admit(rama_ctx* c, int slot, const rama_run_state* state, const int32_t* context_host, int n_context, const rama_q8_serve_plan* plan) {
+// rama_q8_serve_admit (n_cached 0) and rama_q8_serve_admit_at: the slot starts PROMPT at cursor = n_cached, over rows 0 .. n_cached - 1 that
+// earlier work on the stream has put into the run state's caches
+static int serve_admit(rama_ctx* c, int slot, const rama_run_state* state, const int32_t* context_host, int n_context, int n_cached,
+                       const rama_q8_serve_plan* plan) {
     RAMA_ENTER(c);
     REQUIRE(c && c->q8s.n_slots > 0, RAMA_EINVAL, "q8_serve_admit: call rama_q8_serve_begin first");
     auto& sv = c->q8s;
@@ -4074,6 +4078,7 @@ int rama_q8_serve_admit(rama_ctx* c, int slot, const rama_run_state* state, cons
     REQUIRE(!serve_slot_live(sv, slot), RAMA_EINVAL, "q8_serve_admit: the slot is busy");
     const int V = sv.cfg.vocab_size;
     REQUIRE(n_context >= 1, RAMA_EINVAL, "q8_serve_admit: n_context < 1");
+    REQUIRE(n_cached >= 0 && n_cached <= n_context - 1, RAMA_EINVAL, "q8_serve_admit_at: n_cached outside [0, n_context - 1] (the final context position is always fed)");
     REQUIRE(plan->max_new >= 1, RAMA_EINVAL, "q8_serve_admit: max_new < 1");
     REQUIRE(plan->max_new <= sv.out_cap, RAMA_EINVAL, "q8_serve_admit: max_new beyond rama_q8_serve_begin's max_new_cap");
     REQUIRE(n_context <= sv.cfg.seq_len - plan->max_new, RAMA_EINVAL, "q8_serve_admit: n_context + max_new beyond seq_len");
@@ -4089,7 +4094,7 @@ int rama_q8_serve_admit(rama_ctx* c, int slot, const rama_run_state* state, cons
     char* rec = sv.pinned + (size_t)slot * sv.rec_bytes;
     ServeSlot h{};
     h.kc = state->key_cache; h.vc = state->value_cache;
-    h.state = kServePrompt; h.n_ctx = n_context; h.cursor = 0; h.tok = 0; h.n_out = 0;
+    h.state = kServePrompt; h.n_ctx = n_context; h.cursor = n_cached; h.tok = 0; h.n_out = 0;
     h.max_new = plan->max_new; h.stop = plan->stop_token; h.gen = sv.gen[slot] + 1;
     h.temperature = plan->temperature; h.topp = plan->topp; h.u = plan->u;
     memcpy(rec, &h, sizeof h);
@@ -4102,6 +4107,59 @@ int rama_q8_serve_admit(rama_ctx* c, int slot, const rama_run_state* state, cons
     hipLaunchKernelGGL(serve_install_kernel, dim3(1), dim3(256), 0, c->stream, sv.t, slot, reinterpret_cast<const ServeSlot*>(dst));
     LAUNCHCHK();
     sv.states[slot] = *state; sv.occupied[slot] = 1; sv.gen[slot]++;
+    return 0;
+}
+
+int rama_q8_serve_admit(rama_ctx* c, int slot, const rama_run_state* state, const int32_t* context_host, int n_context, const rama_q8_serve_plan* plan) {
+    return serve_admit(c, slot, state, context_host, n_context, 0, plan);
+}
+
+int rama_q8_serve_admit_at(rama_ctx* c, int slot, const rama_run_state* state, const int32_t* context_host, int n_context, int n_cached,
+                           const rama_q8_serve_plan* plan) {
+    return serve_admit(c, slot, state, context_host, n_context, n_cached, plan);
+}
+
+// rows [0, n_rows) of every layer of src's caches into every destination's: one launch (q8_fork.hpp), stream-ordered
+int rama_q8_kv_fork(rama_ctx* c, const rama_config* cfg, const rama_run_state* src, const rama_run_state* dsts, int n_dst, int n_rows) {
+    RAMA_ENTER(c);
+    REQUIRE(c, RAMA_EINVAL, "q8_kv_fork: ctx is NULL");
+    int rc = check_cfg(cfg); if (rc) return rc;
+    REQUIRE(src && dsts, RAMA_EINVAL, "q8_kv_fork: NULL argument");
+    REQUIRE(n_dst >= 1 && n_dst <= kForkMaxDst, RAMA_EINVAL, "q8_kv_fork: 1 <= n_dst <= 16");
+    REQUIRE(n_rows >= 0 && n_rows <= cfg->seq_len, RAMA_EINVAL, "q8_kv_fork: n_rows outside [0, seq_len]");
+    REQUIRE(src->key_cache && src->value_cache, RAMA_EINVAL, "q8_kv_fork: the source has no caches");
+    const size_t layer = (size_t)cfg->seq_len * (size_t)cfg->dim, total = layer * (size_t)cfg->n_layers;
+    // every cache written must lie clear of the source's and of every other one written
+    std::vector<const float*> caches = {src->key_cache, src->value_cache};
+    for (int d = 0; d < n_dst; d++) {
+        REQUIRE(dsts[d].key_cache && dsts[d].value_cache, RAMA_EINVAL, "q8_kv_fork: a destination has no caches");
+        caches.push_back(dsts[d].key_cache); caches.push_back(dsts[d].value_cache);
+    }
+    for (size_t i = 2; i < caches.size(); i++)
+        for (size_t j = 0; j < i; j++)
+            REQUIRE(!ranges_overlap(caches[i], total, caches[j], total), RAMA_EINVAL,
+                    "q8_kv_fork: a destination shares a cache with the source or with another destination");
+    const auto& sv = c->q8s;
+    for (int d = 0; d < n_dst; d++)
+        for (int j = 0; j < sv.n_slots; j++)
+            REQUIRE(!serve_slot_live(sv, j) || (sv.states[j].key_cache != dsts[d].key_cache && sv.states[j].value_cache != dsts[d].value_cache),
+                    RAMA_EINVAL, "q8_kv_fork: a destination is in a live slot of the serving chain");
+    if (n_rows == 0) return 0;
+    const size_t span = (size_t)n_rows * (size_t)cfg->dim, reach = layer * (size_t)(cfg->n_layers - 1) + span;
+    for (int d = 0; d < n_dst; d++) { RAMA_WRITES(c, dsts[d].key_cache, reach); RAMA_WRITES(c, dsts[d].value_cache, reach); }
+    if (set_device(c)) return 1;
+    ForkParams p{};
+    p.src[0] = src->key_cache; p.src[1] = src->value_cache;
+    bool vec = aligned16(p.src[0]) && aligned16(p.src[1]);       // (dim % 4 == 0: a layer and a span are whole 16-byte words)
+    for (int d = 0; d < n_dst; d++) {
+        p.dst[0][d] = dsts[d].key_cache; p.dst[1][d] = dsts[d].value_cache;
+        vec = vec && aligned16(p.dst[0][d]) && aligned16(p.dst[1][d]);
+    }
+    p.n_dst = n_dst; p.layer_floats = layer; p.n_words = vec ? span / 4 : span;
+    const dim3 grid((unsigned)((p.n_words + kForkPiece - 1) / kForkPiece), (unsigned)(2 * cfg->n_layers));
+    if (vec) hipLaunchKernelGGL(kv_fork_kernel<true>, grid, dim3(kForkThreads), 0, c->stream, p);
+    else hipLaunchKernelGGL(kv_fork_kernel<false>, grid, dim3(kForkThreads), 0, c->stream, p);
+    LAUNCHCHK();
     return 0;
 }
 

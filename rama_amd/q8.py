@@ -294,14 +294,16 @@ def serve_sizes(cfg, n_slots, max_rows, max_new_cap):
     return n_slots, max_rows, max_new_cap
 
 
-def serve_plan(cfg, context, max_new, temperature=0.0, topp=0.9, u=TOPP_U_CPU, stop_token=None, max_new_cap=None):
+def serve_plan(cfg, context, max_new, temperature=0.0, topp=0.9, u=TOPP_U_CPU, stop_token=None, max_new_cap=None, n_cached=0):
     """the checked arguments of Q8Server.submit: (context tokens, (temperature, topp, u, max_new, stop token)); ValueError for
-    everything rama_q8_serve_admit would refuse in them.  No library call."""
+    everything rama_q8_serve_admit / rama_q8_serve_admit_at would refuse in them.  No library call."""
     what = "Q8Server.submit"
     V, S = cfg.vocab_size, cfg.seq_len
     ctx = _tokens(context, V, what)
     if not ctx:
         raise ValueError(f"{what}: an empty context (the caller includes BOS)")
+    if not 0 <= int(n_cached) <= len(ctx) - 1:
+        raise ValueError(f"{what}: n_cached {int(n_cached)} outside [0, n_context - 1 = {len(ctx) - 1}] (the final context position is always fed)")
     T, P, U = float(temperature), float(topp), float(u)
     if not (T >= 0.0 and 0.0 <= P <= 1.0 and 0.0 <= U < 1.0):       # (false for NaN)
         raise ValueError(f"{what}: temperature >= 0, topp in [0, 1], u in [0, 1) -- not {T}, {P}, {U}")
@@ -333,20 +335,95 @@ def serve_plan_step(slots, max_rows):
             [(a.state, a.n_context, a.cursor, a.n_out, a.max_new) for a in after[:n]])
 
 
+def common_prefix(a, b) -> int:
+    """the number of leading tokens two sequences share"""
+    n = 0
+    for x, y in zip(a, b):
+        if x != y:
+            break
+        n += 1
+    return n
+
+
+class PrefixPool:
+    """the donors of Q8Server's prefix cache: at most k engines, each keyed by the tokens whose cache rows it holds (row t is a
+    function of tokens 0..t only, and its bits do not depend on who computed it).  Least recently used goes first.  Pure host
+    logic: an engine is any object, compared by identity.  While an engine is here it is a donor and nothing else."""
+
+    def __init__(self, k: int):
+        self.k = int(k)
+        if self.k < 0:
+            raise ValueError(f"PrefixPool: {self.k} donors")
+        self._donors = []                                 # [tokens, engine], least recently used first
+
+    def __len__(self):
+        return len(self._donors)
+
+    def __contains__(self, engine):
+        return any(d[1] is engine for d in self._donors)
+
+    def engines(self):
+        return [d[1] for d in self._donors]
+
+    def match(self, context, at_least: int = 1):
+        """-> (engine, n): the donor that shares the longest token prefix with `context`, n capped at len(context) - 1 (the final
+        context position is always fed: its logits are needed); (None, 0) when no donor shares at_least tokens.  Of equally
+        long matches the most recently used wins.  The donor found becomes the most recently used."""
+        best, best_n = None, 0
+        for d in self._donors:                            # (later = more recently used: >= lets it win a tie)
+            n = min(common_prefix(d[0], context), len(context) - 1)
+            if n >= max(at_least, 1) and n >= best_n:
+                best, best_n = d, n
+        if best is None:
+            return None, 0
+        self._donors.remove(best)
+        self._donors.append(best)
+        return best[1], best_n
+
+    def put(self, tokens, engine):
+        """`engine` holds the rows of `tokens` and becomes the most recently used donor -> the engines that left the pool for
+        it (none while there is room; the engine itself when k == 0)"""
+        if engine in self:
+            raise ValueError("PrefixPool.put: the engine is already a donor")
+        if self.k == 0:
+            return [engine]
+        self._donors.append([list(tokens), engine])
+        out = []
+        while len(self._donors) > self.k:
+            out.append(self._donors.pop(0)[1])
+        return out
+
+    def clear(self):
+        out, self._donors = self.engines(), []
+        return out
+
+
 class Q8Server:
     """continuous batching over one Q8Model (rama_q8_serve_begin / _admit / _steps / _poll): n_slots sequence slots share weight
     passes of max_rows rows; a finished sequence frees its slot for the next queued request while the others run on, and a new
     request's context is ingested in chunks next to the decoding slots.  Every request's tokens are those Q8Engine.generate gives
-    it alone.  One serving chain per device context at a time."""
+    it alone.  One serving chain per device context at a time.
 
-    def __init__(self, model: Q8Model, n_slots: int, max_rows=None, max_new_cap: int = 256):
+    Prompt caching.  submit(..., n_cached=n) admits over rows 0..n-1 that the caller's engine already holds
+    (a chat's next turn on the same engine).  prefix_cache=k keeps a pool of at most k donor engines: a request submitted with
+    retain=True leaves its engine there when it finishes, keyed by the tokens whose rows it holds; every later request is
+    matched against the pool at its admission, the longest shared prefix is forked into its engine (rama_q8_kv_fork) and the
+    slot starts at that cursor (rama_q8_serve_admit_at).  The tokens are the same with the cache on and off."""
+
+    def __init__(self, model: Q8Model, n_slots: int, max_rows=None, max_new_cap: int = 256, prefix_cache: int = 0):
         self.n_slots, self.max_rows, self.max_new_cap = serve_sizes(model.cfg, n_slots, max_rows, max_new_cap)
+        self.pool = PrefixPool(prefix_cache)              # (raises before any library call)
         self.model, self.device, self.cfg = model, model.device, model.cfg
         L = self.device.lib
         check(L.rama_q8_serve_begin(self.device.ctx, C.byref(model.ccfg), C.byref(model.weights), self.n_slots, self.max_rows,
                                     self.max_new_cap), "rama_q8_serve_begin")
         self._open = True
         self._own = [None] * self.n_slots                 # the server's own engine of a slot, made on first use and reused
+        self._eng = [None] * self.n_slots                 # the engine the slot's occupant runs on
+        self._spare = []                                  # the server's own engines that serve nobody: evicted donors
+        self._mine = []                                   # every engine the server made (close frees them)
+        self._cached = {}                                 # handle -> the n_cached it was admitted with
+        self.rows_cached = 0                              # ... summed over the admissions
         self._req = [None] * self.n_slots                 # the handle a slot serves
         self._seen = [0] * self.n_slots
         self._mirror = [(SERVE_FREE, 0, 0, 0, 0)] * self.n_slots      # the host's copy of the slot table (exact unless a stop token fell)
@@ -356,17 +433,28 @@ class Q8Server:
         self.last_rows = []                               # ... and its row table of the last one
 
     # -- requests
-    def submit(self, context, max_new, temperature=0.0, topp=0.9, u=TOPP_U_CPU, stop_token=None, engine=None):
+    def submit(self, context, max_new, temperature=0.0, topp=0.9, u=TOPP_U_CPU, stop_token=None, engine=None, n_cached=0,
+               retain=False):
         """queue a request -> its handle.  It is admitted at once if a slot is free, else when one finishes (step / run).
-        engine: the Q8Engine whose run state the sequence uses (default: one the server owns for the slot)."""
-        ctx, plan = serve_plan(self.cfg, context, max_new, temperature, topp, u, stop_token, self.max_new_cap)
+        engine: the Q8Engine whose run state the sequence uses (default: one the server owns for the slot).
+        n_cached: rows 0..n_cached-1 of `engine` already hold context[0..n_cached) -- written by work enqueued earlier on the
+        device's stream; the slot feeds the rest (at most n_context - 1: the final position is always fed).  Such a request is
+        not matched against the prefix cache.
+        retain: with a prefix cache, the engine stays behind as a donor when the request finishes (a caller's engine too: it
+        is the pool's until it is evicted)."""
+        ctx, plan = serve_plan(self.cfg, context, max_new, temperature, topp, u, stop_token, self.max_new_cap, n_cached)
+        n_cached = int(n_cached)
+        if n_cached and engine is None:
+            raise ValueError("Q8Server.submit: n_cached needs the engine that holds the rows")
         if engine is not None and engine.model is not self.model:
             raise ValueError("Q8Server.submit: the engine belongs to another Q8Model")
         if engine is not None and any(e is engine for e in self._engines_in_use()):
             raise ValueError("Q8Server.submit: the engine already serves a queued or running request")
+        if engine is not None and engine in self.pool:
+            raise ValueError("Q8Server.submit: the engine is a donor of the prefix cache")
         h = self._next
         self._next += 1
-        self._plans[h] = (ctx, plan, engine)
+        self._plans[h] = (ctx, plan, engine, n_cached, bool(retain))
         self._results[h] = []
         self._queue.append(h)
         self._admit()
@@ -374,7 +462,7 @@ class Q8Server:
 
     def _engines_in_use(self):
         waiting = [self._plans[h][2] for h in self._queue]
-        running = [self._plans[h][2] for h in self._req if h is not None]
+        running = [self._eng[i] for i, h in enumerate(self._req) if h is not None]
         return [e for e in waiting + running if e is not None]
 
     def _admit(self):
@@ -386,17 +474,52 @@ class Q8Server:
             if self._req[slot] is not None:
                 continue
             h = self._queue[0]                             # (it leaves the queue once the library has taken it)
-            toks, (T, P, U, new, stop), eng = self._plans[h]
+            toks, (T, P, U, new, stop), eng, n_cached, _ = self._plans[h]
             if eng is None:
                 if self._own[slot] is None:
-                    self._own[slot] = Q8Engine(self.device, self.model)
+                    self._own[slot] = self._spare.pop() if self._spare else self._new_engine()
                 eng = self._own[slot]
+            if not n_cached and len(self.pool):
+                # the donor stays in the pool whatever happens below: donors leave it in _collect only, so a fork that was
+                # enqueued and an admission that then failed find it there at the next attempt; an evicted donor is reused or
+                # freed behind the fork in stream order
+                donor, n_cached = self.pool.match(toks, self.MIN_CACHED)
+                if n_cached:
+                    check(L.rama_q8_kv_fork(ctx, C.byref(self.model.ccfg), C.byref(donor.state), C.byref(eng.state), 1, n_cached),
+                          "rama_q8_kv_fork")
             rec = rama_q8_serve_plan(T, P, U, new, stop)
-            check(L.rama_q8_serve_admit(ctx, slot, C.byref(eng.state), (C.c_int32 * len(toks))(*toks), len(toks), C.byref(rec)),
-                  "rama_q8_serve_admit")
+            arr = (C.c_int32 * len(toks))(*toks)
+            if n_cached:
+                check(L.rama_q8_serve_admit_at(ctx, slot, C.byref(eng.state), arr, len(toks), n_cached, C.byref(rec)), "rama_q8_serve_admit_at")
+            else:
+                check(L.rama_q8_serve_admit(ctx, slot, C.byref(eng.state), arr, len(toks), C.byref(rec)), "rama_q8_serve_admit")
             self._queue.pop(0)
-            self._req[slot], self._seen[slot] = h, 0
-            self._mirror[slot] = (SERVE_PROMPT, len(toks), 0, 0, new)
+            self._req[slot], self._seen[slot], self._eng[slot] = h, 0, eng
+            self._cached[h] = n_cached
+            self.rows_cached += n_cached
+            self._mirror[slot] = (SERVE_PROMPT, len(toks), n_cached, 0, new)
+
+    def _new_engine(self):
+        e = Q8Engine(self.device, self.model)
+        self._mine.append(e)
+        return e
+
+    def _retire(self, slot, h):
+        """a finished occupant: with retain and a prefix cache its engine becomes a donor, keyed by the tokens it was fed (the
+        context and every output but the last); whoever leaves the pool for it serves requests again if the server made it"""
+        toks, _, _, _, retain = self._plans[h]
+        eng, self._eng[slot] = self._eng[slot], None
+        if not retain or self.pool.k == 0:
+            return
+        if self._own[slot] is eng:
+            self._own[slot] = None
+        for e in self.pool.put(toks + self._results[h][:-1], eng):
+            if any(e is m for m in self._mine):
+                self._spare.append(e)
+
+    def cached(self, handle) -> int:
+        """the n_cached request `handle` was admitted with (None while it waits)"""
+        return self._cached.get(handle)
 
     def _collect(self, on_token=None):
         """what the rings hold: new tokens of every occupied slot; a finished occupant frees its slot"""
@@ -421,6 +544,7 @@ class Q8Server:
             if fin.value:
                 self._finished.add(h)
                 self._req[slot] = None
+                self._retire(slot, h)
                 early = early or self._mirror[slot][0] != SERVE_DONE
                 self._mirror[slot] = (SERVE_DONE,) + tuple(self._mirror[slot][1:])
         return early
@@ -462,6 +586,8 @@ class Q8Server:
             if self._queue and live(m) != start:
                 break
         return k
+
+    MIN_CACHED = 2     # a shorter match is not worth a launch: every context shares its first token (BOS) with every donor
 
     LOOKAHEAD = 2      # steps enqueued past a foreseen finish while requests wait: the admission then goes in behind running steps
 
@@ -522,12 +648,13 @@ class Q8Server:
         return list(self._results[handle])
 
     def stats(self):
-        """rama_q8_serve_stats (synchronises): the device's counters, the slot table, the last step's row table"""
+        """rama_q8_serve_stats (synchronises): the device's counters, the slot table, the last step's row table; rows_cached is the
+        host's sum of n_cached over the admissions (context positions taken from cached rows instead of being fed)"""
         from ._lib import rama_q8_serve_report
         r = rama_q8_serve_report()
         check(self.device.lib.rama_q8_serve_stats(self.device.ctx, C.byref(r)), "rama_q8_serve_stats")
         return dict(steps=int(r.steps), graph_captures=int(r.graph_captures), rows_decode=int(r.rows_decode), rows_prompt=int(r.rows_prompt),
-                    rows_idle=int(r.rows_idle), n_slots=int(r.n_slots), max_rows=int(r.max_rows),
+                    rows_idle=int(r.rows_idle), rows_cached=self.rows_cached, n_slots=int(r.n_slots), max_rows=int(r.max_rows),
                     last_rows=[(x.slot, x.pos, x.logits) for x in r.last_rows[:r.max_rows]],
                     slots=[(s.state, s.n_context, s.cursor, s.n_out, s.max_new) for s in r.slots[:r.n_slots]],
                     generation=[int(g) for g in r.generation[:r.n_slots]])
@@ -536,7 +663,8 @@ class Q8Server:
         if self._open:
             self._open = False
             check(self.device.lib.rama_q8_serve_end(self.device.ctx), "rama_q8_serve_end")
-            for e in self._own:
-                if e is not None:
-                    e.free()
-            self._own = [None] * self.n_slots
+            self.pool.clear()                             # (a caller's engine that was a donor is the caller's again)
+            for e in self._mine:
+                e.free()
+            self._mine, self._spare = [], []
+            self._own, self._eng = [None] * self.n_slots, [None] * self.n_slots
