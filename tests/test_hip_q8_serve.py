@@ -373,48 +373,75 @@ def test_device_plan_equals_host_plan(dev, golden_dir, graph):
 
 # ------------------------------------------------------------------ 5. the full shape
 
-def test_7b_shape_one_layer_context_across_1024_next_to_decoding_slots(dev):
-    """one llama2-7B-shaped layer (GS 64): a context of 1 100 tokens ingested in chunks next to three decoding slots, graph mode; tokens
-    and cache rows against rama_q8_forward + the last maximal index, position by position"""
+SIZES_7B = [(2, 14), (1100, 4), (3, 12), (1, 13)]
+
+
+@pytest.fixture(scope="module")
+def shape_7b(dev):
+    """one llama2-7B-shaped layer (GS 64), four contexts, and -- taken once, by rama_q8_forward + the last maximal index, position
+    by position -- every sequence's tokens and cache rows"""
     import rama_amd
     cfg = dict(dim=4096, hidden_dim=11008, n_layers=1, n_heads=32, n_kv_heads=32, vocab_size=32000, seq_len=2048, shared_weight=False)
     m = rama_amd.Q8Model.synth(dev, O.Config(**cfg), 64, 5)
     rng = np.random.default_rng(0)
-    d = cfg["dim"]
-    sizes = [(2, 14), (1100, 4), (3, 12), (1, 13)]
-    ctxs = [[1] + [int(t) for t in rng.integers(2, 32000, n - 1)] for n, _ in sizes]
-    engs = [rama_amd.Q8Engine(dev, m) for _ in sizes]
+    ctxs = [[1] + [int(t) for t in rng.integers(2, 32000, n - 1)] for n, _ in SIZES_7B]
     twin = rama_amd.Q8Engine(dev, m)
-    from rama_amd._lib import rama_q8_serve_plan
+    want, want_rows = [], []
     try:
-        set_graph(dev, 1)
-        assert begin(dev, m, 4, 128, 16) == 0
-        for i, (ctx, (_, new)) in enumerate(zip(ctxs, sizes)):
-            p = rama_q8_serve_plan(0.0, 0.9, 0.0, new, -1)
-            assert dev.lib.rama_q8_serve_admit(dev.ctx, i, C.byref(engs[i].state), (C.c_int32 * len(ctx))(*ctx), len(ctx), C.byref(p)) == 0
-        assert steps(dev, 14) == 0
-        st = stats(dev)
-        assert all(s[0] == DONE for s in st["slots"]) and st["captures"] == 1
-        assert st["prompt"] == sum(n for n, _ in sizes) and st["decode"] == sum(new - 1 for _, new in sizes)
-        set_graph(dev, 0)
-        for i, (ctx, (n, new)) in enumerate(zip(ctxs, sizes)):
-            want, t = [], None
+        for ctx, (n, new) in zip(ctxs, SIZES_7B):
+            toks, t = [], None
             for p in range(n + new - 1):
                 twin.forward(ctx[p] if p < n else t, p)
                 if p >= n - 1:
                     lg = twin.logits()
                     t = int(lg.size - 1 - np.argmax(lg[::-1]))        # Device::sample at temperature 0: the last maximal index
-                    want.append(t)
-            assert tokens(dev, i) == want, i
+                    toks.append(t)
+            want.append(toks)
+            want_rows.append({name: twin.buffer(name, (n + new - 1) * cfg["dim"]) for name in ("key_cache", "value_cache")})
+    finally:
+        twin.free()
+    yield m, ctxs, want, want_rows
+    m.free()
+
+
+@pytest.mark.parametrize("max_rows", [24, 48, 128])
+def test_7b_shape_one_layer_context_across_1024_next_to_decoding_slots(dev, shape_7b, max_rows):
+    """one llama2-7B-shaped layer (GS 64): a context of 1 100 tokens ingested in chunks next to three decoding slots, graph mode, at
+    24 rows (the products' ksplit<2> form), 48 (the one-wave MFMA form over four token tiles, the fourth one beyond max_rows) and
+    128; tokens and cache rows against rama_q8_forward + the last maximal index, position by position (taken once, shape_7b)"""
+    import rama_amd
+    from rama_amd._lib import rama_q8_serve_plan
+    from rama_amd.q8 import serve_plan_step
+    m, ctxs, want, want_rows = shape_7b
+    sizes = SIZES_7B
+    d = m.cfg.dim
+    engs = [rama_amd.Q8Engine(dev, m) for _ in sizes]
+    try:
+        set_graph(dev, 1)
+        assert begin(dev, m, 4, max_rows, 16) == 0
+        for i, (ctx, (_, new)) in enumerate(zip(ctxs, sizes)):
+            p = rama_q8_serve_plan(0.0, 0.9, 0.0, new, -1)
+            assert dev.lib.rama_q8_serve_admit(dev.ctx, i, C.byref(engs[i].state), (C.c_int32 * len(ctx))(*ctx), len(ctx), C.byref(p)) == 0
+        t, n_steps = [(PROMPT, n, 0, 0, new) for n, new in sizes], 0     # greedy plans without a stop token: the host plan is exact
+        while any(s[0] in (PROMPT, DECODE) for s in t):
+            _, t = serve_plan_step(t, max_rows)
+            n_steps += 1
+        assert n_steps == {24: 51, 48: 27, 128: 14}[max_rows]      # (14: the count this test enqueued before it took the plan's)
+        assert steps(dev, n_steps) == 0
+        st = stats(dev)
+        assert all(s[0] == DONE for s in st["slots"]) and st["captures"] == 1 and st["steps"] == n_steps
+        assert st["prompt"] == sum(n for n, _ in sizes) and st["decode"] == sum(new - 1 for _, new in sizes)
+        set_graph(dev, 0)
+        for i, (n, new) in enumerate(sizes):
+            assert tokens(dev, i) == want[i], i
             rows = (n + new - 1) * d
             for name in ("key_cache", "value_cache"):
-                assert same_bits(engs[i].buffer(name, rows), twin.buffer(name, rows)), (i, name)
+                assert same_bits(engs[i].buffer(name, rows), want_rows[i][name]), (i, name)
     finally:
         set_graph(dev, 0)
         dev.lib.rama_q8_serve_end(dev.ctx)
-        for e in engs + [twin]:
+        for e in engs:
             e.free()
-        m.free()
 
 
 # ------------------------------------------------------------------ 6. refusals
