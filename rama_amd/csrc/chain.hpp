@@ -28,6 +28,7 @@
 // Results are bit-identical to ref_order.hpp's and to the oracle's (tests/test_hip_ref_order.py,
 // tests/test_hip_parity_7b.py).
 #pragma once
+#define RAMA_CHAIN_HPP 1      // (q8_api.hip refuses to be compiled with this header: DESIGN.md section 9)
 #include "kernels.hpp"
 #include "ref_order.hpp"
 #include "topp_sort.hpp"
@@ -1186,14 +1187,6 @@ __global__ __launch_bounds__(kGcThreads) void gemm_chain_kernel(GemmChainParams 
             }
         }
     }
-}
-
-// X[t] = token_embedding_table[tokens[t]] (infer.rs:13), rows of a token batch
-__global__ void embed_rows_kernel(float* X, const float* emb, const int* tokens, int n_tok, int dim) {
-    const int t = blockIdx.y;
-    if (t >= n_tok) return;
-    const size_t base = (size_t)tokens[t] * dim;
-    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < dim; k += gridDim.x * blockDim.x) X[(size_t)t * dim + k] = emb[base + k];
 }
 
 // ---------------------------------------------------------------- cpu.rs:23-52 multi_head_attention

@@ -25,7 +25,6 @@
 
 namespace rama {
 
-typedef unsigned long long tagged_t;          // low word: the float's bits, high word: the epoch it was written in
 typedef __attribute__((ext_vector_type(4))) unsigned u4;
 
 struct FusedParams {

@@ -1,0 +1,282 @@
+// ops_kernels.hpp -- the kernels of kernels.hpp that are no templates and that rama_api.hip alone launches: the 1:1 ops, the single-sequence samplers, the synthetic fill.
+// A kernel that is no template is emitted by every translation unit that sees its definition, so these live
+// apart from the types, device functions and template kernels of kernels.hpp, which q8_api.hip sees too.
+#pragma once
+#include "kernels.hpp"
+
+namespace rama {
+
+// generic o_cols > 1 product of the trait signature (never used by forward): one thread per output
+__global__ void matmul_generic(float* o, const float* a, const float* b, int width, int o_rows, int o_cols) {
+    int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= o_rows * o_cols) return;
+    int r = idx / o_cols, c = idx % o_cols;
+    float acc = 0.0f;
+    for (int k = 0; k < width; k++) acc = fmaf(a[(size_t)r * width + k], b[(size_t)k * o_cols + c], acc);
+    o[idx] = acc;
+}
+
+// unaligned-view fallback of the o_cols == 1 product (16-byte alignment not given): one wave per row
+__global__ __launch_bounds__(kWG) void matvec_unaligned(float* o, const float* a, const float* x, int width, int rows) {
+    int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    int lane = threadIdx.x & 63;
+    float acc = 0.0f;
+    for (int k = lane; k < width; k += 64) acc = fmaf(a[(size_t)row * width + k], x[k], acc);
+    acc = wave_sum(acc);
+    if (lane == 0) o[row] = acc;
+}
+
+// split-T combine: xb[h] = sum_s e^(m_s - M) acc_s / sum_s e^(m_s - M) l_s,  M = max_s m_s
+// (algebraically the softmax over all timesteps; an empty slice has l = 0 and drops out)
+// the plain loop (round 1), kept for A/B (rama_set_tuning "combine_v" = 0)
+__global__ void attention_combine_loop_kernel(const float* part, float* xb, int head_size, int nsplit) {
+    const int h = blockIdx.x, i = threadIdx.x;
+    const size_t ps = (size_t)(head_size + 4);
+    const float* ph = part + (size_t)h * nsplit * ps;
+    float M = -INFINITY;
+    for (int s = 0; s < nsplit; s++) if (ph[s * ps + 1] > 0.0f) M = fmaxf(M, ph[s * ps]);
+    float L = 0.0f, o = 0.0f;
+    for (int s = 0; s < nsplit; s++) {
+        const float l = ph[s * ps + 1];
+        if (l > 0.0f) {
+            const float sc = expf(ph[s * ps] - M);
+            L += sc * l;
+            if (i < head_size) o += sc * ph[s * ps + 4 + i];
+        }
+    }
+    if (i < head_size) xb[(size_t)h * head_size + i] = o / L;
+}
+
+// cursor from a token id that lives in device memory (pipeline stages); an id outside the
+// vocabulary is clamped so a corrupted hand-off cannot turn into a wild embedding read
+__global__ void set_ctl_dev_kernel(Ctl* ctl, const int* token_dev, int pos, int vocab) {
+    int t = token_dev ? *token_dev : 0;
+    t = t < 0 ? 0 : (t >= vocab ? vocab - 1 : t);
+    ctl->token = t; ctl->pos = pos; ctl->n_forced = 0; ctl->n_out = 0;
+}
+
+__global__ void array_add_kernel(float* t, const float* s, size_t n) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) t[i] += s[i];
+}
+
+__global__ void array_mult_kernel(float* t, const float* s, size_t n) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) t[i] *= s[i];
+}
+
+__global__ void sinu_kernel(float* o, size_t n) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        float a = o[i];
+        o[i] = a * (1.0f / (1.0f + expf(-a)));
+    }
+}
+
+// two Device::copy_from_slice calls as one launch (infer.rs:32-33: the key row and the value row of the cache)
+__global__ void copy2_kernel(float* t1, const float* s1, size_t n1, float* t2, const float* s2, size_t n2) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n1 + n2; i += (size_t)gridDim.x * blockDim.x) {
+        if (i < n1) t1[i] = s1[i]; else t2[i - n1] = s2[i - n1];
+    }
+}
+
+// Device::sinu followed by Device::array_mult on the same vector (infer.rs:44-45) as one launch, each product rounded as in the two
+__global__ void sinu_mult_kernel(float* o, const float* s, size_t n) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        float a = o[i];
+        a = a * (1.0f / (1.0f + expf(-a)));
+        o[i] = a * s[i];
+    }
+}
+
+// cpu.rs:99-117, one workgroup
+__global__ __launch_bounds__(1024) void rmsnorm_kernel(float* o, const float* x, const float* w, int n) {
+    __shared__ float red[16];
+    float ss = 0.0f;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) ss = fmaf(x[i], x[i], ss);
+    ss = block_sum(ss, red);
+    const float v = rms_scale(ss, n);
+    for (int i = threadIdx.x; i < n; i += blockDim.x) o[i] = w[i] * (v * x[i]);
+}
+
+// cpu.rs:74-97, one head
+__global__ void apply_position_kernel(float* q, float* k, const float* pr, const float* pi, int head_size) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= head_size / 2) return;
+    float c = pr[i], s = pi[i];
+    float q0 = q[2 * i], q1 = q[2 * i + 1];
+    q[2 * i] = q0 * c - q1 * s; q[2 * i + 1] = q0 * s + q1 * c;
+    float k0 = k[2 * i], k1 = k[2 * i + 1];
+    k[2 * i] = k0 * c - k1 * s; k[2 * i + 1] = k0 * s + k1 * c;
+}
+
+// ... for a run of consecutive heads (dim = heads x head_size floats of q and of k; the same table rows for every head: infer.rs:25-29's loop as one launch)
+__global__ void apply_position_heads_kernel(float* q, float* k, const float* pr, const float* pi, int head_size, int dim) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= dim / 2) return;
+    const int i = j % (head_size / 2);
+    float c = pr[i], s = pi[i];
+    float q0 = q[2 * j], q1 = q[2 * j + 1];
+    q[2 * j] = q0 * c - q1 * s; q[2 * j + 1] = q0 * s + q1 * c;
+    float k0 = k[2 * j], k1 = k[2 * j + 1];
+    k[2 * j] = k0 * c - k1 * s; k[2 * j + 1] = k0 * s + k1 * c;
+}
+
+// cpu.rs:119-125, one workgroup
+__global__ __launch_bounds__(1024) void softmax_kernel(float* x, int n) {
+    __shared__ float red[16];
+    float mx = -INFINITY;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) mx = fmaxf(mx, x[i]);
+    mx = block_max(mx, red);
+    float sum = 0.0f;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) { float e = expf(x[i] - mx); x[i] = e; sum += e; }
+    sum = block_sum(sum, red);
+    for (int i = threadIdx.x; i < n; i += blockDim.x) x[i] /= sum;
+}
+
+__global__ __launch_bounds__(1024) void argmax_kernel(ArgmaxParams p) {
+    __shared__ float s_v[16];
+    __shared__ int s_i[16];
+    __shared__ int s_next;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // cursor reads go out first; their latency overlaps the logits sweep
+    int pos = 0, n_forced = 0, n_out = 0, forced_tok = -1;
+    if (p.ctl && tid == 0) {
+        pos = p.ctl->pos; n_forced = p.ctl->n_forced; n_out = p.ctl->n_out;
+        if (pos < n_forced) forced_tok = p.forced[pos];
+    }
+    float bv = -INFINITY; int bi = -1;
+    // 16-byte loads when the view is aligned; every thread visits its indices in ascending
+    // order, so "replace unless strictly smaller" keeps the LAST maximum (cpu.rs:165-167)
+    const int n4 = (((uintptr_t)p.logits & 15) == 0) ? (p.n >> 2) : 0;
+    const f4* l4 = reinterpret_cast<const f4*>(p.logits);
+    // 8 loads in flight per thread: one workgroup sweeps 128 KB, and a dependent load per iteration
+    // would cost a cache round trip each (this launch is pure latency)
+    for (int i0 = tid; i0 < n4; i0 += 8 * 1024) {
+        f4 v[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) v[u] = l4[min(i0 + u * 1024, n4 - 1)];      // ([r4] clamped, not conditional: `i < n4 ? load : x` is a branch with
+                                                                                  // s_waitcnt vmcnt(0) behind it -- the eight loads went out one by one)
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            const int i = i0 + u * 1024;
+            if (i < n4) {
+                if (!(bv > v[u].x)) { bv = v[u].x; bi = 4 * i; }
+                if (!(bv > v[u].y)) { bv = v[u].y; bi = 4 * i + 1; }
+                if (!(bv > v[u].z)) { bv = v[u].z; bi = 4 * i + 2; }
+                if (!(bv > v[u].w)) { bv = v[u].w; bi = 4 * i + 3; }
+            }
+        }
+    }
+    for (int i = 4 * n4 + tid; i < p.n; i += 1024) {
+        const float v = p.logits[i];
+        if (!(bv > v)) { bv = v; bi = i; }
+    }
+    const float wm = wave_max(bv);
+    const int wi = wave_max_i(bv == wm ? bi : -1);
+    if (lane == 0) { s_v[wave] = wm; s_i[wave] = wi; }
+    __syncthreads();
+    if (tid == 0) {
+        float v = s_v[0]; int idx = s_i[0];
+        for (int w = 1; w < 16; w++) {
+            const float ov = s_v[w]; const int oi = s_i[w];
+            if (oi >= 0 && (idx < 0 || ov > v || (ov == v && oi > idx))) { v = ov; idx = oi; }
+        }
+        s_next = finish_step(p, idx, pos, n_forced, n_out, forced_tok);
+    }
+    gather_next_embedding(p, &s_next);
+}
+
+__global__ __launch_bounds__(1024) void topp_pick_kernel(ToppParams p, ArgmaxParams fin) {
+    __shared__ float s_p[2][kToppChunk];
+    __shared__ int s_last, s_next, s_pick;
+    __shared__ float s_cum;
+    const int tid = threadIdx.x;
+    int pos = 0, n_forced = 0, n_out = 0, forced_tok = -1;
+    if (fin.ctl && tid == 0) {
+        pos = fin.ctl->pos; n_forced = fin.ctl->n_forced; n_out = fin.ctl->n_out;
+        if (pos < n_forced) forced_tok = fin.forced[pos];
+    }
+    const int m = *p.m;
+    if (tid == 0) { s_last = m > 0 ? m - 1 : 0; s_cum = 0.0f; s_pick = 0; }
+    // Sequential running sum in sorted order (infer.rs:70-73): the fp32 rounding of cum_i depends
+    // on every earlier add, so the chain cannot be split.  Wave 0 walks it 64 values at a time with
+    // a lane ripple: lane i holds p_i, lane 0 is seeded with carry + p_0, and 63 identical
+    // `v_add_f32_dpp s, s, p wave_shr:1` steps (lane i: s = s[i-1] + p_i; lane 0 has no source lane
+    // and keeps its value) leave S_i in lane i -- one 4-cycle VALU op (+2 wait states) per element,
+    // no LDS turn inside the chain.  All threads stage the next 4096-value chunk meanwhile (double
+    // buffer) and afterwards copy the running sums out.  Padding zeros leave the sum unchanged.
+    const int nchunks = (m + kToppChunk - 1) / kToppChunk;
+    auto stage = [&](int c) {
+        const int base = c * kToppChunk, len = min(kToppChunk, m - base), padded = (len + 63) & ~63;
+        for (int i = tid; i < padded; i += 1024) s_p[c & 1][i] = i < len ? p.keys[base + i] : 0.0f;
+    };
+    if (nchunks > 0) stage(0);
+    __syncthreads();
+    for (int c = 0; c < nchunks; c++) {
+        const int base = c * kToppChunk, len = min(kToppChunk, m - base);
+        if (c + 1 < nchunks) stage(c + 1);
+        if (tid < 64) {
+            float* q = s_p[c & 1];
+            float carry = s_cum;
+            const int nblk = (len + 63) >> 6;
+            int hit = -1;
+            float pv = q[tid];
+            for (int blk = 0; blk < nblk; blk++) {
+                const float pn = q[min(blk + 1, nblk - 1) * 64 + tid];      // next block's values: in flight during the ripple
+                float sv = tid == 0 ? carry + pv : pv;
+#pragma unroll
+                for (int k = 0; k < 63; k++)
+                    asm volatile("s_nop 1\n\tv_add_f32_dpp %0, %0, %1 wave_shr:1 row_mask:0xf bank_mask:0xf" : "+v"(sv) : "v"(pv));
+                q[blk * 64 + tid] = sv;
+                carry = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, sv), 63));
+                const unsigned long long over = __ballot(sv > p.topp);
+                if (over) {                       // sums are non-decreasing: the first set lane is the crossing
+                    const int l0 = __ffsll((long long)over) - 1;
+                    hit = blk * 64 + l0;
+                    carry = __shfl(sv, l0);
+                    break;
+                }
+                pv = pn;
+            }
+            if (tid == 0) {
+                s_cum = carry;
+                if (hit >= 0) { s_last = base + hit; s_pick = 1; }
+            }
+        }
+        __syncthreads();
+        // running sums of this chunk -> global (read again below); only indices < last matter
+        for (int i = tid; i < len; i += 1024) p.prefix[base + i] = s_p[c & 1][i];
+        if (s_pick) break;                                   // uniform
+        __syncthreads();
+    }
+    __syncthreads();
+    // r = u * cum; the first i < last whose running sum exceeds r wins, else `last` (infer.rs:75-84);
+    // the running sums of that loop are exactly the ones stored above
+    const int last = s_last;
+    const float r = p.u * s_cum;
+    // the running sums never decrease, so "first i < last with r < cum_i" = the number of i < last
+    // with cum_i <= r: independent loads, no early exit
+    int below = 0;
+    for (int i = tid; i < last; i += 1024) below += !(r < p.prefix[i]);
+    const int best = min(block_sum_i(below), last);
+    if (tid == 0) {
+        const int idx = m > 0 ? p.vals[best] : -1;
+        s_next = finish_step(fin, idx, pos, n_forced, n_out, forced_tok);
+    }
+    gather_next_embedding(fin, &s_next);
+}
+
+// bit-exact twin of oracle_fill_synth (integer hash, Irwin-Hall(4), one multiply, one add)
+__global__ void fill_synth_kernel(float* dst, size_t n, uint64_t base, float scale, float bias) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        uint64_t z = (uint64_t)i + base;
+        z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ULL;
+        z ^= z >> 27; z *= 0x94D049BB133111EBULL;
+        z ^= z >> 31;
+        int sum = (int)(z & 0xFFFF) + (int)((z >> 16) & 0xFFFF) + (int)((z >> 32) & 0xFFFF) + (int)(z >> 48);
+        float prod = (float)(sum - 131070) * scale;
+        asm volatile("" : "+v"(prod));   // opaque: bias + prod must round twice like the CPU generator, never one FMA
+        dst[i] = bias + prod;
+    }
+}
+
+}  // namespace rama

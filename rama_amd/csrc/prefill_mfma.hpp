@@ -42,7 +42,7 @@ namespace rama {
 
 constexpr int kMfWaves = 8;
 constexpr int kMfThreads = kMfWaves * 64;
-constexpr int kMfMaxTok = 128;               // tokens per pass (PT <= 8; PT = 5 .. 8 need the tile-order weight copy)
+// kMfMaxTok (kernels.hpp) = 128: tokens per pass (PT <= 8; PT = 5 .. 8 need the tile-order weight copy)
 constexpr int kMfMaxTokRows = 64;            // ... with row-major weights (PT <= 4)
 
 enum { EPI_SWIGLU = 3, EPI_STORE_ROWS = 4 };

@@ -1,0 +1,1082 @@
+// q8_api.hip -- the Q8 part of the C ABI of include/rama_hip.h: rama_q8_quantize / _matmul, the Q8 forward and generate, the token
+// batches (prefill, decode batch), the chained batch and the serving chain.  The kernels are q8.hpp, q8_batch.hpp, q8_serve.hpp and
+// q8_fork.hpp; parity mode's norms and attention and the samplers are reached through the launchers of ctx.hpp, which rama_api.hip
+// defines -- this translation unit instantiates none of their kernels (DESIGN.md "Translation units").
+#include "ctx.hpp"
+#include "q8.hpp"
+#include "q8_batch.hpp"
+#include "q8_serve.hpp"
+#include "q8_fork.hpp"
+
+#ifdef RAMA_CHAIN_HPP
+#error "q8_api.hip must not include chain.hpp: its kernels and g_pred_stats belong to rama_api.hip's code object"
+#endif
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+// the captured Q8 steps: all of them (s == NULL) or those over one run state (drop_graph and rama_state_free of rama_api.hip call this too)
+void drop_q8_graphs(rama_ctx* c, const rama_run_state* s) {
+    // the chained batch's step: it goes with all Q8 graphs, and with a member's run state -- after which the chain is dead
+    bool member = false;
+    for (const auto& m : c->q8c.states) member = member || (s && m.key_cache == s->key_cache);
+    if (c->q8c.cg.exec && (!s || member)) { (void)hipStreamSynchronize(c->stream); destroy_graph(c->q8c.cg); }
+    if (member) c->q8c.live = false;
+    // the serving chain: its step goes with all Q8 graphs (the next rama_q8_serve_steps captures again); the run state of a slot whose
+    // occupant the host cannot yet see DONE ends the chain -- a finished occupant's is its owner's again
+    auto& sv = c->q8s;
+    if (!s && sv.cg.exec) { (void)hipStreamSynchronize(c->stream); destroy_graph(sv.cg); }
+    for (int i = 0; s && i < sv.n_slots; i++) {
+        if (!sv.occupied[i] || sv.states[i].key_cache != s->key_cache) continue;
+        if (__atomic_load_n(sv.done + i, __ATOMIC_ACQUIRE)) { sv.occupied[i] = 0; continue; }
+        (void)hipStreamSynchronize(c->stream);
+        sv.live = false;
+    }
+    bool any = false;
+    for (auto& e : c->q8g) any = any || !s || !memcmp(&e.s, s, sizeof *s);
+    if (!any) return;
+    (void)hipStreamSynchronize(c->stream);
+    for (size_t i = 0; i < c->q8g.size();) {
+        auto& e = c->q8g[i];
+        if (s && memcmp(&e.s, s, sizeof *s)) { i++; continue; }
+        destroy_graph(e.cg);
+        c->q8g.erase(c->q8g.begin() + (long)i);
+    }
+}
+// q8_model.hip: a Q8 model (weights *freed) is about to go: the captured Q8 steps, and a chained batch over it is dead
+extern "C" void rama_internal_drop_q8_graphs(rama_ctx* c, const rama_q8_weights* freed) {
+    if (!c) return;
+    drop_q8_graphs(c, nullptr);
+    if (freed && c->q8c.n_seq > 0 && c->q8c.w.wq == freed->wq) c->q8c.live = false;
+    if (freed && c->q8s.n_slots > 0 && c->q8s.w.wq == freed->wq) c->q8s.live = false;
+}
+
+// the serving chain's allocations (rama_q8_serve_begin / _end, release_q8); the stream is idle
+static void serve_release(rama_ctx* c) {
+    auto& sv = c->q8s;
+    destroy_graph(sv.cg);
+    hipFree(sv.blob); hipFree(sv.stage);
+    if (sv.pinned) hipHostFree(sv.pinned);
+    if (sv.ring) hipHostFree(sv.ring);
+    if (sv.done) hipHostFree(sv.done);
+    sv = rama_ctx::Q8Serve();
+}
+// ... and the chained batch's
+static void q8_chain_release(rama_ctx* c) {
+    auto& qc = c->q8c;
+    destroy_graph(qc.cg);
+    hipFree(qc.toks); hipFree(qc.seqs); hipFree(qc.out); hipFree(qc.ends); hipFree(qc.rows); hipFree(qc.forced);
+    if (qc.ring) hipHostFree(qc.ring);
+    if (qc.done) hipHostFree(qc.done);
+    qc = rama_ctx::Q8Chain();
+}
+// rama_ctx_destroy: everything of the Q8 stack the context holds (the captured steps have gone with drop_q8_graphs)
+void release_q8(rama_ctx* c) {
+    q8_chain_release(c);
+    serve_release(c);
+    hipFree(c->q8_xq); hipFree(c->q8_xs); hipFree(c->q8b_blob);
+}
+
+// ---------------------------------------------------------------- Q8_0 models (q8.hpp, q8_model.hip)
+// The forward of a version-2 checkpoint: parity mode's exact norms, RoPE + cache append, attention, SiLU and residual adds,
+// with every matmul replaced by runq.c's quantized product (rama_hip.h).  Per layer: norm, quantize,
+// Wq|Wk|Wv, RoPE + cache rows, attention, quantize, Wo (+ residual), norm, quantize, W1|W3 (+ SiLU * gate), quantize, W2 (+ residual).
+
+static int launch_q8_quantize(rama_ctx* c, const float* x, int n, int gs, int8_t* q, float* s) {
+    const int groups = n / gs;
+    RAMA_LAUNCH(c, q8_quantize_kernel, dim3((groups + 3) / 4), dim3(256), 0, x, n, gs, q, s);
+    LAUNCHCHK();
+    return 0;
+}
+
+template <int EPI>
+static int launch_q8_matvec(rama_ctx* c, Q8MatParams& p) {
+    const int G = p.K / p.gs, nm = EPI == Q8EPI_SWIGLU ? 2 : p.nmat;
+    bool fast = q8_matvec_fast_ok(p.K, p.gs) && (size_t)kQ8Waves * 2 * G * sizeof(float) <= 64 * 1024 && aligned16(p.xq);
+    for (int m = 0; m < nm; m++) fast = fast && aligned16(p.w[m]);
+    if (fast) {
+        const int tasks = EPI == Q8EPI_SWIGLU ? p.rows : (p.nmat * p.rows + 1) / 2;
+        const size_t lds = (size_t)kQ8Waves * 2 * G * sizeof(float);
+        RAMA_LAUNCH(c, (q8_matvec_kernel<2, EPI>), dim3((tasks + kQ8Waves - 1) / kQ8Waves), dim3(kQ8Waves * 64), lds, p);
+    } else {
+        const int total = EPI == Q8EPI_SWIGLU ? p.rows : p.nmat * p.rows;
+        RAMA_LAUNCH(c, (q8_matvec_generic_kernel<EPI>), dim3((total + 255) / 256), dim3(256), 0, p);
+    }
+    LAUNCHCHK();
+    return 0;
+}
+
+int rama_q8_quantize(rama_ctx* c, const float* x, size_t n, int group_size, int8_t* q, float* s) {
+    RAMA_ENTER(c);
+    REQUIRE(c && x && q && s, RAMA_EINVAL, "q8_quantize: NULL argument");
+    REQUIRE(group_size > 0 && n > 0 && n % (size_t)group_size == 0 && n < ((size_t)1 << 31), RAMA_EINVAL, "q8_quantize: group_size must divide n");
+    if (set_device(c)) return 1;
+    RAMA_WRITES(c, s, n / group_size);
+    return launch_q8_quantize(c, x, (int)n, group_size, q, s);
+}
+
+int rama_q8_matmul(rama_ctx* c, float* o, const int8_t* wq, const float* ws, const int8_t* xq, const float* xs, size_t n, size_t d, int group_size) {
+    RAMA_ENTER(c);
+    REQUIRE(c && o && wq && ws && xq && xs, RAMA_EINVAL, "q8_matmul: NULL argument");
+    REQUIRE(group_size > 0 && n > 0 && d > 0 && n % (size_t)group_size == 0 && n < ((size_t)1 << 31) && d < ((size_t)1 << 31), RAMA_EINVAL,
+            "q8_matmul: group_size must divide n");
+    if (set_device(c)) return 1;
+    RAMA_WRITES(c, o, d);
+    Q8MatParams p{};
+    p.w[0] = wq; p.ws[0] = ws; p.o[0] = o; p.xq = xq; p.xs = xs; p.K = (int)n; p.rows = (int)d; p.gs = group_size; p.nmat = 1;
+    return launch_q8_matvec<Q8EPI_STORE>(c, p);
+}
+
+static bool q8_weights_complete(const rama_q8_weights* w) {
+    return w->token_embedding_table && w->rms_att_weight && w->rms_ffn_weight && w->rms_final_weight && w->freq_cis_real && w->freq_cis_imag &&
+           w->wq && w->wk && w->wv && w->wo && w->w1 && w->w2 && w->w3 && w->wcls && w->wq_s && w->wk_s && w->wv_s && w->wo_s && w->w1_s &&
+           w->w2_s && w->w3_s && w->wcls_s;
+}
+
+static int q8_check(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const rama_run_state* s) {
+    REQUIRE(c, RAMA_EINVAL, "ctx is NULL");
+    int rc = check_cfg(cfg); if (rc) return rc;
+    REQUIRE(w && s, RAMA_EINVAL, "q8 forward: NULL argument");
+    const int gs = w->group_size;
+    REQUIRE(gs > 0 && cfg->dim % gs == 0 && cfg->hidden_dim % gs == 0, RAMA_EINVAL, "q8 forward: group_size must divide dim and hidden_dim");
+    REQUIRE(q8_weights_complete(w), RAMA_EINVAL, "q8 forward: missing weights");
+    REQUIRE(s->x && s->xb && s->hb && s->q && s->k && s->v && s->att && s->logits && s->key_cache && s->value_cache, RAMA_EINVAL,
+            "q8 forward: missing state buffer");
+    return 0;
+}
+
+// the int8 activations: one buffer of max(dim, hidden) values and as many scales (sized here, never inside a capture)
+static int ensure_q8_scratch(rama_ctx* c, const rama_config* cfg) {
+    const size_t need = (size_t)std::max(cfg->dim, cfg->hidden_dim);
+    if (need <= c->q8_cap) return 0;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    REQUIRE(hipStreamIsCapturing(c->stream, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone, RAMA_EINVAL,
+            "q8: the activation scratch is sized by the first call, which must not be captured");
+    HIPCHK(hipStreamSynchronize(c->stream));
+    drop_q8_graphs(c, nullptr);        // (they hold the scratch's addresses; nothing else reads it)
+    if (c->q8_xq) { HIPCHK(hipFree(c->q8_xq)); c->q8_xq = nullptr; }
+    if (c->q8_xs) { HIPCHK(hipFree(c->q8_xs)); c->q8_xs = nullptr; }
+    c->q8_cap = 0;
+    HIPCHK(hipMalloc(&c->q8_xq, (need + 15) / 16 * 16));
+    HIPCHK(hipMalloc(&c->q8_xs, need * sizeof(float)));
+    c->q8_cap = need;
+    return 0;
+}
+
+// the attention variant of a Q8 step: parity mode's exact attention, 16 waves per head from position 256, spread over the chip from "spread_pos"
+static int q8_variant(rama_ctx* c, int pos) {
+    c->long_attn = pos >= kLongAttnPos;
+    c->spread_attn = pos >= c->tune_spread_pos;
+    return c->spread_attn ? 2 : (c->long_attn ? 1 : 0);
+}
+
+static int q8_norm(rama_ctx* c, float* o, float* x, const float* gain, int n, float* copy_to) {
+    KTimer kt(c, RAMA_K_NORM);
+    if (rmsnorm_chain_ok(n)) return launch_rmsnorm_chain(c, o, x, gain, n, copy_to);
+    if (copy_to) {      // xb = x; x = rmsnorm(xb) (infer.rs:49-50)
+        hipLaunchKernelGGL(copy_kernel, dim3(ew_grid(n)), dim3(256), 0, c->stream, copy_to, (const float*)x, (size_t)n);
+        LAUNCHCHK();
+        return launch_rmsnorm_ref(c, o, copy_to, gain, n);
+    }
+    return launch_rmsnorm_ref(c, o, x, gain, n);
+}
+
+// one forward (token and position in the device cursor); embed = 0: x already holds the token's embedding (chained decode)
+static int enqueue_q8_stage(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, rama_run_state* s, bool embed) {
+    const int dim = cfg->dim, hidden = cfg->hidden_dim, hs = dim / cfg->n_heads, gs = w->group_size;
+    const size_t dd = (size_t)dim * dim, hd = (size_t)hidden * dim;
+    int8_t* xq = c->q8_xq; float* xs = c->q8_xs;
+    int rc;
+    if (embed) {
+        hipLaunchKernelGGL(embed_kernel, dim3((dim + 255) / 256), dim3(256), 0, c->stream, s->x, w->token_embedding_table, (const Ctl*)c->ctl, 0, dim);
+        LAUNCHCHK();
+    }
+    for (int l = 0; l < cfg->n_layers; l++) {
+        float* kc = s->key_cache + (size_t)l * cfg->seq_len * dim;
+        float* vc = s->value_cache + (size_t)l * cfg->seq_len * dim;
+        rc = q8_norm(c, s->xb, s->x, w->rms_att_weight + (size_t)l * dim, dim, nullptr); if (rc) return rc;          // infer.rs:19
+        rc = launch_q8_quantize(c, s->xb, dim, gs, xq, xs); if (rc) return rc;
+        {   // :20-23
+            KTimer kt(c, RAMA_K_QKV);
+            Q8MatParams p{};
+            p.w[0] = w->wq + l * dd; p.w[1] = w->wk + l * dd; p.w[2] = w->wv + l * dd;
+            p.ws[0] = w->wq_s + l * dd / gs; p.ws[1] = w->wk_s + l * dd / gs; p.ws[2] = w->wv_s + l * dd / gs;
+            p.o[0] = s->q; p.o[1] = s->k; p.o[2] = s->v;
+            p.xq = xq; p.xs = xs; p.K = dim; p.rows = dim; p.gs = gs; p.nmat = 3;
+            rc = launch_q8_matvec<Q8EPI_STORE>(c, p); if (rc) return rc;
+        }
+        hipLaunchKernelGGL(rope_ref_cursor_kernel, dim3((dim / 2 + 255) / 256), dim3(256), 0, c->stream, s->q, s->k, (const float*)s->v,
+                           w->freq_cis_real, w->freq_cis_imag, dim, hs, kc, vc, (const Ctl*)c->ctl);                  // :25-33
+        LAUNCHCHK();
+        {   // :34
+            KTimer kt(c, RAMA_K_ATTN);
+            if (attn_chain_ok(hs, cfg->seq_len))
+                rc = launch_attention_chain(c, s->xb, s->att, s->q, kc, vc, c->ctl, 0, dim, hs, cfg->seq_len, cfg->n_heads, c->long_attn, c->spread_attn);
+            else rc = launch_attention_ref(c, s->xb, s->att, s->q, kc, vc, c->ctl, 0, dim, hs, cfg->seq_len, cfg->n_heads);
+            if (rc) return rc;
+        }
+        rc = launch_q8_quantize(c, s->xb, dim, gs, xq, xs); if (rc) return rc;
+        {   // :35-37: x = x + Wo . xb
+            KTimer kt(c, RAMA_K_WO);
+            Q8MatParams p{};
+            p.w[0] = w->wo + l * dd; p.ws[0] = w->wo_s + l * dd / gs; p.o[0] = s->x;
+            p.xq = xq; p.xs = xs; p.K = dim; p.rows = dim; p.gs = gs; p.nmat = 1;
+            rc = launch_q8_matvec<Q8EPI_RESID>(c, p); if (rc) return rc;
+        }
+        rc = q8_norm(c, s->xb, s->x, w->rms_ffn_weight + (size_t)l * dim, dim, nullptr); if (rc) return rc;          // :39
+        rc = launch_q8_quantize(c, s->xb, dim, gs, xq, xs); if (rc) return rc;
+        {   // :41-45: hb = sinu(W1 . xb) * (W3 . xb)
+            KTimer kt(c, RAMA_K_W13);
+            Q8MatParams p{};
+            p.w[0] = w->w1 + l * hd; p.w[1] = w->w3 + l * hd; p.ws[0] = w->w1_s + l * hd / gs; p.ws[1] = w->w3_s + l * hd / gs;
+            p.o[0] = s->hb; p.xq = xq; p.xs = xs; p.K = dim; p.rows = hidden; p.gs = gs; p.nmat = 2;
+            rc = launch_q8_matvec<Q8EPI_SWIGLU>(c, p); if (rc) return rc;
+        }
+        rc = launch_q8_quantize(c, s->hb, hidden, gs, xq, xs); if (rc) return rc;
+        {   // :46-47: x = x + W2 . hb
+            KTimer kt(c, RAMA_K_W2);
+            Q8MatParams p{};
+            p.w[0] = w->w2 + l * hd; p.ws[0] = w->w2_s + l * hd / gs; p.o[0] = s->x;
+            p.xq = xq; p.xs = xs; p.K = hidden; p.rows = dim; p.gs = gs; p.nmat = 1;
+            rc = launch_q8_matvec<Q8EPI_RESID>(c, p); if (rc) return rc;
+        }
+    }
+    // :49-51: xb = x; x = rmsnorm(xb); logits = Wcls . x
+    rc = q8_norm(c, s->x, s->x, w->rms_final_weight, dim, s->xb); if (rc) return rc;
+    rc = launch_q8_quantize(c, s->x, dim, gs, xq, xs); if (rc) return rc;
+    KTimer kt(c, RAMA_K_CLS);
+    Q8MatParams p{};
+    p.w[0] = w->wcls; p.ws[0] = w->wcls_s; p.o[0] = s->logits;
+    p.xq = xq; p.xs = xs; p.K = dim; p.rows = cfg->vocab_size; p.gs = gs; p.nmat = 1;
+    return launch_q8_matvec<Q8EPI_STORE>(c, p);
+}
+
+// a chained step: the layers, then Device::sample (cursor advance, next token's embedding gather from the fp32 table)
+static int enqueue_q8_step(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, rama_run_state* s) {
+    int rc = enqueue_q8_stage(c, cfg, w, s, false);
+    if (rc) return rc;
+    ArgmaxParams ap{};
+    ap.logits = s->logits; ap.n = cfg->vocab_size;
+    ap.ctl = c->ctl; ap.forced = c->forced; ap.out = c->out; ap.out_cap = c->out_cap; ap.ring = c->ring_dev;
+    ap.emb = w->token_embedding_table; ap.x = s->x; ap.dim = cfg->dim;
+    return enqueue_sample(c, ap, c->samp_T, c->samp_topp, c->samp_u);
+}
+
+// eager, or replayed from the context's Q8 graph for (config, weights, state, attention variant, kind)
+static int run_q8(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, rama_run_state* s, int variant, int chained) {
+    auto enqueue = [&]() { return chained ? enqueue_q8_step(c, cfg, w, s) : enqueue_q8_stage(c, cfg, w, s, true); };
+    if (!c->graph_mode || c->kp.kernel_id >= 0) return enqueue();
+    rama_ctx::Q8Graph* hit = nullptr;
+    for (auto& e : c->q8g)
+        if (e.variant == variant && e.chained == chained && !memcmp(&e.cfg, cfg, sizeof *cfg) && !memcmp(&e.w, w, sizeof *w) && !memcmp(&e.s, s, sizeof *s)) { hit = &e; break; }
+    if (!hit) {
+        if (c->q8g.size() >= 16) {
+            HIPCHK(hipStreamSynchronize(c->stream));
+            for (auto& e : c->q8g) destroy_graph(e.cg);
+            c->q8g.clear();
+        }
+        rama_ctx::Q8Graph e;
+        const int rc = capture_graph(c, e.cg, enqueue);
+        if (rc) return rc;
+        e.cfg = *cfg; e.w = *w; e.s = *s; e.variant = variant; e.chained = chained;
+        c->q8g.push_back(e);
+        hit = &c->q8g.back();
+    }
+    return replay_graph(c, hit->cg);
+}
+
+int rama_q8_forward(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, rama_run_state* s, int token, int pos) {
+    RAMA_ENTER(c);
+    int rc = q8_check(c, cfg, w, s); if (rc) return rc;
+    if (set_device(c)) return 1;
+    REQUIRE(pos >= 0 && pos < cfg->seq_len, RAMA_EINVAL, "q8_forward: pos outside [0, seq_len)");
+    REQUIRE(token >= 0 && token < cfg->vocab_size, RAMA_EINVAL, "q8_forward: token outside the vocabulary");
+    rc = ensure_q8_scratch(c, cfg); if (rc) return rc;
+    hipLaunchKernelGGL(set_ctl_kernel, dim3(1), dim3(1), 0, c->stream, c->ctl, token, pos, 0, 0);
+    LAUNCHCHK();
+    c->embedded_x = nullptr;
+    c->host_pos = -1;
+    return run_q8(c, cfg, w, s, q8_variant(c, pos), 0);
+}
+
+int rama_q8_generate(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, rama_run_state* s, const int32_t* prompt_host, int n_prompt,
+                     int steps, float temperature, float topp, float u, int32_t* out_host) {
+    RAMA_ENTER(c);
+    int rc = q8_check(c, cfg, w, s); if (rc) return rc;
+    REQUIRE(out_host, RAMA_EINVAL, "q8_generate: NULL argument");
+    if (set_device(c)) return 1;
+    rc = rama_decode_sampler(c, temperature, topp, u); if (rc) return rc;
+    REQUIRE(steps >= 0 && steps <= cfg->seq_len && steps <= c->out_cap, RAMA_EINVAL, "q8_generate: steps outside [0, seq_len]");
+    REQUIRE(n_prompt >= 0 && (n_prompt == 0 || prompt_host) && n_prompt <= c->forced_cap, RAMA_EINVAL, "q8_generate: bad prompt");
+    for (int i = 0; i < n_prompt; i++) REQUIRE(prompt_host[i] >= 0 && prompt_host[i] < cfg->vocab_size, RAMA_EINVAL, "q8_generate: prompt token outside the vocabulary");
+    rc = ensure_q8_scratch(c, cfg); if (rc) return rc;
+    if (c->samp_T != 0.0f) { rc = ensure_topp_scratch(c, cfg->vocab_size); if (rc) return rc; c->topp_dist_dirty = true; }
+    rc = rama_decode_begin(c, /*BOS*/ 1, 0, prompt_host, n_prompt); if (rc) return rc;
+    if (steps == 0) { int n = 0; return rama_decode_tokens(c, out_host, 0, &n); }
+    hipLaunchKernelGGL(embed_kernel, dim3((cfg->dim + 255) / 256), dim3(256), 0, c->stream, s->x, w->token_embedding_table, (const Ctl*)c->ctl, 0, cfg->dim);
+    LAUNCHCHK();
+    for (int i = 0; i < steps; i++) {
+        rc = run_q8(c, cfg, w, s, q8_variant(c, c->host_pos), 1);
+        if (rc) return rc;
+        c->host_pos++;
+    }
+    c->embedded_x = nullptr;
+    c->ring_hi = std::min(c->out_cap, c->ring_hi + steps);
+    int n = 0;
+    return rama_decode_tokens(c, out_host, steps, &n);
+}
+
+// ---------------------------------------------------------------- Q8_0 token batches (q8_batch.hpp)
+// rama_q8_prefill and rama_q8_decode_batch: enqueue_q8_stage over up to kQ8bMaxTok tokens per weight pass.  The batched exact
+// norm, the quantizer over T rows (a group never straddles a row), the batched product, RoPE + cache rows per token and parity
+// mode's attention on a (heads, tokens) grid: every token's bits are those of its own rama_q8_forward.
+
+template <int EPI>
+static int launch_q8_gemm(rama_ctx* c, const Q8BatchParams& p) {
+    const int nm = EPI == Q8EPI_SWIGLU ? 2 : p.nmat;
+    bool mf = q8_gemm_mfma_ok(p.K, p.gs) && aligned16(p.xq);
+    for (int m = 0; m < nm; m++) mf = mf && aligned16(p.w[m]);
+    const int G = p.K / p.gs;
+    const int total = EPI == Q8EPI_SWIGLU ? p.rows : p.nmat * p.rows;
+    const int tiles = (p.rows + 15) / 16, tasks = EPI == Q8EPI_SWIGLU ? tiles : p.nmat * tiles;
+    for (int t0 = 0; t0 < p.n_tok; t0 += kQ8bMaxTok) {
+        Q8BatchParams q = p;
+        q.n_tok = std::min(kQ8bMaxTok, p.n_tok - t0);
+        q.xq = p.xq + (size_t)t0 * p.K; q.xs = p.xs + (size_t)t0 * G;
+        for (int m = 0; m < 3; m++) if (q.o[m]) q.o[m] = p.o[m] + (size_t)t0 * p.ostride;
+        if (mf && q.n_tok <= 32 && (q.gs == 32 || q.gs == 64)) {      // few tokens: K split over the waves of a workgroup
+            constexpr int RT = EPI == Q8EPI_SWIGLU ? 2 : 1;
+#define RAMA_Q8S(NT_, G32_) RAMA_LAUNCH(c, (q8_gemm_ksplit_kernel<NT_, EPI, G32_>), dim3(tasks), dim3(kQ8sWaves * 64), q8s_lds_bytes(NT_, RT, G32_), q)
+            if (q.n_tok <= 16) { if (q.gs == 32) RAMA_Q8S(1, true); else RAMA_Q8S(1, false); }
+            else { if (q.gs == 32) RAMA_Q8S(2, true); else RAMA_Q8S(2, false); }
+#undef RAMA_Q8S
+        } else if (mf) {
+            const dim3 grid((tasks + kQ8bWaves - 1) / kQ8bWaves), block(kQ8bWaves * 64);
+#define RAMA_Q8G(NT_) do { if (q.gs == 32) RAMA_LAUNCH(c, (q8_gemm_mfma_kernel<NT_, EPI, true>), grid, block, 0, q); \
+                           else RAMA_LAUNCH(c, (q8_gemm_mfma_kernel<NT_, EPI, false>), grid, block, 0, q); } while (0)
+            if (q.n_tok <= 16) RAMA_Q8G(1);
+            else if (q.n_tok <= 32) RAMA_Q8G(2);
+            else if (q.n_tok <= 64) RAMA_Q8G(4);
+            else RAMA_Q8G(8);
+#undef RAMA_Q8G
+        } else {
+            RAMA_LAUNCH(c, (q8_gemm_generic_kernel<EPI>), dim3((total + 255) / 256, q.n_tok), dim3(256), 0, q);
+        }
+        LAUNCHCHK();
+    }
+    return 0;
+}
+
+int rama_q8_matmul_batch(rama_ctx* c, float* o, const int8_t* wq, const float* ws, const int8_t* xq, const float* xs, size_t n, size_t d,
+                         int group_size, int n_tok) {
+    RAMA_ENTER(c);
+    REQUIRE(c && o && wq && ws && xq && xs, RAMA_EINVAL, "q8_matmul_batch: NULL argument");
+    REQUIRE(group_size > 0 && n > 0 && d > 0 && n % (size_t)group_size == 0 && n < ((size_t)1 << 31) && d < ((size_t)1 << 31), RAMA_EINVAL,
+            "q8_matmul_batch: group_size must divide n");
+    REQUIRE(n_tok >= 1, RAMA_EINVAL, "q8_matmul_batch: n_tok < 1");
+    if (set_device(c)) return 1;
+    RAMA_WRITES(c, o, d * (size_t)n_tok);
+    Q8BatchParams p{};
+    p.w[0] = wq; p.ws[0] = ws; p.o[0] = o; p.xq = xq; p.xs = xs;
+    p.K = (int)n; p.rows = (int)d; p.gs = group_size; p.nmat = 1; p.n_tok = n_tok; p.ostride = (int)d;
+    return launch_q8_gemm<Q8EPI_STORE>(c, p);
+}
+
+// the batch path's scratch, row-major per token (T = kQ8bMaxTok): X residual rows, XN their norms, Q / Kr / V, XB attention
+// output, HB, ATT score rows [T][n_heads][seq_len], LG logits [T][vocab]; the int8 activations [T][max(dim, hidden)] and their
+// scales; token ids; the sequence table
+struct Q8BatchScratch { float *X, *XN, *Q, *Kr, *V, *XB, *HB, *ATT, *LG; int8_t* xq; float* xs; int* toks; SeqSlot* seqs; int nw; size_t att_lds; };
+
+// the shapes the batch path takes: those whose single-token forward runs parity mode's chain norm and chain attention
+static bool q8_batch_ok(const rama_config* cfg) {
+    const int hs = cfg->dim / cfg->n_heads;
+    if (!rmsnorm_chain_ok((size_t)cfg->dim) || !attn_chain_ok(hs, cfg->seq_len) || cfg->dim % 4) return false;
+    return attn_chain_lds_bytes(hs, cfg->seq_len, attn_chain_waves(hs, false)) <= kAttnChainMaxLds;
+}
+
+static int ensure_q8_batch_scratch(rama_ctx* c, const rama_config* cfg, int gs, Q8BatchScratch* b) {
+    const size_t T = kQ8bMaxTok, dim = (size_t)cfg->dim, hidden = (size_t)cfg->hidden_dim, mx = std::max(dim, hidden);
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    const size_t sz[13] = {T * dim * 4, T * dim * 4, T * dim * 4, T * dim * 4, T * dim * 4, T * dim * 4, T * hidden * 4,
+                           T * (size_t)cfg->n_heads * cfg->seq_len * 4, T * (size_t)cfg->vocab_size * 4, T * mx, T * (mx / gs) * 4, T * sizeof(int),
+                           T * sizeof(SeqSlot)};
+    size_t off[13], need = 0;
+    for (int i = 0; i < 13; i++) { off[i] = need; need += up(sz[i]); }
+    if (need > c->q8b_cap) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        REQUIRE(hipStreamIsCapturing(c->stream, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone, RAMA_EINVAL,
+                "q8 batch: the scratch is sized by the first call, which must not be captured");
+        HIPCHK(hipStreamSynchronize(c->stream));
+        destroy_graph(c->q8c.cg);          // (the chained batch's step holds the old scratch's addresses)
+        destroy_graph(c->q8s.cg);          // (and the serving chain's)
+        if (c->q8b_blob) { HIPCHK(hipFree(c->q8b_blob)); c->q8b_blob = nullptr; }
+        c->q8b_cap = 0;
+        HIPCHK(hipMalloc(&c->q8b_blob, need));
+        c->q8b_cap = need;
+    }
+    char* base = c->q8b_blob;
+    float** f[9] = {&b->X, &b->XN, &b->Q, &b->Kr, &b->V, &b->XB, &b->HB, &b->ATT, &b->LG};
+    for (int i = 0; i < 9; i++) *f[i] = reinterpret_cast<float*>(base + off[i]);
+    b->xq = reinterpret_cast<int8_t*>(base + off[9]);
+    b->xs = reinterpret_cast<float*>(base + off[10]);
+    b->toks = reinterpret_cast<int*>(base + off[11]);
+    b->seqs = reinterpret_cast<SeqSlot*>(base + off[12]);
+    const int hs = cfg->dim / cfg->n_heads;
+    b->nw = attn_chain_waves(hs, false);
+    b->att_lds = attn_chain_lds_bytes(hs, cfg->seq_len, b->nw);
+    return 0;
+}
+
+// the layers for nt tokens whose embeddings sit in b.X: consecutive positions p0.. of one sequence (key_cache / value_cache
+// its caches), or -- seqs != NULL -- token t of independent sequence t (device table)
+static int q8_batch_layers(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const Q8BatchScratch& b, int nt, int p0,
+                           float* key_cache, float* value_cache, const SeqSlot* seqs) {
+    const int dim = cfg->dim, hidden = cfg->hidden_dim, hs = dim / cfg->n_heads, H = cfg->n_heads, seq = cfg->seq_len, gs = w->group_size;
+    const size_t dd = (size_t)dim * dim, hd = (size_t)hidden * dim;
+    int rc;
+    for (int l = 0; l < cfg->n_layers; l++) {
+        const size_t layer_off = (size_t)l * seq * dim;
+        float* kc = key_cache ? key_cache + layer_off : nullptr;
+        float* vc = value_cache ? value_cache + layer_off : nullptr;
+        rc = launch_rmsnorm_chain(c, b.XN, b.X, w->rms_att_weight + (size_t)l * dim, dim, nullptr, nt, dim); if (rc) return rc;    // infer.rs:19
+        rc = launch_q8_quantize(c, b.XN, nt * dim, gs, b.xq, b.xs); if (rc) return rc;
+        {   // :20-23
+            Q8BatchParams p{};
+            p.w[0] = w->wq + l * dd; p.w[1] = w->wk + l * dd; p.w[2] = w->wv + l * dd;
+            p.ws[0] = w->wq_s + l * dd / gs; p.ws[1] = w->wk_s + l * dd / gs; p.ws[2] = w->wv_s + l * dd / gs;
+            p.o[0] = b.Q; p.o[1] = b.Kr; p.o[2] = b.V;
+            p.xq = b.xq; p.xs = b.xs; p.K = dim; p.rows = dim; p.gs = gs; p.nmat = 3; p.n_tok = nt; p.ostride = dim;
+            rc = launch_q8_gemm<Q8EPI_STORE>(c, p); if (rc) return rc;
+        }
+        hipLaunchKernelGGL(q8_rope_batch_kernel, dim3((dim / 2 + 255) / 256, nt), dim3(256), 0, c->stream, b.Q, b.Kr, (const float*)b.V,
+                           w->freq_cis_real, w->freq_cis_imag, dim, hs, kc, vc, p0, seqs, layer_off);                    // :25-33
+        LAUNCHCHK();
+        {   // :34, one workgroup per (head, token)
+            RefAttnParams a{};
+            a.q = b.Q; a.kc = kc; a.vc = vc; a.att = b.ATT; a.xb = b.XB; a.ctl = nullptr; a.pos_val = p0;
+            a.dim = dim; a.head_size = hs; a.seq_len = seq; a.tok_stride = dim; a.att_stride = H * seq;
+            a.seqs = seqs; a.layer_off = layer_off;
+            rc = launch_attention_chain_tokens(c, a, H, nt, b.nw, b.att_lds); if (rc) return rc;
+        }
+        rc = launch_q8_quantize(c, b.XB, nt * dim, gs, b.xq, b.xs); if (rc) return rc;
+        {   // :35-37: x = x + Wo . xb
+            Q8BatchParams p{};
+            p.w[0] = w->wo + l * dd; p.ws[0] = w->wo_s + l * dd / gs; p.o[0] = b.X;
+            p.xq = b.xq; p.xs = b.xs; p.K = dim; p.rows = dim; p.gs = gs; p.nmat = 1; p.n_tok = nt; p.ostride = dim;
+            rc = launch_q8_gemm<Q8EPI_RESID>(c, p); if (rc) return rc;
+        }
+        rc = launch_rmsnorm_chain(c, b.XN, b.X, w->rms_ffn_weight + (size_t)l * dim, dim, nullptr, nt, dim); if (rc) return rc;    // :39
+        rc = launch_q8_quantize(c, b.XN, nt * dim, gs, b.xq, b.xs); if (rc) return rc;
+        {   // :41-45: hb = sinu(W1 . xb) * (W3 . xb)
+            Q8BatchParams p{};
+            p.w[0] = w->w1 + l * hd; p.w[1] = w->w3 + l * hd; p.ws[0] = w->w1_s + l * hd / gs; p.ws[1] = w->w3_s + l * hd / gs;
+            p.o[0] = b.HB; p.xq = b.xq; p.xs = b.xs; p.K = dim; p.rows = hidden; p.gs = gs; p.nmat = 2; p.n_tok = nt; p.ostride = hidden;
+            rc = launch_q8_gemm<Q8EPI_SWIGLU>(c, p); if (rc) return rc;
+        }
+        rc = launch_q8_quantize(c, b.HB, nt * hidden, gs, b.xq, b.xs); if (rc) return rc;
+        {   // :46-47: x = x + W2 . hb
+            Q8BatchParams p{};
+            p.w[0] = w->w2 + l * hd; p.ws[0] = w->w2_s + l * hd / gs; p.o[0] = b.X;
+            p.xq = b.xq; p.xs = b.xs; p.K = hidden; p.rows = dim; p.gs = gs; p.nmat = 1; p.n_tok = nt; p.ostride = dim;
+            rc = launch_q8_gemm<Q8EPI_RESID>(c, p); if (rc) return rc;
+        }
+    }
+    return 0;
+}
+
+int rama_q8_prefill(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, rama_run_state* s, const int32_t* tokens_host, int n_tokens, int pos0) {
+    RAMA_ENTER(c);
+    REQUIRE(c && tokens_host, RAMA_EINVAL, "q8_prefill: NULL argument");
+    int rc = q8_check(c, cfg, w, s); if (rc) return rc;
+    REQUIRE(n_tokens >= 1 && pos0 >= 0 && pos0 <= cfg->seq_len - n_tokens, RAMA_EINVAL, "q8_prefill: positions outside [0, seq_len)");
+    for (int i = 0; i < n_tokens; i++) REQUIRE(tokens_host[i] >= 0 && tokens_host[i] < cfg->vocab_size, RAMA_EINVAL, "q8_prefill: token outside the vocabulary");
+    if (set_device(c)) return 1;
+    rc = ensure_q8_scratch(c, cfg); if (rc) return rc;
+    // the last position runs as rama_q8_forward (x and logits); a batched pass of one token costs more than a forward (4.7 against
+    // 3.8 ms at llama2-7B), so batches start at two tokens
+    const int n_batch = q8_batch_ok(cfg) && n_tokens >= 3 ? n_tokens - 1 : 0;
+    if (n_batch > 0) {
+        Q8BatchScratch b{};
+        rc = ensure_q8_batch_scratch(c, cfg, w->group_size, &b); if (rc) return rc;
+        c->embedded_x = nullptr; c->host_pos = -1;
+        for (int c0 = 0; c0 < n_batch; c0 += kQ8bMaxTok) {
+            const int nt = std::min(kQ8bMaxTok, n_batch - c0);
+            rc = stage_tokens(c, b.toks, tokens_host + c0, nt); if (rc) return rc;
+            hipLaunchKernelGGL(embed_rows_kernel, dim3((cfg->dim + 255) / 256, nt), dim3(256), 0, c->stream, b.X, w->token_embedding_table,
+                               (const int*)b.toks, nt, cfg->dim);
+            LAUNCHCHK();
+            rc = q8_batch_layers(c, cfg, w, b, nt, pos0 + c0, s->key_cache, s->value_cache, nullptr); if (rc) return rc;
+        }
+    }
+    for (int i = n_batch; i < n_tokens; i++) { rc = rama_q8_forward(c, cfg, w, s, tokens_host[i], pos0 + i); if (rc) return rc; }
+    return 0;
+}
+
+// infer.rs:49-51 for n_rows rows of src_rows [n_rows, dim]: x = rmsnorm(x), logits = Wcls . x -- the batched final norm, the quantizer
+// and the classifier as one more product into b.LG [n_rows, vocab]
+static int enqueue_q8_classifier(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const Q8BatchScratch& b, const float* src_rows, int n_rows) {
+    const int dim = cfg->dim, V = cfg->vocab_size, gs = w->group_size;
+    int rc = launch_rmsnorm_chain(c, b.XN, src_rows, w->rms_final_weight, dim, nullptr, n_rows, dim); if (rc) return rc;
+    rc = launch_q8_quantize(c, b.XN, n_rows * dim, gs, b.xq, b.xs); if (rc) return rc;
+    Q8BatchParams p{};
+    p.w[0] = w->wcls; p.ws[0] = w->wcls_s; p.o[0] = b.LG;
+    p.xq = b.xq; p.xs = b.xs; p.K = dim; p.rows = V; p.gs = gs; p.nmat = 1; p.n_tok = n_rows; p.ostride = V;
+    return launch_q8_gemm<Q8EPI_STORE>(c, p);
+}
+
+// One pass for the n_seq sequences of the device tables toks / seqs: embedding rows, every layer, then the classifier tail
+static int enqueue_q8_batch_pass(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const Q8BatchScratch& b, const int* toks,
+                                 const SeqSlot* seqs, int n_seq) {
+    const int dim = cfg->dim;
+    hipLaunchKernelGGL(embed_rows_kernel, dim3((dim + 255) / 256, n_seq), dim3(256), 0, c->stream, b.X, w->token_embedding_table, toks, n_seq, dim);
+    LAUNCHCHK();
+    const int rc = q8_batch_layers(c, cfg, w, b, n_seq, 0, nullptr, nullptr, seqs); if (rc) return rc;
+    return enqueue_q8_classifier(c, cfg, w, b, b.X, n_seq);
+}
+
+int rama_q8_decode_batch(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const rama_run_state* states,
+                         const int32_t* tokens_host, const int32_t* positions_host, int n_seq) {
+    RAMA_ENTER(c);
+    REQUIRE(c && states && tokens_host && positions_host, RAMA_EINVAL, "q8_decode_batch: NULL argument");
+    REQUIRE(n_seq >= 1 && n_seq <= kQ8bMaxTok, RAMA_EINVAL, "q8_decode_batch: 1..128 sequences per call");
+    for (int i = 0; i < n_seq; i++) {
+        int rc = q8_check(c, cfg, w, &states[i]); if (rc) return rc;
+        REQUIRE(tokens_host[i] >= 0 && tokens_host[i] < cfg->vocab_size, RAMA_EINVAL, "q8_decode_batch: token outside the vocabulary");
+        REQUIRE(positions_host[i] >= 0 && positions_host[i] < cfg->seq_len, RAMA_EINVAL, "q8_decode_batch: position outside [0, seq_len)");
+        for (int j = 0; j < i; j++)
+            REQUIRE(states[j].key_cache != states[i].key_cache && states[j].value_cache != states[i].value_cache && states[j].logits != states[i].logits,
+                    RAMA_EINVAL, "q8_decode_batch: two sequences share a run state");
+    }
+    if (set_device(c)) return 1;
+    int rc = ensure_q8_scratch(c, cfg); if (rc) return rc;
+    if (!q8_batch_ok(cfg) || n_seq == 1) {      // see rama_q8_prefill: one rama_q8_forward per sequence (and for a single one)
+        for (int i = 0; i < n_seq; i++) {
+            rama_run_state si = states[i];
+            rc = rama_q8_forward(c, cfg, w, &si, tokens_host[i], positions_host[i]); if (rc) return rc;
+        }
+        return 0;
+    }
+    Q8BatchScratch b{};
+    rc = ensure_q8_batch_scratch(c, cfg, w->group_size, &b); if (rc) return rc;
+    c->embedded_x = nullptr; c->host_pos = -1;
+    rc = stage_tokens(c, b.toks, tokens_host, n_seq, b.seqs, states, positions_host); if (rc) return rc;
+    rc = enqueue_q8_batch_pass(c, cfg, w, b, b.toks, b.seqs, n_seq); if (rc) return rc;
+    return copy_out_logits(c, states, b.LG, n_seq, cfg->vocab_size);
+}
+
+// ---- the same pass CHAINED ON THE DEVICE (the Q8 counterpart of rama_decode_batch_begin / _steps): every sequence's (token, position)
+// lives in device memory, a step ends with argmax_batch_kernel or the batched top-p sampler, and -- new here -- a sequence ENDS on its
+// own: after `max_new` tokens or on a sampled stop token (kernels.hpp batch_seq_advance).  A finished slot repeats its last forward,
+// which rewrites one cache row with the same bits, so the pass needs no mask and one captured graph serves the whole chain: nothing in
+// the pass's launch geometry depends on the positions (score rows and attention LDS are sized by seq_len).
+
+// a sequence's budget: its own max_new (0: none) within the chain's max_steps
+static int q8_chain_limit(const rama_q8_seq_plan* per_seq, int i, int max_steps) {
+    return per_seq && per_seq[i].max_new > 0 ? std::min(per_seq[i].max_new, max_steps) : max_steps;
+}
+
+int rama_q8_decode_batch_begin(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const rama_run_state* states,
+                               const int32_t* tokens_host, const int32_t* positions_host, int n_seq, int max_steps,
+                               const rama_q8_seq_plan* per_seq) {
+    RAMA_ENTER(c);
+    // everything is checked before anything of a running chain is touched
+    REQUIRE(c && states && tokens_host && positions_host, RAMA_EINVAL, "q8_decode_batch_begin: NULL argument");
+    REQUIRE(n_seq >= 1 && n_seq <= kQ8bMaxTok, RAMA_EINVAL, "q8_decode_batch_begin: 1..128 sequences");
+    REQUIRE(max_steps >= 1 && max_steps <= (1 << 20), RAMA_EINVAL, "q8_decode_batch_begin: bad max_steps");
+    bool sampled = false;
+    size_t n_forced_all = 0;
+    int cap = 1;
+    for (int i = 0; i < n_seq; i++) {
+        int rc = q8_check(c, cfg, w, &states[i]); if (rc) return rc;
+        REQUIRE(tokens_host[i] >= 0 && tokens_host[i] < cfg->vocab_size, RAMA_EINVAL, "q8_decode_batch_begin: token outside the vocabulary");
+        for (int j = 0; j < i; j++)
+            REQUIRE(states[j].key_cache != states[i].key_cache && states[j].value_cache != states[i].value_cache, RAMA_EINVAL,
+                    "q8_decode_batch_begin: two sequences share a run state");
+        if (per_seq) {
+            const rama_q8_seq_plan& q = per_seq[i];
+            REQUIRE(topp_params_ok(q.temperature, q.topp, q.u), RAMA_EINVAL, "q8_decode_batch_begin: temperature >= 0, topp in [0,1], u in [0,1)");
+            REQUIRE(q.n_forced >= 0 && (q.n_forced == 0 || q.forced), RAMA_EINVAL, "q8_decode_batch_begin: bad forced list");
+            for (int k = 0; k < q.n_forced; k++)
+                REQUIRE(q.forced[k] >= 0 && q.forced[k] < cfg->vocab_size, RAMA_EINVAL, "q8_decode_batch_begin: forced token outside the vocabulary");
+            REQUIRE(q.max_new >= 0, RAMA_EINVAL, "q8_decode_batch_begin: max_new < 0");
+            REQUIRE(q.stop_token >= -1 && q.stop_token < cfg->vocab_size, RAMA_EINVAL, "q8_decode_batch_begin: stop token outside the vocabulary");
+            sampled = sampled || q.temperature != 0.0f || q.n_forced > 0;
+            n_forced_all += (size_t)q.n_forced;
+        }
+        const int limit = q8_chain_limit(per_seq, i, max_steps);
+        REQUIRE(positions_host[i] >= 0 && positions_host[i] <= cfg->seq_len - limit, RAMA_EINVAL,
+                "q8_decode_batch_begin: position + step budget beyond seq_len");
+        cap = std::max(cap, limit);
+    }
+    REQUIRE(q8_batch_ok(cfg), RAMA_EUNSUP, "q8_decode_batch_begin: a shape the Q8 token-batch pass does not take");
+    // argmax_batch_kernel reads 16-byte pieces of the logits rows: other vocabulary sizes end their steps in the sampler's launch
+    const bool use_sampler = sampled || cfg->vocab_size % 4 != 0;
+    REQUIRE(!use_sampler || (cfg->vocab_size > 1 && cfg->vocab_size <= kToppBlock * kToppMaxBlocks), RAMA_EUNSUP,
+            sampled ? "q8_decode_batch_begin: a sampled plan needs vocab_size <= 32768" : "q8_decode_batch_begin: vocab_size % 4 != 0 needs vocab_size <= 32768");
+    if (set_device(c)) return 1;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    auto& qc = c->q8c;
+    destroy_graph(qc.cg);
+    qc.n_seq = 0; qc.live = false; qc.states.clear();
+    // both scratches, the sampler's slices and the chain's tables: sized here, outside any capture
+    int rc = ensure_q8_scratch(c, cfg); if (rc) return rc;
+    Q8BatchScratch b{};
+    rc = ensure_q8_batch_scratch(c, cfg, w->group_size, &b); if (rc) return rc;
+    if (use_sampler) { rc = ensure_topp_batch(c, n_seq, cfg->vocab_size); if (rc) return rc; }
+    if (!qc.toks) {
+        HIPCHK(hipMalloc(&qc.toks, sizeof(int) * kQ8bMaxTok)); HIPCHK(hipMalloc(&qc.seqs, sizeof(SeqSlot) * kQ8bMaxTok));
+        HIPCHK(hipMalloc(&qc.ends, sizeof(BatchEnds)));
+        HIPCHK(hipMalloc(&qc.rows, sizeof(ToppRow) * kQ8bMaxTok));
+        HIPCHK(hipHostMalloc(&qc.done, sizeof(int) * kQ8bMaxTok, hipHostMallocMapped));
+        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&qc.done_dev), qc.done, 0));
+    }
+    if (qc.out_cap < cap) {
+        hipFree(qc.out); qc.out = nullptr; qc.out_cap = 0;
+        if (qc.ring) { hipHostFree(qc.ring); qc.ring = nullptr; }
+        HIPCHK(hipMalloc(&qc.out, sizeof(int) * (size_t)kQ8bMaxTok * cap));
+        HIPCHK(hipHostMalloc(&qc.ring, sizeof(int) * (size_t)kQ8bMaxTok * cap, hipHostMallocMapped));
+        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&qc.ring_dev), qc.ring, 0));
+        qc.out_cap = cap;
+    }
+    memset(qc.ring, 0, sizeof(int) * (size_t)kQ8bMaxTok * qc.out_cap);      // (the stream was drained above: nothing is on its way)
+    memset(qc.done, 0, sizeof(int) * kQ8bMaxTok);
+    if (qc.forced_cap < n_forced_all) {
+        hipFree(qc.forced); qc.forced = nullptr; qc.forced_cap = 0;
+        HIPCHK(hipMalloc(&qc.forced, sizeof(int) * n_forced_all));
+        qc.forced_cap = n_forced_all;
+    }
+    rc = stage_tokens(c, qc.toks, tokens_host, n_seq, qc.seqs, states, positions_host); if (rc) return rc;
+    static_assert(kQ8bMaxTok <= 128, "BatchEnds holds 128 sequences");
+    BatchEnds ends{};
+    ends.done = qc.done_dev;
+    ToppRow rows[kQ8bMaxTok];
+    size_t at = 0;
+    for (int i = 0; i < n_seq; i++) {
+        ends.limit[i] = q8_chain_limit(per_seq, i, max_steps);
+        ends.stop[i] = per_seq ? per_seq[i].stop_token : -1;
+        rows[i] = ToppRow{0.0f, 0.9f, 0.0f, 0, nullptr};
+        if (!per_seq) continue;
+        const rama_q8_seq_plan& q = per_seq[i];
+        rows[i] = ToppRow{q.temperature, q.topp, q.u, q.n_forced, q.n_forced ? qc.forced + at : nullptr};
+        if (q.n_forced) HIPCHK(hipMemcpy(qc.forced + at, q.forced, sizeof(int) * q.n_forced, hipMemcpyHostToDevice));
+        at += (size_t)q.n_forced;
+    }
+    HIPCHK(hipMemcpy(qc.ends, &ends, sizeof ends, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(qc.rows, rows, sizeof(ToppRow) * n_seq, hipMemcpyHostToDevice));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    qc.sampled = use_sampler; qc.cfg = *cfg; qc.w = *w; qc.states.assign(states, states + n_seq);
+    qc.max_steps = max_steps; qc.steps_done = 0; qc.n_seq = n_seq; qc.live = true;
+    return 0;
+}
+
+// n_steps times `enqueue`: eager, or -- graph mode, no kernel class being timed -- captured into g on first use and replayed.  *n_done: the
+// steps enqueued, also when one fails; *captures (if given) counts the captures.
+template <class Enqueue>
+static int q8_run_steps(rama_ctx* c, CapturedGraph& g, int n_steps, Enqueue&& enqueue, int* n_done, unsigned long long* captures = nullptr) {
+    const bool graphs = c->graph_mode && c->kp.kernel_id < 0;
+    for (*n_done = 0; *n_done < n_steps; ++*n_done) {
+        if (!graphs) {
+            const int rc = enqueue(); if (rc) return rc;
+            continue;
+        }
+        if (!g.exec) {
+            const int rc = capture_graph(c, g, enqueue); if (rc) return rc;
+            if (captures) ++*captures;
+        }
+        const int rc = replay_graph(c, g); if (rc) return rc;
+    }
+    return 0;
+}
+
+// one step: the pass over the chain's own tables, then what ends it
+static int enqueue_q8_chain_step(rama_ctx* c, const Q8BatchScratch& b) {
+    auto& qc = c->q8c;
+    const int V = qc.cfg.vocab_size;
+    int rc = enqueue_q8_batch_pass(c, &qc.cfg, &qc.w, b, qc.toks, qc.seqs, qc.n_seq); if (rc) return rc;
+    if (!qc.sampled) {
+        BatchArgmaxParams ap{b.LG, V, qc.toks, qc.seqs, qc.out, qc.out_cap, qc.ring_dev, qc.ends};
+        hipLaunchKernelGGL(argmax_batch_kernel, dim3(qc.n_seq), dim3(1024), 0, c->stream, ap);
+        LAUNCHCHK();
+        return 0;
+    }
+    ToppBatchParams fin{};
+    fin.toks = qc.toks; fin.seqs = qc.seqs; fin.out = qc.out; fin.out_cap = qc.out_cap; fin.ring = qc.ring_dev;
+    fin.ends = qc.ends;
+    return enqueue_topp_batch(c, qc.rows, qc.n_seq, b.LG, (size_t)V, V, fin);
+}
+
+int rama_q8_decode_batch_steps(rama_ctx* c, int n_steps) {
+    RAMA_ENTER(c);
+    REQUIRE(c && c->q8c.n_seq > 0, RAMA_EINVAL, "q8_decode_batch_steps: call rama_q8_decode_batch_begin first");
+    auto& qc = c->q8c;
+    REQUIRE(qc.live, RAMA_EINVAL, "q8_decode_batch_steps: the chain's model or one of its run states has been freed");
+    REQUIRE(n_steps >= 0 && n_steps <= qc.max_steps - qc.steps_done, RAMA_EINVAL, "q8_decode_batch_steps: more steps than rama_q8_decode_batch_begin allowed for");
+    if (set_device(c)) return 1;
+    // (neither grows here: rama_q8_decode_batch_begin sized them, and whoever grew them since for another shape dropped the step's graph)
+    int rc = ensure_q8_scratch(c, &qc.cfg); if (rc) return rc;
+    Q8BatchScratch b{};
+    rc = ensure_q8_batch_scratch(c, &qc.cfg, qc.w.group_size, &b); if (rc) return rc;
+    if (qc.sampled) { rc = ensure_topp_batch(c, qc.n_seq, qc.cfg.vocab_size); if (rc) return rc; }
+    c->embedded_x = nullptr; c->host_pos = -1;
+    int n_done = 0;
+    rc = q8_run_steps(c, qc.cg, n_steps, [&] { return enqueue_q8_chain_step(c, b); }, &n_done);
+    qc.steps_done += n_done;
+    return rc;
+}
+
+int rama_q8_decode_batch_tokens(rama_ctx* c, int32_t* out_host, int max_per_seq, int32_t* n_per_seq) {
+    RAMA_ENTER(c);
+    REQUIRE(c && out_host && n_per_seq && c->q8c.n_seq > 0 && max_per_seq >= 0, RAMA_EINVAL, "q8_decode_batch_tokens: bad argument");
+    auto& qc = c->q8c;
+    if (set_device(c)) return 1;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    { const int rh = handoff_check(c); if (rh) return rh; }
+    SeqSlot slots[kQ8bMaxTok];
+    HIPCHK(hipMemcpy(slots, qc.seqs, sizeof(SeqSlot) * qc.n_seq, hipMemcpyDeviceToHost));
+    for (int s_ = 0; s_ < qc.n_seq; s_++) {
+        const int n = std::min(std::min(slots[s_].pad, qc.out_cap), max_per_seq);      // pad: the tokens the sequence has produced
+        if (n > 0) HIPCHK(hipMemcpy(out_host + (size_t)s_ * max_per_seq, qc.out + (size_t)s_ * qc.out_cap, sizeof(int) * n, hipMemcpyDeviceToHost));
+        n_per_seq[s_] = n;
+    }
+    return 0;
+}
+
+int rama_q8_decode_batch_stream_poll(rama_ctx* c, int seq, int from, int32_t* out_host, int max_tokens, int* n_ready, int* finished) {
+    RAMA_ENTER(c);
+    REQUIRE(c && n_ready && c->q8c.n_seq > 0 && c->q8c.ring && seq >= 0 && seq < c->q8c.n_seq && from >= 0 && max_tokens >= 0 && (max_tokens == 0 || out_host),
+            RAMA_EINVAL, "q8_decode_batch_stream_poll: bad argument");
+    const auto& qc = c->q8c;
+    // the finished word first: it is stored after the sequence's last ring word, so a set word means every token is there to be read
+    const int fin = __atomic_load_n(qc.done + seq, __ATOMIC_ACQUIRE);
+    *n_ready = read_ring(qc.ring + (size_t)seq * qc.out_cap, qc.out_cap, from, out_host, max_tokens);
+    if (finished) *finished = fin != 0;
+    return 0;
+}
+
+// ---- THE SERVING CHAIN (q8_serve.hpp): continuous batching.  n_slots slots share passes of max_rows rows; a scheduler
+// launch builds every step's row table from the slot table on the device, a pick launch runs the slots' state machine, and an admission
+// is a stream-ordered copy + launch between two steps.  Nothing in a step's launch geometry depends on a sequence, so one captured graph
+// serves the chain for its whole life.
+
+// the scheduling rule on the host: the rows every slot gets in the next step (serve_schedule_kernel computes the same numbers by scans)
+static void serve_plan_counts(const rama_q8_serve_slot* slots, int n_slots, int max_rows, int* nrows) {
+    int left = max_rows;
+    for (int i = 0; i < n_slots; i++) {
+        nrows[i] = slots[i].state == RAMA_SERVE_DECODE || slots[i].state == RAMA_SERVE_PROMPT ? 1 : 0;
+        left -= nrows[i];
+    }
+    for (int i = 0; i < n_slots && left > 0; i++) {
+        if (slots[i].state != RAMA_SERVE_PROMPT) continue;
+        const int extra = std::min(slots[i].n_context - slots[i].cursor - 1, left);
+        nrows[i] += extra;
+        left -= extra;
+    }
+}
+
+int rama_q8_serve_plan_step(const rama_q8_serve_slot* slots, int n_slots, int max_rows, rama_q8_serve_row* rows_out, rama_q8_serve_slot* slots_after) {
+    REQUIRE(slots && rows_out, RAMA_EINVAL, "q8_serve_plan_step: NULL argument");
+    REQUIRE(n_slots >= 1 && n_slots <= kServeMaxSlots && max_rows >= n_slots && max_rows <= kQ8bMaxTok, RAMA_EINVAL,
+            "q8_serve_plan_step: 1 <= n_slots <= max_rows <= 128");
+    for (int i = 0; i < n_slots; i++) {
+        const rama_q8_serve_slot& s = slots[i];
+        REQUIRE(s.state >= RAMA_SERVE_FREE && s.state <= RAMA_SERVE_DONE, RAMA_EINVAL, "q8_serve_plan_step: bad slot state");
+        if (s.state == RAMA_SERVE_PROMPT)
+            REQUIRE(s.n_context >= 1 && s.cursor >= 0 && s.cursor < s.n_context && s.max_new >= 1, RAMA_EINVAL, "q8_serve_plan_step: bad PROMPT slot");
+        if (s.state == RAMA_SERVE_DECODE)
+            REQUIRE(s.cursor >= 0 && s.n_out >= 1 && s.n_out < s.max_new, RAMA_EINVAL, "q8_serve_plan_step: bad DECODE slot");
+    }
+    int nrows[kServeMaxSlots];
+    serve_plan_counts(slots, n_slots, max_rows, nrows);
+    int r = 0;
+    for (int i = 0; i < n_slots; i++) {
+        const rama_q8_serve_slot& s = slots[i];
+        const bool lg = s.state == RAMA_SERVE_DECODE || (s.state == RAMA_SERVE_PROMPT && s.cursor + nrows[i] == s.n_context);
+        for (int k = 0; k < nrows[i]; k++) rows_out[r++] = rama_q8_serve_row{i, s.cursor + k, lg && k == nrows[i] - 1 ? 1 : 0};
+        if (!slots_after) continue;
+        rama_q8_serve_slot a = s;
+        if (nrows[i]) {
+            a.cursor = s.cursor + nrows[i];
+            if (lg) {
+                a.n_out = s.n_out + 1;
+                a.state = a.n_out >= s.max_new ? RAMA_SERVE_DONE : RAMA_SERVE_DECODE;
+            }
+        }
+        slots_after[i] = a;
+    }
+    for (; r < max_rows; r++) rows_out[r] = rama_q8_serve_row{-1, -1, 0};
+    return 0;
+}
+
+int rama_q8_serve_end(rama_ctx* c) {
+    RAMA_ENTER(c);
+    REQUIRE(c, RAMA_EINVAL, "q8_serve_end: ctx is NULL");
+    if (!c->q8s.n_slots && !c->q8s.blob) return 0;
+    if (set_device(c)) return 1;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    serve_release(c);
+    return 0;
+}
+
+int rama_q8_serve_begin(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, int n_slots, int max_rows, int max_new_cap) {
+    RAMA_ENTER(c);
+    REQUIRE(c, RAMA_EINVAL, "ctx is NULL");
+    int rc = check_cfg(cfg); if (rc) return rc;
+    REQUIRE(w && w->group_size > 0 && cfg->dim % w->group_size == 0 && cfg->hidden_dim % w->group_size == 0, RAMA_EINVAL,
+            "q8_serve_begin: group_size must divide dim and hidden_dim");
+    REQUIRE(q8_weights_complete(w), RAMA_EINVAL, "q8_serve_begin: missing weights");
+    REQUIRE(n_slots >= 1 && n_slots <= kServeMaxSlots && max_rows >= n_slots && max_rows <= kQ8bMaxTok, RAMA_EINVAL,
+            "q8_serve_begin: 1 <= n_slots <= max_rows <= 128");
+    REQUIRE(max_new_cap >= 1 && max_new_cap <= cfg->seq_len - 1, RAMA_EINVAL, "q8_serve_begin: max_new_cap outside [1, seq_len - 1]");
+    REQUIRE(q8_batch_ok(cfg), RAMA_EUNSUP, "q8_serve_begin: a shape the Q8 token-batch pass does not take");
+    const int V = cfg->vocab_size;
+    const bool sampler = V > 1 && V <= kToppBlock * kToppMaxBlocks;
+    REQUIRE(sampler || V % 4 == 0, RAMA_EUNSUP, "q8_serve_begin: vocab_size % 4 != 0 needs vocab_size <= 32768");
+    if (set_device(c)) return 1;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    serve_release(c);
+    // both scratches, the sampler's slices and the chain's tables: sized here, outside any capture
+    rc = ensure_q8_scratch(c, cfg); if (rc) return rc;
+    Q8BatchScratch b{};
+    rc = ensure_q8_batch_scratch(c, cfg, w->group_size, &b); if (rc) return rc;
+    if (sampler) { rc = ensure_topp_batch(c, n_slots, V); if (rc) return rc; }
+    auto& sv = c->q8s;
+    const size_t S = (size_t)cfg->seq_len, N = (size_t)n_slots, R = (size_t)max_rows, cap = (size_t)max_new_cap;
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    const size_t sz[9] = {N * sizeof(ServeSlot), N * S * sizeof(int), R * sizeof(SeqSlot), R * sizeof(int), N * sizeof(int), N * sizeof(int),
+                          N * sizeof(ToppRow), 4 * sizeof(unsigned long long), N * cap * sizeof(int)};
+    size_t off[9], need = 0;
+    for (int i = 0; i < 9; i++) { off[i] = need; need += up(sz[i]); }
+    HIPCHK(hipMalloc(&sv.blob, need));
+    HIPCHK(hipMemsetAsync(sv.blob, 0, need, c->stream));          // every slot FREE, the counters 0
+    sv.rec_bytes = up(sizeof(ServeSlot) + S * sizeof(int));
+    HIPCHK(hipMalloc(&sv.stage, N * sv.rec_bytes));
+    HIPCHK(hipHostMalloc(&sv.pinned, N * sv.rec_bytes, hipHostMallocDefault));
+    HIPCHK(hipHostMalloc(&sv.ring, sizeof(int) * N * cap, hipHostMallocMapped));
+    HIPCHK(hipHostMalloc(&sv.done, sizeof(int) * N, hipHostMallocMapped));
+    memset(sv.ring, 0, sizeof(int) * N * cap);
+    memset(sv.done, 0, sizeof(int) * N);
+    ServeTables& t = sv.t;
+    t.slots = reinterpret_cast<ServeSlot*>(sv.blob + off[0]); t.ctx = reinterpret_cast<int*>(sv.blob + off[1]);
+    t.rows = reinterpret_cast<SeqSlot*>(sv.blob + off[2]); t.row_tok = reinterpret_cast<int*>(sv.blob + off[3]);
+    t.nrows = reinterpret_cast<int*>(sv.blob + off[4]); t.lrow = reinterpret_cast<int*>(sv.blob + off[5]);
+    t.trow = reinterpret_cast<ToppRow*>(sv.blob + off[6]); t.counters = reinterpret_cast<unsigned long long*>(sv.blob + off[7]);
+    t.out = reinterpret_cast<int*>(sv.blob + off[8]);
+    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&t.ring), sv.ring, 0));
+    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&t.done), sv.done, 0));
+    t.seq_len = cfg->seq_len; t.n_slots = n_slots; t.max_rows = max_rows; t.out_cap = max_new_cap;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    sv.cfg = *cfg; sv.w = *w; sv.sampler = sampler;
+    sv.states.assign(N, rama_run_state{}); sv.occupied.assign(N, 0); sv.gen.assign(N, 0);
+    sv.steps = 0; sv.captures = 0;
+    sv.max_rows = max_rows; sv.out_cap = max_new_cap; sv.n_slots = n_slots; sv.live = true;
+    return 0;
+}
+
+// the slot's occupant is still on the device's hands: admitted, and its finished word not yet set
+static bool serve_slot_live(const rama_ctx::Q8Serve& sv, int slot) {
+    return sv.occupied[slot] && !__atomic_load_n(sv.done + slot, __ATOMIC_ACQUIRE);
+}
+
+// rama_q8_serve_admit (n_cached 0) and rama_q8_serve_admit_at: the slot starts PROMPT at cursor = n_cached, over rows 0 .. n_cached - 1 that
+// earlier work on the stream has put into the run state's caches
+static int serve_admit(rama_ctx* c, int slot, const rama_run_state* state, const int32_t* context_host, int n_context, int n_cached,
+                       const rama_q8_serve_plan* plan) {
+    RAMA_ENTER(c);
+    REQUIRE(c && c->q8s.n_slots > 0, RAMA_EINVAL, "q8_serve_admit: call rama_q8_serve_begin first");
+    auto& sv = c->q8s;
+    // everything is checked before anything of the running chain is touched
+    REQUIRE(sv.live, RAMA_EINVAL, "q8_serve_admit: the chain's model or the run state of an occupied slot has been freed");
+    REQUIRE(state && context_host && plan, RAMA_EINVAL, "q8_serve_admit: NULL argument");
+    REQUIRE(slot >= 0 && slot < sv.n_slots, RAMA_EINVAL, "q8_serve_admit: no such slot");
+    int rc = q8_check(c, &sv.cfg, &sv.w, state); if (rc) return rc;
+    REQUIRE(!serve_slot_live(sv, slot), RAMA_EINVAL, "q8_serve_admit: the slot is busy");
+    const int V = sv.cfg.vocab_size;
+    REQUIRE(n_context >= 1, RAMA_EINVAL, "q8_serve_admit: n_context < 1");
+    REQUIRE(n_cached >= 0 && n_cached <= n_context - 1, RAMA_EINVAL, "q8_serve_admit_at: n_cached outside [0, n_context - 1] (the final context position is always fed)");
+    REQUIRE(plan->max_new >= 1, RAMA_EINVAL, "q8_serve_admit: max_new < 1");
+    REQUIRE(plan->max_new <= sv.out_cap, RAMA_EINVAL, "q8_serve_admit: max_new beyond rama_q8_serve_begin's max_new_cap");
+    REQUIRE(n_context <= sv.cfg.seq_len - plan->max_new, RAMA_EINVAL, "q8_serve_admit: n_context + max_new beyond seq_len");
+    for (int i = 0; i < n_context; i++) REQUIRE(context_host[i] >= 0 && context_host[i] < V, RAMA_EINVAL, "q8_serve_admit: token outside the vocabulary");
+    REQUIRE(topp_params_ok(plan->temperature, plan->topp, plan->u), RAMA_EINVAL, "q8_serve_admit: temperature >= 0, topp in [0,1], u in [0,1)");
+    REQUIRE(plan->stop_token >= -1 && plan->stop_token < V, RAMA_EINVAL, "q8_serve_admit: stop token outside the vocabulary");
+    for (int j = 0; j < sv.n_slots; j++)
+        REQUIRE(j == slot || !serve_slot_live(sv, j) || (sv.states[j].key_cache != state->key_cache && sv.states[j].value_cache != state->value_cache),
+                RAMA_EINVAL, "q8_serve_admit: the run state is already in a live slot");
+    REQUIRE(plan->temperature == 0.0f || sv.sampler, RAMA_EUNSUP, "q8_serve_admit: a sampled plan needs vocab_size <= 32768");
+    if (set_device(c)) return 1;
+    // the slot's own pinned record: its previous copy has run (the occupant it installed has finished, or there was none)
+    char* rec = sv.pinned + (size_t)slot * sv.rec_bytes;
+    ServeSlot h{};
+    h.kc = state->key_cache; h.vc = state->value_cache;
+    h.state = kServePrompt; h.n_ctx = n_context; h.cursor = n_cached; h.tok = 0; h.n_out = 0;
+    h.max_new = plan->max_new; h.stop = plan->stop_token; h.gen = sv.gen[slot] + 1;
+    h.temperature = plan->temperature; h.topp = plan->topp; h.u = plan->u;
+    memcpy(rec, &h, sizeof h);
+    memcpy(rec + sizeof h, context_host, sizeof(int) * (size_t)n_context);
+    // (the device writes neither again for the previous occupant: it is DONE)
+    memset(sv.ring + (size_t)slot * sv.out_cap, 0, sizeof(int) * (size_t)sv.out_cap);
+    __atomic_store_n(sv.done + slot, 0, __ATOMIC_RELEASE);
+    char* dst = sv.stage + (size_t)slot * sv.rec_bytes;
+    HIPCHK(hipMemcpyAsync(dst, rec, sizeof h + sizeof(int) * (size_t)n_context, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(serve_install_kernel, dim3(1), dim3(256), 0, c->stream, sv.t, slot, reinterpret_cast<const ServeSlot*>(dst));
+    LAUNCHCHK();
+    sv.states[slot] = *state; sv.occupied[slot] = 1; sv.gen[slot]++;
+    return 0;
+}
+
+int rama_q8_serve_admit(rama_ctx* c, int slot, const rama_run_state* state, const int32_t* context_host, int n_context, const rama_q8_serve_plan* plan) {
+    return serve_admit(c, slot, state, context_host, n_context, 0, plan);
+}
+
+int rama_q8_serve_admit_at(rama_ctx* c, int slot, const rama_run_state* state, const int32_t* context_host, int n_context, int n_cached,
+                           const rama_q8_serve_plan* plan) {
+    return serve_admit(c, slot, state, context_host, n_context, n_cached, plan);
+}
+
+// rows [0, n_rows) of every layer of src's caches into every destination's: one launch (q8_fork.hpp), stream-ordered
+int rama_q8_kv_fork(rama_ctx* c, const rama_config* cfg, const rama_run_state* src, const rama_run_state* dsts, int n_dst, int n_rows) {
+    RAMA_ENTER(c);
+    REQUIRE(c, RAMA_EINVAL, "q8_kv_fork: ctx is NULL");
+    int rc = check_cfg(cfg); if (rc) return rc;
+    REQUIRE(src && dsts, RAMA_EINVAL, "q8_kv_fork: NULL argument");
+    REQUIRE(n_dst >= 1 && n_dst <= kForkMaxDst, RAMA_EINVAL, "q8_kv_fork: 1 <= n_dst <= 16");
+    REQUIRE(n_rows >= 0 && n_rows <= cfg->seq_len, RAMA_EINVAL, "q8_kv_fork: n_rows outside [0, seq_len]");
+    REQUIRE(src->key_cache && src->value_cache, RAMA_EINVAL, "q8_kv_fork: the source has no caches");
+    const size_t layer = (size_t)cfg->seq_len * (size_t)cfg->dim, total = layer * (size_t)cfg->n_layers;
+    // every cache written must lie clear of the source's and of every other one written
+    std::vector<const float*> caches = {src->key_cache, src->value_cache};
+    for (int d = 0; d < n_dst; d++) {
+        REQUIRE(dsts[d].key_cache && dsts[d].value_cache, RAMA_EINVAL, "q8_kv_fork: a destination has no caches");
+        caches.push_back(dsts[d].key_cache); caches.push_back(dsts[d].value_cache);
+    }
+    for (size_t i = 2; i < caches.size(); i++)
+        for (size_t j = 0; j < i; j++)
+            REQUIRE(!ranges_overlap(caches[i], total, caches[j], total), RAMA_EINVAL,
+                    "q8_kv_fork: a destination shares a cache with the source or with another destination");
+    const auto& sv = c->q8s;
+    for (int d = 0; d < n_dst; d++)
+        for (int j = 0; j < sv.n_slots; j++)
+            REQUIRE(!serve_slot_live(sv, j) || (sv.states[j].key_cache != dsts[d].key_cache && sv.states[j].value_cache != dsts[d].value_cache),
+                    RAMA_EINVAL, "q8_kv_fork: a destination is in a live slot of the serving chain");
+    if (n_rows == 0) return 0;
+    const size_t span = (size_t)n_rows * (size_t)cfg->dim, reach = layer * (size_t)(cfg->n_layers - 1) + span;
+    for (int d = 0; d < n_dst; d++) { RAMA_WRITES(c, dsts[d].key_cache, reach); RAMA_WRITES(c, dsts[d].value_cache, reach); }
+    if (set_device(c)) return 1;
+    ForkParams p{};
+    p.src[0] = src->key_cache; p.src[1] = src->value_cache;
+    bool vec = aligned16(p.src[0]) && aligned16(p.src[1]);       // (dim % 4 == 0: a layer and a span are whole 16-byte words)
+    for (int d = 0; d < n_dst; d++) {
+        p.dst[0][d] = dsts[d].key_cache; p.dst[1][d] = dsts[d].value_cache;
+        vec = vec && aligned16(p.dst[0][d]) && aligned16(p.dst[1][d]);
+    }
+    p.n_dst = n_dst; p.layer_floats = layer; p.n_words = vec ? span / 4 : span;
+    const dim3 grid((unsigned)((p.n_words + kForkPiece - 1) / kForkPiece), (unsigned)(2 * cfg->n_layers));
+    if (vec) hipLaunchKernelGGL(kv_fork_kernel<true>, grid, dim3(kForkThreads), 0, c->stream, p);
+    else hipLaunchKernelGGL(kv_fork_kernel<false>, grid, dim3(kForkThreads), 0, c->stream, p);
+    LAUNCHCHK();
+    return 0;
+}
+
+// one step: the scheduler, the pass over its row table, the logits of the rows that carry them, the pick and the slots' state machine
+static int enqueue_q8_serve_step(rama_ctx* c, const Q8BatchScratch& b) {
+    auto& sv = c->q8s;
+    const rama_config* cfg = &sv.cfg;
+    const rama_q8_weights* w = &sv.w;
+    const int dim = cfg->dim, V = cfg->vocab_size, R = sv.max_rows, N = sv.n_slots;
+    hipLaunchKernelGGL(serve_schedule_kernel, dim3(1), dim3(kServeMaxSlots), 0, c->stream, sv.t);
+    LAUNCHCHK();
+    hipLaunchKernelGGL(embed_rows_kernel, dim3((dim + 255) / 256, R), dim3(256), 0, c->stream, b.X, w->token_embedding_table, (const int*)sv.t.row_tok, R, dim);
+    LAUNCHCHK();
+    int rc = q8_batch_layers(c, cfg, w, b, R, 0, nullptr, nullptr, sv.t.rows); if (rc) return rc;
+    // the classifier tail for the slots' logits rows only (b.Q is free here)
+    hipLaunchKernelGGL(serve_gather_kernel, dim3((dim + 255) / 256, N), dim3(256), 0, c->stream, b.Q, (const float*)b.X, (const int*)sv.t.lrow, dim);
+    LAUNCHCHK();
+    rc = enqueue_q8_classifier(c, cfg, w, b, b.Q, N); if (rc) return rc;
+    ServePickParams fin{};
+    fin.t = sv.t; fin.logits = b.LG; fin.ld = (size_t)V; fin.n = V;
+    if (sv.sampler) {
+        rc = enqueue_topp_batch_order(c, sv.t.trow, N, b.LG, (size_t)V, V, nullptr); if (rc) return rc;
+        fin.keys = c->tb.keys; fin.vals = c->tb.vals; fin.m = c->tb.m; fin.rstride = c->tb.rstride;
+    }
+    hipLaunchKernelGGL(serve_pick_kernel, dim3(N), dim3(1024), 0, c->stream, fin);
+    LAUNCHCHK();
+    return 0;
+}
+
+int rama_q8_serve_steps(rama_ctx* c, int n_steps) {
+    RAMA_ENTER(c);
+    REQUIRE(c && c->q8s.n_slots > 0, RAMA_EINVAL, "q8_serve_steps: call rama_q8_serve_begin first");
+    auto& sv = c->q8s;
+    REQUIRE(sv.live, RAMA_EINVAL, "q8_serve_steps: the chain's model or the run state of an occupied slot has been freed");
+    REQUIRE(n_steps >= 0, RAMA_EINVAL, "q8_serve_steps: n_steps < 0");
+    if (set_device(c)) return 1;
+    // (neither grows here: rama_q8_serve_begin sized them, and whoever grew them since for another shape dropped the step's graph)
+    int rc = ensure_q8_scratch(c, &sv.cfg); if (rc) return rc;
+    Q8BatchScratch b{};
+    rc = ensure_q8_batch_scratch(c, &sv.cfg, sv.w.group_size, &b); if (rc) return rc;
+    if (sv.sampler) { rc = ensure_topp_batch(c, sv.n_slots, sv.cfg.vocab_size); if (rc) return rc; }
+    c->embedded_x = nullptr; c->host_pos = -1;
+    int n_done = 0;
+    rc = q8_run_steps(c, sv.cg, n_steps, [&] { return enqueue_q8_serve_step(c, b); }, &n_done, &sv.captures);
+    sv.steps += (unsigned long long)n_done;
+    return rc;
+}
+
+int rama_q8_serve_poll(rama_ctx* c, int slot, int from, int32_t* out_host, int max_tokens, int* n_ready, int* finished, int* generation) {
+    RAMA_ENTER(c);
+    REQUIRE(c && n_ready && c->q8s.n_slots > 0 && slot >= 0 && slot < c->q8s.n_slots && from >= 0 && max_tokens >= 0 && (max_tokens == 0 || out_host),
+            RAMA_EINVAL, "q8_serve_poll: bad argument");
+    const auto& sv = c->q8s;
+    // the finished word first: it is stored after the occupant's last ring word, so a set word means every token is there to be read
+    const int fin = __atomic_load_n(sv.done + slot, __ATOMIC_ACQUIRE);
+    *n_ready = read_ring(sv.ring + (size_t)slot * sv.out_cap, sv.out_cap, from, out_host, max_tokens);
+    if (finished) *finished = fin != 0;
+    if (generation) *generation = sv.gen[slot];
+    return 0;
+}
+
+int rama_q8_serve_tokens(rama_ctx* c, int slot, int32_t* out_host, int max_tokens, int* n_out) {
+    RAMA_ENTER(c);
+    REQUIRE(c && n_out && c->q8s.n_slots > 0 && slot >= 0 && slot < c->q8s.n_slots && max_tokens >= 0 && (max_tokens == 0 || out_host), RAMA_EINVAL,
+            "q8_serve_tokens: bad argument");
+    auto& sv = c->q8s;
+    if (set_device(c)) return 1;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    { const int rh = handoff_check(c); if (rh) return rh; }
+    ServeSlot s{};
+    HIPCHK(hipMemcpy(&s, sv.t.slots + slot, sizeof s, hipMemcpyDeviceToHost));
+    const int n = std::min(std::min(s.n_out, sv.out_cap), max_tokens);
+    if (n > 0) HIPCHK(hipMemcpy(out_host, sv.t.out + (size_t)slot * sv.out_cap, sizeof(int) * n, hipMemcpyDeviceToHost));
+    *n_out = n;
+    return 0;
+}
+
+int rama_q8_serve_stats(rama_ctx* c, rama_q8_serve_report* out) {
+    RAMA_ENTER(c);
+    REQUIRE(c && out && c->q8s.n_slots > 0, RAMA_EINVAL, "q8_serve_stats: bad argument");
+    auto& sv = c->q8s;
+    if (set_device(c)) return 1;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    { const int rh = handoff_check(c); if (rh) return rh; }
+    memset(out, 0, sizeof *out);
+    unsigned long long cnt[4];
+    ServeSlot slots[kServeMaxSlots];
+    SeqSlot rows[kQ8bMaxTok];
+    int lrow[kServeMaxSlots];
+    HIPCHK(hipMemcpy(cnt, sv.t.counters, sizeof cnt, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(slots, sv.t.slots, sizeof(ServeSlot) * sv.n_slots, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(rows, sv.t.rows, sizeof(SeqSlot) * sv.max_rows, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(lrow, sv.t.lrow, sizeof(int) * sv.n_slots, hipMemcpyDeviceToHost));
+    out->steps = cnt[0]; out->graph_captures = sv.captures; out->rows_decode = cnt[1]; out->rows_prompt = cnt[2]; out->rows_idle = cnt[3];
+    out->n_slots = sv.n_slots; out->max_rows = sv.max_rows;
+    for (int r = 0; r < sv.max_rows; r++) {
+        const bool on = cnt[0] > 0 && rows[r].pos >= 0;            // (before the first step the table holds nothing)
+        out->last_rows[r] = rama_q8_serve_row{on ? rows[r].pad : -1, on ? rows[r].pos : -1, on && lrow[rows[r].pad] == r ? 1 : 0};
+    }
+    for (int i = 0; i < sv.n_slots; i++) {
+        out->slots[i] = rama_q8_serve_slot{slots[i].state, slots[i].n_ctx, slots[i].cursor, slots[i].n_out, slots[i].max_new};
+        out->generation[i] = sv.gen[i];
+    }
+    return 0;
+}

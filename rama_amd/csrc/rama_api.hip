@@ -1,7 +1,11 @@
 // rama_api.hip -- the C ABI of include/rama_hip.h: context, memory, the 1:1 Device<T>
-// ops, the fused decode path, measurement.  Kernels are in kernels.hpp.
+// ops, the fused decode path, measurement.  Kernels are in kernels.hpp.  The Q8 entry points are in q8_api.hip; ctx.hpp is
+// what the two share.
 #include "../../include/rama_hip.h"
 #include "kernels.hpp"
+#include "ops_kernels.hpp"
+#include "ref_kernels.hpp"
+#include "topp_kernels.hpp"
 #include "attn_wo.hpp"
 #include "layer_fused.hpp"
 #include "topp_sort.hpp"
@@ -10,12 +14,7 @@
 #include "ref_order.hpp"
 #include "chain.hpp"
 #include "topp_pick.hpp"
-#include "q8.hpp"
-#include "q8_batch.hpp"
-#include "q8_serve.hpp"
-#include "q8_fork.hpp"
-
-#include <hip/hip_ext.h>   // hipExtLaunchKernelGGL: start/stop events carried by the dispatch itself
+#include "ctx.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -37,11 +36,6 @@ extern "C" void rama_internal_note_alloc(const float* base, size_t n);          
 extern "C" int rama_internal_forget_range(rama_ctx* ctx, const float* base, size_t n, int freed);      // ... the copies derived from a range go
 extern "C" int rama_internal_adopt(rama_ctx* ctx, const rama_config* cfg, const rama_stage* st, const rama_weights* w);
 extern "C" const float* rama_internal_chain_view(rama_ctx* ctx, const float* a, int rows, int K, int capturing);
-extern "C" int rama_internal_note_write(rama_ctx* ctx, const float* dst, size_t n);                    // model.hip: an entry is about to write [dst, dst + n) on the device
-// every entry that writes device memory the caller names says so first: a chain-order copy DERIVED from a tensor uploaded by the caller (an adopted model's, a
-// view's) must not outlive a device-side write into that tensor (rama_fill_synth re-seeding it, an op's output landing in it).  Two atomic loads when the
-// range lies outside everything copies were derived from.
-#define RAMA_WRITES(c, p, n) do { if ((p) && (n)) { const int rw_ = rama_internal_note_write((c), (p), (size_t)(n)); if (rw_) return rw_; } } while (0)
 
 // ---------------------------------------------------------------- error plumbing
 
@@ -49,7 +43,7 @@ static thread_local std::string g_err;
 
 const char* rama_last_error(void) { return g_err.c_str(); }
 
-static int fail(int code, const char* what, const char* file, int line) {
+int fail(int code, const char* what, const char* file, int line) {
     char buf[512];
     if (code > 0)
         snprintf(buf, sizeof buf, "%s: %s (hipError %d) at %s:%d", what, hipGetErrorString((hipError_t)code), code, file, line);
@@ -58,271 +52,25 @@ static int fail(int code, const char* what, const char* file, int line) {
     g_err = buf;
     return code;
 }
-#define HIPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail((int)e_, #expr, __FILE__, __LINE__); } while (0)
-#define REQUIRE(cond, code, msg) do { if (!(cond)) return fail((code), msg, __FILE__, __LINE__); } while (0)
-#define LAUNCHCHK() HIPCHK(hipGetLastError())
 
 // ---------------------------------------------------------------- context
 
-constexpr int kSmallAttnPosDefault = 256;
-constexpr size_t kAttnChainMaxLds = 136 * 1024;      // dynamic LDS attention_chain_kernel may ask for (allowed once per device in rama_ctx_create)
-constexpr int kSpreadAttnPos = 128;        // parity mode: from this position on the attention is two launches spread over the chip (chain.hpp; "spread_pos": 187 against 184 tok/s at positions 124..179, 178 against 152 at 800)
 constexpr int kLeadSlots = 2 * 256 + 2;       // tagged words of the leader-workgroup norms: two per layer of a stage (<= 256 layers), one for the final norm
-constexpr int kLongAttnPos = 256;          // parity mode: attention_chain_kernel runs 16 waves per head from this position on
 
-struct KProf {
-    int kernel_id = -1;
-    int max_records = 0;
-    int used = 0;
-    std::vector<hipEvent_t> ev;   // 2 per record
-};
-
-// a captured, instantiated graph: made by capture_graph, launched by replay_graph
-struct CapturedGraph {
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    bool handoff = false;              // [r6] the captured launches hand data over inside a kernel (a leader norm, attention+Wo, the one-launch stage): a REPLAY must mark
-                                       // the error word as worth reading too (rama_ctx::handoff_dirty is otherwise only set where such a launch is enqueued)
-};
-static void destroy_graph(CapturedGraph& g) {
+void destroy_graph(CapturedGraph& g) {
     if (g.exec) hipGraphExecDestroy(g.exec);
     if (g.graph) hipGraphDestroy(g.graph);
     g = CapturedGraph();
 }
 
-struct GraphCache {
-    CapturedGraph cg;
-    // identity of what was captured
-    rama_config cfg{};
-    rama_weights w{};
-    rama_run_state s{};
-    bool valid = false;
-    int steps = 1;                     // decode steps in the captured graph
-    unsigned long long copies_gen = 0; // model.hip's generation of derived weight copies at capture: a graph holds their addresses, and ANOTHER context may free them
-};
-
-struct rama_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    Ctl* ctl = nullptr;          // device cursor
-    int* forced = nullptr;       // device forced-token list
-    int forced_cap = 0;
-    int* out = nullptr;          // device produced-token list
-    int out_cap = 0;
-    int* ring = nullptr;                    // host-pinned, device-mapped: ring[i] = token i of the chained loop + 1 (0: not produced yet)
-    int* ring_dev = nullptr;
-    int ring_hi = 0;                        // entries that may be non-zero
-    int* argmax_result = nullptr;   // device int for rama_sample_argmax
-    int* pinned_int = nullptr;      // host pinned
-    int* pinned_tok = nullptr;      // host pinned staging: token ids + a SeqSlot table of a token-batch pass
-    bool graph_mode = false;
-    struct StageGraph { GraphCache g; rama_stage st{}; int variant = 0; unsigned long long used = 0; };
-    std::vector<StageGraph> sg;        // rama_forward / rama_forward_stage* in graph mode: one graph per (state, stage, attention variant)
-    unsigned long long sg_clock = 0;
-    GraphCache gc[8];                  // [0..3] one step per graph, [4..7] tune_graph_steps steps per graph; by attention variant (attn_variant)
-    KProf kp;
-    int cu_count = 0;
-    hipEvent_t cur_start = nullptr, cur_stop = nullptr;   // events the next profiled launch carries
-    int tune_geom = 3;
-    int tune_w13i = 1;                     // 1: the fused W1|W3 launch streams the model's row-interleaved copy when there is one
-    int tune_solo = -1;                    // small-K matvecs, one wave per row group: 1 on, 0 off, -1 = rows of <= 2048 floats
-    int tune_ref_order = 0;                // 1: every op in the reference's own rounding order: bit-comparable with the CPU path ("parity mode")
-    int tune_tol = 0;                      // "ref_order" = 2, the tolerance-mode experiment: the chain-order matvecs (the reference's rounding sequence) with the layer
-                                           // norms folded into them as tree-shaped sums and the fast attention -- 0.72 of the roofline, but 1.4e-4 from the CPU path at
-                                           // llama2-7B x 200 positions, no closer than the fast path; kept as the per-op A/B instrument
-    int tune_bar = 0;                      // [r6] "ref_order" = 3, BAR mode: parity mode's launches (chain-order matvecs, exact norms, the exact attention) up to position
-                                           // "bar_pos", the FAST path's attention from there on -- not bit-identical, but measured <= 1e-4 from the CPU path over the WHOLE
-                                           // 2 048-position context at llama2-7B depth (profiles/r06_tolerance_sweep_7b_2048pos.jsonl: fast attention at every position 9.75e-5;
-                                           // every other single swap >= 1.3e-4 already at 200 positions), where the exact attention costs 25 us a layer at position 1 900
-    int tune_bar_pos = kSpreadAttnPos;     // ... the first position that takes the fast attention (clamped to the spread attention's switch and to 256: below it one exact variant)
-    bool bar_fast = false;                 // ... the steps being enqueued / captured are at or behind it
-    int tune_lane_reduce = 0;              // [r6] parity mode: the order of the final 4-lane sum of cpu.rs:148 `v.reduce_add()` (wide::f32x4 leaves it to the build's target
-                                           // features): 0 pairwise (l0+l1)+(l2+l3), 1 strided (l0+l2)+(l1+l3), 2 sequential ((l0+l1)+l2)+l3 -- the oracle's switch of the same name
-    int tune_tol_mask = 0;                 // tolerance mode, A/B: ops swapped for the fast path's (1 qkv, 2 wo, 4 w13, 8 w2, 16 cls) or parity mode's (32 attention, 64 norms)
-    int tune_chain = 1;                    // parity mode streams the model's chain-order weight copy (chain.hpp); 0: ref_order.hpp's one-thread-per-row kernels
-    int tune_chain_d = 0;                  // chain-order matvec geometry: 0 = by row groups per CU, else 100 W + D (waves per group, blocks per wave in flight)
-    // device top-p sampler (Device::sample for temperature != 0); temperature 0 = argmax
-    float samp_T = 0.0f, samp_topp = 0.9f, samp_u = 0.0f;
-    float* topp_keys[2] = {nullptr, nullptr}; int* topp_vals[2] = {nullptr, nullptr};
-    float* topp_prefix = nullptr; int* topp_m = nullptr; unsigned* topp_err = nullptr;
-    int topp_cap = 0;
-    float* topp_bp = nullptr; int* topp_bi = nullptr; int* topp_bcount = nullptr;       // topp_sort.hpp
-    int* topp_racc = nullptr;               // pair-wise ranking: the accumulators, one per block slot
-    unsigned long long* topp_rk = nullptr;  // small-block path: count << 48 | mass accumulators, one per block slot
-    unsigned long long* topp_bm = nullptr;  // ... the blocks' running masses
-    float* topp_approx = nullptr;           // ... the mass in front of every entry of the whole order
-    void* topp_dist = nullptr;              // topp_pick_dist_kernel's hand-off words: items | hdr | cross | epoch | bad
-    bool topp_dist_dirty = false;           // ... a distributed pick has been enqueued since its error word was last read (else a synchronising exit need not read it)
-    int tune_spread_pos = kSpreadAttnPos;   // parity mode: from this position on the attention is spread over the chip (scores | softmax + values)
-    int tune_attn_fv = 1;                   // parity mode, long contexts: softmax + value chains as one launch (0: two launches)
-    int tune_topp_dist = 1;                 // 1: the running sums by up to 32 workgroups in one launch (topp_pick.hpp); 0: one workgroup's scan rounds
-    ToppStats* topp_stats = nullptr;        // small-block path: partial softmax statistics, one per 1024 logits
-    int tune_topp_block = 1024;             // entries per sorted block on the pair-ranking path: 1024 or 512 (statistics once + 8- / 4-wave sorts) or 2048 (round 3's block sort)
-    int tune_topp_pairs = 1;                // 1: the ranking as (block, block) pairs spread over the chip + a scatter launch; 0: one workgroup searches all blocks in its LDS
-    int tune_norm_in_gemm = 1;              // token-batch passes: the rmsnorm's per-token scale is applied by the consuming GEMM (one launch per norm instead of two)
-    int tune_tiled = 1;                     // token-batch GEMMs read the model's tile-order weight copy when it exists
-    int tune_prefill_tok = kMfMaxTok;       // prompt positions per weight pass of rama_prefill: 128 (needs the tile-order copies) or 64
-    int tune_prefill_attn = 1;              // 1: prefill passes run attention as MFMA tiles, 16 queries per workgroup (prefill_attn.hpp)
-    int tune_graph_steps = -1;              // decode steps captured per hipGraph (the cursor lives on the device, so steps are identical); -1: 4 for dim <= 1024, else 1
-    int tune_attn_u = 8;                    // cache rows per lane and round in the split-T attention (8 | 16; 16 measured no faster)
-    int tune_topp_sort = 1;                 // 0: ranks through global memory (topp_rank_global_kernel) for every vocabulary size
-    int tune_topp_keep_sums = 0;            // 1: the scan sampler also writes its running sums to global memory (tests)
-    // the batched top-p sampler (rama_sample_topp_batch_dev, the sampled chained batch; topp_sort.hpp ROWS kernels): one scratch slice
-    // per row, sized by the op's first call or by rama_decode_batch_begin_sampled -- never inside a step, which may be captured
-    struct ToppBatchScratch {
-        int rows = 0; size_t rstride = 0;  // rows x rstride entries per slice array
-        float* keys = nullptr; int* vals = nullptr; float* bp = nullptr; int* bi = nullptr;
-        unsigned long long* rk = nullptr; unsigned long long* bm = nullptr;
-        int* bcount = nullptr; ToppStats* stats = nullptr; int* m = nullptr;     // rows x kToppRowBlocks, rows x kToppRowBlocks, rows
-        ToppRow* rows_dev = nullptr;       // [kMfMaxTok] rama_sample_topp_batch_dev's (T, topp, u) per row, written by a launch
-    } tb;
-    // Q8 models (rama_q8_forward / rama_q8_generate): the int8 activations and their scales, sized by the first call; graphs of their own
-    int8_t* q8_xq = nullptr; float* q8_xs = nullptr; size_t q8_cap = 0;
-    struct Q8Graph { CapturedGraph cg; rama_config cfg{}; rama_q8_weights w{}; rama_run_state s{}; int variant = 0; int chained = 0; };
-    std::vector<Q8Graph> q8g;
-    // Q8 token batches (rama_q8_prefill / rama_q8_decode_batch / the chained batch): row-major scratch for kQ8bMaxTok tokens, sized by
-    // the first call (never inside a capture; only the chained batch's step q8c.cg holds it, and goes when it moves), see Q8BatchScratch
-    char* q8b_blob = nullptr; size_t q8b_cap = 0;
-    int tune_split_pos = -1;               // attention runs split-T (+ combine launch) from this position on; -1 = by model size
-    int tune_resid_r2 = 2;                 // Wo / W2 under geometry 3: 0 = 4-row workgroups, 1 = 2 rows x 8 waves (+0.45 %),
-                                           // 2 = additionally 16 waves for rows wider than 8192 floats (W2: +1.15 % more), 3 = 16 waves x 4 chunks
-    int tune_prefill = 1;                  // 1: rama_generate_greedy runs the forced prompt positions through rama_prefill
-    int tune_merge = -1;                   // attention + Wo in one launch: 1 on, 0 off, -1 by model size (on for dim <= 1024:
-                                           // +4..8 % at the stories shapes; at llama2-7B +0.9 % short / -2.5 % long contexts)
-    int tune_fused = -1;                   // a stage's layers (+ classifier) as one launch (layer_fused.hpp): 1 on, 0 off, -1 on for dim <= 1024
-                                           // (stories15M +4 %, stories110M +25 % tokens/s over the separate launches)
-    int tune_fused_solo = -1;              // its workgroups alone on their CU (LDS request padded): 1, 0, -1 = for dim > 512 (stories110M: 216 -> 200 us
-                                           // per token, a consumer's polls do not queue behind a neighbour's weight requests; stories15M: 89 -> 92)
-    tagged_t* fused_hand = nullptr;        // device: its hand-off vectors (tagged words), room for the largest shape it takes
-    unsigned* fused_epoch = nullptr;       // device: the tag of the current token, advanced after every launch of the stage kernel
-    bool fused_chained = false;            // the step being enqueued ends in a sampler launch, which advances the epoch
-    bool fused_epoch_owed = false;         // ... and the stage launch just enqueued relies on that
-    int merge_blocks_per_cu[3] = {-1, -1, -1};   // occupancy of attn_wo_kernel<16|32|64> at the LDS size below
-    size_t merge_lds[3] = {0, 0, 0};
-    unsigned* attn_counter = nullptr;      // device: arrivals of the attention workgroups
-    float* attn_part = nullptr;            // split-T partials [n_heads, nsplit, head_size + 4]
-    size_t attn_part_floats = 0;
-    float* attn_scores = nullptr;          // parity mode, spread attention: the raw scores [n_heads, seq_len] (the softmax+values launch reads them here and
-    size_t attn_scores_floats = 0;         // writes the probabilities to the caller's att: no workgroup reads a buffer another one of the launch writes)
-    float* pf_blob = nullptr;              // token-batch scratch (tile layout): see BatchScratch
-    float* pc_blob = nullptr;              // parity-mode prefill scratch (row-major token batches): see prefill_chain
-    size_t pc_floats = 0;
-    int tune_chain_lead = 1;               // parity mode, dim > 512: the layer norms' exact sums by a leader workgroup INSIDE the consuming matvec's launch (chain.hpp CNORM_LEAD)
-    unsigned long long* lead_slots = nullptr;   // device: one tagged word per (layer, norm), 256 bytes apart
-    int tune_chain_norm = 1;               // parity mode, dim <= 512: the layer norms folded into the matvecs that consume them
-    int tune_chain_split = 1;              // parity mode: the row groups that do not divide by the compute units walked as half groups (chain.hpp half_from)
-    int tune_chain_lead_w = 0;             // parity mode: waves per row group of the launches with a leader norm (0: by the number of row groups)
-    int tune_chain_resid_d = -1;           // parity mode: 100 W + D for the residual products (Wo, W2) only; 0: by the number of row groups like the others; -1: W = 1, D = 32 when a CU holds one group
-    // [r5] a run of Device::apply_position calls on consecutive heads (infer.rs:25-29: n_heads calls per layer, 1 024 per llama2-7B token, each a launch of
-    // its own) is ISSUED AS ONE LAUNCH: a call only records (q, k, table rows, head size); the next call extends the run when it continues it, and
-    // whatever enters the library next issues it first (RAMA_ENTER).  Only on a stream the context owns ("rope_batch" = 0: every call a launch).
-    struct { float* q = nullptr; float* k = nullptr; const float* pr = nullptr; const float* pi = nullptr; int hs = 0, count = 0; } rope;
-    int tune_rope_batch = 1;
-    // ... and so is a run of up to three parity-mode Device::matmul calls with the same activations and shape on chain-order copies (infer.rs:20-23: Wq, Wk,
-    // Wv; :41-42: W1, W3): one launch over all their row groups ("matmul_batch")
-    struct { const float* w[3]; float* o[3]; const float* x = nullptr; int K = 0, rows = 0, count = 0; bool norm = false; } mm;
-    int tune_matmul_batch = 1;
-    // ... and a parity-mode Device::rmsnorm waits for the run of matmuls on its output (infer.rs:19-23, :40-42): the run's launch then carries the norm as
-    // its leader workgroup (chain.hpp CNORM_LEAD: the exact sum of squares while the row groups' weights are already on their way), and the leader also
-    // stores the normalised vector the call was asked for.  Anything else entering the library issues the norm as its own launch first ("norm_fold").
-    // The leader's tagged words rotate through a range of their own; the epoch advances when the range wraps.
-    struct { float* o = nullptr; const float* x = nullptr; const float* w = nullptr; int n = 0; bool on = false; } nrm;
-    int tune_norm_fold = 1;
-    int tune_qkv_fold = 1;                 // ... and a run of three matmuls, the apply_position calls over all heads of its first two outputs and the copies of its last two into cache
-                                           // rows (infer.rs:20-33) are ONE launch with the Wq|Wk|Wv epilogue (rotation, cache rows)
-    int tune_resid_fold = 1;               // ... and a Device::array_add of a recorded matmul's output becomes that launch's residual epilogue
-    int op_lead_next = 0;
-    // ... and Device::sinu waits for the Device::array_mult on the same vector (infer.rs:44-45), one Device::copy_from_slice for the next (:32-33): one
-    // launch per pair ("ew_batch").  At most ONE of the three records is pending at any time: whoever records flushes the others first.
-    struct { int kind = 0; float* t = nullptr; const float* s = nullptr; size_t n = 0; } ew;      // 1: sinu(t, n); 2: copy(t, s, n)
-    int tune_ew_batch = 1;
-    int tune_chain_views = 1;              // parity mode, Device::matmul on a matrix of no model: a chain-order copy of the tensor is made on first use
-    int tune_prefill_chain = 1;            // parity mode: prompt positions go through the chain-order token-batch kernels (32 per weight pass); 0: one forward() each
-    size_t pf_floats = 0;
-    int host_pos = -1;                     // position of the next chained decode step (mirrors the device cursor)
-    bool split_attn = false;               // variant the steps being enqueued / captured use
-    bool long_attn = false;                // parity mode: the position is >= 256 (16 waves per head in attention_chain_kernel)
-    bool spread_attn = false;              // parity mode: the position is >= tune_spread_pos (the exact attention as launches spread over the whole chip)
-    int variant = 0;                       // attn_variant() of the steps being enqueued / captured
-    bool small_attn = false;               // 4-wave attention workgroups (contexts of <= kSmallAttnPos timesteps)
-    int tune_small_waves = 8, tune_small_pos = kSmallAttnPosDefault;   // waves per head and position limit of the small-attention variant
-    int tune_combine_v = 1;                // split-T combine: 1 = all slice loads up front, 0 = round 1's loop
-    int tune_attn_nsplit = 0;              // split-T slices per head: 0 = #CUs / n_heads (<= 16), else 1..32
-    int tune_attn_waves = 8;               // waves per split-T workgroup (16, 8 or 4); 8 measured best at llama2-7B, 1000-1900 tokens
-    int tune_attn_nt = 1;                  // 1: split-T attention reads the cache rows non-temporally (+2.7 % tokens/s at 1900 tokens)
-    int tune_small_attn = -1;              // fewer-wave attention in the decode step: -1 (default) below tune_small_pos where attention
-                                           // is not merged with Wo, 0 never, 1 always (below the split threshold)
-    unsigned long long* pbar = nullptr;    // device: [1] = error word of the merged attention+Wo launch's bounded spin
-    bool handoff_dirty = false;            // a launch with an in-kernel hand-off (attention+Wo, the one-launch stage) has been enqueued since the error word was last read
-    const float* embedded_x = nullptr;   // run-state x that already holds emb[ctl.token] (chained decode)
-    // rama_decode_batch_begin / _steps: the sequences' cursors live on the device
-    struct BatchChain {
-        int n_seq = 0, pos_max = 0, out_cap = 0, steps_done = 0;
-        int* toks = nullptr;               // [kMfMaxTok] the token each sequence feeds next
-        SeqSlot* seqs = nullptr;           // [kMfMaxTok] cache bases + position of every sequence
-        int* out = nullptr;                // [kMfMaxTok, out_cap] the tokens produced
-        int* ring = nullptr;               // the same, host-pinned and device-mapped: token + 1, 0 = not produced yet (rama_decode_batch_stream_poll)
-        int* ring_dev = nullptr;
-        rama_config cfg{}; rama_weights w{};
-        CapturedGraph cg; int graph_bucket = -1;        // the step captured for contexts of up to 256 * graph_bucket timesteps
-        // rama_decode_batch_begin_sampled: a step ends in the batched top-p sampler instead of argmax_batch_kernel
-        bool sampled = false;
-        ToppRow* rows = nullptr;           // [kMfMaxTok] every sequence's (T, topp, u, forced list)
-        int* forced = nullptr; size_t forced_cap = 0;      // the forced lists, one after the other
-    } bc;
-    // rama_q8_decode_batch_begin / _steps: the same for a Q8 model, with per-sequence ends (a step budget, a stop token).  A state of
-    // its own: the fp32 chain above neither sees nor shares any of it.
-    struct Q8Chain {
-        int n_seq = 0, max_steps = 0, out_cap = 0, steps_done = 0;      // out_cap: row stride of out / ring, >= every sequence's budget
-        bool live = false;                 // false once the model or a member's run state has been freed: rama_q8_decode_batch_steps refuses
-        int* toks = nullptr;               // [kMfMaxTok] the token each sequence feeds next
-        SeqSlot* seqs = nullptr;           // [kMfMaxTok] cache bases, position and tokens produced of every sequence
-        int* out = nullptr;                // [kMfMaxTok, out_cap] the tokens produced
-        int* ring = nullptr;               // the same, host-pinned and device-mapped: token + 1, 0 = not produced yet
-        int* ring_dev = nullptr;
-        BatchEnds* ends = nullptr;         // device: every sequence's budget (a stop lowers it) and stop token, and where `done` is
-        int* done = nullptr;               // [kMfMaxTok] host-pinned and device-mapped: 1 = the sequence has finished
-        int* done_dev = nullptr;
-        bool sampled = false;              // a step ends in the batched top-p sampler (a row samples, or is forced) instead of argmax_batch_kernel
-        ToppRow* rows = nullptr;           // [kMfMaxTok] every sequence's (T, topp, u, forced list)
-        int* forced = nullptr; size_t forced_cap = 0;
-        rama_config cfg{}; rama_q8_weights w{};
-        std::vector<rama_run_state> states;
-        CapturedGraph cg;                  // one step: nothing in its launch geometry depends on the positions
-    } q8c;
-    // rama_q8_serve_begin / _admit / _steps: the serving chain (q8_serve.hpp), a state of its own next to the chain above
-    struct Q8Serve {
-        int n_slots = 0, max_rows = 0, out_cap = 0;       // n_slots 0: no serving chain
-        bool live = false;                 // false once the model or an occupied slot's run state has been freed: rama_q8_serve_steps refuses
-        bool sampler = false;              // a step runs the batched sampler's ordering launches (vocab_size <= 32768)
-        ServeTables t{};                   // the device tables (ring / done: the device addresses of the two below)
-        char* blob = nullptr;              // ... all of them, one allocation
-        char* stage = nullptr;             // device: one admission record per slot (a ServeSlot + seq_len tokens)
-        char* pinned = nullptr;            // host-pinned: the same, what rama_q8_serve_admit fills and copies from
-        size_t rec_bytes = 0;
-        int* ring = nullptr;               // [n_slots, out_cap] host-pinned and device-mapped: token + 1, 0 = not produced yet
-        int* done = nullptr;               // [n_slots] host-pinned and device-mapped: 1 = the slot's occupant has finished
-        rama_config cfg{}; rama_q8_weights w{};
-        std::vector<rama_run_state> states;   // per slot, the occupant's
-        std::vector<char> occupied;        // per slot: admitted, and not yet seen DONE by a call that frees the slot
-        std::vector<int> gen;
-        unsigned long long steps = 0, captures = 0;
-        CapturedGraph cg;                  // one step, for the chain's whole life: the tables' addresses, nothing of a sequence
-    } q8s;
-};
-
-static int set_device(rama_ctx* c) { HIPCHK(hipSetDevice(c->device)); return 0; }
+int set_device(rama_ctx* c) { HIPCHK(hipSetDevice(c->device)); return 0; }
 // the pending run of apply_position calls (rama_ctx::rope) is issued by whatever enters the library next: first statement of every entry point
 // that enqueues, synchronises or changes a setting
 static int flush_rope(rama_ctx* c);
 static int flush_mm(rama_ctx* c);
 static int flush_ew(rama_ctx* c);
 // (in the order they were recorded: a norm and the run of matmuls on it, the rotations of that run's q and k, a copy -- see rama_copy_from_slice)
-static int flush_pending(rama_ctx* c) { int rf = flush_mm(c); if (!rf) rf = flush_rope(c); if (!rf) rf = flush_ew(c); return rf; }      // (flush_mm issues a recorded norm too)
-#define RAMA_PENDING(c) ((c)->rope.count | (c)->mm.count | (c)->ew.kind | (int)(c)->nrm.on)
-#define RAMA_ENTER(c) do { if ((c) && RAMA_PENDING(c)) { const int rf_ = flush_pending(c); if (rf_) return rf_; } } while (0)
+int flush_pending(rama_ctx* c) { int rf = flush_mm(c); if (!rf) rf = flush_rope(c); if (!rf) rf = flush_ew(c); return rf; }      // (flush_mm issues a recorded norm too)
 
 // internal accessors for the library's other translation units (pipe.hip); not in the C ABI header
 extern "C" void* rama_internal_stream(rama_ctx* c) { if (c && RAMA_PENDING(c)) (void)flush_pending(c); return c ? (void*)c->stream : nullptr; }
@@ -426,53 +174,6 @@ int rama_ctx_create(int device, void* hip_stream, rama_ctx** out) {
     return 0;
 }
 
-// the captured Q8 steps: all of them (s == NULL) or those over one run state
-static void drop_q8_graphs(rama_ctx* c, const rama_run_state* s) {
-    // the chained batch's step: it goes with all Q8 graphs, and with a member's run state -- after which the chain is dead
-    bool member = false;
-    for (const auto& m : c->q8c.states) member = member || (s && m.key_cache == s->key_cache);
-    if (c->q8c.cg.exec && (!s || member)) { (void)hipStreamSynchronize(c->stream); destroy_graph(c->q8c.cg); }
-    if (member) c->q8c.live = false;
-    // the serving chain: its step goes with all Q8 graphs (the next rama_q8_serve_steps captures again); the run state of a slot whose
-    // occupant the host cannot yet see DONE ends the chain -- a finished occupant's is its owner's again
-    auto& sv = c->q8s;
-    if (!s && sv.cg.exec) { (void)hipStreamSynchronize(c->stream); destroy_graph(sv.cg); }
-    for (int i = 0; s && i < sv.n_slots; i++) {
-        if (!sv.occupied[i] || sv.states[i].key_cache != s->key_cache) continue;
-        if (__atomic_load_n(sv.done + i, __ATOMIC_ACQUIRE)) { sv.occupied[i] = 0; continue; }
-        (void)hipStreamSynchronize(c->stream);
-        sv.live = false;
-    }
-    bool any = false;
-    for (auto& e : c->q8g) any = any || !s || !memcmp(&e.s, s, sizeof *s);
-    if (!any) return;
-    (void)hipStreamSynchronize(c->stream);
-    for (size_t i = 0; i < c->q8g.size();) {
-        auto& e = c->q8g[i];
-        if (s && memcmp(&e.s, s, sizeof *s)) { i++; continue; }
-        destroy_graph(e.cg);
-        c->q8g.erase(c->q8g.begin() + (long)i);
-    }
-}
-// q8_model.hip: a Q8 model (weights *freed) is about to go: the captured Q8 steps, and a chained batch over it is dead
-extern "C" void rama_internal_drop_q8_graphs(rama_ctx* c, const rama_q8_weights* freed) {
-    if (!c) return;
-    drop_q8_graphs(c, nullptr);
-    if (freed && c->q8c.n_seq > 0 && c->q8c.w.wq == freed->wq) c->q8c.live = false;
-    if (freed && c->q8s.n_slots > 0 && c->q8s.w.wq == freed->wq) c->q8s.live = false;
-}
-
-// the serving chain's allocations (rama_q8_serve_begin / _end, rama_ctx_destroy); the stream is idle
-static void serve_release(rama_ctx* c) {
-    auto& sv = c->q8s;
-    destroy_graph(sv.cg);
-    hipFree(sv.blob); hipFree(sv.stage);
-    if (sv.pinned) hipHostFree(sv.pinned);
-    if (sv.ring) hipHostFree(sv.ring);
-    if (sv.done) hipHostFree(sv.done);
-    sv = rama_ctx::Q8Serve();
-}
-
 static void drop_graph(rama_ctx* c) {
     destroy_graph(c->bc.cg);
     c->bc.graph_bucket = -1;
@@ -498,13 +199,9 @@ int rama_ctx_destroy(rama_ctx* c) {
     hipFree(c->topp_rk); hipFree(c->topp_bm); hipFree(c->topp_approx); hipFree(c->topp_dist); hipFree(c->topp_stats);
     hipFree(c->bc.toks); hipFree(c->bc.seqs); hipFree(c->bc.out); if (c->bc.ring) hipHostFree(c->bc.ring);
     hipFree(c->bc.rows); hipFree(c->bc.forced);
-    hipFree(c->q8c.toks); hipFree(c->q8c.seqs); hipFree(c->q8c.out); hipFree(c->q8c.ends); hipFree(c->q8c.rows); hipFree(c->q8c.forced);
-    if (c->q8c.ring) hipHostFree(c->q8c.ring);
-    if (c->q8c.done) hipHostFree(c->q8c.done);
-    serve_release(c);
+    release_q8(c);
     hipFree(c->tb.keys); hipFree(c->tb.vals); hipFree(c->tb.bp); hipFree(c->tb.bi); hipFree(c->tb.rk); hipFree(c->tb.bm);
     hipFree(c->tb.bcount); hipFree(c->tb.stats); hipFree(c->tb.m); hipFree(c->tb.rows_dev);
-    hipFree(c->q8_xq); hipFree(c->q8_xs); hipFree(c->q8b_blob);
     hipHostFree(c->pinned_int); hipHostFree(c->pinned_tok);
     hipEventDestroy(c->t0); hipEventDestroy(c->t1);
     if (c->own_stream) hipStreamDestroy(c->stream);
@@ -516,7 +213,7 @@ int rama_ctx_destroy(rama_ctx* c) {
 // through the error word at pbar[1]; their results are then invalid.  Every synchronising exit reads the word -- once the stream is idle
 // -- fails the call and clears it, so that neither garbage logits leave with rc 0 nor a stale word makes every later launch give up.
 static int topp_dist_check(rama_ctx* c);
-static int handoff_check(rama_ctx* c) {
+int handoff_check(rama_ctx* c) {
     { const int rt = topp_dist_check(c); if (rt) return rt; }
     if (!c->handoff_dirty || !c->pbar) return 0;
     unsigned long long perr = 0;
@@ -531,25 +228,7 @@ static int handoff_check(rama_ctx* c) {
     return 0;
 }
 
-// g = the launches `enqueue` puts on the stream, captured and instantiated (whatever g held goes first).  The capture always ends -- a stream
-// must never be left capturing --, and an error of `enqueue` comes before the capture's own status.  rama_ctx::handoff_dirty is saved and
-// cleared around the capture: what the enqueue sets is a property of the GRAPH (g.handoff), which replay_graph re-arms at every launch.
-template <class Enqueue>
-static int capture_graph(rama_ctx* c, CapturedGraph& g, Enqueue&& enqueue) {
-    destroy_graph(g);
-    HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    const bool dirty_before = c->handoff_dirty;
-    c->handoff_dirty = false;
-    const int rc = enqueue();
-    hipError_t err = hipStreamEndCapture(c->stream, &g.graph);
-    g.handoff = c->handoff_dirty;
-    c->handoff_dirty = dirty_before;
-    if (rc) { destroy_graph(g); return rc; }
-    if (err == hipSuccess) err = hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0);
-    if (err != hipSuccess) { destroy_graph(g); return fail((int)err, "graph capture", __FILE__, __LINE__); }
-    return 0;
-}
-static int replay_graph(rama_ctx* c, const CapturedGraph& g) {
+int replay_graph(rama_ctx* c, const CapturedGraph& g) {
     HIPCHK(hipGraphLaunch(g.exec, c->stream));
     if (g.handoff) c->handoff_dirty = true;
     return 0;
@@ -639,9 +318,6 @@ int rama_free(rama_ctx* c, void* p) {
 
 // ---------------------------------------------------------------- launch helpers
 
-static inline int ew_grid(size_t n) { return (int)std::min<size_t>((n + 255) / 256, 2048); }
-static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 // Matvec workgroup geometry: R_ rows (R2_ (w1,w3) row pairs) per workgroup of NW_ waves, CH_
 // 1-KiB chunks per wave per step.  Geometry 3 (4 rows x 8 waves x 2 chunks) ships: in the
 // full llama2-7B decode it gives 233 tok/s vs 223 / 221 / 231 for 0 / 1 / 2 (tools/tune.py).
@@ -656,33 +332,6 @@ static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
         case 4: { constexpr int R_ = 8, R2_ = 4, CH_ = 2, NW_ = 8; (void)R_; (void)R2_; KERNEL_CALL; } break;  \
         default: { constexpr int R_ = 4, R2_ = 2, CH_ = 2, NW_ = 8; (void)R_; (void)R2_; KERNEL_CALL; } break; \
     }
-
-// Per-kernel timing: while a kernel class is being profiled, its next launch carries a start and
-// a stop event ON THE DISPATCH ITSELF (hipExtLaunchKernelGGL), so the interval is the kernel's own
-// begin..end as rocprofv3 sees it -- separate event records around the launch add ~3 us.
-struct KTimer {
-    rama_ctx* c; bool on;
-    KTimer(rama_ctx* c_, int kid) : c(c_), on(false) {
-        KProf& k = c->kp;
-        if (k.kernel_id == kid && k.used < k.max_records) {
-            on = true;
-            c->cur_start = k.ev[2 * k.used]; c->cur_stop = k.ev[2 * k.used + 1];
-        }
-    }
-    ~KTimer() {
-        if (on) { c->kp.used++; c->cur_start = c->cur_stop = nullptr; }
-    }
-};
-// launch on the context's stream; the first launch inside an armed KTimer scope takes the events
-#define RAMA_LAUNCH(c, kernel, grid, block, shm, ...)                                                          \
-    do {                                                                                                        \
-        if ((c)->cur_start) {                                                                                   \
-            hipExtLaunchKernelGGL(kernel, grid, block, shm, (c)->stream, (c)->cur_start, (c)->cur_stop, 0, __VA_ARGS__); \
-            (c)->cur_start = nullptr;                                                                           \
-        } else {                                                                                                \
-            hipLaunchKernelGGL(kernel, grid, block, shm, (c)->stream, __VA_ARGS__);                             \
-        }                                                                                                       \
-    } while (0)
 
 // the pending run of apply_position calls (rama_ctx::rope) as one launch: `count` consecutive heads are one vector of count x head_size floats
 static int flush_rope(rama_ctx* c) {
@@ -762,13 +411,13 @@ static int launch_matvec_ref1(rama_ctx* c, float* o, const float* W, const float
     const float* const ww[3] = {W, nullptr, nullptr};
     return launch_matvec_ref(c, 1, oo, ww, x, K, rows);
 }
-static int launch_rmsnorm_ref(rama_ctx* c, float* o, const float* x, const float* w, int n) {
+int launch_rmsnorm_ref(rama_ctx* c, float* o, const float* x, const float* w, int n) {
     REQUIRE((size_t)n * sizeof(float) <= 64 * 1024, RAMA_EUNSUP, "rmsnorm (reference order): vector longer than 16384");
     hipLaunchKernelGGL(rmsnorm_ref_kernel, dim3(1), dim3(1024), (size_t)n * sizeof(float), c->stream, o, x, w, n);
     LAUNCHCHK();
     return 0;
 }
-static int launch_attention_ref(rama_ctx* c, float* xb, float* att, const float* q, const float* kc_layer, const float* vc_layer,
+int launch_attention_ref(rama_ctx* c, float* xb, float* att, const float* q, const float* kc_layer, const float* vc_layer,
                                 const Ctl* ctl, int pos, int dim, int head_size, int seq_len, int n_heads) {
     REQUIRE((size_t)seq_len * sizeof(float) <= 64 * 1024, RAMA_EUNSUP, "attention (reference order): seq_len longer than 16384");
     RefAttnParams p{};
@@ -869,8 +518,8 @@ static int launch_chain(rama_ctx* c, ChainParams& p, int norm = CNORM_NONE) {
     return 0;
 }
 // the pending run of parity-mode matmuls (rama_ctx::mm) as one chain-order launch
-static bool rmsnorm_chain_ok(size_t n) { return n <= (size_t)kNormMax && (n + (n >> 5) + 2) * sizeof(float) <= 64 * 1024; }
-static int launch_rmsnorm_chain(rama_ctx* c, float* o, const float* x, const float* w, int n, float* copy_to, int batch = 1, int stride = 0) {
+bool rmsnorm_chain_ok(size_t n) { return n <= (size_t)kNormMax && (n + (n >> 5) + 2) * sizeof(float) <= 64 * 1024; }
+int launch_rmsnorm_chain(rama_ctx* c, float* o, const float* x, const float* w, int n, float* copy_to, int batch, int stride) {
     const size_t lds = ((size_t)n + ((size_t)n >> 5) + 2) * sizeof(float);
     RAMA_LAUNCH(c, rmsnorm_chain_kernel, dim3(batch), dim3(kNormThreads), lds, o, x, w, n, copy_to, stride);
     LAUNCHCHK();
@@ -904,13 +553,14 @@ static int flush_mm(rama_ctx* c) {
     }
     return launch_chain<CEPI_STORE>(c, p);
 }
-static int attn_chain_waves(int head_size, bool long_ctx) {
+size_t attn_chain_lds_bytes(int head_size, int seq_len, int nw) { return attn_chain_lds_floats(head_size, seq_len, nw) * sizeof(float) + 16; }
+int attn_chain_waves(int head_size, bool long_ctx) {
     const int want = long_ctx ? 8 : 4;
     return attn_chain_fits(head_size, want) ? want : (attn_chain_fits(head_size, 8) ? 8 : 16);
 }
-static bool attn_chain_ok(int head_size, int seq_len) {      // the largest variant a launch may pick must fit
+bool attn_chain_ok(int head_size, int seq_len) {      // the largest variant a launch may pick must fit
     if (head_size % 4 || !attn_chain_fits(head_size, 16)) return false;
-    return attn_chain_lds_floats(head_size, seq_len, attn_chain_waves(head_size, true)) * sizeof(float) + 16 <= kAttnChainMaxLds;
+    return attn_chain_lds_bytes(head_size, seq_len, attn_chain_waves(head_size, true)) <= kAttnChainMaxLds;
 }
 // the score scratch of parity mode's spread attention; inside a stream capture nothing is allocated (the caller then keeps
 // the three-launch form, whose softmax rewrites each head's row from ONE workgroup)
@@ -926,8 +576,8 @@ static int ensure_attn_scores(rama_ctx* c, int n_heads, int seq_len) {
 }
 
 // long_ctx: 8 waves per head (twice the timesteps per score round, twice the loaders of the value tiles) -- from position 256 on
-static int launch_attention_chain(rama_ctx* c, float* xb, float* att, const float* q, const float* kc_layer, const float* vc_layer,
-                                  const Ctl* ctl, int pos, int dim, int head_size, int seq_len, int n_heads, bool long_ctx = false, bool spread_wanted = false) {
+int launch_attention_chain(rama_ctx* c, float* xb, float* att, const float* q, const float* kc_layer, const float* vc_layer,
+                                  const Ctl* ctl, int pos, int dim, int head_size, int seq_len, int n_heads, bool long_ctx, bool spread_wanted) {
     // spread: the three-launch form for long contexts; it needs whole staged pieces and 32-column slices, a score
     // buffer that fits the softmax kernel's LDS, and the att buffer
     const bool spread = spread_wanted && att && head_size % kAttPiece == 0 && head_size % kValCols == 0 && head_size <= 256 &&
@@ -968,7 +618,7 @@ static int launch_attention_chain(rama_ctx* c, float* xb, float* att, const floa
         return 0;
     }
     const int nw = attn_chain_waves(head_size, long_ctx);
-    const size_t lds = attn_chain_lds_floats(head_size, seq_len, nw) * sizeof(float) + 16;
+    const size_t lds = attn_chain_lds_bytes(head_size, seq_len, nw);
     REQUIRE(lds <= kAttnChainMaxLds, RAMA_EUNSUP, "attention (parity mode): context too long for the score buffer");
 #define RAMA_ATTN_CHAIN(NW_) RAMA_LAUNCH(c, (attention_chain_kernel<NW_>), dim3(n_heads), dim3(NW_ * 64), lds, p)
     if (nw == 4) RAMA_ATTN_CHAIN(4);
@@ -981,7 +631,6 @@ static int launch_attention_chain(rama_ctx* c, float* xb, float* att, const floa
 
 // ---------------------------------------------------------------- Device<T> ops, 1:1
 
-static inline bool ranges_overlap(const float* p0, size_t n0, const float* p1, size_t n1) { return p0 < p1 + n1 && p1 < p0 + n0; }
 int rama_array_add(rama_ctx* c, float* t, const float* s, size_t n) {
     REQUIRE(c && (n == 0 || (t && s)), RAMA_EINVAL, "array_add: NULL argument");
     RAMA_WRITES(c, t, n);
@@ -1400,7 +1049,7 @@ int rama_fill_synth(rama_ctx* c, float* dst, size_t n, uint64_t seed, uint64_t t
 
 // ---------------------------------------------------------------- fused decode path
 
-static int check_cfg(const rama_config* cfg) {
+int check_cfg(const rama_config* cfg) {
     REQUIRE(cfg, RAMA_EINVAL, "config is NULL");
     REQUIRE(cfg->dim > 0 && cfg->hidden_dim > 0 && cfg->n_layers > 0 && cfg->n_heads > 0 && cfg->vocab_size > 0 && cfg->seq_len > 0, RAMA_EINVAL, "config: non-positive field");
     REQUIRE(cfg->n_kv_heads == cfg->n_heads, RAMA_EUNSUP, "config: n_kv_heads != n_heads (the reference indexes the cache with stride dim, infer.rs:31-33)");
@@ -1909,7 +1558,7 @@ extern "C" int rama_internal_topp_dist_bad(rama_ctx* c, unsigned* bad) {
 }
 
 // scratch for n logits; called outside any stream capture
-static int ensure_topp_scratch(rama_ctx* c, int n) {
+int ensure_topp_scratch(rama_ctx* c, int n) {
     if (n <= c->topp_cap) return 0;
     if (set_device(c)) return 1;
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1937,7 +1586,7 @@ static int ensure_topp_scratch(rama_ctx* c, int n) {
 // the sampling tail of a step: argmax (temperature 0) or top-p, then whatever `fin` asks for
 // (result word, cursor advance, next embedding gather)
 static int enqueue_sample_launches(rama_ctx* c, ArgmaxParams fin, float temperature, float topp, float u);
-static int enqueue_sample(rama_ctx* c, ArgmaxParams fin, float temperature, float topp, float u) {
+int enqueue_sample(rama_ctx* c, ArgmaxParams fin, float temperature, float topp, float u) {
     // kernel class RAMA_K_SAMPLE: up to five launches, so the bracket is a pair of event records around them (eager mode only)
     KProf& k = c->kp;
     const bool timed = k.kernel_id == RAMA_K_SAMPLE && k.used < k.max_records;
@@ -2023,11 +1672,11 @@ int rama_sample_topp_dev(rama_ctx* c, const float* logits, size_t n, float tempe
 
 // ---- the batched top-p sampler: many rows per launch (topp_sort.hpp ROWS kernels), the parallelism from the rows -- no waits between
 // workgroups (topp_pick_dist_kernel's hand-offs need all its workgroups resident: not at 128 rows), the pick one workgroup per row
-static bool topp_params_ok(float temperature, float topp, float u) {
+bool topp_params_ok(float temperature, float topp, float u) {
     return temperature >= 0.0f && topp >= 0.0f && topp <= 1.0f && u >= 0.0f && u < 1.0f;      // (false for NaN)
 }
 // slices for `rows` rows of n <= 32768 logits; called outside any stream capture
-static int ensure_topp_batch(rama_ctx* c, int rows, int n) {
+int ensure_topp_batch(rama_ctx* c, int rows, int n) {
     auto& t = c->tb;
     size_t rs = ((size_t)n + kToppBlock - 1) / kToppBlock * kToppBlock;      // >= n and >= the blocks' slots of either block size
     if (rows <= t.rows && rs <= t.rstride) return 0;
@@ -2059,7 +1708,7 @@ __global__ void topp_rows_kernel(ToppRowsArg a, ToppRow* rows, int n_rows) {
 // sorts and the ranking are the single-row sampler's launches for the same n (enqueue_sample_launches at the default tuning), so every
 // sampled row gets its bits; the running sums are topp_pick_scan_kernel's, one workgroup per row.
 // (its ordering launches -- everything but the pick -- are enqueue_topp_batch_order: the serving chain ends its step in a pick of its own)
-static int enqueue_topp_batch_order(rama_ctx* c, const ToppRow* rows, int n_rows, const float* logits, size_t ld, int n, const SeqSlot* seqs) {
+int enqueue_topp_batch_order(rama_ctx* c, const ToppRow* rows, int n_rows, const float* logits, size_t ld, int n, const SeqSlot* seqs) {
     auto& t = c->tb;
     REQUIRE(n > 1 && n <= kToppBlock * kToppMaxBlocks && n_rows <= t.rows && (size_t)n <= t.rstride, RAMA_EINVAL, "top-p batch sampler: scratch not prepared");
     ToppSortParams sp{};
@@ -2089,7 +1738,7 @@ static int enqueue_topp_batch_order(rama_ctx* c, const ToppRow* rows, int n_rows
     }
     return 0;
 }
-static int enqueue_topp_batch(rama_ctx* c, const ToppRow* rows, int n_rows, const float* logits, size_t ld, int n, ToppBatchParams fin) {
+int enqueue_topp_batch(rama_ctx* c, const ToppRow* rows, int n_rows, const float* logits, size_t ld, int n, ToppBatchParams fin) {
     auto& t = c->tb;
     { const int rc = enqueue_topp_batch_order(c, rows, n_rows, logits, ld, n, fin.seqs); if (rc) return rc; }
     fin.rows = rows; fin.logits = logits; fin.ld = ld; fin.n = n;
@@ -2193,8 +1842,7 @@ static int launch_mf(rama_ctx* c, MfParams& p, int pt) {
 // n token ids -- and, with seqs_dev, the sequence table of n independent sequences: cache bases and position of each, nothing produced yet --
 // to the device through the context's pinned staging buffer: the caller's arrays may be gone before the copies run.  Synchronises first,
 // after which the pinned buffer is free again.
-static int stage_tokens(rama_ctx* c, int* toks_dev, const int32_t* tokens_host, int n, SeqSlot* seqs_dev = nullptr,
-                        const rama_run_state* states = nullptr, const int32_t* pos_host = nullptr) {
+int stage_tokens(rama_ctx* c, int* toks_dev, const int32_t* tokens_host, int n, SeqSlot* seqs_dev, const rama_run_state* states, const int32_t* pos_host) {
     REQUIRE(n >= 1 && n <= kMfMaxTok, RAMA_EINVAL, "token batch: more tokens than the staging buffer holds");
     HIPCHK(hipStreamSynchronize(c->stream));
     memcpy(c->pinned_tok, tokens_host, sizeof(int) * n);
@@ -2207,7 +1855,7 @@ static int stage_tokens(rama_ctx* c, int* toks_dev, const int32_t* tokens_host, 
 }
 
 // row i of the logits slab lg [n, V] to sequence i's run state
-static int copy_out_logits(rama_ctx* c, const rama_run_state* states, const float* lg, int n, int V) {
+int copy_out_logits(rama_ctx* c, const rama_run_state* states, const float* lg, int n, int V) {
     for (int i = 0; i < n; i++)
         HIPCHK(hipMemcpyAsync(states[i].logits, lg + (size_t)i * V, sizeof(float) * V, hipMemcpyDeviceToDevice, c->stream));
     return 0;
@@ -2393,7 +2041,7 @@ constexpr int kGcMaxTok = 8 * kGcWaves;
 
 // parity mode's exact attention for a token batch: one workgroup of nw waves per (head, token) -- the RefAttnParams carry
 // tok_stride / att_stride and either p.pos_val + token or the sequence table
-static int launch_attention_chain_tokens(rama_ctx* c, const RefAttnParams& a, int n_heads, int nt, int nw, size_t lds) {
+int launch_attention_chain_tokens(rama_ctx* c, const RefAttnParams& a, int n_heads, int nt, int nw, size_t lds) {
     const dim3 grid(n_heads, nt);
     if (nw == 4) hipLaunchKernelGGL((attention_chain_kernel<4>), grid, dim3(4 * 64), lds, c->stream, a);
     else if (nw == 8) hipLaunchKernelGGL((attention_chain_kernel<8>), grid, dim3(8 * 64), lds, c->stream, a);
@@ -2482,7 +2130,7 @@ static int chain_batch_setup(rama_ctx* c, const rama_config* cfg, const rama_wei
     out->LG = reinterpret_cast<float*>(out->toks + 64) + slot_floats + 4 - ((slot_floats) & 3);      // 16-byte aligned
     out->ccls = ccls;
     const int nw = attn_chain_waves(hs, false);
-    const size_t att_lds = attn_chain_lds_floats(hs, seq, nw) * sizeof(float) + 16;
+    const size_t att_lds = attn_chain_lds_bytes(hs, seq, nw);
     REQUIRE(att_lds <= kAttnChainMaxLds, RAMA_EUNSUP, "token batch (parity mode): context too long for the score buffer");
     out->b = ChainBatch{X, XN, Q, XB, HB, ATT, cq, ck, cv, co, c13, c2, nw, att_lds};
     *ok = true;
@@ -2810,14 +2458,7 @@ int rama_decode_batch_stream_poll(rama_ctx* c, int seq, int from, int32_t* out_h
     RAMA_ENTER(c);
     REQUIRE(c && n_ready && c->bc.n_seq > 0 && c->bc.ring && seq >= 0 && seq < c->bc.n_seq && from >= 0 && max_tokens >= 0 && (max_tokens == 0 || out_host),
             RAMA_EINVAL, "decode_batch_stream_poll: bad argument");
-    const int* row = c->bc.ring + (size_t)seq * c->bc.out_cap;
-    int n = 0;
-    while (n < max_tokens && from + n < c->bc.out_cap) {
-        const int v = __atomic_load_n(row + from + n, __ATOMIC_ACQUIRE);
-        if (v == 0) break;
-        out_host[n++] = v - 1;
-    }
-    *n_ready = n;
+    *n_ready = read_ring(c->bc.ring + (size_t)seq * c->bc.out_cap, c->bc.out_cap, from, out_host, max_tokens);
     return 0;
 }
 
@@ -2933,13 +2574,7 @@ int rama_decode_steps(rama_ctx* c, const rama_config* cfg, const rama_weights* w
 int rama_decode_stream_poll(rama_ctx* c, int from, int32_t* out_host, int max_tokens, int* n_ready) {
     RAMA_ENTER(c);
     REQUIRE(c && n_ready && from >= 0 && max_tokens >= 0 && (max_tokens == 0 || out_host), RAMA_EINVAL, "decode_stream_poll: bad argument");
-    int n = 0;
-    while (n < max_tokens && from + n < c->out_cap) {
-        const int v = __atomic_load_n(c->ring + from + n, __ATOMIC_ACQUIRE);
-        if (v == 0) break;
-        out_host[n++] = v - 1;
-    }
-    *n_ready = n;
+    *n_ready = read_ring(c->ring, c->out_cap, from, out_host, max_tokens);
     return 0;
 }
 
@@ -3273,1017 +2908,4 @@ int rama_state_free(rama_ctx* c, rama_run_state* s) {
     int rc = rama_free(c, s->x);   // x is the blob base
     memset(s, 0, sizeof *s);
     return rc;
-}
-
-// ---------------------------------------------------------------- Q8_0 models (q8.hpp, q8_model.hip)
-// The forward of a version-2 checkpoint: parity mode's exact norms, RoPE + cache append, attention, SiLU and residual adds,
-// with every matmul replaced by runq.c's quantized product (rama_hip.h).  Per layer: norm, quantize,
-// Wq|Wk|Wv, RoPE + cache rows, attention, quantize, Wo (+ residual), norm, quantize, W1|W3 (+ SiLU * gate), quantize, W2 (+ residual).
-
-static int launch_q8_quantize(rama_ctx* c, const float* x, int n, int gs, int8_t* q, float* s) {
-    const int groups = n / gs;
-    RAMA_LAUNCH(c, q8_quantize_kernel, dim3((groups + 3) / 4), dim3(256), 0, x, n, gs, q, s);
-    LAUNCHCHK();
-    return 0;
-}
-
-template <int EPI>
-static int launch_q8_matvec(rama_ctx* c, Q8MatParams& p) {
-    const int G = p.K / p.gs, nm = EPI == Q8EPI_SWIGLU ? 2 : p.nmat;
-    bool fast = q8_matvec_fast_ok(p.K, p.gs) && (size_t)kQ8Waves * 2 * G * sizeof(float) <= 64 * 1024 && aligned16(p.xq);
-    for (int m = 0; m < nm; m++) fast = fast && aligned16(p.w[m]);
-    if (fast) {
-        const int tasks = EPI == Q8EPI_SWIGLU ? p.rows : (p.nmat * p.rows + 1) / 2;
-        const size_t lds = (size_t)kQ8Waves * 2 * G * sizeof(float);
-        RAMA_LAUNCH(c, (q8_matvec_kernel<2, EPI>), dim3((tasks + kQ8Waves - 1) / kQ8Waves), dim3(kQ8Waves * 64), lds, p);
-    } else {
-        const int total = EPI == Q8EPI_SWIGLU ? p.rows : p.nmat * p.rows;
-        RAMA_LAUNCH(c, (q8_matvec_generic_kernel<EPI>), dim3((total + 255) / 256), dim3(256), 0, p);
-    }
-    LAUNCHCHK();
-    return 0;
-}
-
-int rama_q8_quantize(rama_ctx* c, const float* x, size_t n, int group_size, int8_t* q, float* s) {
-    RAMA_ENTER(c);
-    REQUIRE(c && x && q && s, RAMA_EINVAL, "q8_quantize: NULL argument");
-    REQUIRE(group_size > 0 && n > 0 && n % (size_t)group_size == 0 && n < ((size_t)1 << 31), RAMA_EINVAL, "q8_quantize: group_size must divide n");
-    if (set_device(c)) return 1;
-    RAMA_WRITES(c, s, n / group_size);
-    return launch_q8_quantize(c, x, (int)n, group_size, q, s);
-}
-
-int rama_q8_matmul(rama_ctx* c, float* o, const int8_t* wq, const float* ws, const int8_t* xq, const float* xs, size_t n, size_t d, int group_size) {
-    RAMA_ENTER(c);
-    REQUIRE(c && o && wq && ws && xq && xs, RAMA_EINVAL, "q8_matmul: NULL argument");
-    REQUIRE(group_size > 0 && n > 0 && d > 0 && n % (size_t)group_size == 0 && n < ((size_t)1 << 31) && d < ((size_t)1 << 31), RAMA_EINVAL,
-            "q8_matmul: group_size must divide n");
-    if (set_device(c)) return 1;
-    RAMA_WRITES(c, o, d);
-    Q8MatParams p{};
-    p.w[0] = wq; p.ws[0] = ws; p.o[0] = o; p.xq = xq; p.xs = xs; p.K = (int)n; p.rows = (int)d; p.gs = group_size; p.nmat = 1;
-    return launch_q8_matvec<Q8EPI_STORE>(c, p);
-}
-
-static int q8_check(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const rama_run_state* s) {
-    REQUIRE(c, RAMA_EINVAL, "ctx is NULL");
-    int rc = check_cfg(cfg); if (rc) return rc;
-    REQUIRE(w && s, RAMA_EINVAL, "q8 forward: NULL argument");
-    const int gs = w->group_size;
-    REQUIRE(gs > 0 && cfg->dim % gs == 0 && cfg->hidden_dim % gs == 0, RAMA_EINVAL, "q8 forward: group_size must divide dim and hidden_dim");
-    REQUIRE(w->token_embedding_table && w->rms_att_weight && w->rms_ffn_weight && w->rms_final_weight && w->freq_cis_real && w->freq_cis_imag &&
-            w->wq && w->wk && w->wv && w->wo && w->w1 && w->w2 && w->w3 && w->wcls && w->wq_s && w->wk_s && w->wv_s && w->wo_s && w->w1_s &&
-            w->w2_s && w->w3_s && w->wcls_s, RAMA_EINVAL, "q8 forward: missing weights");
-    REQUIRE(s->x && s->xb && s->hb && s->q && s->k && s->v && s->att && s->logits && s->key_cache && s->value_cache, RAMA_EINVAL,
-            "q8 forward: missing state buffer");
-    return 0;
-}
-
-// the int8 activations: one buffer of max(dim, hidden) values and as many scales (sized here, never inside a capture)
-static int ensure_q8_scratch(rama_ctx* c, const rama_config* cfg) {
-    const size_t need = (size_t)std::max(cfg->dim, cfg->hidden_dim);
-    if (need <= c->q8_cap) return 0;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    REQUIRE(hipStreamIsCapturing(c->stream, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone, RAMA_EINVAL,
-            "q8: the activation scratch is sized by the first call, which must not be captured");
-    HIPCHK(hipStreamSynchronize(c->stream));
-    drop_q8_graphs(c, nullptr);        // (they hold the scratch's addresses; nothing else reads it)
-    if (c->q8_xq) { HIPCHK(hipFree(c->q8_xq)); c->q8_xq = nullptr; }
-    if (c->q8_xs) { HIPCHK(hipFree(c->q8_xs)); c->q8_xs = nullptr; }
-    c->q8_cap = 0;
-    HIPCHK(hipMalloc(&c->q8_xq, (need + 15) / 16 * 16));
-    HIPCHK(hipMalloc(&c->q8_xs, need * sizeof(float)));
-    c->q8_cap = need;
-    return 0;
-}
-
-// the attention variant of a Q8 step: parity mode's exact attention, 16 waves per head from position 256, spread over the chip from "spread_pos"
-static int q8_variant(rama_ctx* c, int pos) {
-    c->long_attn = pos >= kLongAttnPos;
-    c->spread_attn = pos >= c->tune_spread_pos;
-    return c->spread_attn ? 2 : (c->long_attn ? 1 : 0);
-}
-
-static int q8_norm(rama_ctx* c, float* o, float* x, const float* gain, int n, float* copy_to) {
-    KTimer kt(c, RAMA_K_NORM);
-    if (rmsnorm_chain_ok(n)) return launch_rmsnorm_chain(c, o, x, gain, n, copy_to);
-    if (copy_to) {      // xb = x; x = rmsnorm(xb) (infer.rs:49-50)
-        hipLaunchKernelGGL(copy_kernel, dim3(ew_grid(n)), dim3(256), 0, c->stream, copy_to, (const float*)x, (size_t)n);
-        LAUNCHCHK();
-        return launch_rmsnorm_ref(c, o, copy_to, gain, n);
-    }
-    return launch_rmsnorm_ref(c, o, x, gain, n);
-}
-
-// one forward (token and position in the device cursor); embed = 0: x already holds the token's embedding (chained decode)
-static int enqueue_q8_stage(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, rama_run_state* s, bool embed) {
-    const int dim = cfg->dim, hidden = cfg->hidden_dim, hs = dim / cfg->n_heads, gs = w->group_size;
-    const size_t dd = (size_t)dim * dim, hd = (size_t)hidden * dim;
-    int8_t* xq = c->q8_xq; float* xs = c->q8_xs;
-    int rc;
-    if (embed) {
-        hipLaunchKernelGGL(embed_kernel, dim3((dim + 255) / 256), dim3(256), 0, c->stream, s->x, w->token_embedding_table, (const Ctl*)c->ctl, 0, dim);
-        LAUNCHCHK();
-    }
-    for (int l = 0; l < cfg->n_layers; l++) {
-        float* kc = s->key_cache + (size_t)l * cfg->seq_len * dim;
-        float* vc = s->value_cache + (size_t)l * cfg->seq_len * dim;
-        rc = q8_norm(c, s->xb, s->x, w->rms_att_weight + (size_t)l * dim, dim, nullptr); if (rc) return rc;          // infer.rs:19
-        rc = launch_q8_quantize(c, s->xb, dim, gs, xq, xs); if (rc) return rc;
-        {   // :20-23
-            KTimer kt(c, RAMA_K_QKV);
-            Q8MatParams p{};
-            p.w[0] = w->wq + l * dd; p.w[1] = w->wk + l * dd; p.w[2] = w->wv + l * dd;
-            p.ws[0] = w->wq_s + l * dd / gs; p.ws[1] = w->wk_s + l * dd / gs; p.ws[2] = w->wv_s + l * dd / gs;
-            p.o[0] = s->q; p.o[1] = s->k; p.o[2] = s->v;
-            p.xq = xq; p.xs = xs; p.K = dim; p.rows = dim; p.gs = gs; p.nmat = 3;
-            rc = launch_q8_matvec<Q8EPI_STORE>(c, p); if (rc) return rc;
-        }
-        hipLaunchKernelGGL(rope_ref_cursor_kernel, dim3((dim / 2 + 255) / 256), dim3(256), 0, c->stream, s->q, s->k, (const float*)s->v,
-                           w->freq_cis_real, w->freq_cis_imag, dim, hs, kc, vc, (const Ctl*)c->ctl);                  // :25-33
-        LAUNCHCHK();
-        {   // :34
-            KTimer kt(c, RAMA_K_ATTN);
-            if (attn_chain_ok(hs, cfg->seq_len))
-                rc = launch_attention_chain(c, s->xb, s->att, s->q, kc, vc, c->ctl, 0, dim, hs, cfg->seq_len, cfg->n_heads, c->long_attn, c->spread_attn);
-            else rc = launch_attention_ref(c, s->xb, s->att, s->q, kc, vc, c->ctl, 0, dim, hs, cfg->seq_len, cfg->n_heads);
-            if (rc) return rc;
-        }
-        rc = launch_q8_quantize(c, s->xb, dim, gs, xq, xs); if (rc) return rc;
-        {   // :35-37: x = x + Wo . xb
-            KTimer kt(c, RAMA_K_WO);
-            Q8MatParams p{};
-            p.w[0] = w->wo + l * dd; p.ws[0] = w->wo_s + l * dd / gs; p.o[0] = s->x;
-            p.xq = xq; p.xs = xs; p.K = dim; p.rows = dim; p.gs = gs; p.nmat = 1;
-            rc = launch_q8_matvec<Q8EPI_RESID>(c, p); if (rc) return rc;
-        }
-        rc = q8_norm(c, s->xb, s->x, w->rms_ffn_weight + (size_t)l * dim, dim, nullptr); if (rc) return rc;          // :39
-        rc = launch_q8_quantize(c, s->xb, dim, gs, xq, xs); if (rc) return rc;
-        {   // :41-45: hb = sinu(W1 . xb) * (W3 . xb)
-            KTimer kt(c, RAMA_K_W13);
-            Q8MatParams p{};
-            p.w[0] = w->w1 + l * hd; p.w[1] = w->w3 + l * hd; p.ws[0] = w->w1_s + l * hd / gs; p.ws[1] = w->w3_s + l * hd / gs;
-            p.o[0] = s->hb; p.xq = xq; p.xs = xs; p.K = dim; p.rows = hidden; p.gs = gs; p.nmat = 2;
-            rc = launch_q8_matvec<Q8EPI_SWIGLU>(c, p); if (rc) return rc;
-        }
-        rc = launch_q8_quantize(c, s->hb, hidden, gs, xq, xs); if (rc) return rc;
-        {   // :46-47: x = x + W2 . hb
-            KTimer kt(c, RAMA_K_W2);
-            Q8MatParams p{};
-            p.w[0] = w->w2 + l * hd; p.ws[0] = w->w2_s + l * hd / gs; p.o[0] = s->x;
-            p.xq = xq; p.xs = xs; p.K = hidden; p.rows = dim; p.gs = gs; p.nmat = 1;
-            rc = launch_q8_matvec<Q8EPI_RESID>(c, p); if (rc) return rc;
-        }
-    }
-    // :49-51: xb = x; x = rmsnorm(xb); logits = Wcls . x
-    rc = q8_norm(c, s->x, s->x, w->rms_final_weight, dim, s->xb); if (rc) return rc;
-    rc = launch_q8_quantize(c, s->x, dim, gs, xq, xs); if (rc) return rc;
-    KTimer kt(c, RAMA_K_CLS);
-    Q8MatParams p{};
-    p.w[0] = w->wcls; p.ws[0] = w->wcls_s; p.o[0] = s->logits;
-    p.xq = xq; p.xs = xs; p.K = dim; p.rows = cfg->vocab_size; p.gs = gs; p.nmat = 1;
-    return launch_q8_matvec<Q8EPI_STORE>(c, p);
-}
-
-// a chained step: the layers, then Device::sample (cursor advance, next token's embedding gather from the fp32 table)
-static int enqueue_q8_step(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, rama_run_state* s) {
-    int rc = enqueue_q8_stage(c, cfg, w, s, false);
-    if (rc) return rc;
-    ArgmaxParams ap{};
-    ap.logits = s->logits; ap.n = cfg->vocab_size;
-    ap.ctl = c->ctl; ap.forced = c->forced; ap.out = c->out; ap.out_cap = c->out_cap; ap.ring = c->ring_dev;
-    ap.emb = w->token_embedding_table; ap.x = s->x; ap.dim = cfg->dim;
-    return enqueue_sample(c, ap, c->samp_T, c->samp_topp, c->samp_u);
-}
-
-// eager, or replayed from the context's Q8 graph for (config, weights, state, attention variant, kind)
-static int run_q8(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, rama_run_state* s, int variant, int chained) {
-    auto enqueue = [&]() { return chained ? enqueue_q8_step(c, cfg, w, s) : enqueue_q8_stage(c, cfg, w, s, true); };
-    if (!c->graph_mode || c->kp.kernel_id >= 0) return enqueue();
-    rama_ctx::Q8Graph* hit = nullptr;
-    for (auto& e : c->q8g)
-        if (e.variant == variant && e.chained == chained && !memcmp(&e.cfg, cfg, sizeof *cfg) && !memcmp(&e.w, w, sizeof *w) && !memcmp(&e.s, s, sizeof *s)) { hit = &e; break; }
-    if (!hit) {
-        if (c->q8g.size() >= 16) {
-            HIPCHK(hipStreamSynchronize(c->stream));
-            for (auto& e : c->q8g) destroy_graph(e.cg);
-            c->q8g.clear();
-        }
-        rama_ctx::Q8Graph e;
-        const int rc = capture_graph(c, e.cg, enqueue);
-        if (rc) return rc;
-        e.cfg = *cfg; e.w = *w; e.s = *s; e.variant = variant; e.chained = chained;
-        c->q8g.push_back(e);
-        hit = &c->q8g.back();
-    }
-    return replay_graph(c, hit->cg);
-}
-
-int rama_q8_forward(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, rama_run_state* s, int token, int pos) {
-    RAMA_ENTER(c);
-    int rc = q8_check(c, cfg, w, s); if (rc) return rc;
-    if (set_device(c)) return 1;
-    REQUIRE(pos >= 0 && pos < cfg->seq_len, RAMA_EINVAL, "q8_forward: pos outside [0, seq_len)");
-    REQUIRE(token >= 0 && token < cfg->vocab_size, RAMA_EINVAL, "q8_forward: token outside the vocabulary");
-    rc = ensure_q8_scratch(c, cfg); if (rc) return rc;
-    hipLaunchKernelGGL(set_ctl_kernel, dim3(1), dim3(1), 0, c->stream, c->ctl, token, pos, 0, 0);
-    LAUNCHCHK();
-    c->embedded_x = nullptr;
-    c->host_pos = -1;
-    return run_q8(c, cfg, w, s, q8_variant(c, pos), 0);
-}
-
-int rama_q8_generate(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, rama_run_state* s, const int32_t* prompt_host, int n_prompt,
-                     int steps, float temperature, float topp, float u, int32_t* out_host) {
-    RAMA_ENTER(c);
-    int rc = q8_check(c, cfg, w, s); if (rc) return rc;
-    REQUIRE(out_host, RAMA_EINVAL, "q8_generate: NULL argument");
-    if (set_device(c)) return 1;
-    rc = rama_decode_sampler(c, temperature, topp, u); if (rc) return rc;
-    REQUIRE(steps >= 0 && steps <= cfg->seq_len && steps <= c->out_cap, RAMA_EINVAL, "q8_generate: steps outside [0, seq_len]");
-    REQUIRE(n_prompt >= 0 && (n_prompt == 0 || prompt_host) && n_prompt <= c->forced_cap, RAMA_EINVAL, "q8_generate: bad prompt");
-    for (int i = 0; i < n_prompt; i++) REQUIRE(prompt_host[i] >= 0 && prompt_host[i] < cfg->vocab_size, RAMA_EINVAL, "q8_generate: prompt token outside the vocabulary");
-    rc = ensure_q8_scratch(c, cfg); if (rc) return rc;
-    if (c->samp_T != 0.0f) { rc = ensure_topp_scratch(c, cfg->vocab_size); if (rc) return rc; c->topp_dist_dirty = true; }
-    rc = rama_decode_begin(c, /*BOS*/ 1, 0, prompt_host, n_prompt); if (rc) return rc;
-    if (steps == 0) { int n = 0; return rama_decode_tokens(c, out_host, 0, &n); }
-    hipLaunchKernelGGL(embed_kernel, dim3((cfg->dim + 255) / 256), dim3(256), 0, c->stream, s->x, w->token_embedding_table, (const Ctl*)c->ctl, 0, cfg->dim);
-    LAUNCHCHK();
-    for (int i = 0; i < steps; i++) {
-        rc = run_q8(c, cfg, w, s, q8_variant(c, c->host_pos), 1);
-        if (rc) return rc;
-        c->host_pos++;
-    }
-    c->embedded_x = nullptr;
-    c->ring_hi = std::min(c->out_cap, c->ring_hi + steps);
-    int n = 0;
-    return rama_decode_tokens(c, out_host, steps, &n);
-}
-
-// ---------------------------------------------------------------- Q8_0 token batches (q8_batch.hpp)
-// rama_q8_prefill and rama_q8_decode_batch: enqueue_q8_stage over up to kQ8bMaxTok tokens per weight pass.  The batched exact
-// norm, the quantizer over T rows (a group never straddles a row), the batched product, RoPE + cache rows per token and parity
-// mode's attention on a (heads, tokens) grid: every token's bits are those of its own rama_q8_forward.
-
-template <int EPI>
-static int launch_q8_gemm(rama_ctx* c, const Q8BatchParams& p) {
-    const int nm = EPI == Q8EPI_SWIGLU ? 2 : p.nmat;
-    bool mf = q8_gemm_mfma_ok(p.K, p.gs) && aligned16(p.xq);
-    for (int m = 0; m < nm; m++) mf = mf && aligned16(p.w[m]);
-    const int G = p.K / p.gs;
-    const int total = EPI == Q8EPI_SWIGLU ? p.rows : p.nmat * p.rows;
-    const int tiles = (p.rows + 15) / 16, tasks = EPI == Q8EPI_SWIGLU ? tiles : p.nmat * tiles;
-    for (int t0 = 0; t0 < p.n_tok; t0 += kQ8bMaxTok) {
-        Q8BatchParams q = p;
-        q.n_tok = std::min(kQ8bMaxTok, p.n_tok - t0);
-        q.xq = p.xq + (size_t)t0 * p.K; q.xs = p.xs + (size_t)t0 * G;
-        for (int m = 0; m < 3; m++) if (q.o[m]) q.o[m] = p.o[m] + (size_t)t0 * p.ostride;
-        if (mf && q.n_tok <= 32 && (q.gs == 32 || q.gs == 64)) {      // few tokens: K split over the waves of a workgroup
-            constexpr int RT = EPI == Q8EPI_SWIGLU ? 2 : 1;
-#define RAMA_Q8S(NT_, G32_) RAMA_LAUNCH(c, (q8_gemm_ksplit_kernel<NT_, EPI, G32_>), dim3(tasks), dim3(kQ8sWaves * 64), q8s_lds_bytes(NT_, RT, G32_), q)
-            if (q.n_tok <= 16) { if (q.gs == 32) RAMA_Q8S(1, true); else RAMA_Q8S(1, false); }
-            else { if (q.gs == 32) RAMA_Q8S(2, true); else RAMA_Q8S(2, false); }
-#undef RAMA_Q8S
-        } else if (mf) {
-            const dim3 grid((tasks + kQ8bWaves - 1) / kQ8bWaves), block(kQ8bWaves * 64);
-#define RAMA_Q8G(NT_) do { if (q.gs == 32) RAMA_LAUNCH(c, (q8_gemm_mfma_kernel<NT_, EPI, true>), grid, block, 0, q); \
-                           else RAMA_LAUNCH(c, (q8_gemm_mfma_kernel<NT_, EPI, false>), grid, block, 0, q); } while (0)
-            if (q.n_tok <= 16) RAMA_Q8G(1);
-            else if (q.n_tok <= 32) RAMA_Q8G(2);
-            else if (q.n_tok <= 64) RAMA_Q8G(4);
-            else RAMA_Q8G(8);
-#undef RAMA_Q8G
-        } else {
-            RAMA_LAUNCH(c, (q8_gemm_generic_kernel<EPI>), dim3((total + 255) / 256, q.n_tok), dim3(256), 0, q);
-        }
-        LAUNCHCHK();
-    }
-    return 0;
-}
-
-int rama_q8_matmul_batch(rama_ctx* c, float* o, const int8_t* wq, const float* ws, const int8_t* xq, const float* xs, size_t n, size_t d,
-                         int group_size, int n_tok) {
-    RAMA_ENTER(c);
-    REQUIRE(c && o && wq && ws && xq && xs, RAMA_EINVAL, "q8_matmul_batch: NULL argument");
-    REQUIRE(group_size > 0 && n > 0 && d > 0 && n % (size_t)group_size == 0 && n < ((size_t)1 << 31) && d < ((size_t)1 << 31), RAMA_EINVAL,
-            "q8_matmul_batch: group_size must divide n");
-    REQUIRE(n_tok >= 1, RAMA_EINVAL, "q8_matmul_batch: n_tok < 1");
-    if (set_device(c)) return 1;
-    RAMA_WRITES(c, o, d * (size_t)n_tok);
-    Q8BatchParams p{};
-    p.w[0] = wq; p.ws[0] = ws; p.o[0] = o; p.xq = xq; p.xs = xs;
-    p.K = (int)n; p.rows = (int)d; p.gs = group_size; p.nmat = 1; p.n_tok = n_tok; p.ostride = (int)d;
-    return launch_q8_gemm<Q8EPI_STORE>(c, p);
-}
-
-// the batch path's scratch, row-major per token (T = kQ8bMaxTok): X residual rows, XN their norms, Q / Kr / V, XB attention
-// output, HB, ATT score rows [T][n_heads][seq_len], LG logits [T][vocab]; the int8 activations [T][max(dim, hidden)] and their
-// scales; token ids; the sequence table
-struct Q8BatchScratch { float *X, *XN, *Q, *Kr, *V, *XB, *HB, *ATT, *LG; int8_t* xq; float* xs; int* toks; SeqSlot* seqs; int nw; size_t att_lds; };
-
-// the shapes the batch path takes: those whose single-token forward runs parity mode's chain norm and chain attention
-static bool q8_batch_ok(const rama_config* cfg) {
-    const int hs = cfg->dim / cfg->n_heads;
-    if (!rmsnorm_chain_ok((size_t)cfg->dim) || !attn_chain_ok(hs, cfg->seq_len) || cfg->dim % 4) return false;
-    return attn_chain_lds_floats(hs, cfg->seq_len, attn_chain_waves(hs, false)) * sizeof(float) + 16 <= kAttnChainMaxLds;
-}
-
-static int ensure_q8_batch_scratch(rama_ctx* c, const rama_config* cfg, int gs, Q8BatchScratch* b) {
-    const size_t T = kQ8bMaxTok, dim = (size_t)cfg->dim, hidden = (size_t)cfg->hidden_dim, mx = std::max(dim, hidden);
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-    const size_t sz[13] = {T * dim * 4, T * dim * 4, T * dim * 4, T * dim * 4, T * dim * 4, T * dim * 4, T * hidden * 4,
-                           T * (size_t)cfg->n_heads * cfg->seq_len * 4, T * (size_t)cfg->vocab_size * 4, T * mx, T * (mx / gs) * 4, T * sizeof(int),
-                           T * sizeof(SeqSlot)};
-    size_t off[13], need = 0;
-    for (int i = 0; i < 13; i++) { off[i] = need; need += up(sz[i]); }
-    if (need > c->q8b_cap) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        REQUIRE(hipStreamIsCapturing(c->stream, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone, RAMA_EINVAL,
-                "q8 batch: the scratch is sized by the first call, which must not be captured");
-        HIPCHK(hipStreamSynchronize(c->stream));
-        destroy_graph(c->q8c.cg);          // (the chained batch's step holds the old scratch's addresses)
-        destroy_graph(c->q8s.cg);          // (and the serving chain's)
-        if (c->q8b_blob) { HIPCHK(hipFree(c->q8b_blob)); c->q8b_blob = nullptr; }
-        c->q8b_cap = 0;
-        HIPCHK(hipMalloc(&c->q8b_blob, need));
-        c->q8b_cap = need;
-    }
-    char* base = c->q8b_blob;
-    float** f[9] = {&b->X, &b->XN, &b->Q, &b->Kr, &b->V, &b->XB, &b->HB, &b->ATT, &b->LG};
-    for (int i = 0; i < 9; i++) *f[i] = reinterpret_cast<float*>(base + off[i]);
-    b->xq = reinterpret_cast<int8_t*>(base + off[9]);
-    b->xs = reinterpret_cast<float*>(base + off[10]);
-    b->toks = reinterpret_cast<int*>(base + off[11]);
-    b->seqs = reinterpret_cast<SeqSlot*>(base + off[12]);
-    const int hs = cfg->dim / cfg->n_heads;
-    b->nw = attn_chain_waves(hs, false);
-    b->att_lds = attn_chain_lds_floats(hs, cfg->seq_len, b->nw) * sizeof(float) + 16;
-    return 0;
-}
-
-// the layers for nt tokens whose embeddings sit in b.X: consecutive positions p0.. of one sequence (key_cache / value_cache
-// its caches), or -- seqs != NULL -- token t of independent sequence t (device table)
-static int q8_batch_layers(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const Q8BatchScratch& b, int nt, int p0,
-                           float* key_cache, float* value_cache, const SeqSlot* seqs) {
-    const int dim = cfg->dim, hidden = cfg->hidden_dim, hs = dim / cfg->n_heads, H = cfg->n_heads, seq = cfg->seq_len, gs = w->group_size;
-    const size_t dd = (size_t)dim * dim, hd = (size_t)hidden * dim;
-    int rc;
-    for (int l = 0; l < cfg->n_layers; l++) {
-        const size_t layer_off = (size_t)l * seq * dim;
-        float* kc = key_cache ? key_cache + layer_off : nullptr;
-        float* vc = value_cache ? value_cache + layer_off : nullptr;
-        rc = launch_rmsnorm_chain(c, b.XN, b.X, w->rms_att_weight + (size_t)l * dim, dim, nullptr, nt, dim); if (rc) return rc;    // infer.rs:19
-        rc = launch_q8_quantize(c, b.XN, nt * dim, gs, b.xq, b.xs); if (rc) return rc;
-        {   // :20-23
-            Q8BatchParams p{};
-            p.w[0] = w->wq + l * dd; p.w[1] = w->wk + l * dd; p.w[2] = w->wv + l * dd;
-            p.ws[0] = w->wq_s + l * dd / gs; p.ws[1] = w->wk_s + l * dd / gs; p.ws[2] = w->wv_s + l * dd / gs;
-            p.o[0] = b.Q; p.o[1] = b.Kr; p.o[2] = b.V;
-            p.xq = b.xq; p.xs = b.xs; p.K = dim; p.rows = dim; p.gs = gs; p.nmat = 3; p.n_tok = nt; p.ostride = dim;
-            rc = launch_q8_gemm<Q8EPI_STORE>(c, p); if (rc) return rc;
-        }
-        hipLaunchKernelGGL(q8_rope_batch_kernel, dim3((dim / 2 + 255) / 256, nt), dim3(256), 0, c->stream, b.Q, b.Kr, (const float*)b.V,
-                           w->freq_cis_real, w->freq_cis_imag, dim, hs, kc, vc, p0, seqs, layer_off);                    // :25-33
-        LAUNCHCHK();
-        {   // :34, one workgroup per (head, token)
-            RefAttnParams a{};
-            a.q = b.Q; a.kc = kc; a.vc = vc; a.att = b.ATT; a.xb = b.XB; a.ctl = nullptr; a.pos_val = p0;
-            a.dim = dim; a.head_size = hs; a.seq_len = seq; a.tok_stride = dim; a.att_stride = H * seq;
-            a.seqs = seqs; a.layer_off = layer_off;
-            rc = launch_attention_chain_tokens(c, a, H, nt, b.nw, b.att_lds); if (rc) return rc;
-        }
-        rc = launch_q8_quantize(c, b.XB, nt * dim, gs, b.xq, b.xs); if (rc) return rc;
-        {   // :35-37: x = x + Wo . xb
-            Q8BatchParams p{};
-            p.w[0] = w->wo + l * dd; p.ws[0] = w->wo_s + l * dd / gs; p.o[0] = b.X;
-            p.xq = b.xq; p.xs = b.xs; p.K = dim; p.rows = dim; p.gs = gs; p.nmat = 1; p.n_tok = nt; p.ostride = dim;
-            rc = launch_q8_gemm<Q8EPI_RESID>(c, p); if (rc) return rc;
-        }
-        rc = launch_rmsnorm_chain(c, b.XN, b.X, w->rms_ffn_weight + (size_t)l * dim, dim, nullptr, nt, dim); if (rc) return rc;    // :39
-        rc = launch_q8_quantize(c, b.XN, nt * dim, gs, b.xq, b.xs); if (rc) return rc;
-        {   // :41-45: hb = sinu(W1 . xb) * (W3 . xb)
-            Q8BatchParams p{};
-            p.w[0] = w->w1 + l * hd; p.w[1] = w->w3 + l * hd; p.ws[0] = w->w1_s + l * hd / gs; p.ws[1] = w->w3_s + l * hd / gs;
-            p.o[0] = b.HB; p.xq = b.xq; p.xs = b.xs; p.K = dim; p.rows = hidden; p.gs = gs; p.nmat = 2; p.n_tok = nt; p.ostride = hidden;
-            rc = launch_q8_gemm<Q8EPI_SWIGLU>(c, p); if (rc) return rc;
-        }
-        rc = launch_q8_quantize(c, b.HB, nt * hidden, gs, b.xq, b.xs); if (rc) return rc;
-        {   // :46-47: x = x + W2 . hb
-            Q8BatchParams p{};
-            p.w[0] = w->w2 + l * hd; p.ws[0] = w->w2_s + l * hd / gs; p.o[0] = b.X;
-            p.xq = b.xq; p.xs = b.xs; p.K = hidden; p.rows = dim; p.gs = gs; p.nmat = 1; p.n_tok = nt; p.ostride = dim;
-            rc = launch_q8_gemm<Q8EPI_RESID>(c, p); if (rc) return rc;
-        }
-    }
-    return 0;
-}
-
-int rama_q8_prefill(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, rama_run_state* s, const int32_t* tokens_host, int n_tokens, int pos0) {
-    RAMA_ENTER(c);
-    REQUIRE(c && tokens_host, RAMA_EINVAL, "q8_prefill: NULL argument");
-    int rc = q8_check(c, cfg, w, s); if (rc) return rc;
-    REQUIRE(n_tokens >= 1 && pos0 >= 0 && pos0 <= cfg->seq_len - n_tokens, RAMA_EINVAL, "q8_prefill: positions outside [0, seq_len)");
-    for (int i = 0; i < n_tokens; i++) REQUIRE(tokens_host[i] >= 0 && tokens_host[i] < cfg->vocab_size, RAMA_EINVAL, "q8_prefill: token outside the vocabulary");
-    if (set_device(c)) return 1;
-    rc = ensure_q8_scratch(c, cfg); if (rc) return rc;
-    // the last position runs as rama_q8_forward (x and logits); a batched pass of one token costs more than a forward (4.7 against
-    // 3.8 ms at llama2-7B), so batches start at two tokens
-    const int n_batch = q8_batch_ok(cfg) && n_tokens >= 3 ? n_tokens - 1 : 0;
-    if (n_batch > 0) {
-        Q8BatchScratch b{};
-        rc = ensure_q8_batch_scratch(c, cfg, w->group_size, &b); if (rc) return rc;
-        c->embedded_x = nullptr; c->host_pos = -1;
-        for (int c0 = 0; c0 < n_batch; c0 += kQ8bMaxTok) {
-            const int nt = std::min(kQ8bMaxTok, n_batch - c0);
-            rc = stage_tokens(c, b.toks, tokens_host + c0, nt); if (rc) return rc;
-            hipLaunchKernelGGL(embed_rows_kernel, dim3((cfg->dim + 255) / 256, nt), dim3(256), 0, c->stream, b.X, w->token_embedding_table,
-                               (const int*)b.toks, nt, cfg->dim);
-            LAUNCHCHK();
-            rc = q8_batch_layers(c, cfg, w, b, nt, pos0 + c0, s->key_cache, s->value_cache, nullptr); if (rc) return rc;
-        }
-    }
-    for (int i = n_batch; i < n_tokens; i++) { rc = rama_q8_forward(c, cfg, w, s, tokens_host[i], pos0 + i); if (rc) return rc; }
-    return 0;
-}
-
-// One pass for the n_seq sequences of the device tables toks / seqs: embedding rows, every layer, the final norm, the quantizer and
-// the classifier as one more product into b.LG [n_seq, vocab]
-static int enqueue_q8_batch_pass(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const Q8BatchScratch& b, const int* toks,
-                                 const SeqSlot* seqs, int n_seq) {
-    const int dim = cfg->dim, V = cfg->vocab_size, gs = w->group_size;
-    hipLaunchKernelGGL(embed_rows_kernel, dim3((dim + 255) / 256, n_seq), dim3(256), 0, c->stream, b.X, w->token_embedding_table, toks, n_seq, dim);
-    LAUNCHCHK();
-    int rc = q8_batch_layers(c, cfg, w, b, n_seq, 0, nullptr, nullptr, seqs); if (rc) return rc;
-    // infer.rs:49-51 per sequence: x = rmsnorm(x), logits = Wcls . x
-    rc = launch_rmsnorm_chain(c, b.XN, b.X, w->rms_final_weight, dim, nullptr, n_seq, dim); if (rc) return rc;
-    rc = launch_q8_quantize(c, b.XN, n_seq * dim, gs, b.xq, b.xs); if (rc) return rc;
-    Q8BatchParams p{};
-    p.w[0] = w->wcls; p.ws[0] = w->wcls_s; p.o[0] = b.LG;
-    p.xq = b.xq; p.xs = b.xs; p.K = dim; p.rows = V; p.gs = gs; p.nmat = 1; p.n_tok = n_seq; p.ostride = V;
-    return launch_q8_gemm<Q8EPI_STORE>(c, p);
-}
-
-int rama_q8_decode_batch(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const rama_run_state* states,
-                         const int32_t* tokens_host, const int32_t* positions_host, int n_seq) {
-    RAMA_ENTER(c);
-    REQUIRE(c && states && tokens_host && positions_host, RAMA_EINVAL, "q8_decode_batch: NULL argument");
-    REQUIRE(n_seq >= 1 && n_seq <= kQ8bMaxTok, RAMA_EINVAL, "q8_decode_batch: 1..128 sequences per call");
-    for (int i = 0; i < n_seq; i++) {
-        int rc = q8_check(c, cfg, w, &states[i]); if (rc) return rc;
-        REQUIRE(tokens_host[i] >= 0 && tokens_host[i] < cfg->vocab_size, RAMA_EINVAL, "q8_decode_batch: token outside the vocabulary");
-        REQUIRE(positions_host[i] >= 0 && positions_host[i] < cfg->seq_len, RAMA_EINVAL, "q8_decode_batch: position outside [0, seq_len)");
-        for (int j = 0; j < i; j++)
-            REQUIRE(states[j].key_cache != states[i].key_cache && states[j].value_cache != states[i].value_cache && states[j].logits != states[i].logits,
-                    RAMA_EINVAL, "q8_decode_batch: two sequences share a run state");
-    }
-    if (set_device(c)) return 1;
-    int rc = ensure_q8_scratch(c, cfg); if (rc) return rc;
-    if (!q8_batch_ok(cfg) || n_seq == 1) {      // see rama_q8_prefill: one rama_q8_forward per sequence (and for a single one)
-        for (int i = 0; i < n_seq; i++) {
-            rama_run_state si = states[i];
-            rc = rama_q8_forward(c, cfg, w, &si, tokens_host[i], positions_host[i]); if (rc) return rc;
-        }
-        return 0;
-    }
-    Q8BatchScratch b{};
-    rc = ensure_q8_batch_scratch(c, cfg, w->group_size, &b); if (rc) return rc;
-    c->embedded_x = nullptr; c->host_pos = -1;
-    rc = stage_tokens(c, b.toks, tokens_host, n_seq, b.seqs, states, positions_host); if (rc) return rc;
-    rc = enqueue_q8_batch_pass(c, cfg, w, b, b.toks, b.seqs, n_seq); if (rc) return rc;
-    return copy_out_logits(c, states, b.LG, n_seq, cfg->vocab_size);
-}
-
-// ---- the same pass CHAINED ON THE DEVICE (the Q8 counterpart of rama_decode_batch_begin / _steps): every sequence's (token, position)
-// lives in device memory, a step ends with argmax_batch_kernel or the batched top-p sampler, and -- new here -- a sequence ENDS on its
-// own: after `max_new` tokens or on a sampled stop token (kernels.hpp batch_seq_advance).  A finished slot repeats its last forward,
-// which rewrites one cache row with the same bits, so the pass needs no mask and one captured graph serves the whole chain: nothing in
-// the pass's launch geometry depends on the positions (score rows and attention LDS are sized by seq_len).
-
-// a sequence's budget: its own max_new (0: none) within the chain's max_steps
-static int q8_chain_limit(const rama_q8_seq_plan* per_seq, int i, int max_steps) {
-    return per_seq && per_seq[i].max_new > 0 ? std::min(per_seq[i].max_new, max_steps) : max_steps;
-}
-
-int rama_q8_decode_batch_begin(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const rama_run_state* states,
-                               const int32_t* tokens_host, const int32_t* positions_host, int n_seq, int max_steps,
-                               const rama_q8_seq_plan* per_seq) {
-    RAMA_ENTER(c);
-    // everything is checked before anything of a running chain is touched
-    REQUIRE(c && states && tokens_host && positions_host, RAMA_EINVAL, "q8_decode_batch_begin: NULL argument");
-    REQUIRE(n_seq >= 1 && n_seq <= kQ8bMaxTok, RAMA_EINVAL, "q8_decode_batch_begin: 1..128 sequences");
-    REQUIRE(max_steps >= 1 && max_steps <= (1 << 20), RAMA_EINVAL, "q8_decode_batch_begin: bad max_steps");
-    bool sampled = false;
-    size_t n_forced_all = 0;
-    int cap = 1;
-    for (int i = 0; i < n_seq; i++) {
-        int rc = q8_check(c, cfg, w, &states[i]); if (rc) return rc;
-        REQUIRE(tokens_host[i] >= 0 && tokens_host[i] < cfg->vocab_size, RAMA_EINVAL, "q8_decode_batch_begin: token outside the vocabulary");
-        for (int j = 0; j < i; j++)
-            REQUIRE(states[j].key_cache != states[i].key_cache && states[j].value_cache != states[i].value_cache, RAMA_EINVAL,
-                    "q8_decode_batch_begin: two sequences share a run state");
-        if (per_seq) {
-            const rama_q8_seq_plan& q = per_seq[i];
-            REQUIRE(topp_params_ok(q.temperature, q.topp, q.u), RAMA_EINVAL, "q8_decode_batch_begin: temperature >= 0, topp in [0,1], u in [0,1)");
-            REQUIRE(q.n_forced >= 0 && (q.n_forced == 0 || q.forced), RAMA_EINVAL, "q8_decode_batch_begin: bad forced list");
-            for (int k = 0; k < q.n_forced; k++)
-                REQUIRE(q.forced[k] >= 0 && q.forced[k] < cfg->vocab_size, RAMA_EINVAL, "q8_decode_batch_begin: forced token outside the vocabulary");
-            REQUIRE(q.max_new >= 0, RAMA_EINVAL, "q8_decode_batch_begin: max_new < 0");
-            REQUIRE(q.stop_token >= -1 && q.stop_token < cfg->vocab_size, RAMA_EINVAL, "q8_decode_batch_begin: stop token outside the vocabulary");
-            sampled = sampled || q.temperature != 0.0f || q.n_forced > 0;
-            n_forced_all += (size_t)q.n_forced;
-        }
-        const int limit = q8_chain_limit(per_seq, i, max_steps);
-        REQUIRE(positions_host[i] >= 0 && positions_host[i] <= cfg->seq_len - limit, RAMA_EINVAL,
-                "q8_decode_batch_begin: position + step budget beyond seq_len");
-        cap = std::max(cap, limit);
-    }
-    REQUIRE(q8_batch_ok(cfg), RAMA_EUNSUP, "q8_decode_batch_begin: a shape the Q8 token-batch pass does not take");
-    // argmax_batch_kernel reads 16-byte pieces of the logits rows: other vocabulary sizes end their steps in the sampler's launch
-    const bool use_sampler = sampled || cfg->vocab_size % 4 != 0;
-    REQUIRE(!use_sampler || (cfg->vocab_size > 1 && cfg->vocab_size <= kToppBlock * kToppMaxBlocks), RAMA_EUNSUP,
-            sampled ? "q8_decode_batch_begin: a sampled plan needs vocab_size <= 32768" : "q8_decode_batch_begin: vocab_size % 4 != 0 needs vocab_size <= 32768");
-    if (set_device(c)) return 1;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    auto& qc = c->q8c;
-    destroy_graph(qc.cg);
-    qc.n_seq = 0; qc.live = false; qc.states.clear();
-    // both scratches, the sampler's slices and the chain's tables: sized here, outside any capture
-    int rc = ensure_q8_scratch(c, cfg); if (rc) return rc;
-    Q8BatchScratch b{};
-    rc = ensure_q8_batch_scratch(c, cfg, w->group_size, &b); if (rc) return rc;
-    if (use_sampler) { rc = ensure_topp_batch(c, n_seq, cfg->vocab_size); if (rc) return rc; }
-    if (!qc.toks) {
-        HIPCHK(hipMalloc(&qc.toks, sizeof(int) * kQ8bMaxTok)); HIPCHK(hipMalloc(&qc.seqs, sizeof(SeqSlot) * kQ8bMaxTok));
-        HIPCHK(hipMalloc(&qc.ends, sizeof(BatchEnds)));
-        HIPCHK(hipMalloc(&qc.rows, sizeof(ToppRow) * kQ8bMaxTok));
-        HIPCHK(hipHostMalloc(&qc.done, sizeof(int) * kQ8bMaxTok, hipHostMallocMapped));
-        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&qc.done_dev), qc.done, 0));
-    }
-    if (qc.out_cap < cap) {
-        hipFree(qc.out); qc.out = nullptr; qc.out_cap = 0;
-        if (qc.ring) { hipHostFree(qc.ring); qc.ring = nullptr; }
-        HIPCHK(hipMalloc(&qc.out, sizeof(int) * (size_t)kQ8bMaxTok * cap));
-        HIPCHK(hipHostMalloc(&qc.ring, sizeof(int) * (size_t)kQ8bMaxTok * cap, hipHostMallocMapped));
-        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&qc.ring_dev), qc.ring, 0));
-        qc.out_cap = cap;
-    }
-    memset(qc.ring, 0, sizeof(int) * (size_t)kQ8bMaxTok * qc.out_cap);      // (the stream was drained above: nothing is on its way)
-    memset(qc.done, 0, sizeof(int) * kQ8bMaxTok);
-    if (qc.forced_cap < n_forced_all) {
-        hipFree(qc.forced); qc.forced = nullptr; qc.forced_cap = 0;
-        HIPCHK(hipMalloc(&qc.forced, sizeof(int) * n_forced_all));
-        qc.forced_cap = n_forced_all;
-    }
-    rc = stage_tokens(c, qc.toks, tokens_host, n_seq, qc.seqs, states, positions_host); if (rc) return rc;
-    static_assert(kQ8bMaxTok <= 128, "BatchEnds holds 128 sequences");
-    BatchEnds ends{};
-    ends.done = qc.done_dev;
-    ToppRow rows[kQ8bMaxTok];
-    size_t at = 0;
-    for (int i = 0; i < n_seq; i++) {
-        ends.limit[i] = q8_chain_limit(per_seq, i, max_steps);
-        ends.stop[i] = per_seq ? per_seq[i].stop_token : -1;
-        rows[i] = ToppRow{0.0f, 0.9f, 0.0f, 0, nullptr};
-        if (!per_seq) continue;
-        const rama_q8_seq_plan& q = per_seq[i];
-        rows[i] = ToppRow{q.temperature, q.topp, q.u, q.n_forced, q.n_forced ? qc.forced + at : nullptr};
-        if (q.n_forced) HIPCHK(hipMemcpy(qc.forced + at, q.forced, sizeof(int) * q.n_forced, hipMemcpyHostToDevice));
-        at += (size_t)q.n_forced;
-    }
-    HIPCHK(hipMemcpy(qc.ends, &ends, sizeof ends, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(qc.rows, rows, sizeof(ToppRow) * n_seq, hipMemcpyHostToDevice));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    qc.sampled = use_sampler; qc.cfg = *cfg; qc.w = *w; qc.states.assign(states, states + n_seq);
-    qc.max_steps = max_steps; qc.steps_done = 0; qc.n_seq = n_seq; qc.live = true;
-    return 0;
-}
-
-// one step: the pass over the chain's own tables, then what ends it
-static int enqueue_q8_chain_step(rama_ctx* c, const Q8BatchScratch& b) {
-    auto& qc = c->q8c;
-    const int V = qc.cfg.vocab_size;
-    int rc = enqueue_q8_batch_pass(c, &qc.cfg, &qc.w, b, qc.toks, qc.seqs, qc.n_seq); if (rc) return rc;
-    if (!qc.sampled) {
-        BatchArgmaxParams ap{b.LG, V, qc.toks, qc.seqs, qc.out, qc.out_cap, qc.ring_dev, qc.ends};
-        hipLaunchKernelGGL(argmax_batch_kernel, dim3(qc.n_seq), dim3(1024), 0, c->stream, ap);
-        LAUNCHCHK();
-        return 0;
-    }
-    ToppBatchParams fin{};
-    fin.toks = qc.toks; fin.seqs = qc.seqs; fin.out = qc.out; fin.out_cap = qc.out_cap; fin.ring = qc.ring_dev;
-    fin.ends = qc.ends;
-    return enqueue_topp_batch(c, qc.rows, qc.n_seq, b.LG, (size_t)V, V, fin);
-}
-
-int rama_q8_decode_batch_steps(rama_ctx* c, int n_steps) {
-    RAMA_ENTER(c);
-    REQUIRE(c && c->q8c.n_seq > 0, RAMA_EINVAL, "q8_decode_batch_steps: call rama_q8_decode_batch_begin first");
-    auto& qc = c->q8c;
-    REQUIRE(qc.live, RAMA_EINVAL, "q8_decode_batch_steps: the chain's model or one of its run states has been freed");
-    REQUIRE(n_steps >= 0 && n_steps <= qc.max_steps - qc.steps_done, RAMA_EINVAL, "q8_decode_batch_steps: more steps than rama_q8_decode_batch_begin allowed for");
-    if (set_device(c)) return 1;
-    // (neither grows here: rama_q8_decode_batch_begin sized them, and whoever grew them since for another shape dropped the step's graph)
-    int rc = ensure_q8_scratch(c, &qc.cfg); if (rc) return rc;
-    Q8BatchScratch b{};
-    rc = ensure_q8_batch_scratch(c, &qc.cfg, qc.w.group_size, &b); if (rc) return rc;
-    if (qc.sampled) { rc = ensure_topp_batch(c, qc.n_seq, qc.cfg.vocab_size); if (rc) return rc; }
-    c->embedded_x = nullptr; c->host_pos = -1;
-    const bool graphs = c->graph_mode && c->kp.kernel_id < 0;
-    for (int i = 0; i < n_steps; i++) {
-        if (!graphs) {
-            rc = enqueue_q8_chain_step(c, b); if (rc) return rc;
-        } else {
-            if (!qc.cg.exec) { rc = capture_graph(c, qc.cg, [&] { return enqueue_q8_chain_step(c, b); }); if (rc) return rc; }
-            rc = replay_graph(c, qc.cg); if (rc) return rc;
-        }
-        qc.steps_done++;
-    }
-    return 0;
-}
-
-int rama_q8_decode_batch_tokens(rama_ctx* c, int32_t* out_host, int max_per_seq, int32_t* n_per_seq) {
-    RAMA_ENTER(c);
-    REQUIRE(c && out_host && n_per_seq && c->q8c.n_seq > 0 && max_per_seq >= 0, RAMA_EINVAL, "q8_decode_batch_tokens: bad argument");
-    auto& qc = c->q8c;
-    if (set_device(c)) return 1;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    { const int rh = handoff_check(c); if (rh) return rh; }
-    SeqSlot slots[kQ8bMaxTok];
-    HIPCHK(hipMemcpy(slots, qc.seqs, sizeof(SeqSlot) * qc.n_seq, hipMemcpyDeviceToHost));
-    for (int s_ = 0; s_ < qc.n_seq; s_++) {
-        const int n = std::min(std::min(slots[s_].pad, qc.out_cap), max_per_seq);      // pad: the tokens the sequence has produced
-        if (n > 0) HIPCHK(hipMemcpy(out_host + (size_t)s_ * max_per_seq, qc.out + (size_t)s_ * qc.out_cap, sizeof(int) * n, hipMemcpyDeviceToHost));
-        n_per_seq[s_] = n;
-    }
-    return 0;
-}
-
-int rama_q8_decode_batch_stream_poll(rama_ctx* c, int seq, int from, int32_t* out_host, int max_tokens, int* n_ready, int* finished) {
-    RAMA_ENTER(c);
-    REQUIRE(c && n_ready && c->q8c.n_seq > 0 && c->q8c.ring && seq >= 0 && seq < c->q8c.n_seq && from >= 0 && max_tokens >= 0 && (max_tokens == 0 || out_host),
-            RAMA_EINVAL, "q8_decode_batch_stream_poll: bad argument");
-    const auto& qc = c->q8c;
-    // the finished word first: it is stored after the sequence's last ring word, so a set word means every token is there to be read
-    const int fin = __atomic_load_n(qc.done + seq, __ATOMIC_ACQUIRE);
-    const int* row = qc.ring + (size_t)seq * qc.out_cap;
-    int n = 0;
-    while (n < max_tokens && from + n < qc.out_cap) {
-        const int v = __atomic_load_n(row + from + n, __ATOMIC_ACQUIRE);
-        if (v == 0) break;
-        out_host[n++] = v - 1;
-    }
-    *n_ready = n;
-    if (finished) *finished = fin != 0;
-    return 0;
-}
-
-// ---- THE SERVING CHAIN (q8_serve.hpp): continuous batching.  n_slots slots share passes of max_rows rows; a scheduler
-// launch builds every step's row table from the slot table on the device, a pick launch runs the slots' state machine, and an admission
-// is a stream-ordered copy + launch between two steps.  Nothing in a step's launch geometry depends on a sequence, so one captured graph
-// serves the chain for its whole life.
-
-// the scheduling rule on the host: the rows every slot gets in the next step (serve_schedule_kernel computes the same numbers by scans)
-static void serve_plan_counts(const rama_q8_serve_slot* slots, int n_slots, int max_rows, int* nrows) {
-    int left = max_rows;
-    for (int i = 0; i < n_slots; i++) {
-        nrows[i] = slots[i].state == RAMA_SERVE_DECODE || slots[i].state == RAMA_SERVE_PROMPT ? 1 : 0;
-        left -= nrows[i];
-    }
-    for (int i = 0; i < n_slots && left > 0; i++) {
-        if (slots[i].state != RAMA_SERVE_PROMPT) continue;
-        const int extra = std::min(slots[i].n_context - slots[i].cursor - 1, left);
-        nrows[i] += extra;
-        left -= extra;
-    }
-}
-
-int rama_q8_serve_plan_step(const rama_q8_serve_slot* slots, int n_slots, int max_rows, rama_q8_serve_row* rows_out, rama_q8_serve_slot* slots_after) {
-    REQUIRE(slots && rows_out, RAMA_EINVAL, "q8_serve_plan_step: NULL argument");
-    REQUIRE(n_slots >= 1 && n_slots <= kServeMaxSlots && max_rows >= n_slots && max_rows <= kQ8bMaxTok, RAMA_EINVAL,
-            "q8_serve_plan_step: 1 <= n_slots <= max_rows <= 128");
-    for (int i = 0; i < n_slots; i++) {
-        const rama_q8_serve_slot& s = slots[i];
-        REQUIRE(s.state >= RAMA_SERVE_FREE && s.state <= RAMA_SERVE_DONE, RAMA_EINVAL, "q8_serve_plan_step: bad slot state");
-        if (s.state == RAMA_SERVE_PROMPT)
-            REQUIRE(s.n_context >= 1 && s.cursor >= 0 && s.cursor < s.n_context && s.max_new >= 1, RAMA_EINVAL, "q8_serve_plan_step: bad PROMPT slot");
-        if (s.state == RAMA_SERVE_DECODE)
-            REQUIRE(s.cursor >= 0 && s.n_out >= 1 && s.n_out < s.max_new, RAMA_EINVAL, "q8_serve_plan_step: bad DECODE slot");
-    }
-    int nrows[kServeMaxSlots];
-    serve_plan_counts(slots, n_slots, max_rows, nrows);
-    int r = 0;
-    for (int i = 0; i < n_slots; i++) {
-        const rama_q8_serve_slot& s = slots[i];
-        const bool lg = s.state == RAMA_SERVE_DECODE || (s.state == RAMA_SERVE_PROMPT && s.cursor + nrows[i] == s.n_context);
-        for (int k = 0; k < nrows[i]; k++) rows_out[r++] = rama_q8_serve_row{i, s.cursor + k, lg && k == nrows[i] - 1 ? 1 : 0};
-        if (!slots_after) continue;
-        rama_q8_serve_slot a = s;
-        if (nrows[i]) {
-            a.cursor = s.cursor + nrows[i];
-            if (lg) {
-                a.n_out = s.n_out + 1;
-                a.state = a.n_out >= s.max_new ? RAMA_SERVE_DONE : RAMA_SERVE_DECODE;
-            }
-        }
-        slots_after[i] = a;
-    }
-    for (; r < max_rows; r++) rows_out[r] = rama_q8_serve_row{-1, -1, 0};
-    return 0;
-}
-
-int rama_q8_serve_end(rama_ctx* c) {
-    RAMA_ENTER(c);
-    REQUIRE(c, RAMA_EINVAL, "q8_serve_end: ctx is NULL");
-    if (!c->q8s.n_slots && !c->q8s.blob) return 0;
-    if (set_device(c)) return 1;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    serve_release(c);
-    return 0;
-}
-
-int rama_q8_serve_begin(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, int n_slots, int max_rows, int max_new_cap) {
-    RAMA_ENTER(c);
-    REQUIRE(c, RAMA_EINVAL, "ctx is NULL");
-    int rc = check_cfg(cfg); if (rc) return rc;
-    REQUIRE(w && w->group_size > 0 && cfg->dim % w->group_size == 0 && cfg->hidden_dim % w->group_size == 0, RAMA_EINVAL,
-            "q8_serve_begin: group_size must divide dim and hidden_dim");
-    REQUIRE(w->token_embedding_table && w->rms_att_weight && w->rms_ffn_weight && w->rms_final_weight && w->freq_cis_real && w->freq_cis_imag &&
-            w->wq && w->wk && w->wv && w->wo && w->w1 && w->w2 && w->w3 && w->wcls && w->wq_s && w->wk_s && w->wv_s && w->wo_s && w->w1_s &&
-            w->w2_s && w->w3_s && w->wcls_s, RAMA_EINVAL, "q8_serve_begin: missing weights");
-    REQUIRE(n_slots >= 1 && n_slots <= kServeMaxSlots && max_rows >= n_slots && max_rows <= kQ8bMaxTok, RAMA_EINVAL,
-            "q8_serve_begin: 1 <= n_slots <= max_rows <= 128");
-    REQUIRE(max_new_cap >= 1 && max_new_cap <= cfg->seq_len - 1, RAMA_EINVAL, "q8_serve_begin: max_new_cap outside [1, seq_len - 1]");
-    REQUIRE(q8_batch_ok(cfg), RAMA_EUNSUP, "q8_serve_begin: a shape the Q8 token-batch pass does not take");
-    const int V = cfg->vocab_size;
-    const bool sampler = V > 1 && V <= kToppBlock * kToppMaxBlocks;
-    REQUIRE(sampler || V % 4 == 0, RAMA_EUNSUP, "q8_serve_begin: vocab_size % 4 != 0 needs vocab_size <= 32768");
-    if (set_device(c)) return 1;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    serve_release(c);
-    // both scratches, the sampler's slices and the chain's tables: sized here, outside any capture
-    rc = ensure_q8_scratch(c, cfg); if (rc) return rc;
-    Q8BatchScratch b{};
-    rc = ensure_q8_batch_scratch(c, cfg, w->group_size, &b); if (rc) return rc;
-    if (sampler) { rc = ensure_topp_batch(c, n_slots, V); if (rc) return rc; }
-    auto& sv = c->q8s;
-    const size_t S = (size_t)cfg->seq_len, N = (size_t)n_slots, R = (size_t)max_rows, cap = (size_t)max_new_cap;
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-    const size_t sz[9] = {N * sizeof(ServeSlot), N * S * sizeof(int), R * sizeof(SeqSlot), R * sizeof(int), N * sizeof(int), N * sizeof(int),
-                          N * sizeof(ToppRow), 4 * sizeof(unsigned long long), N * cap * sizeof(int)};
-    size_t off[9], need = 0;
-    for (int i = 0; i < 9; i++) { off[i] = need; need += up(sz[i]); }
-    HIPCHK(hipMalloc(&sv.blob, need));
-    HIPCHK(hipMemsetAsync(sv.blob, 0, need, c->stream));          // every slot FREE, the counters 0
-    sv.rec_bytes = up(sizeof(ServeSlot) + S * sizeof(int));
-    HIPCHK(hipMalloc(&sv.stage, N * sv.rec_bytes));
-    HIPCHK(hipHostMalloc(&sv.pinned, N * sv.rec_bytes, hipHostMallocDefault));
-    HIPCHK(hipHostMalloc(&sv.ring, sizeof(int) * N * cap, hipHostMallocMapped));
-    HIPCHK(hipHostMalloc(&sv.done, sizeof(int) * N, hipHostMallocMapped));
-    memset(sv.ring, 0, sizeof(int) * N * cap);
-    memset(sv.done, 0, sizeof(int) * N);
-    ServeTables& t = sv.t;
-    t.slots = reinterpret_cast<ServeSlot*>(sv.blob + off[0]); t.ctx = reinterpret_cast<int*>(sv.blob + off[1]);
-    t.rows = reinterpret_cast<SeqSlot*>(sv.blob + off[2]); t.row_tok = reinterpret_cast<int*>(sv.blob + off[3]);
-    t.nrows = reinterpret_cast<int*>(sv.blob + off[4]); t.lrow = reinterpret_cast<int*>(sv.blob + off[5]);
-    t.trow = reinterpret_cast<ToppRow*>(sv.blob + off[6]); t.counters = reinterpret_cast<unsigned long long*>(sv.blob + off[7]);
-    t.out = reinterpret_cast<int*>(sv.blob + off[8]);
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&t.ring), sv.ring, 0));
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&t.done), sv.done, 0));
-    t.seq_len = cfg->seq_len; t.n_slots = n_slots; t.max_rows = max_rows; t.out_cap = max_new_cap;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    sv.cfg = *cfg; sv.w = *w; sv.sampler = sampler;
-    sv.states.assign(N, rama_run_state{}); sv.occupied.assign(N, 0); sv.gen.assign(N, 0);
-    sv.steps = 0; sv.captures = 0;
-    sv.max_rows = max_rows; sv.out_cap = max_new_cap; sv.n_slots = n_slots; sv.live = true;
-    return 0;
-}
-
-// the slot's occupant is still on the device's hands: admitted, and its finished word not yet set
-static bool serve_slot_live(const rama_ctx::Q8Serve& sv, int slot) {
-    return sv.occupied[slot] && !__atomic_load_n(sv.done + slot, __ATOMIC_ACQUIRE);
-}
-
-// rama_q8_serve_admit (n_cached 0) and rama_q8_serve_admit_at: the slot starts PROMPT at cursor = n_cached, over rows 0 .. n_cached - 1 that
-// earlier work on the stream has put into the run state's caches
-static int serve_admit(rama_ctx* c, int slot, const rama_run_state* state, const int32_t* context_host, int n_context, int n_cached,
-                       const rama_q8_serve_plan* plan) {
-    RAMA_ENTER(c);
-    REQUIRE(c && c->q8s.n_slots > 0, RAMA_EINVAL, "q8_serve_admit: call rama_q8_serve_begin first");
-    auto& sv = c->q8s;
-    // everything is checked before anything of the running chain is touched
-    REQUIRE(sv.live, RAMA_EINVAL, "q8_serve_admit: the chain's model or the run state of an occupied slot has been freed");
-    REQUIRE(state && context_host && plan, RAMA_EINVAL, "q8_serve_admit: NULL argument");
-    REQUIRE(slot >= 0 && slot < sv.n_slots, RAMA_EINVAL, "q8_serve_admit: no such slot");
-    int rc = q8_check(c, &sv.cfg, &sv.w, state); if (rc) return rc;
-    REQUIRE(!serve_slot_live(sv, slot), RAMA_EINVAL, "q8_serve_admit: the slot is busy");
-    const int V = sv.cfg.vocab_size;
-    REQUIRE(n_context >= 1, RAMA_EINVAL, "q8_serve_admit: n_context < 1");
-    REQUIRE(n_cached >= 0 && n_cached <= n_context - 1, RAMA_EINVAL, "q8_serve_admit_at: n_cached outside [0, n_context - 1] (the final context position is always fed)");
-    REQUIRE(plan->max_new >= 1, RAMA_EINVAL, "q8_serve_admit: max_new < 1");
-    REQUIRE(plan->max_new <= sv.out_cap, RAMA_EINVAL, "q8_serve_admit: max_new beyond rama_q8_serve_begin's max_new_cap");
-    REQUIRE(n_context <= sv.cfg.seq_len - plan->max_new, RAMA_EINVAL, "q8_serve_admit: n_context + max_new beyond seq_len");
-    for (int i = 0; i < n_context; i++) REQUIRE(context_host[i] >= 0 && context_host[i] < V, RAMA_EINVAL, "q8_serve_admit: token outside the vocabulary");
-    REQUIRE(topp_params_ok(plan->temperature, plan->topp, plan->u), RAMA_EINVAL, "q8_serve_admit: temperature >= 0, topp in [0,1], u in [0,1)");
-    REQUIRE(plan->stop_token >= -1 && plan->stop_token < V, RAMA_EINVAL, "q8_serve_admit: stop token outside the vocabulary");
-    for (int j = 0; j < sv.n_slots; j++)
-        REQUIRE(j == slot || !serve_slot_live(sv, j) || (sv.states[j].key_cache != state->key_cache && sv.states[j].value_cache != state->value_cache),
-                RAMA_EINVAL, "q8_serve_admit: the run state is already in a live slot");
-    REQUIRE(plan->temperature == 0.0f || sv.sampler, RAMA_EUNSUP, "q8_serve_admit: a sampled plan needs vocab_size <= 32768");
-    if (set_device(c)) return 1;
-    // the slot's own pinned record: its previous copy has run (the occupant it installed has finished, or there was none)
-    char* rec = sv.pinned + (size_t)slot * sv.rec_bytes;
-    ServeSlot h{};
-    h.kc = state->key_cache; h.vc = state->value_cache;
-    h.state = kServePrompt; h.n_ctx = n_context; h.cursor = n_cached; h.tok = 0; h.n_out = 0;
-    h.max_new = plan->max_new; h.stop = plan->stop_token; h.gen = sv.gen[slot] + 1;
-    h.temperature = plan->temperature; h.topp = plan->topp; h.u = plan->u;
-    memcpy(rec, &h, sizeof h);
-    memcpy(rec + sizeof h, context_host, sizeof(int) * (size_t)n_context);
-    // (the device writes neither again for the previous occupant: it is DONE)
-    memset(sv.ring + (size_t)slot * sv.out_cap, 0, sizeof(int) * (size_t)sv.out_cap);
-    __atomic_store_n(sv.done + slot, 0, __ATOMIC_RELEASE);
-    char* dst = sv.stage + (size_t)slot * sv.rec_bytes;
-    HIPCHK(hipMemcpyAsync(dst, rec, sizeof h + sizeof(int) * (size_t)n_context, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(serve_install_kernel, dim3(1), dim3(256), 0, c->stream, sv.t, slot, reinterpret_cast<const ServeSlot*>(dst));
-    LAUNCHCHK();
-    sv.states[slot] = *state; sv.occupied[slot] = 1; sv.gen[slot]++;
-    return 0;
-}
-
-int rama_q8_serve_admit(rama_ctx* c, int slot, const rama_run_state* state, const int32_t* context_host, int n_context, const rama_q8_serve_plan* plan) {
-    return serve_admit(c, slot, state, context_host, n_context, 0, plan);
-}
-
-int rama_q8_serve_admit_at(rama_ctx* c, int slot, const rama_run_state* state, const int32_t* context_host, int n_context, int n_cached,
-                           const rama_q8_serve_plan* plan) {
-    return serve_admit(c, slot, state, context_host, n_context, n_cached, plan);
-}
-
-// rows [0, n_rows) of every layer of src's caches into every destination's: one launch (q8_fork.hpp), stream-ordered
-int rama_q8_kv_fork(rama_ctx* c, const rama_config* cfg, const rama_run_state* src, const rama_run_state* dsts, int n_dst, int n_rows) {
-    RAMA_ENTER(c);
-    REQUIRE(c, RAMA_EINVAL, "q8_kv_fork: ctx is NULL");
-    int rc = check_cfg(cfg); if (rc) return rc;
-    REQUIRE(src && dsts, RAMA_EINVAL, "q8_kv_fork: NULL argument");
-    REQUIRE(n_dst >= 1 && n_dst <= kForkMaxDst, RAMA_EINVAL, "q8_kv_fork: 1 <= n_dst <= 16");
-    REQUIRE(n_rows >= 0 && n_rows <= cfg->seq_len, RAMA_EINVAL, "q8_kv_fork: n_rows outside [0, seq_len]");
-    REQUIRE(src->key_cache && src->value_cache, RAMA_EINVAL, "q8_kv_fork: the source has no caches");
-    const size_t layer = (size_t)cfg->seq_len * (size_t)cfg->dim, total = layer * (size_t)cfg->n_layers;
-    // every cache written must lie clear of the source's and of every other one written
-    std::vector<const float*> caches = {src->key_cache, src->value_cache};
-    for (int d = 0; d < n_dst; d++) {
-        REQUIRE(dsts[d].key_cache && dsts[d].value_cache, RAMA_EINVAL, "q8_kv_fork: a destination has no caches");
-        caches.push_back(dsts[d].key_cache); caches.push_back(dsts[d].value_cache);
-    }
-    for (size_t i = 2; i < caches.size(); i++)
-        for (size_t j = 0; j < i; j++)
-            REQUIRE(!ranges_overlap(caches[i], total, caches[j], total), RAMA_EINVAL,
-                    "q8_kv_fork: a destination shares a cache with the source or with another destination");
-    const auto& sv = c->q8s;
-    for (int d = 0; d < n_dst; d++)
-        for (int j = 0; j < sv.n_slots; j++)
-            REQUIRE(!serve_slot_live(sv, j) || (sv.states[j].key_cache != dsts[d].key_cache && sv.states[j].value_cache != dsts[d].value_cache),
-                    RAMA_EINVAL, "q8_kv_fork: a destination is in a live slot of the serving chain");
-    if (n_rows == 0) return 0;
-    const size_t span = (size_t)n_rows * (size_t)cfg->dim, reach = layer * (size_t)(cfg->n_layers - 1) + span;
-    for (int d = 0; d < n_dst; d++) { RAMA_WRITES(c, dsts[d].key_cache, reach); RAMA_WRITES(c, dsts[d].value_cache, reach); }
-    if (set_device(c)) return 1;
-    ForkParams p{};
-    p.src[0] = src->key_cache; p.src[1] = src->value_cache;
-    bool vec = aligned16(p.src[0]) && aligned16(p.src[1]);       // (dim % 4 == 0: a layer and a span are whole 16-byte words)
-    for (int d = 0; d < n_dst; d++) {
-        p.dst[0][d] = dsts[d].key_cache; p.dst[1][d] = dsts[d].value_cache;
-        vec = vec && aligned16(p.dst[0][d]) && aligned16(p.dst[1][d]);
-    }
-    p.n_dst = n_dst; p.layer_floats = layer; p.n_words = vec ? span / 4 : span;
-    const dim3 grid((unsigned)((p.n_words + kForkPiece - 1) / kForkPiece), (unsigned)(2 * cfg->n_layers));
-    if (vec) hipLaunchKernelGGL(kv_fork_kernel<true>, grid, dim3(kForkThreads), 0, c->stream, p);
-    else hipLaunchKernelGGL(kv_fork_kernel<false>, grid, dim3(kForkThreads), 0, c->stream, p);
-    LAUNCHCHK();
-    return 0;
-}
-
-// one step: the scheduler, the pass over its row table, the logits of the rows that carry them, the pick and the slots' state machine
-static int enqueue_q8_serve_step(rama_ctx* c, const Q8BatchScratch& b) {
-    auto& sv = c->q8s;
-    const rama_config* cfg = &sv.cfg;
-    const rama_q8_weights* w = &sv.w;
-    const int dim = cfg->dim, V = cfg->vocab_size, gs = w->group_size, R = sv.max_rows, N = sv.n_slots;
-    hipLaunchKernelGGL(serve_schedule_kernel, dim3(1), dim3(kServeMaxSlots), 0, c->stream, sv.t);
-    LAUNCHCHK();
-    hipLaunchKernelGGL(embed_rows_kernel, dim3((dim + 255) / 256, R), dim3(256), 0, c->stream, b.X, w->token_embedding_table, (const int*)sv.t.row_tok, R, dim);
-    LAUNCHCHK();
-    int rc = q8_batch_layers(c, cfg, w, b, R, 0, nullptr, nullptr, sv.t.rows); if (rc) return rc;
-    // infer.rs:49-51 for the slots' logits rows only (b.Q is free here): x = rmsnorm(x), logits = Wcls . x
-    hipLaunchKernelGGL(serve_gather_kernel, dim3((dim + 255) / 256, N), dim3(256), 0, c->stream, b.Q, (const float*)b.X, (const int*)sv.t.lrow, dim);
-    LAUNCHCHK();
-    rc = launch_rmsnorm_chain(c, b.XN, b.Q, w->rms_final_weight, dim, nullptr, N, dim); if (rc) return rc;
-    rc = launch_q8_quantize(c, b.XN, N * dim, gs, b.xq, b.xs); if (rc) return rc;
-    Q8BatchParams p{};
-    p.w[0] = w->wcls; p.ws[0] = w->wcls_s; p.o[0] = b.LG;
-    p.xq = b.xq; p.xs = b.xs; p.K = dim; p.rows = V; p.gs = gs; p.nmat = 1; p.n_tok = N; p.ostride = V;
-    rc = launch_q8_gemm<Q8EPI_STORE>(c, p); if (rc) return rc;
-    ServePickParams fin{};
-    fin.t = sv.t; fin.logits = b.LG; fin.ld = (size_t)V; fin.n = V;
-    if (sv.sampler) {
-        rc = enqueue_topp_batch_order(c, sv.t.trow, N, b.LG, (size_t)V, V, nullptr); if (rc) return rc;
-        fin.keys = c->tb.keys; fin.vals = c->tb.vals; fin.m = c->tb.m; fin.rstride = c->tb.rstride;
-    }
-    hipLaunchKernelGGL(serve_pick_kernel, dim3(N), dim3(1024), 0, c->stream, fin);
-    LAUNCHCHK();
-    return 0;
-}
-
-int rama_q8_serve_steps(rama_ctx* c, int n_steps) {
-    RAMA_ENTER(c);
-    REQUIRE(c && c->q8s.n_slots > 0, RAMA_EINVAL, "q8_serve_steps: call rama_q8_serve_begin first");
-    auto& sv = c->q8s;
-    REQUIRE(sv.live, RAMA_EINVAL, "q8_serve_steps: the chain's model or the run state of an occupied slot has been freed");
-    REQUIRE(n_steps >= 0, RAMA_EINVAL, "q8_serve_steps: n_steps < 0");
-    if (set_device(c)) return 1;
-    // (neither grows here: rama_q8_serve_begin sized them, and whoever grew them since for another shape dropped the step's graph)
-    int rc = ensure_q8_scratch(c, &sv.cfg); if (rc) return rc;
-    Q8BatchScratch b{};
-    rc = ensure_q8_batch_scratch(c, &sv.cfg, sv.w.group_size, &b); if (rc) return rc;
-    if (sv.sampler) { rc = ensure_topp_batch(c, sv.n_slots, sv.cfg.vocab_size); if (rc) return rc; }
-    c->embedded_x = nullptr; c->host_pos = -1;
-    const bool graphs = c->graph_mode && c->kp.kernel_id < 0;
-    for (int i = 0; i < n_steps; i++) {
-        if (!graphs) {
-            rc = enqueue_q8_serve_step(c, b); if (rc) return rc;
-        } else {
-            if (!sv.cg.exec) {
-                rc = capture_graph(c, sv.cg, [&] { return enqueue_q8_serve_step(c, b); }); if (rc) return rc;
-                sv.captures++;
-            }
-            rc = replay_graph(c, sv.cg); if (rc) return rc;
-        }
-        sv.steps++;
-    }
-    return 0;
-}
-
-int rama_q8_serve_poll(rama_ctx* c, int slot, int from, int32_t* out_host, int max_tokens, int* n_ready, int* finished, int* generation) {
-    RAMA_ENTER(c);
-    REQUIRE(c && n_ready && c->q8s.n_slots > 0 && slot >= 0 && slot < c->q8s.n_slots && from >= 0 && max_tokens >= 0 && (max_tokens == 0 || out_host),
-            RAMA_EINVAL, "q8_serve_poll: bad argument");
-    const auto& sv = c->q8s;
-    // the finished word first: it is stored after the occupant's last ring word, so a set word means every token is there to be read
-    const int fin = __atomic_load_n(sv.done + slot, __ATOMIC_ACQUIRE);
-    const int* row = sv.ring + (size_t)slot * sv.out_cap;
-    int n = 0;
-    while (n < max_tokens && from + n < sv.out_cap) {
-        const int v = __atomic_load_n(row + from + n, __ATOMIC_ACQUIRE);
-        if (v == 0) break;
-        out_host[n++] = v - 1;
-    }
-    *n_ready = n;
-    if (finished) *finished = fin != 0;
-    if (generation) *generation = sv.gen[slot];
-    return 0;
-}
-
-int rama_q8_serve_tokens(rama_ctx* c, int slot, int32_t* out_host, int max_tokens, int* n_out) {
-    RAMA_ENTER(c);
-    REQUIRE(c && n_out && c->q8s.n_slots > 0 && slot >= 0 && slot < c->q8s.n_slots && max_tokens >= 0 && (max_tokens == 0 || out_host), RAMA_EINVAL,
-            "q8_serve_tokens: bad argument");
-    auto& sv = c->q8s;
-    if (set_device(c)) return 1;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    { const int rh = handoff_check(c); if (rh) return rh; }
-    ServeSlot s{};
-    HIPCHK(hipMemcpy(&s, sv.t.slots + slot, sizeof s, hipMemcpyDeviceToHost));
-    const int n = std::min(std::min(s.n_out, sv.out_cap), max_tokens);
-    if (n > 0) HIPCHK(hipMemcpy(out_host, sv.t.out + (size_t)slot * sv.out_cap, sizeof(int) * n, hipMemcpyDeviceToHost));
-    *n_out = n;
-    return 0;
-}
-
-int rama_q8_serve_stats(rama_ctx* c, rama_q8_serve_report* out) {
-    RAMA_ENTER(c);
-    REQUIRE(c && out && c->q8s.n_slots > 0, RAMA_EINVAL, "q8_serve_stats: bad argument");
-    auto& sv = c->q8s;
-    if (set_device(c)) return 1;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    { const int rh = handoff_check(c); if (rh) return rh; }
-    memset(out, 0, sizeof *out);
-    unsigned long long cnt[4];
-    ServeSlot slots[kServeMaxSlots];
-    SeqSlot rows[kQ8bMaxTok];
-    int lrow[kServeMaxSlots];
-    HIPCHK(hipMemcpy(cnt, sv.t.counters, sizeof cnt, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(slots, sv.t.slots, sizeof(ServeSlot) * sv.n_slots, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(rows, sv.t.rows, sizeof(SeqSlot) * sv.max_rows, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(lrow, sv.t.lrow, sizeof(int) * sv.n_slots, hipMemcpyDeviceToHost));
-    out->steps = cnt[0]; out->graph_captures = sv.captures; out->rows_decode = cnt[1]; out->rows_prompt = cnt[2]; out->rows_idle = cnt[3];
-    out->n_slots = sv.n_slots; out->max_rows = sv.max_rows;
-    for (int r = 0; r < sv.max_rows; r++) {
-        const bool on = cnt[0] > 0 && rows[r].pos >= 0;            // (before the first step the table holds nothing)
-        out->last_rows[r] = rama_q8_serve_row{on ? rows[r].pad : -1, on ? rows[r].pos : -1, on && lrow[rows[r].pad] == r ? 1 : 0};
-    }
-    for (int i = 0; i < sv.n_slots; i++) {
-        out->slots[i] = rama_q8_serve_slot{slots[i].state, slots[i].n_ctx, slots[i].cursor, slots[i].n_out, slots[i].max_new};
-        out->generation[i] = sv.gen[i];
-    }
-    return 0;
 }

@@ -30,7 +30,7 @@ pytestmark = pytest.mark.gpu
 
 GS = {"d288": 32, "d768": 64, "d2048": 64, "d4096": 64}
 SEED = 11
-SPREAD_POS_DEFAULT = 128      # rama_api.hip kSpreadAttnPos
+SPREAD_POS_DEFAULT = 128      # ctx.hpp kSpreadAttnPos
 SPREAD_NEVER = 1 << 20
 MILD = 7                      # a token of TOKS whose row has no designed property
 

@@ -2,6 +2,7 @@
 // Not part of the product: sizes the floor the small-model decode path (stories15M / 110M: ~26-50
 // dependent launches per token) is up against.  Build: hipcc --offload-arch=gfx950 -O3 -o launch_floor tools/launch_floor.hip
 #include "../rama_amd/csrc/kernels.hpp"
+#include "../rama_amd/csrc/ops_kernels.hpp"
 #include <cstdio>
 #include <cstdlib>
 #include <vector>

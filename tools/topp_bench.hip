@@ -3,6 +3,7 @@
 // each (100 MHz time stamps of workgroup 0).  Not part of the product.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -DRAMA_TOPP_STAMPS -o build/topp_bench tools/topp_bench.hip
 #include "../rama_amd/csrc/topp_pick.hpp"
+#include "../rama_amd/csrc/topp_kernels.hpp"
 #include <cstdio>
 #include <cstdlib>
 #include <random>
