@@ -446,6 +446,15 @@ int  rama_q8_model_free(rama_ctx *ctx, rama_q8_model *m);
 int  rama_q8_quantize(rama_ctx *ctx, const float *x, size_t n, int group_size, int8_t *q, float *s);
 int  rama_q8_matmul(rama_ctx *ctx, float *o, const int8_t *wq, const float *ws, const int8_t *xq, const float *xs,
                     size_t n, size_t d, int group_size);
+/* HOST-ONLY (no context, no GPU): the kernel a Q8 product over rows of n values takes -- the rule the launchers themselves
+ * ask.  n_tok == 0: the single-token matvec (rama_q8_matmul, rama_q8_forward); n_tok >= 1: one pass of min(n_tok, 128)
+ * tokens of a batch.  aligned16: activations and every matrix start on a 16-byte boundary.  MATVEC: 16-byte chunks and
+ * dot4, K % 16 == 0, group size a power of two in [16, 1024], at most 2048 groups (64 KiB of LDS); GEMM_KSPLIT / GEMM_MFMA:
+ * int8 matrix cores, K % 16 == 0, group size 32 or a multiple of 64 up to 4096 (KSPLIT: at most 32 tokens at 32 or 64);
+ * the GENERIC kernels are bytewise and take everything else.  RAMA_EINVAL unless group_size divides n. */
+enum { RAMA_Q8_PATH_MATVEC = 0, RAMA_Q8_PATH_MATVEC_GENERIC = 1, RAMA_Q8_PATH_GEMM_KSPLIT = 2, RAMA_Q8_PATH_GEMM_MFMA = 3,
+       RAMA_Q8_PATH_GEMM_GENERIC = 4 };
+int  rama_q8_product_path(size_t n, int group_size, int n_tok, int aligned16);
 /* rama_forward for a Q8 model: the same run-state buffers (logits, the cache rows of `pos`, x).  The int8 activation
  * scratch belongs to the context and is sized on the first call (outside any capture).  Graph mode: one graph per
  * (run state, attention variant), kept apart from the fp32 graphs; rama_state_free drops the Q8 graphs of the state it frees
@@ -471,6 +480,10 @@ int  rama_q8_prefill(rama_ctx *ctx, const rama_config *cfg, const rama_q8_weight
  * rama_q8_forward(tokens[i], positions[i]) would leave in its cache rows and logits (x / xb / q ... not maintained) */
 int  rama_q8_decode_batch(rama_ctx *ctx, const rama_config *cfg, const rama_q8_weights *w, const rama_run_state *states,
                           const int32_t *tokens_host, const int32_t *positions_host, int n_seq);
+/* HOST-ONLY: 1 if the token-batch pass takes this shape (chain norm, and a context that fits the chain attention's score
+ * buffer), 0 if not: then rama_q8_prefill and rama_q8_decode_batch run one rama_q8_forward per token, and
+ * rama_q8_decode_batch_begin and rama_q8_serve_begin answer RAMA_EUNSUP.  Negative: a bad config. */
+int  rama_q8_batch_shape_ok(const rama_config *cfg);
 
 /* rama_q8_decode_batch CHAINED ON THE DEVICE, with per-sequence sampling, forced prompts, step budgets and stop tokens.
  * rama_q8_decode_batch_begin uploads every sequence's (token, position) and plan once; each step of

@@ -206,6 +206,8 @@ extern "C" {
                             out_tokens_host: *mut i32) -> c_int;
     pub fn rama_q8_matmul_batch(ctx: *mut rama_ctx, o: *mut f32, wq: *const i8, ws: *const f32, xq: *const i8, xs: *const f32,
                                 n: usize, d: usize, group_size: c_int, n_tok: c_int) -> c_int;
+    pub fn rama_q8_product_path(n: usize, group_size: c_int, n_tok: c_int, aligned16: c_int) -> c_int;
+    pub fn rama_q8_batch_shape_ok(cfg: *const rama_config) -> c_int;
     pub fn rama_q8_prefill(ctx: *mut rama_ctx, cfg: *const rama_config, w: *const rama_q8_weights, s: *mut rama_run_state,
                            tokens_host: *const i32, n_tokens: c_int, pos0: c_int) -> c_int;
     pub fn rama_q8_decode_batch(ctx: *mut rama_ctx, cfg: *const rama_config, w: *const rama_q8_weights, states: *const rama_run_state,

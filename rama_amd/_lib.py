@@ -188,6 +188,8 @@ SIGNATURES = {
     "rama_q8_model_free": (_int, [_vp, _vp]),
     "rama_q8_quantize": (_int, [_vp, _vp, _sz, _int, _vp, _vp]),
     "rama_q8_matmul": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _int]),
+    "rama_q8_product_path": (_int, [_sz, _int, _int, _int]),
+    "rama_q8_batch_shape_ok": (_int, [_cfgp]),
     "rama_q8_forward": (_int, [_vp, _cfgp, C.POINTER(rama_q8_weights), _sp, _int, _int]),
     "rama_q8_generate": (_int, [_vp, _cfgp, C.POINTER(rama_q8_weights), _sp, i32p, _int, _int, C.c_float, C.c_float, C.c_float, i32p]),
     "rama_q8_matmul_batch": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _int, _int]),

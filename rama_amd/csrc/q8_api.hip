@@ -90,12 +90,28 @@ static int launch_q8_quantize(rama_ctx* c, const float* x, int n, int gs, int8_t
     return 0;
 }
 
+// The kernel a Q8 product takes: the one statement of the dispatch rule (launch_q8_matvec and launch_q8_gemm ask it; so can a caller).
+// n_tok == 0 is the single-token matvec; a batch answers for one pass of min(n_tok, kQ8bMaxTok) tokens.  aligned16: the activations and
+// every matrix of the product start on a 16-byte boundary.  The fast matvec keeps kQ8Waves x 2 rows of group terms in 64 KiB of LDS.
+int rama_q8_product_path(size_t n, int group_size, int n_tok, int aligned16) {
+    REQUIRE(group_size > 0 && n > 0 && n % (size_t)group_size == 0 && n < ((size_t)1 << 31) && n_tok >= 0, RAMA_EINVAL,
+            "q8_product_path: group_size must divide n, n_tok >= 0");
+    const int K = (int)n, gs = group_size;
+    if (n_tok == 0) {
+        const size_t lds = (size_t)kQ8Waves * 2 * (K / gs) * sizeof(float);
+        return aligned16 && q8_matvec_fast_ok(K, gs) && lds <= 64 * 1024 ? RAMA_Q8_PATH_MATVEC : RAMA_Q8_PATH_MATVEC_GENERIC;
+    }
+    if (!aligned16 || !q8_gemm_mfma_ok(K, gs)) return RAMA_Q8_PATH_GEMM_GENERIC;
+    // few tokens: K split over the waves of a workgroup
+    return std::min(n_tok, kQ8bMaxTok) <= 32 && (gs == 32 || gs == 64) ? RAMA_Q8_PATH_GEMM_KSPLIT : RAMA_Q8_PATH_GEMM_MFMA;
+}
+
 template <int EPI>
 static int launch_q8_matvec(rama_ctx* c, Q8MatParams& p) {
     const int G = p.K / p.gs, nm = EPI == Q8EPI_SWIGLU ? 2 : p.nmat;
-    bool fast = q8_matvec_fast_ok(p.K, p.gs) && (size_t)kQ8Waves * 2 * G * sizeof(float) <= 64 * 1024 && aligned16(p.xq);
-    for (int m = 0; m < nm; m++) fast = fast && aligned16(p.w[m]);
-    if (fast) {
+    bool al = aligned16(p.xq);
+    for (int m = 0; m < nm; m++) al = al && aligned16(p.w[m]);
+    if (rama_q8_product_path((size_t)p.K, p.gs, 0, al) == RAMA_Q8_PATH_MATVEC) {
         const int tasks = EPI == Q8EPI_SWIGLU ? p.rows : (p.nmat * p.rows + 1) / 2;
         const size_t lds = (size_t)kQ8Waves * 2 * G * sizeof(float);
         RAMA_LAUNCH(c, (q8_matvec_kernel<2, EPI>), dim3((tasks + kQ8Waves - 1) / kQ8Waves), dim3(kQ8Waves * 64), lds, p);
@@ -335,8 +351,8 @@ int rama_q8_generate(rama_ctx* c, const rama_config* cfg, const rama_q8_weights*
 template <int EPI>
 static int launch_q8_gemm(rama_ctx* c, const Q8BatchParams& p) {
     const int nm = EPI == Q8EPI_SWIGLU ? 2 : p.nmat;
-    bool mf = q8_gemm_mfma_ok(p.K, p.gs) && aligned16(p.xq);
-    for (int m = 0; m < nm; m++) mf = mf && aligned16(p.w[m]);
+    bool al = aligned16(p.xq);
+    for (int m = 0; m < nm; m++) al = al && aligned16(p.w[m]);
     const int G = p.K / p.gs;
     const int total = EPI == Q8EPI_SWIGLU ? p.rows : p.nmat * p.rows;
     const int tiles = (p.rows + 15) / 16, tasks = EPI == Q8EPI_SWIGLU ? tiles : p.nmat * tiles;
@@ -345,13 +361,14 @@ static int launch_q8_gemm(rama_ctx* c, const Q8BatchParams& p) {
         q.n_tok = std::min(kQ8bMaxTok, p.n_tok - t0);
         q.xq = p.xq + (size_t)t0 * p.K; q.xs = p.xs + (size_t)t0 * G;
         for (int m = 0; m < 3; m++) if (q.o[m]) q.o[m] = p.o[m] + (size_t)t0 * p.ostride;
-        if (mf && q.n_tok <= 32 && (q.gs == 32 || q.gs == 64)) {      // few tokens: K split over the waves of a workgroup
+        const int path = rama_q8_product_path((size_t)q.K, q.gs, q.n_tok, al);
+        if (path == RAMA_Q8_PATH_GEMM_KSPLIT) {
             constexpr int RT = EPI == Q8EPI_SWIGLU ? 2 : 1;
 #define RAMA_Q8S(NT_, G32_) RAMA_LAUNCH(c, (q8_gemm_ksplit_kernel<NT_, EPI, G32_>), dim3(tasks), dim3(kQ8sWaves * 64), q8s_lds_bytes(NT_, RT, G32_), q)
             if (q.n_tok <= 16) { if (q.gs == 32) RAMA_Q8S(1, true); else RAMA_Q8S(1, false); }
             else { if (q.gs == 32) RAMA_Q8S(2, true); else RAMA_Q8S(2, false); }
 #undef RAMA_Q8S
-        } else if (mf) {
+        } else if (path == RAMA_Q8_PATH_GEMM_MFMA) {
             const dim3 grid((tasks + kQ8bWaves - 1) / kQ8bWaves), block(kQ8bWaves * 64);
 #define RAMA_Q8G(NT_) do { if (q.gs == 32) RAMA_LAUNCH(c, (q8_gemm_mfma_kernel<NT_, EPI, true>), grid, block, 0, q); \
                            else RAMA_LAUNCH(c, (q8_gemm_mfma_kernel<NT_, EPI, false>), grid, block, 0, q); } while (0)
@@ -393,6 +410,12 @@ static bool q8_batch_ok(const rama_config* cfg) {
     const int hs = cfg->dim / cfg->n_heads;
     if (!rmsnorm_chain_ok((size_t)cfg->dim) || !attn_chain_ok(hs, cfg->seq_len) || cfg->dim % 4) return false;
     return attn_chain_lds_bytes(hs, cfg->seq_len, attn_chain_waves(hs, false)) <= kAttnChainMaxLds;
+}
+
+int rama_q8_batch_shape_ok(const rama_config* cfg) {
+    REQUIRE(cfg, RAMA_EINVAL, "q8_batch_shape_ok: NULL argument");
+    const int rc = check_cfg(cfg); if (rc) return rc;
+    return q8_batch_ok(cfg) ? 1 : 0;
 }
 
 static int ensure_q8_batch_scratch(rama_ctx* c, const rama_config* cfg, int gs, Q8BatchScratch* b) {

@@ -144,6 +144,126 @@ def test_matmul_negative_zero_terms_start_from_plus_zero(dev):
     assert same_bits(got, want) and got.view(np.uint32)[0] == 0
 
 
+# ------------------------------------------------------------------ off the fast kernels: other group sizes, the LDS ceiling, misalignment
+
+from tests.q8_offlane_cases import MATVEC, MATVEC_GENERIC
+
+
+def product_path(dev, n, gs, n_tok, aligned):
+    return dev.lib.rama_q8_product_path(n, gs, n_tok, int(aligned))
+
+
+def harsh_groups(gs):
+    """the inputs of test_quantize_edge_cases_and_bad_group scaled to group size gs, one kind per group: ties (the last one in
+    the group's last element), a one-hot group, denormals, an all-zero group, a denormal ramp over the whole group"""
+    x = np.zeros((5, gs), np.float32)
+    x[0, 0] = 127.0
+    ties = [0.5, -0.5, 1.5, -1.5, 2.5, -2.5, 126.5, -126.5][:gs - 2]
+    x[0, 1:1 + len(ties)] = ties
+    x[0, gs - 1] = -63.5
+    x[1, min(3, gs - 1)] = -3.0
+    x[2, 0] = np.float32(1e-40); x[2, gs - 1] = np.float32(-5e-41)
+    x[4] = np.linspace(-1, 1, gs, dtype=np.float32) * np.float32(1e-39)
+    return x
+
+
+@pytest.mark.parametrize("gs", [8, 16, 48, 128, 256, 1024, 2048])
+def test_quantize_group_sizes_off_the_wave(dev, gs):
+    """groups smaller than a wave (one partial stride) and of several 64-lane strides; five groups leave the second workgroup
+    of four waves with one group, and every group also goes through alone (n = gs)"""
+    x = harsh_groups(gs)
+    wq, ws = R.quantize(x.reshape(-1), gs)
+    assert wq[gs - 1] == -64 and wq[0] == 127 and ws[3] == 0 and 0 < ws[2] < np.finfo(np.float32).tiny
+    rc, q, s = dev_quantize(dev, x.reshape(-1), gs)
+    assert rc == 0
+    assert np.array_equal(q, wq) and same_bits(s, ws), (gs, np.flatnonzero(q != wq)[:8])
+    for g in range(5):
+        rc, q, s = dev_quantize(dev, x[g], gs)
+        assert rc == 0
+        assert np.array_equal(q, wq[g * gs:(g + 1) * gs]) and same_bits(s, ws[g:g + 1]), (gs, g)
+    # random data over 5 groups on top of the planted ones
+    rng = np.random.default_rng(gs)
+    y = (rng.standard_normal(5 * gs) * rng.choice([1e-3, 1.0, 40.0], size=5 * gs)).astype(np.float32)
+    rc, q, s = dev_quantize(dev, y, gs)
+    wq, ws = R.quantize(y, gs)
+    assert rc == 0 and np.array_equal(q, wq) and same_bits(s, ws), gs
+
+
+def matmul_case(dev, d, n, gs, path):
+    """test_matmul_bit_identical's data recipe (an all-zero row, a row and its negation, all-zero activations) on a product
+    that must take `path`"""
+    assert product_path(dev, n, gs, 0, True) == path, (d, n, gs)
+    rng = np.random.default_rng(d * 7 + n)
+    G = n // gs
+    wq = rng.integers(-127, 128, size=d * n, dtype=np.int8)
+    ws = (rng.random(d * G, dtype=np.float32) * np.float32(0.01)).astype(np.float32)
+    x = rng.standard_normal(n).astype(np.float32)
+    xq, xs = R.quantize(x, gs)
+    if d >= 5:
+        wq[:n] = 0
+        wq[3 * n:4 * n] = -wq[2 * n:3 * n]
+        ws[3 * G:4 * G] = ws[2 * G:3 * G]
+    got = dev_matmul(dev, wq, ws, xq, xs, n, d, gs)
+    want = R.matmul(xq, xs, wq, ws, gs)
+    assert same_bits(got, want), (d, n, gs, np.flatnonzero(got.view(np.uint32) != want.view(np.uint32))[:8])
+    if d >= 5:
+        assert got.view(np.uint32)[0] == 0 and got[3] == -got[2]
+    zq, zs = R.quantize(np.zeros(n, np.float32), gs)
+    got = dev_matmul(dev, wq[:min(d, 64) * n], ws[:min(d, 64) * G], zq, zs, n, min(d, 64), gs)
+    assert not got.view(np.uint32).any()
+
+
+@pytest.mark.parametrize("d,n,gs", [(37, 72, 8), (9, 40, 8), (257, 96, 48), (20, 144, 24), (5, 64, 8), (33, 4096, 2048), (1, 72, 8)])
+def test_matmul_generic_kernel_bit_identical(dev, d, n, gs):
+    """q8_matvec_generic_kernel: K % 16 != 0, group sizes below 16, not a power of two, above 1024; 257 rows are two workgroups"""
+    matmul_case(dev, d, n, gs, MATVEC_GENERIC)
+
+
+@pytest.mark.parametrize("d,n,gs", [(37, 48, 16), (1, 48, 16), (255, 1040, 16), (33, 1536, 512), (19, 2048, 1024), (9, 32768, 16)])
+def test_matmul_fast_kernel_at_its_edges(dev, d, n, gs):
+    """q8_matvec_kernel where its group reduction degenerates (group size 16: one chunk per group, no shuffle) or spans the
+    wave (1024: 64 chunks); n = 1040 is 65 chunks, one past a wave; an odd d leaves the last task's second row empty;
+    (9, 32768, 16) is 2048 groups: exactly 64 KiB of dynamic LDS"""
+    matmul_case(dev, d, n, gs, MATVEC)
+
+
+def test_matmul_one_group_past_the_lds_ceiling_takes_the_generic_kernel(dev):
+    matmul_case(dev, 9, 32784, 16, MATVEC_GENERIC)
+
+
+def guarded_matmul(dev, wq, ws, xq, xs, n, d, gs, w_lead=0, x_lead=0):
+    """rama_q8_matmul with the weights / activations `lead` bytes into their allocations and the output between guard words
+    -> (result, guards untouched)"""
+    def lead(a, k):
+        return np.concatenate([np.full(k, 0x55, np.uint8), np.ascontiguousarray(a).view(np.uint8).reshape(-1)])
+    bw, bs, bx, bxs = Buf(dev, lead(wq, w_lead)), Buf(dev, ws), Buf(dev, lead(xq, x_lead)), Buf(dev, xs)
+    o = Buf(dev, np.full(d + 8, np.float32(7.0)))
+    rc = dev.lib.rama_q8_matmul(dev.ctx, o.p + 16, bw.p + w_lead, bs.p, bx.p + x_lead, bxs.p, n, d, gs)
+    out = o.get(np.float32, d + 8)
+    for b in (bw, bs, bx, bxs, o):
+        b.free()
+    assert rc == 0
+    return out[4:4 + d], bool((out[:4] == np.float32(7.0)).all() and (out[4 + d:] == np.float32(7.0)).all())
+
+
+def test_matmul_misaligned_weights_or_activations(dev):
+    """weights or activations 4 bytes off a 16-byte boundary: the bytewise kernel, the same bits, nothing written outside o"""
+    d, n, gs = 64, 4096, 64
+    assert product_path(dev, n, gs, 0, True) == MATVEC and product_path(dev, n, gs, 0, False) == MATVEC_GENERIC
+    rng = np.random.default_rng(64)
+    wq = rng.integers(-127, 128, size=d * n, dtype=np.int8)
+    ws = (rng.random(d * n // gs, dtype=np.float32) * np.float32(0.01)).astype(np.float32)
+    wq[:n] = 0
+    wq[3 * n:4 * n] = -wq[2 * n:3 * n]
+    ws[3 * (n // gs):4 * (n // gs)] = ws[2 * (n // gs):3 * (n // gs)]
+    xq, xs = R.quantize(rng.standard_normal(n).astype(np.float32), gs)
+    want = R.matmul(xq, xs, wq, ws, gs)
+    for w_lead, x_lead in ((0, 0), (4, 0), (0, 4)):
+        got, clean = guarded_matmul(dev, wq, ws, xq, xs, n, d, gs, w_lead, x_lead)
+        assert same_bits(got, want), (w_lead, x_lead)
+        assert clean, (w_lead, x_lead)
+
+
 # ------------------------------------------------------------------ loader
 
 def test_fixtures_load_and_match_file(dev, golden_dir):

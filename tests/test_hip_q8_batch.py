@@ -62,8 +62,10 @@ def check_rows(got, xq, xs, wq, ws, n, gs):
 
 
 # (n, d, gs): the matrix-core kernel at GS 32 (K = 32 mod 64 too), 64, 128, 256 with ragged rows; the bytewise kernel at
-# GS 48 and at K % 16 != 0
-SHAPES = [(256, 40, 32), (288, 37, 32), (512, 48, 64), (768, 33, 128), (1024, 64, 256), (4096, 19, 64), (96, 20, 48), (40, 9, 8)]
+# GS 48 and at K % 16 != 0; one group in one half-filled chunk; one group of 64 chunks (the largest the matrix-core kernel
+# takes) and one of 128 (bytewise)
+SHAPES = [(256, 40, 32), (288, 37, 32), (512, 48, 64), (768, 33, 128), (1024, 64, 256), (4096, 19, 64), (96, 20, 48), (40, 9, 8),
+          (32, 20, 32), (4096, 17, 4096), (8192, 17, 8192)]
 
 
 @pytest.mark.parametrize("n,d,gs", SHAPES)
@@ -77,6 +79,42 @@ def test_matmul_batch_bit_identical(dev, n, d, gs):
             assert not got[1].view(np.uint32).any()      # zero activations: every row +0.0
         if d >= 4:
             assert not got[:, 3].view(np.uint32).any()
+
+
+def test_new_shapes_take_the_paths_they_are_there_for(dev):
+    from tests.q8_offlane_cases import GEMM_GENERIC, GEMM_KSPLIT, GEMM_MFMA
+    P = dev.lib.rama_q8_product_path
+    assert [P(32, 32, t, 1) for t in (1, 17, 64, 130)] == [GEMM_KSPLIT, GEMM_KSPLIT, GEMM_MFMA, GEMM_MFMA]
+    assert [P(4096, 4096, t, 1) for t in (1, 17, 64, 130)] == [GEMM_MFMA] * 4
+    assert [P(8192, 8192, t, 1) for t in (1, 17, 64, 130)] == [GEMM_GENERIC] * 4
+
+
+@pytest.mark.parametrize("n,d,gs,n_tok", [(512, 48, 64, 17), (512, 48, 64, 40)])
+def test_matmul_batch_misaligned_weights_or_activations(dev, n, d, gs, n_tok):
+    """weights or activations 4 bytes off a 16-byte boundary: the bytewise kernel instead of the K-split (17 tokens) or the
+    matrix-core kernel (40), the same bits as the aligned call and the reference, nothing written outside o"""
+    from tests.q8_offlane_cases import GEMM_GENERIC, GEMM_KSPLIT, GEMM_MFMA
+    P = dev.lib.rama_q8_product_path
+    assert P(n, gs, n_tok, 1) == (GEMM_KSPLIT if n_tok <= 32 else GEMM_MFMA) and P(n, gs, n_tok, 0) == GEMM_GENERIC
+    wq, ws, xq, xs = q8_data(np.random.default_rng(n + n_tok), n, d, gs, n_tok)
+
+    def lead(a, k):
+        return np.concatenate([np.full(k, 0x55, np.uint8), np.ascontiguousarray(a).view(np.uint8).reshape(-1)])
+
+    aligned = None
+    for w_lead, x_lead in ((0, 0), (4, 0), (0, 4)):
+        bw, bs, bx, bxs = Buf(dev, lead(wq, w_lead)), Buf(dev, ws), Buf(dev, lead(xq, x_lead)), Buf(dev, xs)
+        o = Buf(dev, np.full(d * n_tok + 8, np.float32(7.0)))
+        rc = dev.lib.rama_q8_matmul_batch(dev.ctx, o.p + 16, bw.p + w_lead, bs.p, bx.p + x_lead, bxs.p, n, d, gs, n_tok)
+        out = o.get(np.float32, d * n_tok + 8)
+        for b in (bw, bs, bx, bxs, o):
+            b.free()
+        assert rc == 0
+        assert (out[:4] == np.float32(7.0)).all() and (out[-4:] == np.float32(7.0)).all(), (w_lead, x_lead)
+        got = out[4:-4].reshape(n_tok, d)
+        check_rows(got, xq, xs, wq, ws, n, gs)
+        aligned = got if aligned is None else aligned
+        assert same_bits(got, aligned), (w_lead, x_lead)
 
 
 def test_matmul_batch_equals_single_token_calls(dev):

@@ -2,12 +2,15 @@
 """Generate the Q8_0 (llama2.c version-2) fixtures of tests/golden/ with the REFERENCE's own exporter.
 
 Runs only in the build container, like tools/make_goldens.py: it imports the reference's model.py and
-export.py at run time and writes data only -- two tiny torch-initialised models written by
+export.py at run time and writes data only -- four tiny torch-initialised models written by
 ``export.version2_export`` and, next to each, an ``.npz`` with some of the fp32 weights it quantized (v0
 tensor names and shapes: the token table, wq, w2, the norms, an untied classifier), the config, the group size and the exporter's max error.
 
 * ckpt_v2_q80_tied.bin    the make_ckpt_case shape (dim 32, hidden 96): the group size backs off 64 -> 32
 * ckpt_v2_q80_untied.bin  dim 64, hidden 192, 4 heads, seq_len 32, group size 64, non-unit norm gains
+* ckpt_v2_q80_gs16.bin    dim 48, hidden 80, 3 heads, vocab 50, seq_len 40, tied: the group size backs off 64 -> 32 -> 16
+* ckpt_v2_q80_gs8.bin     dim 72, hidden 200, 2 heads (head size 36), vocab 37, seq_len 24, untied: the group size backs off
+                          to 8, and no row is a multiple of 16 bytes (the bytewise kernels' model)
 
 Usage:  python tools/make_q8_goldens.py
 """
@@ -63,7 +66,7 @@ def fp32_weights(m) -> dict:
     return w
 
 
-def make(name, shared, seed, **shape):
+def make(name, shared, seed, want_gs, **shape):
     m = build(shared=shared, seed=seed, **shape)
     w = fp32_weights(m)
     path = OUT / f"{name}.bin"
@@ -72,6 +75,8 @@ def make(name, shared, seed, **shape):
         ref_export.version2_export(m, str(path), group_size=64)
     maxerr = max(float(ln.rsplit(" ", 1)[1]) for ln in log.getvalue().splitlines() if "with max error" in ln)
     gs = int(np.frombuffer(path.read_bytes()[37:41], "<i4")[0])
+    if gs != want_gs:
+        sys.exit(f"{name}: the exporter wrote group size {gs}, the fixture is meant to have {want_gs}")
     cfg = np.array([shape["dim"], shape["hidden"], shape["n_layers"], shape["n_heads"], shape["n_heads"], shape["vocab"],
                     shape["seq_len"], int(shared)], np.int32)
     keep = {k: w[k] for k in KEEP + (("wcls",) if not shared else ())}
@@ -80,5 +85,7 @@ def make(name, shared, seed, **shape):
 
 
 if __name__ == "__main__":
-    make("ckpt_v2_q80_tied", True, 1234, dim=32, hidden=96, n_layers=2, n_heads=2, vocab=64, seq_len=16)
-    make("ckpt_v2_q80_untied", False, 4321, dim=64, hidden=192, n_layers=2, n_heads=4, vocab=64, seq_len=32)
+    make("ckpt_v2_q80_tied", True, 1234, 32, dim=32, hidden=96, n_layers=2, n_heads=2, vocab=64, seq_len=16)
+    make("ckpt_v2_q80_untied", False, 4321, 64, dim=64, hidden=192, n_layers=2, n_heads=4, vocab=64, seq_len=32)
+    make("ckpt_v2_q80_gs16", True, 1616, 16, dim=48, hidden=80, n_layers=2, n_heads=3, vocab=50, seq_len=40)
+    make("ckpt_v2_q80_gs8", False, 808, 8, dim=72, hidden=200, n_layers=2, n_heads=2, vocab=37, seq_len=24)
