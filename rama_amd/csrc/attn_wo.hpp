@@ -8,24 +8,13 @@
 // (checked with the occupancy API by the host), every spin is bounded.
 #pragma once
 #include "kernels.hpp"
+#include "handoff.hpp"          // st_sc1 / ld_sc1 / ld4_sc1
 
 namespace rama {
 
 constexpr int kPWaves = 8;
 constexpr int kPThreads = kPWaves * 64;
 constexpr int kPAttnU = 4;    // cache rows in flight per lane in the attention phase
-
-// ---- sc1 (write-through / L1-bypassing) accessors for inter-workgroup data
-__device__ __forceinline__ void st_sc1(float* p, float v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float ld_sc1(const float* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ f4 ld4_sc1(__amdgpu_buffer_rsrc_t r, unsigned off) {
-    return __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 16));   // cpol sc1
-}
-
 
 struct AttnHeadArgs { int dim, n_heads, seq_len; const float* q; float* xb; };
 

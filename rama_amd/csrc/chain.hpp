@@ -28,13 +28,13 @@
 // Results are bit-identical to ref_order.hpp's and to the oracle's (tests/test_hip_ref_order.py,
 // tests/test_hip_parity_7b.py).
 #pragma once
-#define RAMA_CHAIN_HPP 1      // (q8_api.hip refuses to be compiled with this header: DESIGN.md section 9)
+#define RAMA_CHAIN_HPP 1      // (rama_api.hip and q8_api.hip refuse to be compiled with this header: its kernels are chain_api.hip's)
 #include "kernels.hpp"
+#include "chain_params.hpp"     // ChainParams, GemmChainParams, CEPI_* / CNORM_*, the LDS sizes: what the launchers' callers see
 #include "ref_order.hpp"
 #include "topp_sort.hpp"
 #include "seqsum_fast.hpp"
-#include "layer_fused.hpp"      // put_tagged, the epoch / error-word conventions of in-launch hand-offs
-#include "attn_wo.hpp"          // st_sc1 / ld4_sc1: write-through stores and L1-bypassing loads of in-launch hand-offs
+#include "handoff.hpp"          // put_tagged: the leader norm's word follows layer_fused.hpp's epoch / error-word conventions
 
 namespace rama {
 
@@ -417,7 +417,6 @@ __device__ __forceinline__ bool seq_sum_predict(const float* a, int n, PredShare
 // ---------------------------------------------------------------- cpu.rs:99-117 rmsnorm, one workgroup
 // o[i] = w[i] * (v * x[i]), v = 1 / sqrt(sum(x^2) / n + 1e-5) with the sum in index order.  copy_to, when
 // given, receives x unchanged first (infer.rs:49: xb = x before the final norm writes x in place).
-constexpr int kNormMax = 16384;
 #ifndef RAMA_NORM_WAVES
 #define RAMA_NORM_WAVES 4
 #endif
@@ -537,32 +536,7 @@ __global__ __launch_bounds__(kNormThreads) void softmax_chain_kernel(float* x, i
     for (int i = tid; i < n; i += kNormThreads) x[i] = s_e[scan_slot(i)] / sum;
 }
 
-// ---------------------------------------------------------------- cpu.rs:127-153 matmul on chain-order weights
-enum { CEPI_STORE = 0, CEPI_RESID = 1, CEPI_QKV = 2, CEPI_SWIGLU = 3 };
-
-struct ChainParams {
-    const float* w[3];     // chain-order matrices (nmat <= 3), each [ceil(rows/16)*16, K]
-    float* o[3];           // STORE: o[0]; RESID: o[0] = the product (xb2 / xb); QKV: q, k, v; SWIGLU: o[0] = hb, o[1] = hb2
-    const float* x;        // [K] activations, row-major
-    const float* nw;       // NORM: rmsnorm gain [K]; x is then the residual stream and the kernel normalises it itself
-    float* resid;          // RESID: resid[r] += product (infer.rs:37,47)
-    int K, rows, nmat;     // SWIGLU: rows = 2 * hidden (interleaved W1 | W3)
-    const Ctl* ctl; int pos_val;
-    const float* fr; const float* fi; int head_size;
-    float* kc; float* vc;  // this layer's cache slabs [seq, dim]
-    // CNORM_LEAD: workgroup 0 of the launch forms v = 1 / sqrt(sum(x^2) / K + 1e-5) (the sum in index order) and publishes it as ONE tagged word;
-    // the others request their weights, then wait for it (layer_fused.hpp's put_tagged / epoch / error word)
-    // ([r5] measured and not kept, profiles/r05_experiments.md: 16 copies of the word on different channels -1.8 %; the leader's compute unit kept free of
-    // other workgroups and its waves at priority 3: the word is there 1.1-2 us earlier, the launch no shorter)
-    unsigned long long* lead; const unsigned* epoch; unsigned long long* err;
-    // half_from > 0 ([r5] one wave per row group): the row groups from this index on are walked as TWO workgroups of 8 rows each (lanes 0..31; the
-    // chain-order block of 16 rows is two halves of 512 bytes).  A compute unit streams ~28 GB/s whatever the rest of the chip does, so a launch whose
-    // row groups do not divide by the compute units ends when the CUs with one group more are through: llama2-7B's W1|W3 is 1 376 groups on 256 CUs,
-    // six on 96 of them and five on the rest; with the last 96 groups as 192 halves it is five and a half at most.
-    int half_from;
-    float* xout;           // CNORM_LEAD: the leader also stores the normalised vector here (a Device::rmsnorm recorded in front of the run, rama_api.hip flush_mm)
-    int lane_reduce;       // [r6] the order of cpu.rs:148 `v.reduce_add()`: LANES_PAIRWISE | LANES_STRIDED | LANES_SEQUENTIAL (ref_order.hpp; "lane_reduce")
-};
+// ---------------------------------------------------------------- cpu.rs:127-153 matmul on chain-order weights (ChainParams: chain_params.hpp)
 
 // a descriptor whose inputs the compiler must take as wave-uniform (they are: kernel arguments and blockIdx)
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc_uniform(const void* p, unsigned bytes) {
@@ -582,8 +556,6 @@ __device__ __forceinline__ f4 ld_nt_s(__amdgpu_buffer_rsrc_t r, unsigned voff, u
 // 4 x 48 loads per CU lasts 4.8 us, 2 x 32 lasts 0.8 -- so deeper rings only delay the first turn; in steady state
 // every geometry streams at 6.2-6.9 TB/s and what separates a launch from bytes / 6.9 TB/s is ~2.3 us of start
 // (the first HBM round trip under the burst of every CU's ring) and ~2 us of tail and launch gap.
-// XD = activation blocks read ahead from LDS.  Dynamic LDS: K + chain_pad_floats(W, D, XD) floats.
-__host__ __device__ constexpr int chain_pad_floats(int W, int D, int XD) { return 16 * ((W + 1) * D + XD); }   // everything the x ring can touch
 // time stamps of one wave for tools/chain_bench.hip only (100 MHz counter; lane 0 of wave 0 of block RAMA_CHAIN_STAMP_BLOCK)
 #ifdef RAMA_CHAIN_STAMPS
 __device__ unsigned long long g_chain_stamps[64];
@@ -611,7 +583,6 @@ __device__ unsigned long long g_chain_all[3 * 4096];
 //     workgroup requests x, the gain and its first ring of weights, waits for the word and stages w * (v * x) itself.  What a norm launch of its
 //     own costs (its 7.8 us + a launch boundary on either side + the consumer's cold first round trip behind it) shrinks to the leader's
 //     x round trip + the sum + one hand-off, with the consumers' first weights already in registers when v arrives.
-enum { CNORM_NONE = 0, CNORM_EXACT = 1, CNORM_TREE = 2, CNORM_LEAD = 3 };
 
 constexpr unsigned long long kLeadErr = 0x3100ull;                // error word: a wait for the leader's word gave up
 // (the body of gemv_chain_kernel; `bid_in` = the workgroup's index.  [r5] As a PHASE of merged launches -- a consumer waiting for tagged words of
@@ -973,21 +944,6 @@ __global__ __launch_bounds__(W * 64) void gemv_chain_kernel(ChainParams p) {
 //   layer.  Bound by the latency of the dependent adds (four independent pair-chains per wave), not by HBM (3.5 TB/s)
 //   and not by the instruction count.
 //   Blocks behind the end of a row: weights dropped by the descriptor's range check, activations stored as zeros: + (0 * 0).
-struct GemmChainParams {
-    const float* w[3];      // chain-order matrices (nmat <= 3), each [ceil(rows / 16) * 16, K]
-    int nmat, K, rows;      // SWIGLU: rows = 2 * hidden (interleaved W1 | W3)
-    const float* x; int xstride;          // activations [n_tok][xstride], row-major
-    float* o[3]; int ostride;             // STORE / RESID: o[0][t][row] (RESID: may be NULL); QKV: q = o[0]; SWIGLU: hb = o[0][t][row / 2]
-    float* resid; int rstride;            // RESID: resid[t][row] += product (infer.rs:37,47)
-    int n_tok;
-    int pos0; const float* fr; const float* fi; int head_size; float* kc; float* vc;      // QKV: token t sits at pos0 + t; this layer's cache slabs
-    const SeqSlot* seqs; size_t layer_off;   // QKV, independent sequences: token t at seqs[t].pos, its caches at seqs[t].kc / .vc + layer_off
-    int lane_reduce;        // [r6] as ChainParams::lane_reduce
-};
-constexpr int kGcWaves = 4, kGcThreads = kGcWaves * 64;
-constexpr int kGcBlocks = 8;             // blocks of 16 floats per chunk (8 KiB of weights; 32 KiB of LDS per workgroup at 16 tokens: four workgroups per CU)
-constexpr int kGcSets = 2;               // chunks in flight in registers
-__host__ __device__ constexpr size_t gemm_chain_lds_bytes(int tpw) { return 2 * ((size_t)kGcBlocks * 1024 + (size_t)(kGcWaves * tpw) * kGcBlocks * 64); }
 
 // a * w with a taken from lane I of the caller's DPP row (16 lanes): one v_mul_f32 with the row broadcast on its source
 // operand -- the rounded product of the reference's separate multiply.  (As assembly: hipcc would pack the multiplies of two
@@ -1202,17 +1158,6 @@ __global__ __launch_bounds__(kGcThreads) void gemm_chain_kernel(GemmChainParams 
 //    nothing can shorten.  So everything else leaves the chain: all threads load tiles of kAttTile cache rows and
 //    store the PRODUCTS att[t] * v[t][i] (rounded, as the reference's `a * vi`) in LDS, two tiles in turn (one
 //    barrier per tile), and thread i < head_size only adds them up in row order.
-constexpr int kAttTile = 64;
-constexpr int kAttPiece = 32;                 // floats of a row per staged piece
-constexpr int kAttStride = kAttPiece + 4;     // row pitch of a staged piece (16-byte aligned, conflict-free row reads)
-__host__ __device__ constexpr size_t attn_chain_region_floats(int head_size, int nw) {
-    return (size_t)(nw * 64 * kAttStride) > (size_t)(2 * kAttTile * head_size) ? (size_t)(nw * 64 * kAttStride) : (size_t)(2 * kAttTile * head_size);
-}
-__host__ __device__ constexpr size_t attn_chain_lds_floats(int head_size, int seq_len, int nw) {
-    return (size_t)((head_size + 3) & ~3) + (size_t)seq_len + (size_t)(seq_len >> 5) + 4 + (size_t)((seq_len + 3) & ~3) + attn_chain_region_floats(head_size, nw);
-}
-// the value tiles are loaded with 8 x 16 bytes per thread
-__host__ __device__ constexpr bool attn_chain_fits(int head_size, int nw) { return kAttTile * (head_size / 4) <= (nw >= 16 ? 4 : 8) * 64 * nw; }
 
 // (the body of attention_chain_kernel: head h of token y.  lds_seq = the timesteps the LDS arrays are laid out for.
 // [r5] forms of this body that ran inside merged launches -- xb handed to Wo groups of the same launch, q | k | v taken as tagged words from
@@ -1631,7 +1576,6 @@ constexpr int kFvRows = 192, kFvStride = kFvRows + 4, kFvWaves = 4;
 #define RAMA_FV_SOFT 8
 #endif
 constexpr int kFvSoftWaves = RAMA_FV_SOFT;        // [r5] waves of the softmax phase (waves kFvWaves.. leave after it): its loops are a few elements per thread, each with its latency in full
-__host__ __device__ constexpr size_t attn_fused_values_lds_floats(int seq_len) { return (size_t)seq_len + ((size_t)seq_len >> 5) + 4 + (((size_t)seq_len + 3) & ~(size_t)3); }
 // ([r5] the scores formed by extra waves of the same launch -- ONE launch for the whole spread attention -- is bit-identical and 0.3-1.3 us slower per
 // layer: profiles/r05_experiments.md section 12, profiles/r06_lost_experiments.patch)
 static_assert(kFvSoftWaves >= kFvWaves && kFvSoftWaves <= 8, "the value chain's assembly names v200..v247: at most 8 waves per workgroup (256 VGPRs a wave)");

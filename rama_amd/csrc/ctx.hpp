@@ -1,14 +1,15 @@
-// ctx.hpp -- what the library's C-ABI translation units (rama_api.hip, q8_api.hip) share: the context, the error plumbing, graph capture,
-// the launch macros, and declarations of the launchers that stay defined in rama_api.hip.  Internal: not installed, not part of the C ABI.
+// ctx.hpp -- what the library's C-ABI translation units (rama_api.hip, chain_api.hip, q8_api.hip) share: the context, the error plumbing, graph
+// capture, the launch macros, and declarations of what each defines for the others.  Internal: not installed, not part of the C ABI.
 //
 // The library is built WITHOUT relocatable device code, so a kernel or a __device__ global lives in the code object of the translation
 // unit that instantiates / defines it (DESIGN.md "Translation units").  Hence the launchers below: whoever needs attention_chain_kernel,
-// rmsnorm_chain_kernel or the sampler's kernels calls the one translation unit that owns them.
+// rmsnorm_chain_kernel or the sampler's kernels calls chain_api.hip, the one translation unit that owns them.
 #pragma once
 #include "../../include/rama_hip.h"
 #include "kernels.hpp"
 #include "topp_sort.hpp"        // ToppRow, ToppStats, ToppBatchParams
 #include "ref_order.hpp"        // RefAttnParams
+#include "chain_params.hpp"     // ChainParams, GemmChainParams, CEPI_* / CNORM_*
 #include "q8_serve_tables.hpp"  // ServeTables
 
 #include <hip/hip_ext.h>   // hipExtLaunchKernelGGL: start/stop events carried by the dispatch itself
@@ -287,24 +288,37 @@ int flush_pending(rama_ctx* c);
 int check_cfg(const rama_config* cfg);
 int handoff_check(rama_ctx* c);
 int replay_graph(rama_ctx* c, const CapturedGraph& g);
+void drop_graph(rama_ctx* c);      // every captured graph of the context (scratch a graph holds is about to move); exported as rama_internal_drop_graphs
 
-bool rmsnorm_chain_ok(size_t n);
-int launch_rmsnorm_chain(rama_ctx* c, float* o, const float* x, const float* w, int n, float* copy_to, int batch = 1, int stride = 0);
 int launch_rmsnorm_ref(rama_ctx* c, float* o, const float* x, const float* w, int n);
-
-int attn_chain_waves(int head_size, bool long_ctx);
-bool attn_chain_ok(int head_size, int seq_len);
-size_t attn_chain_lds_bytes(int head_size, int seq_len, int nw);      // dynamic LDS of attention_chain_kernel<nw>
-int launch_attention_chain(rama_ctx* c, float* xb, float* att, const float* q, const float* kc_layer, const float* vc_layer,
-                           const Ctl* ctl, int pos, int dim, int head_size, int seq_len, int n_heads, bool long_ctx = false, bool spread_wanted = false);
 int launch_attention_ref(rama_ctx* c, float* xb, float* att, const float* q, const float* kc_layer, const float* vc_layer,
                          const Ctl* ctl, int pos, int dim, int head_size, int seq_len, int n_heads);
-int launch_attention_chain_tokens(rama_ctx* c, const RefAttnParams& a, int n_heads, int nt, int nw, size_t lds);
 
 int stage_tokens(rama_ctx* c, int* toks_dev, const int32_t* tokens_host, int n, SeqSlot* seqs_dev = nullptr,
                  const rama_run_state* states = nullptr, const int32_t* pos_host = nullptr);
 int copy_out_logits(rama_ctx* c, const rama_run_state* states, const float* lg, int n, int V);
 
+// ---------------------------------------------------------------- defined in chain_api.hip: parity mode's launches (chain.hpp) and the samplers
+
+int chain_api_init(rama_ctx* c);      // rama_ctx_create: the dynamic-LDS attributes of attention_chain_kernel and gemm_chain_kernel
+
+// epi: CEPI_*; norm: CNORM_*.  A pair no caller uses has no kernel: RAMA_EINVAL
+int launch_chain(rama_ctx* c, ChainParams& p, int epi, int norm = CNORM_NONE);
+int launch_gemm_chain(rama_ctx* c, GemmChainParams& p, int epi);
+
+bool rmsnorm_chain_ok(size_t n);      // (softmax_chain_kernel's limit too)
+int launch_rmsnorm_chain(rama_ctx* c, float* o, const float* x, const float* w, int n, float* copy_to, int batch = 1, int stride = 0);
+int launch_softmax_chain(rama_ctx* c, float* x, int n);
+
+int attn_chain_waves(int head_size, bool long_ctx);
+bool attn_chain_ok(int head_size, int seq_len);
+size_t attn_chain_lds_bytes(int head_size, int seq_len, int nw);      // dynamic LDS of attention_chain_kernel<nw>
+int ensure_attn_scores(rama_ctx* c, int n_heads, int seq_len);
+int launch_attention_chain(rama_ctx* c, float* xb, float* att, const float* q, const float* kc_layer, const float* vc_layer,
+                           const Ctl* ctl, int pos, int dim, int head_size, int seq_len, int n_heads, bool long_ctx = false, bool spread_wanted = false);
+int launch_attention_chain_tokens(rama_ctx* c, const RefAttnParams& a, int n_heads, int nt, int nw, size_t lds);
+
+int topp_dist_check(rama_ctx* c);     // handoff_check: the distributed pick's error word
 int enqueue_sample(rama_ctx* c, ArgmaxParams fin, float temperature, float topp, float u);
 int ensure_topp_scratch(rama_ctx* c, int n);
 int ensure_topp_batch(rama_ctx* c, int rows, int n);

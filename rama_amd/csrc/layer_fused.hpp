@@ -59,12 +59,7 @@ __device__ unsigned long long g_fused_stamps[8][6][8];
 // before: by the sampler's last thread in the chained decode loop (kernels.hpp finish_step), by this kernel otherwise.
 __global__ void fused_epoch_kernel(unsigned* epoch) { *epoch = *epoch + 1u; }
 
-__device__ __forceinline__ void put_tagged(tagged_t* p, float v, unsigned epoch) {
-    __hip_atomic_store(p, ((tagged_t)epoch << 32) | (tagged_t)__float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float get_tagged(const tagged_t* p) {      // a word some phase before the awaited one wrote
-    return __uint_as_float((unsigned)__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
+// (put_tagged / get_tagged: handoff.hpp, through attn_wo.hpp)
 
 // one lane: wait (sleeping) until the word at p carries `epoch` -- the cheap wait of workgroups far ahead of the data
 __device__ __forceinline__ void fused_watch(const tagged_t* p, unsigned epoch, unsigned long long* err) {

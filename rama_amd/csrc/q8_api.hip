@@ -1,6 +1,6 @@
 // q8_api.hip -- the Q8 part of the C ABI of include/rama_hip.h: rama_q8_quantize / _matmul, the Q8 forward and generate, the token
 // batches (prefill, decode batch), the chained batch and the serving chain.  The kernels are q8.hpp, q8_batch.hpp, q8_serve.hpp and
-// q8_fork.hpp; parity mode's norms and attention and the samplers are reached through the launchers of ctx.hpp, which rama_api.hip
+// q8_fork.hpp; parity mode's norms and attention and the samplers are reached through the launchers of ctx.hpp, which chain_api.hip
 // defines -- this translation unit instantiates none of their kernels (DESIGN.md "Translation units").
 #include "ctx.hpp"
 #include "q8.hpp"
@@ -9,7 +9,7 @@
 #include "q8_fork.hpp"
 
 #ifdef RAMA_CHAIN_HPP
-#error "q8_api.hip must not include chain.hpp: its kernels and g_pred_stats belong to rama_api.hip's code object"
+#error "q8_api.hip must not include chain.hpp: its kernels and g_pred_stats belong to chain_api.hip's code object"
 #endif
 
 #include <algorithm>

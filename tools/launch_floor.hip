@@ -3,6 +3,7 @@
 // dependent launches per token) is up against.  Build: hipcc --offload-arch=gfx950 -O3 -o launch_floor tools/launch_floor.hip
 #include "../rama_amd/csrc/kernels.hpp"
 #include "../rama_amd/csrc/ops_kernels.hpp"
+#include "../rama_amd/csrc/topp_kernels.hpp"      // argmax_kernel
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
