@@ -211,6 +211,12 @@ SIGNATURES = {
     "rama_q8_serve_end": (_int, [_vp]),
 }
 
+# exported but not in the header (the rama_internal_* accessors tests read; most declare their own types where they call them): here
+# because ctypes would otherwise cut a 64-bit result down to an int
+INTERNAL_SIGNATURES = {
+    "rama_internal_op_launches": (C.c_ulonglong, [_vp, _int]),
+}
+
 _lib = None
 
 
@@ -223,7 +229,7 @@ def load() -> C.CDLL:
         raise RamaError(f"{LIB_PATH} not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
                         f"or `make -C rama_amd/csrc`")
     L = C.CDLL(str(LIB_PATH))
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **INTERNAL_SIGNATURES}.items():
         fn = getattr(L, name)          # AttributeError if the library lacks a declared symbol
         fn.restype, fn.argtypes = res, args
     _lib = L

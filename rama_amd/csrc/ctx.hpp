@@ -64,6 +64,39 @@ struct GraphCache {
     unsigned long long copies_gen = 0; // model.hip's generation of derived weight copies at capture: a graph holds their addresses, and ANOTHER context may free them
 };
 
+// The peephole recorder of the 1:1 Device<T> ops (rama_api.hip "the 1:1 op recorder"): an op entry may RECORD its call instead of launching it, and
+// the next entry either folds its own call into what is recorded or issues what is recorded first.  Whatever else enters the library issues it too
+// (RAMA_ENTER, flush_pending).  Only on a stream the context owns; every record has its switch among rama_ctx's tune_* ("rope_batch" = 0: every
+// call a launch, ...).
+//
+//   rope  [r5] a run of Device::apply_position calls on consecutive heads (infer.rs:25-29: n_heads calls per layer, 1 024 per llama2-7B token, each a
+//         launch of its own) is ISSUED AS ONE LAUNCH: a call only records (q, k, table rows, head size), the next call extends the run when it
+//         continues it ("rope_batch")
+//   mm    a run of up to three parity-mode Device::matmul calls with the same activations and shape on chain-order copies (infer.rs:20-23: Wq, Wk,
+//         Wv; :41-42: W1, W3): one launch over all their row groups ("matmul_batch").  A Device::array_add of a recorded matmul's output becomes
+//         that launch's residual epilogue ("resid_fold")
+//   nrm   a parity-mode Device::rmsnorm waits for the run of matmuls on its output (infer.rs:19-23, :40-42): the run's launch then carries the norm
+//         as its leader workgroup (chain.hpp CNORM_LEAD: the exact sum of squares while the row groups' weights are already on their way), and
+//         the leader also stores the normalised vector the call was asked for; mm.norm says that the pending run takes it.  No run on its output:
+//         the norm is a launch of its own ("norm_fold").  The leader's tagged words rotate through a range of their own (lead_next, the second
+//         half of rama_ctx::lead_slots); the epoch advances when the range wraps
+//   ew    Device::sinu waits for the Device::array_mult on the same vector (infer.rs:44-45), one Device::copy_from_slice for the next (:32-33): one
+//         launch per pair ("ew_batch")
+//
+// THE INVARIANT.  Pending together may be: a norm and the run of matmuls on its output; a run of three matmuls, the rotations of its first two
+// outputs over their heads and the copy of its second output into a cache row (infer.rs:20-33, which the second copy turns into ONE launch with the
+// Wq|Wk|Wv epilogue: "qkv_fold").  Otherwise at most ONE record is pending: whoever records issues the others first.  Records are issued in the
+// order they can have been made: the norm and the run, the rotations, the elementwise op (flush_pending).
+struct PendingOps {
+    struct { float* q = nullptr; float* k = nullptr; const float* pr = nullptr; const float* pi = nullptr; int hs = 0, count = 0; } rope;
+    struct { const float* w[3]; float* o[3]; const float* x = nullptr; int K = 0, rows = 0, count = 0; bool norm = false; } mm;
+    struct { float* o = nullptr; const float* x = nullptr; const float* w = nullptr; int n = 0; bool on = false; } nrm;
+    struct { int kind = 0; float* t = nullptr; const float* s = nullptr; size_t n = 0; } ew;      // 1: sinu(t, n); 2: copy(t, s, n)
+    int lead_next = 0;                     // the leader word the next recorded norm takes
+    unsigned long long op_launches = 0;    // launches made for the 1:1 op entries and by flush_pending (rama_internal_op_launches): a fold that stops happening shows here
+    int any() const { return rope.count | mm.count | ew.kind | (int)nrm.on; }
+};
+
 struct rama_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -178,29 +211,13 @@ struct rama_ctx {
     int tune_chain_split = 1;              // parity mode: the row groups that do not divide by the compute units walked as half groups (chain.hpp half_from)
     int tune_chain_lead_w = 0;             // parity mode: waves per row group of the launches with a leader norm (0: by the number of row groups)
     int tune_chain_resid_d = -1;           // parity mode: 100 W + D for the residual products (Wo, W2) only; 0: by the number of row groups like the others; -1: W = 1, D = 32 when a CU holds one group
-    // [r5] a run of Device::apply_position calls on consecutive heads (infer.rs:25-29: n_heads calls per layer, 1 024 per llama2-7B token, each a launch of
-    // its own) is ISSUED AS ONE LAUNCH: a call only records (q, k, table rows, head size); the next call extends the run when it continues it, and
-    // whatever enters the library next issues it first (RAMA_ENTER).  Only on a stream the context owns ("rope_batch" = 0: every call a launch).
-    struct { float* q = nullptr; float* k = nullptr; const float* pr = nullptr; const float* pi = nullptr; int hs = 0, count = 0; } rope;
-    int tune_rope_batch = 1;
-    // ... and so is a run of up to three parity-mode Device::matmul calls with the same activations and shape on chain-order copies (infer.rs:20-23: Wq, Wk,
-    // Wv; :41-42: W1, W3): one launch over all their row groups ("matmul_batch")
-    struct { const float* w[3]; float* o[3]; const float* x = nullptr; int K = 0, rows = 0, count = 0; bool norm = false; } mm;
-    int tune_matmul_batch = 1;
-    // ... and a parity-mode Device::rmsnorm waits for the run of matmuls on its output (infer.rs:19-23, :40-42): the run's launch then carries the norm as
-    // its leader workgroup (chain.hpp CNORM_LEAD: the exact sum of squares while the row groups' weights are already on their way), and the leader also
-    // stores the normalised vector the call was asked for.  Anything else entering the library issues the norm as its own launch first ("norm_fold").
-    // The leader's tagged words rotate through a range of their own; the epoch advances when the range wraps.
-    struct { float* o = nullptr; const float* x = nullptr; const float* w = nullptr; int n = 0; bool on = false; } nrm;
-    int tune_norm_fold = 1;
-    int tune_qkv_fold = 1;                 // ... and a run of three matmuls, the apply_position calls over all heads of its first two outputs and the copies of its last two into cache
-                                           // rows (infer.rs:20-33) are ONE launch with the Wq|Wk|Wv epilogue (rotation, cache rows)
-    int tune_resid_fold = 1;               // ... and a Device::array_add of a recorded matmul's output becomes that launch's residual epilogue
-    int op_lead_next = 0;
-    // ... and Device::sinu waits for the Device::array_mult on the same vector (infer.rs:44-45), one Device::copy_from_slice for the next (:32-33): one
-    // launch per pair ("ew_batch").  At most ONE of the three records is pending at any time: whoever records flushes the others first.
-    struct { int kind = 0; float* t = nullptr; const float* s = nullptr; size_t n = 0; } ew;      // 1: sinu(t, n); 2: copy(t, s, n)
-    int tune_ew_batch = 1;
+    PendingOps rec;                        // the recorded 1:1 ops (above); the switches of what it may record and fold:
+    int tune_rope_batch = 1;               // runs of apply_position calls are recorded
+    int tune_matmul_batch = 1;             // runs of parity-mode matmuls are recorded
+    int tune_norm_fold = 1;                // a parity-mode rmsnorm waits for the run on its output
+    int tune_qkv_fold = 1;                 // Wq|Wk|Wv, the rotations over all heads and the two cache copies as one launch
+    int tune_resid_fold = 1;               // an array_add of a recorded matmul's output becomes that launch's residual epilogue
+    int tune_ew_batch = 1;                 // sinu and copy_from_slice are recorded
     int tune_chain_views = 1;              // parity mode, Device::matmul on a matrix of no model: a chain-order copy of the tensor is made on first use
     int tune_prefill_chain = 1;            // parity mode: prompt positions go through the chain-order token-batch kernels (32 per weight pass); 0: one forward() each
     size_t pf_floats = 0;
@@ -333,7 +350,7 @@ void release_q8(rama_ctx* c);                                   // rama_ctx_dest
 
 // the pending run of recorded 1:1 ops is issued by whatever enters the library next: first statement of every entry point
 // that enqueues, synchronises or changes a setting
-#define RAMA_PENDING(c) ((c)->rope.count | (c)->mm.count | (c)->ew.kind | (int)(c)->nrm.on)
+#define RAMA_PENDING(c) ((c)->rec.any())
 #define RAMA_ENTER(c) do { if ((c) && RAMA_PENDING(c)) { const int rf_ = flush_pending(c); if (rf_) return rf_; } } while (0)
 
 // g = the launches `enqueue` puts on the stream, captured and instantiated (whatever g held goes first).  The capture always ends -- a stream

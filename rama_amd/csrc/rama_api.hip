@@ -22,6 +22,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 using namespace rama;
@@ -62,17 +63,20 @@ void destroy_graph(CapturedGraph& g) {
 }
 
 int set_device(rama_ctx* c) { HIPCHK(hipSetDevice(c->device)); return 0; }
-// the pending run of apply_position calls (rama_ctx::rope) is issued by whatever enters the library next: first statement of every entry point
-// that enqueues, synchronises or changes a setting
-static int flush_rope(rama_ctx* c);
-static int flush_mm(rama_ctx* c);
-static int flush_ew(rama_ctx* c);
-// (in the order they were recorded: a norm and the run of matmuls on it, the rotations of that run's q and k, a copy -- see rama_copy_from_slice)
-int flush_pending(rama_ctx* c) { int rf = flush_mm(c); if (!rf) rf = flush_rope(c); if (!rf) rf = flush_ew(c); return rf; }      // (flush_mm issues a recorded norm too)
 
-// internal accessors for the library's other translation units (pipe.hip); not in the C ABI header
+// internal accessors for the library's other translation units (pipe.hip); not in the C ABI header.  (The recorded 1:1 ops are issued by whatever
+// enters the library next -- flush_pending, "the 1:1 op recorder" below: first statement of every entry point that enqueues, synchronises or
+// changes a setting.)
 extern "C" void* rama_internal_stream(rama_ctx* c) { if (c && RAMA_PENDING(c)) (void)flush_pending(c); return c ? (void*)c->stream : nullptr; }
 extern "C" int rama_internal_device(rama_ctx* c) { return c ? c->device : 0; }
+// launches made for the 1:1 op entries and by flush_pending since the last reset (PendingOps::op_launches): what tells a test that a fold still
+// happens.  Issues nothing that is pending and touches no stream.
+extern "C" unsigned long long rama_internal_op_launches(rama_ctx* c, int reset) {
+    if (!c) return 0;
+    const unsigned long long n = c->rec.op_launches;
+    if (reset) c->rec.op_launches = 0;
+    return n;
+}
 // the sampler's device scratch after a rama_sample_topp* call (tests compare the running sums with a
 // sequential fp32 cumsum): sorted probabilities, sorted indices, running sums, candidate count
 extern "C" void rama_internal_topp_scratch(rama_ctx* c, float** keys, int** vals, float** prefix, int** m) {
@@ -292,30 +296,6 @@ int rama_free(rama_ctx* c, void* p) {
         default: { constexpr int R_ = 4, R2_ = 2, CH_ = 2, NW_ = 8; (void)R_; (void)R2_; KERNEL_CALL; } break; \
     }
 
-// the pending run of apply_position calls (rama_ctx::rope) as one launch: `count` consecutive heads are one vector of count x head_size floats
-static int flush_rope(rama_ctx* c) {
-    if (!c->rope.count) return 0;
-    const int hs = c->rope.hs, dim = c->rope.count * hs, n = dim / 2;
-    c->rope.count = 0;
-    if (c->tune_ref_order) hipLaunchKernelGGL(rope_ref_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, c->rope.q, c->rope.k, (const float*)nullptr, c->rope.pr, c->rope.pi, dim, hs,
-                                              (float*)nullptr, (float*)nullptr);
-    else hipLaunchKernelGGL(apply_position_heads_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, c->rope.q, c->rope.k, c->rope.pr, c->rope.pi, hs, dim);
-    LAUNCHCHK();
-    return 0;
-}
-// the pending elementwise op (rama_ctx::ew) by itself
-static int flush_ew(rama_ctx* c) {
-    if (!c->ew.kind) return 0;
-    const int kind = c->ew.kind;
-    c->ew.kind = 0;
-    const dim3 grid((unsigned)std::min<size_t>((c->ew.n + 255) / 256, 2048));
-    if (kind == 1) {
-        if (c->tune_ref_order) hipLaunchKernelGGL(sinu_ref_kernel, grid, dim3(256), 0, c->stream, c->ew.t, c->ew.n);
-        else hipLaunchKernelGGL(sinu_kernel, grid, dim3(256), 0, c->stream, c->ew.t, c->ew.n);
-    } else hipLaunchKernelGGL(copy_kernel, grid, dim3(256), 0, c->stream, c->ew.t, c->ew.s, c->ew.n);
-    LAUNCHCHK();
-    return 0;
-}
 static int check_matvec_shape(size_t width, size_t rows) {
     REQUIRE(width % 4 == 0, RAMA_EINVAL, "matmul: width % 4 != 0 (the reference CPU body panics here, cpu.rs:142-143)");
     REQUIRE(width > 0 && rows > 0, RAMA_EINVAL, "matmul: empty shape");
@@ -387,215 +367,297 @@ int launch_attention_ref(rama_ctx* c, float* xb, float* att, const float* q, con
     return 0;
 }
 
-// ---------------------------------------------------------------- parity mode at streaming speed (the launchers: chain_api.hip)
+// ---------------------------------------------------------------- the 1:1 op recorder (rama_ctx::rec; what may be pending together: ctx.hpp PendingOps)
 
-// the recorded norm (rama_ctx::nrm) as a launch of its own: no run of matmuls took it
-static int flush_norm(rama_ctx* c) {
-    if (!c->nrm.on) return 0;
-    c->nrm.on = false;
-    return launch_rmsnorm_chain(c, c->nrm.o, c->nrm.x, c->nrm.w, c->nrm.n, nullptr);
+// every launch for a 1:1 op entry or for flush_pending is counted (rama_internal_op_launches): a kernel of this translation unit ...
+#define OP_LAUNCH(c, kernel, grid, block, shm, ...) do { hipLaunchKernelGGL(kernel, grid, block, shm, (c)->stream, __VA_ARGS__); (c)->rec.op_launches++; LAUNCHCHK(); } while (0)
+// ... or a launcher's one launch, by its return code
+static int counted(rama_ctx* c, int rc) { if (!rc) c->rec.op_launches++; return rc; }
+
+static bool may_record(const rama_ctx* c, int tune_switch) { return tune_switch && c->own_stream; }
+// rama_rmsnorm records only on CAPTURE_NONE; rama_matmul takes a failed query (CAPTURE_UNKNOWN) for a capture
+enum Capture { CAPTURE_NONE, CAPTURE_ON, CAPTURE_UNKNOWN };
+static Capture stream_capture(rama_ctx* c) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(c->stream, &cs) != hipSuccess) return CAPTURE_UNKNOWN;
+    return cs == hipStreamCaptureStatusNone ? CAPTURE_NONE : CAPTURE_ON;
 }
-// the pending run of parity-mode matmuls (rama_ctx::mm) as one chain-order launch
-static int flush_mm(rama_ctx* c) {
-    if (!(c->mm.count && c->mm.norm)) { const int rn = flush_norm(c); if (rn) return rn; }
-    if (!c->mm.count) return 0;
+struct Range { const float* p; size_t n; };
+static bool apart_from(const float* p, size_t n, std::initializer_list<Range> others) {
+    for (const Range& r : others) if (ranges_overlap(p, n, r.p, r.n)) return false;
+    return true;
+}
+
+// the launches an entry and the flush of its record share: the reference's rounding order in parity mode, else the fast kernel
+static int launch_sinu(rama_ctx* c, float* t, size_t n) {
+    if (c->tune_ref_order) OP_LAUNCH(c, sinu_ref_kernel, dim3(ew_grid(n)), dim3(256), 0, t, n);
+    else OP_LAUNCH(c, sinu_kernel, dim3(ew_grid(n)), dim3(256), 0, t, n);
+    return 0;
+}
+static int launch_copy(rama_ctx* c, float* t, const float* s, size_t n) {
+    OP_LAUNCH(c, copy_kernel, dim3(ew_grid(n)), dim3(256), 0, t, s, n);
+    return 0;
+}
+// `count` consecutive heads are one vector of count x head_size floats
+static int launch_rope_run(rama_ctx* c, float* q, float* k, const float* pr, const float* pi, int hs, int count) {
+    const int dim = count * hs, n = dim / 2;
+    if (c->tune_ref_order) OP_LAUNCH(c, rope_ref_kernel, dim3((n + 63) / 64), dim3(64), 0, q, k, (const float*)nullptr, pr, pi, dim, hs, (float*)nullptr, (float*)nullptr);
+    else OP_LAUNCH(c, apply_position_heads_kernel, dim3((n + 63) / 64), dim3(64), 0, q, k, pr, pi, hs, dim);
+    return 0;
+}
+
+// the pending run of matmuls as the parameters of its chain-order launch
+static ChainParams run_params(const PendingOps& r) {
     ChainParams p{};
-    for (int i = 0; i < c->mm.count; i++) { p.w[i] = c->mm.w[i]; p.o[i] = c->mm.o[i]; }
-    p.x = c->mm.x; p.K = c->mm.K; p.rows = c->mm.rows; p.nmat = c->mm.count;
-    c->mm.count = 0;
-    if (c->mm.norm) {      // the run reads the recorded norm's output: the norm rides in the run's launch, whose leader also stores that output
-        c->mm.norm = false; c->nrm.on = false;
-        p.x = c->nrm.x; p.nw = c->nrm.w; p.xout = c->nrm.o;
-        p.lead = c->lead_slots + 32 * (kLeadSlots + c->op_lead_next); p.epoch = c->fused_epoch; p.err = c->pbar + 1;
-        const int rc = launch_chain(c, p, CEPI_STORE, CNORM_LEAD);
-        if (rc) return rc;
-        if (++c->op_lead_next == kLeadSlots) {      // every word of the range carries this epoch: the next one
-            c->op_lead_next = 0;
-            hipLaunchKernelGGL(fused_epoch_kernel, dim3(1), dim3(1), 0, c->stream, c->fused_epoch);
-            LAUNCHCHK();
-        }
-        return 0;
+    for (int i = 0; i < r.mm.count; i++) { p.w[i] = r.mm.w[i]; p.o[i] = r.mm.o[i]; }
+    p.x = r.mm.x; p.K = r.mm.K; p.rows = r.mm.rows; p.nmat = r.mm.count;
+    return p;
+}
+// THE launch of a chain run.  with_norm: the run reads the recorded norm's output, so the norm rides in the run's launch as its leader workgroup,
+// which also stores that output; the leader's word is the next of the op path's range, and when the range wraps every word of it carries this
+// epoch: the next one.  (The one place that advances PendingOps::lead_next.)
+static int launch_run(rama_ctx* c, ChainParams& p, int epi, bool with_norm) {
+    PendingOps& r = c->rec;
+    if (!with_norm) return counted(c, launch_chain(c, p, epi));
+    r.nrm.on = false;
+    p.x = r.nrm.x; p.nw = r.nrm.w; p.xout = r.nrm.o;
+    p.lead = c->lead_slots + 32 * (kLeadSlots + r.lead_next); p.epoch = c->fused_epoch; p.err = c->pbar + 1;
+    const int rc = counted(c, launch_chain(c, p, epi, CNORM_LEAD));
+    if (rc) return rc;
+    if (++r.lead_next == kLeadSlots) {
+        r.lead_next = 0;
+        OP_LAUNCH(c, fused_epoch_kernel, dim3(1), dim3(1), 0, c->fused_epoch);
     }
-    return launch_chain(c, p, CEPI_STORE);
+    return 0;
+}
+
+// what is pending, record by record.  flush_norm: no run of matmuls took the norm; flush_mm: the run as one chain-order launch, and the recorded norm in
+// that launch or in front of it; flush_rope: the rotations as one launch; flush_ew: the elementwise op by itself
+static int flush_norm(rama_ctx* c) {
+    auto& n = c->rec.nrm;
+    return std::exchange(n.on, false) ? counted(c, launch_rmsnorm_chain(c, n.o, n.x, n.w, n.n, nullptr)) : 0;
+}
+static int flush_mm(rama_ctx* c) {
+    PendingOps& r = c->rec;
+    if (!(r.mm.count && r.mm.norm)) { const int rn = flush_norm(c); if (rn) return rn; }
+    if (!r.mm.count) return 0;
+    ChainParams p = run_params(r);
+    r.mm.count = 0;
+    return launch_run(c, p, CEPI_STORE, std::exchange(r.mm.norm, false));
+}
+static int flush_rope(rama_ctx* c) {
+    auto& r = c->rec.rope;
+    const int count = std::exchange(r.count, 0);
+    return count ? launch_rope_run(c, r.q, r.k, r.pr, r.pi, r.hs, count) : 0;
+}
+static int flush_ew(rama_ctx* c) {
+    auto& e = c->rec.ew;
+    const int kind = std::exchange(e.kind, 0);
+    return !kind ? 0 : kind == 1 ? launch_sinu(c, e.t, e.n) : launch_copy(c, e.t, e.s, e.n);
+}
+// everything pending, in the order it can have been recorded: a norm and the run of matmuls on it, the rotations of that run's q and k, a copy
+int flush_pending(rama_ctx* c) { int rf = flush_mm(c); if (!rf) rf = flush_rope(c); if (!rf) rf = flush_ew(c); return rf; }
+
+// ---- the folds: when a call joins what is recorded (r) instead of issuing it
+
+// [r5] array_add(t, s) where s is the output of the one recorded matmul (infer.rs:35-37, :46-47): ONE launch with the residual epilogue (product stored, t += product)
+static bool add_is_residual_of_run(const rama_ctx* c, const PendingOps& r, const float* t, const float* s, size_t n) {
+    return r.mm.count == 1 && !r.mm.norm && !r.nrm.on && !r.rope.count && !r.ew.kind && c->tune_ref_order && c->tune_resid_fold && s == r.mm.o[0] && n == (size_t)r.mm.rows &&
+           aligned16(t) && apart_from(t, n, {{r.mm.x, (size_t)r.mm.K}, {s, n}});
+}
+// array_mult(t, s) on the vector of the recorded sinu: one launch for both
+static bool mult_takes_sinu(const PendingOps& r, const float* t, const float* s, size_t n) {
+    return r.ew.kind == 1 && !r.rope.count && !r.mm.count && r.ew.t == t && r.ew.n == n && n && !ranges_overlap(s, n, t, n);
+}
+// copy_from_slice(t, s) behind a recorded copy that it neither reads nor overwrites: one launch for both
+static bool copy_pairs_with_copy(const PendingOps& r, const float* t, const float* s, size_t n) {
+    return r.ew.kind == 2 && !r.rope.count && !r.mm.count && n && apart_from(r.ew.t, r.ew.n, {{s, n}, {t, n}}) && apart_from(t, n, {{r.ew.s, r.ew.n}, {s, n}});
+}
+// [r5] infer.rs:20-33 as the fused entry runs it: a pending run of three matmuls (a recorded norm in front, perhaps), every head of its first two outputs
+// rotated, and then its second and third outputs copied into cache rows -- ONE launch with the Wq|Wk|Wv epilogue.  The first copy is recorded
+// (copy_opens_qkv_fold), the second issues the launch (copy_closes_qkv_fold); a copy of that shape that is neither issues what is pending in program order.
+static bool copy_meets_rotated_qkv_run(const rama_ctx* c, const PendingOps& r, size_t n) {
+    return r.mm.count == 3 && r.rope.count && c->tune_qkv_fold && c->tune_ref_order && n == (size_t)r.mm.rows && r.rope.count * r.rope.hs == r.mm.rows;
+}
+static bool apart_from_qkv_run(const PendingOps& r, const float* p, size_t n) {      // from everything that launch reads or writes besides
+    const size_t rows = (size_t)r.mm.rows, hh = (size_t)r.rope.hs / 2;
+    return apart_from(p, n, {{r.mm.o[0], rows}, {r.mm.o[1], rows}, {r.mm.o[2], rows}, {r.mm.x, (size_t)r.mm.K}, {r.rope.pr, hh}, {r.rope.pi, hh}}) &&
+           (!r.mm.norm || apart_from(p, n, {{r.nrm.x, (size_t)r.nrm.n}, {r.nrm.w, (size_t)r.nrm.n}}));
+}
+static bool copy_opens_qkv_fold(const rama_ctx* c, const PendingOps& r, const float* t, const float* s, size_t n) {
+    return !r.ew.kind && s == r.mm.o[1] && aligned16(t) && apart_from_qkv_run(r, t, n) && may_record(c, c->tune_ew_batch);
+}
+static bool copy_closes_qkv_fold(const PendingOps& r, const float* t, const float* s, size_t n) {
+    const size_t hh = (size_t)r.rope.hs / 2;
+    return r.ew.kind == 2 && r.ew.s == r.mm.o[1] && r.ew.n == n && s == r.mm.o[2] && aligned16(t) && apart_from_qkv_run(r, t, n) && !ranges_overlap(t, n, r.ew.t, n) &&
+           apart_from(r.rope.pr, hh, {{r.mm.o[0], n}, {r.mm.o[1], n}, {r.mm.o[2], n}}) && apart_from(r.rope.pi, hh, {{r.mm.o[0], n}, {r.mm.o[1], n}, {r.mm.o[2], n}});
+}
+static int launch_qkv_fold(rama_ctx* c, float* value_row) {
+    PendingOps& r = c->rec;
+    ChainParams p = run_params(r);
+    p.fr = r.rope.pr; p.fi = r.rope.pi; p.head_size = r.rope.hs; p.kc = r.ew.t; p.vc = value_row; p.pos_val = 0;      // (the table rows and cache rows of this position themselves)
+    r.mm.count = 0; r.rope.count = 0; r.ew.kind = 0;
+    return launch_run(c, p, CEPI_QKV, std::exchange(r.mm.norm, false));
+}
+// apply_position(q, k) that starts to rotate the first two outputs of a pending run of three matmuls, or goes on rotating them: the run stays pending
+static bool rope_is_on_qkv_run(const rama_ctx* c, const PendingOps& r, const float* q, const float* k, size_t head_size) {
+    return r.mm.count == 3 && c->tune_qkv_fold && !r.ew.kind && may_record(c, c->tune_rope_batch) && head_size % 2 == 0 && r.mm.rows % (int)head_size == 0 &&
+           (r.rope.count ? true : (q == r.mm.o[0] && k == r.mm.o[1]));
+}
+// apply_position on the head behind the recorded run's last, with the same table rows (and inside the outputs of a pending run of matmuls)
+static bool rope_extends_run(const PendingOps& r, const float* q, const float* k, const float* pr, const float* pi, int hs) {
+    return r.rope.count && r.rope.count < 4096 && hs == r.rope.hs && pr == r.rope.pr && pi == r.rope.pi && q == r.rope.q + (size_t)r.rope.count * hs &&
+           k == r.rope.k + (size_t)r.rope.count * hs && (!r.mm.count || (r.rope.count + 1) * hs <= r.mm.rows);
+}
+// a parity-mode rmsnorm the leader workgroup of a chain launch can carry: not in place, 64 <= n <= 4096 in whole 16-float blocks, default geometry, no
+// kernel class being timed (rama_rmsnorm asks last whether the stream is capturing)
+static bool norm_may_ride(const rama_ctx* c, const float* o, const float* x, const float* w, size_t n) {
+    return c->tune_ref_order && c->tune_chain && rmsnorm_chain_ok(n) && c->tune_norm_fold && c->tune_chain_lead && may_record(c, c->tune_matmul_batch) && c->tune_chain_d <= 0 &&
+           c->tune_chain_lead_w <= 0 && c->kp.kernel_id < 0 && n % 16 == 0 && n <= 4096 && n >= 64 && aligned16(x) && aligned16(w) && aligned16(o) && (o + n <= x || x + n <= o) && c->lead_slots && c->pbar;
+}
+// matmul(o, a, b) with the activations and the shape of the pending run of one or two: the run's next member, if its output allows (below)
+static bool matmul_joins_run(const rama_ctx* c, const PendingOps& r, const float* b, size_t width, size_t o_rows, size_t o_cols) {
+    return r.mm.count && r.mm.count < 3 && c->tune_ref_order && o_cols == 1 && r.mm.x == b && r.mm.K == (int)width && r.mm.rows == (int)o_rows;
+}
+// the recorded norm rides with a run on its output: the run this matmul joins has taken it, or this matmul opens the run
+static bool run_takes_norm(const PendingOps& r, const float* b, size_t width) { return r.nrm.on && (r.mm.count ? r.mm.norm : (b == r.nrm.o && (int)width == r.nrm.n)); }
+// an output that overlaps the activations, an output of the run, or the input of the norm the run takes (which the launch then reads) is no member
+static bool output_clashes_with_run(const PendingOps& r, const float* o, const float* b, size_t width, size_t o_rows, bool takes_norm) {
+    bool clash = ranges_overlap(o, o_rows, b, width);
+    for (int i = 0; i < r.mm.count && !clash; i++) clash = ranges_overlap(o, o_rows, r.mm.o[i], o_rows);
+    return clash || (takes_norm && ranges_overlap(o, o_rows, r.nrm.x, (size_t)r.nrm.n));
 }
 
 // ---------------------------------------------------------------- Device<T> ops, 1:1
+// Each entry: argument checks, RAMA_WRITES, the folds that apply to the op, else what is pending is issued, else the call is recorded or launched.
+// Where an entry's order of REQUIRE, RAMA_WRITES and the flush differs from that, it decides which error a bad call returns and whether pending work
+// is issued in front of the error: kept as it was.
 
 int rama_array_add(rama_ctx* c, float* t, const float* s, size_t n) {
-    REQUIRE(c && (n == 0 || (t && s)), RAMA_EINVAL, "array_add: NULL argument");
+    REQUIRE(c && (n == 0 || (t && s)), RAMA_EINVAL, "array_add: NULL argument");      // (in front of RAMA_ENTER, unlike rama_sinu: a bad call leaves what is pending pending.  Looks accidental; kept)
     RAMA_WRITES(c, t, n);
-    // [r5] the recorded matmul whose output this call adds to `t` (infer.rs:35-37, :46-47): ONE launch with the residual epilogue (product stored, t += product)
-    if (c->mm.count == 1 && !c->mm.norm && !c->nrm.on && !c->rope.count && !c->ew.kind && c->tune_ref_order && c->tune_resid_fold && s == c->mm.o[0] && n == (size_t)c->mm.rows &&
-        aligned16(t) && !ranges_overlap(t, n, c->mm.x, (size_t)c->mm.K) && !ranges_overlap(t, n, s, n)) {
-        ChainParams p{};
-        p.w[0] = c->mm.w[0]; p.o[0] = c->mm.o[0]; p.resid = t; p.x = c->mm.x; p.K = c->mm.K; p.rows = c->mm.rows; p.nmat = 1;
-        c->mm.count = 0;
-        return launch_chain(c, p, CEPI_RESID);
+    if (add_is_residual_of_run(c, c->rec, t, s, n)) {
+        ChainParams p = run_params(c->rec);
+        p.resid = t;
+        c->rec.mm.count = 0;
+        return launch_run(c, p, CEPI_RESID, false);
     }
     RAMA_ENTER(c);
     if (!n) return 0;
-    hipLaunchKernelGGL(array_add_kernel, dim3(ew_grid(n)), dim3(256), 0, c->stream, t, s, n);
-    LAUNCHCHK(); return 0;
+    OP_LAUNCH(c, array_add_kernel, dim3(ew_grid(n)), dim3(256), 0, t, s, n);
+    return 0;
 }
 int rama_array_mult(rama_ctx* c, float* t, const float* s, size_t n) {
-    REQUIRE(c && (n == 0 || (t && s)), RAMA_EINVAL, "array_mult: NULL argument");
+    REQUIRE(c && (n == 0 || (t && s)), RAMA_EINVAL, "array_mult: NULL argument");      // (as rama_array_add)
     RAMA_WRITES(c, t, n);
-    if (c->ew.kind == 1 && !c->rope.count && !c->mm.count && c->ew.t == t && c->ew.n == n && n && !ranges_overlap(s, n, t, n)) {      // the recorded sinu and this product: one launch
-        c->ew.kind = 0;
-        if (c->tune_ref_order) hipLaunchKernelGGL(sinu_mult_ref_kernel, dim3(ew_grid(n)), dim3(256), 0, c->stream, t, s, n);
-        else hipLaunchKernelGGL(sinu_mult_kernel, dim3(ew_grid(n)), dim3(256), 0, c->stream, t, s, n);
-        LAUNCHCHK(); return 0;
+    if (mult_takes_sinu(c->rec, t, s, n)) {
+        c->rec.ew.kind = 0;
+        if (c->tune_ref_order) OP_LAUNCH(c, sinu_mult_ref_kernel, dim3(ew_grid(n)), dim3(256), 0, t, s, n);
+        else OP_LAUNCH(c, sinu_mult_kernel, dim3(ew_grid(n)), dim3(256), 0, t, s, n);
+        return 0;
     }
     RAMA_ENTER(c);
     if (!n) return 0;
-    hipLaunchKernelGGL(array_mult_kernel, dim3(ew_grid(n)), dim3(256), 0, c->stream, t, s, n);
-    LAUNCHCHK(); return 0;
+    OP_LAUNCH(c, array_mult_kernel, dim3(ew_grid(n)), dim3(256), 0, t, s, n);
+    return 0;
 }
 int rama_sinu(rama_ctx* c, float* o, size_t n) {
-    RAMA_ENTER(c);
+    RAMA_ENTER(c);      // (no fold applies: what is pending goes first, in front of the argument check)
     REQUIRE(c && (n == 0 || o), RAMA_EINVAL, "sinu: NULL argument");
     RAMA_WRITES(c, o, n);
     if (!n) return 0;
-    if (c->tune_ew_batch && c->own_stream) { c->ew.kind = 1; c->ew.t = o; c->ew.s = nullptr; c->ew.n = n; return 0; }      // recorded: the product that usually follows takes it along
-    if (c->tune_ref_order) hipLaunchKernelGGL(sinu_ref_kernel, dim3(ew_grid(n)), dim3(256), 0, c->stream, o, n);
-    else hipLaunchKernelGGL(sinu_kernel, dim3(ew_grid(n)), dim3(256), 0, c->stream, o, n);
-    LAUNCHCHK(); return 0;
+    if (may_record(c, c->tune_ew_batch)) { c->rec.ew = {1, o, nullptr, n}; return 0; }      // recorded: the product that usually follows takes it along
+    return launch_sinu(c, o, n);
 }
 int rama_copy_from_slice(rama_ctx* c, float* t, const float* s, size_t n) {
-    REQUIRE(c && (n == 0 || (t && s)), RAMA_EINVAL, "copy_from_slice: NULL argument");
+    REQUIRE(c && (n == 0 || (t && s)), RAMA_EINVAL, "copy_from_slice: NULL argument");      // (as rama_array_add)
     RAMA_WRITES(c, t, n);
-    // [r5] infer.rs:20-33 as the fused entry runs it: a pending run of three matmuls (a recorded norm in front, perhaps), every head of its first two outputs
-    // rotated, and now its second and third outputs copied into cache rows -- ONE launch with the Wq|Wk|Wv epilogue.  The first copy is recorded, the second
-    // issues the launch; anything that does not fit issues what is pending in program order.
-    if (c->mm.count == 3 && c->rope.count && c->tune_qkv_fold && c->tune_ref_order && n == (size_t)c->mm.rows && c->rope.count * c->rope.hs == c->mm.rows) {
-        const auto& m = c->mm;
-        const size_t hh = (size_t)c->rope.hs / 2;
-        auto apart = [&](const float* p0, size_t n0) {      // from everything the launch reads or writes besides
-            bool ok = !ranges_overlap(p0, n0, m.o[0], n) && !ranges_overlap(p0, n0, m.o[1], n) && !ranges_overlap(p0, n0, m.o[2], n) && !ranges_overlap(p0, n0, m.x, (size_t)m.K) &&
-                      !ranges_overlap(p0, n0, c->rope.pr, hh) && !ranges_overlap(p0, n0, c->rope.pi, hh);
-            if (ok && m.norm) ok = !ranges_overlap(p0, n0, c->nrm.x, (size_t)c->nrm.n) && !ranges_overlap(p0, n0, c->nrm.w, (size_t)c->nrm.n);
-            return ok;
-        };
-        if (!c->ew.kind && s == m.o[1] && aligned16(t) && apart(t, n) && c->tune_ew_batch) { c->ew.kind = 2; c->ew.t = t; c->ew.s = s; c->ew.n = n; return 0; }
-        if (c->ew.kind == 2 && c->ew.s == m.o[1] && c->ew.n == n && s == m.o[2] && aligned16(t) && apart(t, n) && !ranges_overlap(t, n, c->ew.t, n) &&
-            !ranges_overlap(c->rope.pr, hh, m.o[0], n) && !ranges_overlap(c->rope.pr, hh, m.o[1], n) && !ranges_overlap(c->rope.pr, hh, m.o[2], n) &&
-            !ranges_overlap(c->rope.pi, hh, m.o[0], n) && !ranges_overlap(c->rope.pi, hh, m.o[1], n) && !ranges_overlap(c->rope.pi, hh, m.o[2], n)) {
-            ChainParams p{};
-            for (int i = 0; i < 3; i++) { p.w[i] = m.w[i]; p.o[i] = m.o[i]; }
-            p.x = m.x; p.K = m.K; p.rows = m.rows; p.nmat = 3;
-            p.fr = c->rope.pr; p.fi = c->rope.pi; p.head_size = c->rope.hs; p.kc = c->ew.t; p.vc = t; p.pos_val = 0;      // (the table rows and cache rows of this position themselves)
-            const bool norm = m.norm;
-            c->mm.count = 0; c->mm.norm = false; c->rope.count = 0; c->ew.kind = 0;
-            if (!norm) return launch_chain(c, p, CEPI_QKV);
-            c->nrm.on = false;
-            p.x = c->nrm.x; p.nw = c->nrm.w; p.xout = c->nrm.o;
-            p.lead = c->lead_slots + 32 * (kLeadSlots + c->op_lead_next); p.epoch = c->fused_epoch; p.err = c->pbar + 1;
-            const int rc = launch_chain(c, p, CEPI_QKV, CNORM_LEAD);
-            if (rc) return rc;
-            if (++c->op_lead_next == kLeadSlots) { c->op_lead_next = 0; hipLaunchKernelGGL(fused_epoch_kernel, dim3(1), dim3(1), 0, c->stream, c->fused_epoch); LAUNCHCHK(); }
-            return 0;
-        }
+    if (copy_meets_rotated_qkv_run(c, c->rec, n)) {
+        if (copy_opens_qkv_fold(c, c->rec, t, s, n)) { c->rec.ew = {2, t, s, n}; return 0; }
+        if (copy_closes_qkv_fold(c->rec, t, s, n)) return launch_qkv_fold(c, t);
         { const int rf = flush_pending(c); if (rf) return rf; }
     }
-    if (c->ew.kind == 2 && !c->rope.count && !c->mm.count && n && !ranges_overlap(s, n, c->ew.t, c->ew.n) && !ranges_overlap(t, n, c->ew.t, c->ew.n) &&
-        !ranges_overlap(t, n, c->ew.s, c->ew.n) && !ranges_overlap(t, n, s, n)) {      // the recorded copy and this one: one launch
-        c->ew.kind = 0;
-        hipLaunchKernelGGL(copy2_kernel, dim3(ew_grid(n + c->ew.n)), dim3(256), 0, c->stream, c->ew.t, c->ew.s, c->ew.n, t, s, n);
-        LAUNCHCHK(); return 0;
+    if (copy_pairs_with_copy(c->rec, t, s, n)) {
+        PendingOps& r = c->rec;
+        r.ew.kind = 0;
+        OP_LAUNCH(c, copy2_kernel, dim3(ew_grid(n + r.ew.n)), dim3(256), 0, r.ew.t, r.ew.s, r.ew.n, t, s, n);
+        return 0;
     }
     RAMA_ENTER(c);
     if (!n) return 0;
-    if (c->tune_ew_batch && c->own_stream && !ranges_overlap(t, n, s, n)) { c->ew.kind = 2; c->ew.t = t; c->ew.s = s; c->ew.n = n; return 0; }
-    hipLaunchKernelGGL(copy_kernel, dim3(ew_grid(n)), dim3(256), 0, c->stream, t, s, n);
-    LAUNCHCHK(); return 0;
+    if (may_record(c, c->tune_ew_batch) && !ranges_overlap(t, n, s, n)) { c->rec.ew = {2, t, s, n}; return 0; }      // recorded: one more copy may follow
+    return launch_copy(c, t, s, n);
 }
 int rama_rmsnorm(rama_ctx* c, float* o, const float* x, const float* w, size_t n) {
-    RAMA_ENTER(c);
+    RAMA_ENTER(c);      // (as rama_sinu)
     REQUIRE(c && o && x && w && n > 0, RAMA_EINVAL, "rmsnorm: bad argument");
     RAMA_WRITES(c, o, n);
-    if (c->tune_ref_order && c->tune_chain && rmsnorm_chain_ok(n) && c->tune_norm_fold && c->tune_chain_lead && c->tune_matmul_batch && c->own_stream && c->tune_chain_d <= 0 &&
-        c->tune_chain_lead_w <= 0 && c->kp.kernel_id < 0 && n % 16 == 0 && n <= 4096 && n >= 64 && aligned16(x) && aligned16(w) && aligned16(o) && (o + n <= x || x + n <= o) && c->lead_slots && c->pbar) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(c->stream, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) {      // recorded: the run of matmuls on `o` carries it (flush_mm)
-            c->nrm.o = o; c->nrm.x = x; c->nrm.w = w; c->nrm.n = (int)n; c->nrm.on = true;
-            return 0;
-        }
+    if (norm_may_ride(c, o, x, w, n)) {
+        if (stream_capture(c) == CAPTURE_NONE) { c->rec.nrm = {o, x, w, (int)n, true}; return 0; }      // recorded: the run of matmuls on `o` carries it (launch_run)
         (void)hipGetLastError();
     }
-    if (c->tune_ref_order) return c->tune_chain && rmsnorm_chain_ok(n) ? launch_rmsnorm_chain(c, o, x, w, (int)n, nullptr) : launch_rmsnorm_ref(c, o, x, w, (int)n);
-    hipLaunchKernelGGL(rmsnorm_kernel, dim3(1), dim3(1024), 0, c->stream, o, x, w, (int)n);
-    LAUNCHCHK(); return 0;
+    if (c->tune_ref_order) return counted(c, c->tune_chain && rmsnorm_chain_ok(n) ? launch_rmsnorm_chain(c, o, x, w, (int)n, nullptr) : launch_rmsnorm_ref(c, o, x, w, (int)n));
+    OP_LAUNCH(c, rmsnorm_kernel, dim3(1), dim3(1024), 0, o, x, w, (int)n);
+    return 0;
 }
 int rama_apply_position(rama_ctx* c, float* q, float* k, const float* pr, const float* pi, size_t head_size) {
-    REQUIRE(c && q && k && pr && pi && head_size >= 2, RAMA_EINVAL, "apply_position: bad argument");
+    REQUIRE(c && q && k && pr && pi && head_size >= 2, RAMA_EINVAL, "apply_position: bad argument");      // (as rama_array_add)
     RAMA_WRITES(c, q, head_size); RAMA_WRITES(c, k, head_size);
-    // (whatever was recorded before this call comes first -- except a run of three matmuls whose first two outputs this call starts to rotate, or goes on rotating)
-    const bool on_run = c->mm.count == 3 && c->tune_qkv_fold && !c->ew.kind && c->tune_rope_batch && c->own_stream && head_size % 2 == 0 && c->mm.rows % (int)head_size == 0 &&
-                        (c->rope.count ? true : (q == c->mm.o[0] && k == c->mm.o[1]));
-    if (!on_run && (c->mm.count | c->ew.kind | (int)c->nrm.on)) { const int rm = flush_pending(c); if (rm) return rm; }      // (a run of rotations by itself goes on)
-    if (c->tune_rope_batch && c->own_stream && head_size % 2 == 0 && head_size <= 4096) {
-        auto& r = c->rope;
+    PendingOps& r = c->rec;
+    // whatever was recorded before this call comes first -- except a run of rotations, which may go on, and a run of three matmuls that this call rotates
+    if (!rope_is_on_qkv_run(c, r, q, k, head_size) && (r.mm.count | r.ew.kind | (int)r.nrm.on)) { const int rm = flush_pending(c); if (rm) return rm; }
+    if (may_record(c, c->tune_rope_batch) && head_size % 2 == 0 && head_size <= 4096) {
         const int hs = (int)head_size;
-        if (r.count && r.count < 4096 && hs == r.hs && pr == r.pr && pi == r.pi && q == r.q + (size_t)r.count * hs && k == r.k + (size_t)r.count * hs &&
-            (!c->mm.count || (r.count + 1) * hs <= c->mm.rows)) { r.count++; return 0; }
+        if (rope_extends_run(r, q, k, pr, pi, hs)) { r.rope.count++; return 0; }
+        // (a new run: EVERYTHING pending is issued, a run of three matmuls that this call starts to rotate too -- so the rotations of a run are
+        // recorded only once the run has gone, and rama_copy_from_slice never meets a run with its rotations.  Kept as it was: DESIGN.md 3.6)
         const int rf = flush_pending(c); if (rf) return rf;
-        r.q = q; r.k = k; r.pr = pr; r.pi = pi; r.hs = hs; r.count = 1;
+        r.rope = {q, k, pr, pi, hs, 1};
         return 0;
     }
     { const int rf = flush_pending(c); if (rf) return rf; }
-    int n = (int)(head_size / 2);
-    if (c->tune_ref_order) {
-        hipLaunchKernelGGL(rope_ref_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, q, k, (const float*)nullptr, pr, pi, (int)head_size, (int)head_size,
-                           (float*)nullptr, (float*)nullptr);
-        LAUNCHCHK(); return 0;
-    }
-    hipLaunchKernelGGL(apply_position_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, q, k, pr, pi, (int)head_size);
-    LAUNCHCHK(); return 0;
+    if (c->tune_ref_order) return launch_rope_run(c, q, k, pr, pi, (int)head_size, 1);      // (one head as a run of one: the same launch)
+    const int n = (int)(head_size / 2);
+    OP_LAUNCH(c, apply_position_kernel, dim3((n + 63) / 64), dim3(64), 0, q, k, pr, pi, (int)head_size);
+    return 0;
 }
 int rama_matmul(rama_ctx* c, float* o, const float* a, const float* b, size_t width, size_t o_rows, size_t o_cols) {
-    if (c && (c->rope.count | c->ew.kind)) { const int rf = flush_pending(c); if (rf) return rf; }      // (a pending run of matmuls may be extended by this call, a recorded norm taken along: below)
+    if (c && (c->rec.rope.count | c->rec.ew.kind)) { const int rf = flush_pending(c); if (rf) return rf; }      // (in front of the argument checks; a pending run of matmuls may be extended by this call, a recorded norm taken along: below)
     REQUIRE(c && o && a && b, RAMA_EINVAL, "matmul: NULL argument");
     REQUIRE(o_cols >= 1, RAMA_EINVAL, "matmul: o_cols == 0");
     RAMA_WRITES(c, o, o_rows * o_cols);
     int rc = check_matvec_shape(width, o_rows);
     if (rc) { (void)flush_mm(c); return rc; }
-    const bool extendable = c->mm.count && c->mm.count < 3 && c->tune_ref_order && o_cols == 1 && c->mm.x == b && c->mm.K == (int)width && c->mm.rows == (int)o_rows;
-    if (!extendable && c->mm.count) { rc = flush_mm(c); if (rc) return rc; }      // (no run pending: a recorded norm stays, this call may open the run that takes it)
+    PendingOps& r = c->rec;
+    if (!matmul_joins_run(c, r, b, width, o_rows, o_cols) && r.mm.count) { rc = flush_mm(c); if (rc) return rc; }      // (no run pending: a recorded norm stays, this call may open the run that takes it)
     if (c->tune_ref_order && o_cols == 1) {
         // a layer-aligned view of a resident model's matrix streams the model's chain-order copy
         if (c->tune_chain && width % 16 == 0 && width <= 16000 && aligned16(b)) {
             rc = rama_internal_model_ensure_ptr(c, a, 1); if (rc) return rc;
             // ... and a matrix that belongs to no model -- uploaded by itself (hbm.rs:14-16), or a view no model copy covers (w1, w3: a model keeps
             // them interleaved) -- gets a chain-order copy of its own on first use ("chain_views"; freed with the tensor: rama_free)
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            const bool capturing = hipStreamIsCapturing(c->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+            const bool capturing = stream_capture(c) != CAPTURE_NONE;
             if (const float* ch = c->tune_chain_views ? rama_internal_chain_view(c, a, (int)o_rows, (int)width, capturing ? 1 : 0) : rama_internal_chain_lookup(a, (int)o_rows, (int)width)) {
-                auto& mmb = c->mm;
                 // [r5] recorded, not launched: the next call extends the run (same activations, same shape, an output that overlaps nothing of the run) or
                 // issues it.  A run is one launch over all its row groups.
-                auto overlaps = [](const float* p0, size_t n0, const float* p1, size_t n1) { return p0 < p1 + n1 && p1 < p0 + n0; };
-                bool clash = overlaps(o, o_rows, b, width);
-                for (int i = 0; i < mmb.count && !clash; i++) clash = overlaps(o, o_rows, mmb.o[i], o_rows);
-                // the recorded norm rides with a run on its output; the run then reads the norm's input, which no output of the run may touch
-                const bool takes_norm = c->nrm.on && (mmb.count ? mmb.norm : (b == c->nrm.o && (int)width == c->nrm.n));
-                if (takes_norm && overlaps(o, o_rows, c->nrm.x, (size_t)c->nrm.n)) clash = true;
-                if (c->tune_matmul_batch && c->own_stream && !capturing && !clash) {
-                    if (!mmb.count) {
-                        mmb.x = b; mmb.K = (int)width; mmb.rows = (int)o_rows; mmb.norm = takes_norm;
+                const bool takes_norm = run_takes_norm(r, b, width);
+                if (may_record(c, c->tune_matmul_batch) && !capturing && !output_clashes_with_run(r, o, b, width, o_rows, takes_norm)) {
+                    if (!r.mm.count) {
+                        r.mm.x = b; r.mm.K = (int)width; r.mm.rows = (int)o_rows; r.mm.norm = takes_norm;
                         if (!takes_norm) { rc = flush_norm(c); if (rc) return rc; }
                     }
-                    mmb.w[mmb.count] = ch; mmb.o[mmb.count] = o; mmb.count++;
-                    if (mmb.count == 3 && !(c->tune_qkv_fold && c->tune_rope_batch && c->tune_ew_batch)) return flush_mm(c);      // (else: the rotations and cache copies may follow)
+                    r.mm.w[r.mm.count] = ch; r.mm.o[r.mm.count] = o; r.mm.count++;
+                    if (r.mm.count == 3 && !(c->tune_qkv_fold && c->tune_rope_batch && c->tune_ew_batch)) return flush_mm(c);      // (else: the rotations and cache copies may follow)
                     return 0;
                 }
                 rc = flush_mm(c); if (rc) return rc;
                 ChainParams p{};
                 p.w[0] = ch; p.o[0] = o; p.x = b; p.K = (int)width; p.rows = (int)o_rows; p.nmat = 1;
-                return launch_chain(c, p, CEPI_STORE);
+                return launch_run(c, p, CEPI_STORE, false);
             }
         }
         rc = flush_mm(c); if (rc) return rc;
-        return launch_matvec_ref1(c, o, a, b, (int)width, (int)o_rows);
+        return counted(c, launch_matvec_ref1(c, o, a, b, (int)width, (int)o_rows));
     }
     // (none of the paths below records: whatever is pending -- a parity-mode Device::rmsnorm whose output this call may read -- is issued first)
     rc = flush_mm(c); if (rc) return rc;
@@ -603,26 +665,26 @@ int rama_matmul(rama_ctx* c, float* o, const float* a, const float* b, size_t wi
         size_t n = o_rows * o_cols;
         if (c->tune_ref_order) {      // the reference's rounding order for this shape too (cpu.rs:137-151)
             REQUIRE(width % 4 == 0, RAMA_EINVAL, "matmul: width % 4 != 0 (the reference CPU body panics here, cpu.rs:142-143)");
-            hipLaunchKernelGGL(matmul_cols_ref_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, o, a, b, (int)width, (int)o_rows, (int)o_cols, c->tune_lane_reduce);
-            LAUNCHCHK(); return 0;
+            OP_LAUNCH(c, matmul_cols_ref_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, o, a, b, (int)width, (int)o_rows, (int)o_cols, c->tune_lane_reduce);
+            return 0;
         }
-        hipLaunchKernelGGL(matmul_generic, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, o, a, b, (int)width, (int)o_rows, (int)o_cols);
-        LAUNCHCHK(); return 0;
+        OP_LAUNCH(c, matmul_generic, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, o, a, b, (int)width, (int)o_rows, (int)o_cols);
+        return 0;
     }
     if (!aligned16(a) || !aligned16(b)) {   // a view that does not start on a 16-byte boundary
-        hipLaunchKernelGGL(matvec_unaligned, dim3((unsigned)((o_rows + 3) / 4)), dim3(kWG), 0, c->stream, o, a, b, (int)width, (int)o_rows);
-        LAUNCHCHK(); return 0;
+        OP_LAUNCH(c, matvec_unaligned, dim3((unsigned)((o_rows + 3) / 4)), dim3(kWG), 0, o, a, b, (int)width, (int)o_rows);
+        return 0;
     }
-    return launch_rows<false, EPI_STORE>(c, o, a, b, nullptr, (int)width, (int)o_rows);
+    return counted(c, launch_rows<false, EPI_STORE>(c, o, a, b, nullptr, (int)width, (int)o_rows));
 }
 int rama_softmax(rama_ctx* c, float* x, size_t n) {
-    RAMA_ENTER(c);
+    RAMA_ENTER(c);      // (as rama_sinu)
     REQUIRE(c && x && n > 0, RAMA_EINVAL, "softmax: bad argument");
     RAMA_WRITES(c, x, n);
-    if (c->tune_ref_order && c->tune_chain && rmsnorm_chain_ok(n)) return launch_softmax_chain(c, x, (int)n);
-    if (c->tune_ref_order) { hipLaunchKernelGGL(softmax_ref_kernel, dim3(1), dim3(1024), 0, c->stream, x, (int)n); LAUNCHCHK(); return 0; }
-    hipLaunchKernelGGL(softmax_kernel, dim3(1), dim3(1024), 0, c->stream, x, (int)n);
-    LAUNCHCHK(); return 0;
+    if (c->tune_ref_order && c->tune_chain && rmsnorm_chain_ok(n)) return counted(c, launch_softmax_chain(c, x, (int)n));
+    if (c->tune_ref_order) { OP_LAUNCH(c, softmax_ref_kernel, dim3(1), dim3(1024), 0, x, (int)n); return 0; }
+    OP_LAUNCH(c, softmax_kernel, dim3(1), dim3(1024), 0, x, (int)n);
+    return 0;
 }
 
 static int attn_nsplit(const rama_ctx* c, int n_heads) {

@@ -884,6 +884,128 @@ def test_recorded_ops_random_sequences(dev, seed):
     assert sum(bool(np.isfinite(a).all() and np.abs(a).max() > 0) for a in results[1]) >= 5, f"seed {seed}: the program degenerated (inf / nan / zeros): nothing is compared"
 
 
+RECORD_KEYS = (b"rope_batch", b"matmul_batch", b"ew_batch", b"norm_fold", b"resid_fold", b"qkv_fold")
+
+
+class _LayerOps:
+    """the reference's layer sequence without attention (infer.rs:19-47), the 19 calls of layer_like() in test_recorded_ops_random_sequences, on
+    distinct pool vectors (x, xb, q, k, v, xb2 = 0..5, cache rows 0 and 3) with uploaded matrices, at dim 256 with 4 heads: the smallest size at
+    which every fold is eligible (a recorded norm needs n >= 64 and n % 16 == 0)"""
+    dim, heads = 256, 4
+
+    def __init__(self, dev):
+        self.dev, hs = dev, self.dim // self.heads
+        self.mats = [up(dev, rnd(self.dim * self.dim, 300 + i, 0.06)) for i in range(5)]
+        self.gains = [up(dev, (rnd(self.dim, 310 + i, 0.1) + np.float32(1.0)).astype(np.float32)) for i in range(2)]
+        self.tfr = up(dev, np.cos(np.arange(hs // 2, dtype=np.float32) * np.float32(0.3)).astype(np.float32))
+        self.tfi = up(dev, np.sin(np.arange(hs // 2, dtype=np.float32) * np.float32(0.3)).astype(np.float32))
+        x, xb, q, k, v, xb2 = range(6)
+        self.qkv = [("rmsnorm", xb, x, 0), ("matmul", q, 0, xb), ("matmul", k, 1, xb), ("matmul", v, 2, xb)]
+        self.rotations = [("rope", q, k, h) for h in range(self.heads)]
+        self.copies = [("tocache", 0, k), ("tocache", 3, v)]
+        self.rest = [("matmul", xb2, 3, q), ("add", x, xb2), ("rmsnorm", xb, x, 1), ("matmul", q, 4, xb), ("matmul", k, 0, xb),
+                     ("sinu", q), ("mult", q, k), ("matmul", xb2, 1, q), ("add", x, xb2)]
+        self.layer = self.qkv + self.rotations + self.copies + self.rest
+        assert len(self.layer) == 19
+
+    def fresh(self):
+        self.pool = [up(self.dev, rnd(self.dim, 200 + i)) for i in range(6)]
+        self.cache = up(self.dev, np.zeros(6 * self.dim, np.float32))
+
+    def run(self, ops):
+        dev, dim, hs, pool = self.dev, self.dim, self.dim // self.heads, self.pool
+        for op in ops:
+            if op[0] == "matmul":
+                dev.matmul(pool[op[1]], self.mats[op[2]].as_view(), pool[op[3]].as_view(), dim, dim, 1)
+            elif op[0] == "rmsnorm":
+                dev.rmsnorm(pool[op[1]], pool[op[2]].as_view(), self.gains[op[3]].as_view(), dim)
+            elif op[0] == "add":
+                dev.array_add(pool[op[1]], pool[op[2]].as_view(), dim)
+            elif op[0] == "mult":
+                dev.array_mult(pool[op[1]], pool[op[2]].as_view(), dim)
+            elif op[0] == "sinu":
+                dev.sinu(pool[op[1]], dim)
+            elif op[0] == "rope":
+                h = op[3]
+                dev.apply_position(pool[op[1]].mut_slice(h * hs, (h + 1) * hs), pool[op[2]].mut_slice(h * hs, (h + 1) * hs), self.tfr.as_view(), self.tfi.as_view(), hs)
+            elif op[0] == "tocache":
+                dev.copy_from_slice(self.cache.mut_slice(op[1] * dim, (op[1] + 1) * dim), pool[op[2]].as_view(), dim)
+            elif op[0] == "download":
+                dev.download(pool[op[1]])
+
+    def download_all(self):
+        return [self.dev.download(t) for t in self.pool] + [self.dev.download(self.cache)]
+
+
+# The expected counts are the parent library's (the commit in front of PendingOps, which has no counter): the same calls under
+# `rocprofv3 --kernel-trace`, the dispatches between the warm-up and the end of the download counted.  They are NOT what reading the fold rules
+# promises (5 for the layer, 1 for the fold alone): rama_apply_position issues everything pending when it opens a run of rotations, the run of three
+# matmuls it is about to rotate included, so rama_copy_from_slice never meets that run and "qkv_fold" folds nothing -- norm + Wq|Wk|Wv, the
+# rotations and the two copies are three launches.  The counts pin what the library does; a fold that STOPS happening raises them.
+@pytest.mark.parametrize("case,switches,want", [
+    ("layer", 1, 7),          # norm + Wq|Wk|Wv, rotations, both copies, Wo + add, norm + W1|W3, sinu * mult, W2 + add
+    ("layer", 0, 19),         # one per call
+    ("qkv", 1, 3),            # the sequence cut behind the second copy: the run with its norm, the rotations, the copies
+    ("qkv_download", 1, 3),   # a download between the matmuls and the rotations: the run goes out by itself, then the rotations, the copies
+])
+def test_recorded_layer_sequence_launch_counts(case, switches, want):
+    """launches the 1:1 op path makes for the reference's layer sequence (rama_internal_op_launches: every launch of an op entry or of what it left
+    pending): the bits of test_recorded_ops_random_sequences do not notice a fold that no longer happens, this count does.  In a context of its
+    own, so that the leader range of the recorded norms starts at its first word and no epoch bump falls into the count"""
+    import rama_amd
+    from rama_amd._lib import check
+    d = rama_amd.Hip(0)
+    try:
+        check(d.lib.rama_set_tuning(d.ctx, b"ref_order", 1))
+        for key in RECORD_KEYS:
+            check(d.lib.rama_set_tuning(d.ctx, key, switches))
+        ops = _LayerOps(d)
+        prog = {"layer": ops.layer, "qkv": ops.qkv + ops.rotations + ops.copies,
+                "qkv_download": ops.qkv + [("download", 2)] + ops.rotations + ops.copies}[case]
+        ops.fresh()
+        ops.run(prog); ops.download_all()      # warm-up: the matrices' chain-order copies are made on first use
+        d.lib.rama_internal_op_launches(d.ctx, 1)
+        ops.run(prog); d.download(ops.pool[0])
+        got = d.lib.rama_internal_op_launches(d.ctx, 0)
+    finally:
+        d.close()
+    print(f"{case}, switches {switches}: {got} launches")
+    assert got == want, (case, switches, got, want)
+
+
+def test_recorded_norms_cross_the_leader_range_wrap(dev):
+    """a recorded norm's leader takes the next tagged word of the op path's range and the epoch advances when the range wraps (launch_run): the
+    whole-layer sequence (two recorded norms) kLeadSlots + 2 times in one context crosses the wrap two or three times, wherever the module's
+    context stood -- every vector bit for bit as with all recording off, and the launch count says that the wraps happened: 7 per layer (above) and
+    one epoch bump per wrap"""
+    from rama_amd._lib import check
+    k_lead_slots = 2 * 256 + 2      # chain_params.hpp kLeadSlots
+    reps = k_lead_slots + 2
+    ops = _LayerOps(dev)
+    results, launches = {}, {}
+    for on in (1, 0):
+        for key in RECORD_KEYS:
+            check(dev.lib.rama_set_tuning(dev.ctx, key, on))
+        try:
+            ops.fresh()
+            ops.run(ops.layer); dev.download(ops.pool[0])      # (the chain-order copies)
+            dev.lib.rama_internal_op_launches(dev.ctx, 1)
+            for _ in range(reps):
+                ops.run(ops.layer)
+            results[on] = ops.download_all()
+            launches[on] = dev.lib.rama_internal_op_launches(dev.ctx, 0)
+        finally:
+            for key in RECORD_KEYS:
+                check(dev.lib.rama_set_tuning(dev.ctx, key, 1))
+    for i, (a, b) in enumerate(zip(results[1], results[0])):
+        assert np.array_equal(bits(a), bits(b)), f"vector {i} differs between recorded and unrecorded issue after {reps} layers"
+    assert all(np.isfinite(a).all() for a in results[1]) and sum(bool(np.abs(a).max() > 0) for a in results[1]) >= 5, "the program degenerated: nothing is compared"
+    print(f"launches over {reps} layers: recorded {launches[1]}, unrecorded {launches[0]}")
+    assert launches[0] == 19 * reps
+    wraps = launches[1] - 7 * reps      # 2 * reps = 2 * kLeadSlots + 4 norms over a range of kLeadSlots words
+    assert wraps in (2, 3), (launches, reps)
+
+
 @pytest.mark.gpu
 def test_op_path_at_long_contexts_matches_the_fused_entry(dev):
     """[r5] forward() composed op for op from the trait (recorded and merged launches) against the resident model's fused entry at positions around every
