@@ -624,6 +624,76 @@ int  rama_q8_serve_admit_at(rama_ctx *ctx, int slot, const rama_run_state *state
 int  rama_q8_kv_fork(rama_ctx *ctx, const rama_config *cfg, const rama_run_state *src, const rama_run_state *dsts, int n_dst,
                      int n_rows);
 
+/* THE SPECULATIVE CHAIN: one-stream Q8 decode that drafts by n-gram lookup and verifies in one pass.  A third
+ * chain next to the two above, with a state of its own, for ONE sequence.  A token-batch pass over rows at consecutive positions
+ * of one sequence leaves every row the cache rows and logits of its own rama_q8_forward, and a pass of up to 16 rows costs about
+ * what a pass of 2 costs: so K guessed tokens and the token before them are checked in one weight pass of K + 1 rows, and what
+ * is accepted is exactly what rama_q8_generate would have produced.  A wrong guess costs time only.
+ *
+ * Notation: s[0..L) are the sequence's known tokens (the context, BOS first, and everything emitted so far); cache rows
+ * 0..L-2 are valid and s[L-1] is fed next, at position P = L-1; hint[0..n_hint) is an optional text to look up in as well (a
+ * document being edited or quoted, a previous answer); K = n_draft in 0..15, N = ngram in 1..4.
+ * DRAFT (rama_q8_spec_draft).  For n = min(N, L) down to 1: look for the tail s[L-n..L) first in hint, then in s, and take the
+ *   latest occurrence; in s it must end before L (the tail itself does not count).  The first n for which one of the two texts
+ *   has an occurrence decides -- the hint's if both have one.  The drafts d[0..n_d) are the tokens that follow that occurrence in
+ *   the same text, up to that text's end, with n_d <= K, n_d <= seq_len - 1 - P and n_d <= remaining - 1 (remaining = max_new
+ *   minus the tokens emitted so far).  No occurrence at any n, or K = 0: n_d = 0.
+ * STEP.  Rows j = 0..n_d carry s[L-1], d[0], .., d[n_d-1] at positions P..P+n_d; the other rows of the K + 1-row pass are idle
+ *   (position -1: they write nothing and nothing is read through them).  All K + 1 rows go through the final norm, the quantizer
+ *   and the classifier, and pick_j = Device::sample(logits_j) with the plan's temperature, topp and draw u, as rama_q8_generate
+ *   applies them at that position.
+ * ACCEPT (rama_q8_spec_accept).  a = the largest value <= n_d with pick_j == d[j] for all j < a.  pick_0..pick_a are emitted, cut
+ *   after the first emitted token equal to stop_token and cut at the budget; either cut finishes the sequence.  L grows by the
+ *   number of tokens emitted.  A finished sequence's further steps are all-idle passes.
+ * The output is the sampled tokens only and is, bit for bit,
+ *   rama_q8_generate(prompt = c[1:], steps = n_context - 1 + max_new, T, topp, u)[n_context-1:]  cut after the stop token
+ * whatever n_draft, ngram, the hint and the graph mode.  Cache rows at or below the new P - 1 hold that run's bits.  UNLIKE the
+ * other two chains, rows BEHIND that position may hold the rows of rejected drafts: the next step rewrites whatever it reads
+ * before it reads it.  Nothing at or beyond position n_context - 1 + max_new is ever written.  In graph mode a step is one
+ * hipGraph replay and ONE captured graph serves the chain for its whole life.
+ *
+ * rama_q8_spec_begin: the contract of rama_q8_serve_admit_at with n_cached = n_context - 1 -- rows 0..n_context-2 of `state`
+ * were written by work enqueued earlier on the context's stream (a rama_q8_prefill of context[:-1]; nothing for n_context == 1)
+ * -- and the chain feeds context[n_context-1] first.  It sizes everything outside any capture (a device token buffer of n_hint +
+ * seq_len, out and a pinned host-visible ring of max_new tokens, pinned count and finished words) and ends a previous
+ * speculative chain.  Everything is checked first and a refusal leaves the previous chain as it was: RAMA_EINVAL for a NULL
+ * argument, temperature < 0 / topp outside [0, 1] / u outside [0, 1) / NaN, a stop token outside [-1, vocab_size), n_draft
+ * outside 0..15, ngram outside 1..4, a hint or context token outside the vocabulary, n_hint < 0, n_hint > 0 with hint == NULL,
+ * n_context < 1, max_new < 1, n_context + max_new > seq_len; RAMA_EUNSUP where rama_q8_decode_batch_begin gives it
+ * (rama_q8_batch_shape_ok == 0; a sampled plan on vocab_size > 32768).
+ * rama_q8_spec_steps: no overall limit.  RAMA_EINVAL once the model (rama_q8_model_free) or the run state (rama_state_free) is
+ * gone.  rama_q8_prefill / rama_q8_decode_batch / the other chains on other run states between two calls are fine.
+ * rama_q8_spec_poll never touches the stream: tokens from.. of the host-visible ring, and *finished (may be NULL) = 1 once the
+ * sequence has finished -- set after its last token is visible.  rama_q8_spec_tokens and rama_q8_spec_stats synchronise.  The
+ * report: steps (idle ones included), the captures so far, and over the steps before the finish rows_fed = sum (n_d + 1),
+ * drafts = sum n_d, accepted = sum a, emitted, accepted_hist[a] = steps that accepted a drafts; cursor = P.
+ * rama_q8_spec_draft and rama_q8_spec_accept are HOST-ONLY (no context, no GPU): the two rules above as pure functions, which
+ * the device reproduces exactly.  _draft: room = min(seq_len - 1 - P, remaining - 1); returns n_d and fills drafts_out[0..n_d).
+ * _accept: picks[0..n_d], remaining >= 1; returns the tokens emitted (pick_0 ..) and *finished (may be NULL).  Both answer
+ * RAMA_EINVAL (negative) for a bad argument. */
+typedef struct {
+    float temperature, topp, u;                 /* Device::sample; temperature 0 = argmax */
+    int32_t max_new;                            /* >= 1 */
+    int32_t stop_token;                         /* -1 = none; an emitted token equal to it is recorded, then the sequence is finished */
+    int32_t n_draft, ngram;                     /* K in 0..15, N in 1..4 */
+    const int32_t *hint; int32_t n_hint;        /* a text to look up in besides the sequence's own; may be NULL / 0 */
+} rama_q8_spec_plan;
+typedef struct {
+    uint64_t steps, graph_captures, rows_fed, drafts, accepted, emitted;
+    uint64_t accepted_hist[16];
+    int32_t finished, n_out, cursor;
+} rama_q8_spec_report;
+int  rama_q8_spec_begin(rama_ctx *ctx, const rama_config *cfg, const rama_q8_weights *w, const rama_run_state *state,
+                        const int32_t *context_host, int n_context, const rama_q8_spec_plan *plan);
+int  rama_q8_spec_steps(rama_ctx *ctx, int n_steps);
+int  rama_q8_spec_poll(rama_ctx *ctx, int from, int32_t *out_tokens_host, int max_tokens, int *n_ready, int *finished);
+int  rama_q8_spec_tokens(rama_ctx *ctx, int32_t *out_host, int max_tokens, int *n);
+int  rama_q8_spec_stats(rama_ctx *ctx, rama_q8_spec_report *out);
+int  rama_q8_spec_end(rama_ctx *ctx);
+int  rama_q8_spec_draft(const int32_t *hint, int n_hint, const int32_t *seq, int L, int n_draft, int ngram, int room,
+                        int32_t *drafts_out);
+int  rama_q8_spec_accept(const int32_t *drafts, int n_d, const int32_t *picks, int stop_token, int remaining, int *finished);
+
 /* ---------------------------------------------------------------- measurement
  * HIP events on the context's stream (the stream the kernels are launched on). */
 int  rama_timer_start(rama_ctx *ctx);

@@ -54,6 +54,18 @@ pub struct rama_q8_serve_report {
     pub n_slots: i32, pub max_rows: i32,
     pub last_rows: [rama_q8_serve_row; 128], pub slots: [rama_q8_serve_slot; 128], pub generation: [i32; 128],
 }
+/// the speculative chain's plan (hint may be null with n_hint 0) and what rama_q8_spec_stats reports
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct rama_q8_spec_plan {
+    pub temperature: f32, pub topp: f32, pub u: f32, pub max_new: i32, pub stop_token: i32, pub n_draft: i32, pub ngram: i32,
+    pub hint: *const i32, pub n_hint: i32,
+}
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct rama_q8_spec_report {
+    pub steps: u64, pub graph_captures: u64, pub rows_fed: u64, pub drafts: u64, pub accepted: u64, pub emitted: u64,
+    pub accepted_hist: [u64; 16],
+    pub finished: i32, pub n_out: i32, pub cursor: i32,
+}
 #[repr(C)] pub struct rama_q8_model { _p: [u8; 0] }
 /// a Q8_0 (llama2.c version-2) model as device pointers; `x_s` = the fp32 scales of the int8 tensor `x`
 #[repr(C)] #[derive(Clone, Copy)]
@@ -236,6 +248,19 @@ extern "C" {
     pub fn rama_q8_serve_plan_step(slots: *const rama_q8_serve_slot, n_slots: c_int, max_rows: c_int, rows_out: *mut rama_q8_serve_row,
                                    slots_after: *mut rama_q8_serve_slot) -> c_int;
     pub fn rama_q8_serve_end(ctx: *mut rama_ctx) -> c_int;
+    // the speculative chain: one sequence, n-gram lookup drafts verified in one pass; _draft and _accept are host-only
+    pub fn rama_q8_spec_begin(ctx: *mut rama_ctx, cfg: *const rama_config, w: *const rama_q8_weights, state: *const rama_run_state,
+                              context_host: *const i32, n_context: c_int, plan: *const rama_q8_spec_plan) -> c_int;
+    pub fn rama_q8_spec_steps(ctx: *mut rama_ctx, n_steps: c_int) -> c_int;
+    pub fn rama_q8_spec_poll(ctx: *mut rama_ctx, from: c_int, out_tokens_host: *mut i32, max_tokens: c_int, n_ready: *mut c_int,
+                             finished: *mut c_int) -> c_int;
+    pub fn rama_q8_spec_tokens(ctx: *mut rama_ctx, out_host: *mut i32, max_tokens: c_int, n: *mut c_int) -> c_int;
+    pub fn rama_q8_spec_stats(ctx: *mut rama_ctx, out: *mut rama_q8_spec_report) -> c_int;
+    pub fn rama_q8_spec_end(ctx: *mut rama_ctx) -> c_int;
+    pub fn rama_q8_spec_draft(hint: *const i32, n_hint: c_int, seq: *const i32, l: c_int, n_draft: c_int, ngram: c_int, room: c_int,
+                              drafts_out: *mut i32) -> c_int;
+    pub fn rama_q8_spec_accept(drafts: *const i32, n_d: c_int, picks: *const i32, stop_token: c_int, remaining: c_int,
+                               finished: *mut c_int) -> c_int;
 }
 
 #[repr(C)] pub struct rama_pipe { _p: [u8; 0] }

@@ -91,6 +91,18 @@ class rama_q8_serve_report(C.Structure):
                  ("slots", rama_q8_serve_slot * 128), ("generation", C.c_int32 * 128)])
 
 
+class rama_q8_spec_plan(C.Structure):
+    """the speculative chain's sampler, budget, stop token, draft sizes and hint text (rama_q8_spec_begin)"""
+    _fields_ = [("temperature", C.c_float), ("topp", C.c_float), ("u", C.c_float), ("max_new", C.c_int32), ("stop_token", C.c_int32),
+                ("n_draft", C.c_int32), ("ngram", C.c_int32), ("hint", C.POINTER(C.c_int32)), ("n_hint", C.c_int32)]
+
+
+class rama_q8_spec_report(C.Structure):
+    """what rama_q8_spec_stats fills in: the device counters, the accept histogram, the sequence's cursor"""
+    _fields_ = ([(n, C.c_uint64) for n in ("steps", "graph_captures", "rows_fed", "drafts", "accepted", "emitted")] +
+                [("accepted_hist", C.c_uint64 * 16), ("finished", C.c_int32), ("n_out", C.c_int32), ("cursor", C.c_int32)])
+
+
 class rama_pipe_plan(C.Structure):
     _fields_ = [("n_seq", C.c_int32), ("n_pos", C.c_int32), ("wrap", C.c_int32), ("prompt", C.POINTER(C.c_int32)), ("n_prompt", C.c_int32),
                 ("temperature", C.c_float), ("topp", C.c_float), ("u", C.c_float), ("out_tokens_dev", C.c_void_p)]
@@ -209,6 +221,14 @@ SIGNATURES = {
     "rama_q8_serve_stats": (_int, [_vp, C.POINTER(rama_q8_serve_report)]),
     "rama_q8_serve_plan_step": (_int, [C.POINTER(rama_q8_serve_slot), _int, _int, C.POINTER(rama_q8_serve_row), C.POINTER(rama_q8_serve_slot)]),
     "rama_q8_serve_end": (_int, [_vp]),
+    "rama_q8_spec_begin": (_int, [_vp, _cfgp, C.POINTER(rama_q8_weights), _sp, i32p, _int, C.POINTER(rama_q8_spec_plan)]),
+    "rama_q8_spec_steps": (_int, [_vp, _int]),
+    "rama_q8_spec_poll": (_int, [_vp, _int, i32p, _int, C.POINTER(_int), C.POINTER(_int)]),
+    "rama_q8_spec_tokens": (_int, [_vp, i32p, _int, C.POINTER(_int)]),
+    "rama_q8_spec_stats": (_int, [_vp, C.POINTER(rama_q8_spec_report)]),
+    "rama_q8_spec_end": (_int, [_vp]),
+    "rama_q8_spec_draft": (_int, [i32p, _int, i32p, _int, _int, _int, _int, i32p]),
+    "rama_q8_spec_accept": (_int, [i32p, _int, i32p, _int, _int, C.POINTER(_int)]),
 }
 
 # exported but not in the header (the rama_internal_* accessors tests read; most declare their own types where they call them): here

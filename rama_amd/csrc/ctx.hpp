@@ -11,6 +11,7 @@
 #include "ref_order.hpp"        // RefAttnParams
 #include "chain_params.hpp"     // ChainParams, GemmChainParams, CEPI_* / CNORM_*
 #include "q8_serve_tables.hpp"  // ServeTables
+#include "q8_spec_tables.hpp"   // SpecTables
 
 #include <hip/hip_ext.h>   // hipExtLaunchKernelGGL: start/stop events carried by the dispatch itself
 
@@ -291,6 +292,20 @@ struct rama_ctx {
         unsigned long long steps = 0, captures = 0;
         CapturedGraph cg;                  // one step, for the chain's whole life: the tables' addresses, nothing of a sequence
     } q8s;
+    // rama_q8_spec_begin / _steps: the speculative chain (q8_spec.hpp), a third state next to the two above
+    struct Q8Spec {
+        bool active = false;               // false: no speculative chain
+        bool live = false;                 // false once the model or the run state has been freed: rama_q8_spec_steps refuses
+        bool sampled = false;              // a step runs the batched sampler's ordering launches
+        int n_rows = 0, out_cap = 0;       // n_draft + 1 rows per pass; max_new
+        SpecTables t{};                    // the device tables (ring / count / done: the device addresses of the two below)
+        char* blob = nullptr;              // ... all of them, one allocation
+        int* ring = nullptr;               // [max_new] host-pinned and device-mapped: token + 1, 0 = not emitted yet
+        int* words = nullptr;              // host-pinned and device-mapped: [0] tokens emitted, [1] 1 = the sequence has finished
+        rama_config cfg{}; rama_q8_weights w{}; rama_run_state state{};
+        unsigned long long captures = 0;
+        CapturedGraph cg;                  // one step, for the chain's whole life
+    } q8p;
 };
 
 // everything declared from here on is shared inside the library and kept out of its exported symbols

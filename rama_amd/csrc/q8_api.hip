@@ -1,12 +1,13 @@
 // q8_api.hip -- the Q8 part of the C ABI of include/rama_hip.h: rama_q8_quantize / _matmul, the Q8 forward and generate, the token
-// batches (prefill, decode batch), the chained batch and the serving chain.  The kernels are q8.hpp, q8_batch.hpp, q8_serve.hpp and
-// q8_fork.hpp; parity mode's norms and attention and the samplers are reached through the launchers of ctx.hpp, which chain_api.hip
+// batches (prefill, decode batch), the chained batch, the serving chain and the speculative chain.  The kernels are q8.hpp, q8_batch.hpp,
+// q8_serve.hpp, q8_fork.hpp and q8_spec.hpp; parity mode's norms and attention and the samplers are reached through the launchers of ctx.hpp, which chain_api.hip
 // defines -- this translation unit instantiates none of their kernels (DESIGN.md "Translation units").
 #include "ctx.hpp"
 #include "q8.hpp"
 #include "q8_batch.hpp"
 #include "q8_serve.hpp"
 #include "q8_fork.hpp"
+#include "q8_spec.hpp"
 
 #ifdef RAMA_CHAIN_HPP
 #error "q8_api.hip must not include chain.hpp: its kernels and g_pred_stats belong to chain_api.hip's code object"
@@ -33,6 +34,11 @@ void drop_q8_graphs(rama_ctx* c, const rama_run_state* s) {
         (void)hipStreamSynchronize(c->stream);
         sv.live = false;
     }
+    // the speculative chain: its step goes with all Q8 graphs; its run state ends it
+    auto& sp = c->q8p;
+    const bool spec_state = s && sp.active && sp.state.key_cache == s->key_cache;
+    if (sp.cg.exec && (!s || spec_state)) { (void)hipStreamSynchronize(c->stream); destroy_graph(sp.cg); }
+    if (spec_state) sp.live = false;
     bool any = false;
     for (auto& e : c->q8g) any = any || !s || !memcmp(&e.s, s, sizeof *s);
     if (!any) return;
@@ -50,6 +56,7 @@ extern "C" void rama_internal_drop_q8_graphs(rama_ctx* c, const rama_q8_weights*
     drop_q8_graphs(c, nullptr);
     if (freed && c->q8c.n_seq > 0 && c->q8c.w.wq == freed->wq) c->q8c.live = false;
     if (freed && c->q8s.n_slots > 0 && c->q8s.w.wq == freed->wq) c->q8s.live = false;
+    if (freed && c->q8p.active && c->q8p.w.wq == freed->wq) c->q8p.live = false;
 }
 
 // the serving chain's allocations (rama_q8_serve_begin / _end, release_q8); the stream is idle
@@ -71,10 +78,20 @@ static void q8_chain_release(rama_ctx* c) {
     if (qc.done) hipHostFree(qc.done);
     qc = rama_ctx::Q8Chain();
 }
+// ... and the speculative chain's
+static void spec_release(rama_ctx* c) {
+    auto& sp = c->q8p;
+    destroy_graph(sp.cg);
+    hipFree(sp.blob);
+    if (sp.ring) hipHostFree(sp.ring);
+    if (sp.words) hipHostFree(sp.words);
+    sp = rama_ctx::Q8Spec();
+}
 // rama_ctx_destroy: everything of the Q8 stack the context holds (the captured steps have gone with drop_q8_graphs)
 void release_q8(rama_ctx* c) {
     q8_chain_release(c);
     serve_release(c);
+    spec_release(c);
     hipFree(c->q8_xq); hipFree(c->q8_xs); hipFree(c->q8b_blob);
 }
 
@@ -433,6 +450,7 @@ static int ensure_q8_batch_scratch(rama_ctx* c, const rama_config* cfg, int gs, 
         HIPCHK(hipStreamSynchronize(c->stream));
         destroy_graph(c->q8c.cg);          // (the chained batch's step holds the old scratch's addresses)
         destroy_graph(c->q8s.cg);          // (and the serving chain's)
+        destroy_graph(c->q8p.cg);          // (and the speculative chain's)
         if (c->q8b_blob) { HIPCHK(hipFree(c->q8b_blob)); c->q8b_blob = nullptr; }
         c->q8b_cap = 0;
         HIPCHK(hipMalloc(&c->q8b_blob, need));
@@ -1101,5 +1119,204 @@ int rama_q8_serve_stats(rama_ctx* c, rama_q8_serve_report* out) {
         out->slots[i] = rama_q8_serve_slot{slots[i].state, slots[i].n_ctx, slots[i].cursor, slots[i].n_out, slots[i].max_new};
         out->generation[i] = sv.gen[i];
     }
+    return 0;
+}
+
+// ---- THE SPECULATIVE CHAIN (q8_spec.hpp): one sequence, up to 15 drafted tokens per step by n-gram lookup in its own text
+// and a caller's hint, drafts and the token before them verified in ONE weight pass of n_draft + 1 rows.  A token-batch pass over rows at
+// consecutive positions of one sequence gives every row the bits of its own rama_q8_forward, so whatever is accepted is what
+// rama_q8_generate produces: a wrong draft costs time only.  A third chain next to the two above, with a state of its own.
+
+// the drafting rule on the host (spec_draft_kernel finds the same occurrence by a max reduction over candidate ends)
+int rama_q8_spec_draft(const int32_t* hint, int n_hint, const int32_t* seq, int L, int n_draft, int ngram, int room, int32_t* drafts_out) {
+    REQUIRE(seq && L >= 1 && n_hint >= 0 && (n_hint == 0 || hint), RAMA_EINVAL, "q8_spec_draft: bad text");
+    REQUIRE(n_draft >= 0 && n_draft <= kSpecMaxDraft && ngram >= 1 && ngram <= kSpecMaxNgram, RAMA_EINVAL, "q8_spec_draft: n_draft in 0..15, ngram in 1..4");
+    REQUIRE(n_draft == 0 || drafts_out, RAMA_EINVAL, "q8_spec_draft: NULL argument");
+    const int cap = std::min(n_draft, room);
+    if (cap <= 0) return 0;
+    for (int n = std::min(ngram, L); n >= 1; n--) {
+        const int32_t* tail = seq + (L - n);
+        // the latest occurrence: its exclusive end e, in the hint first; in the sequence it ends before L
+        const int32_t* text = hint; int len = n_hint, e = -1;
+        for (int k = n_hint; k >= n && e < 0; k--) if (!memcmp(hint + (k - n), tail, sizeof(int32_t) * n)) e = k;
+        if (e < 0) {
+            text = seq; len = L;
+            for (int k = L - 1; k >= n && e < 0; k--) if (!memcmp(seq + (k - n), tail, sizeof(int32_t) * n)) e = k;
+        }
+        if (e < 0) continue;
+        const int n_d = std::min(cap, len - e);
+        for (int j = 0; j < n_d; j++) drafts_out[j] = text[e + j];
+        return n_d;
+    }
+    return 0;
+}
+
+int rama_q8_spec_accept(const int32_t* drafts, int n_d, const int32_t* picks, int stop_token, int remaining, int* finished) {
+    REQUIRE(picks && n_d >= 0 && n_d <= kSpecMaxDraft && (n_d == 0 || drafts) && remaining >= 1, RAMA_EINVAL,
+            "q8_spec_accept: n_d in 0..15 drafts, n_d + 1 picks, remaining >= 1");
+    int a = 0, fin = 0;
+    const int emit = spec_accept_rule(drafts, n_d, picks, stop_token, remaining, &a, &fin);
+    if (finished) *finished = fin;
+    return emit;
+}
+
+int rama_q8_spec_end(rama_ctx* c) {
+    RAMA_ENTER(c);
+    REQUIRE(c, RAMA_EINVAL, "q8_spec_end: ctx is NULL");
+    if (!c->q8p.active && !c->q8p.blob) return 0;
+    if (set_device(c)) return 1;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    spec_release(c);
+    return 0;
+}
+
+int rama_q8_spec_begin(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const rama_run_state* state, const int32_t* context_host,
+                       int n_context, const rama_q8_spec_plan* plan) {
+    RAMA_ENTER(c);
+    // everything is checked before anything of a running chain is touched
+    REQUIRE(c && state && context_host && plan, RAMA_EINVAL, "q8_spec_begin: NULL argument");
+    int rc = q8_check(c, cfg, w, state); if (rc) return rc;
+    const int V = cfg->vocab_size;
+    REQUIRE(topp_params_ok(plan->temperature, plan->topp, plan->u), RAMA_EINVAL, "q8_spec_begin: temperature >= 0, topp in [0,1], u in [0,1)");
+    REQUIRE(plan->stop_token >= -1 && plan->stop_token < V, RAMA_EINVAL, "q8_spec_begin: stop token outside the vocabulary");
+    REQUIRE(plan->n_draft >= 0 && plan->n_draft <= kSpecMaxDraft, RAMA_EINVAL, "q8_spec_begin: n_draft outside 0..15");
+    REQUIRE(plan->ngram >= 1 && plan->ngram <= kSpecMaxNgram, RAMA_EINVAL, "q8_spec_begin: ngram outside 1..4");
+    REQUIRE(plan->n_hint >= 0 && (plan->n_hint == 0 || plan->hint) && plan->n_hint < kSpecHintBit, RAMA_EINVAL, "q8_spec_begin: bad hint");
+    for (int i = 0; i < plan->n_hint; i++) REQUIRE(plan->hint[i] >= 0 && plan->hint[i] < V, RAMA_EINVAL, "q8_spec_begin: hint token outside the vocabulary");
+    REQUIRE(n_context >= 1, RAMA_EINVAL, "q8_spec_begin: n_context < 1");
+    REQUIRE(plan->max_new >= 1, RAMA_EINVAL, "q8_spec_begin: max_new < 1");
+    REQUIRE(plan->max_new <= cfg->seq_len && n_context <= cfg->seq_len - plan->max_new, RAMA_EINVAL, "q8_spec_begin: n_context + max_new beyond seq_len");
+    for (int i = 0; i < n_context; i++) REQUIRE(context_host[i] >= 0 && context_host[i] < V, RAMA_EINVAL, "q8_spec_begin: token outside the vocabulary");
+    REQUIRE(q8_batch_ok(cfg), RAMA_EUNSUP, "q8_spec_begin: a shape the Q8 token-batch pass does not take");
+    const bool sampled = plan->temperature != 0.0f;
+    REQUIRE(!sampled || (V > 1 && V <= kToppBlock * kToppMaxBlocks), RAMA_EUNSUP, "q8_spec_begin: a sampled plan needs vocab_size <= 32768");
+    if (set_device(c)) return 1;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    spec_release(c);
+    // both scratches, the sampler's slices and the chain's tables: sized here, outside any capture
+    rc = ensure_q8_scratch(c, cfg); if (rc) return rc;
+    Q8BatchScratch b{};
+    rc = ensure_q8_batch_scratch(c, cfg, w->group_size, &b); if (rc) return rc;
+    const int R = plan->n_draft + 1;
+    if (sampled) { rc = ensure_topp_batch(c, R, V); if (rc) return rc; }
+    auto& sp = c->q8p;
+    const size_t S = (size_t)cfg->seq_len, H = (size_t)plan->n_hint, cap = (size_t)plan->max_new;
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    const size_t sz[6] = {sizeof(SpecState), (H + S) * sizeof(int), kSpecRows * sizeof(SeqSlot), kSpecRows * sizeof(int), kSpecRows * sizeof(ToppRow),
+                          cap * sizeof(int)};
+    size_t off[6], need = 0;
+    for (int i = 0; i < 6; i++) { off[i] = need; need += up(sz[i]); }
+    HIPCHK(hipMalloc(&sp.blob, need));
+    HIPCHK(hipMemset(sp.blob, 0, need));
+    HIPCHK(hipHostMalloc(&sp.ring, sizeof(int) * cap, hipHostMallocMapped));
+    HIPCHK(hipHostMalloc(&sp.words, sizeof(int) * 2, hipHostMallocMapped));
+    memset(sp.ring, 0, sizeof(int) * cap);
+    memset(sp.words, 0, sizeof(int) * 2);
+    SpecTables& t = sp.t;
+    t.st = reinterpret_cast<SpecState*>(sp.blob + off[0]); t.text = reinterpret_cast<int*>(sp.blob + off[1]);
+    t.rows = reinterpret_cast<SeqSlot*>(sp.blob + off[2]); t.row_tok = reinterpret_cast<int*>(sp.blob + off[3]);
+    t.trow = reinterpret_cast<ToppRow*>(sp.blob + off[4]); t.out = reinterpret_cast<int*>(sp.blob + off[5]);
+    int* words_dev = nullptr;
+    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&t.ring), sp.ring, 0));
+    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&words_dev), sp.words, 0));
+    t.count = words_dev; t.done = words_dev + 1;
+    SpecState h{};
+    h.kc = state->key_cache; h.vc = state->value_cache;
+    h.L = n_context; h.max_new = plan->max_new; h.stop = plan->stop_token;
+    h.n_draft = plan->n_draft; h.ngram = plan->ngram; h.n_hint = plan->n_hint; h.seq_len = cfg->seq_len;
+    h.temperature = plan->temperature; h.topp = plan->topp; h.u = plan->u;
+    HIPCHK(hipMemcpy(t.st, &h, sizeof h, hipMemcpyHostToDevice));
+    if (plan->n_hint) HIPCHK(hipMemcpy(t.text, plan->hint, sizeof(int) * H, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(t.text + H, context_host, sizeof(int) * (size_t)n_context, hipMemcpyHostToDevice));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    sp.cfg = *cfg; sp.w = *w; sp.state = *state; sp.sampled = sampled;
+    sp.n_rows = R; sp.out_cap = plan->max_new; sp.captures = 0; sp.active = true; sp.live = true;
+    return 0;
+}
+
+// one step: the drafts and the row table, the pass over it, every row's logits, every row's pick, the accept rule
+static int enqueue_q8_spec_step(rama_ctx* c, const Q8BatchScratch& b) {
+    auto& sp = c->q8p;
+    const rama_config* cfg = &sp.cfg;
+    const rama_q8_weights* w = &sp.w;
+    const int dim = cfg->dim, V = cfg->vocab_size, R = sp.n_rows;
+    hipLaunchKernelGGL(spec_draft_kernel, dim3(1), dim3(1024), 0, c->stream, sp.t);
+    LAUNCHCHK();
+    hipLaunchKernelGGL(embed_rows_kernel, dim3((dim + 255) / 256, R), dim3(256), 0, c->stream, b.X, w->token_embedding_table, (const int*)sp.t.row_tok, R, dim);
+    LAUNCHCHK();
+    int rc = q8_batch_layers(c, cfg, w, b, R, 0, nullptr, nullptr, sp.t.rows); if (rc) return rc;
+    rc = enqueue_q8_classifier(c, cfg, w, b, b.X, R); if (rc) return rc;
+    SpecPickParams fin{};
+    fin.t = sp.t; fin.logits = b.LG; fin.ld = (size_t)V; fin.n = V;
+    if (sp.sampled) {
+        rc = enqueue_topp_batch_order(c, sp.t.trow, R, b.LG, (size_t)V, V, nullptr); if (rc) return rc;
+        fin.keys = c->tb.keys; fin.vals = c->tb.vals; fin.m = c->tb.m; fin.rstride = c->tb.rstride;
+    }
+    hipLaunchKernelGGL(spec_pick_kernel, dim3(R), dim3(1024), 0, c->stream, fin);
+    LAUNCHCHK();
+    hipLaunchKernelGGL(spec_accept_kernel, dim3(1), dim3(64), 0, c->stream, sp.t);
+    LAUNCHCHK();
+    return 0;
+}
+
+int rama_q8_spec_steps(rama_ctx* c, int n_steps) {
+    RAMA_ENTER(c);
+    REQUIRE(c && c->q8p.active, RAMA_EINVAL, "q8_spec_steps: call rama_q8_spec_begin first");
+    auto& sp = c->q8p;
+    REQUIRE(sp.live, RAMA_EINVAL, "q8_spec_steps: the chain's model or its run state has been freed");
+    REQUIRE(n_steps >= 0, RAMA_EINVAL, "q8_spec_steps: n_steps < 0");
+    if (set_device(c)) return 1;
+    // (neither grows here: rama_q8_spec_begin sized them, and whoever grew them since for another shape dropped the step's graph)
+    int rc = ensure_q8_scratch(c, &sp.cfg); if (rc) return rc;
+    Q8BatchScratch b{};
+    rc = ensure_q8_batch_scratch(c, &sp.cfg, sp.w.group_size, &b); if (rc) return rc;
+    if (sp.sampled) { rc = ensure_topp_batch(c, sp.n_rows, sp.cfg.vocab_size); if (rc) return rc; }
+    c->embedded_x = nullptr; c->host_pos = -1;
+    int n_done = 0;
+    return q8_run_steps(c, sp.cg, n_steps, [&] { return enqueue_q8_spec_step(c, b); }, &n_done, &sp.captures);
+}
+
+int rama_q8_spec_poll(rama_ctx* c, int from, int32_t* out_host, int max_tokens, int* n_ready, int* finished) {
+    RAMA_ENTER(c);
+    REQUIRE(c && n_ready && c->q8p.active && from >= 0 && max_tokens >= 0 && (max_tokens == 0 || out_host), RAMA_EINVAL, "q8_spec_poll: bad argument");
+    const auto& sp = c->q8p;
+    // the finished word first, then the count: each is stored after what it vouches for
+    const int fin = __atomic_load_n(sp.words + 1, __ATOMIC_ACQUIRE);
+    const int cnt = std::min(__atomic_load_n(sp.words, __ATOMIC_ACQUIRE), sp.out_cap);
+    *n_ready = read_ring(sp.ring, cnt, from, out_host, max_tokens);
+    if (finished) *finished = fin != 0;
+    return 0;
+}
+
+int rama_q8_spec_tokens(rama_ctx* c, int32_t* out_host, int max_tokens, int* n) {
+    RAMA_ENTER(c);
+    REQUIRE(c && n && c->q8p.active && max_tokens >= 0 && (max_tokens == 0 || out_host), RAMA_EINVAL, "q8_spec_tokens: bad argument");
+    auto& sp = c->q8p;
+    if (set_device(c)) return 1;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    { const int rh = handoff_check(c); if (rh) return rh; }
+    SpecState s{};
+    HIPCHK(hipMemcpy(&s, sp.t.st, sizeof s, hipMemcpyDeviceToHost));
+    const int k = std::min(std::min(s.n_out, sp.out_cap), max_tokens);
+    if (k > 0) HIPCHK(hipMemcpy(out_host, sp.t.out, sizeof(int) * k, hipMemcpyDeviceToHost));
+    *n = k;
+    return 0;
+}
+
+int rama_q8_spec_stats(rama_ctx* c, rama_q8_spec_report* out) {
+    RAMA_ENTER(c);
+    REQUIRE(c && out && c->q8p.active, RAMA_EINVAL, "q8_spec_stats: bad argument");
+    auto& sp = c->q8p;
+    if (set_device(c)) return 1;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    { const int rh = handoff_check(c); if (rh) return rh; }
+    SpecState s{};
+    HIPCHK(hipMemcpy(&s, sp.t.st, sizeof s, hipMemcpyDeviceToHost));
+    memset(out, 0, sizeof *out);
+    out->steps = s.steps; out->graph_captures = sp.captures; out->rows_fed = s.rows_fed; out->drafts = s.drafts;
+    out->accepted = s.accepted; out->emitted = s.emitted;
+    static_assert(sizeof out->accepted_hist == sizeof s.hist, "one histogram entry per accept count 0..15");
+    memcpy(out->accepted_hist, s.hist, sizeof s.hist);
+    out->finished = s.finished; out->n_out = s.n_out; out->cursor = s.L - 1;
     return 0;
 }

@@ -1,0 +1,57 @@
+// q8_spec_tables.hpp -- the speculative chain's device tables and its accept rule (q8_spec.hpp has the kernels that work on them): what
+// the host's context (ctx.hpp) keeps a copy of, so it holds no kernel
+#pragma once
+
+#include "kernels.hpp"          // SeqSlot
+#include "topp_sort.hpp"        // ToppRow
+
+namespace rama {
+
+constexpr int kSpecMaxDraft = 15;       // drafts per step: a pass of up to 16 rows is one 16-token tile of the K-split product
+constexpr int kSpecRows = kSpecMaxDraft + 1;
+constexpr int kSpecMaxNgram = 4;
+constexpr int kSpecHintBit = 1 << 30;   // spec_draft_kernel's match key: an occurrence in the hint beats every one in the sequence
+
+// the sequence on the device (one record; the counters are what rama_q8_spec_stats reports)
+struct SpecState {
+    float* kc; float* vc;               // the sequence's cache bases
+    int L;                              // known tokens s[0..L): s[L - 1] is fed next, at position L - 1
+    int n_out;                          // tokens emitted
+    int finished;
+    int n_d;                            // drafts of the step under way
+    int max_new, stop;                  // the budget; the token whose sampling ends the sequence (-1: none)
+    int n_draft, ngram, n_hint, seq_len;
+    float temperature, topp, u;
+    int pad_;
+    unsigned long long steps, rows_fed, drafts, accepted, emitted, hist[kSpecRows];
+    int d[kSpecRows];                   // the step's drafts (-1 behind n_d)
+    int picks[kSpecRows];               // Device::sample of rows 0..n_d
+};
+
+struct SpecTables {
+    SpecState* st;
+    int* text;                          // [n_hint + seq_len] the hint, then the sequence s
+    SeqSlot* rows;                      // [kSpecRows] the step's row table (n_draft + 1 entries used; idle: position -1)
+    int* row_tok;                       // [kSpecRows]
+    ToppRow* trow;                      // [kSpecRows] the sampler's record of the step: temperature 0 for an idle row
+    int* out;                           // [max_new] the tokens emitted
+    int* ring;                          // the same host-visible (token + 1)
+    int* count; int* done;              // host-visible: tokens emitted, stored after their ring words; the finished word, stored after both
+};
+
+// THE ACCEPT RULE (rama_q8_spec_accept on the host, spec_accept_kernel on the device: one statement for both).  *a: the drafts the picks
+// reproduce, from the front; pick_0 .. pick_a are emitted, cut at the budget (`remaining` >= 1 tokens) and after the first emitted token
+// equal to `stop`; either cut finishes the sequence.  Returns the tokens emitted (>= 1).
+__host__ __device__ inline int spec_accept_rule(const int* drafts, int n_d, const int* picks, int stop, int remaining, int* a, int* finished) {
+    int k = 0;
+    while (k < n_d && picks[k] == drafts[k]) k++;
+    *a = k;
+    int emit = k + 1 < remaining ? k + 1 : remaining;
+    int fin = emit >= remaining;
+    for (int j = 0; j < emit; j++)
+        if (picks[j] == stop) { emit = j + 1; fin = 1; break; }
+    *finished = fin;
+    return emit;
+}
+
+}  // namespace rama

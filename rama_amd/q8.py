@@ -122,6 +122,68 @@ class Q8Engine:
     def generate_greedy(self, prompt_tokens, steps: int):
         return self.generate(prompt_tokens, steps, 0.0)
 
+    SPEC_BLOCK = 4     # steps enqueued between two looks at the ring
+
+    spec_stats = None  # the last generate_spec's report (rama_q8_spec_stats)
+
+    def generate_spec(self, context, max_new, temperature=0.0, topp=0.9, u=TOPP_U_CPU, stop_token=None, n_draft=7, ngram=3,
+                      hint=None, on_token=None):
+        """speculative decode (rama_q8_spec_begin / _steps / _poll): context = the tokens fed at positions
+        0..n-1 (the caller includes BOS) -> the up to max_new sampled tokens, those generate(context[1:], n - 1 + max_new,
+        ...)[n-1:] gives, cut after stop_token.  Up to n_draft tokens per step are guessed by looking the last <= ngram
+        tokens up in `hint` (a token list, optional) and in the sequence itself, and verified in one weight pass.
+        context[:-1] is prefilled here; on_token(index, token), when given, is fed from the host-visible ring while the steps
+        run.  The report of the run stays behind as self.spec_stats."""
+        from ._lib import rama_q8_spec_plan, rama_q8_spec_report
+        import time
+        ctx_toks, hint_toks, (T, P, U, new, stop, K, N) = spec_plan(self.cfg, context, max_new, temperature, topp, u, stop_token,
+                                                                    n_draft, ngram, hint)
+        L, ctx = self.device.lib, self.device.ctx
+        if len(ctx_toks) > 1:
+            self.prefill(ctx_toks[:-1])
+        harr = (C.c_int32 * max(len(hint_toks), 1))(*hint_toks)
+        rec = rama_q8_spec_plan(T, P, U, new, stop, K, N, harr if hint_toks else None, len(hint_toks))
+        check(L.rama_q8_spec_begin(ctx, C.byref(self.model.ccfg), C.byref(self.model.weights), C.byref(self.state),
+                                   (C.c_int32 * len(ctx_toks))(*ctx_toks), len(ctx_toks), C.byref(rec)), "rama_q8_spec_begin")
+        out, buf = [], (C.c_int32 * 64)()
+        k, fin = C.c_int(), C.c_int()
+
+        def collect():
+            """what the ring holds -> True once the finished word is set and every token has been taken"""
+            while True:
+                # the finished word is read before the ring: once it is set, every token is there
+                check(L.rama_q8_spec_poll(ctx, len(out), buf, 64, C.byref(k), C.byref(fin)), "rama_q8_spec_poll")
+                for i in range(k.value):
+                    if on_token is not None:
+                        on_token(len(out), int(buf[i]))
+                    out.append(int(buf[i]))
+                if k.value < 64:
+                    return bool(fin.value)
+
+        left, done = new, False          # every step before the finish emits at least one token
+        while not done:
+            if left <= 0:
+                raise RuntimeError("generate_spec: max_new steps have run but the sequence has not finished")
+            n = min(self.SPEC_BLOCK, left)
+            check(L.rama_q8_spec_steps(ctx, n), "rama_q8_spec_steps")
+            left -= n
+            while True:
+                done = collect()
+                if done:
+                    break
+                q = L.rama_stream_query(ctx)
+                if q == 1:
+                    time.sleep(0.0001)
+                    continue
+                check(q, "rama_stream_query")
+                done = collect()
+                break
+        r = rama_q8_spec_report()
+        check(L.rama_q8_spec_stats(ctx, C.byref(r)), "rama_q8_spec_stats")
+        self.spec_stats = spec_report(r)
+        check(L.rama_q8_spec_end(ctx), "rama_q8_spec_end")
+        return out
+
     def set_graph_mode(self, on: bool):
         check(self.device.lib.rama_set_graph_mode(self.device.ctx, int(bool(on))), "rama_set_graph_mode")
 
@@ -668,3 +730,118 @@ class Q8Server:
                 e.free()
             self._mine, self._spare = [], []
             self._own, self._eng = [None] * self.n_slots, [None] * self.n_slots
+
+
+# ------------------------------------------------------------------ the speculative chain: n-gram lookup drafts (rama_q8_spec_*)
+
+MAX_DRAFT, MAX_NGRAM = 15, 4
+
+
+def spec_plan(cfg, context, max_new, temperature=0.0, topp=0.9, u=TOPP_U_CPU, stop_token=None, n_draft=7, ngram=3, hint=None):
+    """the checked arguments of Q8Engine.generate_spec: (context tokens, hint tokens, (temperature, topp, u, max_new, stop token,
+    n_draft, ngram)); ValueError for everything rama_q8_spec_begin would refuse in them.  No library call."""
+    what = "generate_spec"
+    V, S = cfg.vocab_size, cfg.seq_len
+    ctx = _tokens(context, V, what)
+    if not ctx:
+        raise ValueError(f"{what}: an empty context (the caller includes BOS)")
+    hint_toks = [] if hint is None else _tokens(hint, V, what + " hint")
+    T, P, U = float(temperature), float(topp), float(u)
+    if not (T >= 0.0 and 0.0 <= P <= 1.0 and 0.0 <= U < 1.0):       # (false for NaN)
+        raise ValueError(f"{what}: temperature >= 0, topp in [0, 1], u in [0, 1) -- not {T}, {P}, {U}")
+    new, K, N = int(max_new), int(n_draft), int(ngram)
+    if new < 1:
+        raise ValueError(f"{what}: max_new {new} < 1")
+    if len(ctx) + new > S:
+        raise ValueError(f"{what}: {len(ctx)} context tokens + {new} new ones beyond seq_len {S}")
+    if not 0 <= K <= MAX_DRAFT:
+        raise ValueError(f"{what}: n_draft {K} outside [0, {MAX_DRAFT}]")
+    if not 1 <= N <= MAX_NGRAM:
+        raise ValueError(f"{what}: ngram {N} outside [1, {MAX_NGRAM}]")
+    stop = -1 if stop_token is None else int(stop_token)
+    if not -1 <= stop < V:
+        raise ValueError(f"{what}: stop token {stop} outside the vocabulary [0, {V})")
+    if T != 0.0 and V > 32768:
+        raise ValueError(f"{what}: a sampled plan needs vocab_size <= 32768")
+    return ctx, hint_toks, (T, P, U, new, stop, K, N)
+
+
+def spec_report(r) -> dict:
+    """a rama_q8_spec_report as a dict"""
+    return dict(steps=int(r.steps), graph_captures=int(r.graph_captures), rows_fed=int(r.rows_fed), drafts=int(r.drafts),
+                accepted=int(r.accepted), emitted=int(r.emitted), accepted_hist=[int(v) for v in r.accepted_hist],
+                finished=int(r.finished), n_out=int(r.n_out), cursor=int(r.cursor))
+
+
+def spec_draft(hint, seq, n_draft, ngram, room):
+    """rama_q8_spec_draft, the drafting rule as a pure host function: the tokens that follow the latest occurrence of the last
+    <= ngram tokens of seq -- in hint first, then in seq itself -- at most min(n_draft, room) of them.  No GPU."""
+    from ._lib import load
+    hint, seq = [int(t) for t in (hint or [])], [int(t) for t in seq]
+    harr = (C.c_int32 * max(len(hint), 1))(*hint)
+    sarr = (C.c_int32 * max(len(seq), 1))(*seq)
+    out = (C.c_int32 * (MAX_DRAFT + 1))()
+    n = load().rama_q8_spec_draft(harr if hint else None, len(hint), sarr, len(seq), int(n_draft), int(ngram), int(room), out)
+    if n < 0:
+        check(n, "rama_q8_spec_draft")
+    return [int(out[i]) for i in range(n)]
+
+
+def spec_accept(drafts, picks, stop_token, remaining):
+    """rama_q8_spec_accept, the accept rule as a pure host function: picks = Device::sample of rows 0..len(drafts) ->
+    (tokens emitted, finished).  No GPU."""
+    from ._lib import load
+    drafts, picks = [int(t) for t in drafts], [int(t) for t in picks]
+    if len(picks) != len(drafts) + 1:
+        raise ValueError(f"spec_accept: {len(picks)} picks for {len(drafts)} drafts, not one more")
+    darr = (C.c_int32 * max(len(drafts), 1))(*drafts)
+    parr = (C.c_int32 * len(picks))(*picks)
+    fin = C.c_int()
+    n = load().rama_q8_spec_accept(darr, len(drafts), parr, -1 if stop_token is None else int(stop_token), int(remaining), C.byref(fin))
+    if n < 0:
+        check(n, "rama_q8_spec_accept")
+    return n, bool(fin.value)
+
+
+def _draft_py(hint, seq, n_draft, ngram, room):
+    cap = min(n_draft, room)
+    if cap <= 0:
+        return []
+    L = len(seq)
+    for n in range(min(ngram, L), 0, -1):
+        tail = seq[L - n:]
+        for text, hi in ((hint, len(hint)), (seq, L - 1)):          # an occurrence ends at e <= hi: in seq before L
+            for e in range(hi, n - 1, -1):
+                if text[e - n:e] == tail:
+                    return text[e:e + cap]
+    return []
+
+
+def spec_replay(ref_tokens, context, hint, n_draft, ngram, max_new, stop_token):
+    """the speculative chain's steps as a pure function of its inputs, no library call: ref_tokens = the max_new tokens the
+    sequence produces alone (Q8Engine.generate(context[1:], ...)[len(context) - 1:], not cut at the stop token) -> one
+    (n_d, a, emitted) per step up to the one that finishes the sequence.  Row j's pick is ref_tokens[emitted so far + j] as long
+    as the drafts before it were right, which is all the accept rule looks at."""
+    ref, s = [int(t) for t in ref_tokens], [int(t) for t in context]
+    hint = [int(t) for t in (hint or [])]
+    stop = -1 if stop_token is None else int(stop_token)
+    if len(ref) < max_new:
+        raise ValueError(f"spec_replay: {len(ref)} reference tokens for max_new {max_new}")
+    out, e, fin = [], 0, False
+    while not fin:
+        remaining = max_new - e
+        d = _draft_py(hint, s, n_draft, ngram, remaining - 1)
+        picks = ref[e:e + len(d) + 1]
+        a = 0
+        while a < len(d) and picks[a] == d[a]:
+            a += 1
+        emit = min(a + 1, remaining)
+        fin = emit >= remaining
+        for j in range(emit):
+            if picks[j] == stop:
+                emit, fin = j + 1, True
+                break
+        s += picks[:emit]
+        e += emit
+        out.append((len(d), a, emit))
+    return out
