@@ -616,7 +616,8 @@ int  rama_q8_serve_end(rama_ctx *ctx);
  * successful no-op.  Only cfg's dim, n_layers and seq_len and the states' key_cache / value_cache are used.  Stream-ordered on
  * the context's stream, never synchronises, legal between any two rama_q8_serve_steps calls.  The source may belong to a live
  * slot provided the copied rows lie below what earlier enqueued work has written (rows below a slot's cursor are never
- * rewritten).  RAMA_EINVAL for a NULL argument or cache, n_dst or n_rows out of range, a destination whose caches overlap the
+ * rewritten -- on a chain begun with rama_q8_serve_begin_spec too, where rows AT AND BEHIND a speculating slot's cursor may
+ * hold rejected drafts: fork only rows below the cursor, n_rows <= n_context - 1 + the tokens the host has seen).  RAMA_EINVAL for a NULL argument or cache, n_dst or n_rows out of range, a destination whose caches overlap the
  * source's or another destination's, and a destination that is in a live slot of the serving chain.  Cache bases that are not
  * 16-byte aligned take a slower path with the same result. */
 int  rama_q8_serve_admit_at(rama_ctx *ctx, int slot, const rama_run_state *state, const int32_t *context_host, int n_context,
@@ -693,6 +694,76 @@ int  rama_q8_spec_end(rama_ctx *ctx);
 int  rama_q8_spec_draft(const int32_t *hint, int n_hint, const int32_t *seq, int L, int n_draft, int ngram, int room,
                         int32_t *drafts_out);
 int  rama_q8_spec_accept(const int32_t *drafts, int n_d, const int32_t *picks, int stop_token, int remaining, int *finished);
+
+/* SPECULATION INSIDE THE SERVING CHAIN: a DECODE slot's drafts fill the rows no slot wants.  A step of the
+ * serving chain costs its weight pass of max_rows rows whatever they hold, and rows at consecutive positions of one sequence
+ * are exact (the speculative chain above); so a slot may put drafted tokens into rows that would otherwise be idle, and take
+ * several tokens out of one step.  Opt-in per chain and per slot: a chain begun with rama_q8_serve_begin is untouched.
+ *
+ * TEXT.  A slot's text is s = context ++ outputs, L = n_context + n_out tokens; on such a chain the slot's context buffer holds
+ *   s contiguously (n_context + max_new <= seq_len, so it fits) and every emitted token is appended to it on the device.
+ * DRAFT, per DECODE slot with n_draft > 0, at every step: exactly
+ *   rama_q8_spec_draft(hint, n_hint, s, L, n_draft, ngram, room),  room = min(seq_len - 1 - P, max_new - n_out - 1),  P = L - 1
+ *   (P is the slot's cursor) -> want[i] drafts d[i][0..want).  PROMPT, FREE and DONE slots, and slots with n_draft == 0, want 0.
+ * SCHEDULE (rama_q8_serve_spec_plan_step).  First rules 1-3 of the serving chain, unchanged: one row per DECODE slot, one per
+ *   PROMPT slot, the rows left over to PROMPT slots in ascending slot index.  Then
+ *   3a. the rows still left go to the DECODE slots' drafts in ascending slot index, slot i being granted min(want[i], left);
+ *   4.  the rest are idle.
+ *   Ingestion is certain work and a draft is a bet, so prompts go first.  Rows are laid out by slot index as before; a DECODE
+ *   slot's rows are tok, d[0..granted) at positions cursor .. cursor + granted; idle rows last.  With every want == 0 the table
+ *   is rama_q8_serve_plan_step's, except that the logits flag below is per row.
+ * LOGITS.  Every row of a DECODE slot and the final context row of a PROMPT slot are classified and picked: the final norm, the
+ *   quantizer and the classifier run over all max_rows rows in place (no gather), the sampler's records are per row, and
+ *   pick_r = Device::sample(logits_r) with the slot's temperature, topp and u.  A row's `logits` flag (rama_q8_serve_stats,
+ *   rama_q8_serve_spec_plan_step) is 1 for exactly those rows.
+ * ACCEPT, per slot.  A PROMPT slot inside its context moves its cursor on; at its final context position it records its one
+ *   pick and becomes DECODE (or DONE), as on any serving chain.  A DECODE slot takes
+ *   rama_q8_spec_accept(d, granted, picks of its rows, stop_token, max_new - n_out): the emitted tokens go to its output, to its
+ *   ring words in order and to its text; its token becomes the last one emitted, its cursor advances by the number emitted, and
+ *   it becomes DONE -- the finished word stored after the ring words -- when the rule says finished.
+ * Slot i's tokens are still, bit for bit, those of rama_q8_generate on that sequence alone, cut at the stop token, whatever
+ * the drafts, the hints, the neighbours, max_rows and the graph mode: row j of a slot gets the bits of its own rama_q8_forward
+ * provided the rows before it carry the right tokens (8.5), rows of different slots do not interact (8.1-8.3), and only picks
+ * behind verified drafts are emitted.  Cache rows below a slot's cursor hold that run's bits and are never rewritten, so
+ * rama_q8_kv_fork from a live speculating slot (rows below what earlier enqueued work has written as accepted, i.e. below its
+ * cursor) and prompt caching stay exact.  UNLIKE a plain serving chain, rows AT AND BEHIND the cursor, up to
+ * n_context - 2 + max_new, may hold the rows of rejected drafts: each is rewritten by the step that feeds its position before
+ * any attention reads it.  Nothing at or beyond row n_context - 1 + max_new is ever written.
+ *
+ * rama_q8_serve_begin_spec: rama_q8_serve_begin with its checks, plus 0 <= n_draft_cap <= 15 and 0 <= hint_cap < 2^30 (RAMA_EINVAL).
+ * Everything is sized here, outside any capture: the serving chain's tables, a hint buffer of hint_cap tokens and draft / pick
+ * arrays per slot, logits flags, sampler records and sampler slices for max_rows rows.  One serving chain per context, of
+ * either kind; rama_q8_serve_end, _steps, _poll, _tokens, _stats, the `live` rules and the graph rules are the same entries.
+ * rama_q8_serve_admit_spec: rama_q8_serve_admit_at (n_cached may be 0) with the slot's drafting fields; its checks in its
+ * order, then RAMA_EINVAL on a chain not begun with rama_q8_serve_begin_spec, for spec == NULL, n_draft outside
+ * [0, n_draft_cap], ngram outside 1..4, n_hint outside [0, hint_cap], n_hint > 0 with hint == NULL, a hint token outside the
+ * vocabulary.  rama_q8_serve_admit and rama_q8_serve_admit_at on such a chain admit with n_draft = 0.
+ * rama_q8_serve_spec_plan_step is HOST-ONLY (no context, no GPU): the schedule above as a pure function of the slot table and
+ * want[n_slots] (0..15 each; non-zero only for a DECODE slot, and then <= max_new - n_out - 1) -> rows_out[max_rows] and
+ * granted_out[n_slots].  The device scheduler produces exactly this table.
+ * rama_q8_serve_spec_stats synchronises.  steps and rows_decode / rows_prompt / rows_idle as rama_q8_serve_stats (rows_decode
+ * counts a DECODE slot's first row only), rows_draft and drafts_wanted as the scheduler counted them, drafts_granted,
+ * drafts_accepted and accepted_hist[a] (DECODE slot-steps that accepted a drafts) as the accept launch summed them --
+ * rows_draft == drafts_granted --, tokens_emitted (every token recorded, a PROMPT slot's first one included), and per slot the
+ * last step's wanted and granted drafts (0 for a slot admitted since).  RAMA_EINVAL on a chain begun without drafts. */
+typedef struct {
+    int32_t n_draft, ngram;                     /* K in 0..n_draft_cap, N in 1..4 */
+    const int32_t *hint; int32_t n_hint;        /* a text to look up in besides the slot's own; may be NULL / 0 */
+} rama_q8_serve_spec;
+typedef struct {
+    uint64_t steps, rows_decode, rows_draft, rows_prompt, rows_idle;
+    uint64_t drafts_wanted, drafts_granted, drafts_accepted, tokens_emitted;
+    uint64_t accepted_hist[16];
+    int32_t n_slots, max_rows, n_draft_cap, hint_cap;
+    int32_t last_want[128], last_granted[128];
+} rama_q8_serve_spec_report;
+int  rama_q8_serve_begin_spec(rama_ctx *ctx, const rama_config *cfg, const rama_q8_weights *w, int n_slots, int max_rows,
+                              int max_new_cap, int n_draft_cap, int hint_cap);
+int  rama_q8_serve_admit_spec(rama_ctx *ctx, int slot, const rama_run_state *state, const int32_t *context_host, int n_context,
+                              int n_cached, const rama_q8_serve_plan *plan, const rama_q8_serve_spec *spec);
+int  rama_q8_serve_spec_plan_step(const rama_q8_serve_slot *slots, int n_slots, int max_rows, const int32_t *want,
+                                  rama_q8_serve_row *rows_out, int32_t *granted_out);
+int  rama_q8_serve_spec_stats(rama_ctx *ctx, rama_q8_serve_spec_report *out);
 
 /* ---------------------------------------------------------------- measurement
  * HIP events on the context's stream (the stream the kernels are launched on). */

@@ -66,6 +66,18 @@ pub struct rama_q8_spec_report {
     pub accepted_hist: [u64; 16],
     pub finished: i32, pub n_out: i32, pub cursor: i32,
 }
+/// a slot's drafting fields on a serving chain begun with rama_q8_serve_begin_spec (hint may be null with n_hint 0) and what
+/// rama_q8_serve_spec_stats reports
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct rama_q8_serve_spec { pub n_draft: i32, pub ngram: i32, pub hint: *const i32, pub n_hint: i32 }
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct rama_q8_serve_spec_report {
+    pub steps: u64, pub rows_decode: u64, pub rows_draft: u64, pub rows_prompt: u64, pub rows_idle: u64,
+    pub drafts_wanted: u64, pub drafts_granted: u64, pub drafts_accepted: u64, pub tokens_emitted: u64,
+    pub accepted_hist: [u64; 16],
+    pub n_slots: i32, pub max_rows: i32, pub n_draft_cap: i32, pub hint_cap: i32,
+    pub last_want: [i32; 128], pub last_granted: [i32; 128],
+}
 #[repr(C)] pub struct rama_q8_model { _p: [u8; 0] }
 /// a Q8_0 (llama2.c version-2) model as device pointers; `x_s` = the fp32 scales of the int8 tensor `x`
 #[repr(C)] #[derive(Clone, Copy)]
@@ -261,6 +273,14 @@ extern "C" {
                               drafts_out: *mut i32) -> c_int;
     pub fn rama_q8_spec_accept(drafts: *const i32, n_d: c_int, picks: *const i32, stop_token: c_int, remaining: c_int,
                                finished: *mut c_int) -> c_int;
+    // speculation inside the serving chain: a DECODE slot's drafts in the rows no slot wants; _plan_step is host-only
+    pub fn rama_q8_serve_begin_spec(ctx: *mut rama_ctx, cfg: *const rama_config, w: *const rama_q8_weights, n_slots: c_int, max_rows: c_int,
+                                    max_new_cap: c_int, n_draft_cap: c_int, hint_cap: c_int) -> c_int;
+    pub fn rama_q8_serve_admit_spec(ctx: *mut rama_ctx, slot: c_int, state: *const rama_run_state, context_host: *const i32, n_context: c_int,
+                                    n_cached: c_int, plan: *const rama_q8_serve_plan, spec: *const rama_q8_serve_spec) -> c_int;
+    pub fn rama_q8_serve_spec_plan_step(slots: *const rama_q8_serve_slot, n_slots: c_int, max_rows: c_int, want: *const i32,
+                                        rows_out: *mut rama_q8_serve_row, granted_out: *mut i32) -> c_int;
+    pub fn rama_q8_serve_spec_stats(ctx: *mut rama_ctx, out: *mut rama_q8_serve_spec_report) -> c_int;
 }
 
 #[repr(C)] pub struct rama_pipe { _p: [u8; 0] }

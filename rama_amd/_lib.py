@@ -103,6 +103,19 @@ class rama_q8_spec_report(C.Structure):
                 [("accepted_hist", C.c_uint64 * 16), ("finished", C.c_int32), ("n_out", C.c_int32), ("cursor", C.c_int32)])
 
 
+class rama_q8_serve_spec(C.Structure):
+    """a slot's drafting fields on a serving chain begun with rama_q8_serve_begin_spec (rama_q8_serve_admit_spec)"""
+    _fields_ = [("n_draft", C.c_int32), ("ngram", C.c_int32), ("hint", C.POINTER(C.c_int32)), ("n_hint", C.c_int32)]
+
+
+class rama_q8_serve_spec_report(C.Structure):
+    """what rama_q8_serve_spec_stats fills in: the row counters, the draft counters, the accept histogram, per slot the last step's drafts"""
+    _fields_ = ([(n, C.c_uint64) for n in ("steps", "rows_decode", "rows_draft", "rows_prompt", "rows_idle", "drafts_wanted", "drafts_granted",
+                                           "drafts_accepted", "tokens_emitted")] +
+                [("accepted_hist", C.c_uint64 * 16)] + [(n, C.c_int32) for n in ("n_slots", "max_rows", "n_draft_cap", "hint_cap")] +
+                [("last_want", C.c_int32 * 128), ("last_granted", C.c_int32 * 128)])
+
+
 class rama_pipe_plan(C.Structure):
     _fields_ = [("n_seq", C.c_int32), ("n_pos", C.c_int32), ("wrap", C.c_int32), ("prompt", C.POINTER(C.c_int32)), ("n_prompt", C.c_int32),
                 ("temperature", C.c_float), ("topp", C.c_float), ("u", C.c_float), ("out_tokens_dev", C.c_void_p)]
@@ -229,6 +242,10 @@ SIGNATURES = {
     "rama_q8_spec_end": (_int, [_vp]),
     "rama_q8_spec_draft": (_int, [i32p, _int, i32p, _int, _int, _int, _int, i32p]),
     "rama_q8_spec_accept": (_int, [i32p, _int, i32p, _int, _int, C.POINTER(_int)]),
+    "rama_q8_serve_begin_spec": (_int, [_vp, _cfgp, C.POINTER(rama_q8_weights), _int, _int, _int, _int, _int]),
+    "rama_q8_serve_admit_spec": (_int, [_vp, _int, _sp, i32p, _int, _int, C.POINTER(rama_q8_serve_plan), C.POINTER(rama_q8_serve_spec)]),
+    "rama_q8_serve_spec_plan_step": (_int, [C.POINTER(rama_q8_serve_slot), _int, _int, i32p, C.POINTER(rama_q8_serve_row), i32p]),
+    "rama_q8_serve_spec_stats": (_int, [_vp, C.POINTER(rama_q8_serve_spec_report)]),
 }
 
 # exported but not in the header (the rama_internal_* accessors tests read; most declare their own types where they call them): here

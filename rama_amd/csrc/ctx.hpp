@@ -12,6 +12,7 @@
 #include "chain_params.hpp"     // ChainParams, GemmChainParams, CEPI_* / CNORM_*
 #include "q8_serve_tables.hpp"  // ServeTables
 #include "q8_spec_tables.hpp"   // SpecTables
+#include "q8_serve_spec_tables.hpp"     // ServeSpecTables
 
 #include <hip/hip_ext.h>   // hipExtLaunchKernelGGL: start/stop events carried by the dispatch itself
 
@@ -291,6 +292,13 @@ struct rama_ctx {
         std::vector<int> gen;
         unsigned long long steps = 0, captures = 0;
         CapturedGraph cg;                  // one step, for the chain's whole life: the tables' addresses, nothing of a sequence
+        // rama_q8_serve_begin_spec (q8_serve_spec.hpp): drafts in the rows no slot wants; all of it unused on a chain begun without it
+        bool spec = false;
+        int n_draft_cap = 0, hint_cap = 0;
+        ServeSpecTables st{};              // the device tables (inside blob)
+        char* sstage = nullptr;            // device: one spec admission record per slot (a ServeSpecSlot + hint_cap tokens)
+        char* spinned = nullptr;           // host-pinned: the same
+        size_t srec_bytes = 0;
     } q8s;
     // rama_q8_spec_begin / _steps: the speculative chain (q8_spec.hpp), a third state next to the two above
     struct Q8Spec {

@@ -1,6 +1,6 @@
 // q8_api.hip -- the Q8 part of the C ABI of include/rama_hip.h: rama_q8_quantize / _matmul, the Q8 forward and generate, the token
-// batches (prefill, decode batch), the chained batch, the serving chain and the speculative chain.  The kernels are q8.hpp, q8_batch.hpp,
-// q8_serve.hpp, q8_fork.hpp and q8_spec.hpp; parity mode's norms and attention and the samplers are reached through the launchers of ctx.hpp, which chain_api.hip
+// batches (prefill, decode batch), the chained batch, the serving chain (with and without drafts) and the speculative chain.  The kernels are q8.hpp,
+// q8_batch.hpp, q8_serve.hpp, q8_fork.hpp, q8_spec.hpp and q8_serve_spec.hpp; parity mode's norms and attention and the samplers are reached through the launchers of ctx.hpp, which chain_api.hip
 // defines -- this translation unit instantiates none of their kernels (DESIGN.md "Translation units").
 #include "ctx.hpp"
 #include "q8.hpp"
@@ -8,6 +8,7 @@
 #include "q8_serve.hpp"
 #include "q8_fork.hpp"
 #include "q8_spec.hpp"
+#include "q8_serve_spec.hpp"
 
 #ifdef RAMA_CHAIN_HPP
 #error "q8_api.hip must not include chain.hpp: its kernels and g_pred_stats belong to chain_api.hip's code object"
@@ -63,8 +64,9 @@ extern "C" void rama_internal_drop_q8_graphs(rama_ctx* c, const rama_q8_weights*
 static void serve_release(rama_ctx* c) {
     auto& sv = c->q8s;
     destroy_graph(sv.cg);
-    hipFree(sv.blob); hipFree(sv.stage);
+    hipFree(sv.blob); hipFree(sv.stage); hipFree(sv.sstage);
     if (sv.pinned) hipHostFree(sv.pinned);
+    if (sv.spinned) hipHostFree(sv.spinned);
     if (sv.ring) hipHostFree(sv.ring);
     if (sv.done) hipHostFree(sv.done);
     sv = rama_ctx::Q8Serve();
@@ -849,6 +851,43 @@ int rama_q8_serve_plan_step(const rama_q8_serve_slot* slots, int n_slots, int ma
     return 0;
 }
 
+// the same rule with the third class (serve_spec_schedule_kernel computes the same numbers by scans): what the prompts leave goes to the
+// DECODE slots' drafts, in ascending slot index
+int rama_q8_serve_spec_plan_step(const rama_q8_serve_slot* slots, int n_slots, int max_rows, const int32_t* want, rama_q8_serve_row* rows_out,
+                                 int32_t* granted_out) {
+    REQUIRE(slots && want && rows_out && granted_out, RAMA_EINVAL, "q8_serve_spec_plan_step: NULL argument");
+    REQUIRE(n_slots >= 1 && n_slots <= kServeMaxSlots && max_rows >= n_slots && max_rows <= kQ8bMaxTok, RAMA_EINVAL,
+            "q8_serve_spec_plan_step: 1 <= n_slots <= max_rows <= 128");
+    for (int i = 0; i < n_slots; i++) {
+        const rama_q8_serve_slot& s = slots[i];
+        REQUIRE(s.state >= RAMA_SERVE_FREE && s.state <= RAMA_SERVE_DONE, RAMA_EINVAL, "q8_serve_spec_plan_step: bad slot state");
+        if (s.state == RAMA_SERVE_PROMPT)
+            REQUIRE(s.n_context >= 1 && s.cursor >= 0 && s.cursor < s.n_context && s.max_new >= 1, RAMA_EINVAL, "q8_serve_spec_plan_step: bad PROMPT slot");
+        if (s.state == RAMA_SERVE_DECODE)
+            REQUIRE(s.cursor >= 0 && s.n_out >= 1 && s.n_out < s.max_new, RAMA_EINVAL, "q8_serve_spec_plan_step: bad DECODE slot");
+        REQUIRE(want[i] >= 0 && want[i] <= kSpecMaxDraft, RAMA_EINVAL, "q8_serve_spec_plan_step: a slot wants 0..15 drafts");
+        REQUIRE(want[i] == 0 || (s.state == RAMA_SERVE_DECODE && want[i] <= s.max_new - s.n_out - 1), RAMA_EINVAL,
+                "q8_serve_spec_plan_step: only a DECODE slot drafts, and at most max_new - n_out - 1 tokens");
+    }
+    int nrows[kServeMaxSlots];
+    serve_plan_counts(slots, n_slots, max_rows, nrows);
+    int left = max_rows;
+    for (int i = 0; i < n_slots; i++) left -= nrows[i];
+    for (int i = 0; i < n_slots; i++) {
+        granted_out[i] = std::min(want[i], left);
+        left -= granted_out[i];
+    }
+    int r = 0;
+    for (int i = 0; i < n_slots; i++) {
+        const rama_q8_serve_slot& s = slots[i];
+        const bool dec = s.state == RAMA_SERVE_DECODE;
+        for (int k = 0; k < nrows[i] + granted_out[i]; k++)
+            rows_out[r++] = rama_q8_serve_row{i, s.cursor + k, dec || s.cursor + k == s.n_context - 1 ? 1 : 0};
+    }
+    for (; r < max_rows; r++) rows_out[r] = rama_q8_serve_row{-1, -1, 0};
+    return 0;
+}
+
 int rama_q8_serve_end(rama_ctx* c) {
     RAMA_ENTER(c);
     REQUIRE(c, RAMA_EINVAL, "q8_serve_end: ctx is NULL");
@@ -859,7 +898,9 @@ int rama_q8_serve_end(rama_ctx* c) {
     return 0;
 }
 
-int rama_q8_serve_begin(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, int n_slots, int max_rows, int max_new_cap) {
+// rama_q8_serve_begin (spec false) and rama_q8_serve_begin_spec: the latter sizes the drafting tables as well, and its sampler for max_rows rows
+static int serve_begin(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, int n_slots, int max_rows, int max_new_cap, bool spec,
+                       int n_draft_cap, int hint_cap) {
     RAMA_ENTER(c);
     REQUIRE(c, RAMA_EINVAL, "ctx is NULL");
     int rc = check_cfg(cfg); if (rc) return rc;
@@ -873,6 +914,8 @@ int rama_q8_serve_begin(rama_ctx* c, const rama_config* cfg, const rama_q8_weigh
     const int V = cfg->vocab_size;
     const bool sampler = V > 1 && V <= kToppBlock * kToppMaxBlocks;
     REQUIRE(sampler || V % 4 == 0, RAMA_EUNSUP, "q8_serve_begin: vocab_size % 4 != 0 needs vocab_size <= 32768");
+    REQUIRE(n_draft_cap >= 0 && n_draft_cap <= kSpecMaxDraft, RAMA_EINVAL, "q8_serve_begin_spec: n_draft_cap outside 0..15");
+    REQUIRE(hint_cap >= 0 && hint_cap < kSpecHintBit, RAMA_EINVAL, "q8_serve_begin_spec: hint_cap outside [0, 2^30)");
     if (set_device(c)) return 1;
     HIPCHK(hipStreamSynchronize(c->stream));
     serve_release(c);
@@ -880,19 +923,34 @@ int rama_q8_serve_begin(rama_ctx* c, const rama_config* cfg, const rama_q8_weigh
     rc = ensure_q8_scratch(c, cfg); if (rc) return rc;
     Q8BatchScratch b{};
     rc = ensure_q8_batch_scratch(c, cfg, w->group_size, &b); if (rc) return rc;
-    if (sampler) { rc = ensure_topp_batch(c, n_slots, V); if (rc) return rc; }
+    if (sampler) { rc = ensure_topp_batch(c, spec ? max_rows : n_slots, V); if (rc) return rc; }      // (a spec chain picks per row)
     auto& sv = c->q8s;
-    const size_t S = (size_t)cfg->seq_len, N = (size_t)n_slots, R = (size_t)max_rows, cap = (size_t)max_new_cap;
+    const size_t S = (size_t)cfg->seq_len, N = (size_t)n_slots, R = (size_t)max_rows, cap = (size_t)max_new_cap, H = (size_t)hint_cap;
     auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-    const size_t sz[9] = {N * sizeof(ServeSlot), N * S * sizeof(int), R * sizeof(SeqSlot), R * sizeof(int), N * sizeof(int), N * sizeof(int),
-                          N * sizeof(ToppRow), 4 * sizeof(unsigned long long), N * cap * sizeof(int)};
-    size_t off[9], need = 0;
-    for (int i = 0; i < 9; i++) { off[i] = need; need += up(sz[i]); }
+    // [9..15]: the drafting tables, nothing of them on a chain begun without drafts
+    const size_t sz[16] = {N * sizeof(ServeSlot), N * S * sizeof(int), R * sizeof(SeqSlot), R * sizeof(int), N * sizeof(int), N * sizeof(int),
+                           N * sizeof(ToppRow), 4 * sizeof(unsigned long long), N * cap * sizeof(int),
+                           N * sizeof(ServeSpecSlot), N * H * sizeof(int), R * sizeof(int), R * sizeof(int), R * sizeof(ToppRow),
+                           N * sizeof(ServeSpecSums), 2 * sizeof(unsigned long long)};
+    const int n_tab = spec ? 16 : 9;
+    size_t off[16] = {}, need = 0;
+    for (int i = 0; i < n_tab; i++) { off[i] = need; need += up(sz[i]); }
     HIPCHK(hipMalloc(&sv.blob, need));
     HIPCHK(hipMemsetAsync(sv.blob, 0, need, c->stream));          // every slot FREE, the counters 0
     sv.rec_bytes = up(sizeof(ServeSlot) + S * sizeof(int));
     HIPCHK(hipMalloc(&sv.stage, N * sv.rec_bytes));
     HIPCHK(hipHostMalloc(&sv.pinned, N * sv.rec_bytes, hipHostMallocDefault));
+    if (spec) {
+        sv.srec_bytes = up(sizeof(ServeSpecSlot) + H * sizeof(int));
+        HIPCHK(hipMalloc(&sv.sstage, N * sv.srec_bytes));
+        HIPCHK(hipHostMalloc(&sv.spinned, N * sv.srec_bytes, hipHostMallocDefault));
+        ServeSpecTables& st = sv.st;
+        st.ss = reinterpret_cast<ServeSpecSlot*>(sv.blob + off[9]); st.hint = reinterpret_cast<int*>(sv.blob + off[10]);
+        st.picks = reinterpret_cast<int*>(sv.blob + off[11]); st.lflag = reinterpret_cast<int*>(sv.blob + off[12]);
+        st.rrow = reinterpret_cast<ToppRow*>(sv.blob + off[13]); st.sums = reinterpret_cast<ServeSpecSums*>(sv.blob + off[14]);
+        st.sched = reinterpret_cast<unsigned long long*>(sv.blob + off[15]);
+        st.hint_cap = hint_cap;
+    }
     HIPCHK(hipHostMalloc(&sv.ring, sizeof(int) * N * cap, hipHostMallocMapped));
     HIPCHK(hipHostMalloc(&sv.done, sizeof(int) * N, hipHostMallocMapped));
     memset(sv.ring, 0, sizeof(int) * N * cap);
@@ -910,8 +968,18 @@ int rama_q8_serve_begin(rama_ctx* c, const rama_config* cfg, const rama_q8_weigh
     sv.cfg = *cfg; sv.w = *w; sv.sampler = sampler;
     sv.states.assign(N, rama_run_state{}); sv.occupied.assign(N, 0); sv.gen.assign(N, 0);
     sv.steps = 0; sv.captures = 0;
+    sv.spec = spec; sv.n_draft_cap = n_draft_cap; sv.hint_cap = hint_cap;
     sv.max_rows = max_rows; sv.out_cap = max_new_cap; sv.n_slots = n_slots; sv.live = true;
     return 0;
+}
+
+int rama_q8_serve_begin(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, int n_slots, int max_rows, int max_new_cap) {
+    return serve_begin(c, cfg, w, n_slots, max_rows, max_new_cap, false, 0, 0);
+}
+
+int rama_q8_serve_begin_spec(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, int n_slots, int max_rows, int max_new_cap,
+                             int n_draft_cap, int hint_cap) {
+    return serve_begin(c, cfg, w, n_slots, max_rows, max_new_cap, true, n_draft_cap, hint_cap);
 }
 
 // the slot's occupant is still on the device's hands: admitted, and its finished word not yet set
@@ -921,8 +989,10 @@ static bool serve_slot_live(const rama_ctx::Q8Serve& sv, int slot) {
 
 // rama_q8_serve_admit (n_cached 0) and rama_q8_serve_admit_at: the slot starts PROMPT at cursor = n_cached, over rows 0 .. n_cached - 1 that
 // earlier work on the stream has put into the run state's caches
+// spec (rama_q8_serve_admit_spec; a chain begun with rama_q8_serve_begin_spec only): the slot's drafting fields and hint; without it a slot of
+// such a chain is admitted with n_draft = 0
 static int serve_admit(rama_ctx* c, int slot, const rama_run_state* state, const int32_t* context_host, int n_context, int n_cached,
-                       const rama_q8_serve_plan* plan) {
+                       const rama_q8_serve_plan* plan, const rama_q8_serve_spec* spec = nullptr) {
     RAMA_ENTER(c);
     REQUIRE(c && c->q8s.n_slots > 0, RAMA_EINVAL, "q8_serve_admit: call rama_q8_serve_begin first");
     auto& sv = c->q8s;
@@ -945,6 +1015,14 @@ static int serve_admit(rama_ctx* c, int slot, const rama_run_state* state, const
         REQUIRE(j == slot || !serve_slot_live(sv, j) || (sv.states[j].key_cache != state->key_cache && sv.states[j].value_cache != state->value_cache),
                 RAMA_EINVAL, "q8_serve_admit: the run state is already in a live slot");
     REQUIRE(plan->temperature == 0.0f || sv.sampler, RAMA_EUNSUP, "q8_serve_admit: a sampled plan needs vocab_size <= 32768");
+    if (spec) {
+        REQUIRE(sv.spec, RAMA_EINVAL, "q8_serve_admit_spec: the chain was not begun with rama_q8_serve_begin_spec");
+        REQUIRE(spec->n_draft >= 0 && spec->n_draft <= sv.n_draft_cap, RAMA_EINVAL, "q8_serve_admit_spec: n_draft beyond rama_q8_serve_begin_spec's n_draft_cap");
+        REQUIRE(spec->ngram >= 1 && spec->ngram <= kSpecMaxNgram, RAMA_EINVAL, "q8_serve_admit_spec: ngram outside 1..4");
+        REQUIRE(spec->n_hint >= 0 && (spec->n_hint == 0 || spec->hint) && spec->n_hint <= sv.hint_cap, RAMA_EINVAL,
+                "q8_serve_admit_spec: bad hint, or one beyond rama_q8_serve_begin_spec's hint_cap");
+        for (int i = 0; i < spec->n_hint; i++) REQUIRE(spec->hint[i] >= 0 && spec->hint[i] < V, RAMA_EINVAL, "q8_serve_admit_spec: hint token outside the vocabulary");
+    }
     if (set_device(c)) return 1;
     // the slot's own pinned record: its previous copy has run (the occupant it installed has finished, or there was none)
     char* rec = sv.pinned + (size_t)slot * sv.rec_bytes;
@@ -962,6 +1040,17 @@ static int serve_admit(rama_ctx* c, int slot, const rama_run_state* state, const
     HIPCHK(hipMemcpyAsync(dst, rec, sizeof h + sizeof(int) * (size_t)n_context, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(serve_install_kernel, dim3(1), dim3(256), 0, c->stream, sv.t, slot, reinterpret_cast<const ServeSlot*>(dst));
     LAUNCHCHK();
+    if (sv.spec) {      // the same way, the slot's own pinned spec record
+        char* srec = sv.spinned + (size_t)slot * sv.srec_bytes;
+        ServeSpecSlot g{};
+        g.n_draft = spec ? spec->n_draft : 0; g.ngram = spec ? spec->ngram : 1; g.n_hint = spec ? spec->n_hint : 0;
+        memcpy(srec, &g, sizeof g);
+        if (g.n_hint) memcpy(srec + sizeof g, spec->hint, sizeof(int) * (size_t)g.n_hint);
+        char* sdst = sv.sstage + (size_t)slot * sv.srec_bytes;
+        HIPCHK(hipMemcpyAsync(sdst, srec, sizeof g + sizeof(int) * (size_t)g.n_hint, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(serve_spec_install_kernel, dim3(1), dim3(256), 0, c->stream, sv.st, slot, reinterpret_cast<const ServeSpecSlot*>(sdst));
+        LAUNCHCHK();
+    }
     sv.states[slot] = *state; sv.occupied[slot] = 1; sv.gen[slot]++;
     return 0;
 }
@@ -973,6 +1062,12 @@ int rama_q8_serve_admit(rama_ctx* c, int slot, const rama_run_state* state, cons
 int rama_q8_serve_admit_at(rama_ctx* c, int slot, const rama_run_state* state, const int32_t* context_host, int n_context, int n_cached,
                            const rama_q8_serve_plan* plan) {
     return serve_admit(c, slot, state, context_host, n_context, n_cached, plan);
+}
+
+int rama_q8_serve_admit_spec(rama_ctx* c, int slot, const rama_run_state* state, const int32_t* context_host, int n_context, int n_cached,
+                             const rama_q8_serve_plan* plan, const rama_q8_serve_spec* spec) {
+    REQUIRE(spec, RAMA_EINVAL, "q8_serve_admit_spec: NULL argument");
+    return serve_admit(c, slot, state, context_host, n_context, n_cached, plan, spec);
 }
 
 // rows [0, n_rows) of every layer of src's caches into every destination's: one launch (q8_fork.hpp), stream-ordered
@@ -1045,6 +1140,34 @@ static int enqueue_q8_serve_step(rama_ctx* c, const Q8BatchScratch& b) {
     return 0;
 }
 
+// one step of a chain begun with rama_q8_serve_begin_spec: the drafts, the scheduler, the pass over its row table, every row's logits, every
+// flagged row's pick, the accept rule per slot
+static int enqueue_q8_serve_spec_step(rama_ctx* c, const Q8BatchScratch& b) {
+    auto& sv = c->q8s;
+    const rama_config* cfg = &sv.cfg;
+    const rama_q8_weights* w = &sv.w;
+    const int dim = cfg->dim, V = cfg->vocab_size, R = sv.max_rows, N = sv.n_slots;
+    hipLaunchKernelGGL(serve_draft_kernel, dim3(N), dim3(kServeDraftThreads), 0, c->stream, sv.t, sv.st);
+    LAUNCHCHK();
+    hipLaunchKernelGGL(serve_spec_schedule_kernel, dim3(1), dim3(kServeMaxSlots), 0, c->stream, sv.t, sv.st);
+    LAUNCHCHK();
+    hipLaunchKernelGGL(embed_rows_kernel, dim3((dim + 255) / 256, R), dim3(256), 0, c->stream, b.X, w->token_embedding_table, (const int*)sv.t.row_tok, R, dim);
+    LAUNCHCHK();
+    int rc = q8_batch_layers(c, cfg, w, b, R, 0, nullptr, nullptr, sv.t.rows); if (rc) return rc;
+    rc = enqueue_q8_classifier(c, cfg, w, b, b.X, R); if (rc) return rc;
+    ServeSpecPickParams fin{};
+    fin.t = sv.t; fin.st = sv.st; fin.logits = b.LG; fin.ld = (size_t)V; fin.n = V;
+    if (sv.sampler) {
+        rc = enqueue_topp_batch_order(c, sv.st.rrow, R, b.LG, (size_t)V, V, nullptr); if (rc) return rc;
+        fin.keys = c->tb.keys; fin.vals = c->tb.vals; fin.m = c->tb.m; fin.rstride = c->tb.rstride;
+    }
+    hipLaunchKernelGGL(serve_spec_pick_kernel, dim3(R), dim3(1024), 0, c->stream, fin);
+    LAUNCHCHK();
+    hipLaunchKernelGGL(serve_spec_accept_kernel, dim3(N), dim3(64), 0, c->stream, sv.t, sv.st);
+    LAUNCHCHK();
+    return 0;
+}
+
 int rama_q8_serve_steps(rama_ctx* c, int n_steps) {
     RAMA_ENTER(c);
     REQUIRE(c && c->q8s.n_slots > 0, RAMA_EINVAL, "q8_serve_steps: call rama_q8_serve_begin first");
@@ -1056,10 +1179,10 @@ int rama_q8_serve_steps(rama_ctx* c, int n_steps) {
     int rc = ensure_q8_scratch(c, &sv.cfg); if (rc) return rc;
     Q8BatchScratch b{};
     rc = ensure_q8_batch_scratch(c, &sv.cfg, sv.w.group_size, &b); if (rc) return rc;
-    if (sv.sampler) { rc = ensure_topp_batch(c, sv.n_slots, sv.cfg.vocab_size); if (rc) return rc; }
+    if (sv.sampler) { rc = ensure_topp_batch(c, sv.spec ? sv.max_rows : sv.n_slots, sv.cfg.vocab_size); if (rc) return rc; }
     c->embedded_x = nullptr; c->host_pos = -1;
     int n_done = 0;
-    rc = q8_run_steps(c, sv.cg, n_steps, [&] { return enqueue_q8_serve_step(c, b); }, &n_done, &sv.captures);
+    rc = q8_run_steps(c, sv.cg, n_steps, [&] { return sv.spec ? enqueue_q8_serve_spec_step(c, b) : enqueue_q8_serve_step(c, b); }, &n_done, &sv.captures);
     sv.steps += (unsigned long long)n_done;
     return rc;
 }
@@ -1104,7 +1227,8 @@ int rama_q8_serve_stats(rama_ctx* c, rama_q8_serve_report* out) {
     unsigned long long cnt[4];
     ServeSlot slots[kServeMaxSlots];
     SeqSlot rows[kQ8bMaxTok];
-    int lrow[kServeMaxSlots];
+    int lrow[kServeMaxSlots], lflag[kQ8bMaxTok];
+    if (sv.spec) HIPCHK(hipMemcpy(lflag, sv.st.lflag, sizeof(int) * sv.max_rows, hipMemcpyDeviceToHost));      // (a spec chain flags per row)
     HIPCHK(hipMemcpy(cnt, sv.t.counters, sizeof cnt, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(slots, sv.t.slots, sizeof(ServeSlot) * sv.n_slots, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(rows, sv.t.rows, sizeof(SeqSlot) * sv.max_rows, hipMemcpyDeviceToHost));
@@ -1113,11 +1237,40 @@ int rama_q8_serve_stats(rama_ctx* c, rama_q8_serve_report* out) {
     out->n_slots = sv.n_slots; out->max_rows = sv.max_rows;
     for (int r = 0; r < sv.max_rows; r++) {
         const bool on = cnt[0] > 0 && rows[r].pos >= 0;            // (before the first step the table holds nothing)
-        out->last_rows[r] = rama_q8_serve_row{on ? rows[r].pad : -1, on ? rows[r].pos : -1, on && lrow[rows[r].pad] == r ? 1 : 0};
+        const bool lg = on && (sv.spec ? lflag[r] != 0 : lrow[rows[r].pad] == r);
+        out->last_rows[r] = rama_q8_serve_row{on ? rows[r].pad : -1, on ? rows[r].pos : -1, lg ? 1 : 0};
     }
     for (int i = 0; i < sv.n_slots; i++) {
         out->slots[i] = rama_q8_serve_slot{slots[i].state, slots[i].n_ctx, slots[i].cursor, slots[i].n_out, slots[i].max_new};
         out->generation[i] = sv.gen[i];
+    }
+    return 0;
+}
+
+int rama_q8_serve_spec_stats(rama_ctx* c, rama_q8_serve_spec_report* out) {
+    RAMA_ENTER(c);
+    REQUIRE(c && out && c->q8s.n_slots > 0 && c->q8s.spec, RAMA_EINVAL, "q8_serve_spec_stats: no chain begun with rama_q8_serve_begin_spec");
+    auto& sv = c->q8s;
+    if (set_device(c)) return 1;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    { const int rh = handoff_check(c); if (rh) return rh; }
+    memset(out, 0, sizeof *out);
+    unsigned long long cnt[4], sched[2];
+    std::vector<ServeSpecSlot> ss(sv.n_slots);
+    std::vector<ServeSpecSums> sums(sv.n_slots);
+    HIPCHK(hipMemcpy(cnt, sv.t.counters, sizeof cnt, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(sched, sv.st.sched, sizeof sched, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ss.data(), sv.st.ss, sizeof(ServeSpecSlot) * sv.n_slots, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(sums.data(), sv.st.sums, sizeof(ServeSpecSums) * sv.n_slots, hipMemcpyDeviceToHost));
+    out->steps = cnt[0]; out->rows_decode = cnt[1]; out->rows_prompt = cnt[2]; out->rows_idle = cnt[3];
+    out->rows_draft = sched[0]; out->drafts_wanted = sched[1];
+    out->n_slots = sv.n_slots; out->max_rows = sv.max_rows; out->n_draft_cap = sv.n_draft_cap; out->hint_cap = sv.hint_cap;
+    static_assert(sizeof out->accepted_hist == sizeof sums[0].hist, "one histogram entry per accept count 0..15");
+    for (int i = 0; i < sv.n_slots; i++) {
+        out->drafts_granted += sums[i].granted; out->drafts_accepted += sums[i].accepted; out->tokens_emitted += sums[i].emitted;
+        for (int a = 0; a < kSpecRows; a++) out->accepted_hist[a] += sums[i].hist[a];
+        out->last_want[i] = cnt[0] ? ss[i].want : 0;
+        out->last_granted[i] = cnt[0] ? ss[i].granted : 0;
     }
     return 0;
 }

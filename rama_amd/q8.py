@@ -407,6 +407,174 @@ def common_prefix(a, b) -> int:
     return n
 
 
+MAX_DRAFT, MAX_NGRAM = 15, 4
+
+
+def serve_spec_sizes(n_draft, ngram, hint_cap):
+    """the checked drafting sizes of a Q8Server; ValueError for what rama_q8_serve_begin_spec would refuse.  No library call."""
+    n_draft, ngram, hint_cap = int(n_draft), int(ngram), int(hint_cap)
+    if not 0 <= n_draft <= MAX_DRAFT:
+        raise ValueError(f"Q8Server: n_draft {n_draft} outside [0, {MAX_DRAFT}]")
+    if not 1 <= ngram <= MAX_NGRAM:
+        raise ValueError(f"Q8Server: ngram {ngram} outside [1, {MAX_NGRAM}]")
+    if hint_cap < 0 or (hint_cap and not n_draft):
+        raise ValueError(f"Q8Server: hint_cap {hint_cap} (>= 0, and 0 on a server without drafts)")
+    return n_draft, ngram, hint_cap
+
+
+def serve_spec_request(cfg, n_draft_cap, ngram, hint_cap, n_draft=None, hint=None):
+    """the checked drafting arguments of Q8Server.submit: (n_draft, ngram, hint tokens); ValueError for everything
+    rama_q8_serve_admit_spec would refuse in them.  No library call."""
+    what = "Q8Server.submit"
+    K = n_draft_cap if n_draft is None else int(n_draft)
+    if not 0 <= K <= n_draft_cap:
+        raise ValueError(f"{what}: n_draft {K} outside [0, the server's n_draft = {n_draft_cap}]")
+    toks = [] if hint is None else _tokens(hint, cfg.vocab_size, what + " hint")
+    if len(toks) > hint_cap:
+        raise ValueError(f"{what}: {len(toks)} hint tokens beyond the server's hint_cap {hint_cap}")
+    return K, ngram, toks
+
+
+def serve_spec_report(r) -> dict:
+    """a rama_q8_serve_spec_report as a dict"""
+    return dict(steps=int(r.steps), rows_decode=int(r.rows_decode), rows_draft=int(r.rows_draft), rows_prompt=int(r.rows_prompt),
+                rows_idle=int(r.rows_idle), drafts_wanted=int(r.drafts_wanted), drafts_granted=int(r.drafts_granted),
+                drafts_accepted=int(r.drafts_accepted), tokens_emitted=int(r.tokens_emitted), accepted_hist=[int(v) for v in r.accepted_hist],
+                n_draft_cap=int(r.n_draft_cap), hint_cap=int(r.hint_cap), last_want=[int(v) for v in r.last_want[:r.n_slots]],
+                last_granted=[int(v) for v in r.last_granted[:r.n_slots]])
+
+
+def serve_spec_plan_step(slots, want, max_rows):
+    """rama_q8_serve_spec_plan_step, the scheduling rule with drafts as a pure host function: slots = (state, n_context, cursor,
+    n_out, max_new) tuples, want = the drafts every slot has for the step -> (rows [(slot, pos, logits)] * max_rows, the drafts
+    granted per slot).  No GPU."""
+    from ._lib import load, rama_q8_serve_row, rama_q8_serve_slot
+    n = len(slots)
+    if len(want) != n:
+        raise ValueError(f"serve_spec_plan_step: {len(want)} want values for {n} slots")
+    arr = (rama_q8_serve_slot * max(n, 1))(*[rama_q8_serve_slot(*[int(v) for v in s]) for s in slots])
+    warr = (C.c_int32 * max(n, 1))(*[int(v) for v in want])
+    rows = (rama_q8_serve_row * max(int(max_rows), 1))()
+    granted = (C.c_int32 * max(n, 1))()
+    check(load().rama_q8_serve_spec_plan_step(arr, n, int(max_rows), warr, rows, granted), "rama_q8_serve_spec_plan_step")
+    return [(r.slot, r.pos, r.logits) for r in rows[:int(max_rows)]], [int(g) for g in granted[:n]]
+
+
+def _spec_plan_py(slots, want, max_rows):
+    """the scheduling rule with drafts, in Python: slots = [state, n_context, cursor, ...] -> (rows, granted)"""
+    nrows = [1 if s[0] in (SERVE_PROMPT, SERVE_DECODE) else 0 for s in slots]
+    left = max_rows - sum(nrows)
+    for i, s in enumerate(slots):
+        if s[0] == SERVE_PROMPT:
+            extra = min(s[1] - s[2] - 1, left)
+            nrows[i] += extra
+            left -= extra
+    granted = [0] * len(slots)
+    for i, s in enumerate(slots):
+        granted[i] = min(want[i], left) if s[0] == SERVE_DECODE else 0
+        left -= granted[i]
+    rows = []
+    for i, s in enumerate(slots):
+        for k in range(nrows[i] + granted[i]):
+            rows.append((i, s[2] + k, 1 if s[0] == SERVE_DECODE or s[2] + k == s[1] - 1 else 0))
+    return rows + [(-1, -1, 0)] * (max_rows - len(rows)), granted
+
+
+def serve_spec_replay(requests, ref_tokens, n_slots, max_rows, use_slots=None):
+    """a whole workload of a serving chain with drafts as a pure function of its inputs, no library call.  requests = dicts with
+    context and max_new, and optionally stop_token, n_draft (0), ngram (3), hint and n_cached (0); ref_tokens[i] = the max_new
+    tokens request i produces alone (Q8Engine.generate(context[1:], ...)[len(context) - 1:], not cut at the stop token).
+    Admission: before every step the waiting requests, in order, take the slots of use_slots (default: all) that are FREE or
+    DONE, in ascending slot index.  Every step is the draft rule per DECODE slot, the scheduling rule, and the accept rule by
+    comparison with the reference tokens: row j's pick is ref[n_out + j] as long as the drafts before it were right, which is
+    all the accept rule looks at.  -> dict(steps = one dict per step: admitted [(slot, request)], rows, want, granted, accepted
+    {slot: a} for the DECODE slots, emitted {slot: n}, finished [slots]; counters = what rama_q8_serve_spec_stats reports;
+    finish_step = per request the step it finishes in; slot = per request its slot; outputs = per request its tokens)."""
+    reqs = []
+    for r, ref in zip(requests, ref_tokens):
+        ctx, new = [int(t) for t in r["context"]], int(r["max_new"])
+        if len(ref) < new:
+            raise ValueError(f"serve_spec_replay: {len(ref)} reference tokens for max_new {new}")
+        stop = r.get("stop_token")
+        reqs.append(dict(ctx=ctx, new=new, stop=-1 if stop is None else int(stop), K=int(r.get("n_draft", 0)), N=int(r.get("ngram", 3)),
+                         hint=[int(t) for t in (r.get("hint") or [])], cached=int(r.get("n_cached", 0)), ref=[int(t) for t in ref]))
+    usable = list(range(n_slots)) if use_slots is None else sorted(use_slots)
+    slots = [[SERVE_FREE, 0, 0, 0, 0] for _ in range(n_slots)]      # state, n_context, cursor, n_out, max_new
+    who, text = [None] * n_slots, [None] * n_slots
+    waiting = list(range(len(reqs)))
+    steps, finish, slot_of, outputs = [], [None] * len(reqs), [None] * len(reqs), [[] for _ in reqs]
+    cnt = dict(steps=0, rows_decode=0, rows_draft=0, rows_prompt=0, rows_idle=0, drafts_wanted=0, drafts_granted=0, drafts_accepted=0,
+               tokens_emitted=0, accepted_hist=[0] * 16)
+    while waiting or any(s[0] in (SERVE_PROMPT, SERVE_DECODE) for s in slots):
+        admitted = []
+        for i in usable:
+            if waiting and slots[i][0] in (SERVE_FREE, SERVE_DONE):
+                q = waiting.pop(0)
+                r = reqs[q]
+                slots[i] = [SERVE_PROMPT, len(r["ctx"]), r["cached"], 0, r["new"]]
+                who[i], text[i], slot_of[q] = q, list(r["ctx"]), i
+                admitted.append((i, q))
+        if not any(s[0] in (SERVE_PROMPT, SERVE_DECODE) for s in slots):
+            raise ValueError("serve_spec_replay: requests are waiting but no slot can take them")
+        want, drafts = [0] * n_slots, [[] for _ in range(n_slots)]
+        for i, s in enumerate(slots):
+            if s[0] == SERVE_DECODE and reqs[who[i]]["K"] > 0:
+                r = reqs[who[i]]
+                drafts[i] = _draft_py(r["hint"], text[i], r["K"], r["N"], s[4] - s[3] - 1)      # (n_context + max_new <= seq_len: the budget binds first)
+                want[i] = len(drafts[i])
+        rows, granted = _spec_plan_py(slots, want, max_rows)
+        used = sum(1 for r in rows if r[0] >= 0)
+        n_dec = sum(1 for s in slots if s[0] == SERVE_DECODE)
+        cnt["steps"] += 1
+        cnt["rows_decode"] += n_dec
+        cnt["rows_draft"] += sum(granted)
+        cnt["rows_prompt"] += used - n_dec - sum(granted)
+        cnt["rows_idle"] += max_rows - used
+        cnt["drafts_wanted"] += sum(want)
+        accepted, emitted, finished = {}, {}, []
+        for i, s in enumerate(slots):
+            n = sum(1 for r in rows if r[0] == i)
+            if n == 0:
+                continue
+            r = reqs[who[i]]
+            if s[0] == SERVE_PROMPT and s[2] + n < s[1]:
+                s[2] += n
+                continue
+            if s[0] == SERVE_PROMPT:
+                picks, emit = r["ref"][:1], 1
+                fin = s[4] <= 1 or picks[0] == r["stop"]
+                s[2] = s[1]
+            else:
+                d, remaining = drafts[i][:granted[i]], s[4] - s[3]
+                picks = r["ref"][s[3]:s[3] + len(d) + 1]
+                a = 0
+                while a < len(d) and picks[a] == d[a]:
+                    a += 1
+                emit = min(a + 1, remaining)
+                fin = emit >= remaining
+                for j in range(emit):
+                    if picks[j] == r["stop"]:
+                        emit, fin = j + 1, True
+                        break
+                accepted[i] = a
+                cnt["drafts_granted"] += len(d)
+                cnt["drafts_accepted"] += a
+                cnt["accepted_hist"][a] += 1
+                s[2] += emit
+            emitted[i] = emit
+            cnt["tokens_emitted"] += emit
+            text[i] += picks[:emit]
+            outputs[who[i]] += picks[:emit]
+            s[3] += emit
+            s[0] = SERVE_DONE if fin else SERVE_DECODE
+            if fin:
+                finished.append(i)
+                finish[who[i]] = len(steps)
+        steps.append(dict(admitted=admitted, rows=rows, want=want, granted=granted, accepted=accepted, emitted=emitted, finished=finished,
+                          slots=[tuple(s) for s in slots]))
+    return dict(steps=steps, counters=cnt, finish_step=finish, slot=slot_of, outputs=outputs)
+
+
 class PrefixPool:
     """the donors of Q8Server's prefix cache: at most k engines, each keyed by the tokens whose cache rows it holds (row t is a
     function of tokens 0..t only, and its bits do not depend on who computed it).  Least recently used goes first.  Pure host
@@ -470,41 +638,58 @@ class Q8Server:
     (a chat's next turn on the same engine).  prefix_cache=k keeps a pool of at most k donor engines: a request submitted with
     retain=True leaves its engine there when it finishes, keyed by the tokens whose rows it holds; every later request is
     matched against the pool at its admission, the longest shared prefix is forked into its engine (rama_q8_kv_fork) and the
-    slot starts at that cursor (rama_q8_serve_admit_at).  The tokens are the same with the cache on and off."""
+    slot starts at that cursor (rama_q8_serve_admit_at).  The tokens are the same with the cache on and off.
 
-    def __init__(self, model: Q8Model, n_slots: int, max_rows=None, max_new_cap: int = 256, prefix_cache: int = 0):
+    Drafts.  n_draft=K > 0 begins the chain with rama_q8_serve_begin_spec: a decoding request guesses up to K
+    tokens per step by looking its last <= ngram tokens up in its own text and in the hint it was submitted with (at most
+    hint_cap tokens), the guesses take the rows of the step that no slot wants -- prompts first -- and are verified in the same
+    weight pass.  The tokens are the same with drafts on and off; n_draft=0 (the default) is the plain chain."""
+
+    def __init__(self, model: Q8Model, n_slots: int, max_rows=None, max_new_cap: int = 256, prefix_cache: int = 0, n_draft: int = 0,
+                 ngram: int = 3, hint_cap: int = 0):
         self.n_slots, self.max_rows, self.max_new_cap = serve_sizes(model.cfg, n_slots, max_rows, max_new_cap)
+        self.n_draft, self.ngram, self.hint_cap = serve_spec_sizes(n_draft, ngram, hint_cap)
+        self.spec = self.n_draft > 0                      # n_draft == 0: the plain chain, rama_q8_serve_begin
         self.pool = PrefixPool(prefix_cache)              # (raises before any library call)
         self.model, self.device, self.cfg = model, model.device, model.cfg
         L = self.device.lib
-        check(L.rama_q8_serve_begin(self.device.ctx, C.byref(model.ccfg), C.byref(model.weights), self.n_slots, self.max_rows,
-                                    self.max_new_cap), "rama_q8_serve_begin")
+        if self.spec:
+            check(L.rama_q8_serve_begin_spec(self.device.ctx, C.byref(model.ccfg), C.byref(model.weights), self.n_slots, self.max_rows,
+                                             self.max_new_cap, self.n_draft, self.hint_cap), "rama_q8_serve_begin_spec")
+        else:
+            check(L.rama_q8_serve_begin(self.device.ctx, C.byref(model.ccfg), C.byref(model.weights), self.n_slots, self.max_rows,
+                                        self.max_new_cap), "rama_q8_serve_begin")
         self._open = True
         self._own = [None] * self.n_slots                 # the server's own engine of a slot, made on first use and reused
         self._eng = [None] * self.n_slots                 # the engine the slot's occupant runs on
         self._spare = []                                  # the server's own engines that serve nobody: evicted donors
         self._mine = []                                   # every engine the server made (close frees them)
         self._cached = {}                                 # handle -> the n_cached it was admitted with
+        self._drafts = {}                                 # handle -> (n_draft, ngram, hint tokens)
         self.rows_cached = 0                              # ... summed over the admissions
         self._req = [None] * self.n_slots                 # the handle a slot serves
         self._seen = [0] * self.n_slots
         self._mirror = [(SERVE_FREE, 0, 0, 0, 0)] * self.n_slots      # the host's copy of the slot table (exact unless a stop token fell)
         self._queue, self._results, self._finished, self._plans = [], {}, set(), {}
         self._next = 0
-        self.planned = dict(steps=0, rows_decode=0, rows_prompt=0, rows_idle=0)      # the host plan's sums over the steps enqueued
+        self.planned = dict(steps=0, rows_decode=0, rows_prompt=0, rows_idle=0)      # the host plan's sums over the steps enqueued (none with drafts: no host plan)
         self.last_rows = []                               # ... and its row table of the last one
 
     # -- requests
     def submit(self, context, max_new, temperature=0.0, topp=0.9, u=TOPP_U_CPU, stop_token=None, engine=None, n_cached=0,
-               retain=False):
+               retain=False, n_draft=None, hint=None):
         """queue a request -> its handle.  It is admitted at once if a slot is free, else when one finishes (step / run).
         engine: the Q8Engine whose run state the sequence uses (default: one the server owns for the slot).
         n_cached: rows 0..n_cached-1 of `engine` already hold context[0..n_cached) -- written by work enqueued earlier on the
         device's stream; the slot feeds the rest (at most n_context - 1: the final position is always fed).  Such a request is
         not matched against the prefix cache.
         retain: with a prefix cache, the engine stays behind as a donor when the request finishes (a caller's engine too: it
-        is the pool's until it is evicted)."""
+        is the pool's until it is evicted).
+        n_draft, hint: on a server made with n_draft > 0, the drafts per step of this request (default: the server's; 0: none)
+        and a token list to look up in besides the request's own text (at most hint_cap tokens).  The tokens are the same
+        whatever they are."""
         ctx, plan = serve_plan(self.cfg, context, max_new, temperature, topp, u, stop_token, self.max_new_cap, n_cached)
+        draft = serve_spec_request(self.cfg, self.n_draft, self.ngram, self.hint_cap, n_draft, hint)
         n_cached = int(n_cached)
         if n_cached and engine is None:
             raise ValueError("Q8Server.submit: n_cached needs the engine that holds the rows")
@@ -517,6 +702,7 @@ class Q8Server:
         h = self._next
         self._next += 1
         self._plans[h] = (ctx, plan, engine, n_cached, bool(retain))
+        self._drafts[h] = draft
         self._results[h] = []
         self._queue.append(h)
         self._admit()
@@ -551,7 +737,14 @@ class Q8Server:
                           "rama_q8_kv_fork")
             rec = rama_q8_serve_plan(T, P, U, new, stop)
             arr = (C.c_int32 * len(toks))(*toks)
-            if n_cached:
+            if self.spec:
+                from ._lib import rama_q8_serve_spec
+                K, N, hint = self._drafts[h]
+                harr = (C.c_int32 * max(len(hint), 1))(*hint)
+                srec = rama_q8_serve_spec(K, N, harr if hint else None, len(hint))
+                check(L.rama_q8_serve_admit_spec(ctx, slot, C.byref(eng.state), arr, len(toks), n_cached, C.byref(rec), C.byref(srec)),
+                      "rama_q8_serve_admit_spec")
+            elif n_cached:
                 check(L.rama_q8_serve_admit_at(ctx, slot, C.byref(eng.state), arr, len(toks), n_cached, C.byref(rec)), "rama_q8_serve_admit_at")
             else:
                 check(L.rama_q8_serve_admit(ctx, slot, C.byref(eng.state), arr, len(toks), C.byref(rec)), "rama_q8_serve_admit")
@@ -619,7 +812,7 @@ class Q8Server:
         self._count_and_enqueue(int(n))
 
     def _count_and_enqueue(self, n):
-        for _ in range(n):
+        for _ in range(0 if self.spec else n):            # (with drafts the rows of a step depend on what is accepted: no host plan)
             before = self._mirror
             rows, self._mirror = serve_plan_step(before, self.max_rows)
             self.last_rows = rows
@@ -660,6 +853,8 @@ class Q8Server:
         no rows, and an admission is stream-ordered behind them, so the host plan stays exact.  A stop token that ends a sequence
         earlier is seen at the next collection."""
         import time
+        if self.spec:
+            return self._run_spec(on_token)
         done_in = lambda t: {i for i in range(self.n_slots) if self._req[i] is not None and t[i][0] == SERVE_DONE}
         while True:
             if self._collect(on_token):
@@ -691,6 +886,33 @@ class Q8Server:
                     raise RuntimeError(f"Q8Server.run: the steps have run but slots {[i for i in expect if self._req[i] is not None]} have not finished")
                 break
 
+    SPEC_BLOCK = 4     # with drafts: at most this many steps between two looks at the device's slot table
+
+    def _run_spec(self, on_token=None):
+        """run() on a server with drafts.  A slot may finish earlier than the host plan foresees, so the plan -- one token per
+        DECODE slot and step -- is an upper bound: the slot table is taken from the device before every block, the steps to the
+        next finish by that plan -- SPEC_BLOCK at most -- are enqueued, and the finished words alone say who has finished.  A request that waits is
+        admitted as soon as a finished word shows, behind the steps still in flight; the device never idles past a finish by
+        more than the block enqueued."""
+        import time
+        while True:
+            self._resync()                                # (synchronises: the block before has run)
+            self._collect(on_token)
+            self._admit()
+            if all(h is None for h in self._req):
+                if self._queue:
+                    raise RuntimeError("Q8Server.run: requests are waiting but no slot can take them")
+                return
+            self._count_and_enqueue(max(min(self._steps_to_next_finish(), self.SPEC_BLOCK), 1))
+            while True:
+                self._collect(on_token)
+                self._admit()
+                q = self.device.lib.rama_stream_query(self.device.ctx)
+                if q != 1:
+                    check(q, "rama_stream_query")
+                    break
+                time.sleep(0.0001)
+
     def _after(self, k):
         m = list(self._mirror)
         for _ in range(k):
@@ -715,7 +937,13 @@ class Q8Server:
         from ._lib import rama_q8_serve_report
         r = rama_q8_serve_report()
         check(self.device.lib.rama_q8_serve_stats(self.device.ctx, C.byref(r)), "rama_q8_serve_stats")
-        return dict(steps=int(r.steps), graph_captures=int(r.graph_captures), rows_decode=int(r.rows_decode), rows_prompt=int(r.rows_prompt),
+        spec = {}
+        if self.spec:
+            from ._lib import rama_q8_serve_spec_report
+            q = rama_q8_serve_spec_report()
+            check(self.device.lib.rama_q8_serve_spec_stats(self.device.ctx, C.byref(q)), "rama_q8_serve_spec_stats")
+            spec = dict(spec=serve_spec_report(q))
+        return dict(**spec, steps=int(r.steps), graph_captures=int(r.graph_captures), rows_decode=int(r.rows_decode), rows_prompt=int(r.rows_prompt),
                     rows_idle=int(r.rows_idle), rows_cached=self.rows_cached, n_slots=int(r.n_slots), max_rows=int(r.max_rows),
                     last_rows=[(x.slot, x.pos, x.logits) for x in r.last_rows[:r.max_rows]],
                     slots=[(s.state, s.n_context, s.cursor, s.n_out, s.max_new) for s in r.slots[:r.n_slots]],
@@ -733,9 +961,6 @@ class Q8Server:
 
 
 # ------------------------------------------------------------------ the speculative chain: n-gram lookup drafts (rama_q8_spec_*)
-
-MAX_DRAFT, MAX_NGRAM = 15, 4
-
 
 def spec_plan(cfg, context, max_new, temperature=0.0, topp=0.9, u=TOPP_U_CPU, stop_token=None, n_draft=7, ngram=3, hint=None):
     """the checked arguments of Q8Engine.generate_spec: (context tokens, hint tokens, (temperature, topp, u, max_new, stop token,
