@@ -254,11 +254,18 @@ struct rama_ctx {
         ToppRow* rows = nullptr;           // [kMfMaxTok] every sequence's (T, topp, u, forced list)
         int* forced = nullptr; size_t forced_cap = 0;      // the forced lists, one after the other
     } bc;
+    // what the three Q8 chains below share, and all that drop_q8_graphs, rama_internal_drop_q8_graphs and the _steps entries need of one (q8_api.hip
+    // q8_chains, q8_chain_steps): the model it was begun on, whether it may still run, its one captured step.  The chains share procedures, not state.
+    struct Q8ChainBase {
+        bool live = false;                 // false once the model or a run state the chain still uses has been freed: its _steps entry refuses
+        rama_config cfg{}; rama_q8_weights w{};
+        CapturedGraph cg;                  // one step, for the chain's whole life: the tables' addresses, nothing of a sequence or a position
+        unsigned long long captures = 0;
+    };
     // rama_q8_decode_batch_begin / _steps: the same for a Q8 model, with per-sequence ends (a step budget, a stop token).  A state of
     // its own: the fp32 chain above neither sees nor shares any of it.
-    struct Q8Chain {
+    struct Q8Chain : Q8ChainBase {
         int n_seq = 0, max_steps = 0, out_cap = 0, steps_done = 0;      // out_cap: row stride of out / ring, >= every sequence's budget
-        bool live = false;                 // false once the model or a member's run state has been freed: rama_q8_decode_batch_steps refuses
         int* toks = nullptr;               // [kMfMaxTok] the token each sequence feeds next
         SeqSlot* seqs = nullptr;           // [kMfMaxTok] cache bases, position and tokens produced of every sequence
         int* out = nullptr;                // [kMfMaxTok, out_cap] the tokens produced
@@ -270,14 +277,11 @@ struct rama_ctx {
         bool sampled = false;              // a step ends in the batched top-p sampler (a row samples, or is forced) instead of argmax_batch_kernel
         ToppRow* rows = nullptr;           // [kMfMaxTok] every sequence's (T, topp, u, forced list)
         int* forced = nullptr; size_t forced_cap = 0;
-        rama_config cfg{}; rama_q8_weights w{};
         std::vector<rama_run_state> states;
-        CapturedGraph cg;                  // one step: nothing in its launch geometry depends on the positions
     } q8c;
     // rama_q8_serve_begin / _admit / _steps: the serving chain (q8_serve.hpp), a state of its own next to the chain above
-    struct Q8Serve {
+    struct Q8Serve : Q8ChainBase {
         int n_slots = 0, max_rows = 0, out_cap = 0;       // n_slots 0: no serving chain
-        bool live = false;                 // false once the model or an occupied slot's run state has been freed: rama_q8_serve_steps refuses
         bool sampler = false;              // a step runs the batched sampler's ordering launches (vocab_size <= 32768)
         ServeTables t{};                   // the device tables (ring / done: the device addresses of the two below)
         char* blob = nullptr;              // ... all of them, one allocation
@@ -286,12 +290,10 @@ struct rama_ctx {
         size_t rec_bytes = 0;
         int* ring = nullptr;               // [n_slots, out_cap] host-pinned and device-mapped: token + 1, 0 = not produced yet
         int* done = nullptr;               // [n_slots] host-pinned and device-mapped: 1 = the slot's occupant has finished
-        rama_config cfg{}; rama_q8_weights w{};
         std::vector<rama_run_state> states;   // per slot, the occupant's
         std::vector<char> occupied;        // per slot: admitted, and not yet seen DONE by a call that frees the slot
         std::vector<int> gen;
-        unsigned long long steps = 0, captures = 0;
-        CapturedGraph cg;                  // one step, for the chain's whole life: the tables' addresses, nothing of a sequence
+        unsigned long long steps = 0;
         // rama_q8_serve_begin_spec (q8_serve_spec.hpp): drafts in the rows no slot wants; all of it unused on a chain begun without it
         bool spec = false;
         int n_draft_cap = 0, hint_cap = 0;
@@ -301,18 +303,15 @@ struct rama_ctx {
         size_t srec_bytes = 0;
     } q8s;
     // rama_q8_spec_begin / _steps: the speculative chain (q8_spec.hpp), a third state next to the two above
-    struct Q8Spec {
+    struct Q8Spec : Q8ChainBase {
         bool active = false;               // false: no speculative chain
-        bool live = false;                 // false once the model or the run state has been freed: rama_q8_spec_steps refuses
         bool sampled = false;              // a step runs the batched sampler's ordering launches
         int n_rows = 0, out_cap = 0;       // n_draft + 1 rows per pass; max_new
         SpecTables t{};                    // the device tables (ring / count / done: the device addresses of the two below)
         char* blob = nullptr;              // ... all of them, one allocation
         int* ring = nullptr;               // [max_new] host-pinned and device-mapped: token + 1, 0 = not emitted yet
         int* words = nullptr;              // host-pinned and device-mapped: [0] tokens emitted, [1] 1 = the sequence has finished
-        rama_config cfg{}; rama_q8_weights w{}; rama_run_state state{};
-        unsigned long long captures = 0;
-        CapturedGraph cg;                  // one step, for the chain's whole life
+        rama_run_state state{};
     } q8p;
 };
 

@@ -2,6 +2,11 @@
 // batches (prefill, decode batch), the chained batch, the serving chain (with and without drafts) and the speculative chain.  The kernels are q8.hpp,
 // q8_batch.hpp, q8_serve.hpp, q8_fork.hpp, q8_spec.hpp and q8_serve_spec.hpp; parity mode's norms and attention and the samplers are reached through the launchers of ctx.hpp, which chain_api.hip
 // defines -- this translation unit instantiates none of their kernels (DESIGN.md "Translation units").
+// The three device-chained loops are states of their own (rama_ctx::Q8Chain / Q8Serve / Q8Spec over Q8ChainBase) that share PROCEDURES, each
+// written once here (DESIGN.md "Q8 chains: shared pass, layout, pick and lookup"): q8_chains (graph and lifetime handling), q8_product (a layer's five
+// products, for the forward and the batch), BlobCarver (a blob's tables), enqueue_q8_row_layers / enqueue_q8_batch_pass (a pass over a device row
+// table), enqueue_q8_pick_rows (what a sampled step does behind the classifier), q8_chain_scratch / q8_chain_steps (the begin and _steps
+// preambles, the step loop), q8_drain / q8_tokens_back (the _tokens and _stats entries) and the check_* refusals in the calling entry's words.
 #include "ctx.hpp"
 #include "q8.hpp"
 #include "q8_batch.hpp"
@@ -15,31 +20,34 @@
 #endif
 
 #include <algorithm>
+#include <array>
+#include <cstdio>
 #include <cstring>
 #include <vector>
 
+// the three device-chained loops, as what their graph and lifetime handling needs of them: the chained batch, the serving chain, the speculative chain
+static std::array<rama_ctx::Q8ChainBase*, 3> q8_chains(rama_ctx* c) { return {&c->q8c, &c->q8s, &c->q8p}; }
+
 // the captured Q8 steps: all of them (s == NULL) or those over one run state (drop_graph and rama_state_free of rama_api.hip call this too)
 void drop_q8_graphs(rama_ctx* c, const rama_run_state* s) {
-    // the chained batch's step: it goes with all Q8 graphs, and with a member's run state -- after which the chain is dead
-    bool member = false;
-    for (const auto& m : c->q8c.states) member = member || (s && m.key_cache == s->key_cache);
-    if (c->q8c.cg.exec && (!s || member)) { (void)hipStreamSynchronize(c->stream); destroy_graph(c->q8c.cg); }
-    if (member) c->q8c.live = false;
-    // the serving chain: its step goes with all Q8 graphs (the next rama_q8_serve_steps captures again); the run state of a slot whose
-    // occupant the host cannot yet see DONE ends the chain -- a finished occupant's is its owner's again
+    // a chain's step goes with all Q8 graphs (its next _steps call captures again), and with a run state the chain still uses -- after which the
+    // chain is dead.  Which run states those are is each chain's own: a member's, a live slot's, the one sequence's.
     auto& sv = c->q8s;
-    if (!s && sv.cg.exec) { (void)hipStreamSynchronize(c->stream); destroy_graph(sv.cg); }
+    bool uses[3] = {false, false, s && c->q8p.active && c->q8p.state.key_cache == s->key_cache};
+    for (const auto& m : c->q8c.states) uses[0] = uses[0] || (s && m.key_cache == s->key_cache);
+    // the serving chain's per-slot rule: the run state of a slot whose occupant the host cannot yet see DONE ends the chain -- a finished
+    // occupant's is its owner's again
     for (int i = 0; s && i < sv.n_slots; i++) {
         if (!sv.occupied[i] || sv.states[i].key_cache != s->key_cache) continue;
         if (__atomic_load_n(sv.done + i, __ATOMIC_ACQUIRE)) { sv.occupied[i] = 0; continue; }
-        (void)hipStreamSynchronize(c->stream);
-        sv.live = false;
+        uses[1] = true;
     }
-    // the speculative chain: its step goes with all Q8 graphs; its run state ends it
-    auto& sp = c->q8p;
-    const bool spec_state = s && sp.active && sp.state.key_cache == s->key_cache;
-    if (sp.cg.exec && (!s || spec_state)) { (void)hipStreamSynchronize(c->stream); destroy_graph(sp.cg); }
-    if (spec_state) sp.live = false;
+    const auto chains = q8_chains(c);
+    for (int k = 0; k < 3; k++) {
+        if (uses[k] || (!s && chains[k]->cg.exec)) (void)hipStreamSynchronize(c->stream);
+        if (uses[k] || !s) destroy_graph(chains[k]->cg);
+        if (uses[k]) chains[k]->live = false;
+    }
     bool any = false;
     for (auto& e : c->q8g) any = any || !s || !memcmp(&e.s, s, sizeof *s);
     if (!any) return;
@@ -51,13 +59,13 @@ void drop_q8_graphs(rama_ctx* c, const rama_run_state* s) {
         c->q8g.erase(c->q8g.begin() + (long)i);
     }
 }
-// q8_model.hip: a Q8 model (weights *freed) is about to go: the captured Q8 steps, and a chained batch over it is dead
+// q8_model.hip: a Q8 model (weights *freed) is about to go: the captured Q8 steps, and a chain over it is dead (one never begun, or ended, is
+// not live in the first place)
 extern "C" void rama_internal_drop_q8_graphs(rama_ctx* c, const rama_q8_weights* freed) {
     if (!c) return;
     drop_q8_graphs(c, nullptr);
-    if (freed && c->q8c.n_seq > 0 && c->q8c.w.wq == freed->wq) c->q8c.live = false;
-    if (freed && c->q8s.n_slots > 0 && c->q8s.w.wq == freed->wq) c->q8s.live = false;
-    if (freed && c->q8p.active && c->q8p.w.wq == freed->wq) c->q8p.live = false;
+    for (auto* ch : q8_chains(c))
+        if (freed && ch->w.wq == freed->wq) ch->live = false;
 }
 
 // the serving chain's allocations (rama_q8_serve_begin / _end, release_q8); the stream is idle
@@ -181,6 +189,52 @@ static int q8_check(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* 
     return 0;
 }
 
+// ---- The refusals several entries share, each in the calling entry's words: "<entry>: <what>" is the text that entry has always given.  An
+// entry calls them where its own REQUIREs of the same matter stood, so which error a bad call gets does not change.
+static int refuse(const char* entry, const char* what, int line) {
+    char msg[256];
+    snprintf(msg, sizeof msg, "%s: %s", entry, what);
+    return fail(RAMA_EINVAL, msg, __FILE__, line);
+}
+#define REFUSE_UNLESS(cond, entry, what) do { if (!(cond)) return refuse((entry), (what), __LINE__); } while (0)
+
+// every token of a list is in the vocabulary
+static int check_tokens(const char* entry, const char* what, const int32_t* toks, int n, int V) {
+    for (int i = 0; i < n; i++) REFUSE_UNLESS(toks[i] >= 0 && toks[i] < V, entry, what);
+    return 0;
+}
+// a sampling plan's two halves (rama_q8_decode_batch_begin has refusals of its own between them): Device::sample's (temperature, topp, u) ...
+static int check_sampler(const char* entry, float temperature, float topp, float u) {
+    REFUSE_UNLESS(topp_params_ok(temperature, topp, u), entry, "temperature >= 0, topp in [0,1], u in [0,1)");
+    return 0;
+}
+// ... and the stop token (-1: none) against the vocabulary
+static int check_stop_token(const char* entry, int stop_token, int V) {
+    REFUSE_UNLESS(stop_token >= -1 && stop_token < V, entry, "stop token outside the vocabulary");
+    return 0;
+}
+// the drafting fields of a plan (rama_q8_serve_spec, rama_q8_spec_plan): n_draft and the hint's length against the caller's caps -- those two
+// refusals name the cap in the caller's words --, ngram, the hint's tokens against the vocabulary
+template <class Plan>
+static int check_drafting(const char* entry, const Plan& p, int n_draft_cap, const char* n_draft_what, int n_hint_cap, const char* hint_what, int V) {
+    REFUSE_UNLESS(p.n_draft >= 0 && p.n_draft <= n_draft_cap, entry, n_draft_what);
+    REFUSE_UNLESS(p.ngram >= 1 && p.ngram <= kSpecMaxNgram, entry, "ngram outside 1..4");
+    REFUSE_UNLESS(p.n_hint >= 0 && (p.n_hint == 0 || p.hint) && p.n_hint <= n_hint_cap, entry, hint_what);
+    return check_tokens(entry, "hint token outside the vocabulary", p.hint, p.n_hint, V);
+}
+// the serving chain's geometry, and a slot of a slot table handed to one of the two plan functions
+static int check_slots_rows(const char* entry, int n_slots, int max_rows) {
+    REFUSE_UNLESS(n_slots >= 1 && n_slots <= kServeMaxSlots && max_rows >= n_slots && max_rows <= kQ8bMaxTok, entry, "1 <= n_slots <= max_rows <= 128");
+    return 0;
+}
+static int check_plan_slot(const char* entry, const rama_q8_serve_slot& s) {
+    REFUSE_UNLESS(s.state >= RAMA_SERVE_FREE && s.state <= RAMA_SERVE_DONE, entry, "bad slot state");
+    if (s.state == RAMA_SERVE_PROMPT) REFUSE_UNLESS(s.n_context >= 1 && s.cursor >= 0 && s.cursor < s.n_context && s.max_new >= 1, entry, "bad PROMPT slot");
+    if (s.state == RAMA_SERVE_DECODE) REFUSE_UNLESS(s.cursor >= 0 && s.n_out >= 1 && s.n_out < s.max_new, entry, "bad DECODE slot");
+    return 0;
+}
+#define CHECKED(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
+
 // the int8 activations: one buffer of max(dim, hidden) values and as many scales (sized here, never inside a capture)
 static int ensure_q8_scratch(rama_ctx* c, const rama_config* cfg) {
     const size_t need = (size_t)std::max(cfg->dim, cfg->hidden_dim);
@@ -217,10 +271,31 @@ static int q8_norm(rama_ctx* c, float* o, float* x, const float* gain, int n, fl
     return launch_rmsnorm_ref(c, o, x, gain, n);
 }
 
+// The products of a model, stated once for the forward (P = Q8MatParams) and the token batch (Q8BatchParams): layer l's Wq|Wk|Wv, Wo, W1|W3 and
+// W2, and the classifier (l ignored) -- the matrices and their scales, K, rows and nmat over the activations xq / xs, into o0 (.. o2).
+enum Q8Product { Q8P_QKV, Q8P_WO, Q8P_W13, Q8P_W2, Q8P_CLS };
+template <class P>
+static P q8_product(const rama_config* cfg, const rama_q8_weights* w, int l, Q8Product kind, const int8_t* xq, const float* xs, float* o0, float* o1 = nullptr,
+                    float* o2 = nullptr) {
+    const int dim = cfg->dim, hidden = cfg->hidden_dim, gs = w->group_size;
+    const size_t dd = (size_t)l * dim * dim, hd = (size_t)l * hidden * dim;      // layer l's offset in the square matrices and in the FFN's
+    P p{};
+    p.xq = xq; p.xs = xs; p.gs = gs; p.K = dim; p.rows = dim; p.nmat = 1;
+    p.o[0] = o0; p.o[1] = o1; p.o[2] = o2;
+    auto mat = [&](int m, const int8_t* q, const float* s, size_t off) { p.w[m] = q + off; p.ws[m] = s + off / gs; };
+    switch (kind) {
+    case Q8P_QKV: mat(0, w->wq, w->wq_s, dd); mat(1, w->wk, w->wk_s, dd); mat(2, w->wv, w->wv_s, dd); p.nmat = 3; break;
+    case Q8P_WO:  mat(0, w->wo, w->wo_s, dd); break;
+    case Q8P_W13: mat(0, w->w1, w->w1_s, hd); mat(1, w->w3, w->w3_s, hd); p.rows = hidden; p.nmat = 2; break;
+    case Q8P_W2:  mat(0, w->w2, w->w2_s, hd); p.K = hidden; break;
+    case Q8P_CLS: mat(0, w->wcls, w->wcls_s, 0); p.rows = cfg->vocab_size; break;
+    }
+    return p;
+}
+
 // one forward (token and position in the device cursor); embed = 0: x already holds the token's embedding (chained decode)
 static int enqueue_q8_stage(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, rama_run_state* s, bool embed) {
     const int dim = cfg->dim, hidden = cfg->hidden_dim, hs = dim / cfg->n_heads, gs = w->group_size;
-    const size_t dd = (size_t)dim * dim, hd = (size_t)hidden * dim;
     int8_t* xq = c->q8_xq; float* xs = c->q8_xs;
     int rc;
     if (embed) {
@@ -234,11 +309,7 @@ static int enqueue_q8_stage(rama_ctx* c, const rama_config* cfg, const rama_q8_w
         rc = launch_q8_quantize(c, s->xb, dim, gs, xq, xs); if (rc) return rc;
         {   // :20-23
             KTimer kt(c, RAMA_K_QKV);
-            Q8MatParams p{};
-            p.w[0] = w->wq + l * dd; p.w[1] = w->wk + l * dd; p.w[2] = w->wv + l * dd;
-            p.ws[0] = w->wq_s + l * dd / gs; p.ws[1] = w->wk_s + l * dd / gs; p.ws[2] = w->wv_s + l * dd / gs;
-            p.o[0] = s->q; p.o[1] = s->k; p.o[2] = s->v;
-            p.xq = xq; p.xs = xs; p.K = dim; p.rows = dim; p.gs = gs; p.nmat = 3;
+            Q8MatParams p = q8_product<Q8MatParams>(cfg, w, l, Q8P_QKV, xq, xs, s->q, s->k, s->v);
             rc = launch_q8_matvec<Q8EPI_STORE>(c, p); if (rc) return rc;
         }
         hipLaunchKernelGGL(rope_ref_cursor_kernel, dim3((dim / 2 + 255) / 256), dim3(256), 0, c->stream, s->q, s->k, (const float*)s->v,
@@ -254,26 +325,20 @@ static int enqueue_q8_stage(rama_ctx* c, const rama_config* cfg, const rama_q8_w
         rc = launch_q8_quantize(c, s->xb, dim, gs, xq, xs); if (rc) return rc;
         {   // :35-37: x = x + Wo . xb
             KTimer kt(c, RAMA_K_WO);
-            Q8MatParams p{};
-            p.w[0] = w->wo + l * dd; p.ws[0] = w->wo_s + l * dd / gs; p.o[0] = s->x;
-            p.xq = xq; p.xs = xs; p.K = dim; p.rows = dim; p.gs = gs; p.nmat = 1;
+            Q8MatParams p = q8_product<Q8MatParams>(cfg, w, l, Q8P_WO, xq, xs, s->x);
             rc = launch_q8_matvec<Q8EPI_RESID>(c, p); if (rc) return rc;
         }
         rc = q8_norm(c, s->xb, s->x, w->rms_ffn_weight + (size_t)l * dim, dim, nullptr); if (rc) return rc;          // :39
         rc = launch_q8_quantize(c, s->xb, dim, gs, xq, xs); if (rc) return rc;
         {   // :41-45: hb = sinu(W1 . xb) * (W3 . xb)
             KTimer kt(c, RAMA_K_W13);
-            Q8MatParams p{};
-            p.w[0] = w->w1 + l * hd; p.w[1] = w->w3 + l * hd; p.ws[0] = w->w1_s + l * hd / gs; p.ws[1] = w->w3_s + l * hd / gs;
-            p.o[0] = s->hb; p.xq = xq; p.xs = xs; p.K = dim; p.rows = hidden; p.gs = gs; p.nmat = 2;
+            Q8MatParams p = q8_product<Q8MatParams>(cfg, w, l, Q8P_W13, xq, xs, s->hb);
             rc = launch_q8_matvec<Q8EPI_SWIGLU>(c, p); if (rc) return rc;
         }
         rc = launch_q8_quantize(c, s->hb, hidden, gs, xq, xs); if (rc) return rc;
         {   // :46-47: x = x + W2 . hb
             KTimer kt(c, RAMA_K_W2);
-            Q8MatParams p{};
-            p.w[0] = w->w2 + l * hd; p.ws[0] = w->w2_s + l * hd / gs; p.o[0] = s->x;
-            p.xq = xq; p.xs = xs; p.K = hidden; p.rows = dim; p.gs = gs; p.nmat = 1;
+            Q8MatParams p = q8_product<Q8MatParams>(cfg, w, l, Q8P_W2, xq, xs, s->x);
             rc = launch_q8_matvec<Q8EPI_RESID>(c, p); if (rc) return rc;
         }
     }
@@ -281,9 +346,7 @@ static int enqueue_q8_stage(rama_ctx* c, const rama_config* cfg, const rama_q8_w
     rc = q8_norm(c, s->x, s->x, w->rms_final_weight, dim, s->xb); if (rc) return rc;
     rc = launch_q8_quantize(c, s->x, dim, gs, xq, xs); if (rc) return rc;
     KTimer kt(c, RAMA_K_CLS);
-    Q8MatParams p{};
-    p.w[0] = w->wcls; p.ws[0] = w->wcls_s; p.o[0] = s->logits;
-    p.xq = xq; p.xs = xs; p.K = dim; p.rows = cfg->vocab_size; p.gs = gs; p.nmat = 1;
+    Q8MatParams p = q8_product<Q8MatParams>(cfg, w, 0, Q8P_CLS, xq, xs, s->logits);
     return launch_q8_matvec<Q8EPI_STORE>(c, p);
 }
 
@@ -344,7 +407,7 @@ int rama_q8_generate(rama_ctx* c, const rama_config* cfg, const rama_q8_weights*
     rc = rama_decode_sampler(c, temperature, topp, u); if (rc) return rc;
     REQUIRE(steps >= 0 && steps <= cfg->seq_len && steps <= c->out_cap, RAMA_EINVAL, "q8_generate: steps outside [0, seq_len]");
     REQUIRE(n_prompt >= 0 && (n_prompt == 0 || prompt_host) && n_prompt <= c->forced_cap, RAMA_EINVAL, "q8_generate: bad prompt");
-    for (int i = 0; i < n_prompt; i++) REQUIRE(prompt_host[i] >= 0 && prompt_host[i] < cfg->vocab_size, RAMA_EINVAL, "q8_generate: prompt token outside the vocabulary");
+    CHECKED(check_tokens("q8_generate", "prompt token outside the vocabulary", prompt_host, n_prompt, cfg->vocab_size));
     rc = ensure_q8_scratch(c, cfg); if (rc) return rc;
     if (c->samp_T != 0.0f) { rc = ensure_topp_scratch(c, cfg->vocab_size); if (rc) return rc; c->topp_dist_dirty = true; }
     rc = rama_decode_begin(c, /*BOS*/ 1, 0, prompt_host, n_prompt); if (rc) return rc;
@@ -437,34 +500,39 @@ int rama_q8_batch_shape_ok(const rama_config* cfg) {
     return q8_batch_ok(cfg) ? 1 : 0;
 }
 
+// The tables of one allocation in order, each rounded up to 256 bytes.  The same code lays a blob out twice: over no base for its size
+// (`used`), then over the allocation for the typed pointers.
+struct BlobCarver {
+    char* base = nullptr;
+    size_t used = 0;
+    template <class T> void take(T*& table, size_t count) {
+        table = base ? reinterpret_cast<T*>(base + used) : nullptr;
+        used += (count * sizeof(T) + 255) / 256 * 256;
+    }
+};
+
 static int ensure_q8_batch_scratch(rama_ctx* c, const rama_config* cfg, int gs, Q8BatchScratch* b) {
     const size_t T = kQ8bMaxTok, dim = (size_t)cfg->dim, hidden = (size_t)cfg->hidden_dim, mx = std::max(dim, hidden);
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-    const size_t sz[13] = {T * dim * 4, T * dim * 4, T * dim * 4, T * dim * 4, T * dim * 4, T * dim * 4, T * hidden * 4,
-                           T * (size_t)cfg->n_heads * cfg->seq_len * 4, T * (size_t)cfg->vocab_size * 4, T * mx, T * (mx / gs) * 4, T * sizeof(int),
-                           T * sizeof(SeqSlot)};
-    size_t off[13], need = 0;
-    for (int i = 0; i < 13; i++) { off[i] = need; need += up(sz[i]); }
+    auto lay = [&](char* base) {
+        BlobCarver bc{base};
+        for (float** f : {&b->X, &b->XN, &b->Q, &b->Kr, &b->V, &b->XB}) bc.take(*f, T * dim);
+        bc.take(b->HB, T * hidden); bc.take(b->ATT, T * (size_t)cfg->n_heads * cfg->seq_len); bc.take(b->LG, T * (size_t)cfg->vocab_size);
+        bc.take(b->xq, T * mx); bc.take(b->xs, T * (mx / gs)); bc.take(b->toks, T); bc.take(b->seqs, T);
+        return bc.used;
+    };
+    const size_t need = lay(nullptr);
     if (need > c->q8b_cap) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         REQUIRE(hipStreamIsCapturing(c->stream, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone, RAMA_EINVAL,
                 "q8 batch: the scratch is sized by the first call, which must not be captured");
         HIPCHK(hipStreamSynchronize(c->stream));
-        destroy_graph(c->q8c.cg);          // (the chained batch's step holds the old scratch's addresses)
-        destroy_graph(c->q8s.cg);          // (and the serving chain's)
-        destroy_graph(c->q8p.cg);          // (and the speculative chain's)
+        for (auto* ch : q8_chains(c)) destroy_graph(ch->cg);      // (every chain's step holds the old scratch's addresses)
         if (c->q8b_blob) { HIPCHK(hipFree(c->q8b_blob)); c->q8b_blob = nullptr; }
         c->q8b_cap = 0;
         HIPCHK(hipMalloc(&c->q8b_blob, need));
         c->q8b_cap = need;
     }
-    char* base = c->q8b_blob;
-    float** f[9] = {&b->X, &b->XN, &b->Q, &b->Kr, &b->V, &b->XB, &b->HB, &b->ATT, &b->LG};
-    for (int i = 0; i < 9; i++) *f[i] = reinterpret_cast<float*>(base + off[i]);
-    b->xq = reinterpret_cast<int8_t*>(base + off[9]);
-    b->xs = reinterpret_cast<float*>(base + off[10]);
-    b->toks = reinterpret_cast<int*>(base + off[11]);
-    b->seqs = reinterpret_cast<SeqSlot*>(base + off[12]);
+    lay(c->q8b_blob);
     const int hs = cfg->dim / cfg->n_heads;
     b->nw = attn_chain_waves(hs, false);
     b->att_lds = attn_chain_lds_bytes(hs, cfg->seq_len, b->nw);
@@ -476,22 +544,20 @@ static int ensure_q8_batch_scratch(rama_ctx* c, const rama_config* cfg, int gs, 
 static int q8_batch_layers(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const Q8BatchScratch& b, int nt, int p0,
                            float* key_cache, float* value_cache, const SeqSlot* seqs) {
     const int dim = cfg->dim, hidden = cfg->hidden_dim, hs = dim / cfg->n_heads, H = cfg->n_heads, seq = cfg->seq_len, gs = w->group_size;
-    const size_t dd = (size_t)dim * dim, hd = (size_t)hidden * dim;
     int rc;
     for (int l = 0; l < cfg->n_layers; l++) {
+        // a product of this layer over the nt rows of b.xq, into rows `ostride` floats apart
+        auto product = [&](Q8Product kind, int ostride, float* o0, float* o1 = nullptr, float* o2 = nullptr) {
+            Q8BatchParams p = q8_product<Q8BatchParams>(cfg, w, l, kind, b.xq, b.xs, o0, o1, o2);
+            p.n_tok = nt; p.ostride = ostride;
+            return p;
+        };
         const size_t layer_off = (size_t)l * seq * dim;
         float* kc = key_cache ? key_cache + layer_off : nullptr;
         float* vc = value_cache ? value_cache + layer_off : nullptr;
         rc = launch_rmsnorm_chain(c, b.XN, b.X, w->rms_att_weight + (size_t)l * dim, dim, nullptr, nt, dim); if (rc) return rc;    // infer.rs:19
         rc = launch_q8_quantize(c, b.XN, nt * dim, gs, b.xq, b.xs); if (rc) return rc;
-        {   // :20-23
-            Q8BatchParams p{};
-            p.w[0] = w->wq + l * dd; p.w[1] = w->wk + l * dd; p.w[2] = w->wv + l * dd;
-            p.ws[0] = w->wq_s + l * dd / gs; p.ws[1] = w->wk_s + l * dd / gs; p.ws[2] = w->wv_s + l * dd / gs;
-            p.o[0] = b.Q; p.o[1] = b.Kr; p.o[2] = b.V;
-            p.xq = b.xq; p.xs = b.xs; p.K = dim; p.rows = dim; p.gs = gs; p.nmat = 3; p.n_tok = nt; p.ostride = dim;
-            rc = launch_q8_gemm<Q8EPI_STORE>(c, p); if (rc) return rc;
-        }
+        rc = launch_q8_gemm<Q8EPI_STORE>(c, product(Q8P_QKV, dim, b.Q, b.Kr, b.V)); if (rc) return rc;                             // :20-23
         hipLaunchKernelGGL(q8_rope_batch_kernel, dim3((dim / 2 + 255) / 256, nt), dim3(256), 0, c->stream, b.Q, b.Kr, (const float*)b.V,
                            w->freq_cis_real, w->freq_cis_imag, dim, hs, kc, vc, p0, seqs, layer_off);                    // :25-33
         LAUNCHCHK();
@@ -503,27 +569,12 @@ static int q8_batch_layers(rama_ctx* c, const rama_config* cfg, const rama_q8_we
             rc = launch_attention_chain_tokens(c, a, H, nt, b.nw, b.att_lds); if (rc) return rc;
         }
         rc = launch_q8_quantize(c, b.XB, nt * dim, gs, b.xq, b.xs); if (rc) return rc;
-        {   // :35-37: x = x + Wo . xb
-            Q8BatchParams p{};
-            p.w[0] = w->wo + l * dd; p.ws[0] = w->wo_s + l * dd / gs; p.o[0] = b.X;
-            p.xq = b.xq; p.xs = b.xs; p.K = dim; p.rows = dim; p.gs = gs; p.nmat = 1; p.n_tok = nt; p.ostride = dim;
-            rc = launch_q8_gemm<Q8EPI_RESID>(c, p); if (rc) return rc;
-        }
+        rc = launch_q8_gemm<Q8EPI_RESID>(c, product(Q8P_WO, dim, b.X)); if (rc) return rc;                // :35-37: x = x + Wo . xb
         rc = launch_rmsnorm_chain(c, b.XN, b.X, w->rms_ffn_weight + (size_t)l * dim, dim, nullptr, nt, dim); if (rc) return rc;    // :39
         rc = launch_q8_quantize(c, b.XN, nt * dim, gs, b.xq, b.xs); if (rc) return rc;
-        {   // :41-45: hb = sinu(W1 . xb) * (W3 . xb)
-            Q8BatchParams p{};
-            p.w[0] = w->w1 + l * hd; p.w[1] = w->w3 + l * hd; p.ws[0] = w->w1_s + l * hd / gs; p.ws[1] = w->w3_s + l * hd / gs;
-            p.o[0] = b.HB; p.xq = b.xq; p.xs = b.xs; p.K = dim; p.rows = hidden; p.gs = gs; p.nmat = 2; p.n_tok = nt; p.ostride = hidden;
-            rc = launch_q8_gemm<Q8EPI_SWIGLU>(c, p); if (rc) return rc;
-        }
+        rc = launch_q8_gemm<Q8EPI_SWIGLU>(c, product(Q8P_W13, hidden, b.HB)); if (rc) return rc;          // :41-45: hb = sinu(W1 . xb) * (W3 . xb)
         rc = launch_q8_quantize(c, b.HB, nt * hidden, gs, b.xq, b.xs); if (rc) return rc;
-        {   // :46-47: x = x + W2 . hb
-            Q8BatchParams p{};
-            p.w[0] = w->w2 + l * hd; p.ws[0] = w->w2_s + l * hd / gs; p.o[0] = b.X;
-            p.xq = b.xq; p.xs = b.xs; p.K = hidden; p.rows = dim; p.gs = gs; p.nmat = 1; p.n_tok = nt; p.ostride = dim;
-            rc = launch_q8_gemm<Q8EPI_RESID>(c, p); if (rc) return rc;
-        }
+        rc = launch_q8_gemm<Q8EPI_RESID>(c, product(Q8P_W2, dim, b.X)); if (rc) return rc;                // :46-47: x = x + W2 . hb
     }
     return 0;
 }
@@ -533,7 +584,7 @@ int rama_q8_prefill(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* 
     REQUIRE(c && tokens_host, RAMA_EINVAL, "q8_prefill: NULL argument");
     int rc = q8_check(c, cfg, w, s); if (rc) return rc;
     REQUIRE(n_tokens >= 1 && pos0 >= 0 && pos0 <= cfg->seq_len - n_tokens, RAMA_EINVAL, "q8_prefill: positions outside [0, seq_len)");
-    for (int i = 0; i < n_tokens; i++) REQUIRE(tokens_host[i] >= 0 && tokens_host[i] < cfg->vocab_size, RAMA_EINVAL, "q8_prefill: token outside the vocabulary");
+    CHECKED(check_tokens("q8_prefill", "token outside the vocabulary", tokens_host, n_tokens, cfg->vocab_size));
     if (set_device(c)) return 1;
     rc = ensure_q8_scratch(c, cfg); if (rc) return rc;
     // the last position runs as rama_q8_forward (x and logits); a batched pass of one token costs more than a forward (4.7 against
@@ -559,23 +610,38 @@ int rama_q8_prefill(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* 
 // infer.rs:49-51 for n_rows rows of src_rows [n_rows, dim]: x = rmsnorm(x), logits = Wcls . x -- the batched final norm, the quantizer
 // and the classifier as one more product into b.LG [n_rows, vocab]
 static int enqueue_q8_classifier(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const Q8BatchScratch& b, const float* src_rows, int n_rows) {
-    const int dim = cfg->dim, V = cfg->vocab_size, gs = w->group_size;
+    const int dim = cfg->dim, V = cfg->vocab_size;
     int rc = launch_rmsnorm_chain(c, b.XN, src_rows, w->rms_final_weight, dim, nullptr, n_rows, dim); if (rc) return rc;
-    rc = launch_q8_quantize(c, b.XN, n_rows * dim, gs, b.xq, b.xs); if (rc) return rc;
-    Q8BatchParams p{};
-    p.w[0] = w->wcls; p.ws[0] = w->wcls_s; p.o[0] = b.LG;
-    p.xq = b.xq; p.xs = b.xs; p.K = dim; p.rows = V; p.gs = gs; p.nmat = 1; p.n_tok = n_rows; p.ostride = V;
+    rc = launch_q8_quantize(c, b.XN, n_rows * dim, w->group_size, b.xq, b.xs); if (rc) return rc;
+    Q8BatchParams p = q8_product<Q8BatchParams>(cfg, w, 0, Q8P_CLS, b.xq, b.xs, b.LG);
+    p.n_tok = n_rows; p.ostride = V;
     return launch_q8_gemm<Q8EPI_STORE>(c, p);
 }
 
-// One pass for the n_seq sequences of the device tables toks / seqs: embedding rows, every layer, then the classifier tail
-static int enqueue_q8_batch_pass(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const Q8BatchScratch& b, const int* toks,
-                                 const SeqSlot* seqs, int n_seq) {
+// A pass over a device row table: the embedding rows of row_tok and every layer over `rows` (n_rows of them; an idle row has position -1) ...
+static int enqueue_q8_row_layers(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const Q8BatchScratch& b, const int* row_tok,
+                                 const SeqSlot* rows, int n_rows) {
     const int dim = cfg->dim;
-    hipLaunchKernelGGL(embed_rows_kernel, dim3((dim + 255) / 256, n_seq), dim3(256), 0, c->stream, b.X, w->token_embedding_table, toks, n_seq, dim);
+    hipLaunchKernelGGL(embed_rows_kernel, dim3((dim + 255) / 256, n_rows), dim3(256), 0, c->stream, b.X, w->token_embedding_table, row_tok, n_rows, dim);
     LAUNCHCHK();
-    const int rc = q8_batch_layers(c, cfg, w, b, n_seq, 0, nullptr, nullptr, seqs); if (rc) return rc;
-    return enqueue_q8_classifier(c, cfg, w, b, b.X, n_seq);
+    return q8_batch_layers(c, cfg, w, b, n_rows, 0, nullptr, nullptr, rows);
+}
+// ... and the classifier tail over every row: rama_q8_decode_batch's pass, and that of every chain's step but the serving chain's without
+// drafts, which classifies the rows it has gathered
+static int enqueue_q8_batch_pass(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const Q8BatchScratch& b, const int* row_tok,
+                                 const SeqSlot* rows, int n_rows) {
+    const int rc = enqueue_q8_row_layers(c, cfg, w, b, row_tok, rows, n_rows); if (rc) return rc;
+    return enqueue_q8_classifier(c, cfg, w, b, b.X, n_rows);
+}
+
+// What every sampled chain's step does behind the classifier: the pick kernel's rows are b.LG's, and -- `sampled` -- the batched sampler's
+// ordering launches over the rows' sampler records leave their slices in the context's scratch
+static int enqueue_q8_pick_rows(rama_ctx* c, const Q8BatchScratch& b, int V, bool sampled, const ToppRow* trow, int n_rows, PickRows* r) {
+    *r = PickRows{b.LG, (size_t)V, V, nullptr, nullptr, nullptr, 0};
+    if (!sampled) return 0;
+    const int rc = enqueue_topp_batch_order(c, trow, n_rows, b.LG, (size_t)V, V, nullptr); if (rc) return rc;
+    r->keys = c->tb.keys; r->vals = c->tb.vals; r->m = c->tb.m; r->rstride = c->tb.rstride;
+    return 0;
 }
 
 int rama_q8_decode_batch(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const rama_run_state* states,
@@ -614,6 +680,38 @@ int rama_q8_decode_batch(rama_ctx* c, const rama_config* cfg, const rama_q8_weig
 // which rewrites one cache row with the same bits, so the pass needs no mask and one captured graph serves the whole chain: nothing in
 // the pass's launch geometry depends on the positions (score rows and attention LDS are sized by seq_len).
 
+// What a chain's step runs on: both scratches and -- sampler_rows > 0 -- the batched sampler's slices for so many rows.  A chain's begin sizes
+// them here, outside any capture; at its _steps entry neither grows: whoever grew them since for another shape dropped the step's graph.
+static int q8_chain_scratch(rama_ctx* c, const rama_config* cfg, int group_size, int sampler_rows, Q8BatchScratch* b) {
+    int rc = ensure_q8_scratch(c, cfg); if (rc) return rc;
+    rc = ensure_q8_batch_scratch(c, cfg, group_size, b); if (rc) return rc;
+    return sampler_rows > 0 ? ensure_topp_batch(c, sampler_rows, cfg->vocab_size) : 0;
+}
+
+// What every _steps entry does behind its own checks: the scratch, then n_steps times `step(b)` -- eager, or (graph mode, no kernel class being
+// timed) captured into the chain's graph on first use and replayed.  *n_done: the steps enqueued, also when one fails.
+template <class Step>
+static int q8_chain_steps(rama_ctx* c, rama_ctx::Q8ChainBase& ch, int sampler_rows, int n_steps, Step&& step, int* n_done) {
+    *n_done = 0;
+    Q8BatchScratch b{};
+    int rc = q8_chain_scratch(c, &ch.cfg, ch.w.group_size, sampler_rows, &b); if (rc) return rc;
+    c->embedded_x = nullptr; c->host_pos = -1;
+    auto enqueue = [&] { return step(b); };
+    const bool graphs = c->graph_mode && c->kp.kernel_id < 0;
+    for (; *n_done < n_steps; ++*n_done) {
+        if (!graphs) {
+            rc = enqueue(); if (rc) return rc;
+            continue;
+        }
+        if (!ch.cg.exec) {
+            rc = capture_graph(c, ch.cg, enqueue); if (rc) return rc;
+            ch.captures++;
+        }
+        rc = replay_graph(c, ch.cg); if (rc) return rc;
+    }
+    return 0;
+}
+
 // a sequence's budget: its own max_new (0: none) within the chain's max_steps
 static int q8_chain_limit(const rama_q8_seq_plan* per_seq, int i, int max_steps) {
     return per_seq && per_seq[i].max_new > 0 ? std::min(per_seq[i].max_new, max_steps) : max_steps;
@@ -638,12 +736,11 @@ int rama_q8_decode_batch_begin(rama_ctx* c, const rama_config* cfg, const rama_q
                     "q8_decode_batch_begin: two sequences share a run state");
         if (per_seq) {
             const rama_q8_seq_plan& q = per_seq[i];
-            REQUIRE(topp_params_ok(q.temperature, q.topp, q.u), RAMA_EINVAL, "q8_decode_batch_begin: temperature >= 0, topp in [0,1], u in [0,1)");
+            CHECKED(check_sampler("q8_decode_batch_begin", q.temperature, q.topp, q.u));
             REQUIRE(q.n_forced >= 0 && (q.n_forced == 0 || q.forced), RAMA_EINVAL, "q8_decode_batch_begin: bad forced list");
-            for (int k = 0; k < q.n_forced; k++)
-                REQUIRE(q.forced[k] >= 0 && q.forced[k] < cfg->vocab_size, RAMA_EINVAL, "q8_decode_batch_begin: forced token outside the vocabulary");
+            CHECKED(check_tokens("q8_decode_batch_begin", "forced token outside the vocabulary", q.forced, q.n_forced, cfg->vocab_size));
             REQUIRE(q.max_new >= 0, RAMA_EINVAL, "q8_decode_batch_begin: max_new < 0");
-            REQUIRE(q.stop_token >= -1 && q.stop_token < cfg->vocab_size, RAMA_EINVAL, "q8_decode_batch_begin: stop token outside the vocabulary");
+            CHECKED(check_stop_token("q8_decode_batch_begin", q.stop_token, cfg->vocab_size));
             sampled = sampled || q.temperature != 0.0f || q.n_forced > 0;
             n_forced_all += (size_t)q.n_forced;
         }
@@ -662,11 +759,9 @@ int rama_q8_decode_batch_begin(rama_ctx* c, const rama_config* cfg, const rama_q
     auto& qc = c->q8c;
     destroy_graph(qc.cg);
     qc.n_seq = 0; qc.live = false; qc.states.clear();
-    // both scratches, the sampler's slices and the chain's tables: sized here, outside any capture
-    int rc = ensure_q8_scratch(c, cfg); if (rc) return rc;
+    // the scratch and the chain's tables: sized here, outside any capture
     Q8BatchScratch b{};
-    rc = ensure_q8_batch_scratch(c, cfg, w->group_size, &b); if (rc) return rc;
-    if (use_sampler) { rc = ensure_topp_batch(c, n_seq, cfg->vocab_size); if (rc) return rc; }
+    int rc = q8_chain_scratch(c, cfg, w->group_size, use_sampler ? n_seq : 0, &b); if (rc) return rc;
     if (!qc.toks) {
         HIPCHK(hipMalloc(&qc.toks, sizeof(int) * kQ8bMaxTok)); HIPCHK(hipMalloc(&qc.seqs, sizeof(SeqSlot) * kQ8bMaxTok));
         HIPCHK(hipMalloc(&qc.ends, sizeof(BatchEnds)));
@@ -713,25 +808,6 @@ int rama_q8_decode_batch_begin(rama_ctx* c, const rama_config* cfg, const rama_q
     return 0;
 }
 
-// n_steps times `enqueue`: eager, or -- graph mode, no kernel class being timed -- captured into g on first use and replayed.  *n_done: the
-// steps enqueued, also when one fails; *captures (if given) counts the captures.
-template <class Enqueue>
-static int q8_run_steps(rama_ctx* c, CapturedGraph& g, int n_steps, Enqueue&& enqueue, int* n_done, unsigned long long* captures = nullptr) {
-    const bool graphs = c->graph_mode && c->kp.kernel_id < 0;
-    for (*n_done = 0; *n_done < n_steps; ++*n_done) {
-        if (!graphs) {
-            const int rc = enqueue(); if (rc) return rc;
-            continue;
-        }
-        if (!g.exec) {
-            const int rc = capture_graph(c, g, enqueue); if (rc) return rc;
-            if (captures) ++*captures;
-        }
-        const int rc = replay_graph(c, g); if (rc) return rc;
-    }
-    return 0;
-}
-
 // one step: the pass over the chain's own tables, then what ends it
 static int enqueue_q8_chain_step(rama_ctx* c, const Q8BatchScratch& b) {
     auto& qc = c->q8c;
@@ -756,31 +832,35 @@ int rama_q8_decode_batch_steps(rama_ctx* c, int n_steps) {
     REQUIRE(qc.live, RAMA_EINVAL, "q8_decode_batch_steps: the chain's model or one of its run states has been freed");
     REQUIRE(n_steps >= 0 && n_steps <= qc.max_steps - qc.steps_done, RAMA_EINVAL, "q8_decode_batch_steps: more steps than rama_q8_decode_batch_begin allowed for");
     if (set_device(c)) return 1;
-    // (neither grows here: rama_q8_decode_batch_begin sized them, and whoever grew them since for another shape dropped the step's graph)
-    int rc = ensure_q8_scratch(c, &qc.cfg); if (rc) return rc;
-    Q8BatchScratch b{};
-    rc = ensure_q8_batch_scratch(c, &qc.cfg, qc.w.group_size, &b); if (rc) return rc;
-    if (qc.sampled) { rc = ensure_topp_batch(c, qc.n_seq, qc.cfg.vocab_size); if (rc) return rc; }
-    c->embedded_x = nullptr; c->host_pos = -1;
     int n_done = 0;
-    rc = q8_run_steps(c, qc.cg, n_steps, [&] { return enqueue_q8_chain_step(c, b); }, &n_done);
+    const int rc = q8_chain_steps(c, qc, qc.sampled ? qc.n_seq : 0, n_steps, [&](const Q8BatchScratch& b) { return enqueue_q8_chain_step(c, b); }, &n_done);
     qc.steps_done += n_done;
     return rc;
+}
+
+// What the _tokens and _stats entries of the chains open with: the stream drained, the hand-off words read
+static int q8_drain(rama_ctx* c) {
+    if (set_device(c)) return 1;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return handoff_check(c);
+}
+// ... and what a _tokens entry ends with: the first min(produced, cap, max_tokens) tokens of a device row, and their number
+static int q8_tokens_back(int32_t* out_host, const int* row_dev, int produced, int cap, int max_tokens, int* n) {
+    *n = std::min(std::min(produced, cap), max_tokens);
+    if (*n > 0) HIPCHK(hipMemcpy(out_host, row_dev, sizeof(int) * *n, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 int rama_q8_decode_batch_tokens(rama_ctx* c, int32_t* out_host, int max_per_seq, int32_t* n_per_seq) {
     RAMA_ENTER(c);
     REQUIRE(c && out_host && n_per_seq && c->q8c.n_seq > 0 && max_per_seq >= 0, RAMA_EINVAL, "q8_decode_batch_tokens: bad argument");
     auto& qc = c->q8c;
-    if (set_device(c)) return 1;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    { const int rh = handoff_check(c); if (rh) return rh; }
+    int rc = q8_drain(c); if (rc) return rc;
     SeqSlot slots[kQ8bMaxTok];
     HIPCHK(hipMemcpy(slots, qc.seqs, sizeof(SeqSlot) * qc.n_seq, hipMemcpyDeviceToHost));
-    for (int s_ = 0; s_ < qc.n_seq; s_++) {
-        const int n = std::min(std::min(slots[s_].pad, qc.out_cap), max_per_seq);      // pad: the tokens the sequence has produced
-        if (n > 0) HIPCHK(hipMemcpy(out_host + (size_t)s_ * max_per_seq, qc.out + (size_t)s_ * qc.out_cap, sizeof(int) * n, hipMemcpyDeviceToHost));
-        n_per_seq[s_] = n;
+    for (int s_ = 0; s_ < qc.n_seq; s_++) {      // pad: the tokens the sequence has produced
+        rc = q8_tokens_back(out_host + (size_t)s_ * max_per_seq, qc.out + (size_t)s_ * qc.out_cap, slots[s_].pad, qc.out_cap, max_per_seq, n_per_seq + s_);
+        if (rc) return rc;
     }
     return 0;
 }
@@ -819,16 +899,8 @@ static void serve_plan_counts(const rama_q8_serve_slot* slots, int n_slots, int 
 
 int rama_q8_serve_plan_step(const rama_q8_serve_slot* slots, int n_slots, int max_rows, rama_q8_serve_row* rows_out, rama_q8_serve_slot* slots_after) {
     REQUIRE(slots && rows_out, RAMA_EINVAL, "q8_serve_plan_step: NULL argument");
-    REQUIRE(n_slots >= 1 && n_slots <= kServeMaxSlots && max_rows >= n_slots && max_rows <= kQ8bMaxTok, RAMA_EINVAL,
-            "q8_serve_plan_step: 1 <= n_slots <= max_rows <= 128");
-    for (int i = 0; i < n_slots; i++) {
-        const rama_q8_serve_slot& s = slots[i];
-        REQUIRE(s.state >= RAMA_SERVE_FREE && s.state <= RAMA_SERVE_DONE, RAMA_EINVAL, "q8_serve_plan_step: bad slot state");
-        if (s.state == RAMA_SERVE_PROMPT)
-            REQUIRE(s.n_context >= 1 && s.cursor >= 0 && s.cursor < s.n_context && s.max_new >= 1, RAMA_EINVAL, "q8_serve_plan_step: bad PROMPT slot");
-        if (s.state == RAMA_SERVE_DECODE)
-            REQUIRE(s.cursor >= 0 && s.n_out >= 1 && s.n_out < s.max_new, RAMA_EINVAL, "q8_serve_plan_step: bad DECODE slot");
-    }
+    CHECKED(check_slots_rows("q8_serve_plan_step", n_slots, max_rows));
+    for (int i = 0; i < n_slots; i++) CHECKED(check_plan_slot("q8_serve_plan_step", slots[i]));
     int nrows[kServeMaxSlots];
     serve_plan_counts(slots, n_slots, max_rows, nrows);
     int r = 0;
@@ -856,15 +928,10 @@ int rama_q8_serve_plan_step(const rama_q8_serve_slot* slots, int n_slots, int ma
 int rama_q8_serve_spec_plan_step(const rama_q8_serve_slot* slots, int n_slots, int max_rows, const int32_t* want, rama_q8_serve_row* rows_out,
                                  int32_t* granted_out) {
     REQUIRE(slots && want && rows_out && granted_out, RAMA_EINVAL, "q8_serve_spec_plan_step: NULL argument");
-    REQUIRE(n_slots >= 1 && n_slots <= kServeMaxSlots && max_rows >= n_slots && max_rows <= kQ8bMaxTok, RAMA_EINVAL,
-            "q8_serve_spec_plan_step: 1 <= n_slots <= max_rows <= 128");
+    CHECKED(check_slots_rows("q8_serve_spec_plan_step", n_slots, max_rows));
     for (int i = 0; i < n_slots; i++) {
         const rama_q8_serve_slot& s = slots[i];
-        REQUIRE(s.state >= RAMA_SERVE_FREE && s.state <= RAMA_SERVE_DONE, RAMA_EINVAL, "q8_serve_spec_plan_step: bad slot state");
-        if (s.state == RAMA_SERVE_PROMPT)
-            REQUIRE(s.n_context >= 1 && s.cursor >= 0 && s.cursor < s.n_context && s.max_new >= 1, RAMA_EINVAL, "q8_serve_spec_plan_step: bad PROMPT slot");
-        if (s.state == RAMA_SERVE_DECODE)
-            REQUIRE(s.cursor >= 0 && s.n_out >= 1 && s.n_out < s.max_new, RAMA_EINVAL, "q8_serve_spec_plan_step: bad DECODE slot");
+        CHECKED(check_plan_slot("q8_serve_spec_plan_step", s));
         REQUIRE(want[i] >= 0 && want[i] <= kSpecMaxDraft, RAMA_EINVAL, "q8_serve_spec_plan_step: a slot wants 0..15 drafts");
         REQUIRE(want[i] == 0 || (s.state == RAMA_SERVE_DECODE && want[i] <= s.max_new - s.n_out - 1), RAMA_EINVAL,
                 "q8_serve_spec_plan_step: only a DECODE slot drafts, and at most max_new - n_out - 1 tokens");
@@ -907,8 +974,7 @@ static int serve_begin(rama_ctx* c, const rama_config* cfg, const rama_q8_weight
     REQUIRE(w && w->group_size > 0 && cfg->dim % w->group_size == 0 && cfg->hidden_dim % w->group_size == 0, RAMA_EINVAL,
             "q8_serve_begin: group_size must divide dim and hidden_dim");
     REQUIRE(q8_weights_complete(w), RAMA_EINVAL, "q8_serve_begin: missing weights");
-    REQUIRE(n_slots >= 1 && n_slots <= kServeMaxSlots && max_rows >= n_slots && max_rows <= kQ8bMaxTok, RAMA_EINVAL,
-            "q8_serve_begin: 1 <= n_slots <= max_rows <= 128");
+    CHECKED(check_slots_rows("q8_serve_begin", n_slots, max_rows));
     REQUIRE(max_new_cap >= 1 && max_new_cap <= cfg->seq_len - 1, RAMA_EINVAL, "q8_serve_begin: max_new_cap outside [1, seq_len - 1]");
     REQUIRE(q8_batch_ok(cfg), RAMA_EUNSUP, "q8_serve_begin: a shape the Q8 token-batch pass does not take");
     const int V = cfg->vocab_size;
@@ -919,24 +985,28 @@ static int serve_begin(rama_ctx* c, const rama_config* cfg, const rama_q8_weight
     if (set_device(c)) return 1;
     HIPCHK(hipStreamSynchronize(c->stream));
     serve_release(c);
-    // both scratches, the sampler's slices and the chain's tables: sized here, outside any capture
-    rc = ensure_q8_scratch(c, cfg); if (rc) return rc;
+    // the scratch (a spec chain picks per row) and the chain's tables: sized here, outside any capture
     Q8BatchScratch b{};
-    rc = ensure_q8_batch_scratch(c, cfg, w->group_size, &b); if (rc) return rc;
-    if (sampler) { rc = ensure_topp_batch(c, spec ? max_rows : n_slots, V); if (rc) return rc; }      // (a spec chain picks per row)
+    rc = q8_chain_scratch(c, cfg, w->group_size, sampler ? (spec ? max_rows : n_slots) : 0, &b); if (rc) return rc;
     auto& sv = c->q8s;
+    ServeTables& t = sv.t;
+    ServeSpecTables& st = sv.st;
     const size_t S = (size_t)cfg->seq_len, N = (size_t)n_slots, R = (size_t)max_rows, cap = (size_t)max_new_cap, H = (size_t)hint_cap;
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-    // [9..15]: the drafting tables, nothing of them on a chain begun without drafts
-    const size_t sz[16] = {N * sizeof(ServeSlot), N * S * sizeof(int), R * sizeof(SeqSlot), R * sizeof(int), N * sizeof(int), N * sizeof(int),
-                           N * sizeof(ToppRow), 4 * sizeof(unsigned long long), N * cap * sizeof(int),
-                           N * sizeof(ServeSpecSlot), N * H * sizeof(int), R * sizeof(int), R * sizeof(int), R * sizeof(ToppRow),
-                           N * sizeof(ServeSpecSums), 2 * sizeof(unsigned long long)};
-    const int n_tab = spec ? 16 : 9;
-    size_t off[16] = {}, need = 0;
-    for (int i = 0; i < n_tab; i++) { off[i] = need; need += up(sz[i]); }
+    auto lay = [&](char* base) {
+        BlobCarver bc{base};
+        bc.take(t.slots, N); bc.take(t.ctx, N * S); bc.take(t.rows, R); bc.take(t.row_tok, R); bc.take(t.nrows, N); bc.take(t.lrow, N);
+        bc.take(t.trow, N); bc.take(t.counters, 4); bc.take(t.out, N * cap);
+        if (spec) {      // the drafting tables: nothing of them on a chain begun without drafts
+            bc.take(st.ss, N); bc.take(st.hint, N * H); bc.take(st.picks, R); bc.take(st.lflag, R); bc.take(st.rrow, R); bc.take(st.sums, N);
+            bc.take(st.sched, 2);
+        }
+        return bc.used;
+    };
+    const size_t need = lay(nullptr);
     HIPCHK(hipMalloc(&sv.blob, need));
     HIPCHK(hipMemsetAsync(sv.blob, 0, need, c->stream));          // every slot FREE, the counters 0
+    lay(sv.blob);
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
     sv.rec_bytes = up(sizeof(ServeSlot) + S * sizeof(int));
     HIPCHK(hipMalloc(&sv.stage, N * sv.rec_bytes));
     HIPCHK(hipHostMalloc(&sv.pinned, N * sv.rec_bytes, hipHostMallocDefault));
@@ -944,23 +1014,12 @@ static int serve_begin(rama_ctx* c, const rama_config* cfg, const rama_q8_weight
         sv.srec_bytes = up(sizeof(ServeSpecSlot) + H * sizeof(int));
         HIPCHK(hipMalloc(&sv.sstage, N * sv.srec_bytes));
         HIPCHK(hipHostMalloc(&sv.spinned, N * sv.srec_bytes, hipHostMallocDefault));
-        ServeSpecTables& st = sv.st;
-        st.ss = reinterpret_cast<ServeSpecSlot*>(sv.blob + off[9]); st.hint = reinterpret_cast<int*>(sv.blob + off[10]);
-        st.picks = reinterpret_cast<int*>(sv.blob + off[11]); st.lflag = reinterpret_cast<int*>(sv.blob + off[12]);
-        st.rrow = reinterpret_cast<ToppRow*>(sv.blob + off[13]); st.sums = reinterpret_cast<ServeSpecSums*>(sv.blob + off[14]);
-        st.sched = reinterpret_cast<unsigned long long*>(sv.blob + off[15]);
         st.hint_cap = hint_cap;
     }
     HIPCHK(hipHostMalloc(&sv.ring, sizeof(int) * N * cap, hipHostMallocMapped));
     HIPCHK(hipHostMalloc(&sv.done, sizeof(int) * N, hipHostMallocMapped));
     memset(sv.ring, 0, sizeof(int) * N * cap);
     memset(sv.done, 0, sizeof(int) * N);
-    ServeTables& t = sv.t;
-    t.slots = reinterpret_cast<ServeSlot*>(sv.blob + off[0]); t.ctx = reinterpret_cast<int*>(sv.blob + off[1]);
-    t.rows = reinterpret_cast<SeqSlot*>(sv.blob + off[2]); t.row_tok = reinterpret_cast<int*>(sv.blob + off[3]);
-    t.nrows = reinterpret_cast<int*>(sv.blob + off[4]); t.lrow = reinterpret_cast<int*>(sv.blob + off[5]);
-    t.trow = reinterpret_cast<ToppRow*>(sv.blob + off[6]); t.counters = reinterpret_cast<unsigned long long*>(sv.blob + off[7]);
-    t.out = reinterpret_cast<int*>(sv.blob + off[8]);
     HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&t.ring), sv.ring, 0));
     HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&t.done), sv.done, 0));
     t.seq_len = cfg->seq_len; t.n_slots = n_slots; t.max_rows = max_rows; t.out_cap = max_new_cap;
@@ -1008,20 +1067,17 @@ static int serve_admit(rama_ctx* c, int slot, const rama_run_state* state, const
     REQUIRE(plan->max_new >= 1, RAMA_EINVAL, "q8_serve_admit: max_new < 1");
     REQUIRE(plan->max_new <= sv.out_cap, RAMA_EINVAL, "q8_serve_admit: max_new beyond rama_q8_serve_begin's max_new_cap");
     REQUIRE(n_context <= sv.cfg.seq_len - plan->max_new, RAMA_EINVAL, "q8_serve_admit: n_context + max_new beyond seq_len");
-    for (int i = 0; i < n_context; i++) REQUIRE(context_host[i] >= 0 && context_host[i] < V, RAMA_EINVAL, "q8_serve_admit: token outside the vocabulary");
-    REQUIRE(topp_params_ok(plan->temperature, plan->topp, plan->u), RAMA_EINVAL, "q8_serve_admit: temperature >= 0, topp in [0,1], u in [0,1)");
-    REQUIRE(plan->stop_token >= -1 && plan->stop_token < V, RAMA_EINVAL, "q8_serve_admit: stop token outside the vocabulary");
+    CHECKED(check_tokens("q8_serve_admit", "token outside the vocabulary", context_host, n_context, V));
+    CHECKED(check_sampler("q8_serve_admit", plan->temperature, plan->topp, plan->u));
+    CHECKED(check_stop_token("q8_serve_admit", plan->stop_token, V));
     for (int j = 0; j < sv.n_slots; j++)
         REQUIRE(j == slot || !serve_slot_live(sv, j) || (sv.states[j].key_cache != state->key_cache && sv.states[j].value_cache != state->value_cache),
                 RAMA_EINVAL, "q8_serve_admit: the run state is already in a live slot");
     REQUIRE(plan->temperature == 0.0f || sv.sampler, RAMA_EUNSUP, "q8_serve_admit: a sampled plan needs vocab_size <= 32768");
     if (spec) {
         REQUIRE(sv.spec, RAMA_EINVAL, "q8_serve_admit_spec: the chain was not begun with rama_q8_serve_begin_spec");
-        REQUIRE(spec->n_draft >= 0 && spec->n_draft <= sv.n_draft_cap, RAMA_EINVAL, "q8_serve_admit_spec: n_draft beyond rama_q8_serve_begin_spec's n_draft_cap");
-        REQUIRE(spec->ngram >= 1 && spec->ngram <= kSpecMaxNgram, RAMA_EINVAL, "q8_serve_admit_spec: ngram outside 1..4");
-        REQUIRE(spec->n_hint >= 0 && (spec->n_hint == 0 || spec->hint) && spec->n_hint <= sv.hint_cap, RAMA_EINVAL,
-                "q8_serve_admit_spec: bad hint, or one beyond rama_q8_serve_begin_spec's hint_cap");
-        for (int i = 0; i < spec->n_hint; i++) REQUIRE(spec->hint[i] >= 0 && spec->hint[i] < V, RAMA_EINVAL, "q8_serve_admit_spec: hint token outside the vocabulary");
+        CHECKED(check_drafting("q8_serve_admit_spec", *spec, sv.n_draft_cap, "n_draft beyond rama_q8_serve_begin_spec's n_draft_cap", sv.hint_cap,
+                               "bad hint, or one beyond rama_q8_serve_begin_spec's hint_cap", V));
     }
     if (set_device(c)) return 1;
     // the slot's own pinned record: its previous copy has run (the occupant it installed has finished, or there was none)
@@ -1119,22 +1175,17 @@ static int enqueue_q8_serve_step(rama_ctx* c, const Q8BatchScratch& b) {
     auto& sv = c->q8s;
     const rama_config* cfg = &sv.cfg;
     const rama_q8_weights* w = &sv.w;
-    const int dim = cfg->dim, V = cfg->vocab_size, R = sv.max_rows, N = sv.n_slots;
+    const int dim = cfg->dim, R = sv.max_rows, N = sv.n_slots;
     hipLaunchKernelGGL(serve_schedule_kernel, dim3(1), dim3(kServeMaxSlots), 0, c->stream, sv.t);
     LAUNCHCHK();
-    hipLaunchKernelGGL(embed_rows_kernel, dim3((dim + 255) / 256, R), dim3(256), 0, c->stream, b.X, w->token_embedding_table, (const int*)sv.t.row_tok, R, dim);
-    LAUNCHCHK();
-    int rc = q8_batch_layers(c, cfg, w, b, R, 0, nullptr, nullptr, sv.t.rows); if (rc) return rc;
+    int rc = enqueue_q8_row_layers(c, cfg, w, b, sv.t.row_tok, sv.t.rows, R); if (rc) return rc;
     // the classifier tail for the slots' logits rows only (b.Q is free here)
     hipLaunchKernelGGL(serve_gather_kernel, dim3((dim + 255) / 256, N), dim3(256), 0, c->stream, b.Q, (const float*)b.X, (const int*)sv.t.lrow, dim);
     LAUNCHCHK();
     rc = enqueue_q8_classifier(c, cfg, w, b, b.Q, N); if (rc) return rc;
     ServePickParams fin{};
-    fin.t = sv.t; fin.logits = b.LG; fin.ld = (size_t)V; fin.n = V;
-    if (sv.sampler) {
-        rc = enqueue_topp_batch_order(c, sv.t.trow, N, b.LG, (size_t)V, V, nullptr); if (rc) return rc;
-        fin.keys = c->tb.keys; fin.vals = c->tb.vals; fin.m = c->tb.m; fin.rstride = c->tb.rstride;
-    }
+    fin.t = sv.t;
+    rc = enqueue_q8_pick_rows(c, b, cfg->vocab_size, sv.sampler, sv.t.trow, N, &fin.r); if (rc) return rc;
     hipLaunchKernelGGL(serve_pick_kernel, dim3(N), dim3(1024), 0, c->stream, fin);
     LAUNCHCHK();
     return 0;
@@ -1144,23 +1195,15 @@ static int enqueue_q8_serve_step(rama_ctx* c, const Q8BatchScratch& b) {
 // flagged row's pick, the accept rule per slot
 static int enqueue_q8_serve_spec_step(rama_ctx* c, const Q8BatchScratch& b) {
     auto& sv = c->q8s;
-    const rama_config* cfg = &sv.cfg;
-    const rama_q8_weights* w = &sv.w;
-    const int dim = cfg->dim, V = cfg->vocab_size, R = sv.max_rows, N = sv.n_slots;
+    const int R = sv.max_rows, N = sv.n_slots;
     hipLaunchKernelGGL(serve_draft_kernel, dim3(N), dim3(kServeDraftThreads), 0, c->stream, sv.t, sv.st);
     LAUNCHCHK();
     hipLaunchKernelGGL(serve_spec_schedule_kernel, dim3(1), dim3(kServeMaxSlots), 0, c->stream, sv.t, sv.st);
     LAUNCHCHK();
-    hipLaunchKernelGGL(embed_rows_kernel, dim3((dim + 255) / 256, R), dim3(256), 0, c->stream, b.X, w->token_embedding_table, (const int*)sv.t.row_tok, R, dim);
-    LAUNCHCHK();
-    int rc = q8_batch_layers(c, cfg, w, b, R, 0, nullptr, nullptr, sv.t.rows); if (rc) return rc;
-    rc = enqueue_q8_classifier(c, cfg, w, b, b.X, R); if (rc) return rc;
+    int rc = enqueue_q8_batch_pass(c, &sv.cfg, &sv.w, b, sv.t.row_tok, sv.t.rows, R); if (rc) return rc;
     ServeSpecPickParams fin{};
-    fin.t = sv.t; fin.st = sv.st; fin.logits = b.LG; fin.ld = (size_t)V; fin.n = V;
-    if (sv.sampler) {
-        rc = enqueue_topp_batch_order(c, sv.st.rrow, R, b.LG, (size_t)V, V, nullptr); if (rc) return rc;
-        fin.keys = c->tb.keys; fin.vals = c->tb.vals; fin.m = c->tb.m; fin.rstride = c->tb.rstride;
-    }
+    fin.t = sv.t; fin.st = sv.st;
+    rc = enqueue_q8_pick_rows(c, b, sv.cfg.vocab_size, sv.sampler, sv.st.rrow, R, &fin.r); if (rc) return rc;
     hipLaunchKernelGGL(serve_spec_pick_kernel, dim3(R), dim3(1024), 0, c->stream, fin);
     LAUNCHCHK();
     hipLaunchKernelGGL(serve_spec_accept_kernel, dim3(N), dim3(64), 0, c->stream, sv.t, sv.st);
@@ -1175,14 +1218,9 @@ int rama_q8_serve_steps(rama_ctx* c, int n_steps) {
     REQUIRE(sv.live, RAMA_EINVAL, "q8_serve_steps: the chain's model or the run state of an occupied slot has been freed");
     REQUIRE(n_steps >= 0, RAMA_EINVAL, "q8_serve_steps: n_steps < 0");
     if (set_device(c)) return 1;
-    // (neither grows here: rama_q8_serve_begin sized them, and whoever grew them since for another shape dropped the step's graph)
-    int rc = ensure_q8_scratch(c, &sv.cfg); if (rc) return rc;
-    Q8BatchScratch b{};
-    rc = ensure_q8_batch_scratch(c, &sv.cfg, sv.w.group_size, &b); if (rc) return rc;
-    if (sv.sampler) { rc = ensure_topp_batch(c, sv.spec ? sv.max_rows : sv.n_slots, sv.cfg.vocab_size); if (rc) return rc; }
-    c->embedded_x = nullptr; c->host_pos = -1;
     int n_done = 0;
-    rc = q8_run_steps(c, sv.cg, n_steps, [&] { return sv.spec ? enqueue_q8_serve_spec_step(c, b) : enqueue_q8_serve_step(c, b); }, &n_done, &sv.captures);
+    const int rc = q8_chain_steps(c, sv, sv.sampler ? (sv.spec ? sv.max_rows : sv.n_slots) : 0, n_steps,
+                                  [&](const Q8BatchScratch& b) { return sv.spec ? enqueue_q8_serve_spec_step(c, b) : enqueue_q8_serve_step(c, b); }, &n_done);
     sv.steps += (unsigned long long)n_done;
     return rc;
 }
@@ -1205,24 +1243,17 @@ int rama_q8_serve_tokens(rama_ctx* c, int slot, int32_t* out_host, int max_token
     REQUIRE(c && n_out && c->q8s.n_slots > 0 && slot >= 0 && slot < c->q8s.n_slots && max_tokens >= 0 && (max_tokens == 0 || out_host), RAMA_EINVAL,
             "q8_serve_tokens: bad argument");
     auto& sv = c->q8s;
-    if (set_device(c)) return 1;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    { const int rh = handoff_check(c); if (rh) return rh; }
+    const int rc = q8_drain(c); if (rc) return rc;
     ServeSlot s{};
     HIPCHK(hipMemcpy(&s, sv.t.slots + slot, sizeof s, hipMemcpyDeviceToHost));
-    const int n = std::min(std::min(s.n_out, sv.out_cap), max_tokens);
-    if (n > 0) HIPCHK(hipMemcpy(out_host, sv.t.out + (size_t)slot * sv.out_cap, sizeof(int) * n, hipMemcpyDeviceToHost));
-    *n_out = n;
-    return 0;
+    return q8_tokens_back(out_host, sv.t.out + (size_t)slot * sv.out_cap, s.n_out, sv.out_cap, max_tokens, n_out);
 }
 
 int rama_q8_serve_stats(rama_ctx* c, rama_q8_serve_report* out) {
     RAMA_ENTER(c);
     REQUIRE(c && out && c->q8s.n_slots > 0, RAMA_EINVAL, "q8_serve_stats: bad argument");
     auto& sv = c->q8s;
-    if (set_device(c)) return 1;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    { const int rh = handoff_check(c); if (rh) return rh; }
+    { const int rh = q8_drain(c); if (rh) return rh; }
     memset(out, 0, sizeof *out);
     unsigned long long cnt[4];
     ServeSlot slots[kServeMaxSlots];
@@ -1251,9 +1282,7 @@ int rama_q8_serve_spec_stats(rama_ctx* c, rama_q8_serve_spec_report* out) {
     RAMA_ENTER(c);
     REQUIRE(c && out && c->q8s.n_slots > 0 && c->q8s.spec, RAMA_EINVAL, "q8_serve_spec_stats: no chain begun with rama_q8_serve_begin_spec");
     auto& sv = c->q8s;
-    if (set_device(c)) return 1;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    { const int rh = handoff_check(c); if (rh) return rh; }
+    { const int rh = q8_drain(c); if (rh) return rh; }
     memset(out, 0, sizeof *out);
     unsigned long long cnt[4], sched[2];
     std::vector<ServeSpecSlot> ss(sv.n_slots);
@@ -1330,45 +1359,40 @@ int rama_q8_spec_begin(rama_ctx* c, const rama_config* cfg, const rama_q8_weight
     REQUIRE(c && state && context_host && plan, RAMA_EINVAL, "q8_spec_begin: NULL argument");
     int rc = q8_check(c, cfg, w, state); if (rc) return rc;
     const int V = cfg->vocab_size;
-    REQUIRE(topp_params_ok(plan->temperature, plan->topp, plan->u), RAMA_EINVAL, "q8_spec_begin: temperature >= 0, topp in [0,1], u in [0,1)");
-    REQUIRE(plan->stop_token >= -1 && plan->stop_token < V, RAMA_EINVAL, "q8_spec_begin: stop token outside the vocabulary");
-    REQUIRE(plan->n_draft >= 0 && plan->n_draft <= kSpecMaxDraft, RAMA_EINVAL, "q8_spec_begin: n_draft outside 0..15");
-    REQUIRE(plan->ngram >= 1 && plan->ngram <= kSpecMaxNgram, RAMA_EINVAL, "q8_spec_begin: ngram outside 1..4");
-    REQUIRE(plan->n_hint >= 0 && (plan->n_hint == 0 || plan->hint) && plan->n_hint < kSpecHintBit, RAMA_EINVAL, "q8_spec_begin: bad hint");
-    for (int i = 0; i < plan->n_hint; i++) REQUIRE(plan->hint[i] >= 0 && plan->hint[i] < V, RAMA_EINVAL, "q8_spec_begin: hint token outside the vocabulary");
+    CHECKED(check_sampler("q8_spec_begin", plan->temperature, plan->topp, plan->u));
+    CHECKED(check_stop_token("q8_spec_begin", plan->stop_token, V));
+    CHECKED(check_drafting("q8_spec_begin", *plan, kSpecMaxDraft, "n_draft outside 0..15", kSpecHintBit - 1, "bad hint", V));
     REQUIRE(n_context >= 1, RAMA_EINVAL, "q8_spec_begin: n_context < 1");
     REQUIRE(plan->max_new >= 1, RAMA_EINVAL, "q8_spec_begin: max_new < 1");
     REQUIRE(plan->max_new <= cfg->seq_len && n_context <= cfg->seq_len - plan->max_new, RAMA_EINVAL, "q8_spec_begin: n_context + max_new beyond seq_len");
-    for (int i = 0; i < n_context; i++) REQUIRE(context_host[i] >= 0 && context_host[i] < V, RAMA_EINVAL, "q8_spec_begin: token outside the vocabulary");
+    CHECKED(check_tokens("q8_spec_begin", "token outside the vocabulary", context_host, n_context, V));
     REQUIRE(q8_batch_ok(cfg), RAMA_EUNSUP, "q8_spec_begin: a shape the Q8 token-batch pass does not take");
     const bool sampled = plan->temperature != 0.0f;
     REQUIRE(!sampled || (V > 1 && V <= kToppBlock * kToppMaxBlocks), RAMA_EUNSUP, "q8_spec_begin: a sampled plan needs vocab_size <= 32768");
     if (set_device(c)) return 1;
     HIPCHK(hipStreamSynchronize(c->stream));
     spec_release(c);
-    // both scratches, the sampler's slices and the chain's tables: sized here, outside any capture
-    rc = ensure_q8_scratch(c, cfg); if (rc) return rc;
-    Q8BatchScratch b{};
-    rc = ensure_q8_batch_scratch(c, cfg, w->group_size, &b); if (rc) return rc;
+    // the scratch and the chain's tables: sized here, outside any capture
     const int R = plan->n_draft + 1;
-    if (sampled) { rc = ensure_topp_batch(c, R, V); if (rc) return rc; }
+    Q8BatchScratch b{};
+    rc = q8_chain_scratch(c, cfg, w->group_size, sampled ? R : 0, &b); if (rc) return rc;
     auto& sp = c->q8p;
+    SpecTables& t = sp.t;
     const size_t S = (size_t)cfg->seq_len, H = (size_t)plan->n_hint, cap = (size_t)plan->max_new;
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-    const size_t sz[6] = {sizeof(SpecState), (H + S) * sizeof(int), kSpecRows * sizeof(SeqSlot), kSpecRows * sizeof(int), kSpecRows * sizeof(ToppRow),
-                          cap * sizeof(int)};
-    size_t off[6], need = 0;
-    for (int i = 0; i < 6; i++) { off[i] = need; need += up(sz[i]); }
+    auto lay = [&](char* base) {
+        BlobCarver bc{base};
+        bc.take(t.st, 1); bc.take(t.text, H + S); bc.take(t.rows, kSpecRows); bc.take(t.row_tok, kSpecRows); bc.take(t.trow, kSpecRows);
+        bc.take(t.out, cap);
+        return bc.used;
+    };
+    const size_t need = lay(nullptr);
     HIPCHK(hipMalloc(&sp.blob, need));
     HIPCHK(hipMemset(sp.blob, 0, need));
+    lay(sp.blob);
     HIPCHK(hipHostMalloc(&sp.ring, sizeof(int) * cap, hipHostMallocMapped));
     HIPCHK(hipHostMalloc(&sp.words, sizeof(int) * 2, hipHostMallocMapped));
     memset(sp.ring, 0, sizeof(int) * cap);
     memset(sp.words, 0, sizeof(int) * 2);
-    SpecTables& t = sp.t;
-    t.st = reinterpret_cast<SpecState*>(sp.blob + off[0]); t.text = reinterpret_cast<int*>(sp.blob + off[1]);
-    t.rows = reinterpret_cast<SeqSlot*>(sp.blob + off[2]); t.row_tok = reinterpret_cast<int*>(sp.blob + off[3]);
-    t.trow = reinterpret_cast<ToppRow*>(sp.blob + off[4]); t.out = reinterpret_cast<int*>(sp.blob + off[5]);
     int* words_dev = nullptr;
     HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&t.ring), sp.ring, 0));
     HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&words_dev), sp.words, 0));
@@ -1390,21 +1414,13 @@ int rama_q8_spec_begin(rama_ctx* c, const rama_config* cfg, const rama_q8_weight
 // one step: the drafts and the row table, the pass over it, every row's logits, every row's pick, the accept rule
 static int enqueue_q8_spec_step(rama_ctx* c, const Q8BatchScratch& b) {
     auto& sp = c->q8p;
-    const rama_config* cfg = &sp.cfg;
-    const rama_q8_weights* w = &sp.w;
-    const int dim = cfg->dim, V = cfg->vocab_size, R = sp.n_rows;
+    const int R = sp.n_rows;
     hipLaunchKernelGGL(spec_draft_kernel, dim3(1), dim3(1024), 0, c->stream, sp.t);
     LAUNCHCHK();
-    hipLaunchKernelGGL(embed_rows_kernel, dim3((dim + 255) / 256, R), dim3(256), 0, c->stream, b.X, w->token_embedding_table, (const int*)sp.t.row_tok, R, dim);
-    LAUNCHCHK();
-    int rc = q8_batch_layers(c, cfg, w, b, R, 0, nullptr, nullptr, sp.t.rows); if (rc) return rc;
-    rc = enqueue_q8_classifier(c, cfg, w, b, b.X, R); if (rc) return rc;
+    int rc = enqueue_q8_batch_pass(c, &sp.cfg, &sp.w, b, sp.t.row_tok, sp.t.rows, R); if (rc) return rc;
     SpecPickParams fin{};
-    fin.t = sp.t; fin.logits = b.LG; fin.ld = (size_t)V; fin.n = V;
-    if (sp.sampled) {
-        rc = enqueue_topp_batch_order(c, sp.t.trow, R, b.LG, (size_t)V, V, nullptr); if (rc) return rc;
-        fin.keys = c->tb.keys; fin.vals = c->tb.vals; fin.m = c->tb.m; fin.rstride = c->tb.rstride;
-    }
+    fin.t = sp.t;
+    rc = enqueue_q8_pick_rows(c, b, sp.cfg.vocab_size, sp.sampled, sp.t.trow, R, &fin.r); if (rc) return rc;
     hipLaunchKernelGGL(spec_pick_kernel, dim3(R), dim3(1024), 0, c->stream, fin);
     LAUNCHCHK();
     hipLaunchKernelGGL(spec_accept_kernel, dim3(1), dim3(64), 0, c->stream, sp.t);
@@ -1419,14 +1435,8 @@ int rama_q8_spec_steps(rama_ctx* c, int n_steps) {
     REQUIRE(sp.live, RAMA_EINVAL, "q8_spec_steps: the chain's model or its run state has been freed");
     REQUIRE(n_steps >= 0, RAMA_EINVAL, "q8_spec_steps: n_steps < 0");
     if (set_device(c)) return 1;
-    // (neither grows here: rama_q8_spec_begin sized them, and whoever grew them since for another shape dropped the step's graph)
-    int rc = ensure_q8_scratch(c, &sp.cfg); if (rc) return rc;
-    Q8BatchScratch b{};
-    rc = ensure_q8_batch_scratch(c, &sp.cfg, sp.w.group_size, &b); if (rc) return rc;
-    if (sp.sampled) { rc = ensure_topp_batch(c, sp.n_rows, sp.cfg.vocab_size); if (rc) return rc; }
-    c->embedded_x = nullptr; c->host_pos = -1;
     int n_done = 0;
-    return q8_run_steps(c, sp.cg, n_steps, [&] { return enqueue_q8_spec_step(c, b); }, &n_done, &sp.captures);
+    return q8_chain_steps(c, sp, sp.sampled ? sp.n_rows : 0, n_steps, [&](const Q8BatchScratch& b) { return enqueue_q8_spec_step(c, b); }, &n_done);
 }
 
 int rama_q8_spec_poll(rama_ctx* c, int from, int32_t* out_host, int max_tokens, int* n_ready, int* finished) {
@@ -1445,24 +1455,17 @@ int rama_q8_spec_tokens(rama_ctx* c, int32_t* out_host, int max_tokens, int* n) 
     RAMA_ENTER(c);
     REQUIRE(c && n && c->q8p.active && max_tokens >= 0 && (max_tokens == 0 || out_host), RAMA_EINVAL, "q8_spec_tokens: bad argument");
     auto& sp = c->q8p;
-    if (set_device(c)) return 1;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    { const int rh = handoff_check(c); if (rh) return rh; }
+    { const int rh = q8_drain(c); if (rh) return rh; }
     SpecState s{};
     HIPCHK(hipMemcpy(&s, sp.t.st, sizeof s, hipMemcpyDeviceToHost));
-    const int k = std::min(std::min(s.n_out, sp.out_cap), max_tokens);
-    if (k > 0) HIPCHK(hipMemcpy(out_host, sp.t.out, sizeof(int) * k, hipMemcpyDeviceToHost));
-    *n = k;
-    return 0;
+    return q8_tokens_back(out_host, sp.t.out, s.n_out, sp.out_cap, max_tokens, n);
 }
 
 int rama_q8_spec_stats(rama_ctx* c, rama_q8_spec_report* out) {
     RAMA_ENTER(c);
     REQUIRE(c && out && c->q8p.active, RAMA_EINVAL, "q8_spec_stats: bad argument");
     auto& sp = c->q8p;
-    if (set_device(c)) return 1;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    { const int rh = handoff_check(c); if (rh) return rh; }
+    { const int rh = q8_drain(c); if (rh) return rh; }
     SpecState s{};
     HIPCHK(hipMemcpy(&s, sp.t.st, sizeof s, hipMemcpyDeviceToHost));
     memset(out, 0, sizeof *out);

@@ -113,8 +113,7 @@ __global__ void serve_install_kernel(ServeTables t, int slot, const ServeSlot* r
 // and becomes DECODE, or DONE on its max_new-th token or a sampled stop token.
 struct ServePickParams {
     ServeTables t;
-    const float* logits; size_t ld; int n;         // slot s's logits at logits + s ld
-    float* keys; int* vals; int* m; size_t rstride;
+    PickRows r;                                    // one row per slot
 };
 __global__ __launch_bounds__(1024) void serve_pick_kernel(ServePickParams p) {
     __shared__ ScanShared sh;
@@ -129,22 +128,9 @@ __global__ __launch_bounds__(1024) void serve_pick_kernel(ServePickParams p) {
         if (tid == 0) p.t.slots[b].cursor = s.cursor + n;
         return;
     }
-    int idx;
-    if (s.temperature == 0.0f) idx = topp_row_argmax(p.logits + (size_t)b * p.ld, p.n, s_v, s_i);
-    else {
-        const size_t o = (size_t)b * p.rstride;
-        ToppParams tp{};
-        tp.logits = p.logits + (size_t)b * p.ld; tp.n = p.n; tp.temperature = s.temperature; tp.topp = s.topp; tp.u = s.u;
-        tp.keys = p.keys + o; tp.vals = p.vals + o; tp.m = p.m + b;
-        ArgmaxParams fin{};
-        fin.result = &s_i[0];                                      // finish_step's raw pick (-1: nothing kept)
-        topp_pick_scan_body(tp, fin, sh);
-        __syncthreads();
-        idx = s_i[0];
-    }
+    const int next = topp_row_pick(p.r, b, s.temperature, s.topp, s.u, sh, s_v, s_i);
     __syncthreads();
     if (tid != 0) return;
-    const int next = idx < 0 ? 0 : idx;                            // (a sample that keeps nothing gives token 0, as finish_step)
     const int k = s.n_out;
     ServeSlot* d = p.t.slots + b;
     p.t.out[(size_t)b * p.t.out_cap + k] = next;

@@ -167,8 +167,7 @@ __global__ __launch_bounds__(kServeMaxSlots) void serve_spec_schedule_kernel(Ser
 // It advances nothing: serve_spec_accept_kernel decides what the picks mean.
 struct ServeSpecPickParams {
     ServeTables t; ServeSpecTables st;
-    const float* logits; size_t ld; int n;         // row b's logits at logits + b ld
-    float* keys; int* vals; int* m; size_t rstride;
+    PickRows r;
 };
 __global__ __launch_bounds__(1024) void serve_spec_pick_kernel(ServeSpecPickParams p) {
     __shared__ ScanShared sh;
@@ -177,21 +176,8 @@ __global__ __launch_bounds__(1024) void serve_spec_pick_kernel(ServeSpecPickPara
     const int b = blockIdx.x, tid = threadIdx.x;
     if (!p.st.lflag[b]) return;                                    // idle, or inside a context (uniform: the whole workgroup)
     const ServeSlot* sl = p.t.slots + p.t.rows[b].pad;
-    const float T = sl->temperature;
-    int idx;
-    if (T == 0.0f) idx = topp_row_argmax(p.logits + (size_t)b * p.ld, p.n, s_v, s_i);
-    else {
-        const size_t o = (size_t)b * p.rstride;
-        ToppParams tp{};
-        tp.logits = p.logits + (size_t)b * p.ld; tp.n = p.n; tp.temperature = T; tp.topp = sl->topp; tp.u = sl->u;
-        tp.keys = p.keys + o; tp.vals = p.vals + o; tp.m = p.m + b;
-        ArgmaxParams fin{};
-        fin.result = &s_i[0];                                      // finish_step's raw pick (-1: nothing kept)
-        topp_pick_scan_body(tp, fin, sh);
-        __syncthreads();
-        idx = s_i[0];
-    }
-    if (tid == 0) p.st.picks[b] = idx < 0 ? 0 : idx;               // (a sample that keeps nothing gives token 0, as finish_step)
+    const int tok = topp_row_pick(p.r, b, sl->temperature, sl->topp, sl->u, sh, s_v, s_i);
+    if (tid == 0) p.st.picks[b] = tok;
 }
 
 // What ends a step, one workgroup per slot and one thread of it: at most 16 tokens, and the host-visible words must go out in order.

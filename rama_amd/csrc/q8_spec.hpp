@@ -86,8 +86,7 @@ __global__ __launch_bounds__(1024) void spec_draft_kernel(SpecTables t) {
 // the ordering launches left -- into picks[b].  It advances nothing: spec_accept_kernel decides what the picks mean.
 struct SpecPickParams {
     SpecTables t;
-    const float* logits; size_t ld; int n;         // row b's logits at logits + b ld
-    float* keys; int* vals; int* m; size_t rstride;
+    PickRows r;
 };
 __global__ __launch_bounds__(1024) void spec_pick_kernel(SpecPickParams p) {
     __shared__ ScanShared sh;
@@ -96,21 +95,8 @@ __global__ __launch_bounds__(1024) void spec_pick_kernel(SpecPickParams p) {
     const int b = blockIdx.x, tid = threadIdx.x;
     SpecState* st = p.t.st;
     if (st->finished || b > st->n_d) return;                       // an idle row (uniform: the whole workgroup)
-    const float T = st->temperature;
-    int idx;
-    if (T == 0.0f) idx = topp_row_argmax(p.logits + (size_t)b * p.ld, p.n, s_v, s_i);
-    else {
-        const size_t o = (size_t)b * p.rstride;
-        ToppParams tp{};
-        tp.logits = p.logits + (size_t)b * p.ld; tp.n = p.n; tp.temperature = T; tp.topp = st->topp; tp.u = st->u;
-        tp.keys = p.keys + o; tp.vals = p.vals + o; tp.m = p.m + b;
-        ArgmaxParams fin{};
-        fin.result = &s_i[0];                                      // finish_step's raw pick (-1: nothing kept)
-        topp_pick_scan_body(tp, fin, sh);
-        __syncthreads();
-        idx = s_i[0];
-    }
-    if (tid == 0) st->picks[b] = idx < 0 ? 0 : idx;                // (a sample that keeps nothing gives token 0, as finish_step)
+    const int tok = topp_row_pick(p.r, b, st->temperature, st->topp, st->u, sh, s_v, s_i);
+    if (tid == 0) st->picks[b] = tok;
 }
 
 // What ends a step: one workgroup, one thread of it -- at most 16 tokens, and the host-visible words must go out in order.

@@ -785,4 +785,27 @@ __device__ __forceinline__ int topp_row_argmax(const float* lg, int n, float* s_
     return idx < 0 ? 0 : idx;
 }
 
+// what the pick kernels of the Q8 chains (q8_serve.hpp, q8_spec.hpp, q8_serve_spec.hpp) are given behind their tables: row b's logits at
+// logits + b ld, and -- a sampled chain -- the slices the batched sampler's ordering launches left for it
+struct PickRows {
+    const float* logits; size_t ld; int n;
+    float* keys; int* vals; int* m; size_t rstride;
+};
+// Device::sample of row b by its whole workgroup of 1 024 threads, as a token: the argmax at temperature 0 (cpu.rs:163-167: the LAST
+// maximal index), else topp_pick_scan_kernel's pick on the row's slices (a sample that keeps nothing gives token 0, as finish_step).
+// The caller decides what the token means; s_v / s_i: 16 entries each.
+__device__ __forceinline__ int topp_row_pick(const PickRows& r, int b, float T, float topp, float u, ScanShared& sh, float* s_v, int* s_i) {
+    if (T == 0.0f) return topp_row_argmax(r.logits + (size_t)b * r.ld, r.n, s_v, s_i);
+    const size_t o = (size_t)b * r.rstride;
+    ToppParams tp{};
+    tp.logits = r.logits + (size_t)b * r.ld; tp.n = r.n; tp.temperature = T; tp.topp = topp; tp.u = u;
+    tp.keys = r.keys + o; tp.vals = r.vals + o; tp.m = r.m + b;
+    ArgmaxParams fin{};
+    fin.result = &s_i[0];                                          // finish_step's raw pick (-1: nothing kept)
+    topp_pick_scan_body(tp, fin, sh);
+    __syncthreads();
+    const int idx = s_i[0];
+    return idx < 0 ? 0 : idx;
+}
+
 }  // namespace rama
