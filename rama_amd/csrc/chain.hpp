@@ -683,7 +683,9 @@ __device__ __forceinline__ void gemv_chain_body(const ChainParams p, int bid_in)
     const __amdgpu_buffer_rsrc_t rx = make_rsrc_uniform(p.x, (unsigned)p.K * 4u);
     const int n4 = p.K >> 2;
     // (whatever of x does not fit the registers follows behind the weights.  [r5] 24 x 16 bytes per thread up front for
-    // the residual products -- llama2-7B's W2 reads 11 008 floats on 128 threads, the last 2 816 in a second round trip -- measured: 33.70 against 33.77 us)
+    // the residual products -- llama2-7B's W2 reads 11 008 floats on 128 threads, the last 2 816 in a second round trip -- measured: 33.70 against 33.77 us.
+    // That was TWO waves.  On the one wave the residual products run on since, 6 912 of W2's floats are behind the up-front pieces: a lone wave
+    // stages them between the chunks of its chain, see the W == 1 loop below)
     constexpr int T = WL * 64, XU = 16;                            // (host: K <= 16 XU T floats where a norm is folded in)
     f4 xa[XU];
 #pragma unroll
@@ -793,15 +795,20 @@ __device__ __forceinline__ void gemv_chain_body(const ChainParams p, int bid_in)
             float* d = xs + (i < n4 ? 16 * (i >> 2) + (i & 3) : p.K);
             d[0] = xa[u].x; d[4] = xa[u].y; d[8] = xa[u].z; d[12] = xa[u].w;
         }
-        for (int i0 = (int)threadIdx.x + T * XU; i0 < n4; i0 += T * 8) {      // rows longer than 64 T floats: the rest, behind the weights
-            f4 a[8];
+        // rows longer than 64 T floats: the rest, behind the weights.  Several waves stage all of it HERE, in front of the barrier (every wave reads
+        // all of xs); a lone wave stages it UNDER THE STREAM, between the chunks of its chain (kStream below): the chain of the first 4 T XU floats
+        // does not wait for the rest.  (W > 1 as it was: with T >= 128 llama2-7B's W2 is ONE trip of this loop -- nothing serial to remove.)
+        if constexpr (!(W == 1 && NORM == CNORM_NONE)) {
+            for (int i0 = (int)threadIdx.x + T * XU; i0 < n4; i0 += T * 8) {
+                f4 a[8];
 #pragma unroll
-            for (int u = 0; u < 8; u++) a[u] = ld_c(rx, (i0 + T * u) < n4 ? (unsigned)(i0 + T * u) * 16u : kOOB);
+                for (int u = 0; u < 8; u++) a[u] = ld_c(rx, (i0 + T * u) < n4 ? (unsigned)(i0 + T * u) * 16u : kOOB);
 #pragma unroll
-            for (int u = 0; u < 8; u++) {
-                const int i = i0 + T * u;
-                float* d = xs + (i < n4 ? 16 * (i >> 2) + (i & 3) : p.K);
-                d[0] = a[u].x; d[4] = a[u].y; d[8] = a[u].z; d[12] = a[u].w;
+                for (int u = 0; u < 8; u++) {
+                    const int i = i0 + T * u;
+                    float* d = xs + (i < n4 ? 16 * (i >> 2) + (i & 3) : p.K);
+                    d[0] = a[u].x; d[4] = a[u].y; d[8] = a[u].z; d[12] = a[u].w;
+                }
             }
         }
     }
@@ -823,7 +830,7 @@ __device__ __forceinline__ void gemv_chain_body(const ChainParams p, int bid_in)
         f4 xr[XD];
 #pragma unroll
         for (int u = 0; u < XD; u++) xr[u] = xq[4 * u];
-        for (int c = 0; c < nchunk; c++) {
+        auto chunk = [&](int c) __attribute__((always_inline)) {
             __amdgpu_buffer_rsrc_t rn[D / 16];                    // the chunk reloaded behind this one, stretch by stretch
 #pragma unroll
             for (int h = 0; h < D / 16; h++) rn[h] = stretch((c + 1) * (D / 16) + h);
@@ -840,7 +847,49 @@ __device__ __forceinline__ void gemv_chain_body(const ChainParams p, int bid_in)
                 wr[u] = ld_nt(rn[u >> 4], vo[(u & 15) >> 2] + (unsigned)(u & 3) * 1024u);
                 __builtin_amdgcn_sched_barrier(0);                // keep the ring rolling: one reload per consumed block
             }
+        };
+        int c = 0;
+        // A row longer than the up-front pieces (n4 > T XU; llama2-7B's W2: 11 008 floats against 4 096): the rest of x is staged UNDER the stream,
+        // a batch of T XN pieces (4 XN blocks of x: XN = 16 beside a ring of 32, the registers the up-front pieces left; 8 beside a ring of 16,
+        // whose kernels run three waves per SIMD and keep to those registers) at a time.  A batch is requested behind the ring (a wave's loads return
+        // in order: it arrives with the ring's first round trip), the chain goes on with what LDS holds, and the batch is stored when the chain is
+        // about to need it: one wait for loads that came back microseconds ago, instead of a round trip per eight pieces in front of the first block.
+        // INVARIANT.  With blocks [0, B) of x in LDS, chunk c may run iff (c + 1) D + XD <= B or B >= nblk: it multiplies blocks c D .. c D + D - 1
+        // out of xr / xs and reads blocks up to (c + 1) D + XD - 1 ahead into xr for the chunk behind it.  Blocks from nblk on are the zeros behind
+        // x, written in front of the barrier above (a lane of a batch past the end of x holds zeros -- the descriptor's range check -- and drops them
+        // there too).  B = s4 / 4 on entry of a trip and s4 / 4 + 4 XN behind its stores, so a trip runs the chunks below (s4 / 4 - XD) / D (at least
+        // one, since 4 XN >= D; fewer than nchunk, since s4 < n4 there) and the loop behind the last trip runs the rest with B >= nblk.  The stores
+        // and the reads behind them belong to ONE wave, whose LDS instructions execute in the order they were issued: no barrier, the fence keeps the
+        // compiler from moving a read in front of them.
+        // The FIRST chunk of a trip is peeled so that the waits on the ring in it count the batch's loads behind the ring's (vmcnt D + XN - 1), not
+        // in front of them; the plain loop's body is the one a short row runs, instruction for instruction.
+        if constexpr (NORM == CNORM_NONE) {
+            constexpr int XN = D >= 32 ? XU : XU / 2;
+            static_assert(4 * XN >= D && 4 * XU >= D + XD, "a trip runs at least its peeled chunk");
+#pragma unroll 1
+            for (int s4 = T * XU; s4 < n4; s4 += T * XN) {        // (uniform)
+                f4 xn[XN];
+#pragma unroll
+                for (int u = 0; u < XN; u++) {
+                    const int i = s4 + lane + T * u;
+                    xn[u] = ld_c(rx, i < n4 ? (unsigned)i * 16u : kOOB);
+                }
+                const int cl = ((s4 >> 2) - XD) / D;
+                chunk(c++);
+#pragma unroll 1
+                for (; c < cl; c++) chunk(c);
+#pragma unroll
+                for (int u = 0; u < XN; u++) {
+                    const int i = s4 + lane + T * u;
+                    float* d = xs + (i < n4 ? 16 * (i >> 2) + (i & 3) : p.K);
+                    d[0] = xn[u].x; d[4] = xn[u].y; d[8] = xn[u].z; d[12] = xn[u].w;
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+            }
         }
+#pragma unroll 1
+        for (; c < nchunk; c++) chunk(c);
     } else {
         auto premultiply = [&](int c) {                           // wr <- wr * x for chunk c (this wave's next turn)
             const f4* xc = xq + 4 * c * D;

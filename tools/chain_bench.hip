@@ -36,6 +36,11 @@ static int run(const char* name, int rows, int K, int nbuf, std::vector<float*>&
         auto q = [](std::vector<double> v, double f) { std::sort(v.begin(), v.end()); return v[(size_t)(f * (v.size() - 1))]; };
         printf("   all %d groups, us after the first start: start min/med/max %.2f %.2f %.2f | staged %.2f %.2f %.2f | loop done %.2f %.2f %.2f (p90 %.2f, p99 %.2f)\n", groups,
                q(st_, 0), q(st_, .5), q(st_, 1), q(sg_, 0), q(sg_, .5), q(sg_, 1), q(dn_, 0), q(dn_, .5), q(dn_, 1), q(dn_, .9), q(dn_, .99));
+        // a group's own start -> its chain's first block (stamp 2 - stamp 0), and first block -> loop done
+        std::vector<double> lead_, body_;
+        for (size_t b = 0; b < st_.size(); b++) { lead_.push_back(sg_[b] - st_[b]); body_.push_back(dn_[b] - sg_[b]); }
+        printf("   per group: start -> first block min/med/max %.2f %.2f %.2f | first block -> loop done %.2f %.2f %.2f us\n",
+               q(lead_, 0), q(lead_, .5), q(lead_, 1), q(body_, 0), q(body_, .5), q(body_, 1));
     }
     unsigned long long z[64] = {0}; CK(hipMemcpyToSymbol(HIP_SYMBOL(rama::g_chain_stamps), z, sizeof z));
     return 0;
@@ -51,5 +56,10 @@ int main() {
     if (run<2, 16>("wo", 4096, 4096, nbuf, Wb, x, o, r)) return 1;
     if (run<4, 32>("w2", 4096, 11008, nbuf, Wb, x, o, r)) return 1;
     if (run<4, 16>("w2", 4096, 11008, nbuf, Wb, x, o, r)) return 1;
+    // the residual products as parity mode launches them: one wave per row group, a ring of 32 blocks (256 groups on 256 compute units).
+    // 8 192 sits between the two: one whole batch of x behind the up-front pieces
+    if (run<1, 32>("wo", 4096, 4096, nbuf, Wb, x, o, r)) return 1;
+    if (run<1, 32>("mid", 4096, 8192, nbuf, Wb, x, o, r)) return 1;
+    if (run<1, 32>("w2", 4096, 11008, nbuf, Wb, x, o, r)) return 1;
     return 0;
 }
