@@ -4,12 +4,159 @@ include/rama_hip.h).  The fp32 Model / Engine are untouched.  No CPU fallback an
 from __future__ import annotations
 
 import ctypes as C
+import time
 
 import numpy as np
 
-from ._lib import Q8_TENSORS, check, rama_config, rama_q8_weights, rama_run_state
+from ._lib import (Q8_TENSORS, check, load, rama_config, rama_q8_seq_plan, rama_q8_serve_plan, rama_q8_serve_report, rama_q8_serve_row,
+                   rama_q8_serve_slot, rama_q8_serve_spec, rama_q8_serve_spec_report, rama_q8_spec_plan, rama_q8_spec_report,
+                   rama_q8_weights, rama_run_state)
+from .q8_replay import (SERVE_DECODE, SERVE_DONE, SERVE_FREE, SERVE_PROMPT,  # noqa: F401  (the restatements: re-exported)
+                        _accept_py, _draft_py, _spec_plan_py, serve_spec_replay, spec_replay)
 from .sampler_const import TOPP_U_CPU
 from .transformer import Config, Hip
+
+MAX_BATCH = 128
+MAX_DRAFT, MAX_NGRAM = 15, 4
+
+
+# ------------------------------------------------------------------ marshalling
+
+def _i32(values):
+    """a c_int32 array of the values; one unused entry for none, so that the library always gets a pointer"""
+    return (C.c_int32 * max(len(values), 1))(*values)
+
+
+def _slot_table(slots):
+    """(state, n_context, cursor, n_out, max_new) tuples -> rama_q8_serve_slot[]"""
+    return (rama_q8_serve_slot * max(len(slots), 1))(*[rama_q8_serve_slot(*[int(v) for v in s]) for s in slots])
+
+
+def _row_table(rows, n):
+    """rama_q8_serve_row[] -> n (slot, pos, logits) tuples"""
+    return [(r.slot, r.pos, r.logits) for r in rows[:n]]
+
+
+def _report(r, skip=()):
+    """a report struct as a dict of its fields: a counter as an int, an array as a list"""
+    out = {}
+    for name, _ in r._fields_:
+        if name not in skip:
+            v = getattr(r, name)
+            out[name] = v if isinstance(v, int) else list(v)
+    return out
+
+
+# ------------------------------------------------------------------ the refusals the entry points share (as check_* in q8_api.hip:
+# each takes the caller's prefix and, where two callers word a cap differently, that text)
+
+def _tokens(tokens, vocab_size: int, what: str) -> list:
+    out = [int(t) for t in tokens]
+    bad = [t for t in out if not 0 <= t < vocab_size]
+    if bad:
+        raise ValueError(f"{what}: token {bad[0]} outside the vocabulary [0, {vocab_size})")
+    return out
+
+
+def _check_batch(what, engines, tokens, positions):
+    """1..128 distinct engines over one Q8Model, a token and a position for each"""
+    n = len(engines)
+    if not 1 <= n <= MAX_BATCH:
+        raise ValueError(f"{what}: {n} sequences, not 1..{MAX_BATCH}")
+    if len(tokens) != n or len(positions) != n:
+        raise ValueError(f"{what}: {len(tokens)} tokens and {len(positions)} positions for {n} sequences")
+    if any(e.model is not engines[0].model for e in engines):
+        raise ValueError(f"{what}: the engines do not share one Q8Model")
+    if len({id(e) for e in engines}) != n:
+        raise ValueError(f"{what}: an engine appears twice")
+
+
+def _check_sampler(what, temperature, topp, u):
+    T, P, U = float(temperature), float(topp), float(u)
+    if not (T >= 0.0 and 0.0 <= P <= 1.0 and 0.0 <= U < 1.0):       # (false for NaN)
+        raise ValueError(f"{what}: temperature >= 0, topp in [0, 1], u in [0, 1) -- not {T}, {P}, {U}")
+    return T, P, U
+
+
+def _check_stop(what, stop_token, vocab_size):
+    """None: no stop token, -1 to the library"""
+    stop = -1 if stop_token is None else int(stop_token)
+    if not -1 <= stop < vocab_size:
+        raise ValueError(f"{what}: stop token {stop} outside the vocabulary [0, {vocab_size})")
+    return stop
+
+
+def _check_context(what, context, vocab_size):
+    ctx = _tokens(context, vocab_size, what)
+    if not ctx:
+        raise ValueError(f"{what}: an empty context (the caller includes BOS)")
+    return ctx
+
+
+def _check_budget(what, n_context, new, seq_len, cap=None):
+    """max_new >= 1, within the server's cap where there is one, and the context with it within seq_len"""
+    if new < 1:
+        raise ValueError(f"{what}: max_new {new} < 1")
+    if cap is not None and new > int(cap):
+        raise ValueError(f"{what}: max_new {new} beyond the server's max_new_cap {int(cap)}")
+    if n_context + new > seq_len:
+        raise ValueError(f"{what}: {n_context} context tokens + {new} new ones beyond seq_len {seq_len}")
+
+
+def _check_n_draft(what, n_draft, cap, cap_text):
+    if not 0 <= n_draft <= cap:
+        raise ValueError(f"{what}: n_draft {n_draft} outside [0, {cap_text}]")
+
+
+def _check_drafting(what, n_draft, ngram):
+    """the drafting sizes against the library's own caps"""
+    _check_n_draft(what, n_draft, MAX_DRAFT, MAX_DRAFT)
+    if not 1 <= ngram <= MAX_NGRAM:
+        raise ValueError(f"{what}: ngram {ngram} outside [1, {MAX_NGRAM}]")
+
+
+def _check_sampled_vocab(what, temperature, vocab_size):
+    if temperature != 0.0 and vocab_size > 32768:
+        raise ValueError(f"{what}: a sampled plan needs vocab_size <= 32768")
+
+
+# ------------------------------------------------------------------ the host-visible rings and the stream behind them
+
+def _ring_poll(entry, name, *before, after=()):
+    """one of the three poll entries, entry(*before, start, tokens, 64, &n, &finished, *after), as _drain's poll(start)"""
+    buf, k, fin = (C.c_int32 * 64)(), C.c_int(), C.c_int()
+    rest = (buf, 64, C.byref(k), C.byref(fin)) + tuple(after)
+
+    def poll(start):
+        check(entry(*before, start, *rest), name)
+        return buf[:k.value], fin.value
+    return poll
+
+
+def _drain(poll, seen, sink):
+    """empties a ring from its token `seen` on, 64 tokens at a time: poll(start) -> (the tokens from start on, 64 at most, the
+    finished word), sink(index, token) for each of them -> (tokens taken, finished).  The poll entries read the finished word before
+    the ring: once it is set every token of the sequence is there, and the sequence has finished when a poll with the word set
+    comes back short -- a full one may have left tokens behind."""
+    n = 0
+    while True:
+        toks, fin = poll(seen + n)
+        for t in toks:
+            sink(seen + n, t)
+            n += 1
+        if len(toks) < 64:
+            return n, bool(fin)
+
+
+def _stream_busy(device, sleep):
+    """rama_stream_query: the stream still has work -> True after `sleep` seconds, and the caller looks at its rings again; it has
+    drained -> False: one more look collects what is there.  A failed stream raises instead of being waited for."""
+    q = device.lib.rama_stream_query(device.ctx)
+    if q == 1:
+        time.sleep(sleep)
+        return True
+    check(q, "rama_stream_query")
+    return False
 
 
 class Q8Model:
@@ -106,16 +253,14 @@ class Q8Engine:
         pos0 = int(pos0)
         if pos0 < 0 or pos0 + len(toks) > self.cfg.seq_len:
             raise ValueError(f"prefill: positions {pos0} .. {pos0 + len(toks) - 1} outside [0, {self.cfg.seq_len})")
-        arr = (C.c_int32 * len(toks))(*toks)
         check(self.device.lib.rama_q8_prefill(self.device.ctx, C.byref(self.model.ccfg), C.byref(self.model.weights),
-                                              C.byref(self.state), arr, len(toks), pos0), "rama_q8_prefill")
+                                              C.byref(self.state), _i32(toks), len(toks), pos0), "rama_q8_prefill")
 
     def generate(self, prompt_tokens, steps: int, temperature: float = 0.0, topp: float = 0.9, u: float = TOPP_U_CPU):
         """generate() chained on the device (rama_q8_generate); u defaults to the reference's constant draw"""
-        pt = (C.c_int32 * max(len(prompt_tokens), 1))(*prompt_tokens)
         out = (C.c_int32 * max(steps, 1))()
         check(self.device.lib.rama_q8_generate(self.device.ctx, C.byref(self.model.ccfg), C.byref(self.model.weights),
-                                               C.byref(self.state), pt, len(prompt_tokens), steps, temperature, topp, u, out),
+                                               C.byref(self.state), _i32(prompt_tokens), len(prompt_tokens), steps, temperature, topp, u, out),
               "rama_q8_generate")
         return [int(v) for v in out[:steps]]
 
@@ -134,31 +279,25 @@ class Q8Engine:
         tokens up in `hint` (a token list, optional) and in the sequence itself, and verified in one weight pass.
         context[:-1] is prefilled here; on_token(index, token), when given, is fed from the host-visible ring while the steps
         run.  The report of the run stays behind as self.spec_stats."""
-        from ._lib import rama_q8_spec_plan, rama_q8_spec_report
-        import time
         ctx_toks, hint_toks, (T, P, U, new, stop, K, N) = spec_plan(self.cfg, context, max_new, temperature, topp, u, stop_token,
                                                                     n_draft, ngram, hint)
         L, ctx = self.device.lib, self.device.ctx
         if len(ctx_toks) > 1:
             self.prefill(ctx_toks[:-1])
-        harr = (C.c_int32 * max(len(hint_toks), 1))(*hint_toks)
+        harr = _i32(hint_toks)
         rec = rama_q8_spec_plan(T, P, U, new, stop, K, N, harr if hint_toks else None, len(hint_toks))
         check(L.rama_q8_spec_begin(ctx, C.byref(self.model.ccfg), C.byref(self.model.weights), C.byref(self.state),
-                                   (C.c_int32 * len(ctx_toks))(*ctx_toks), len(ctx_toks), C.byref(rec)), "rama_q8_spec_begin")
-        out, buf = [], (C.c_int32 * 64)()
-        k, fin = C.c_int(), C.c_int()
+                                   _i32(ctx_toks), len(ctx_toks), C.byref(rec)), "rama_q8_spec_begin")
+        out, poll = [], _ring_poll(L.rama_q8_spec_poll, "rama_q8_spec_poll", ctx)
+
+        def sink(index, token):
+            if on_token is not None:
+                on_token(index, token)
+            out.append(token)
 
         def collect():
-            """what the ring holds -> True once the finished word is set and every token has been taken"""
-            while True:
-                # the finished word is read before the ring: once it is set, every token is there
-                check(L.rama_q8_spec_poll(ctx, len(out), buf, 64, C.byref(k), C.byref(fin)), "rama_q8_spec_poll")
-                for i in range(k.value):
-                    if on_token is not None:
-                        on_token(len(out), int(buf[i]))
-                    out.append(int(buf[i]))
-                if k.value < 64:
-                    return bool(fin.value)
+            """what the ring holds -> True once the sequence has finished and every token has been taken"""
+            return _drain(poll, len(out), sink)[1]
 
         left, done = new, False          # every step before the finish emits at least one token
         while not done:
@@ -167,17 +306,11 @@ class Q8Engine:
             n = min(self.SPEC_BLOCK, left)
             check(L.rama_q8_spec_steps(ctx, n), "rama_q8_spec_steps")
             left -= n
-            while True:
+            done = collect()
+            while not done and _stream_busy(self.device, 0.0001):
                 done = collect()
-                if done:
-                    break
-                q = L.rama_stream_query(ctx)
-                if q == 1:
-                    time.sleep(0.0001)
-                    continue
-                check(q, "rama_stream_query")
+            if not done:                 # the stream has drained: what the steps emitted is there
                 done = collect()
-                break
         r = rama_q8_spec_report()
         check(L.rama_q8_spec_stats(ctx, C.byref(r)), "rama_q8_spec_stats")
         self.spec_stats = spec_report(r)
@@ -193,31 +326,12 @@ class Q8Engine:
             self.state = rama_run_state()
 
 
-MAX_BATCH = 128
-
-
-def _tokens(tokens, vocab_size: int, what: str) -> list:
-    out = [int(t) for t in tokens]
-    bad = [t for t in out if not 0 <= t < vocab_size]
-    if bad:
-        raise ValueError(f"{what}: token {bad[0]} outside the vocabulary [0, {vocab_size})")
-    return out
-
-
 def decode_batch(engines, tokens, positions):
     """one decode step of up to 128 independent sequences over one Q8Model, sharing every weight pass (rama_q8_decode_batch):
     engines[i]'s caches and logits() become what engines[i].forward(tokens[i], positions[i]) would leave"""
     engines = list(engines)
-    n = len(engines)
-    if not 1 <= n <= MAX_BATCH:
-        raise ValueError(f"decode_batch: {n} sequences, not 1..{MAX_BATCH}")
-    if len(tokens) != n or len(positions) != n:
-        raise ValueError(f"decode_batch: {len(tokens)} tokens and {len(positions)} positions for {n} sequences")
-    e0 = engines[0]
-    if any(e.model is not e0.model for e in engines):
-        raise ValueError("decode_batch: the engines do not share one Q8Model")
-    if len({id(e) for e in engines}) != n:
-        raise ValueError("decode_batch: an engine appears twice")
+    _check_batch("decode_batch", engines, tokens, positions)
+    n, e0 = len(engines), engines[0]
     toks = _tokens(tokens, e0.cfg.vocab_size, "decode_batch")
     poss = [int(p) for p in positions]
     bad = [p for p in poss if not 0 <= p < e0.cfg.seq_len]
@@ -225,7 +339,7 @@ def decode_batch(engines, tokens, positions):
         raise ValueError(f"decode_batch: position {bad[0]} outside [0, {e0.cfg.seq_len})")
     states = (rama_run_state * n)(*[e.state for e in engines])
     check(e0.device.lib.rama_q8_decode_batch(e0.device.ctx, C.byref(e0.model.ccfg), C.byref(e0.model.weights), states,
-                                             (C.c_int32 * n)(*toks), (C.c_int32 * n)(*poss), n), "rama_q8_decode_batch")
+                                             _i32(toks), _i32(poss), n), "rama_q8_decode_batch")
 
 
 def _per_seq(v, n: int, what: str) -> list:
@@ -243,17 +357,9 @@ def chain_plan(engines, tokens, positions, n_steps, temperature=0.0, topp=0.9, u
     """the checked arguments of decode_batch_chained: (tokens, positions, per-sequence records as tuples (temperature, topp, u,
     forced list, max_new, stop token)); ValueError for anything rama_q8_decode_batch_begin would refuse.  No library call."""
     engines = list(engines)
-    n = len(engines)
     what = "decode_batch_chained"
-    if not 1 <= n <= MAX_BATCH:
-        raise ValueError(f"{what}: {n} sequences, not 1..{MAX_BATCH}")
-    if len(tokens) != n or len(positions) != n:
-        raise ValueError(f"{what}: {len(tokens)} tokens and {len(positions)} positions for {n} sequences")
-    e0 = engines[0]
-    if any(e.model is not e0.model for e in engines):
-        raise ValueError(f"{what}: the engines do not share one Q8Model")
-    if len({id(e) for e in engines}) != n:
-        raise ValueError(f"{what}: an engine appears twice")
+    _check_batch(what, engines, tokens, positions)
+    n, e0 = len(engines), engines[0]
     n_steps = int(n_steps)
     if n_steps < 1:
         raise ValueError(f"{what}: n_steps {n_steps} < 1")
@@ -267,18 +373,15 @@ def chain_plan(engines, tokens, positions, n_steps, temperature=0.0, topp=0.9, u
         raise ValueError(f"{what}: {len(prompts)} prompts for {n} sequences")
     plan = []
     for i in range(n):
-        T, P, U = float(Ts[i]), float(Ps[i]), float(Us[i])
-        if not (T >= 0.0 and 0.0 <= P <= 1.0 and 0.0 <= U < 1.0):       # (false for NaN)
-            raise ValueError(f"{what}: sequence {i}: temperature >= 0, topp in [0, 1], u in [0, 1) -- not {T}, {P}, {U}")
-        new = 0 if news[i] is None else int(news[i])
+        seq = f"{what}: sequence {i}"
+        T, P, U = _check_sampler(seq, Ts[i], Ps[i], Us[i])
+        new = 0 if news[i] is None else int(news[i])                    # (0 or None: no budget of its own, and no cap on a sampled vocabulary here)
         if new < 0:
-            raise ValueError(f"{what}: sequence {i}: max_new {new} < 0")
-        stop = -1 if stops[i] is None else int(stops[i])
-        if not -1 <= stop < V:
-            raise ValueError(f"{what}: sequence {i}: stop token {stop} outside the vocabulary [0, {V})")
+            raise ValueError(f"{seq}: max_new {new} < 0")
+        stop = _check_stop(seq, stops[i], V)
         budget = min(new, n_steps) if new else n_steps
         if not 0 <= poss[i] <= S - budget:
-            raise ValueError(f"{what}: sequence {i}: position {poss[i]} + {budget} steps outside [0, {S}]")
+            raise ValueError(f"{seq}: position {poss[i]} + {budget} steps outside [0, {S}]")
         plan.append((T, P, U, prompts[i], new, stop))
     return toks, poss, plan
 
@@ -292,46 +395,33 @@ def decode_batch_chained(engines, tokens, positions, n_steps, temperature=0.0, t
     ends after max_new tokens or on a sampled stop token, which it still returns.  on_token(sequence, index, token), when
     given, is fed from the host-visible rings (rama_q8_decode_batch_stream_poll) while the steps run, until every sequence
     has set its finished word or the steps have run.  engines[i]'s caches are advanced; its logits() are not written."""
-    from ._lib import rama_q8_seq_plan
     engines = list(engines)
     toks, poss, plan = chain_plan(engines, tokens, positions, n_steps, temperature, topp, u, prompts, max_new, stop_tokens)
     n, n_steps = len(engines), int(n_steps)
     e0 = engines[0]
     L, ctx = e0.device.lib, e0.device.ctx
     states = (rama_run_state * n)(*[e.state for e in engines])
-    forced = [(C.c_int32 * max(len(p[3]), 1))(*p[3]) for p in plan]
+    forced = [_i32(p[3]) for p in plan]
     per = (rama_q8_seq_plan * n)(*[rama_q8_seq_plan(p[0], p[1], p[2], forced[i], len(p[3]), p[4], p[5]) for i, p in enumerate(plan)])
-    check(L.rama_q8_decode_batch_begin(ctx, C.byref(e0.model.ccfg), C.byref(e0.model.weights), states, (C.c_int32 * n)(*toks),
-                                       (C.c_int32 * n)(*poss), n, n_steps, per), "rama_q8_decode_batch_begin")
+    check(L.rama_q8_decode_batch_begin(ctx, C.byref(e0.model.ccfg), C.byref(e0.model.weights), states, _i32(toks), _i32(poss), n,
+                                       n_steps, per), "rama_q8_decode_batch_begin")
     check(L.rama_q8_decode_batch_steps(ctx, n_steps), "rama_q8_decode_batch_steps")
     if on_token is not None:
-        import time
+        polls = [_ring_poll(L.rama_q8_decode_batch_stream_poll, "rama_q8_decode_batch_stream_poll", ctx, s_) for s_ in range(n)]
         seen, done = [0] * n, [False] * n
-        buf = (C.c_int32 * 64)()
-        k, fin = C.c_int(), C.c_int()
         ran = False                   # the stream has drained: one more sweep collects what is there
         while not all(done):
             progress = 0
             for s_ in range(n):
-                if done[s_]:
-                    continue
-                # the finished word is read before the ring: once it is set, every token of the sequence is there
-                check(L.rama_q8_decode_batch_stream_poll(ctx, s_, seen[s_], buf, 64, C.byref(k), C.byref(fin)), "rama_q8_decode_batch_stream_poll")
-                for i in range(k.value):
-                    on_token(s_, seen[s_] + i, int(buf[i]))
-                seen[s_] += k.value
-                progress += k.value
-                done[s_] = bool(fin.value) and k.value < 64
+                if not done[s_]:
+                    k, done[s_] = _drain(polls[s_], seen[s_], lambda i, t: on_token(s_, i, t))
+                    seen[s_] += k
+                    progress += k
             if progress or all(done):
                 continue
             if ran:
                 raise RuntimeError(f"decode_batch_chained: the steps have run but sequences {[i for i in range(n) if not done[i]]} have not finished")
-            q = L.rama_stream_query(ctx)
-            if q == 1:
-                time.sleep(0.0002)
-                continue
-            check(q, "rama_stream_query")
-            ran = True
+            ran = not _stream_busy(e0.device, 0.0002)
     out = (C.c_int32 * (n * n_steps))()
     cnt = (C.c_int32 * n)()
     check(L.rama_q8_decode_batch_tokens(ctx, out, n_steps, cnt), "rama_q8_decode_batch_tokens")
@@ -339,9 +429,6 @@ def decode_batch_chained(engines, tokens, positions, n_steps, temperature=0.0, t
 
 
 # ------------------------------------------------------------------ the serving chain: continuous batching (rama_q8_serve_*)
-
-SERVE_FREE, SERVE_PROMPT, SERVE_DECODE, SERVE_DONE = 0, 1, 2, 3
-
 
 def serve_sizes(cfg, n_slots, max_rows, max_new_cap):
     """the checked sizes of a serving chain; ValueError for what rama_q8_serve_begin would refuse as a bad size.  No library call."""
@@ -361,40 +448,25 @@ def serve_plan(cfg, context, max_new, temperature=0.0, topp=0.9, u=TOPP_U_CPU, s
     everything rama_q8_serve_admit / rama_q8_serve_admit_at would refuse in them.  No library call."""
     what = "Q8Server.submit"
     V, S = cfg.vocab_size, cfg.seq_len
-    ctx = _tokens(context, V, what)
-    if not ctx:
-        raise ValueError(f"{what}: an empty context (the caller includes BOS)")
+    ctx = _check_context(what, context, V)
     if not 0 <= int(n_cached) <= len(ctx) - 1:
         raise ValueError(f"{what}: n_cached {int(n_cached)} outside [0, n_context - 1 = {len(ctx) - 1}] (the final context position is always fed)")
-    T, P, U = float(temperature), float(topp), float(u)
-    if not (T >= 0.0 and 0.0 <= P <= 1.0 and 0.0 <= U < 1.0):       # (false for NaN)
-        raise ValueError(f"{what}: temperature >= 0, topp in [0, 1], u in [0, 1) -- not {T}, {P}, {U}")
+    T, P, U = _check_sampler(what, temperature, topp, u)
     new = int(max_new)
-    if new < 1:
-        raise ValueError(f"{what}: max_new {new} < 1")
-    if max_new_cap is not None and new > int(max_new_cap):
-        raise ValueError(f"{what}: max_new {new} beyond the server's max_new_cap {int(max_new_cap)}")
-    if len(ctx) + new > S:
-        raise ValueError(f"{what}: {len(ctx)} context tokens + {new} new ones beyond seq_len {S}")
-    stop = -1 if stop_token is None else int(stop_token)
-    if not -1 <= stop < V:
-        raise ValueError(f"{what}: stop token {stop} outside the vocabulary [0, {V})")
-    if T != 0.0 and V > 32768:
-        raise ValueError(f"{what}: a sampled plan needs vocab_size <= 32768")
+    _check_budget(what, len(ctx), new, S, max_new_cap)
+    stop = _check_stop(what, stop_token, V)
+    _check_sampled_vocab(what, T, V)
     return ctx, (T, P, U, new, stop)
 
 
 def serve_plan_step(slots, max_rows):
     """rama_q8_serve_plan_step, the scheduling rule as a pure host function: slots = (state, n_context, cursor, n_out, max_new)
     tuples -> (rows [(slot, pos, logits)] * max_rows, the slots after the step when no stop token is sampled).  No GPU."""
-    from ._lib import load, rama_q8_serve_row, rama_q8_serve_slot
-    n = len(slots)
-    arr = (rama_q8_serve_slot * max(n, 1))(*[rama_q8_serve_slot(*[int(v) for v in s]) for s in slots])
-    rows = (rama_q8_serve_row * max(int(max_rows), 1))()
+    n, table, max_rows = len(slots), _slot_table(slots), int(max_rows)
+    rows = (rama_q8_serve_row * max(max_rows, 1))()
     after = (rama_q8_serve_slot * max(n, 1))()
-    check(load().rama_q8_serve_plan_step(arr, n, int(max_rows), rows, after), "rama_q8_serve_plan_step")
-    return ([(r.slot, r.pos, r.logits) for r in rows[:int(max_rows)]],
-            [(a.state, a.n_context, a.cursor, a.n_out, a.max_new) for a in after[:n]])
+    check(load().rama_q8_serve_plan_step(table, n, max_rows, rows, after), "rama_q8_serve_plan_step")
+    return _row_table(rows, max_rows), [(a.state, a.n_context, a.cursor, a.n_out, a.max_new) for a in after[:n]]
 
 
 def common_prefix(a, b) -> int:
@@ -407,16 +479,10 @@ def common_prefix(a, b) -> int:
     return n
 
 
-MAX_DRAFT, MAX_NGRAM = 15, 4
-
-
 def serve_spec_sizes(n_draft, ngram, hint_cap):
     """the checked drafting sizes of a Q8Server; ValueError for what rama_q8_serve_begin_spec would refuse.  No library call."""
     n_draft, ngram, hint_cap = int(n_draft), int(ngram), int(hint_cap)
-    if not 0 <= n_draft <= MAX_DRAFT:
-        raise ValueError(f"Q8Server: n_draft {n_draft} outside [0, {MAX_DRAFT}]")
-    if not 1 <= ngram <= MAX_NGRAM:
-        raise ValueError(f"Q8Server: ngram {ngram} outside [1, {MAX_NGRAM}]")
+    _check_drafting("Q8Server", n_draft, ngram)
     if hint_cap < 0 or (hint_cap and not n_draft):
         raise ValueError(f"Q8Server: hint_cap {hint_cap} (>= 0, and 0 on a server without drafts)")
     return n_draft, ngram, hint_cap
@@ -427,8 +493,7 @@ def serve_spec_request(cfg, n_draft_cap, ngram, hint_cap, n_draft=None, hint=Non
     rama_q8_serve_admit_spec would refuse in them.  No library call."""
     what = "Q8Server.submit"
     K = n_draft_cap if n_draft is None else int(n_draft)
-    if not 0 <= K <= n_draft_cap:
-        raise ValueError(f"{what}: n_draft {K} outside [0, the server's n_draft = {n_draft_cap}]")
+    _check_n_draft(what, K, n_draft_cap, f"the server's n_draft = {n_draft_cap}")
     toks = [] if hint is None else _tokens(hint, cfg.vocab_size, what + " hint")
     if len(toks) > hint_cap:
         raise ValueError(f"{what}: {len(toks)} hint tokens beyond the server's hint_cap {hint_cap}")
@@ -436,143 +501,24 @@ def serve_spec_request(cfg, n_draft_cap, ngram, hint_cap, n_draft=None, hint=Non
 
 
 def serve_spec_report(r) -> dict:
-    """a rama_q8_serve_spec_report as a dict"""
-    return dict(steps=int(r.steps), rows_decode=int(r.rows_decode), rows_draft=int(r.rows_draft), rows_prompt=int(r.rows_prompt),
-                rows_idle=int(r.rows_idle), drafts_wanted=int(r.drafts_wanted), drafts_granted=int(r.drafts_granted),
-                drafts_accepted=int(r.drafts_accepted), tokens_emitted=int(r.tokens_emitted), accepted_hist=[int(v) for v in r.accepted_hist],
-                n_draft_cap=int(r.n_draft_cap), hint_cap=int(r.hint_cap), last_want=[int(v) for v in r.last_want[:r.n_slots]],
-                last_granted=[int(v) for v in r.last_granted[:r.n_slots]])
+    """a rama_q8_serve_spec_report as a dict: its counters and caps, and the last step's drafts of its n_slots slots"""
+    d = _report(r, skip=("n_slots", "max_rows"))
+    d["last_want"], d["last_granted"] = d["last_want"][:r.n_slots], d["last_granted"][:r.n_slots]
+    return d
 
 
 def serve_spec_plan_step(slots, want, max_rows):
     """rama_q8_serve_spec_plan_step, the scheduling rule with drafts as a pure host function: slots = (state, n_context, cursor,
     n_out, max_new) tuples, want = the drafts every slot has for the step -> (rows [(slot, pos, logits)] * max_rows, the drafts
     granted per slot).  No GPU."""
-    from ._lib import load, rama_q8_serve_row, rama_q8_serve_slot
     n = len(slots)
     if len(want) != n:
         raise ValueError(f"serve_spec_plan_step: {len(want)} want values for {n} slots")
-    arr = (rama_q8_serve_slot * max(n, 1))(*[rama_q8_serve_slot(*[int(v) for v in s]) for s in slots])
-    warr = (C.c_int32 * max(n, 1))(*[int(v) for v in want])
-    rows = (rama_q8_serve_row * max(int(max_rows), 1))()
+    table, warr, max_rows = _slot_table(slots), _i32([int(v) for v in want]), int(max_rows)
+    rows = (rama_q8_serve_row * max(max_rows, 1))()
     granted = (C.c_int32 * max(n, 1))()
-    check(load().rama_q8_serve_spec_plan_step(arr, n, int(max_rows), warr, rows, granted), "rama_q8_serve_spec_plan_step")
-    return [(r.slot, r.pos, r.logits) for r in rows[:int(max_rows)]], [int(g) for g in granted[:n]]
-
-
-def _spec_plan_py(slots, want, max_rows):
-    """the scheduling rule with drafts, in Python: slots = [state, n_context, cursor, ...] -> (rows, granted)"""
-    nrows = [1 if s[0] in (SERVE_PROMPT, SERVE_DECODE) else 0 for s in slots]
-    left = max_rows - sum(nrows)
-    for i, s in enumerate(slots):
-        if s[0] == SERVE_PROMPT:
-            extra = min(s[1] - s[2] - 1, left)
-            nrows[i] += extra
-            left -= extra
-    granted = [0] * len(slots)
-    for i, s in enumerate(slots):
-        granted[i] = min(want[i], left) if s[0] == SERVE_DECODE else 0
-        left -= granted[i]
-    rows = []
-    for i, s in enumerate(slots):
-        for k in range(nrows[i] + granted[i]):
-            rows.append((i, s[2] + k, 1 if s[0] == SERVE_DECODE or s[2] + k == s[1] - 1 else 0))
-    return rows + [(-1, -1, 0)] * (max_rows - len(rows)), granted
-
-
-def serve_spec_replay(requests, ref_tokens, n_slots, max_rows, use_slots=None):
-    """a whole workload of a serving chain with drafts as a pure function of its inputs, no library call.  requests = dicts with
-    context and max_new, and optionally stop_token, n_draft (0), ngram (3), hint and n_cached (0); ref_tokens[i] = the max_new
-    tokens request i produces alone (Q8Engine.generate(context[1:], ...)[len(context) - 1:], not cut at the stop token).
-    Admission: before every step the waiting requests, in order, take the slots of use_slots (default: all) that are FREE or
-    DONE, in ascending slot index.  Every step is the draft rule per DECODE slot, the scheduling rule, and the accept rule by
-    comparison with the reference tokens: row j's pick is ref[n_out + j] as long as the drafts before it were right, which is
-    all the accept rule looks at.  -> dict(steps = one dict per step: admitted [(slot, request)], rows, want, granted, accepted
-    {slot: a} for the DECODE slots, emitted {slot: n}, finished [slots]; counters = what rama_q8_serve_spec_stats reports;
-    finish_step = per request the step it finishes in; slot = per request its slot; outputs = per request its tokens)."""
-    reqs = []
-    for r, ref in zip(requests, ref_tokens):
-        ctx, new = [int(t) for t in r["context"]], int(r["max_new"])
-        if len(ref) < new:
-            raise ValueError(f"serve_spec_replay: {len(ref)} reference tokens for max_new {new}")
-        stop = r.get("stop_token")
-        reqs.append(dict(ctx=ctx, new=new, stop=-1 if stop is None else int(stop), K=int(r.get("n_draft", 0)), N=int(r.get("ngram", 3)),
-                         hint=[int(t) for t in (r.get("hint") or [])], cached=int(r.get("n_cached", 0)), ref=[int(t) for t in ref]))
-    usable = list(range(n_slots)) if use_slots is None else sorted(use_slots)
-    slots = [[SERVE_FREE, 0, 0, 0, 0] for _ in range(n_slots)]      # state, n_context, cursor, n_out, max_new
-    who, text = [None] * n_slots, [None] * n_slots
-    waiting = list(range(len(reqs)))
-    steps, finish, slot_of, outputs = [], [None] * len(reqs), [None] * len(reqs), [[] for _ in reqs]
-    cnt = dict(steps=0, rows_decode=0, rows_draft=0, rows_prompt=0, rows_idle=0, drafts_wanted=0, drafts_granted=0, drafts_accepted=0,
-               tokens_emitted=0, accepted_hist=[0] * 16)
-    while waiting or any(s[0] in (SERVE_PROMPT, SERVE_DECODE) for s in slots):
-        admitted = []
-        for i in usable:
-            if waiting and slots[i][0] in (SERVE_FREE, SERVE_DONE):
-                q = waiting.pop(0)
-                r = reqs[q]
-                slots[i] = [SERVE_PROMPT, len(r["ctx"]), r["cached"], 0, r["new"]]
-                who[i], text[i], slot_of[q] = q, list(r["ctx"]), i
-                admitted.append((i, q))
-        if not any(s[0] in (SERVE_PROMPT, SERVE_DECODE) for s in slots):
-            raise ValueError("serve_spec_replay: requests are waiting but no slot can take them")
-        want, drafts = [0] * n_slots, [[] for _ in range(n_slots)]
-        for i, s in enumerate(slots):
-            if s[0] == SERVE_DECODE and reqs[who[i]]["K"] > 0:
-                r = reqs[who[i]]
-                drafts[i] = _draft_py(r["hint"], text[i], r["K"], r["N"], s[4] - s[3] - 1)      # (n_context + max_new <= seq_len: the budget binds first)
-                want[i] = len(drafts[i])
-        rows, granted = _spec_plan_py(slots, want, max_rows)
-        used = sum(1 for r in rows if r[0] >= 0)
-        n_dec = sum(1 for s in slots if s[0] == SERVE_DECODE)
-        cnt["steps"] += 1
-        cnt["rows_decode"] += n_dec
-        cnt["rows_draft"] += sum(granted)
-        cnt["rows_prompt"] += used - n_dec - sum(granted)
-        cnt["rows_idle"] += max_rows - used
-        cnt["drafts_wanted"] += sum(want)
-        accepted, emitted, finished = {}, {}, []
-        for i, s in enumerate(slots):
-            n = sum(1 for r in rows if r[0] == i)
-            if n == 0:
-                continue
-            r = reqs[who[i]]
-            if s[0] == SERVE_PROMPT and s[2] + n < s[1]:
-                s[2] += n
-                continue
-            if s[0] == SERVE_PROMPT:
-                picks, emit = r["ref"][:1], 1
-                fin = s[4] <= 1 or picks[0] == r["stop"]
-                s[2] = s[1]
-            else:
-                d, remaining = drafts[i][:granted[i]], s[4] - s[3]
-                picks = r["ref"][s[3]:s[3] + len(d) + 1]
-                a = 0
-                while a < len(d) and picks[a] == d[a]:
-                    a += 1
-                emit = min(a + 1, remaining)
-                fin = emit >= remaining
-                for j in range(emit):
-                    if picks[j] == r["stop"]:
-                        emit, fin = j + 1, True
-                        break
-                accepted[i] = a
-                cnt["drafts_granted"] += len(d)
-                cnt["drafts_accepted"] += a
-                cnt["accepted_hist"][a] += 1
-                s[2] += emit
-            emitted[i] = emit
-            cnt["tokens_emitted"] += emit
-            text[i] += picks[:emit]
-            outputs[who[i]] += picks[:emit]
-            s[3] += emit
-            s[0] = SERVE_DONE if fin else SERVE_DECODE
-            if fin:
-                finished.append(i)
-                finish[who[i]] = len(steps)
-        steps.append(dict(admitted=admitted, rows=rows, want=want, granted=granted, accepted=accepted, emitted=emitted, finished=finished,
-                          slots=[tuple(s) for s in slots]))
-    return dict(steps=steps, counters=cnt, finish_step=finish, slot=slot_of, outputs=outputs)
+    check(load().rama_q8_serve_spec_plan_step(table, n, max_rows, warr, rows, granted), "rama_q8_serve_spec_plan_step")
+    return _row_table(rows, max_rows), granted[:n]
 
 
 class PrefixPool:
@@ -669,7 +615,8 @@ class Q8Server:
         self.rows_cached = 0                              # ... summed over the admissions
         self._req = [None] * self.n_slots                 # the handle a slot serves
         self._seen = [0] * self.n_slots
-        self._mirror = [(SERVE_FREE, 0, 0, 0, 0)] * self.n_slots      # the host's copy of the slot table (exact unless a stop token fell)
+        self._poll = [_ring_poll(L.rama_q8_serve_poll, "rama_q8_serve_poll", self.device.ctx, slot, after=(None,)) for slot in range(self.n_slots)]
+        self._mirror =[(SERVE_FREE, 0, 0, 0, 0)] * self.n_slots      # the host's copy of the slot table (exact unless a stop token fell)
         self._queue, self._results, self._finished, self._plans = [], {}, set(), {}
         self._next = 0
         self.planned = dict(steps=0, rows_decode=0, rows_prompt=0, rows_idle=0)      # the host plan's sums over the steps enqueued (none with drafts: no host plan)
@@ -714,7 +661,6 @@ class Q8Server:
         return [e for e in waiting + running if e is not None]
 
     def _admit(self):
-        from ._lib import rama_q8_serve_plan
         L, ctx = self.device.lib, self.device.ctx
         for slot in range(self.n_slots):
             if not self._queue:
@@ -736,11 +682,10 @@ class Q8Server:
                     check(L.rama_q8_kv_fork(ctx, C.byref(self.model.ccfg), C.byref(donor.state), C.byref(eng.state), 1, n_cached),
                           "rama_q8_kv_fork")
             rec = rama_q8_serve_plan(T, P, U, new, stop)
-            arr = (C.c_int32 * len(toks))(*toks)
+            arr = _i32(toks)
             if self.spec:
-                from ._lib import rama_q8_serve_spec
                 K, N, hint = self._drafts[h]
-                harr = (C.c_int32 * max(len(hint), 1))(*hint)
+                harr = _i32(hint)
                 srec = rama_q8_serve_spec(K, N, harr if hint else None, len(hint))
                 check(L.rama_q8_serve_admit_spec(ctx, slot, C.byref(eng.state), arr, len(toks), n_cached, C.byref(rec), C.byref(srec)),
                       "rama_q8_serve_admit_spec")
@@ -778,25 +723,20 @@ class Q8Server:
 
     def _collect(self, on_token=None):
         """what the rings hold: new tokens of every occupied slot; a finished occupant frees its slot"""
-        L, ctx = self.device.lib, self.device.ctx
-        buf = (C.c_int32 * 64)()
-        k, fin = C.c_int(), C.c_int()
         early = False
         for slot in range(self.n_slots):
             h = self._req[slot]
             if h is None:
                 continue
-            while True:
-                # the finished word is read before the ring: once it is set, every token of the occupant is there
-                check(L.rama_q8_serve_poll(ctx, slot, self._seen[slot], buf, 64, C.byref(k), C.byref(fin), None), "rama_q8_serve_poll")
-                for i in range(k.value):
-                    if on_token is not None:
-                        on_token(h, self._seen[slot] + i, int(buf[i]))
-                    self._results[h].append(int(buf[i]))
-                self._seen[slot] += k.value
-                if k.value < 64:
-                    break
-            if fin.value:
+            got = self._results[h]
+
+            def sink(index, token):
+                if on_token is not None:
+                    on_token(h, index, token)
+                got.append(token)
+            n, fin = _drain(self._poll[slot], self._seen[slot], sink)
+            self._seen[slot] += n
+            if fin:
                 self._finished.add(h)
                 self._req[slot] = None
                 self._retire(slot, h)
@@ -852,7 +792,6 @@ class Q8Server:
         device does not idle until the host has seen the finished word and admitted -- are enqueued at once; a DONE slot takes
         no rows, and an admission is stream-ordered behind them, so the host plan stays exact.  A stop token that ends a sequence
         earlier is seen at the next collection."""
-        import time
         if self.spec:
             return self._run_spec(on_token)
         done_in = lambda t: {i for i in range(self.n_slots) if self._req[i] is not None and t[i][0] == SERVE_DONE}
@@ -876,11 +815,8 @@ class Q8Server:
                     self._resync()
                 if all(self._req[i] is None for i in expect):
                     break
-                q = self.device.lib.rama_stream_query(self.device.ctx)
-                if q == 1:
-                    time.sleep(0.0001)
+                if _stream_busy(self.device, 0.0001):
                     continue
-                check(q, "rama_stream_query")
                 self._collect(on_token)
                 if not all(self._req[i] is None for i in expect):
                     raise RuntimeError(f"Q8Server.run: the steps have run but slots {[i for i in expect if self._req[i] is not None]} have not finished")
@@ -894,7 +830,6 @@ class Q8Server:
         next finish by that plan -- SPEC_BLOCK at most -- are enqueued, and the finished words alone say who has finished.  A request that waits is
         admitted as soon as a finished word shows, behind the steps still in flight; the device never idles past a finish by
         more than the block enqueued."""
-        import time
         while True:
             self._resync()                                # (synchronises: the block before has run)
             self._collect(on_token)
@@ -907,11 +842,8 @@ class Q8Server:
             while True:
                 self._collect(on_token)
                 self._admit()
-                q = self.device.lib.rama_stream_query(self.device.ctx)
-                if q != 1:
-                    check(q, "rama_stream_query")
+                if not _stream_busy(self.device, 0.0001):
                     break
-                time.sleep(0.0001)
 
     def _after(self, k):
         m = list(self._mirror)
@@ -934,18 +866,16 @@ class Q8Server:
     def stats(self):
         """rama_q8_serve_stats (synchronises): the device's counters, the slot table, the last step's row table; rows_cached is the
         host's sum of n_cached over the admissions (context positions taken from cached rows instead of being fed)"""
-        from ._lib import rama_q8_serve_report
         r = rama_q8_serve_report()
         check(self.device.lib.rama_q8_serve_stats(self.device.ctx, C.byref(r)), "rama_q8_serve_stats")
         spec = {}
         if self.spec:
-            from ._lib import rama_q8_serve_spec_report
             q = rama_q8_serve_spec_report()
             check(self.device.lib.rama_q8_serve_spec_stats(self.device.ctx, C.byref(q)), "rama_q8_serve_spec_stats")
             spec = dict(spec=serve_spec_report(q))
         return dict(**spec, steps=int(r.steps), graph_captures=int(r.graph_captures), rows_decode=int(r.rows_decode), rows_prompt=int(r.rows_prompt),
                     rows_idle=int(r.rows_idle), rows_cached=self.rows_cached, n_slots=int(r.n_slots), max_rows=int(r.max_rows),
-                    last_rows=[(x.slot, x.pos, x.logits) for x in r.last_rows[:r.max_rows]],
+                    last_rows=_row_table(r.last_rows, r.max_rows),
                     slots=[(s.state, s.n_context, s.cursor, s.n_out, s.max_new) for s in r.slots[:r.n_slots]],
                     generation=[int(g) for g in r.generation[:r.n_slots]])
 
@@ -967,106 +897,41 @@ def spec_plan(cfg, context, max_new, temperature=0.0, topp=0.9, u=TOPP_U_CPU, st
     n_draft, ngram)); ValueError for everything rama_q8_spec_begin would refuse in them.  No library call."""
     what = "generate_spec"
     V, S = cfg.vocab_size, cfg.seq_len
-    ctx = _tokens(context, V, what)
-    if not ctx:
-        raise ValueError(f"{what}: an empty context (the caller includes BOS)")
+    ctx = _check_context(what, context, V)
     hint_toks = [] if hint is None else _tokens(hint, V, what + " hint")
-    T, P, U = float(temperature), float(topp), float(u)
-    if not (T >= 0.0 and 0.0 <= P <= 1.0 and 0.0 <= U < 1.0):       # (false for NaN)
-        raise ValueError(f"{what}: temperature >= 0, topp in [0, 1], u in [0, 1) -- not {T}, {P}, {U}")
+    T, P, U = _check_sampler(what, temperature, topp, u)
     new, K, N = int(max_new), int(n_draft), int(ngram)
-    if new < 1:
-        raise ValueError(f"{what}: max_new {new} < 1")
-    if len(ctx) + new > S:
-        raise ValueError(f"{what}: {len(ctx)} context tokens + {new} new ones beyond seq_len {S}")
-    if not 0 <= K <= MAX_DRAFT:
-        raise ValueError(f"{what}: n_draft {K} outside [0, {MAX_DRAFT}]")
-    if not 1 <= N <= MAX_NGRAM:
-        raise ValueError(f"{what}: ngram {N} outside [1, {MAX_NGRAM}]")
-    stop = -1 if stop_token is None else int(stop_token)
-    if not -1 <= stop < V:
-        raise ValueError(f"{what}: stop token {stop} outside the vocabulary [0, {V})")
-    if T != 0.0 and V > 32768:
-        raise ValueError(f"{what}: a sampled plan needs vocab_size <= 32768")
+    _check_budget(what, len(ctx), new, S)
+    _check_drafting(what, K, N)
+    stop = _check_stop(what, stop_token, V)
+    _check_sampled_vocab(what, T, V)
     return ctx, hint_toks, (T, P, U, new, stop, K, N)
 
 
 def spec_report(r) -> dict:
     """a rama_q8_spec_report as a dict"""
-    return dict(steps=int(r.steps), graph_captures=int(r.graph_captures), rows_fed=int(r.rows_fed), drafts=int(r.drafts),
-                accepted=int(r.accepted), emitted=int(r.emitted), accepted_hist=[int(v) for v in r.accepted_hist],
-                finished=int(r.finished), n_out=int(r.n_out), cursor=int(r.cursor))
+    return _report(r)
 
 
 def spec_draft(hint, seq, n_draft, ngram, room):
     """rama_q8_spec_draft, the drafting rule as a pure host function: the tokens that follow the latest occurrence of the last
     <= ngram tokens of seq -- in hint first, then in seq itself -- at most min(n_draft, room) of them.  No GPU."""
-    from ._lib import load
     hint, seq = [int(t) for t in (hint or [])], [int(t) for t in seq]
-    harr = (C.c_int32 * max(len(hint), 1))(*hint)
-    sarr = (C.c_int32 * max(len(seq), 1))(*seq)
     out = (C.c_int32 * (MAX_DRAFT + 1))()
-    n = load().rama_q8_spec_draft(harr if hint else None, len(hint), sarr, len(seq), int(n_draft), int(ngram), int(room), out)
+    n = load().rama_q8_spec_draft(_i32(hint) if hint else None, len(hint), _i32(seq), len(seq), int(n_draft), int(ngram), int(room), out)
     if n < 0:
         check(n, "rama_q8_spec_draft")
-    return [int(out[i]) for i in range(n)]
+    return out[:n]
 
 
 def spec_accept(drafts, picks, stop_token, remaining):
     """rama_q8_spec_accept, the accept rule as a pure host function: picks = Device::sample of rows 0..len(drafts) ->
     (tokens emitted, finished).  No GPU."""
-    from ._lib import load
     drafts, picks = [int(t) for t in drafts], [int(t) for t in picks]
     if len(picks) != len(drafts) + 1:
         raise ValueError(f"spec_accept: {len(picks)} picks for {len(drafts)} drafts, not one more")
-    darr = (C.c_int32 * max(len(drafts), 1))(*drafts)
-    parr = (C.c_int32 * len(picks))(*picks)
     fin = C.c_int()
-    n = load().rama_q8_spec_accept(darr, len(drafts), parr, -1 if stop_token is None else int(stop_token), int(remaining), C.byref(fin))
+    n = load().rama_q8_spec_accept(_i32(drafts), len(drafts), _i32(picks), -1 if stop_token is None else int(stop_token), int(remaining), C.byref(fin))
     if n < 0:
         check(n, "rama_q8_spec_accept")
     return n, bool(fin.value)
-
-
-def _draft_py(hint, seq, n_draft, ngram, room):
-    cap = min(n_draft, room)
-    if cap <= 0:
-        return []
-    L = len(seq)
-    for n in range(min(ngram, L), 0, -1):
-        tail = seq[L - n:]
-        for text, hi in ((hint, len(hint)), (seq, L - 1)):          # an occurrence ends at e <= hi: in seq before L
-            for e in range(hi, n - 1, -1):
-                if text[e - n:e] == tail:
-                    return text[e:e + cap]
-    return []
-
-
-def spec_replay(ref_tokens, context, hint, n_draft, ngram, max_new, stop_token):
-    """the speculative chain's steps as a pure function of its inputs, no library call: ref_tokens = the max_new tokens the
-    sequence produces alone (Q8Engine.generate(context[1:], ...)[len(context) - 1:], not cut at the stop token) -> one
-    (n_d, a, emitted) per step up to the one that finishes the sequence.  Row j's pick is ref_tokens[emitted so far + j] as long
-    as the drafts before it were right, which is all the accept rule looks at."""
-    ref, s = [int(t) for t in ref_tokens], [int(t) for t in context]
-    hint = [int(t) for t in (hint or [])]
-    stop = -1 if stop_token is None else int(stop_token)
-    if len(ref) < max_new:
-        raise ValueError(f"spec_replay: {len(ref)} reference tokens for max_new {max_new}")
-    out, e, fin = [], 0, False
-    while not fin:
-        remaining = max_new - e
-        d = _draft_py(hint, s, n_draft, ngram, remaining - 1)
-        picks = ref[e:e + len(d) + 1]
-        a = 0
-        while a < len(d) and picks[a] == d[a]:
-            a += 1
-        emit = min(a + 1, remaining)
-        fin = emit >= remaining
-        for j in range(emit):
-            if picks[j] == stop:
-                emit, fin = j + 1, True
-                break
-        s += picks[:emit]
-        e += emit
-        out.append((len(d), a, emit))
-    return out

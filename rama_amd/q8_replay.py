@@ -1,0 +1,165 @@
+"""The Q8 chains' rules restated in plain Python, as oracles for the tests and the benchmarks: the drafting rule, the scheduling
+rule with drafts, the accept rule, and whole runs of the speculative chain and of a serving chain with drafts replayed from
+reference tokens.  No library call, nothing of rama_amd imported: rama_amd.q8 imports from here."""
+from __future__ import annotations
+
+SERVE_FREE, SERVE_PROMPT, SERVE_DECODE, SERVE_DONE = 0, 1, 2, 3
+
+
+def _draft_py(hint, seq, n_draft, ngram, room):
+    cap = min(n_draft, room)
+    if cap <= 0:
+        return []
+    L = len(seq)
+    for n in range(min(ngram, L), 0, -1):
+        tail = seq[L - n:]
+        for text, hi in ((hint, len(hint)), (seq, L - 1)):          # an occurrence ends at e <= hi: in seq before L
+            for e in range(hi, n - 1, -1):
+                if text[e - n:e] == tail:
+                    return text[e:e + cap]
+    return []
+
+
+def _accept_py(drafts, picks, remaining, stop):
+    """the accept rule: picks = Device::sample of rows 0..len(drafts), remaining = the tokens the budget still allows (>= 1) ->
+    (drafts accepted, tokens emitted, finished).  The accepted drafts and the pick behind them are emitted, cut at the budget and
+    after a stop token."""
+    a = 0
+    while a < len(drafts) and picks[a] == drafts[a]:
+        a += 1
+    emit = min(a + 1, remaining)
+    fin = emit >= remaining
+    for j in range(emit):
+        if picks[j] == stop:
+            emit, fin = j + 1, True
+            break
+    return a, emit, fin
+
+
+def _spec_plan_py(slots, want, max_rows):
+    """the scheduling rule with drafts, in Python: slots = [state, n_context, cursor, ...] -> (rows, granted)"""
+    nrows = [1 if s[0] in (SERVE_PROMPT, SERVE_DECODE) else 0 for s in slots]
+    left = max_rows - sum(nrows)
+    for i, s in enumerate(slots):
+        if s[0] == SERVE_PROMPT:
+            extra = min(s[1] - s[2] - 1, left)
+            nrows[i] += extra
+            left -= extra
+    granted = [0] * len(slots)
+    for i, s in enumerate(slots):
+        granted[i] = min(want[i], left) if s[0] == SERVE_DECODE else 0
+        left -= granted[i]
+    rows = []
+    for i, s in enumerate(slots):
+        for k in range(nrows[i] + granted[i]):
+            rows.append((i, s[2] + k, 1 if s[0] == SERVE_DECODE or s[2] + k == s[1] - 1 else 0))
+    return rows + [(-1, -1, 0)] * (max_rows - len(rows)), granted
+
+
+def spec_replay(ref_tokens, context, hint, n_draft, ngram, max_new, stop_token):
+    """the speculative chain's steps as a pure function of its inputs, no library call: ref_tokens = the max_new tokens the
+    sequence produces alone (Q8Engine.generate(context[1:], ...)[len(context) - 1:], not cut at the stop token) -> one
+    (n_d, a, emitted) per step up to the one that finishes the sequence.  Row j's pick is ref_tokens[emitted so far + j] as long
+    as the drafts before it were right, which is all the accept rule looks at."""
+    ref, s = [int(t) for t in ref_tokens], [int(t) for t in context]
+    hint = [int(t) for t in (hint or [])]
+    stop = -1 if stop_token is None else int(stop_token)
+    if len(ref) < max_new:
+        raise ValueError(f"spec_replay: {len(ref)} reference tokens for max_new {max_new}")
+    out, e, fin = [], 0, False
+    while not fin:
+        remaining = max_new - e
+        d = _draft_py(hint, s, n_draft, ngram, remaining - 1)
+        picks = ref[e:e + len(d) + 1]
+        a, emit, fin = _accept_py(d, picks, remaining, stop)
+        s += picks[:emit]
+        e += emit
+        out.append((len(d), a, emit))
+    return out
+
+
+def serve_spec_replay(requests, ref_tokens, n_slots, max_rows, use_slots=None):
+    """a whole workload of a serving chain with drafts as a pure function of its inputs, no library call.  requests = dicts with
+    context and max_new, and optionally stop_token, n_draft (0), ngram (3), hint and n_cached (0); ref_tokens[i] = the max_new
+    tokens request i produces alone (Q8Engine.generate(context[1:], ...)[len(context) - 1:], not cut at the stop token).
+    Admission: before every step the waiting requests, in order, take the slots of use_slots (default: all) that are FREE or
+    DONE, in ascending slot index.  Every step is the draft rule per DECODE slot, the scheduling rule, and the accept rule by
+    comparison with the reference tokens: row j's pick is ref[n_out + j] as long as the drafts before it were right, which is
+    all the accept rule looks at.  -> dict(steps = one dict per step: admitted [(slot, request)], rows, want, granted, accepted
+    {slot: a} for the DECODE slots, emitted {slot: n}, finished [slots]; counters = what rama_q8_serve_spec_stats reports;
+    finish_step = per request the step it finishes in; slot = per request its slot; outputs = per request its tokens)."""
+    reqs = []
+    for r, ref in zip(requests, ref_tokens):
+        ctx, new = [int(t) for t in r["context"]], int(r["max_new"])
+        if len(ref) < new:
+            raise ValueError(f"serve_spec_replay: {len(ref)} reference tokens for max_new {new}")
+        stop = r.get("stop_token")
+        reqs.append(dict(ctx=ctx, new=new, stop=-1 if stop is None else int(stop), K=int(r.get("n_draft", 0)), N=int(r.get("ngram", 3)),
+                         hint=[int(t) for t in (r.get("hint") or [])], cached=int(r.get("n_cached", 0)), ref=[int(t) for t in ref]))
+    usable = list(range(n_slots)) if use_slots is None else sorted(use_slots)
+    slots = [[SERVE_FREE, 0, 0, 0, 0] for _ in range(n_slots)]      # state, n_context, cursor, n_out, max_new
+    who, text = [None] * n_slots, [None] * n_slots
+    waiting = list(range(len(reqs)))
+    steps, finish, slot_of, outputs = [], [None] * len(reqs), [None] * len(reqs), [[] for _ in reqs]
+    cnt = dict(steps=0, rows_decode=0, rows_draft=0, rows_prompt=0, rows_idle=0, drafts_wanted=0, drafts_granted=0, drafts_accepted=0,
+               tokens_emitted=0, accepted_hist=[0] * 16)
+    while waiting or any(s[0] in (SERVE_PROMPT, SERVE_DECODE) for s in slots):
+        admitted = []
+        for i in usable:
+            if waiting and slots[i][0] in (SERVE_FREE, SERVE_DONE):
+                q = waiting.pop(0)
+                r = reqs[q]
+                slots[i] = [SERVE_PROMPT, len(r["ctx"]), r["cached"], 0, r["new"]]
+                who[i], text[i], slot_of[q] = q, list(r["ctx"]), i
+                admitted.append((i, q))
+        if not any(s[0] in (SERVE_PROMPT, SERVE_DECODE) for s in slots):
+            raise ValueError("serve_spec_replay: requests are waiting but no slot can take them")
+        want, drafts = [0] * n_slots, [[] for _ in range(n_slots)]
+        for i, s in enumerate(slots):
+            if s[0] == SERVE_DECODE and reqs[who[i]]["K"] > 0:
+                r = reqs[who[i]]
+                drafts[i] = _draft_py(r["hint"], text[i], r["K"], r["N"], s[4] - s[3] - 1)      # (n_context + max_new <= seq_len: the budget binds first)
+                want[i] = len(drafts[i])
+        rows, granted = _spec_plan_py(slots, want, max_rows)
+        used = sum(1 for r in rows if r[0] >= 0)
+        n_dec = sum(1 for s in slots if s[0] == SERVE_DECODE)
+        cnt["steps"] += 1
+        cnt["rows_decode"] += n_dec
+        cnt["rows_draft"] += sum(granted)
+        cnt["rows_prompt"] += used - n_dec - sum(granted)
+        cnt["rows_idle"] += max_rows - used
+        cnt["drafts_wanted"] += sum(want)
+        accepted, emitted, finished = {}, {}, []
+        for i, s in enumerate(slots):
+            n = sum(1 for r in rows if r[0] == i)
+            if n == 0:
+                continue
+            r = reqs[who[i]]
+            if s[0] == SERVE_PROMPT and s[2] + n < s[1]:
+                s[2] += n
+                continue
+            if s[0] == SERVE_PROMPT:
+                picks, emit = r["ref"][:1], 1
+                fin = s[4] <= 1 or picks[0] == r["stop"]
+                s[2] = s[1]
+            else:
+                d = drafts[i][:granted[i]]
+                picks = r["ref"][s[3]:s[3] + len(d) + 1]
+                a, emit, fin = _accept_py(d, picks, s[4] - s[3], r["stop"])
+                accepted[i] = a
+                cnt["drafts_granted"] += len(d)
+                cnt["drafts_accepted"] += a
+                cnt["accepted_hist"][a] += 1
+                s[2] += emit
+            emitted[i] = emit
+            cnt["tokens_emitted"] += emit
+            text[i] += picks[:emit]
+            outputs[who[i]] += picks[:emit]
+            s[3] += emit
+            s[0] = SERVE_DONE if fin else SERVE_DECODE
+            if fin:
+                finished.append(i)
+                finish[who[i]] = len(steps)
+        steps.append(dict(admitted=admitted, rows=rows, want=want, granted=granted, accepted=accepted, emitted=emitted, finished=finished,
+                          slots=[tuple(s) for s in slots]))
+    return dict(steps=steps, counters=cnt, finish_step=finish, slot=slot_of, outputs=outputs)

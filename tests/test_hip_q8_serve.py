@@ -564,3 +564,33 @@ def test_the_two_chains_alternate_on_one_context(dev, golden_dir, graph):
         for r in reqs:
             r.free()
         m.free()
+
+
+# ------------------------------------------------------------------ 9. the host's drain across a full poll
+
+def test_server_collects_more_than_one_full_poll_at_once(dev):
+    """70 tokens wait in a slot's ring when the host first looks: one poll() takes the 64 a call of rama_q8_serve_poll returns
+    and the 6 behind them, and sees the finished word only with the short call"""
+    import rama_amd
+    from rama_amd.q8 import Q8Server
+    cfg = O.Config(dim=64, hidden_dim=192, n_layers=1, n_heads=2, n_kv_heads=2, vocab_size=64, seq_len=128, shared_weight=True)
+    m = rama_amd.Q8Model.synth(dev, cfg, 64, 3)
+    twin = rama_amd.Q8Engine(dev, m)
+    srv = None
+    try:
+        ctx, new = [1, 7], 70
+        want = twin.generate(ctx[1:], 1 + new)[1:]
+        srv = Q8Server(m, 1, max_new_cap=new)
+        h = srv.submit(ctx, new)
+        srv.step(1 + new)                                     # (one row a step: two steps for the context, the second gives token 0)
+        assert dev.lib.rama_sync(dev.ctx) == 0
+        assert srv.result(h) == [] and not srv.finished(h)
+        streamed = []
+        srv.poll(on_token=lambda hh, i, t: streamed.append((hh, i, t)))
+        assert len(want) == new and srv.result(h) == want and srv.finished(h)
+        assert streamed == [(h, i, t) for i, t in enumerate(want)]
+    finally:
+        if srv is not None:
+            srv.close()
+        twin.free()
+        m.free()

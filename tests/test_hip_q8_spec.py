@@ -608,3 +608,22 @@ def test_generate_spec_equals_generate(dev, benches, which, graph):
             b.eng.generate_spec([1, 2], b.cfg.seq_len)
     finally:
         dev.lib.rama_set_graph_mode(dev.ctx, 0)
+
+
+def test_generate_spec_without_drafts_past_64_tokens(dev):
+    """n_draft = 0, 70 tokens: the wrapper looks at the ring every SPEC_BLOCK steps, so no look finds a full poll of 64 -- what
+    this shows is the drain going on from a count beyond 64"""
+    import rama_amd
+    cfg = O.Config(dim=64, hidden_dim=192, n_layers=1, n_heads=2, n_kv_heads=2, vocab_size=64, seq_len=128, shared_weight=True)
+    m = rama_amd.Q8Model.synth(dev, cfg, 64, 3)
+    eng, twin = rama_amd.Q8Engine(dev, m), rama_amd.Q8Engine(dev, m)
+    try:
+        ctx, new = [1, 7], 70
+        want = twin.generate(ctx[1:], 1 + new)[1:]
+        seen = []
+        got = eng.generate_spec(ctx, new, n_draft=0, on_token=lambda i, t: seen.append((i, t)))
+        assert len(want) == new and got == want and seen == list(enumerate(want))
+        assert eng.spec_stats["steps"] == new and eng.spec_stats["finished"] == 1
+    finally:
+        eng.free(); twin.free()
+        m.free()
