@@ -625,6 +625,40 @@ int  rama_q8_serve_admit_at(rama_ctx *ctx, int slot, const rama_run_state *state
 int  rama_q8_kv_fork(rama_ctx *ctx, const rama_config *cfg, const rama_run_state *src, const rama_run_state *dsts, int n_dst,
                      int n_rows);
 
+/* THE SERVING CHAIN IN PARITY MODE: continuous batching over an fp32 model, in the reference's rounding order.
+ * The rama_q8_serve_* entries above argument for argument, with rama_weights in place of rama_q8_weights and the same plan,
+ * slot, row and report records; rama_q8_serve_plan_step is the host rule of both chains.  Slot i's tokens are, bit for bit,
+ * parity-mode rama_generate(prompt = c[1:], steps = n - 1 + max_new, T, topp, u)[n-1:] run on that sequence alone (for
+ * c[0] == 1), cut at the stop token -- the oracle's tokens; its cache rows 0..last are that run's and nothing behind its last
+ * position is written, whatever the chunking, the neighbours, max_rows, the tile a row lands in and the graph mode.
+ * A step's pass runs the row table in tiles of 32 rows, in ascending order; idle rows come last, and a tile whose first row is
+ * idle costs its launches but streams no weight.  A state of its own: it may be live next to a Q8 serving chain on the same
+ * context, and neither chain touches the other's tables or captured step.  No prompt caching, no drafts, no pipeline.
+ *
+ * rama_serve_begin: 1 <= n_slots <= max_rows <= 128 and 1 <= max_new_cap <= seq_len - 1 (RAMA_EINVAL).  PARITY MODE ONLY:
+ *   RAMA_EUNSUP unless "ref_order" = 1 -- fast mode ("ref_order" = 0), tolerance mode (2) and bar mode (3) are out of scope --,
+ *   and for a shape or weights the parity-mode token batch does not take: no chain-order copies ("chain" / "prefill_chain" = 0,
+ *   or none can be made), dim or hidden_dim not a multiple of 16, a context too long for the attention's score buffer;
+ *   vocab_size % 4 != 0 beyond 32768.  A refusal or a failed allocation leaves a running chain untouched: the new chain is made
+ *   beside it, and success ends the previous fp32 chain.
+ * rama_serve_admit: rama_q8_serve_admit's checks in the same order (one body), the run state checked against the fp32 model;
+ *   RAMA_EUNSUP for a sampled plan on vocab_size > 32768.  Stream-ordered, the captured step untouched.
+ * rama_serve_steps: no overall limit.  RAMA_EINVAL once the model (rama_model_free) or the run state of an occupied slot
+ *   (rama_state_free before the host could see the slot DONE) is gone; RAMA_EUNSUP once the context has left parity mode.
+ * rama_serve_poll never touches the stream: tokens from.. of the slot's occupant, *finished, *generation (each may be NULL).
+ * rama_serve_tokens synchronises and copies the slot's tokens.
+ * rama_serve_stats synchronises: the device's counters, the captures so far, the slot table, the last step's row table.
+ * rama_serve_end synchronises and frees the chain; nothing to end is success. */
+int  rama_serve_begin(rama_ctx *ctx, const rama_config *cfg, const rama_weights *w, int n_slots, int max_rows, int max_new_cap);
+int  rama_serve_admit(rama_ctx *ctx, int slot, const rama_run_state *state, const int32_t *context_host, int n_context,
+                      const rama_q8_serve_plan *plan);
+int  rama_serve_steps(rama_ctx *ctx, int n_steps);
+int  rama_serve_poll(rama_ctx *ctx, int slot, int from, int32_t *out_tokens_host, int max_tokens, int *n_ready, int *finished,
+                     int *generation);
+int  rama_serve_tokens(rama_ctx *ctx, int slot, int32_t *out_host, int max_tokens, int *n);
+int  rama_serve_stats(rama_ctx *ctx, rama_q8_serve_report *out);
+int  rama_serve_end(rama_ctx *ctx);
+
 /* THE SPECULATIVE CHAIN: one-stream Q8 decode that drafts by n-gram lookup and verifies in one pass.  A third
  * chain next to the two above, with a state of its own, for ONE sequence.  A token-batch pass over rows at consecutive positions
  * of one sequence leaves every row the cache rows and logits of its own rama_q8_forward, and a pass of up to 16 rows costs about

@@ -260,6 +260,17 @@ extern "C" {
     pub fn rama_q8_serve_plan_step(slots: *const rama_q8_serve_slot, n_slots: c_int, max_rows: c_int, rows_out: *mut rama_q8_serve_row,
                                    slots_after: *mut rama_q8_serve_slot) -> c_int;
     pub fn rama_q8_serve_end(ctx: *mut rama_ctx) -> c_int;
+    // the serving chain of an fp32 model in parity mode: the same arguments and records, rama_weights for the model
+    pub fn rama_serve_begin(ctx: *mut rama_ctx, cfg: *const rama_config, w: *const rama_weights, n_slots: c_int, max_rows: c_int,
+                            max_new_cap: c_int) -> c_int;
+    pub fn rama_serve_admit(ctx: *mut rama_ctx, slot: c_int, state: *const rama_run_state, context_host: *const i32, n_context: c_int,
+                            plan: *const rama_q8_serve_plan) -> c_int;
+    pub fn rama_serve_steps(ctx: *mut rama_ctx, n_steps: c_int) -> c_int;
+    pub fn rama_serve_poll(ctx: *mut rama_ctx, slot: c_int, from: c_int, out_tokens_host: *mut i32, max_tokens: c_int,
+                           n_ready: *mut c_int, finished: *mut c_int, generation: *mut c_int) -> c_int;
+    pub fn rama_serve_tokens(ctx: *mut rama_ctx, slot: c_int, out_host: *mut i32, max_tokens: c_int, n: *mut c_int) -> c_int;
+    pub fn rama_serve_stats(ctx: *mut rama_ctx, out: *mut rama_q8_serve_report) -> c_int;
+    pub fn rama_serve_end(ctx: *mut rama_ctx) -> c_int;
     // the speculative chain: one sequence, n-gram lookup drafts verified in one pass; _draft and _accept are host-only
     pub fn rama_q8_spec_begin(ctx: *mut rama_ctx, cfg: *const rama_config, w: *const rama_q8_weights, state: *const rama_run_state,
                               context_host: *const i32, n_context: c_int, plan: *const rama_q8_spec_plan) -> c_int;

@@ -11,3 +11,4 @@ from .transformer import (Config, Hip, HipSlice, MutView, RunState, RunStateView
                           forward_fused, generate, generate_device, generate_greedy_device)
 from .engine import Engine, Model, algorithmic_bytes, decode_batch, decode_batch_chained, sample_topp_batch  # noqa: F401
 from .q8 import Q8Engine, Q8Model, Q8Server  # noqa: F401
+from .server import Server  # noqa: F401

@@ -234,6 +234,14 @@ SIGNATURES = {
     "rama_q8_serve_stats": (_int, [_vp, C.POINTER(rama_q8_serve_report)]),
     "rama_q8_serve_plan_step": (_int, [C.POINTER(rama_q8_serve_slot), _int, _int, C.POINTER(rama_q8_serve_row), C.POINTER(rama_q8_serve_slot)]),
     "rama_q8_serve_end": (_int, [_vp]),
+    # the fp32 serving chain (parity mode): the same arguments with rama_weights
+    "rama_serve_begin": (_int, [_vp, _cfgp, C.POINTER(rama_weights), _int, _int, _int]),
+    "rama_serve_admit": (_int, [_vp, _int, _sp, i32p, _int, C.POINTER(rama_q8_serve_plan)]),
+    "rama_serve_steps": (_int, [_vp, _int]),
+    "rama_serve_poll": (_int, [_vp, _int, _int, i32p, _int, C.POINTER(_int), C.POINTER(_int), C.POINTER(_int)]),
+    "rama_serve_tokens": (_int, [_vp, _int, i32p, _int, C.POINTER(_int)]),
+    "rama_serve_stats": (_int, [_vp, C.POINTER(rama_q8_serve_report)]),
+    "rama_serve_end": (_int, [_vp]),
     "rama_q8_spec_begin": (_int, [_vp, _cfgp, C.POINTER(rama_q8_weights), _sp, i32p, _int, C.POINTER(rama_q8_spec_plan)]),
     "rama_q8_spec_steps": (_int, [_vp, _int]),
     "rama_q8_spec_poll": (_int, [_vp, _int, i32p, _int, C.POINTER(_int), C.POINTER(_int)]),

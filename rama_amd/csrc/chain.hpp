@@ -459,8 +459,12 @@ __device__ __forceinline__ float seq_sum_cascade(const float* a, int n, FastSumS
     return sum;
 }
 // (a grid of several workgroups: vector b of a token batch, `stride` floats after the one before it)
-__global__ __launch_bounds__(kNormThreads) void rmsnorm_chain_kernel(float* o, const float* x, const float* w, int n, float* copy_to, int stride = 0) {
+// (tile: the rows of the serving chain's step this launch stands for, rama_api.hip serve_pass -- idle rows come last in that table, so a tile whose FIRST row
+// is idle has no row anybody wants and every workgroup leaves before its first load.  One scalar load and compare on a kernel argument; NULL: no table)
+__global__ __launch_bounds__(kNormThreads) void rmsnorm_chain_kernel(float* o, const float* x, const float* w, int n, float* copy_to, int stride = 0,
+                                                                     const SeqSlot* tile = nullptr) {
     RAMA_NO_CONTRACT
+    if (tile && tile[0].pos < 0) return;
     o += (size_t)blockIdx.x * stride; x += (size_t)blockIdx.x * stride;
     extern __shared__ __attribute__((aligned(16))) float s_sq[];
     __shared__ SeqSumShared<kNormWaves> sh;
@@ -1017,6 +1021,9 @@ __global__ __launch_bounds__(kGcThreads) void gemm_chain_kernel(GemmChainParams 
     extern __shared__ __attribute__((aligned(16))) float gsm[];
     f4* wl = reinterpret_cast<f4*>(gsm);                         // [2][kGcBlocks * 64] weights, chain order
     float* xl = gsm + 2 * kGcBlocks * 256;                       // [2][T][kGcBlocks * 16] activations, chain order per token
+    // a tile of the serving chain's step that nobody wants (rmsnorm_chain_kernel above: idle rows come last, so the first row tells): gone before the
+    // first weight request.  p.seqs is a kernel argument: one scalar load and compare, the same for every lane
+    if (p.seqs && p.seqs[0].pos < 0) return;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int groups = (p.rows + 15) >> 4;
@@ -1171,6 +1178,7 @@ __global__ __launch_bounds__(kGcThreads) void gemm_chain_kernel(GemmChainParams 
             }
         } else if (EPI == CEPI_QKV) {
             const int pos = p.seqs ? p.seqs[t].pos : p.pos0 + t;
+            if (pos < 0) continue;                               // an idle row (null bases): no RoPE table entry read, nothing written (uniform per wave)
             float* kcl = p.seqs ? p.seqs[t].kc + p.layer_off : p.kc;
             float* vcl = p.seqs ? p.seqs[t].vc + p.layer_off : p.vc;
             float out = d;

@@ -155,9 +155,9 @@ int launch_chain(rama_ctx* c, ChainParams& p, int epi, int norm) {
     return fail(RAMA_EINVAL, "chain-order matvec: no launch for this epilogue and norm", __FILE__, __LINE__);
 }
 bool rmsnorm_chain_ok(size_t n) { return n <= (size_t)kNormMax && (n + (n >> 5) + 2) * sizeof(float) <= 64 * 1024; }
-int launch_rmsnorm_chain(rama_ctx* c, float* o, const float* x, const float* w, int n, float* copy_to, int batch, int stride) {
+int launch_rmsnorm_chain(rama_ctx* c, float* o, const float* x, const float* w, int n, float* copy_to, int batch, int stride, const SeqSlot* tile) {
     const size_t lds = ((size_t)n + ((size_t)n >> 5) + 2) * sizeof(float);
-    RAMA_LAUNCH(c, rmsnorm_chain_kernel, dim3(batch), dim3(kNormThreads), lds, o, x, w, n, copy_to, stride);
+    RAMA_LAUNCH(c, rmsnorm_chain_kernel, dim3(batch), dim3(kNormThreads), lds, o, x, w, n, copy_to, stride, tile);
     LAUNCHCHK();
     return 0;
 }

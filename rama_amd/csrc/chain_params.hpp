@@ -51,6 +51,7 @@ struct GemmChainParams {
     int n_tok;
     int pos0; const float* fr; const float* fi; int head_size; float* kc; float* vc;      // QKV: token t sits at pos0 + t; this layer's cache slabs
     const SeqSlot* seqs; size_t layer_off;   // QKV, independent sequences: token t at seqs[t].pos, its caches at seqs[t].kc / .vc + layer_off
+                                             // (every epilogue: the launch returns at once when seqs[0].pos < 0 -- an idle tile of the serving chain, chain.hpp)
     int lane_reduce;        // [r6] as ChainParams::lane_reduce
 };
 constexpr int kGcWaves = 4, kGcThreads = kGcWaves * 64;

@@ -279,14 +279,15 @@ struct rama_ctx {
         int* forced = nullptr; size_t forced_cap = 0;
         std::vector<rama_run_state> states;
     } q8c;
-    // rama_q8_serve_begin / _admit / _steps: the serving chain (q8_serve.hpp), a state of its own next to the chain above
-    struct Q8Serve : Q8ChainBase {
+    // What a serving chain keeps whatever its model (q8_api.hip serve_state_* / serve_admit_*): the geometry, the device tables, the admission records,
+    // the host-visible rings and the host's view of the slots.  The Q8 chain and the fp32 chain below each have one; they share procedures, not state.
+    struct ServeState {
         int n_slots = 0, max_rows = 0, out_cap = 0;       // n_slots 0: no serving chain
         bool sampler = false;              // a step runs the batched sampler's ordering launches (vocab_size <= 32768)
         ServeTables t{};                   // the device tables (ring / done: the device addresses of the two below)
         char* blob = nullptr;              // ... all of them, one allocation
         char* stage = nullptr;             // device: one admission record per slot (a ServeSlot + seq_len tokens)
-        char* pinned = nullptr;            // host-pinned: the same, what rama_q8_serve_admit fills and copies from
+        char* pinned = nullptr;            // host-pinned: the same, what an _admit entry fills and copies from
         size_t rec_bytes = 0;
         int* ring = nullptr;               // [n_slots, out_cap] host-pinned and device-mapped: token + 1, 0 = not produced yet
         int* done = nullptr;               // [n_slots] host-pinned and device-mapped: 1 = the slot's occupant has finished
@@ -294,6 +295,9 @@ struct rama_ctx {
         std::vector<char> occupied;        // per slot: admitted, and not yet seen DONE by a call that frees the slot
         std::vector<int> gen;
         unsigned long long steps = 0;
+    };
+    // rama_q8_serve_begin / _admit / _steps: the serving chain (q8_serve.hpp), a state of its own next to the chain above
+    struct Q8Serve : Q8ChainBase, ServeState {
         // rama_q8_serve_begin_spec (q8_serve_spec.hpp): drafts in the rows no slot wants; all of it unused on a chain begun without it
         bool spec = false;
         int n_draft_cap = 0, hint_cap = 0;
@@ -313,6 +317,16 @@ struct rama_ctx {
         int* words = nullptr;              // host-pinned and device-mapped: [0] tokens emitted, [1] 1 = the sequence has finished
         rama_run_state state{};
     } q8p;
+    // rama_serve_begin / _admit / _steps: the serving chain of an fp32 model in parity mode (rama_api.hip).  A state of its own: it
+    // may be live next to q8s on the same context, and neither touches the other's graph or tables.
+    struct Serve : ServeState {
+        bool live = false;                 // false once the model or the run state of an occupied slot has been freed: _admit and _steps refuse
+        rama_config cfg{}; rama_weights w{};
+        CapturedGraph cg;                  // one step, for the chain's whole life
+        unsigned long long captures = 0;
+        const float* copies[7] = {};       // the chain-order copies the captured step streams (they may be released and made again: the step is then captured again)
+        float* scratch = nullptr;          // the pass's rows, one allocation: X | XN | Q | XB | HB [max_rows], ATT [kGcMaxTok], XG | XGN [n_slots], LG [n_slots, vocab]
+    } sv;
 };
 
 // everything declared from here on is shared inside the library and kept out of its exported symbols
@@ -346,7 +360,7 @@ int launch_chain(rama_ctx* c, ChainParams& p, int epi, int norm = CNORM_NONE);
 int launch_gemm_chain(rama_ctx* c, GemmChainParams& p, int epi);
 
 bool rmsnorm_chain_ok(size_t n);      // (softmax_chain_kernel's limit too)
-int launch_rmsnorm_chain(rama_ctx* c, float* o, const float* x, const float* w, int n, float* copy_to, int batch = 1, int stride = 0);
+int launch_rmsnorm_chain(rama_ctx* c, float* o, const float* x, const float* w, int n, float* copy_to, int batch = 1, int stride = 0, const SeqSlot* tile = nullptr);
 int launch_softmax_chain(rama_ctx* c, float* x, int n);
 
 int attn_chain_waves(int head_size, bool long_ctx);
@@ -369,6 +383,41 @@ int enqueue_topp_batch_order(rama_ctx* c, const ToppRow* rows, int n_rows, const
 
 void drop_q8_graphs(rama_ctx* c, const rama_run_state* s);      // drop_graph, rama_state_free: the captured Q8 steps, all of them (s == NULL) or those over one run state
 void release_q8(rama_ctx* c);                                   // rama_ctx_destroy: the Q8 stack's allocations; the stream is idle
+
+// the serving chains' shared host layer: what rama_q8_serve_* and rama_serve_* do alike is written once in q8_api.hip, which also
+// owns q8_serve.hpp's kernels -- rama_api.hip reaches them through the launchers
+// The tables of one allocation in order, each rounded up to 256 bytes.  The same code lays a blob out twice: over no base for its size
+// (`used`), then over the allocation for the typed pointers.
+struct BlobCarver {
+    char* base = nullptr;
+    size_t used = 0;
+    template <class T> void take(T*& table, size_t count) {
+        table = base ? reinterpret_cast<T*>(base + used) : nullptr;
+        used += (count * sizeof(T) + 255) / 256 * 256;
+    }
+};
+int check_slots_rows(const char* entry, int n_slots, int max_rows);
+void serve_state_free(rama_ctx::ServeState& sv);            // the allocations; the stream is idle.  The caller resets its state
+// the tables, admission records and rings of a chain of this geometry; `more` carves further tables out of the same blob
+int serve_state_alloc(rama_ctx* c, rama_ctx::ServeState& sv, int seq_len, int n_slots, int max_rows, int max_new_cap, void (*more)(BlobCarver&, void*), void* arg);
+bool serve_slot_live(const rama_ctx::ServeState& sv, int slot);
+// an admission's refusals in their order, in the calling entry's words: the head up to the slot index, then -- behind the caller's own check of
+// the run state against its model -- the tail; then the install (the record's copy and serve_install_kernel, stream-ordered)
+struct ServeNames { const char* admit; const char* admit_at; const char* begin; };      // a chain's entries as its refusals name them
+int serve_admit_head(const ServeNames& names, const rama_ctx::ServeState& sv, bool live, int slot, const rama_run_state* state, const int32_t* context_host, const rama_q8_serve_plan* plan);
+int serve_admit_tail(const ServeNames& names, const rama_ctx::ServeState& sv, const rama_config& cfg, int slot, const rama_run_state* state, const int32_t* context_host, int n_context,
+                     int n_cached, const rama_q8_serve_plan* plan);
+int serve_admit_install(rama_ctx* c, rama_ctx::ServeState& sv, int slot, const rama_run_state* state, const int32_t* context_host, int n_context, int n_cached,
+                        const rama_q8_serve_plan* plan);
+// the run state s is about to be freed: true when a slot whose occupant the host cannot yet see DONE still uses it (a finished occupant's is its owner's again)
+bool serve_state_uses(rama_ctx::ServeState& sv, const rama_run_state* s);
+int serve_poll_ring(const char* entry, const rama_ctx::ServeState& sv, int slot, int from, int32_t* out_host, int max_tokens, int* n_ready, int* finished, int* generation);
+int serve_tokens_back(rama_ctx* c, const char* entry, const rama_ctx::ServeState& sv, int slot, int32_t* out_host, int max_tokens, int* n_out);
+int serve_report(rama_ctx* c, const rama_ctx::ServeState& sv, unsigned long long captures, const int* lflag_dev, rama_q8_serve_report* out);
+int launch_serve_schedule(rama_ctx* c, const ServeTables& t);
+int launch_serve_embed(rama_ctx* c, float* X, const float* emb, const ServeTables& t, int dim);      // rows at position -1 keep what they hold
+int launch_serve_gather(rama_ctx* c, float* XG, const float* X, const ServeTables& t, int dim);
+int launch_serve_pick(rama_ctx* c, const ServeTables& t, const float* logits, int V, bool sampled);
 
 // the pending run of recorded 1:1 ops is issued by whatever enters the library next: first statement of every entry point
 // that enqueues, synchronises or changes a setting

@@ -702,6 +702,7 @@ extern "C" int rama_model_weights(const rama_model* m, rama_weights* w) {
 extern "C" size_t rama_model_bytes(const rama_model* m) { return m ? m->blob_floats * sizeof(float) : 0; }
 
 extern "C" void rama_internal_drop_graphs(rama_ctx* ctx);      // rama_api.hip: captured graphs hold the copies' addresses
+extern "C" void rama_internal_serve_weights_gone(rama_ctx* ctx, const float* base, size_t n);      // rama_api.hip: the fp32 serving chain over these tensors is dead
 
 // Give the derived weight copies back: mask bit 0 (1) = the chain-order copy (parity mode), bit 1 (2) = the tile-order copy (token-batch
 // passes).  A server that only decodes in fast mode holds 38 GB for llama2-7B instead of up to 92.  They are made again on the
@@ -721,7 +722,7 @@ extern "C" int rama_model_free(rama_ctx* ctx, rama_model* m) {
     if (!m) return 0;
     { std::lock_guard<std::mutex> lk(g_models_mu); g_models.erase(std::remove(g_models.begin(), g_models.end(), m), g_models.end()); }      // nobody finds it any more
     { std::lock_guard<std::mutex> bl(m->build_mu); }      // ... and whoever found it before and is making a copy right now has finished
-    if (ctx) { rama_sync(ctx); rama_internal_drop_graphs(ctx); }
+    if (ctx) { rama_sync(ctx); rama_internal_drop_graphs(ctx); rama_internal_serve_weights_gone(ctx, m->blob ? m->blob : m->w.wq, m->blob ? m->blob_floats : 1); }      // (a serving chain over the model ends)
     drop_chain(ctx, m);
     if (m->w13i) {
         {

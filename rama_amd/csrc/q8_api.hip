@@ -37,11 +37,7 @@ void drop_q8_graphs(rama_ctx* c, const rama_run_state* s) {
     for (const auto& m : c->q8c.states) uses[0] = uses[0] || (s && m.key_cache == s->key_cache);
     // the serving chain's per-slot rule: the run state of a slot whose occupant the host cannot yet see DONE ends the chain -- a finished
     // occupant's is its owner's again
-    for (int i = 0; s && i < sv.n_slots; i++) {
-        if (!sv.occupied[i] || sv.states[i].key_cache != s->key_cache) continue;
-        if (__atomic_load_n(sv.done + i, __ATOMIC_ACQUIRE)) { sv.occupied[i] = 0; continue; }
-        uses[1] = true;
-    }
+    uses[1] = s && serve_state_uses(sv, s);
     const auto chains = q8_chains(c);
     for (int k = 0; k < 3; k++) {
         if (uses[k] || (!s && chains[k]->cg.exec)) (void)hipStreamSynchronize(c->stream);
@@ -69,14 +65,18 @@ extern "C" void rama_internal_drop_q8_graphs(rama_ctx* c, const rama_q8_weights*
 }
 
 // the serving chain's allocations (rama_q8_serve_begin / _end, release_q8); the stream is idle
+void serve_state_free(rama_ctx::ServeState& sv) {
+    hipFree(sv.blob); hipFree(sv.stage);
+    if (sv.pinned) hipHostFree(sv.pinned);
+    if (sv.ring) hipHostFree(sv.ring);
+    if (sv.done) hipHostFree(sv.done);
+}
 static void serve_release(rama_ctx* c) {
     auto& sv = c->q8s;
     destroy_graph(sv.cg);
-    hipFree(sv.blob); hipFree(sv.stage); hipFree(sv.sstage);
-    if (sv.pinned) hipHostFree(sv.pinned);
+    serve_state_free(sv);
+    hipFree(sv.sstage);
     if (sv.spinned) hipHostFree(sv.spinned);
-    if (sv.ring) hipHostFree(sv.ring);
-    if (sv.done) hipHostFree(sv.done);
     sv = rama_ctx::Q8Serve();
 }
 // ... and the chained batch's
@@ -223,7 +223,7 @@ static int check_drafting(const char* entry, const Plan& p, int n_draft_cap, con
     return check_tokens(entry, "hint token outside the vocabulary", p.hint, p.n_hint, V);
 }
 // the serving chain's geometry, and a slot of a slot table handed to one of the two plan functions
-static int check_slots_rows(const char* entry, int n_slots, int max_rows) {
+int check_slots_rows(const char* entry, int n_slots, int max_rows) {
     REFUSE_UNLESS(n_slots >= 1 && n_slots <= kServeMaxSlots && max_rows >= n_slots && max_rows <= kQ8bMaxTok, entry, "1 <= n_slots <= max_rows <= 128");
     return 0;
 }
@@ -500,17 +500,7 @@ int rama_q8_batch_shape_ok(const rama_config* cfg) {
     return q8_batch_ok(cfg) ? 1 : 0;
 }
 
-// The tables of one allocation in order, each rounded up to 256 bytes.  The same code lays a blob out twice: over no base for its size
-// (`used`), then over the allocation for the typed pointers.
-struct BlobCarver {
-    char* base = nullptr;
-    size_t used = 0;
-    template <class T> void take(T*& table, size_t count) {
-        table = base ? reinterpret_cast<T*>(base + used) : nullptr;
-        used += (count * sizeof(T) + 255) / 256 * 256;
-    }
-};
-
+// (BlobCarver, ctx.hpp: the tables of one allocation in order)
 static int ensure_q8_batch_scratch(rama_ctx* c, const rama_config* cfg, int gs, Q8BatchScratch* b) {
     const size_t T = kQ8bMaxTok, dim = (size_t)cfg->dim, hidden = (size_t)cfg->hidden_dim, mx = std::max(dim, hidden);
     auto lay = [&](char* base) {
@@ -989,46 +979,58 @@ static int serve_begin(rama_ctx* c, const rama_config* cfg, const rama_q8_weight
     Q8BatchScratch b{};
     rc = q8_chain_scratch(c, cfg, w->group_size, sampler ? (spec ? max_rows : n_slots) : 0, &b); if (rc) return rc;
     auto& sv = c->q8s;
-    ServeTables& t = sv.t;
     ServeSpecTables& st = sv.st;
-    const size_t S = (size_t)cfg->seq_len, N = (size_t)n_slots, R = (size_t)max_rows, cap = (size_t)max_new_cap, H = (size_t)hint_cap;
+    const size_t N = (size_t)n_slots, H = (size_t)hint_cap;
+    struct More { ServeSpecTables* st; size_t N, R, H; bool spec; } more{&st, N, (size_t)max_rows, H, spec};
+    rc = serve_state_alloc(c, sv, cfg->seq_len, n_slots, max_rows, max_new_cap, [](BlobCarver& bc, void* arg) {
+        const More& m = *static_cast<const More*>(arg);
+        if (!m.spec) return;      // the drafting tables: nothing of them on a chain begun without drafts
+        ServeSpecTables& st = *m.st;
+        bc.take(st.ss, m.N); bc.take(st.hint, m.N * m.H); bc.take(st.picks, m.R); bc.take(st.lflag, m.R); bc.take(st.rrow, m.R); bc.take(st.sums, m.N);
+        bc.take(st.sched, 2);
+    }, &more);
+    if (rc) return rc;
+    if (spec) {
+        sv.srec_bytes = (sizeof(ServeSpecSlot) + H * sizeof(int) + 255) / 256 * 256;
+        HIPCHK(hipMalloc(&sv.sstage, N * sv.srec_bytes));
+        HIPCHK(hipHostMalloc(&sv.spinned, N * sv.srec_bytes, hipHostMallocDefault));
+        st.hint_cap = hint_cap;
+    }
+    sv.cfg = *cfg; sv.w = *w; sv.sampler = sampler;
+    sv.captures = 0;
+    sv.spec = spec; sv.n_draft_cap = n_draft_cap; sv.hint_cap = hint_cap;
+    sv.live = true;
+    return 0;
+}
+
+int serve_state_alloc(rama_ctx* c, rama_ctx::ServeState& sv, int seq_len, int n_slots, int max_rows, int max_new_cap, void (*more)(BlobCarver&, void*), void* arg) {
+    ServeTables& t = sv.t;
+    const size_t S = (size_t)seq_len, N = (size_t)n_slots, R = (size_t)max_rows, cap = (size_t)max_new_cap;
     auto lay = [&](char* base) {
         BlobCarver bc{base};
         bc.take(t.slots, N); bc.take(t.ctx, N * S); bc.take(t.rows, R); bc.take(t.row_tok, R); bc.take(t.nrows, N); bc.take(t.lrow, N);
         bc.take(t.trow, N); bc.take(t.counters, 4); bc.take(t.out, N * cap);
-        if (spec) {      // the drafting tables: nothing of them on a chain begun without drafts
-            bc.take(st.ss, N); bc.take(st.hint, N * H); bc.take(st.picks, R); bc.take(st.lflag, R); bc.take(st.rrow, R); bc.take(st.sums, N);
-            bc.take(st.sched, 2);
-        }
+        if (more) more(bc, arg);
         return bc.used;
     };
     const size_t need = lay(nullptr);
     HIPCHK(hipMalloc(&sv.blob, need));
     HIPCHK(hipMemsetAsync(sv.blob, 0, need, c->stream));          // every slot FREE, the counters 0
     lay(sv.blob);
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-    sv.rec_bytes = up(sizeof(ServeSlot) + S * sizeof(int));
+    sv.rec_bytes = (sizeof(ServeSlot) + S * sizeof(int) + 255) / 256 * 256;
     HIPCHK(hipMalloc(&sv.stage, N * sv.rec_bytes));
     HIPCHK(hipHostMalloc(&sv.pinned, N * sv.rec_bytes, hipHostMallocDefault));
-    if (spec) {
-        sv.srec_bytes = up(sizeof(ServeSpecSlot) + H * sizeof(int));
-        HIPCHK(hipMalloc(&sv.sstage, N * sv.srec_bytes));
-        HIPCHK(hipHostMalloc(&sv.spinned, N * sv.srec_bytes, hipHostMallocDefault));
-        st.hint_cap = hint_cap;
-    }
     HIPCHK(hipHostMalloc(&sv.ring, sizeof(int) * N * cap, hipHostMallocMapped));
     HIPCHK(hipHostMalloc(&sv.done, sizeof(int) * N, hipHostMallocMapped));
     memset(sv.ring, 0, sizeof(int) * N * cap);
     memset(sv.done, 0, sizeof(int) * N);
     HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&t.ring), sv.ring, 0));
     HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&t.done), sv.done, 0));
-    t.seq_len = cfg->seq_len; t.n_slots = n_slots; t.max_rows = max_rows; t.out_cap = max_new_cap;
+    t.seq_len = seq_len; t.n_slots = n_slots; t.max_rows = max_rows; t.out_cap = max_new_cap;
     HIPCHK(hipStreamSynchronize(c->stream));
-    sv.cfg = *cfg; sv.w = *w; sv.sampler = sampler;
     sv.states.assign(N, rama_run_state{}); sv.occupied.assign(N, 0); sv.gen.assign(N, 0);
-    sv.steps = 0; sv.captures = 0;
-    sv.spec = spec; sv.n_draft_cap = n_draft_cap; sv.hint_cap = hint_cap;
-    sv.max_rows = max_rows; sv.out_cap = max_new_cap; sv.n_slots = n_slots; sv.live = true;
+    sv.steps = 0;
+    sv.max_rows = max_rows; sv.out_cap = max_new_cap; sv.n_slots = n_slots;
     return 0;
 }
 
@@ -1042,44 +1044,60 @@ int rama_q8_serve_begin_spec(rama_ctx* c, const rama_config* cfg, const rama_q8_
 }
 
 // the slot's occupant is still on the device's hands: admitted, and its finished word not yet set
-static bool serve_slot_live(const rama_ctx::Q8Serve& sv, int slot) {
+bool serve_slot_live(const rama_ctx::ServeState& sv, int slot) {
     return sv.occupied[slot] && !__atomic_load_n(sv.done + slot, __ATOMIC_ACQUIRE);
 }
-
-// rama_q8_serve_admit (n_cached 0) and rama_q8_serve_admit_at: the slot starts PROMPT at cursor = n_cached, over rows 0 .. n_cached - 1 that
-// earlier work on the stream has put into the run state's caches
-// spec (rama_q8_serve_admit_spec; a chain begun with rama_q8_serve_begin_spec only): the slot's drafting fields and hint; without it a slot of
-// such a chain is admitted with n_draft = 0
-static int serve_admit(rama_ctx* c, int slot, const rama_run_state* state, const int32_t* context_host, int n_context, int n_cached,
-                       const rama_q8_serve_plan* plan, const rama_q8_serve_spec* spec = nullptr) {
-    RAMA_ENTER(c);
-    REQUIRE(c && c->q8s.n_slots > 0, RAMA_EINVAL, "q8_serve_admit: call rama_q8_serve_begin first");
-    auto& sv = c->q8s;
-    // everything is checked before anything of the running chain is touched
-    REQUIRE(sv.live, RAMA_EINVAL, "q8_serve_admit: the chain's model or the run state of an occupied slot has been freed");
-    REQUIRE(state && context_host && plan, RAMA_EINVAL, "q8_serve_admit: NULL argument");
-    REQUIRE(slot >= 0 && slot < sv.n_slots, RAMA_EINVAL, "q8_serve_admit: no such slot");
-    int rc = q8_check(c, &sv.cfg, &sv.w, state); if (rc) return rc;
-    REQUIRE(!serve_slot_live(sv, slot), RAMA_EINVAL, "q8_serve_admit: the slot is busy");
-    const int V = sv.cfg.vocab_size;
-    REQUIRE(n_context >= 1, RAMA_EINVAL, "q8_serve_admit: n_context < 1");
-    REQUIRE(n_cached >= 0 && n_cached <= n_context - 1, RAMA_EINVAL, "q8_serve_admit_at: n_cached outside [0, n_context - 1] (the final context position is always fed)");
-    REQUIRE(plan->max_new >= 1, RAMA_EINVAL, "q8_serve_admit: max_new < 1");
-    REQUIRE(plan->max_new <= sv.out_cap, RAMA_EINVAL, "q8_serve_admit: max_new beyond rama_q8_serve_begin's max_new_cap");
-    REQUIRE(n_context <= sv.cfg.seq_len - plan->max_new, RAMA_EINVAL, "q8_serve_admit: n_context + max_new beyond seq_len");
-    CHECKED(check_tokens("q8_serve_admit", "token outside the vocabulary", context_host, n_context, V));
-    CHECKED(check_sampler("q8_serve_admit", plan->temperature, plan->topp, plan->u));
-    CHECKED(check_stop_token("q8_serve_admit", plan->stop_token, V));
-    for (int j = 0; j < sv.n_slots; j++)
-        REQUIRE(j == slot || !serve_slot_live(sv, j) || (sv.states[j].key_cache != state->key_cache && sv.states[j].value_cache != state->value_cache),
-                RAMA_EINVAL, "q8_serve_admit: the run state is already in a live slot");
-    REQUIRE(plan->temperature == 0.0f || sv.sampler, RAMA_EUNSUP, "q8_serve_admit: a sampled plan needs vocab_size <= 32768");
-    if (spec) {
-        REQUIRE(sv.spec, RAMA_EINVAL, "q8_serve_admit_spec: the chain was not begun with rama_q8_serve_begin_spec");
-        CHECKED(check_drafting("q8_serve_admit_spec", *spec, sv.n_draft_cap, "n_draft beyond rama_q8_serve_begin_spec's n_draft_cap", sv.hint_cap,
-                               "bad hint, or one beyond rama_q8_serve_begin_spec's hint_cap", V));
+bool serve_state_uses(rama_ctx::ServeState& sv, const rama_run_state* s) {
+    bool uses = false;
+    for (int i = 0; i < sv.n_slots; i++) {
+        if (!sv.occupied[i] || sv.states[i].key_cache != s->key_cache) continue;
+        if (__atomic_load_n(sv.done + i, __ATOMIC_ACQUIRE)) { sv.occupied[i] = 0; continue; }
+        uses = true;
     }
-    if (set_device(c)) return 1;
+    return uses;
+}
+
+// ---- an admission, for either serving chain (ctx.hpp): the refusals in the calling entry's words, then the install
+static int refuse_as(int code, const char* entry, const char* what, int line) {
+    char msg[256];
+    snprintf(msg, sizeof msg, "%s: %s", entry, what);
+    return fail(code, msg, __FILE__, line);
+}
+#define ADMIT_UNLESS(cond, what) do { if (!(cond)) return refuse_as(RAMA_EINVAL, names.admit, (what), __LINE__); } while (0)
+static const ServeNames kQ8ServeNames{"q8_serve_admit", "q8_serve_admit_at", "rama_q8_serve_begin"};
+int serve_admit_head(const ServeNames& names, const rama_ctx::ServeState& sv, bool live, int slot, const rama_run_state* state, const int32_t* context_host,
+                     const rama_q8_serve_plan* plan) {
+    // everything is checked before anything of the running chain is touched
+    ADMIT_UNLESS(live, "the chain's model or the run state of an occupied slot has been freed");
+    ADMIT_UNLESS(state && context_host && plan, "NULL argument");
+    ADMIT_UNLESS(slot >= 0 && slot < sv.n_slots, "no such slot");
+    return 0;
+}
+int serve_admit_tail(const ServeNames& names, const rama_ctx::ServeState& sv, const rama_config& cfg, int slot, const rama_run_state* state, const int32_t* context_host,
+                     int n_context, int n_cached, const rama_q8_serve_plan* plan) {
+    ADMIT_UNLESS(!serve_slot_live(sv, slot), "the slot is busy");
+    const int V = cfg.vocab_size;
+    ADMIT_UNLESS(n_context >= 1, "n_context < 1");
+    if (!(n_cached >= 0 && n_cached <= n_context - 1))
+        return refuse_as(RAMA_EINVAL, names.admit_at, "n_cached outside [0, n_context - 1] (the final context position is always fed)", __LINE__);
+    ADMIT_UNLESS(plan->max_new >= 1, "max_new < 1");
+    if (plan->max_new > sv.out_cap) {
+        char what[96];
+        snprintf(what, sizeof what, "max_new beyond %s's max_new_cap", names.begin);
+        return refuse_as(RAMA_EINVAL, names.admit, what, __LINE__);
+    }
+    ADMIT_UNLESS(n_context <= cfg.seq_len - plan->max_new, "n_context + max_new beyond seq_len");
+    CHECKED(check_tokens(names.admit, "token outside the vocabulary", context_host, n_context, V));
+    CHECKED(check_sampler(names.admit, plan->temperature, plan->topp, plan->u));
+    CHECKED(check_stop_token(names.admit, plan->stop_token, V));
+    for (int j = 0; j < sv.n_slots; j++)
+        ADMIT_UNLESS(j == slot || !serve_slot_live(sv, j) || (sv.states[j].key_cache != state->key_cache && sv.states[j].value_cache != state->value_cache),
+                     "the run state is already in a live slot");
+    if (!(plan->temperature == 0.0f || sv.sampler)) return refuse_as(RAMA_EUNSUP, names.admit, "a sampled plan needs vocab_size <= 32768", __LINE__);
+    return 0;
+}
+int serve_admit_install(rama_ctx* c, rama_ctx::ServeState& sv, int slot, const rama_run_state* state, const int32_t* context_host, int n_context, int n_cached,
+                        const rama_q8_serve_plan* plan) {
     // the slot's own pinned record: its previous copy has run (the occupant it installed has finished, or there was none)
     char* rec = sv.pinned + (size_t)slot * sv.rec_bytes;
     ServeSlot h{};
@@ -1096,6 +1114,28 @@ static int serve_admit(rama_ctx* c, int slot, const rama_run_state* state, const
     HIPCHK(hipMemcpyAsync(dst, rec, sizeof h + sizeof(int) * (size_t)n_context, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(serve_install_kernel, dim3(1), dim3(256), 0, c->stream, sv.t, slot, reinterpret_cast<const ServeSlot*>(dst));
     LAUNCHCHK();
+    return 0;
+}
+
+// rama_q8_serve_admit (n_cached 0) and rama_q8_serve_admit_at: the slot starts PROMPT at cursor = n_cached, over rows 0 .. n_cached - 1 that
+// earlier work on the stream has put into the run state's caches
+// spec (rama_q8_serve_admit_spec; a chain begun with rama_q8_serve_begin_spec only): the slot's drafting fields and hint; without it a slot of
+// such a chain is admitted with n_draft = 0
+static int serve_admit(rama_ctx* c, int slot, const rama_run_state* state, const int32_t* context_host, int n_context, int n_cached,
+                       const rama_q8_serve_plan* plan, const rama_q8_serve_spec* spec = nullptr) {
+    RAMA_ENTER(c);
+    REQUIRE(c && c->q8s.n_slots > 0, RAMA_EINVAL, "q8_serve_admit: call rama_q8_serve_begin first");
+    auto& sv = c->q8s;
+    CHECKED(serve_admit_head(kQ8ServeNames, sv, sv.live, slot, state, context_host, plan));
+    int rc = q8_check(c, &sv.cfg, &sv.w, state); if (rc) return rc;
+    CHECKED(serve_admit_tail(kQ8ServeNames, sv, sv.cfg, slot, state, context_host, n_context, n_cached, plan));
+    if (spec) {
+        REQUIRE(sv.spec, RAMA_EINVAL, "q8_serve_admit_spec: the chain was not begun with rama_q8_serve_begin_spec");
+        CHECKED(check_drafting("q8_serve_admit_spec", *spec, sv.n_draft_cap, "n_draft beyond rama_q8_serve_begin_spec's n_draft_cap", sv.hint_cap,
+                               "bad hint, or one beyond rama_q8_serve_begin_spec's hint_cap", sv.cfg.vocab_size));
+    }
+    if (set_device(c)) return 1;
+    rc = serve_admit_install(c, sv, slot, state, context_host, n_context, n_cached, plan); if (rc) return rc;
     if (sv.spec) {      // the same way, the slot's own pinned spec record
         char* srec = sv.spinned + (size_t)slot * sv.srec_bytes;
         ServeSpecSlot g{};
@@ -1170,25 +1210,47 @@ int rama_q8_kv_fork(rama_ctx* c, const rama_config* cfg, const rama_run_state* s
     return 0;
 }
 
+// q8_serve.hpp's kernels for whoever runs a serving chain's step (ctx.hpp): this translation unit instantiates them
+int launch_serve_schedule(rama_ctx* c, const ServeTables& t) {
+    hipLaunchKernelGGL(serve_schedule_kernel, dim3(1), dim3(kServeMaxSlots), 0, c->stream, t);
+    LAUNCHCHK();
+    return 0;
+}
+int launch_serve_embed(rama_ctx* c, float* X, const float* emb, const ServeTables& t, int dim) {
+    hipLaunchKernelGGL(serve_embed_rows_kernel, dim3((dim + 255) / 256, t.max_rows), dim3(256), 0, c->stream, X, emb, (const int*)t.row_tok, (const SeqSlot*)t.rows, dim);
+    LAUNCHCHK();
+    return 0;
+}
+int launch_serve_gather(rama_ctx* c, float* XG, const float* X, const ServeTables& t, int dim) {
+    hipLaunchKernelGGL(serve_gather_kernel, dim3((dim + 255) / 256, t.n_slots), dim3(256), 0, c->stream, XG, X, (const int*)t.lrow, dim);
+    LAUNCHCHK();
+    return 0;
+}
+// the pick over one logits row per slot; `sampled`: the batched sampler's ordering launches over the slots' sampler records go first
+int launch_serve_pick(rama_ctx* c, const ServeTables& t, const float* logits, int V, bool sampled) {
+    ServePickParams fin{};
+    fin.t = t;
+    fin.r = PickRows{logits, (size_t)V, V, nullptr, nullptr, nullptr, 0};
+    if (sampled) {
+        const int rc = enqueue_topp_batch_order(c, t.trow, t.n_slots, logits, (size_t)V, V, nullptr); if (rc) return rc;
+        fin.r.keys = c->tb.keys; fin.r.vals = c->tb.vals; fin.r.m = c->tb.m; fin.r.rstride = c->tb.rstride;
+    }
+    hipLaunchKernelGGL(serve_pick_kernel, dim3(t.n_slots), dim3(1024), 0, c->stream, fin);
+    LAUNCHCHK();
+    return 0;
+}
+
 // one step: the scheduler, the pass over its row table, the logits of the rows that carry them, the pick and the slots' state machine
 static int enqueue_q8_serve_step(rama_ctx* c, const Q8BatchScratch& b) {
     auto& sv = c->q8s;
     const rama_config* cfg = &sv.cfg;
     const rama_q8_weights* w = &sv.w;
-    const int dim = cfg->dim, R = sv.max_rows, N = sv.n_slots;
-    hipLaunchKernelGGL(serve_schedule_kernel, dim3(1), dim3(kServeMaxSlots), 0, c->stream, sv.t);
-    LAUNCHCHK();
-    int rc = enqueue_q8_row_layers(c, cfg, w, b, sv.t.row_tok, sv.t.rows, R); if (rc) return rc;
+    int rc = launch_serve_schedule(c, sv.t); if (rc) return rc;
+    rc = enqueue_q8_row_layers(c, cfg, w, b, sv.t.row_tok, sv.t.rows, sv.max_rows); if (rc) return rc;
     // the classifier tail for the slots' logits rows only (b.Q is free here)
-    hipLaunchKernelGGL(serve_gather_kernel, dim3((dim + 255) / 256, N), dim3(256), 0, c->stream, b.Q, (const float*)b.X, (const int*)sv.t.lrow, dim);
-    LAUNCHCHK();
-    rc = enqueue_q8_classifier(c, cfg, w, b, b.Q, N); if (rc) return rc;
-    ServePickParams fin{};
-    fin.t = sv.t;
-    rc = enqueue_q8_pick_rows(c, b, cfg->vocab_size, sv.sampler, sv.t.trow, N, &fin.r); if (rc) return rc;
-    hipLaunchKernelGGL(serve_pick_kernel, dim3(N), dim3(1024), 0, c->stream, fin);
-    LAUNCHCHK();
-    return 0;
+    rc = launch_serve_gather(c, b.Q, b.X, sv.t, cfg->dim); if (rc) return rc;
+    rc = enqueue_q8_classifier(c, cfg, w, b, b.Q, sv.n_slots); if (rc) return rc;
+    return launch_serve_pick(c, sv.t, b.LG, cfg->vocab_size, sv.sampler);
 }
 
 // one step of a chain begun with rama_q8_serve_begin_spec: the drafts, the scheduler, the pass over its row table, every row's logits, every
@@ -1225,11 +1287,10 @@ int rama_q8_serve_steps(rama_ctx* c, int n_steps) {
     return rc;
 }
 
-int rama_q8_serve_poll(rama_ctx* c, int slot, int from, int32_t* out_host, int max_tokens, int* n_ready, int* finished, int* generation) {
-    RAMA_ENTER(c);
-    REQUIRE(c && n_ready && c->q8s.n_slots > 0 && slot >= 0 && slot < c->q8s.n_slots && from >= 0 && max_tokens >= 0 && (max_tokens == 0 || out_host),
-            RAMA_EINVAL, "q8_serve_poll: bad argument");
-    const auto& sv = c->q8s;
+// ---- what either serving chain's _poll / _tokens / _stats entry does behind RAMA_ENTER (ctx.hpp)
+int serve_poll_ring(const char* entry, const rama_ctx::ServeState& sv, int slot, int from, int32_t* out_host, int max_tokens, int* n_ready, int* finished, int* generation) {
+    if (!(n_ready && sv.n_slots > 0 && slot >= 0 && slot < sv.n_slots && from >= 0 && max_tokens >= 0 && (max_tokens == 0 || out_host)))
+        return refuse_as(RAMA_EINVAL, entry, "bad argument", __LINE__);
     // the finished word first: it is stored after the occupant's last ring word, so a set word means every token is there to be read
     const int fin = __atomic_load_n(sv.done + slot, __ATOMIC_ACQUIRE);
     *n_ready = read_ring(sv.ring + (size_t)slot * sv.out_cap, sv.out_cap, from, out_host, max_tokens);
@@ -1237,38 +1298,32 @@ int rama_q8_serve_poll(rama_ctx* c, int slot, int from, int32_t* out_host, int m
     if (generation) *generation = sv.gen[slot];
     return 0;
 }
-
-int rama_q8_serve_tokens(rama_ctx* c, int slot, int32_t* out_host, int max_tokens, int* n_out) {
-    RAMA_ENTER(c);
-    REQUIRE(c && n_out && c->q8s.n_slots > 0 && slot >= 0 && slot < c->q8s.n_slots && max_tokens >= 0 && (max_tokens == 0 || out_host), RAMA_EINVAL,
-            "q8_serve_tokens: bad argument");
-    auto& sv = c->q8s;
+int serve_tokens_back(rama_ctx* c, const char* entry, const rama_ctx::ServeState& sv, int slot, int32_t* out_host, int max_tokens, int* n_out) {
+    if (!(n_out && sv.n_slots > 0 && slot >= 0 && slot < sv.n_slots && max_tokens >= 0 && (max_tokens == 0 || out_host)))
+        return refuse_as(RAMA_EINVAL, entry, "bad argument", __LINE__);
     const int rc = q8_drain(c); if (rc) return rc;
     ServeSlot s{};
     HIPCHK(hipMemcpy(&s, sv.t.slots + slot, sizeof s, hipMemcpyDeviceToHost));
     return q8_tokens_back(out_host, sv.t.out + (size_t)slot * sv.out_cap, s.n_out, sv.out_cap, max_tokens, n_out);
 }
-
-int rama_q8_serve_stats(rama_ctx* c, rama_q8_serve_report* out) {
-    RAMA_ENTER(c);
-    REQUIRE(c && out && c->q8s.n_slots > 0, RAMA_EINVAL, "q8_serve_stats: bad argument");
-    auto& sv = c->q8s;
+// lflag_dev: a chain with drafts flags its logits rows per row; NULL: a slot's logits row is lrow[slot]
+int serve_report(rama_ctx* c, const rama_ctx::ServeState& sv, unsigned long long captures, const int* lflag_dev, rama_q8_serve_report* out) {
     { const int rh = q8_drain(c); if (rh) return rh; }
     memset(out, 0, sizeof *out);
     unsigned long long cnt[4];
     ServeSlot slots[kServeMaxSlots];
     SeqSlot rows[kQ8bMaxTok];
     int lrow[kServeMaxSlots], lflag[kQ8bMaxTok];
-    if (sv.spec) HIPCHK(hipMemcpy(lflag, sv.st.lflag, sizeof(int) * sv.max_rows, hipMemcpyDeviceToHost));      // (a spec chain flags per row)
+    if (lflag_dev) HIPCHK(hipMemcpy(lflag, lflag_dev, sizeof(int) * sv.max_rows, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(cnt, sv.t.counters, sizeof cnt, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(slots, sv.t.slots, sizeof(ServeSlot) * sv.n_slots, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(rows, sv.t.rows, sizeof(SeqSlot) * sv.max_rows, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(lrow, sv.t.lrow, sizeof(int) * sv.n_slots, hipMemcpyDeviceToHost));
-    out->steps = cnt[0]; out->graph_captures = sv.captures; out->rows_decode = cnt[1]; out->rows_prompt = cnt[2]; out->rows_idle = cnt[3];
+    out->steps = cnt[0]; out->graph_captures = captures; out->rows_decode = cnt[1]; out->rows_prompt = cnt[2]; out->rows_idle = cnt[3];
     out->n_slots = sv.n_slots; out->max_rows = sv.max_rows;
     for (int r = 0; r < sv.max_rows; r++) {
         const bool on = cnt[0] > 0 && rows[r].pos >= 0;            // (before the first step the table holds nothing)
-        const bool lg = on && (sv.spec ? lflag[r] != 0 : lrow[rows[r].pad] == r);
+        const bool lg = on && (lflag_dev ? lflag[r] != 0 : lrow[rows[r].pad] == r);
         out->last_rows[r] = rama_q8_serve_row{on ? rows[r].pad : -1, on ? rows[r].pos : -1, lg ? 1 : 0};
     }
     for (int i = 0; i < sv.n_slots; i++) {
@@ -1276,6 +1331,24 @@ int rama_q8_serve_stats(rama_ctx* c, rama_q8_serve_report* out) {
         out->generation[i] = sv.gen[i];
     }
     return 0;
+}
+
+int rama_q8_serve_poll(rama_ctx* c, int slot, int from, int32_t* out_host, int max_tokens, int* n_ready, int* finished, int* generation) {
+    RAMA_ENTER(c);
+    REQUIRE(c, RAMA_EINVAL, "q8_serve_poll: bad argument");
+    return serve_poll_ring("q8_serve_poll", c->q8s, slot, from, out_host, max_tokens, n_ready, finished, generation);
+}
+
+int rama_q8_serve_tokens(rama_ctx* c, int slot, int32_t* out_host, int max_tokens, int* n_out) {
+    RAMA_ENTER(c);
+    REQUIRE(c, RAMA_EINVAL, "q8_serve_tokens: bad argument");
+    return serve_tokens_back(c, "q8_serve_tokens", c->q8s, slot, out_host, max_tokens, n_out);
+}
+
+int rama_q8_serve_stats(rama_ctx* c, rama_q8_serve_report* out) {
+    RAMA_ENTER(c);
+    REQUIRE(c && out && c->q8s.n_slots > 0, RAMA_EINVAL, "q8_serve_stats: bad argument");
+    return serve_report(c, c->q8s, c->q8s.captures, c->q8s.spec ? c->q8s.st.lflag : nullptr, out);
 }
 
 int rama_q8_serve_spec_stats(rama_ctx* c, rama_q8_serve_spec_report* out) {

@@ -92,6 +92,15 @@ __global__ __launch_bounds__(kServeMaxSlots) void serve_schedule_kernel(ServeTab
     }
 }
 
+// X[r] = token_embedding_table[row_tok[r]] for the rows of the step's table that some slot wants (the fp32 chain's pass, rama_api.hip: an idle
+// row keeps what it holds, so a tile nobody wants is not touched at all)
+__global__ void serve_embed_rows_kernel(float* X, const float* emb, const int* row_tok, const SeqSlot* rows, int dim) {
+    const int r = blockIdx.y;
+    if (rows[r].pos < 0) return;                                  // (uniform: the whole workgroup)
+    const size_t base = (size_t)row_tok[r] * dim;
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < dim; k += gridDim.x * blockDim.x) X[(size_t)r * dim + k] = emb[base + k];
+}
+
 // XG[s] = X[the slot's logits row] (row 0 for a slot without one: a harmless row the pick skips)
 __global__ void serve_gather_kernel(float* XG, const float* X, const int* lrow, int dim) {
     const int s = blockIdx.y;

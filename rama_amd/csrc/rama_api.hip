@@ -138,9 +138,12 @@ int rama_ctx_create(int device, void* hip_stream, rama_ctx** out) {
     return 0;
 }
 
+static void serve_release(rama_ctx* c);                              // the fp32 serving chain (below)
+static void serve_state_gone(rama_ctx* c, const rama_run_state* s);
 void drop_graph(rama_ctx* c) {
     destroy_graph(c->bc.cg);
     c->bc.graph_bucket = -1;
+    destroy_graph(c->sv.cg);           // (the fp32 serving chain's step: captured again by its next _steps call)
     for (auto& g : c->gc) { destroy_graph(g.cg); g = GraphCache(); }
     for (auto& e : c->sg) destroy_graph(e.g.cg);
     c->sg.clear();
@@ -163,6 +166,7 @@ int rama_ctx_destroy(rama_ctx* c) {
     hipFree(c->topp_rk); hipFree(c->topp_bm); hipFree(c->topp_approx); hipFree(c->topp_dist); hipFree(c->topp_stats);
     hipFree(c->bc.toks); hipFree(c->bc.seqs); hipFree(c->bc.out); if (c->bc.ring) hipHostFree(c->bc.ring);
     hipFree(c->bc.rows); hipFree(c->bc.forced);
+    serve_release(c);
     release_q8(c);
     hipFree(c->tb.keys); hipFree(c->tb.vals); hipFree(c->tb.bp); hipFree(c->tb.bi); hipFree(c->tb.rk); hipFree(c->tb.bm);
     hipFree(c->tb.bcount); hipFree(c->tb.stats); hipFree(c->tb.m); hipFree(c->tb.rows_dev);
@@ -1560,8 +1564,10 @@ static int run_layers_batched(rama_ctx* c, const rama_config* cfg, const rama_we
 // the layers of one pass of nt <= 16 tokens whose residual rows sit in b.X: consecutive positions p0.. of one sequence
 // (key_cache / value_cache its cache bases), or -- seqs != NULL -- token t of independent sequence t (device table)
 struct ChainBatch { float *X, *XN, *Q, *XB, *HB, *ATT; const float *cq, *ck, *cv, *co, *c13, *c2; int nw; size_t att_lds; };
+// tile: the rows are a tile of the serving chain's row table (serve_pass below) -- every launch gets the table, and returns at once when the tile's first row is idle
 static int chain_batch_layers(rama_ctx* c, const rama_config* cfg, const rama_weights* w, const ChainBatch& b, int nt, int p0,
-                              float* key_cache, float* value_cache, const SeqSlot* seqs) {
+                              float* key_cache, float* value_cache, const SeqSlot* seqs, bool tile = false) {
+    const SeqSlot* tseqs = tile ? seqs : nullptr;
     const int dim = cfg->dim, hidden = cfg->hidden_dim, hs = dim / cfg->n_heads, H = cfg->n_heads, seq = cfg->seq_len;
     const size_t dd = (size_t)dim * dim, hd = (size_t)hidden * dim;
     int rc;
@@ -1569,7 +1575,7 @@ static int chain_batch_layers(rama_ctx* c, const rama_config* cfg, const rama_we
         const size_t li = (size_t)layer, layer_off = li * seq * dim;
         float* kc = key_cache ? key_cache + layer_off : nullptr;
         float* vc = value_cache ? value_cache + layer_off : nullptr;
-        rc = launch_rmsnorm_chain(c, b.XN, b.X, w->rms_att_weight + li * dim, dim, nullptr, nt, dim); if (rc) return rc;      // infer.rs:19
+        rc = launch_rmsnorm_chain(c, b.XN, b.X, w->rms_att_weight + li * dim, dim, nullptr, nt, dim, tseqs); if (rc) return rc;      // infer.rs:19
         {   // :20-33
             GemmChainParams p{};
             p.w[0] = b.cq + li * dd; p.w[1] = b.ck + li * dd; p.w[2] = b.cv + li * dd; p.nmat = 3; p.K = dim; p.rows = dim;
@@ -1588,20 +1594,20 @@ static int chain_batch_layers(rama_ctx* c, const rama_config* cfg, const rama_we
         {   // :35-37
             GemmChainParams p{};
             p.w[0] = b.co + li * dd; p.nmat = 1; p.K = dim; p.rows = dim; p.x = b.XB; p.xstride = dim; p.n_tok = nt;
-            p.resid = b.X; p.rstride = dim;
+            p.resid = b.X; p.rstride = dim; p.seqs = tseqs;
             rc = launch_gemm_chain(c, p, CEPI_RESID); if (rc) return rc;
         }
-        rc = launch_rmsnorm_chain(c, b.XN, b.X, w->rms_ffn_weight + li * dim, dim, nullptr, nt, dim); if (rc) return rc;      // :39
+        rc = launch_rmsnorm_chain(c, b.XN, b.X, w->rms_ffn_weight + li * dim, dim, nullptr, nt, dim, tseqs); if (rc) return rc;      // :39
         {   // :41-45
             GemmChainParams p{};
             p.w[0] = b.c13 + li * 2 * hd; p.nmat = 1; p.K = dim; p.rows = 2 * hidden; p.x = b.XN; p.xstride = dim; p.n_tok = nt;
-            p.o[0] = b.HB; p.ostride = hidden;
+            p.o[0] = b.HB; p.ostride = hidden; p.seqs = tseqs;
             rc = launch_gemm_chain(c, p, CEPI_SWIGLU); if (rc) return rc;
         }
         {   // :46-47
             GemmChainParams p{};
             p.w[0] = b.c2 + li * hd; p.nmat = 1; p.K = hidden; p.rows = dim; p.x = b.HB; p.xstride = hidden; p.n_tok = nt;
-            p.resid = b.X; p.rstride = dim;
+            p.resid = b.X; p.rstride = dim; p.seqs = tseqs;
             rc = launch_gemm_chain(c, p, CEPI_RESID); if (rc) return rc;
         }
     }
@@ -1612,9 +1618,11 @@ static int chain_batch_layers(rama_ctx* c, const rama_config* cfg, const rama_we
 // shape / these weights (the caller falls back to one forward() per token).  Scratch, row-major per token: X residual
 // stream, XN its norm, Q, XB attention output, HB; att rows; token ids; the sequence table; (with_logits) LG [16][vocab]
 struct ChainScratch { ChainBatch b; int* toks; SeqSlot* seqs; float* LG; const float* ccls; };
-static int chain_batch_setup(rama_ctx* c, const rama_config* cfg, const rama_weights* w, bool with_logits, ChainScratch* out, bool* ok) {
+// the part that sizes nothing: the shape check, the chain-order copies (made when the model has none yet) and the attention's geometry -- b's weight
+// pointers, nw and att_lds, *ccls.  (the serving chain has rows of its own and asks for this alone)
+static int chain_batch_copies(rama_ctx* c, const rama_config* cfg, const rama_weights* w, bool with_logits, ChainBatch* b, const float** ccls_out, bool* ok) {
     *ok = false;
-    const int dim = cfg->dim, hidden = cfg->hidden_dim, hs = dim / cfg->n_heads, H = cfg->n_heads, seq = cfg->seq_len, V = cfg->vocab_size;
+    const int dim = cfg->dim, hidden = cfg->hidden_dim, hs = dim / cfg->n_heads, seq = cfg->seq_len, V = cfg->vocab_size;
     if (!c->tune_chain || !c->tune_prefill_chain || dim % 16 || hidden % 16 || dim > 16000 || hidden > 16000 || !attn_chain_ok(hs, seq)) return 0;
     if (!rmsnorm_chain_ok((size_t)dim)) return 0;
     int rc = ensure_chain_copy(c, cfg, w, nullptr); if (rc) return rc;
@@ -1623,6 +1631,20 @@ static int chain_batch_setup(rama_ctx* c, const rama_config* cfg, const rama_wei
     const float* c13 = rama_internal_chain_lookup(w->w1, 2 * hidden, dim), *c2 = rama_internal_chain_lookup(w->w2, dim, hidden);
     const float* ccls = with_logits ? rama_internal_chain_lookup(w->wcls, V, dim) : nullptr;
     if (!cq || !ck || !cv || !co || !c13 || !c2 || (with_logits && !ccls)) return 0;
+    const int nw = attn_chain_waves(hs, false);
+    const size_t att_lds = attn_chain_lds_bytes(hs, seq, nw);
+    REQUIRE(att_lds <= kAttnChainMaxLds, RAMA_EUNSUP, "token batch (parity mode): context too long for the score buffer");
+    *b = ChainBatch{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, cq, ck, cv, co, c13, c2, nw, att_lds};
+    *ccls_out = ccls;
+    *ok = true;
+    return 0;
+}
+static int chain_batch_setup(rama_ctx* c, const rama_config* cfg, const rama_weights* w, bool with_logits, ChainScratch* out, bool* ok) {
+    const int dim = cfg->dim, hidden = cfg->hidden_dim, H = cfg->n_heads, seq = cfg->seq_len, V = cfg->vocab_size;
+    ChainBatch cb{};
+    const float* ccls = nullptr;
+    int rc = chain_batch_copies(c, cfg, w, with_logits, &cb, &ccls, ok); if (rc || !*ok) return rc;
+    *ok = false;
     const size_t T = kGcMaxTok;
     const size_t slot_floats = (sizeof(SeqSlot) * T + sizeof(float) - 1) / sizeof(float);
     const size_t need = T * (4 * (size_t)dim + hidden) + T * (size_t)H * seq + 64 + slot_floats + 4 + (with_logits ? T * (size_t)V : 0);
@@ -1636,10 +1658,8 @@ static int chain_batch_setup(rama_ctx* c, const rama_config* cfg, const rama_wei
     out->seqs = reinterpret_cast<SeqSlot*>(out->toks + 64);                       // 8-byte aligned: every term above is a multiple of 16 floats
     out->LG = reinterpret_cast<float*>(out->toks + 64) + slot_floats + 4 - ((slot_floats) & 3);      // 16-byte aligned
     out->ccls = ccls;
-    const int nw = attn_chain_waves(hs, false);
-    const size_t att_lds = attn_chain_lds_bytes(hs, seq, nw);
-    REQUIRE(att_lds <= kAttnChainMaxLds, RAMA_EUNSUP, "token batch (parity mode): context too long for the score buffer");
-    out->b = ChainBatch{X, XN, Q, XB, HB, ATT, cq, ck, cv, co, c13, c2, nw, att_lds};
+    cb.X = X; cb.XN = XN; cb.Q = Q; cb.XB = XB; cb.HB = HB; cb.ATT = ATT;
+    out->b = cb;
     *ok = true;
     return 0;
 }
@@ -1967,6 +1987,203 @@ int rama_decode_batch_stream_poll(rama_ctx* c, int seq, int from, int32_t* out_h
             RAMA_EINVAL, "decode_batch_stream_poll: bad argument");
     *n_ready = read_ring(c->bc.ring + (size_t)seq * c->bc.out_cap, c->bc.out_cap, from, out_host, max_tokens);
     return 0;
+}
+
+// ---- THE SERVING CHAIN IN PARITY MODE (rama_serve_*): continuous batching for an fp32 model in the reference's rounding order.  The
+// tables, the scheduler, the gather, the admission and the pick are the Q8 serving chain's (q8_serve.hpp, reached through ctx.hpp's launchers and the
+// shared host layer of q8_api.hip); the pass is chain_batch_layers over the step's row table in TILES of kGcMaxTok rows, in ascending order -- a slot's
+// prompt rows may straddle a tile boundary, and the later tile's attention reads the cache rows the earlier tile's pass wrote.  Idle rows come last in
+// the table: a tile whose first row is idle costs its launches and no weight pass (chain.hpp).
+
+static void serve_release(rama_ctx* c) {
+    auto& sv = c->sv;
+    destroy_graph(sv.cg);
+    serve_state_free(sv);
+    hipFree(sv.scratch);
+    sv = rama_ctx::Serve();
+}
+// rama_state_free: the run state of a slot whose occupant the host cannot yet see DONE ends the chain
+static void serve_state_gone(rama_ctx* c, const rama_run_state* s) {
+    auto& sv = c->sv;
+    if (!sv.n_slots || !serve_state_uses(sv, s)) return;
+    (void)hipStreamSynchronize(c->stream);
+    destroy_graph(sv.cg);
+    sv.live = false;
+}
+// model.hip: the tensors in [base, base + n) are about to be freed -- a chain over them is dead
+extern "C" void rama_internal_serve_weights_gone(rama_ctx* c, const float* base, size_t n) {
+    if (!c || !c->sv.n_slots || !base) return;
+    const float* q = c->sv.w.wq;
+    if (q >= base && q < base + n) { destroy_graph(c->sv.cg); c->sv.live = false; }
+}
+
+// the pass's rows: one allocation, laid out the same way at begin and at every _steps call
+struct ServeScratch { ChainBatch b; float *XG, *XGN, *LG; const float* ccls; size_t floats; };
+static ServeScratch serve_scratch(const rama_ctx::Serve& sv, const ChainBatch& copies, const float* ccls) {
+    const rama_config& cfg = sv.cfg;
+    const size_t R = (size_t)sv.max_rows, N = (size_t)sv.n_slots, dim = (size_t)cfg.dim, hidden = (size_t)cfg.hidden_dim;
+    ServeScratch s{};
+    s.b = copies;
+    float* p = sv.scratch;
+    s.b.X = p; p += R * dim; s.b.XN = p; p += R * dim; s.b.Q = p; p += R * dim; s.b.XB = p; p += R * dim;
+    s.b.HB = p; p += R * hidden;
+    s.b.ATT = p; p += (size_t)kGcMaxTok * (size_t)cfg.n_heads * (size_t)cfg.seq_len;       // one tile's score rows: the tiles run one after the other
+    s.XG = p; p += N * dim; s.XGN = p; p += N * dim;
+    s.LG = p; p += N * (size_t)cfg.vocab_size;
+    s.ccls = ccls;
+    s.floats = (size_t)(p - sv.scratch);
+    return s;
+}
+// A hook for the tests, exported like the other rama_internal_* accessors and not in the header: where the pass keeps its rows
+// (X | XN | Q | XB | HB, max_rows rows each) -- tests/test_hip_serve.py fills an idle tile's rows with a sentinel and sees that no step writes them
+extern "C" int rama_internal_serve_scratch(rama_ctx* c, float** rows5, int* max_rows) {
+    if (!c || !c->sv.n_slots || !rows5 || !max_rows) return RAMA_EINVAL;
+    const ServeScratch s = serve_scratch(c->sv, ChainBatch{}, nullptr);
+    rows5[0] = s.b.X; rows5[1] = s.b.XN; rows5[2] = s.b.Q; rows5[3] = s.b.XB; rows5[4] = s.b.HB;
+    *max_rows = c->sv.max_rows;
+    return 0;
+}
+
+int rama_serve_end(rama_ctx* c) {
+    RAMA_ENTER(c);
+    REQUIRE(c, RAMA_EINVAL, "serve_end: ctx is NULL");
+    if (!c->sv.n_slots && !c->sv.blob) return 0;
+    if (set_device(c)) return 1;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    serve_release(c);
+    return 0;
+}
+
+int rama_serve_begin(rama_ctx* c, const rama_config* cfg, const rama_weights* w, int n_slots, int max_rows, int max_new_cap) {
+    RAMA_ENTER(c);
+    REQUIRE(c, RAMA_EINVAL, "ctx is NULL");
+    int rc = check_cfg(cfg); if (rc) return rc;
+    REQUIRE(w && w->token_embedding_table && w->rms_final_weight && w->wq && w->wcls, RAMA_EINVAL, "serve_begin: missing weights");
+    rc = check_slots_rows("serve_begin", n_slots, max_rows); if (rc) return rc;
+    REQUIRE(max_new_cap >= 1 && max_new_cap <= cfg->seq_len - 1, RAMA_EINVAL, "serve_begin: max_new_cap outside [1, seq_len - 1]");
+    REQUIRE(c->tune_ref_order == 1 && !c->tune_tol && !c->tune_bar, RAMA_EUNSUP, "serve_begin: parity mode only (\"ref_order\" = 1): no fast mode, no bar mode");
+    const int V = cfg->vocab_size;
+    const bool sampler = V > 1 && V <= kToppBlock * kToppMaxBlocks;
+    REQUIRE(sampler || V % 4 == 0, RAMA_EUNSUP, "serve_begin: vocab_size % 4 != 0 needs vocab_size <= 32768");
+    if (set_device(c)) return 1;
+    // shape, chain-order copies (made here when the model has none yet), the score buffer: what chain_batch_setup takes.  Nothing of a running chain is touched
+    ChainBatch copies{};
+    const float* ccls = nullptr;
+    bool ok = false;
+    rc = chain_batch_copies(c, cfg, w, true, &copies, &ccls, &ok); if (rc) return rc;
+    REQUIRE(ok, RAMA_EUNSUP, "serve_begin: a shape or weights the parity-mode token batch does not take (dim, hidden_dim multiples of 16; chain-order copies)");
+    if (sampler) { rc = ensure_topp_batch(c, n_slots, V); if (rc) return rc; }      // sized here, outside any capture
+    // the new chain is made beside the running one, which goes only when nothing can fail any more
+    rama_ctx::Serve fresh;
+    auto make = [&]() -> int {
+        int rm = serve_state_alloc(c, fresh, cfg->seq_len, n_slots, max_rows, max_new_cap, nullptr, nullptr); if (rm) return rm;
+        fresh.cfg = *cfg; fresh.w = *w; fresh.sampler = sampler;
+        const size_t floats = serve_scratch(fresh, copies, ccls).floats;
+        HIPCHK(hipMalloc(&fresh.scratch, floats * sizeof(float)));
+        HIPCHK(hipMemsetAsync(fresh.scratch, 0, floats * sizeof(float), c->stream));      // (an idle row is computed along in a live tile: finite values, never read by anyone)
+        HIPCHK(hipStreamSynchronize(c->stream));      // (also: nothing of the previous chain is still running)
+        return 0;
+    };
+    rc = make();
+    if (rc) { serve_state_free(fresh); hipFree(fresh.scratch); return rc; }
+    serve_release(c);
+    fresh.live = true;
+    c->sv = std::move(fresh);
+    return 0;
+}
+
+static const ServeNames kServeNames{"serve_admit", "serve_admit", "rama_serve_begin"};
+int rama_serve_admit(rama_ctx* c, int slot, const rama_run_state* state, const int32_t* context_host, int n_context, const rama_q8_serve_plan* plan) {
+    RAMA_ENTER(c);
+    REQUIRE(c && c->sv.n_slots > 0, RAMA_EINVAL, "serve_admit: call rama_serve_begin first");
+    auto& sv = c->sv;
+    int rc = serve_admit_head(kServeNames, sv, sv.live, slot, state, context_host, plan); if (rc) return rc;
+    rama_stage st{0, sv.cfg.n_layers, 1, 1};
+    rc = check_stage(&sv.cfg, &sv.w, state, &st); if (rc) return rc;
+    rc = serve_admit_tail(kServeNames, sv, sv.cfg, slot, state, context_host, n_context, 0, plan); if (rc) return rc;
+    if (set_device(c)) return 1;
+    rc = serve_admit_install(c, sv, slot, state, context_host, n_context, 0, plan); if (rc) return rc;
+    sv.states[slot] = *state; sv.occupied[slot] = 1; sv.gen[slot]++;
+    return 0;
+}
+
+// the pass over the step's row table, tile by tile in ascending order
+static int serve_pass(rama_ctx* c, const ServeScratch& s) {
+    auto& sv = c->sv;
+    const size_t dim = (size_t)sv.cfg.dim, hidden = (size_t)sv.cfg.hidden_dim;
+    for (int r0 = 0; r0 < sv.max_rows; r0 += kGcMaxTok) {
+        ChainBatch tb = s.b;
+        tb.X += r0 * dim; tb.XN += r0 * dim; tb.Q += r0 * dim; tb.XB += r0 * dim; tb.HB += r0 * hidden;
+        const int rc = chain_batch_layers(c, &sv.cfg, &sv.w, tb, std::min(kGcMaxTok, sv.max_rows - r0), 0, nullptr, nullptr, sv.t.rows + r0, true);
+        if (rc) return rc;
+    }
+    return 0;
+}
+// one step: the scheduler, the wanted rows' embeddings, the pass, the logits of the rows that carry them (infer.rs:49-51 per slot), the pick
+static int enqueue_serve_step(rama_ctx* c, const ServeScratch& s) {
+    auto& sv = c->sv;
+    const int dim = sv.cfg.dim, V = sv.cfg.vocab_size, N = sv.n_slots;
+    int rc = launch_serve_schedule(c, sv.t); if (rc) return rc;
+    rc = launch_serve_embed(c, s.b.X, sv.w.token_embedding_table, sv.t, dim); if (rc) return rc;
+    rc = serve_pass(c, s); if (rc) return rc;
+    rc = launch_serve_gather(c, s.XG, s.b.X, sv.t, dim); if (rc) return rc;
+    rc = launch_rmsnorm_chain(c, s.XGN, s.XG, sv.w.rms_final_weight, dim, nullptr, N, dim); if (rc) return rc;
+    for (int s0 = 0; s0 < N; s0 += kGcMaxTok) {
+        GemmChainParams p{};
+        p.w[0] = s.ccls; p.nmat = 1; p.K = dim; p.rows = V; p.x = s.XGN + (size_t)s0 * dim; p.xstride = dim;
+        p.o[0] = s.LG + (size_t)s0 * V; p.ostride = V; p.n_tok = std::min(kGcMaxTok, N - s0);
+        rc = launch_gemm_chain(c, p, CEPI_STORE); if (rc) return rc;
+    }
+    return launch_serve_pick(c, sv.t, s.LG, V, sv.sampler);
+}
+
+int rama_serve_steps(rama_ctx* c, int n_steps) {
+    RAMA_ENTER(c);
+    REQUIRE(c && c->sv.n_slots > 0, RAMA_EINVAL, "serve_steps: call rama_serve_begin first");
+    auto& sv = c->sv;
+    REQUIRE(sv.live, RAMA_EINVAL, "serve_steps: the chain's model or the run state of an occupied slot has been freed");
+    REQUIRE(n_steps >= 0, RAMA_EINVAL, "serve_steps: n_steps < 0");
+    REQUIRE(c->tune_ref_order == 1 && !c->tune_tol && !c->tune_bar, RAMA_EUNSUP, "serve_steps: the context has left parity mode");
+    if (set_device(c)) return 1;
+    // the chain-order copies may have been released and made again since the step was captured: it is then captured again
+    ChainBatch copies{};
+    const float* ccls = nullptr;
+    bool ok = false;
+    int rc = chain_batch_copies(c, &sv.cfg, &sv.w, true, &copies, &ccls, &ok); if (rc) return rc;
+    REQUIRE(ok, RAMA_EUNSUP, "serve_steps: the chain-order copies are gone and cannot be made (\"chain\" / \"prefill_chain\" = 0?)");
+    const float* now[7] = {copies.cq, copies.ck, copies.cv, copies.co, copies.c13, copies.c2, ccls};
+    if (memcmp(now, sv.copies, sizeof now)) { if (sv.cg.exec) HIPCHK(hipStreamSynchronize(c->stream)); destroy_graph(sv.cg); memcpy(sv.copies, now, sizeof now); }
+    if (sv.sampler) { rc = ensure_topp_batch(c, sv.n_slots, sv.cfg.vocab_size); if (rc) return rc; }
+    const ServeScratch s = serve_scratch(sv, copies, ccls);
+    c->embedded_x = nullptr; c->host_pos = -1;
+    const bool graphs = c->graph_mode && c->kp.kernel_id < 0;
+    for (int i = 0; i < n_steps; i++, sv.steps++) {
+        if (!graphs) { rc = enqueue_serve_step(c, s); if (rc) return rc; continue; }
+        if (!sv.cg.exec) {
+            rc = capture_graph(c, sv.cg, [&] { return enqueue_serve_step(c, s); }); if (rc) return rc;
+            sv.captures++;
+        }
+        rc = replay_graph(c, sv.cg); if (rc) return rc;
+    }
+    return 0;
+}
+
+int rama_serve_poll(rama_ctx* c, int slot, int from, int32_t* out_host, int max_tokens, int* n_ready, int* finished, int* generation) {
+    RAMA_ENTER(c);
+    REQUIRE(c, RAMA_EINVAL, "serve_poll: bad argument");
+    return serve_poll_ring("serve_poll", c->sv, slot, from, out_host, max_tokens, n_ready, finished, generation);
+}
+
+int rama_serve_tokens(rama_ctx* c, int slot, int32_t* out_host, int max_tokens, int* n_out) {
+    RAMA_ENTER(c);
+    REQUIRE(c, RAMA_EINVAL, "serve_tokens: bad argument");
+    return serve_tokens_back(c, "serve_tokens", c->sv, slot, out_host, max_tokens, n_out);
+}
+
+int rama_serve_stats(rama_ctx* c, rama_q8_serve_report* out) {
+    RAMA_ENTER(c);
+    REQUIRE(c && out && c->sv.n_slots > 0, RAMA_EINVAL, "serve_stats: bad argument");
+    return serve_report(c, c->sv, c->sv.captures, nullptr, out);
 }
 
 // ---- device-chained greedy decode (generate() at T == 0, mod.rs:169-206)
@@ -2412,6 +2629,7 @@ int rama_state_free(rama_ctx* c, rama_run_state* s) {
     RAMA_ENTER(c);
     REQUIRE(c && s, RAMA_EINVAL, "state_free: NULL argument");
     drop_q8_graphs(c, s);          // the Q8 steps captured over this state (the fp32 graphs: rama_set_graph_mode(0) first, as documented)
+    serve_state_gone(c, s);        // ... and the fp32 serving chain ends when a slot still on the device's hands uses it
     int rc = rama_free(c, s->x);   // x is the blob base
     memset(s, 0, sizeof *s);
     return rc;

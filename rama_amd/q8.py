@@ -430,23 +430,23 @@ def decode_batch_chained(engines, tokens, positions, n_steps, temperature=0.0, t
 
 # ------------------------------------------------------------------ the serving chain: continuous batching (rama_q8_serve_*)
 
-def serve_sizes(cfg, n_slots, max_rows, max_new_cap):
+def serve_sizes(cfg, n_slots, max_rows, max_new_cap, who="Q8Server"):
     """the checked sizes of a serving chain; ValueError for what rama_q8_serve_begin would refuse as a bad size.  No library call."""
     n_slots, max_new_cap = int(n_slots), int(max_new_cap)
     max_rows = n_slots if max_rows is None else int(max_rows)
     if not 1 <= n_slots <= MAX_BATCH:
-        raise ValueError(f"Q8Server: {n_slots} slots, not 1..{MAX_BATCH}")
+        raise ValueError(f"{who}: {n_slots} slots, not 1..{MAX_BATCH}")
     if not n_slots <= max_rows <= MAX_BATCH:
-        raise ValueError(f"Q8Server: max_rows {max_rows} outside [n_slots = {n_slots}, {MAX_BATCH}]")
+        raise ValueError(f"{who}: max_rows {max_rows} outside [n_slots = {n_slots}, {MAX_BATCH}]")
     if not 1 <= max_new_cap <= cfg.seq_len - 1:
-        raise ValueError(f"Q8Server: max_new_cap {max_new_cap} outside [1, seq_len - 1 = {cfg.seq_len - 1}]")
+        raise ValueError(f"{who}: max_new_cap {max_new_cap} outside [1, seq_len - 1 = {cfg.seq_len - 1}]")
     return n_slots, max_rows, max_new_cap
 
 
-def serve_plan(cfg, context, max_new, temperature=0.0, topp=0.9, u=TOPP_U_CPU, stop_token=None, max_new_cap=None, n_cached=0):
+def serve_plan(cfg, context, max_new, temperature=0.0, topp=0.9, u=TOPP_U_CPU, stop_token=None, max_new_cap=None, n_cached=0, who="Q8Server"):
     """the checked arguments of Q8Server.submit: (context tokens, (temperature, topp, u, max_new, stop token)); ValueError for
     everything rama_q8_serve_admit / rama_q8_serve_admit_at would refuse in them.  No library call."""
-    what = "Q8Server.submit"
+    what = who + ".submit"
     V, S = cfg.vocab_size, cfg.seq_len
     ctx = _check_context(what, context, V)
     if not 0 <= int(n_cached) <= len(ctx) - 1:
@@ -574,85 +574,73 @@ class PrefixPool:
         return out
 
 
-class Q8Server:
-    """continuous batching over one Q8Model (rama_q8_serve_begin / _admit / _steps / _poll): n_slots sequence slots share weight
-    passes of max_rows rows; a finished sequence frees its slot for the next queued request while the others run on, and a new
-    request's context is ingested in chunks next to the decoding slots.  Every request's tokens are those Q8Engine.generate gives
-    it alone.  One serving chain per device context at a time.
+class ServeLoop:
+    """What a serving chain's host loop does whatever the model: the queue, the slots' engines, the mirror of the device's slot table kept
+    by the host plan (rama_q8_serve_plan_step), the steps to the next finish, admissions behind the steps in flight, the host-visible
+    rings.  Q8Server (rama_q8_serve_*) and rama_amd.Server (rama_serve_*, parity mode) are this loop over their entries' family; a
+    subclass says how a chain begins (_begin), what engine a slot gets (_new_engine) and how a request goes in (_admit_slot)."""
 
-    Prompt caching (DESIGN.md 8.4).  submit(..., n_cached=n) admits over rows 0..n-1 that the caller's engine already holds
-    (a chat's next turn on the same engine).  prefix_cache=k keeps a pool of at most k donor engines: a request submitted with
-    retain=True leaves its engine there when it finishes, keyed by the tokens whose rows it holds; every later request is
-    matched against the pool at its admission, the longest shared prefix is forked into its engine (rama_q8_kv_fork) and the
-    slot starts at that cursor (rama_q8_serve_admit_at).  The tokens are the same with the cache on and off.
+    ABI = None         # the C entries' family: <ABI>_begin / _admit / _steps / _poll / _stats / _end
+    NAME = "ServeLoop"
+    spec = False       # with drafts the rows of a step depend on what is accepted: no host plan (Q8Server only)
 
-    Drafts (DESIGN.md 8.6).  n_draft=K > 0 begins the chain with rama_q8_serve_begin_spec: a decoding request guesses up to K
-    tokens per step by looking its last <= ngram tokens up in its own text and in the hint it was submitted with (at most
-    hint_cap tokens), the guesses take the rows of the step that no slot wants -- prompts first -- and are verified in the same
-    weight pass.  The tokens are the same with drafts on and off; n_draft=0 (the default) is the plain chain."""
+    def _call(self, name, *args):
+        entry = f"{self.ABI}_{name}"
+        check(getattr(self.device.lib, entry)(self.device.ctx, *args), entry)
 
-    def __init__(self, model: Q8Model, n_slots: int, max_rows=None, max_new_cap: int = 256, prefix_cache: int = 0, n_draft: int = 0,
-                 ngram: int = 3, hint_cap: int = 0):
-        self.n_slots, self.max_rows, self.max_new_cap = serve_sizes(model.cfg, n_slots, max_rows, max_new_cap)
-        self.n_draft, self.ngram, self.hint_cap = serve_spec_sizes(n_draft, ngram, hint_cap)
-        self.spec = self.n_draft > 0                      # n_draft == 0: the plain chain, rama_q8_serve_begin
-        self.pool = PrefixPool(prefix_cache)              # (raises before any library call)
+    def _start(self, model, n_slots, max_rows, max_new_cap):
+        """the sizes (checked before any library call), the chain's begin, the loop's books"""
+        self.n_slots, self.max_rows, self.max_new_cap = serve_sizes(model.cfg, n_slots, max_rows, max_new_cap, self.NAME)
         self.model, self.device, self.cfg = model, model.device, model.cfg
+        self._begin()
         L = self.device.lib
-        if self.spec:
-            check(L.rama_q8_serve_begin_spec(self.device.ctx, C.byref(model.ccfg), C.byref(model.weights), self.n_slots, self.max_rows,
-                                             self.max_new_cap, self.n_draft, self.hint_cap), "rama_q8_serve_begin_spec")
-        else:
-            check(L.rama_q8_serve_begin(self.device.ctx, C.byref(model.ccfg), C.byref(model.weights), self.n_slots, self.max_rows,
-                                        self.max_new_cap), "rama_q8_serve_begin")
         self._open = True
         self._own = [None] * self.n_slots                 # the server's own engine of a slot, made on first use and reused
         self._eng = [None] * self.n_slots                 # the engine the slot's occupant runs on
-        self._spare = []                                  # the server's own engines that serve nobody: evicted donors
+        self._spare = []                                  # the server's own engines that serve nobody
         self._mine = []                                   # every engine the server made (close frees them)
-        self._cached = {}                                 # handle -> the n_cached it was admitted with
-        self._drafts = {}                                 # handle -> (n_draft, ngram, hint tokens)
-        self.rows_cached = 0                              # ... summed over the admissions
         self._req = [None] * self.n_slots                 # the handle a slot serves
         self._seen = [0] * self.n_slots
-        self._poll = [_ring_poll(L.rama_q8_serve_poll, "rama_q8_serve_poll", self.device.ctx, slot, after=(None,)) for slot in range(self.n_slots)]
+        self._poll = [_ring_poll(getattr(L, self.ABI + "_poll"), self.ABI + "_poll", self.device.ctx, slot, after=(None,)) for slot in range(self.n_slots)]
         self._mirror =[(SERVE_FREE, 0, 0, 0, 0)] * self.n_slots      # the host's copy of the slot table (exact unless a stop token fell)
         self._queue, self._results, self._finished, self._plans = [], {}, set(), {}
         self._next = 0
         self.planned = dict(steps=0, rows_decode=0, rows_prompt=0, rows_idle=0)      # the host plan's sums over the steps enqueued (none with drafts: no host plan)
         self.last_rows = []                               # ... and its row table of the last one
 
+    def _begin(self):
+        self._call("begin", C.byref(self.model.ccfg), C.byref(self.model.weights), self.n_slots, self.max_rows, self.max_new_cap)
+
+    def _new_engine(self):
+        raise NotImplementedError
+
+    def _admit_slot(self, slot, h, eng, toks, rec, n_cached):
+        """the request h goes into the slot on engine eng -> the n_cached it was admitted with"""
+        self._call("admit", slot, C.byref(eng.state), _i32(toks), len(toks), C.byref(rec))
+        return 0
+
+    def _admitted(self, h, n_cached):
+        pass
+
+    def _retire(self, slot, h):
+        """a finished occupant leaves its engine"""
+        self._eng[slot] = None
+
+    def _closed(self):
+        pass
+
     # -- requests
-    def submit(self, context, max_new, temperature=0.0, topp=0.9, u=TOPP_U_CPU, stop_token=None, engine=None, n_cached=0,
-               retain=False, n_draft=None, hint=None):
-        """queue a request -> its handle.  It is admitted at once if a slot is free, else when one finishes (step / run).
-        engine: the Q8Engine whose run state the sequence uses (default: one the server owns for the slot).
-        n_cached: rows 0..n_cached-1 of `engine` already hold context[0..n_cached) -- written by work enqueued earlier on the
-        device's stream; the slot feeds the rest (at most n_context - 1: the final position is always fed).  Such a request is
-        not matched against the prefix cache.
-        retain: with a prefix cache, the engine stays behind as a donor when the request finishes (a caller's engine too: it
-        is the pool's until it is evicted).
-        n_draft, hint: on a server made with n_draft > 0, the drafts per step of this request (default: the server's; 0: none)
-        and a token list to look up in besides the request's own text (at most hint_cap tokens).  The tokens are the same
-        whatever they are."""
-        ctx, plan = serve_plan(self.cfg, context, max_new, temperature, topp, u, stop_token, self.max_new_cap, n_cached)
-        draft = serve_spec_request(self.cfg, self.n_draft, self.ngram, self.hint_cap, n_draft, hint)
-        n_cached = int(n_cached)
-        if n_cached and engine is None:
-            raise ValueError("Q8Server.submit: n_cached needs the engine that holds the rows")
+    def _submit(self, ctx, plan, engine, n_cached=0, retain=False):
+        """a checked request joins the queue -> its handle"""
         if engine is not None and engine.model is not self.model:
-            raise ValueError("Q8Server.submit: the engine belongs to another Q8Model")
+            raise ValueError(f"{self.NAME}.submit: the engine belongs to another {type(self.model).__name__}")
         if engine is not None and any(e is engine for e in self._engines_in_use()):
-            raise ValueError("Q8Server.submit: the engine already serves a queued or running request")
-        if engine is not None and engine in self.pool:
-            raise ValueError("Q8Server.submit: the engine is a donor of the prefix cache")
+            raise ValueError(f"{self.NAME}.submit: the engine already serves a queued or running request")
         h = self._next
         self._next += 1
         self._plans[h] = (ctx, plan, engine, n_cached, bool(retain))
-        self._drafts[h] = draft
         self._results[h] = []
         self._queue.append(h)
-        self._admit()
         return h
 
     def _engines_in_use(self):
@@ -661,7 +649,6 @@ class Q8Server:
         return [e for e in waiting + running if e is not None]
 
     def _admit(self):
-        L, ctx = self.device.lib, self.device.ctx
         for slot in range(self.n_slots):
             if not self._queue:
                 return
@@ -673,53 +660,11 @@ class Q8Server:
                 if self._own[slot] is None:
                     self._own[slot] = self._spare.pop() if self._spare else self._new_engine()
                 eng = self._own[slot]
-            if not n_cached and len(self.pool):
-                # the donor stays in the pool whatever happens below: donors leave it in _collect only, so a fork that was
-                # enqueued and an admission that then failed find it there at the next attempt; an evicted donor is reused or
-                # freed behind the fork in stream order
-                donor, n_cached = self.pool.match(toks, self.MIN_CACHED)
-                if n_cached:
-                    check(L.rama_q8_kv_fork(ctx, C.byref(self.model.ccfg), C.byref(donor.state), C.byref(eng.state), 1, n_cached),
-                          "rama_q8_kv_fork")
-            rec = rama_q8_serve_plan(T, P, U, new, stop)
-            arr = _i32(toks)
-            if self.spec:
-                K, N, hint = self._drafts[h]
-                harr = _i32(hint)
-                srec = rama_q8_serve_spec(K, N, harr if hint else None, len(hint))
-                check(L.rama_q8_serve_admit_spec(ctx, slot, C.byref(eng.state), arr, len(toks), n_cached, C.byref(rec), C.byref(srec)),
-                      "rama_q8_serve_admit_spec")
-            elif n_cached:
-                check(L.rama_q8_serve_admit_at(ctx, slot, C.byref(eng.state), arr, len(toks), n_cached, C.byref(rec)), "rama_q8_serve_admit_at")
-            else:
-                check(L.rama_q8_serve_admit(ctx, slot, C.byref(eng.state), arr, len(toks), C.byref(rec)), "rama_q8_serve_admit")
+            n_cached = self._admit_slot(slot, h, eng, toks, rama_q8_serve_plan(T, P, U, new, stop), n_cached)
             self._queue.pop(0)
             self._req[slot], self._seen[slot], self._eng[slot] = h, 0, eng
-            self._cached[h] = n_cached
-            self.rows_cached += n_cached
+            self._admitted(h, n_cached)
             self._mirror[slot] = (SERVE_PROMPT, len(toks), n_cached, 0, new)
-
-    def _new_engine(self):
-        e = Q8Engine(self.device, self.model)
-        self._mine.append(e)
-        return e
-
-    def _retire(self, slot, h):
-        """a finished occupant: with retain and a prefix cache its engine becomes a donor, keyed by the tokens it was fed (the
-        context and every output but the last); whoever leaves the pool for it serves requests again if the server made it"""
-        toks, _, _, _, retain = self._plans[h]
-        eng, self._eng[slot] = self._eng[slot], None
-        if not retain or self.pool.k == 0:
-            return
-        if self._own[slot] is eng:
-            self._own[slot] = None
-        for e in self.pool.put(toks + self._results[h][:-1], eng):
-            if any(e is m for m in self._mine):
-                self._spare.append(e)
-
-    def cached(self, handle) -> int:
-        """the n_cached request `handle` was admitted with (None while it waits)"""
-        return self._cached.get(handle)
 
     def _collect(self, on_token=None):
         """what the rings hold: new tokens of every occupied slot; a finished occupant frees its slot"""
@@ -763,7 +708,7 @@ class Q8Server:
             self.planned["rows_prompt"] += used - dec
             self.planned["rows_idle"] += self.max_rows - used
         if n:
-            check(self.device.lib.rama_q8_serve_steps(self.device.ctx, n), "rama_q8_serve_steps")
+            self._call("steps", n)
 
     def _resync(self):
         """a stop token ended a sequence before its budget: the host's copy of the slot table is taken from the device again"""
@@ -782,8 +727,6 @@ class Q8Server:
                 break
         return k
 
-    MIN_CACHED = 2     # a shorter match is not worth a launch: every context shares its first token (BOS) with every donor
-
     LOOKAHEAD = 2      # steps enqueued past a foreseen finish while requests wait: the admission then goes in behind running steps
 
     def run(self, on_token=None):
@@ -792,8 +735,6 @@ class Q8Server:
         device does not idle until the host has seen the finished word and admitted -- are enqueued at once; a DONE slot takes
         no rows, and an admission is stream-ordered behind them, so the host plan stays exact.  A stop token that ends a sequence
         earlier is seen at the next collection."""
-        if self.spec:
-            return self._run_spec(on_token)
         done_in = lambda t: {i for i in range(self.n_slots) if self._req[i] is not None and t[i][0] == SERVE_DONE}
         while True:
             if self._collect(on_token):
@@ -803,7 +744,7 @@ class Q8Server:
             k = self._steps_to_next_finish()
             if k == 0 and not expect:
                 if self._queue:
-                    raise RuntimeError("Q8Server.run: requests are waiting but no slot can take them")
+                    raise RuntimeError(f"{self.NAME}.run: requests are waiting but no slot can take them")
                 return
             if k:
                 after = self._after(k)
@@ -819,8 +760,169 @@ class Q8Server:
                     continue
                 self._collect(on_token)
                 if not all(self._req[i] is None for i in expect):
-                    raise RuntimeError(f"Q8Server.run: the steps have run but slots {[i for i in expect if self._req[i] is not None]} have not finished")
+                    raise RuntimeError(f"{self.NAME}.run: the steps have run but slots {[i for i in expect if self._req[i] is not None]} have not finished")
                 break
+
+    def _after(self, k):
+        m = list(self._mirror)
+        for _ in range(k):
+            _, m = serve_plan_step(m, self.max_rows)
+        return m
+
+    def finished(self, handle) -> bool:
+        return handle in self._finished
+
+    def poll(self, on_token=None):
+        """collect what the rings hold now (never touches the stream); on_token(handle, index, token) for every new token"""
+        if self._collect(on_token):
+            self._resync()
+
+    def result(self, handle):
+        """the tokens of request `handle` collected so far by run / step / poll (all of them once finished(handle))"""
+        return list(self._results[handle])
+
+    def stats(self):
+        """<ABI>_stats (synchronises): the device's counters, the slot table, the last step's row table"""
+        r = rama_q8_serve_report()
+        self._call("stats", C.byref(r))
+        return dict(steps=int(r.steps), graph_captures=int(r.graph_captures), rows_decode=int(r.rows_decode), rows_prompt=int(r.rows_prompt),
+                    rows_idle=int(r.rows_idle), n_slots=int(r.n_slots), max_rows=int(r.max_rows),
+                    last_rows=_row_table(r.last_rows, r.max_rows),
+                    slots=[(s.state, s.n_context, s.cursor, s.n_out, s.max_new) for s in r.slots[:r.n_slots]],
+                    generation=[int(g) for g in r.generation[:r.n_slots]])
+
+    def close(self):
+        if self._open:
+            self._open = False
+            self._call("end")
+            self._closed()
+            for e in self._mine:
+                e.free()
+            self._mine, self._spare = [], []
+            self._own, self._eng = [None] * self.n_slots, [None] * self.n_slots
+
+
+class Q8Server(ServeLoop):
+    """continuous batching over one Q8Model (rama_q8_serve_begin / _admit / _steps / _poll): n_slots sequence slots share weight
+    passes of max_rows rows; a finished sequence frees its slot for the next queued request while the others run on, and a new
+    request's context is ingested in chunks next to the decoding slots.  Every request's tokens are those Q8Engine.generate gives
+    it alone.  One serving chain per device context at a time.
+
+    Prompt caching (DESIGN.md 8.4).  submit(..., n_cached=n) admits over rows 0..n-1 that the caller's engine already holds
+    (a chat's next turn on the same engine).  prefix_cache=k keeps a pool of at most k donor engines: a request submitted with
+    retain=True leaves its engine there when it finishes, keyed by the tokens whose rows it holds; every later request is
+    matched against the pool at its admission, the longest shared prefix is forked into its engine (rama_q8_kv_fork) and the
+    slot starts at that cursor (rama_q8_serve_admit_at).  The tokens are the same with the cache on and off.
+
+    Drafts (DESIGN.md 8.6).  n_draft=K > 0 begins the chain with rama_q8_serve_begin_spec: a decoding request guesses up to K
+    tokens per step by looking its last <= ngram tokens up in its own text and in the hint it was submitted with (at most
+    hint_cap tokens), the guesses take the rows of the step that no slot wants -- prompts first -- and are verified in the same
+    weight pass.  The tokens are the same with drafts on and off; n_draft=0 (the default) is the plain chain."""
+
+    ABI = "rama_q8_serve"
+    NAME = "Q8Server"
+
+    def __init__(self, model: Q8Model, n_slots: int, max_rows=None, max_new_cap: int = 256, prefix_cache: int = 0, n_draft: int = 0,
+                 ngram: int = 3, hint_cap: int = 0):
+        serve_sizes(model.cfg, n_slots, max_rows, max_new_cap)      # (every size is checked before any library call, in this order)
+        self.n_draft, self.ngram, self.hint_cap = serve_spec_sizes(n_draft, ngram, hint_cap)
+        self.spec = self.n_draft > 0                      # n_draft == 0: the plain chain, rama_q8_serve_begin
+        self.pool = PrefixPool(prefix_cache)              # (raises before any library call)
+        self._cached = {}                                 # handle -> the n_cached it was admitted with
+        self._drafts = {}                                 # handle -> (n_draft, ngram, hint tokens)
+        self.rows_cached = 0                              # ... summed over the admissions
+        self._start(model, n_slots, max_rows, max_new_cap)
+
+    def _begin(self):
+        if not self.spec:
+            return super()._begin()
+        m = self.model
+        check(self.device.lib.rama_q8_serve_begin_spec(self.device.ctx, C.byref(m.ccfg), C.byref(m.weights), self.n_slots, self.max_rows,
+                                                       self.max_new_cap, self.n_draft, self.hint_cap), "rama_q8_serve_begin_spec")
+
+    def _new_engine(self):
+        e = Q8Engine(self.device, self.model)
+        self._mine.append(e)
+        return e
+
+    # -- requests
+    def submit(self, context, max_new, temperature=0.0, topp=0.9, u=TOPP_U_CPU, stop_token=None, engine=None, n_cached=0,
+               retain=False, n_draft=None, hint=None):
+        """queue a request -> its handle.  It is admitted at once if a slot is free, else when one finishes (step / run).
+        engine: the Q8Engine whose run state the sequence uses (default: one the server owns for the slot).
+        n_cached: rows 0..n_cached-1 of `engine` already hold context[0..n_cached) -- written by work enqueued earlier on the
+        device's stream; the slot feeds the rest (at most n_context - 1: the final position is always fed).  Such a request is
+        not matched against the prefix cache.
+        retain: with a prefix cache, the engine stays behind as a donor when the request finishes (a caller's engine too: it
+        is the pool's until it is evicted).
+        n_draft, hint: on a server made with n_draft > 0, the drafts per step of this request (default: the server's; 0: none)
+        and a token list to look up in besides the request's own text (at most hint_cap tokens).  The tokens are the same
+        whatever they are."""
+        ctx, plan = serve_plan(self.cfg, context, max_new, temperature, topp, u, stop_token, self.max_new_cap, n_cached)
+        draft = serve_spec_request(self.cfg, self.n_draft, self.ngram, self.hint_cap, n_draft, hint)
+        n_cached = int(n_cached)
+        if n_cached and engine is None:
+            raise ValueError("Q8Server.submit: n_cached needs the engine that holds the rows")
+        if engine is not None and engine.model is not self.model:
+            raise ValueError("Q8Server.submit: the engine belongs to another Q8Model")
+        if engine is not None and any(e is engine for e in self._engines_in_use()):
+            raise ValueError("Q8Server.submit: the engine already serves a queued or running request")
+        if engine is not None and engine in self.pool:
+            raise ValueError("Q8Server.submit: the engine is a donor of the prefix cache")
+        h = self._submit(ctx, plan, engine, n_cached, retain)
+        self._drafts[h] = draft
+        self._admit()
+        return h
+
+    def _admit_slot(self, slot, h, eng, toks, rec, n_cached):
+        L, ctx = self.device.lib, self.device.ctx
+        if not n_cached and len(self.pool):
+            # the donor stays in the pool whatever happens below: donors leave it in _collect only, so a fork that was
+            # enqueued and an admission that then failed find it there at the next attempt; an evicted donor is reused or
+            # freed behind the fork in stream order
+            donor, n_cached = self.pool.match(toks, self.MIN_CACHED)
+            if n_cached:
+                check(L.rama_q8_kv_fork(ctx, C.byref(self.model.ccfg), C.byref(donor.state), C.byref(eng.state), 1, n_cached),
+                      "rama_q8_kv_fork")
+        arr = _i32(toks)
+        if self.spec:
+            K, N, hint = self._drafts[h]
+            harr = _i32(hint)
+            srec = rama_q8_serve_spec(K, N, harr if hint else None, len(hint))
+            check(L.rama_q8_serve_admit_spec(ctx, slot, C.byref(eng.state), arr, len(toks), n_cached, C.byref(rec), C.byref(srec)),
+                  "rama_q8_serve_admit_spec")
+        elif n_cached:
+            check(L.rama_q8_serve_admit_at(ctx, slot, C.byref(eng.state), arr, len(toks), n_cached, C.byref(rec)), "rama_q8_serve_admit_at")
+        else:
+            self._call("admit", slot, C.byref(eng.state), arr, len(toks), C.byref(rec))
+        return n_cached
+
+    def _admitted(self, h, n_cached):
+        self._cached[h] = n_cached
+        self.rows_cached += n_cached
+
+    def _retire(self, slot, h):
+        """a finished occupant: with retain and a prefix cache its engine becomes a donor, keyed by the tokens it was fed (the
+        context and every output but the last); whoever leaves the pool for it serves requests again if the server made it"""
+        toks, _, _, _, retain = self._plans[h]
+        eng, self._eng[slot] = self._eng[slot], None
+        if not retain or self.pool.k == 0:
+            return
+        if self._own[slot] is eng:
+            self._own[slot] = None
+        for e in self.pool.put(toks + self._results[h][:-1], eng):
+            if any(e is m for m in self._mine):
+                self._spare.append(e)
+
+    def cached(self, handle) -> int:
+        """the n_cached request `handle` was admitted with (None while it waits)"""
+        return self._cached.get(handle)
+
+    MIN_CACHED = 2     # a shorter match is not worth a launch: every context shares its first token (BOS) with every donor
+
+    def run(self, on_token=None):
+        """ServeLoop.run; with drafts, _run_spec"""
+        return self._run_spec(on_token) if self.spec else super().run(on_token)
 
     SPEC_BLOCK = 4     # with drafts: at most this many steps between two looks at the device's slot table
 
@@ -845,49 +947,18 @@ class Q8Server:
                 if not _stream_busy(self.device, 0.0001):
                     break
 
-    def _after(self, k):
-        m = list(self._mirror)
-        for _ in range(k):
-            _, m = serve_plan_step(m, self.max_rows)
-        return m
-
-    def finished(self, handle) -> bool:
-        return handle in self._finished
-
-    def poll(self, on_token=None):
-        """collect what the rings hold now (never touches the stream); on_token(handle, index, token) for every new token"""
-        if self._collect(on_token):
-            self._resync()
-
-    def result(self, handle):
-        """the tokens of request `handle` collected so far by run / step / poll (all of them once finished(handle))"""
-        return list(self._results[handle])
-
     def stats(self):
         """rama_q8_serve_stats (synchronises): the device's counters, the slot table, the last step's row table; rows_cached is the
         host's sum of n_cached over the admissions (context positions taken from cached rows instead of being fed)"""
-        r = rama_q8_serve_report()
-        check(self.device.lib.rama_q8_serve_stats(self.device.ctx, C.byref(r)), "rama_q8_serve_stats")
-        spec = {}
+        out = dict(super().stats(), rows_cached=self.rows_cached)
         if self.spec:
             q = rama_q8_serve_spec_report()
             check(self.device.lib.rama_q8_serve_spec_stats(self.device.ctx, C.byref(q)), "rama_q8_serve_spec_stats")
-            spec = dict(spec=serve_spec_report(q))
-        return dict(**spec, steps=int(r.steps), graph_captures=int(r.graph_captures), rows_decode=int(r.rows_decode), rows_prompt=int(r.rows_prompt),
-                    rows_idle=int(r.rows_idle), rows_cached=self.rows_cached, n_slots=int(r.n_slots), max_rows=int(r.max_rows),
-                    last_rows=_row_table(r.last_rows, r.max_rows),
-                    slots=[(s.state, s.n_context, s.cursor, s.n_out, s.max_new) for s in r.slots[:r.n_slots]],
-                    generation=[int(g) for g in r.generation[:r.n_slots]])
+            out["spec"] = serve_spec_report(q)
+        return out
 
-    def close(self):
-        if self._open:
-            self._open = False
-            check(self.device.lib.rama_q8_serve_end(self.device.ctx), "rama_q8_serve_end")
-            self.pool.clear()                             # (a caller's engine that was a donor is the caller's again)
-            for e in self._mine:
-                e.free()
-            self._mine, self._spare = [], []
-            self._own, self._eng = [None] * self.n_slots, [None] * self.n_slots
+    def _closed(self):
+        self.pool.clear()                             # (a caller's engine that was a donor is the caller's again)
 
 
 # ------------------------------------------------------------------ the speculative chain: n-gram lookup drafts (rama_q8_spec_*)
