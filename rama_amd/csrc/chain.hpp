@@ -28,7 +28,7 @@
 // Results are bit-identical to ref_order.hpp's and to the oracle's (tests/test_hip_ref_order.py,
 // tests/test_hip_parity_7b.py).
 #pragma once
-#define RAMA_CHAIN_HPP 1      // (rama_api.hip and q8_api.hip refuse to be compiled with this header: its kernels are chain_api.hip's)
+#define RAMA_CHAIN_HPP 1      // (rama_api.hip, batch_api.hip and q8_api.hip refuse to be compiled with this header: its kernels are chain_api.hip's)
 #include "kernels.hpp"
 #include "chain_params.hpp"     // ChainParams, GemmChainParams, CEPI_* / CNORM_*, the LDS sizes: what the launchers' callers see
 #include "ref_order.hpp"
@@ -459,7 +459,7 @@ __device__ __forceinline__ float seq_sum_cascade(const float* a, int n, FastSumS
     return sum;
 }
 // (a grid of several workgroups: vector b of a token batch, `stride` floats after the one before it)
-// (tile: the rows of the serving chain's step this launch stands for, rama_api.hip serve_pass -- idle rows come last in that table, so a tile whose FIRST row
+// (tile: the rows of the serving chain's step this launch stands for, batch_api.hip serve_pass -- idle rows come last in that table, so a tile whose FIRST row
 // is idle has no row anybody wants and every workgroup leaves before its first load.  One scalar load and compare on a kernel argument; NULL: no table)
 __global__ __launch_bounds__(kNormThreads) void rmsnorm_chain_kernel(float* o, const float* x, const float* w, int n, float* copy_to, int stride = 0,
                                                                      const SeqSlot* tile = nullptr) {

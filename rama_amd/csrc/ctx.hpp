@@ -1,4 +1,4 @@
-// ctx.hpp -- what the library's C-ABI translation units (rama_api.hip, chain_api.hip, q8_api.hip) share: the context, the error plumbing, graph
+// ctx.hpp -- what the library's C-ABI translation units (rama_api.hip, batch_api.hip, chain_api.hip, q8_api.hip) share: the context, the error plumbing, graph
 // capture, the launch macros, and declarations of what each defines for the others.  Internal: not installed, not part of the C ABI.
 //
 // The library is built WITHOUT relocatable device code, so a kernel or a __device__ global lives in the code object of the translation
@@ -317,7 +317,7 @@ struct rama_ctx {
         int* words = nullptr;              // host-pinned and device-mapped: [0] tokens emitted, [1] 1 = the sequence has finished
         rama_run_state state{};
     } q8p;
-    // rama_serve_begin / _admit / _steps: the serving chain of an fp32 model in parity mode (rama_api.hip).  A state of its own: it
+    // rama_serve_begin / _admit / _steps: the serving chain of an fp32 model in parity mode (batch_api.hip).  A state of its own: it
     // may be live next to q8s on the same context, and neither touches the other's graph or tables.
     struct Serve : ServeState {
         bool live = false;                 // false once the model or the run state of an occupied slot has been freed: _admit and _steps refuse
@@ -347,9 +347,20 @@ int launch_rmsnorm_ref(rama_ctx* c, float* o, const float* x, const float* w, in
 int launch_attention_ref(rama_ctx* c, float* xb, float* att, const float* q, const float* kc_layer, const float* vc_layer,
                          const Ctl* ctl, int pos, int dim, int head_size, int seq_len, int n_heads);
 
+// what batch_api.hip needs of the one-token forward: the check of (weights, run state, stage), parity mode's chain-order copy made on first use
+// (st == NULL: the whole model), and the final norm + classifier of one token through this translation unit's gemv_rows
+int check_stage(const rama_config* cfg, const rama_weights* w, const rama_run_state* s, const rama_stage* st);
+int ensure_chain_copy(rama_ctx* c, const rama_config* cfg, const rama_weights* w, const rama_stage* st);
+int launch_classifier(rama_ctx* c, float* logits, const float* wcls, const float* x, const float* gain, int dim, int vocab);
+
+// ---------------------------------------------------------------- defined in batch_api.hip: the token batches, the chained batch, the fp32 serving chain
+
 int stage_tokens(rama_ctx* c, int* toks_dev, const int32_t* tokens_host, int n, SeqSlot* seqs_dev = nullptr,
                  const rama_run_state* states = nullptr, const int32_t* pos_host = nullptr);
 int copy_out_logits(rama_ctx* c, const rama_run_state* states, const float* lg, int n, int V);
+void drop_batch_graphs(rama_ctx* c);                                 // drop_graph: the chained batch's step and the serving chain's
+void release_batch(rama_ctx* c);                                     // rama_ctx_destroy: the scratch blobs, the chained batch's and the serving chain's allocations; the stream is idle
+void serve_state_gone(rama_ctx* c, const rama_run_state* s);         // rama_state_free: a serving chain whose live slot uses s ends
 
 // ---------------------------------------------------------------- defined in chain_api.hip: parity mode's launches (chain.hpp) and the samplers
 
@@ -385,7 +396,7 @@ void drop_q8_graphs(rama_ctx* c, const rama_run_state* s);      // drop_graph, r
 void release_q8(rama_ctx* c);                                   // rama_ctx_destroy: the Q8 stack's allocations; the stream is idle
 
 // the serving chains' shared host layer: what rama_q8_serve_* and rama_serve_* do alike is written once in q8_api.hip, which also
-// owns q8_serve.hpp's kernels -- rama_api.hip reaches them through the launchers
+// owns q8_serve.hpp's kernels -- batch_api.hip reaches them through the launchers
 // The tables of one allocation in order, each rounded up to 256 bytes.  The same code lays a blob out twice: over no base for its size
 // (`used`), then over the allocation for the typed pointers.
 struct BlobCarver {

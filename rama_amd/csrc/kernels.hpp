@@ -539,6 +539,8 @@ constexpr int kAttnWaves = 16;
 constexpr int kAttnThreads = kAttnWaves * 64;
 // LDS floats: [2 * W] max / sum, [W * G * 4] partial outputs, [seq_len] scores (W waves, default 16)
 __host__ __device__ constexpr int attn_scratch_floats(int G, int W = kAttnWaves) { return 2 * W + W * G * 4; }
+constexpr int attn_group_width(int head_size) { return head_size <= 64 ? 16 : (head_size <= 128 ? 32 : 64); }      // G by head size: what the host picks the instantiation by
+constexpr bool attn_one_wg_holds(int head_size, int tmax) { return (size_t)(attn_scratch_floats(attn_group_width(head_size)) + tmax) * sizeof(float) <= 64 * 1024; }      // the one-workgroup kernel: tmax scores beside its scratch in 64 KiB of LDS
 
 // W = 4: the token-batch passes' short contexts (a few dozen timesteps per query, thousands of
 // (head, query) workgroups): a round of 4 waves already covers 64 timesteps, and 8 such workgroups fit a CU

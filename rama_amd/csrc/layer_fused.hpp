@@ -21,6 +21,7 @@
 // No deadlock whatever is resident: a workgroup only ever waits for workgroups with LOWER indices, which are dispatched
 // before it.  Every spin is bounded all the same, and gives up at once when another workgroup already has (error word).
 #pragma once
+#define RAMA_LAYER_FUSED_HPP 1      // (batch_api.hip refuses to be compiled with this header: its kernels and attn_wo.hpp's are rama_api.hip's)
 #include "attn_wo.hpp"
 
 namespace rama {

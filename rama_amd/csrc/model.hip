@@ -702,7 +702,7 @@ extern "C" int rama_model_weights(const rama_model* m, rama_weights* w) {
 extern "C" size_t rama_model_bytes(const rama_model* m) { return m ? m->blob_floats * sizeof(float) : 0; }
 
 extern "C" void rama_internal_drop_graphs(rama_ctx* ctx);      // rama_api.hip: captured graphs hold the copies' addresses
-extern "C" void rama_internal_serve_weights_gone(rama_ctx* ctx, const float* base, size_t n);      // rama_api.hip: the fp32 serving chain over these tensors is dead
+extern "C" void rama_internal_serve_weights_gone(rama_ctx* ctx, const float* base, size_t n);      // batch_api.hip: the fp32 serving chain over these tensors is dead
 
 // Give the derived weight copies back: mask bit 0 (1) = the chain-order copy (parity mode), bit 1 (2) = the tile-order copy (token-batch
 // passes).  A server that only decodes in fast mode holds 38 GB for llama2-7B instead of up to 92.  They are made again on the

@@ -35,6 +35,7 @@
 // K is split over the workgroup's 8 waves in 64-float chunks (chunk c -> wave c mod 8: the
 // workgroup sweeps each row front to back like the decode kernels); partial tiles meet in LDS.
 #pragma once
+#define RAMA_PREFILL_MFMA_HPP 1      // (rama_api.hip refuses to be compiled with this header: its kernels are batch_api.hip's)
 #include "kernels.hpp"
 #include <type_traits>
 

@@ -92,7 +92,7 @@ __global__ __launch_bounds__(kServeMaxSlots) void serve_schedule_kernel(ServeTab
     }
 }
 
-// X[r] = token_embedding_table[row_tok[r]] for the rows of the step's table that some slot wants (the fp32 chain's pass, rama_api.hip: an idle
+// X[r] = token_embedding_table[row_tok[r]] for the rows of the step's table that some slot wants (the fp32 chain's pass, batch_api.hip: an idle
 // row keeps what it holds, so a tile nobody wants is not touched at all)
 __global__ void serve_embed_rows_kernel(float* X, const float* emb, const int* row_tok, const SeqSlot* rows, int dim) {
     const int r = blockIdx.y;

@@ -522,6 +522,53 @@ def test_refusals_leave_the_running_chain_as_it_was(dev, models):
     a.twin.free(); b.twin.free(); rb.free(); mb.free(); r.free(); other.free()
 
 
+def test_model_free_ends_a_live_chain_and_a_context_goes_with_its_chains_begun(dev):
+    """rama_model_free under a live chain with a captured step: what the chain produced stays the solo run's and readable, _steps and _admit
+    refuse.  Then a context of its own is destroyed with a serving chain and a chained batch both still begun (no rama_serve_end; the
+    chained batch has no end entry) after each has produced its solo / oracle tokens."""
+    import rama_amd
+    from rama_amd._lib import check
+    cfg = W.TINY
+    rope = S.rope_tables(cfg.seq_len, cfg.head_size)
+    d = rama_amd.Hip(0)
+    L = d.lib
+    check(L.rama_set_tuning(d.ctx, b"ref_order", 1))
+    L.rama_set_graph_mode(d.ctx, 1)
+    m1, m2 = (rama_amd.Model.synth(d, to_rama_cfg(cfg), SEED, rope=rope) for _ in range(2))
+    rng = np.random.default_rng(14)
+    r, late = Req(d, cfg, m1, rng, 3, 6), Req(d, cfg, m1, rng, 2, 2)
+    want = r.want()
+    assert begin(d, m1, 2, 8, 8) == 0 and admit(d, 0, r) == 0
+    assert steps(d, 3) == 0 and L.rama_sync(d.ctx) == 0
+    got, fin, _ = poll(d, 0)
+    assert got and got == want[:len(got)] and not fin
+    m1.free()                                                # the chain's model goes: the chain is dead
+    assert steps(d, 1) == EINVAL and admit(d, 1, late) == EINVAL
+    assert tokens(d, 0) == got
+    r.free(); late.free()
+    # a chain over the second model (it takes the dead one's place) and, in fast mode, a chained batch
+    q = Req(d, cfg, m2, rng, 3, 4)
+    assert begin(d, m2, 2, 8, 8) == 0 and admit(d, 0, q) == 0
+    run_all(d, [q])
+    q.check(tokens(d, 0), "the chain begun after the first model went")
+    check(L.rama_set_tuning(d.ctx, b"ref_order", 0))
+    pair = [rama_amd.Engine(d, m2), rama_amd.Engine(d, m2)]
+    batch = rama_amd.decode_batch_chained(pair, [3, 7], [0, 0], 6)
+    w = S.synth_weights(cfg, SEED, rope=rope)
+    for i, t in enumerate((3, 7)):
+        orc, greedy = O.Oracle(cfg, w), []
+        for p in range(6):
+            t = O.argmax(orc.forward(t, p)); greedy.append(t)
+        assert batch[i] == greedy, i
+    assert L.rama_ctx_destroy(d.ctx) == 0                    # both chains begun, the serving chain live with its step captured
+    d.ctx = None
+    # the run states and the model outlive their context: freed through the module's
+    for e in (q.eng, q.twin, *pair):
+        assert dev.lib.rama_state_free(dev.ctx, C.byref(e.state)) == 0
+    assert dev.lib.rama_model_free(dev.ctx, m2.handle) == 0
+    m2.handle = None
+
+
 def test_a_q8_chain_and_the_fp32_chain_on_one_context(dev, models, golden_dir):
     """their steps interleaved; both end with their solo tokens, each with one captured step"""
     import rama_amd
