@@ -618,8 +618,10 @@ int  rama_q8_serve_end(rama_ctx *ctx);
  * slot provided the copied rows lie below what earlier enqueued work has written (rows below a slot's cursor are never
  * rewritten -- on a chain begun with rama_q8_serve_begin_spec too, where rows AT AND BEHIND a speculating slot's cursor may
  * hold rejected drafts: fork only rows below the cursor, n_rows <= n_context - 1 + the tokens the host has seen).  RAMA_EINVAL for a NULL argument or cache, n_dst or n_rows out of range, a destination whose caches overlap the
- * source's or another destination's, and a destination that is in a live slot of the serving chain.  Cache bases that are not
- * 16-byte aligned take a slower path with the same result. */
+ * source's or another destination's, and a destination that is in a live slot of a serving chain -- the Q8 chain's or the fp32
+ * chain's (rama_serve_*, below).  Cache bases that are not 16-byte aligned take a slower path with the same result.
+ * THE ONE FORK OF BOTH STACKS: the KV cache is fp32 whatever the model, and the fork reads no weight, so rows written by
+ * rama_prefill, rama_generate or an fp32 serving slot are forked by this entry too (rama_serve_admit_at below). */
 int  rama_q8_serve_admit_at(rama_ctx *ctx, int slot, const rama_run_state *state, const int32_t *context_host, int n_context,
                             int n_cached, const rama_q8_serve_plan *plan);
 int  rama_q8_kv_fork(rama_ctx *ctx, const rama_config *cfg, const rama_run_state *src, const rama_run_state *dsts, int n_dst,
@@ -633,7 +635,8 @@ int  rama_q8_kv_fork(rama_ctx *ctx, const rama_config *cfg, const rama_run_state
  * position is written, whatever the chunking, the neighbours, max_rows, the tile a row lands in and the graph mode.
  * A step's pass runs the row table in tiles of 32 rows, in ascending order; idle rows come last, and a tile whose first row is
  * idle costs its launches but streams no weight.  A state of its own: it may be live next to a Q8 serving chain on the same
- * context, and neither chain touches the other's tables or captured step.  No prompt caching, no drafts, no pipeline.
+ * context, and neither chain touches the other's tables or captured step.  No pipeline.  Prompt caching (rama_serve_admit_at)
+ * and drafts in idle rows (rama_serve_begin_spec, declared behind the Q8 entries they mirror) are opt-in.
  *
  * rama_serve_begin: 1 <= n_slots <= max_rows <= 128 and 1 <= max_new_cap <= seq_len - 1 (RAMA_EINVAL).  PARITY MODE ONLY:
  *   RAMA_EUNSUP unless "ref_order" = 1 -- fast mode ("ref_order" = 0), tolerance mode (2) and bar mode (3) are out of scope --,
@@ -643,6 +646,11 @@ int  rama_q8_kv_fork(rama_ctx *ctx, const rama_config *cfg, const rama_run_state
  *   beside it, and success ends the previous fp32 chain.
  * rama_serve_admit: rama_q8_serve_admit's checks in the same order (one body), the run state checked against the fp32 model;
  *   RAMA_EUNSUP for a sampled plan on vocab_size > 32768.  Stream-ordered, the captured step untouched.
+ * rama_serve_admit_at: rama_q8_serve_admit_at's contract.  0 <= n_cached <= n_context - 1 (RAMA_EINVAL); the slot is installed
+ *   PROMPT with cursor = n_cached; rows 0..n_cached-1 of every layer of `state`'s caches are the caller's contract: the rows
+ *   of context[0..n_cached), written by work enqueued earlier on the context's stream (a rama_prefill or rama_generate in
+ *   parity mode, a rama_q8_kv_fork, an earlier occupant's steps).  rama_serve_admit is its n_cached == 0 case: one body, the
+ *   same checks in the same order.  The tokens and cache rows are those of the solo run, bit for bit.
  * rama_serve_steps: no overall limit.  RAMA_EINVAL once the model (rama_model_free) or the run state of an occupied slot
  *   (rama_state_free before the host could see the slot DONE) is gone; RAMA_EUNSUP once the context has left parity mode.
  * rama_serve_poll never touches the stream: tokens from.. of the slot's occupant, *finished, *generation (each may be NULL).
@@ -652,6 +660,8 @@ int  rama_q8_kv_fork(rama_ctx *ctx, const rama_config *cfg, const rama_run_state
 int  rama_serve_begin(rama_ctx *ctx, const rama_config *cfg, const rama_weights *w, int n_slots, int max_rows, int max_new_cap);
 int  rama_serve_admit(rama_ctx *ctx, int slot, const rama_run_state *state, const int32_t *context_host, int n_context,
                       const rama_q8_serve_plan *plan);
+int  rama_serve_admit_at(rama_ctx *ctx, int slot, const rama_run_state *state, const int32_t *context_host, int n_context,
+                         int n_cached, const rama_q8_serve_plan *plan);
 int  rama_serve_steps(rama_ctx *ctx, int n_steps);
 int  rama_serve_poll(rama_ctx *ctx, int slot, int from, int32_t *out_tokens_host, int max_tokens, int *n_ready, int *finished,
                      int *generation);
@@ -798,6 +808,34 @@ int  rama_q8_serve_admit_spec(rama_ctx *ctx, int slot, const rama_run_state *sta
 int  rama_q8_serve_spec_plan_step(const rama_q8_serve_slot *slots, int n_slots, int max_rows, const int32_t *want,
                                   rama_q8_serve_row *rows_out, int32_t *granted_out);
 int  rama_q8_serve_spec_stats(rama_ctx *ctx, rama_q8_serve_spec_report *out);
+
+/* DRAFTS IN THE IDLE ROWS OF THE PARITY-MODE SERVING CHAIN: the three entries above for an fp32 model, argument
+ * for argument, with rama_weights and the same plan, spec and report records.  A parity pass runs in tiles of 32 rows and a tile
+ * costs its whole weight pass whatever its rows hold, so the rows of a live tile that no slot wants are paid for: a DECODE
+ * slot's n-gram drafts take them.  THE SCHEDULE, LOGITS flags and ACCEPT rule are those above (the same kernels); a DECODE
+ * slot's rows tok, d[0..granted) sit at consecutive positions like a prompt chunk and may straddle a tile boundary.  The final
+ * norm and the classifier run over the pass's rows where they sit, tile by tile: a tile none of whose rows carries logits --
+ * wholly idle, or holding only rows inside a context -- is skipped before its first load.  Slot i's tokens are still, bit for
+ * bit, parity-mode rama_generate's on that sequence alone, cut at the stop token, whatever the drafts, the hints, the
+ * neighbours, max_rows, the tile a row lands in and the graph mode.
+ * THE CACHE CONTRACT OF SUCH A CHAIN.  Rows below a slot's cursor hold the solo run's bits and are never rewritten.  UNLIKE the
+ * plain chain (nothing behind a slot's last position is written), rows AT AND BEHIND a speculating slot's cursor, up to
+ * n_context - 2 + max_new, may hold the rows of rejected drafts: each is rewritten by the step that feeds its position before
+ * any attention reads it.  Nothing at or beyond row n_context - 1 + max_new is ever written.  Fork from a live speculating
+ * slot only rows below its cursor.
+ * rama_serve_begin_spec: rama_serve_begin's checks, then 0 <= n_draft_cap <= 15 and 0 <= hint_cap < 2^30 (RAMA_EINVAL).
+ *   Everything is sized here, outside any capture: the drafting tables, per-row sampler records, sampler slices and logits for
+ *   max_rows rows.  One fp32 serving chain per context, of either kind; rama_serve_end, _steps, _poll, _tokens, _stats, the
+ *   `live` rules, the re-capture when the chain-order copies move and the parity-mode rule are the same entries'.
+ * rama_serve_admit_spec: rama_serve_admit_at (n_cached may be 0) with the slot's drafting fields; its checks in its order --
+ *   n_context + max_new <= seq_len among them --, then RAMA_EINVAL as rama_q8_serve_admit_spec.  rama_serve_admit and
+ *   rama_serve_admit_at on such a chain admit with n_draft = 0.
+ * rama_serve_spec_stats: as rama_q8_serve_spec_stats; RAMA_EINVAL on a chain begun with rama_serve_begin. */
+int  rama_serve_begin_spec(rama_ctx *ctx, const rama_config *cfg, const rama_weights *w, int n_slots, int max_rows,
+                           int max_new_cap, int n_draft_cap, int hint_cap);
+int  rama_serve_admit_spec(rama_ctx *ctx, int slot, const rama_run_state *state, const int32_t *context_host, int n_context,
+                           int n_cached, const rama_q8_serve_plan *plan, const rama_q8_serve_spec *spec);
+int  rama_serve_spec_stats(rama_ctx *ctx, rama_q8_serve_spec_report *out);
 
 /* ---------------------------------------------------------------- measurement
  * HIP events on the context's stream (the stream the kernels are launched on). */

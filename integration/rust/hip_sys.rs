@@ -265,6 +265,14 @@ extern "C" {
                             max_new_cap: c_int) -> c_int;
     pub fn rama_serve_admit(ctx: *mut rama_ctx, slot: c_int, state: *const rama_run_state, context_host: *const i32, n_context: c_int,
                             plan: *const rama_q8_serve_plan) -> c_int;
+    pub fn rama_serve_admit_at(ctx: *mut rama_ctx, slot: c_int, state: *const rama_run_state, context_host: *const i32, n_context: c_int,
+                               n_cached: c_int, plan: *const rama_q8_serve_plan) -> c_int;
+    // ... with drafts in the rows no slot wants: the Q8 spec serving entries' arguments and records
+    pub fn rama_serve_begin_spec(ctx: *mut rama_ctx, cfg: *const rama_config, w: *const rama_weights, n_slots: c_int, max_rows: c_int,
+                                 max_new_cap: c_int, n_draft_cap: c_int, hint_cap: c_int) -> c_int;
+    pub fn rama_serve_admit_spec(ctx: *mut rama_ctx, slot: c_int, state: *const rama_run_state, context_host: *const i32, n_context: c_int,
+                                 n_cached: c_int, plan: *const rama_q8_serve_plan, spec: *const rama_q8_serve_spec) -> c_int;
+    pub fn rama_serve_spec_stats(ctx: *mut rama_ctx, out: *mut rama_q8_serve_spec_report) -> c_int;
     pub fn rama_serve_steps(ctx: *mut rama_ctx, n_steps: c_int) -> c_int;
     pub fn rama_serve_poll(ctx: *mut rama_ctx, slot: c_int, from: c_int, out_tokens_host: *mut i32, max_tokens: c_int,
                            n_ready: *mut c_int, finished: *mut c_int, generation: *mut c_int) -> c_int;

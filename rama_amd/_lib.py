@@ -237,6 +237,7 @@ SIGNATURES = {
     # the fp32 serving chain (parity mode): the same arguments with rama_weights
     "rama_serve_begin": (_int, [_vp, _cfgp, C.POINTER(rama_weights), _int, _int, _int]),
     "rama_serve_admit": (_int, [_vp, _int, _sp, i32p, _int, C.POINTER(rama_q8_serve_plan)]),
+    "rama_serve_admit_at": (_int, [_vp, _int, _sp, i32p, _int, _int, C.POINTER(rama_q8_serve_plan)]),
     "rama_serve_steps": (_int, [_vp, _int]),
     "rama_serve_poll": (_int, [_vp, _int, _int, i32p, _int, C.POINTER(_int), C.POINTER(_int), C.POINTER(_int)]),
     "rama_serve_tokens": (_int, [_vp, _int, i32p, _int, C.POINTER(_int)]),
@@ -254,6 +255,9 @@ SIGNATURES = {
     "rama_q8_serve_admit_spec": (_int, [_vp, _int, _sp, i32p, _int, _int, C.POINTER(rama_q8_serve_plan), C.POINTER(rama_q8_serve_spec)]),
     "rama_q8_serve_spec_plan_step": (_int, [C.POINTER(rama_q8_serve_slot), _int, _int, i32p, C.POINTER(rama_q8_serve_row), i32p]),
     "rama_q8_serve_spec_stats": (_int, [_vp, C.POINTER(rama_q8_serve_spec_report)]),
+    "rama_serve_begin_spec": (_int, [_vp, _cfgp, C.POINTER(rama_weights), _int, _int, _int, _int, _int]),
+    "rama_serve_admit_spec": (_int, [_vp, _int, _sp, i32p, _int, _int, C.POINTER(rama_q8_serve_plan), C.POINTER(rama_q8_serve_spec)]),
+    "rama_serve_spec_stats": (_int, [_vp, C.POINTER(rama_q8_serve_spec_report)]),
 }
 
 # exported but not in the header (the rama_internal_* accessors tests read; most declare their own types where they call them): here

@@ -1,12 +1,13 @@
 // batch_api.hip -- the entries that push many tokens through a layer together: the MFMA token batch (rama_prefill, rama_decode_batch), its
 // parity-mode twin, the chained batch (rama_decode_batch_begin* / _steps / _tokens / _stream_poll) and the fp32 serving chain (rama_serve_*).
-// Every kernel of prefill_mfma.hpp and prefill_attn.hpp lives in this translation unit's code object; parity mode's kernels, the samplers, the
+// Every kernel of prefill_mfma.hpp, prefill_attn.hpp and serve_tile_guard.hpp lives in this translation unit's code object; parity mode's kernels, the samplers, the
 // serving chain's tables and the one-token forward are reached through ctx.hpp's launchers and the public entries (DESIGN.md "Translation units").
 #include "../../include/rama_hip.h"
 #include "kernels.hpp"
 #include "prefill_mfma.hpp"
 #include "prefill_attn.hpp"
 #include "ref_order.hpp"
+#include "serve_tile_guard.hpp"
 #include "ctx.hpp"
 
 #if defined(RAMA_CHAIN_HPP) || defined(RAMA_LAYER_FUSED_HPP)
@@ -687,7 +688,7 @@ static void serve_release(rama_ctx* c) {
     auto& sv = c->sv;
     destroy_graph(sv.cg);
     serve_state_free(sv);
-    hipFree(sv.scratch);
+    hipFree(sv.scratch); hipFree(sv.tguard);
     sv = rama_ctx::Serve();
 }
 // drop_graph of rama_api.hip: the chained batch's step and the serving chain's (each captured again by its next _steps call)
@@ -729,8 +730,8 @@ static ServeScratch serve_scratch(const rama_ctx::Serve& sv, const ChainBatch& c
     s.b.X = p; p += R * dim; s.b.XN = p; p += R * dim; s.b.Q = p; p += R * dim; s.b.XB = p; p += R * dim;
     s.b.HB = p; p += R * hidden;
     s.b.ATT = p; p += (size_t)kGcMaxTok * (size_t)cfg.n_heads * (size_t)cfg.seq_len;       // one tile's score rows: the tiles run one after the other
-    s.XG = p; p += N * dim; s.XGN = p; p += N * dim;
-    s.LG = p; p += N * (size_t)cfg.vocab_size;
+    if (!sv.spec) { s.XG = p; p += N * dim; s.XGN = p; p += N * dim; }       // (a chain with drafts classifies the rows where they sit)
+    s.LG = p; p += (sv.spec ? R : N) * (size_t)cfg.vocab_size;
     s.ccls = ccls;
     s.floats = (size_t)(p - sv.scratch);
     return s;
@@ -745,6 +746,16 @@ extern "C" int rama_internal_serve_scratch(rama_ctx* c, float** rows5, int* max_
     return 0;
 }
 
+// ... and its logits rows: [n_slots, vocab] on a plain chain, [max_rows, vocab] on one with drafts -- tests/test_hip_serve_spec.py poisons the rows of a
+// tile that carries no logits and sees that the classifier leaves them alone
+extern "C" int rama_internal_serve_logits(rama_ctx* c, float** logits, int* rows, int* vocab) {
+    if (!c || !c->sv.n_slots || !logits || !rows || !vocab) return RAMA_EINVAL;
+    *logits = serve_scratch(c->sv, ChainBatch{}, nullptr).LG;
+    *rows = c->sv.spec ? c->sv.max_rows : c->sv.n_slots;
+    *vocab = c->sv.cfg.vocab_size;
+    return 0;
+}
+
 int rama_serve_end(rama_ctx* c) {
     RAMA_ENTER(c);
     REQUIRE(c, RAMA_EINVAL, "serve_end: ctx is NULL");
@@ -755,7 +766,8 @@ int rama_serve_end(rama_ctx* c) {
     return 0;
 }
 
-int rama_serve_begin(rama_ctx* c, const rama_config* cfg, const rama_weights* w, int n_slots, int max_rows, int max_new_cap) {
+// rama_serve_begin (spec false) and rama_serve_begin_spec: the latter sizes the drafting tables as well, and its sampler and logits for max_rows rows
+static int serve_begin(rama_ctx* c, const rama_config* cfg, const rama_weights* w, int n_slots, int max_rows, int max_new_cap, bool spec, int n_draft_cap, int hint_cap) {
     RAMA_ENTER(c);
     REQUIRE(c, RAMA_EINVAL, "ctx is NULL");
     int rc = check_cfg(cfg); if (rc) return rc;
@@ -766,6 +778,7 @@ int rama_serve_begin(rama_ctx* c, const rama_config* cfg, const rama_weights* w,
     const int V = cfg->vocab_size;
     const bool sampler = V > 1 && V <= kToppBlock * kToppMaxBlocks;
     REQUIRE(sampler || V % 4 == 0, RAMA_EUNSUP, "serve_begin: vocab_size % 4 != 0 needs vocab_size <= 32768");
+    rc = check_spec_caps("serve_begin_spec", n_draft_cap, hint_cap); if (rc) return rc;      // (before anything is allocated: the copies below may be made here)
     if (set_device(c)) return 1;
     // shape, chain-order copies (made here when the model has none yet), the score buffer: what chain_batch_setup takes.  Nothing of a running chain is touched
     ChainBatch copies{};
@@ -773,12 +786,13 @@ int rama_serve_begin(rama_ctx* c, const rama_config* cfg, const rama_weights* w,
     bool ok = false;
     rc = chain_batch_copies(c, cfg, w, true, &copies, &ccls, &ok); if (rc) return rc;
     REQUIRE(ok, RAMA_EUNSUP, "serve_begin: a shape or weights the parity-mode token batch does not take (dim, hidden_dim multiples of 16; chain-order copies)");
-    if (sampler) { rc = ensure_topp_batch(c, n_slots, V); if (rc) return rc; }      // sized here, outside any capture
+    if (sampler) { rc = ensure_topp_batch(c, spec ? max_rows : n_slots, V); if (rc) return rc; }      // sized here, outside any capture (a chain with drafts picks per row)
     // the new chain is made beside the running one, which goes only when nothing can fail any more
     rama_ctx::Serve fresh;
     auto make = [&]() -> int {
-        int rm = serve_state_alloc(c, fresh, cfg->seq_len, n_slots, max_rows, max_new_cap, nullptr, nullptr); if (rm) return rm;
+        int rm = serve_state_alloc_spec(c, fresh, cfg->seq_len, n_slots, max_rows, max_new_cap, spec, n_draft_cap, hint_cap); if (rm) return rm;
         fresh.cfg = *cfg; fresh.w = *w; fresh.sampler = sampler;
+        if (spec) HIPCHK(hipMalloc(&fresh.tguard, sizeof(SeqSlot) * (size_t)((max_rows + kGcMaxTok - 1) / kGcMaxTok)));
         const size_t floats = serve_scratch(fresh, copies, ccls).floats;
         HIPCHK(hipMalloc(&fresh.scratch, floats * sizeof(float)));
         HIPCHK(hipMemsetAsync(fresh.scratch, 0, floats * sizeof(float), c->stream));      // (an idle row is computed along in a live tile: finite values, never read by anyone)
@@ -786,26 +800,54 @@ int rama_serve_begin(rama_ctx* c, const rama_config* cfg, const rama_weights* w,
         return 0;
     };
     rc = make();
-    if (rc) { serve_state_free(fresh); hipFree(fresh.scratch); return rc; }
+    if (rc) { serve_state_free(fresh); hipFree(fresh.scratch); hipFree(fresh.tguard); return rc; }
     serve_release(c);
     fresh.live = true;
     c->sv = std::move(fresh);
     return 0;
 }
 
-static const ServeNames kServeNames{"serve_admit", "serve_admit", "rama_serve_begin"};
-int rama_serve_admit(rama_ctx* c, int slot, const rama_run_state* state, const int32_t* context_host, int n_context, const rama_q8_serve_plan* plan) {
+int rama_serve_begin(rama_ctx* c, const rama_config* cfg, const rama_weights* w, int n_slots, int max_rows, int max_new_cap) {
+    return serve_begin(c, cfg, w, n_slots, max_rows, max_new_cap, false, 0, 0);
+}
+
+int rama_serve_begin_spec(rama_ctx* c, const rama_config* cfg, const rama_weights* w, int n_slots, int max_rows, int max_new_cap, int n_draft_cap, int hint_cap) {
+    return serve_begin(c, cfg, w, n_slots, max_rows, max_new_cap, true, n_draft_cap, hint_cap);
+}
+
+// rama_serve_admit (n_cached 0), rama_serve_admit_at and -- spec != NULL -- rama_serve_admit_spec: one body, rama_q8_serve_admit*'s checks in their order.
+// The slot starts PROMPT at cursor = n_cached, over rows 0 .. n_cached - 1 that earlier work on the stream has put into the run state's caches
+static const ServeNames kServeNames{"serve_admit", "serve_admit_at", "rama_serve_begin", "serve_admit_spec", "rama_serve_begin_spec"};
+static int serve_admit(rama_ctx* c, int slot, const rama_run_state* state, const int32_t* context_host, int n_context, int n_cached,
+                       const rama_q8_serve_plan* plan, const rama_q8_serve_spec* spec = nullptr) {
     RAMA_ENTER(c);
     REQUIRE(c && c->sv.n_slots > 0, RAMA_EINVAL, "serve_admit: call rama_serve_begin first");
     auto& sv = c->sv;
     int rc = serve_admit_head(kServeNames, sv, sv.live, slot, state, context_host, plan); if (rc) return rc;
     rama_stage st{0, sv.cfg.n_layers, 1, 1};
     rc = check_stage(&sv.cfg, &sv.w, state, &st); if (rc) return rc;
-    rc = serve_admit_tail(kServeNames, sv, sv.cfg, slot, state, context_host, n_context, 0, plan); if (rc) return rc;
+    rc = serve_admit_tail(kServeNames, sv, sv.cfg, slot, state, context_host, n_context, n_cached, plan); if (rc) return rc;
+    rc = serve_admit_spec_check(kServeNames, sv, sv.cfg.vocab_size, spec); if (rc) return rc;
     if (set_device(c)) return 1;
-    rc = serve_admit_install(c, sv, slot, state, context_host, n_context, 0, plan); if (rc) return rc;
+    rc = serve_admit_install(c, sv, slot, state, context_host, n_context, n_cached, plan); if (rc) return rc;
+    rc = serve_admit_spec_install(c, sv, slot, spec); if (rc) return rc;
     sv.states[slot] = *state; sv.occupied[slot] = 1; sv.gen[slot]++;
     return 0;
+}
+
+int rama_serve_admit(rama_ctx* c, int slot, const rama_run_state* state, const int32_t* context_host, int n_context, const rama_q8_serve_plan* plan) {
+    return serve_admit(c, slot, state, context_host, n_context, 0, plan);
+}
+
+int rama_serve_admit_at(rama_ctx* c, int slot, const rama_run_state* state, const int32_t* context_host, int n_context, int n_cached,
+                        const rama_q8_serve_plan* plan) {
+    return serve_admit(c, slot, state, context_host, n_context, n_cached, plan);
+}
+
+int rama_serve_admit_spec(rama_ctx* c, int slot, const rama_run_state* state, const int32_t* context_host, int n_context, int n_cached,
+                          const rama_q8_serve_plan* plan, const rama_q8_serve_spec* spec) {
+    REQUIRE(spec, RAMA_EINVAL, "serve_admit_spec: NULL argument");
+    return serve_admit(c, slot, state, context_host, n_context, n_cached, plan, spec);
 }
 
 // the pass over the step's row table, tile by tile in ascending order
@@ -832,6 +874,30 @@ static int enqueue_serve_step(rama_ctx* c, const ServeScratch& s) {
     return launch_serve_pick(c, sv.t, s.LG, V, sv.sampler);
 }
 
+// one step of a chain begun with rama_serve_begin_spec: the drafts, the scheduler, the tiles' guard entries, the wanted rows' embeddings, the pass, then --
+// tile by tile, where the rows sit -- the final norm and the classifier of the tiles that hold a logits row, every flagged row's pick, the accept rule
+static int enqueue_serve_spec_step(rama_ctx* c, const ServeScratch& s) {
+    auto& sv = c->sv;
+    const int dim = sv.cfg.dim, V = sv.cfg.vocab_size, R = sv.max_rows;
+    int rc = launch_serve_draft(c, sv.t, sv.st); if (rc) return rc;
+    rc = launch_serve_spec_schedule(c, sv.t, sv.st); if (rc) return rc;
+    hipLaunchKernelGGL(serve_tile_guard_kernel, dim3(1), dim3(kTileGuardThreads), 0, c->stream, (const int*)sv.st.lflag, R, sv.tguard);
+    LAUNCHCHK();
+    rc = launch_serve_embed(c, s.b.X, sv.w.token_embedding_table, sv.t, dim); if (rc) return rc;
+    rc = serve_pass(c, s); if (rc) return rc;
+    for (int r0 = 0; r0 < R; r0 += kGcMaxTok) {       // infer.rs:49-51 per tile: a tile without a logits row returns before its first load
+        const int nt = std::min(kGcMaxTok, R - r0);
+        const SeqSlot* guard = sv.tguard + r0 / kGcMaxTok;
+        rc = launch_rmsnorm_chain(c, s.b.XN + (size_t)r0 * dim, s.b.X + (size_t)r0 * dim, sv.w.rms_final_weight, dim, nullptr, nt, dim, guard); if (rc) return rc;
+        GemmChainParams p{};
+        p.w[0] = s.ccls; p.nmat = 1; p.K = dim; p.rows = V; p.x = s.b.XN + (size_t)r0 * dim; p.xstride = dim; p.o[0] = s.LG + (size_t)r0 * V; p.ostride = V; p.n_tok = nt;
+        p.seqs = guard;
+        rc = launch_gemm_chain(c, p, CEPI_STORE); if (rc) return rc;
+    }
+    rc = launch_serve_spec_pick(c, sv.t, sv.st, s.LG, V, sv.sampler); if (rc) return rc;
+    return launch_serve_spec_accept(c, sv.t, sv.st);
+}
+
 int rama_serve_steps(rama_ctx* c, int n_steps) {
     RAMA_ENTER(c);
     REQUIRE(c && c->sv.n_slots > 0, RAMA_EINVAL, "serve_steps: call rama_serve_begin first");
@@ -848,14 +914,15 @@ int rama_serve_steps(rama_ctx* c, int n_steps) {
     REQUIRE(ok, RAMA_EUNSUP, "serve_steps: the chain-order copies are gone and cannot be made (\"chain\" / \"prefill_chain\" = 0?)");
     const float* now[7] = {copies.cq, copies.ck, copies.cv, copies.co, copies.c13, copies.c2, ccls};
     if (memcmp(now, sv.copies, sizeof now)) { if (sv.cg.exec) HIPCHK(hipStreamSynchronize(c->stream)); destroy_graph(sv.cg); memcpy(sv.copies, now, sizeof now); }
-    if (sv.sampler) { rc = ensure_topp_batch(c, sv.n_slots, sv.cfg.vocab_size); if (rc) return rc; }
+    if (sv.sampler) { rc = ensure_topp_batch(c, sv.spec ? sv.max_rows : sv.n_slots, sv.cfg.vocab_size); if (rc) return rc; }
     const ServeScratch s = serve_scratch(sv, copies, ccls);
+    auto step = [&] { return sv.spec ? enqueue_serve_spec_step(c, s) : enqueue_serve_step(c, s); };
     c->embedded_x = nullptr; c->host_pos = -1;
     const bool graphs = c->graph_mode && c->kp.kernel_id < 0;
     for (int i = 0; i < n_steps; i++, sv.steps++) {
-        if (!graphs) { rc = enqueue_serve_step(c, s); if (rc) return rc; continue; }
+        if (!graphs) { rc = step(); if (rc) return rc; continue; }
         if (!sv.cg.exec) {
-            rc = capture_graph(c, sv.cg, [&] { return enqueue_serve_step(c, s); }); if (rc) return rc;
+            rc = capture_graph(c, sv.cg, step); if (rc) return rc;
             sv.captures++;
         }
         rc = replay_graph(c, sv.cg); if (rc) return rc;
@@ -878,6 +945,12 @@ int rama_serve_tokens(rama_ctx* c, int slot, int32_t* out_host, int max_tokens, 
 int rama_serve_stats(rama_ctx* c, rama_q8_serve_report* out) {
     RAMA_ENTER(c);
     REQUIRE(c && out && c->sv.n_slots > 0, RAMA_EINVAL, "serve_stats: bad argument");
-    return serve_report(c, c->sv, c->sv.captures, nullptr, out);
+    return serve_report(c, c->sv, c->sv.captures, c->sv.spec ? c->sv.st.lflag : nullptr, out);
+}
+
+int rama_serve_spec_stats(rama_ctx* c, rama_q8_serve_spec_report* out) {
+    RAMA_ENTER(c);
+    REQUIRE(c && out && c->sv.n_slots > 0 && c->sv.spec, RAMA_EINVAL, "serve_spec_stats: no chain begun with rama_serve_begin_spec");
+    return serve_spec_report(c, c->sv, out);
 }
 

@@ -295,17 +295,17 @@ struct rama_ctx {
         std::vector<char> occupied;        // per slot: admitted, and not yet seen DONE by a call that frees the slot
         std::vector<int> gen;
         unsigned long long steps = 0;
-    };
-    // rama_q8_serve_begin / _admit / _steps: the serving chain (q8_serve.hpp), a state of its own next to the chain above
-    struct Q8Serve : Q8ChainBase, ServeState {
-        // rama_q8_serve_begin_spec (q8_serve_spec.hpp): drafts in the rows no slot wants; all of it unused on a chain begun without it
+        // a chain begun with rama_q8_serve_begin_spec / rama_serve_begin_spec (q8_serve_spec.hpp): drafts in the rows no slot wants; all of it unused on
+        // a chain begun without it
         bool spec = false;
         int n_draft_cap = 0, hint_cap = 0;
         ServeSpecTables st{};              // the device tables (inside blob)
         char* sstage = nullptr;            // device: one spec admission record per slot (a ServeSpecSlot + hint_cap tokens)
         char* spinned = nullptr;           // host-pinned: the same
         size_t srec_bytes = 0;
-    } q8s;
+    };
+    // rama_q8_serve_begin / _admit / _steps: the serving chain (q8_serve.hpp), a state of its own next to the chain above
+    struct Q8Serve : Q8ChainBase, ServeState {} q8s;
     // rama_q8_spec_begin / _steps: the speculative chain (q8_spec.hpp), a third state next to the two above
     struct Q8Spec : Q8ChainBase {
         bool active = false;               // false: no speculative chain
@@ -326,6 +326,9 @@ struct rama_ctx {
         unsigned long long captures = 0;
         const float* copies[7] = {};       // the chain-order copies the captured step streams (they may be released and made again: the step is then captured again)
         float* scratch = nullptr;          // the pass's rows, one allocation: X | XN | Q | XB | HB [max_rows], ATT [kGcMaxTok], XG | XGN [n_slots], LG [n_slots, vocab]
+                                           // (a chain with drafts classifies the rows where they sit: no XG | XGN, LG [max_rows, vocab])
+        SeqSlot* tguard = nullptr;         // a chain with drafts: one guard entry per tile of kGcMaxTok rows, pos -1 when no row of the tile carries logits
+                                           // (serve_tile_guard.hpp) -- what that tile's classifier launches get as their row table
     } sv;
 };
 
@@ -408,18 +411,25 @@ struct BlobCarver {
     }
 };
 int check_slots_rows(const char* entry, int n_slots, int max_rows);
-void serve_state_free(rama_ctx::ServeState& sv);            // the allocations; the stream is idle.  The caller resets its state
+void serve_state_free(rama_ctx::ServeState& sv);            // the allocations, the drafting records included; the stream is idle.  The caller resets its state
 // the tables, admission records and rings of a chain of this geometry; `more` carves further tables out of the same blob
 int serve_state_alloc(rama_ctx* c, rama_ctx::ServeState& sv, int seq_len, int n_slots, int max_rows, int max_new_cap, void (*more)(BlobCarver&, void*), void* arg);
+// the same for a chain that may draft: with `spec` the drafting tables come out of the same blob, and the spec admission records are made
+int check_spec_caps(const char* entry, int n_draft_cap, int hint_cap);
+int serve_state_alloc_spec(rama_ctx* c, rama_ctx::ServeState& sv, int seq_len, int n_slots, int max_rows, int max_new_cap, bool spec, int n_draft_cap, int hint_cap);
 bool serve_slot_live(const rama_ctx::ServeState& sv, int slot);
 // an admission's refusals in their order, in the calling entry's words: the head up to the slot index, then -- behind the caller's own check of
 // the run state against its model -- the tail; then the install (the record's copy and serve_install_kernel, stream-ordered)
-struct ServeNames { const char* admit; const char* admit_at; const char* begin; };      // a chain's entries as its refusals name them
+struct ServeNames { const char* admit; const char* admit_at; const char* begin; const char* admit_spec; const char* begin_spec; };      // a chain's entries as its refusals name them
 int serve_admit_head(const ServeNames& names, const rama_ctx::ServeState& sv, bool live, int slot, const rama_run_state* state, const int32_t* context_host, const rama_q8_serve_plan* plan);
 int serve_admit_tail(const ServeNames& names, const rama_ctx::ServeState& sv, const rama_config& cfg, int slot, const rama_run_state* state, const int32_t* context_host, int n_context,
                      int n_cached, const rama_q8_serve_plan* plan);
 int serve_admit_install(rama_ctx* c, rama_ctx::ServeState& sv, int slot, const rama_run_state* state, const int32_t* context_host, int n_context, int n_cached,
                         const rama_q8_serve_plan* plan);
+// the drafting half of an admission, behind the tail: spec != NULL is an _admit_spec entry's record -- refused on a chain begun without drafts --, and
+// the install puts the slot's drafting fields and hint in (spec == NULL: n_draft = 0); nothing to do on a chain begun without drafts
+int serve_admit_spec_check(const ServeNames& names, const rama_ctx::ServeState& sv, int vocab_size, const rama_q8_serve_spec* spec);
+int serve_admit_spec_install(rama_ctx* c, rama_ctx::ServeState& sv, int slot, const rama_q8_serve_spec* spec);
 // the run state s is about to be freed: true when a slot whose occupant the host cannot yet see DONE still uses it (a finished occupant's is its owner's again)
 bool serve_state_uses(rama_ctx::ServeState& sv, const rama_run_state* s);
 int serve_poll_ring(const char* entry, const rama_ctx::ServeState& sv, int slot, int from, int32_t* out_host, int max_tokens, int* n_ready, int* finished, int* generation);
@@ -429,6 +439,13 @@ int launch_serve_schedule(rama_ctx* c, const ServeTables& t);
 int launch_serve_embed(rama_ctx* c, float* X, const float* emb, const ServeTables& t, int dim);      // rows at position -1 keep what they hold
 int launch_serve_gather(rama_ctx* c, float* XG, const float* X, const ServeTables& t, int dim);
 int launch_serve_pick(rama_ctx* c, const ServeTables& t, const float* logits, int V, bool sampled);
+// ... and q8_serve_spec.hpp's, for the step of a chain with drafts: the drafts, the scheduler, the pick over one logits row per ROW (`sampled`: the
+// ordering launches over the rows' sampler records go first), the accept rule
+int launch_serve_draft(rama_ctx* c, const ServeTables& t, const ServeSpecTables& st);
+int launch_serve_spec_schedule(rama_ctx* c, const ServeTables& t, const ServeSpecTables& st);
+int launch_serve_spec_pick(rama_ctx* c, const ServeTables& t, const ServeSpecTables& st, const float* logits, int V, bool sampled);
+int launch_serve_spec_accept(rama_ctx* c, const ServeTables& t, const ServeSpecTables& st);
+int serve_spec_report(rama_ctx* c, const rama_ctx::ServeState& sv, rama_q8_serve_spec_report* out);
 
 // the pending run of recorded 1:1 ops is issued by whatever enters the library next: first statement of every entry point
 // that enqueues, synchronises or changes a setting

@@ -70,13 +70,13 @@ void serve_state_free(rama_ctx::ServeState& sv) {
     if (sv.pinned) hipHostFree(sv.pinned);
     if (sv.ring) hipHostFree(sv.ring);
     if (sv.done) hipHostFree(sv.done);
+    hipFree(sv.sstage);
+    if (sv.spinned) hipHostFree(sv.spinned);
 }
 static void serve_release(rama_ctx* c) {
     auto& sv = c->q8s;
     destroy_graph(sv.cg);
     serve_state_free(sv);
-    hipFree(sv.sstage);
-    if (sv.spinned) hipHostFree(sv.spinned);
     sv = rama_ctx::Q8Serve();
 }
 // ... and the chained batch's
@@ -970,8 +970,7 @@ static int serve_begin(rama_ctx* c, const rama_config* cfg, const rama_q8_weight
     const int V = cfg->vocab_size;
     const bool sampler = V > 1 && V <= kToppBlock * kToppMaxBlocks;
     REQUIRE(sampler || V % 4 == 0, RAMA_EUNSUP, "q8_serve_begin: vocab_size % 4 != 0 needs vocab_size <= 32768");
-    REQUIRE(n_draft_cap >= 0 && n_draft_cap <= kSpecMaxDraft, RAMA_EINVAL, "q8_serve_begin_spec: n_draft_cap outside 0..15");
-    REQUIRE(hint_cap >= 0 && hint_cap < kSpecHintBit, RAMA_EINVAL, "q8_serve_begin_spec: hint_cap outside [0, 2^30)");
+    CHECKED(check_spec_caps("q8_serve_begin_spec", n_draft_cap, hint_cap));
     if (set_device(c)) return 1;
     HIPCHK(hipStreamSynchronize(c->stream));
     serve_release(c);
@@ -979,10 +978,25 @@ static int serve_begin(rama_ctx* c, const rama_config* cfg, const rama_q8_weight
     Q8BatchScratch b{};
     rc = q8_chain_scratch(c, cfg, w->group_size, sampler ? (spec ? max_rows : n_slots) : 0, &b); if (rc) return rc;
     auto& sv = c->q8s;
+    rc = serve_state_alloc_spec(c, sv, cfg->seq_len, n_slots, max_rows, max_new_cap, spec, n_draft_cap, hint_cap); if (rc) return rc;
+    sv.cfg = *cfg; sv.w = *w; sv.sampler = sampler;
+    sv.captures = 0;
+    sv.live = true;
+    return 0;
+}
+
+// a drafting chain's two caps, in the calling entry's words
+int check_spec_caps(const char* entry, int n_draft_cap, int hint_cap) {
+    REFUSE_UNLESS(n_draft_cap >= 0 && n_draft_cap <= kSpecMaxDraft, entry, "n_draft_cap outside 0..15");
+    REFUSE_UNLESS(hint_cap >= 0 && hint_cap < kSpecHintBit, entry, "hint_cap outside [0, 2^30)");
+    return 0;
+}
+
+int serve_state_alloc_spec(rama_ctx* c, rama_ctx::ServeState& sv, int seq_len, int n_slots, int max_rows, int max_new_cap, bool spec, int n_draft_cap, int hint_cap) {
     ServeSpecTables& st = sv.st;
     const size_t N = (size_t)n_slots, H = (size_t)hint_cap;
     struct More { ServeSpecTables* st; size_t N, R, H; bool spec; } more{&st, N, (size_t)max_rows, H, spec};
-    rc = serve_state_alloc(c, sv, cfg->seq_len, n_slots, max_rows, max_new_cap, [](BlobCarver& bc, void* arg) {
+    const int rc = serve_state_alloc(c, sv, seq_len, n_slots, max_rows, max_new_cap, [](BlobCarver& bc, void* arg) {
         const More& m = *static_cast<const More*>(arg);
         if (!m.spec) return;      // the drafting tables: nothing of them on a chain begun without drafts
         ServeSpecTables& st = *m.st;
@@ -996,10 +1010,7 @@ static int serve_begin(rama_ctx* c, const rama_config* cfg, const rama_q8_weight
         HIPCHK(hipHostMalloc(&sv.spinned, N * sv.srec_bytes, hipHostMallocDefault));
         st.hint_cap = hint_cap;
     }
-    sv.cfg = *cfg; sv.w = *w; sv.sampler = sampler;
-    sv.captures = 0;
     sv.spec = spec; sv.n_draft_cap = n_draft_cap; sv.hint_cap = hint_cap;
-    sv.live = true;
     return 0;
 }
 
@@ -1064,7 +1075,7 @@ static int refuse_as(int code, const char* entry, const char* what, int line) {
     return fail(code, msg, __FILE__, line);
 }
 #define ADMIT_UNLESS(cond, what) do { if (!(cond)) return refuse_as(RAMA_EINVAL, names.admit, (what), __LINE__); } while (0)
-static const ServeNames kQ8ServeNames{"q8_serve_admit", "q8_serve_admit_at", "rama_q8_serve_begin"};
+static const ServeNames kQ8ServeNames{"q8_serve_admit", "q8_serve_admit_at", "rama_q8_serve_begin", "q8_serve_admit_spec", "rama_q8_serve_begin_spec"};
 int serve_admit_head(const ServeNames& names, const rama_ctx::ServeState& sv, bool live, int slot, const rama_run_state* state, const int32_t* context_host,
                      const rama_q8_serve_plan* plan) {
     // everything is checked before anything of the running chain is touched
@@ -1116,6 +1127,29 @@ int serve_admit_install(rama_ctx* c, rama_ctx::ServeState& sv, int slot, const r
     LAUNCHCHK();
     return 0;
 }
+int serve_admit_spec_check(const ServeNames& names, const rama_ctx::ServeState& sv, int vocab_size, const rama_q8_serve_spec* spec) {
+    if (!spec) return 0;
+    char what[3][112];
+    snprintf(what[0], sizeof what[0], "the chain was not begun with %s", names.begin_spec);
+    snprintf(what[1], sizeof what[1], "n_draft beyond %s's n_draft_cap", names.begin_spec);
+    snprintf(what[2], sizeof what[2], "bad hint, or one beyond %s's hint_cap", names.begin_spec);
+    REFUSE_UNLESS(sv.spec, names.admit_spec, what[0]);
+    return check_drafting(names.admit_spec, *spec, sv.n_draft_cap, what[1], sv.hint_cap, what[2], vocab_size);
+}
+int serve_admit_spec_install(rama_ctx* c, rama_ctx::ServeState& sv, int slot, const rama_q8_serve_spec* spec) {
+    if (!sv.spec) return 0;
+    // the same way as serve_admit_install, the slot's own pinned spec record
+    char* srec = sv.spinned + (size_t)slot * sv.srec_bytes;
+    ServeSpecSlot g{};
+    g.n_draft = spec ? spec->n_draft : 0; g.ngram = spec ? spec->ngram : 1; g.n_hint = spec ? spec->n_hint : 0;
+    memcpy(srec, &g, sizeof g);
+    if (g.n_hint) memcpy(srec + sizeof g, spec->hint, sizeof(int) * (size_t)g.n_hint);
+    char* sdst = sv.sstage + (size_t)slot * sv.srec_bytes;
+    HIPCHK(hipMemcpyAsync(sdst, srec, sizeof g + sizeof(int) * (size_t)g.n_hint, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(serve_spec_install_kernel, dim3(1), dim3(256), 0, c->stream, sv.st, slot, reinterpret_cast<const ServeSpecSlot*>(sdst));
+    LAUNCHCHK();
+    return 0;
+}
 
 // rama_q8_serve_admit (n_cached 0) and rama_q8_serve_admit_at: the slot starts PROMPT at cursor = n_cached, over rows 0 .. n_cached - 1 that
 // earlier work on the stream has put into the run state's caches
@@ -1129,24 +1163,10 @@ static int serve_admit(rama_ctx* c, int slot, const rama_run_state* state, const
     CHECKED(serve_admit_head(kQ8ServeNames, sv, sv.live, slot, state, context_host, plan));
     int rc = q8_check(c, &sv.cfg, &sv.w, state); if (rc) return rc;
     CHECKED(serve_admit_tail(kQ8ServeNames, sv, sv.cfg, slot, state, context_host, n_context, n_cached, plan));
-    if (spec) {
-        REQUIRE(sv.spec, RAMA_EINVAL, "q8_serve_admit_spec: the chain was not begun with rama_q8_serve_begin_spec");
-        CHECKED(check_drafting("q8_serve_admit_spec", *spec, sv.n_draft_cap, "n_draft beyond rama_q8_serve_begin_spec's n_draft_cap", sv.hint_cap,
-                               "bad hint, or one beyond rama_q8_serve_begin_spec's hint_cap", sv.cfg.vocab_size));
-    }
+    CHECKED(serve_admit_spec_check(kQ8ServeNames, sv, sv.cfg.vocab_size, spec));
     if (set_device(c)) return 1;
     rc = serve_admit_install(c, sv, slot, state, context_host, n_context, n_cached, plan); if (rc) return rc;
-    if (sv.spec) {      // the same way, the slot's own pinned spec record
-        char* srec = sv.spinned + (size_t)slot * sv.srec_bytes;
-        ServeSpecSlot g{};
-        g.n_draft = spec ? spec->n_draft : 0; g.ngram = spec ? spec->ngram : 1; g.n_hint = spec ? spec->n_hint : 0;
-        memcpy(srec, &g, sizeof g);
-        if (g.n_hint) memcpy(srec + sizeof g, spec->hint, sizeof(int) * (size_t)g.n_hint);
-        char* sdst = sv.sstage + (size_t)slot * sv.srec_bytes;
-        HIPCHK(hipMemcpyAsync(sdst, srec, sizeof g + sizeof(int) * (size_t)g.n_hint, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(serve_spec_install_kernel, dim3(1), dim3(256), 0, c->stream, sv.st, slot, reinterpret_cast<const ServeSpecSlot*>(sdst));
-        LAUNCHCHK();
-    }
+    rc = serve_admit_spec_install(c, sv, slot, spec); if (rc) return rc;
     sv.states[slot] = *state; sv.occupied[slot] = 1; sv.gen[slot]++;
     return 0;
 }
@@ -1186,11 +1206,15 @@ int rama_q8_kv_fork(rama_ctx* c, const rama_config* cfg, const rama_run_state* s
         for (size_t j = 0; j < i; j++)
             REQUIRE(!ranges_overlap(caches[i], total, caches[j], total), RAMA_EINVAL,
                     "q8_kv_fork: a destination shares a cache with the source or with another destination");
-    const auto& sv = c->q8s;
-    for (int d = 0; d < n_dst; d++)
-        for (int j = 0; j < sv.n_slots; j++)
-            REQUIRE(!serve_slot_live(sv, j) || (sv.states[j].key_cache != dsts[d].key_cache && sv.states[j].value_cache != dsts[d].value_cache),
-                    RAMA_EINVAL, "q8_kv_fork: a destination is in a live slot of the serving chain");
+    // the Q8 serving chain's slots and the fp32 one's: the fork serves both stacks
+    const struct { const rama_ctx::ServeState* sv; const char* what; } chains[2] = {
+        {&c->q8s, "q8_kv_fork: a destination is in a live slot of the serving chain"},
+        {&c->sv, "q8_kv_fork: a destination is in a live slot of the fp32 serving chain (rama_serve_*)"}};
+    for (const auto& ch : chains)
+        for (int d = 0; d < n_dst; d++)
+            for (int j = 0; j < ch.sv->n_slots; j++)
+                REQUIRE(!serve_slot_live(*ch.sv, j) || (ch.sv->states[j].key_cache != dsts[d].key_cache && ch.sv->states[j].value_cache != dsts[d].value_cache),
+                        RAMA_EINVAL, ch.what);
     if (n_rows == 0) return 0;
     const size_t span = (size_t)n_rows * (size_t)cfg->dim, reach = layer * (size_t)(cfg->n_layers - 1) + span;
     for (int d = 0; d < n_dst; d++) { RAMA_WRITES(c, dsts[d].key_cache, reach); RAMA_WRITES(c, dsts[d].value_cache, reach); }
@@ -1239,6 +1263,35 @@ int launch_serve_pick(rama_ctx* c, const ServeTables& t, const float* logits, in
     LAUNCHCHK();
     return 0;
 }
+// ... and q8_serve_spec.hpp's, for the step of either chain with drafts
+int launch_serve_draft(rama_ctx* c, const ServeTables& t, const ServeSpecTables& st) {
+    hipLaunchKernelGGL(serve_draft_kernel, dim3(t.n_slots), dim3(kServeDraftThreads), 0, c->stream, t, st);
+    LAUNCHCHK();
+    return 0;
+}
+int launch_serve_spec_schedule(rama_ctx* c, const ServeTables& t, const ServeSpecTables& st) {
+    hipLaunchKernelGGL(serve_spec_schedule_kernel, dim3(1), dim3(kServeMaxSlots), 0, c->stream, t, st);
+    LAUNCHCHK();
+    return 0;
+}
+// the pick over one logits row per ROW of the step's table, logits [max_rows, V]; `sampled`: the ordering launches over the rows' sampler records go first
+int launch_serve_spec_pick(rama_ctx* c, const ServeTables& t, const ServeSpecTables& st, const float* logits, int V, bool sampled) {
+    ServeSpecPickParams fin{};
+    fin.t = t; fin.st = st;
+    fin.r = PickRows{logits, (size_t)V, V, nullptr, nullptr, nullptr, 0};
+    if (sampled) {
+        const int rc = enqueue_topp_batch_order(c, st.rrow, t.max_rows, logits, (size_t)V, V, nullptr); if (rc) return rc;
+        fin.r.keys = c->tb.keys; fin.r.vals = c->tb.vals; fin.r.m = c->tb.m; fin.r.rstride = c->tb.rstride;
+    }
+    hipLaunchKernelGGL(serve_spec_pick_kernel, dim3(t.max_rows), dim3(1024), 0, c->stream, fin);
+    LAUNCHCHK();
+    return 0;
+}
+int launch_serve_spec_accept(rama_ctx* c, const ServeTables& t, const ServeSpecTables& st) {
+    hipLaunchKernelGGL(serve_spec_accept_kernel, dim3(t.n_slots), dim3(64), 0, c->stream, t, st);
+    LAUNCHCHK();
+    return 0;
+}
 
 // one step: the scheduler, the pass over its row table, the logits of the rows that carry them, the pick and the slots' state machine
 static int enqueue_q8_serve_step(rama_ctx* c, const Q8BatchScratch& b) {
@@ -1257,20 +1310,11 @@ static int enqueue_q8_serve_step(rama_ctx* c, const Q8BatchScratch& b) {
 // flagged row's pick, the accept rule per slot
 static int enqueue_q8_serve_spec_step(rama_ctx* c, const Q8BatchScratch& b) {
     auto& sv = c->q8s;
-    const int R = sv.max_rows, N = sv.n_slots;
-    hipLaunchKernelGGL(serve_draft_kernel, dim3(N), dim3(kServeDraftThreads), 0, c->stream, sv.t, sv.st);
-    LAUNCHCHK();
-    hipLaunchKernelGGL(serve_spec_schedule_kernel, dim3(1), dim3(kServeMaxSlots), 0, c->stream, sv.t, sv.st);
-    LAUNCHCHK();
-    int rc = enqueue_q8_batch_pass(c, &sv.cfg, &sv.w, b, sv.t.row_tok, sv.t.rows, R); if (rc) return rc;
-    ServeSpecPickParams fin{};
-    fin.t = sv.t; fin.st = sv.st;
-    rc = enqueue_q8_pick_rows(c, b, sv.cfg.vocab_size, sv.sampler, sv.st.rrow, R, &fin.r); if (rc) return rc;
-    hipLaunchKernelGGL(serve_spec_pick_kernel, dim3(R), dim3(1024), 0, c->stream, fin);
-    LAUNCHCHK();
-    hipLaunchKernelGGL(serve_spec_accept_kernel, dim3(N), dim3(64), 0, c->stream, sv.t, sv.st);
-    LAUNCHCHK();
-    return 0;
+    int rc = launch_serve_draft(c, sv.t, sv.st); if (rc) return rc;
+    rc = launch_serve_spec_schedule(c, sv.t, sv.st); if (rc) return rc;
+    rc = enqueue_q8_batch_pass(c, &sv.cfg, &sv.w, b, sv.t.row_tok, sv.t.rows, sv.max_rows); if (rc) return rc;
+    rc = launch_serve_spec_pick(c, sv.t, sv.st, b.LG, sv.cfg.vocab_size, sv.sampler); if (rc) return rc;
+    return launch_serve_spec_accept(c, sv.t, sv.st);
 }
 
 int rama_q8_serve_steps(rama_ctx* c, int n_steps) {
@@ -1354,7 +1398,10 @@ int rama_q8_serve_stats(rama_ctx* c, rama_q8_serve_report* out) {
 int rama_q8_serve_spec_stats(rama_ctx* c, rama_q8_serve_spec_report* out) {
     RAMA_ENTER(c);
     REQUIRE(c && out && c->q8s.n_slots > 0 && c->q8s.spec, RAMA_EINVAL, "q8_serve_spec_stats: no chain begun with rama_q8_serve_begin_spec");
-    auto& sv = c->q8s;
+    return serve_spec_report(c, c->q8s, out);
+}
+// what either chain's _spec_stats entry does behind its refusal
+int serve_spec_report(rama_ctx* c, const rama_ctx::ServeState& sv, rama_q8_serve_spec_report* out) {
     { const int rh = q8_drain(c); if (rh) return rh; }
     memset(out, 0, sizeof *out);
     unsigned long long cnt[4], sched[2];

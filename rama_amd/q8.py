@@ -479,19 +479,20 @@ def common_prefix(a, b) -> int:
     return n
 
 
-def serve_spec_sizes(n_draft, ngram, hint_cap):
-    """the checked drafting sizes of a Q8Server; ValueError for what rama_q8_serve_begin_spec would refuse.  No library call."""
+def serve_spec_sizes(n_draft, ngram, hint_cap, who="Q8Server"):
+    """the checked drafting sizes of a Q8Server (or, `who`, a Server); ValueError for what rama_q8_serve_begin_spec would refuse.
+    No library call."""
     n_draft, ngram, hint_cap = int(n_draft), int(ngram), int(hint_cap)
-    _check_drafting("Q8Server", n_draft, ngram)
+    _check_drafting(who, n_draft, ngram)
     if hint_cap < 0 or (hint_cap and not n_draft):
-        raise ValueError(f"Q8Server: hint_cap {hint_cap} (>= 0, and 0 on a server without drafts)")
+        raise ValueError(f"{who}: hint_cap {hint_cap} (>= 0, and 0 on a server without drafts)")
     return n_draft, ngram, hint_cap
 
 
-def serve_spec_request(cfg, n_draft_cap, ngram, hint_cap, n_draft=None, hint=None):
+def serve_spec_request(cfg, n_draft_cap, ngram, hint_cap, n_draft=None, hint=None, who="Q8Server"):
     """the checked drafting arguments of Q8Server.submit: (n_draft, ngram, hint tokens); ValueError for everything
     rama_q8_serve_admit_spec would refuse in them.  No library call."""
-    what = "Q8Server.submit"
+    what = who + ".submit"
     K = n_draft_cap if n_draft is None else int(n_draft)
     _check_n_draft(what, K, n_draft_cap, f"the server's n_draft = {n_draft_cap}")
     toks = [] if hint is None else _tokens(hint, cfg.vocab_size, what + " hint")
@@ -578,11 +579,12 @@ class ServeLoop:
     """What a serving chain's host loop does whatever the model: the queue, the slots' engines, the mirror of the device's slot table kept
     by the host plan (rama_q8_serve_plan_step), the steps to the next finish, admissions behind the steps in flight, the host-visible
     rings.  Q8Server (rama_q8_serve_*) and rama_amd.Server (rama_serve_*, parity mode) are this loop over their entries' family; a
-    subclass says how a chain begins (_begin), what engine a slot gets (_new_engine) and how a request goes in (_admit_slot)."""
+    subclass says how a chain begins (_begin), what engine a slot gets (_new_engine) and how a request goes in (_admit_slot).
+    CachingServeLoop below adds what both servers offer on request: prompt caching and drafts."""
 
     ABI = None         # the C entries' family: <ABI>_begin / _admit / _steps / _poll / _stats / _end
     NAME = "ServeLoop"
-    spec = False       # with drafts the rows of a step depend on what is accepted: no host plan (Q8Server only)
+    spec = False       # with drafts the rows of a step depend on what is accepted: no host plan (CachingServeLoop)
 
     def _call(self, name, *args):
         entry = f"{self.ABI}_{name}"
@@ -802,31 +804,16 @@ class ServeLoop:
             self._own, self._eng = [None] * self.n_slots, [None] * self.n_slots
 
 
-class Q8Server(ServeLoop):
-    """continuous batching over one Q8Model (rama_q8_serve_begin / _admit / _steps / _poll): n_slots sequence slots share weight
-    passes of max_rows rows; a finished sequence frees its slot for the next queued request while the others run on, and a new
-    request's context is ingested in chunks next to the decoding slots.  Every request's tokens are those Q8Engine.generate gives
-    it alone.  One serving chain per device context at a time.
+class CachingServeLoop(ServeLoop):
+    """ServeLoop with what both serving chains offer on request, one copy for Q8Server (rama_q8_serve_*) and rama_amd.Server
+    (rama_serve_*): prompt caching -- submit(n_cached=), the donor pool of prefix_cache=k, the fork (rama_q8_kv_fork: the KV cache
+    is fp32 in both stacks) and <ABI>_admit_at -- and drafts -- <ABI>_begin_spec / _admit_spec / _spec_stats and the run loop of a
+    chain whose steps the host cannot foresee."""
 
-    Prompt caching (DESIGN.md 8.4).  submit(..., n_cached=n) admits over rows 0..n-1 that the caller's engine already holds
-    (a chat's next turn on the same engine).  prefix_cache=k keeps a pool of at most k donor engines: a request submitted with
-    retain=True leaves its engine there when it finishes, keyed by the tokens whose rows it holds; every later request is
-    matched against the pool at its admission, the longest shared prefix is forked into its engine (rama_q8_kv_fork) and the
-    slot starts at that cursor (rama_q8_serve_admit_at).  The tokens are the same with the cache on and off.
-
-    Drafts (DESIGN.md 8.6).  n_draft=K > 0 begins the chain with rama_q8_serve_begin_spec: a decoding request guesses up to K
-    tokens per step by looking its last <= ngram tokens up in its own text and in the hint it was submitted with (at most
-    hint_cap tokens), the guesses take the rows of the step that no slot wants -- prompts first -- and are verified in the same
-    weight pass.  The tokens are the same with drafts on and off; n_draft=0 (the default) is the plain chain."""
-
-    ABI = "rama_q8_serve"
-    NAME = "Q8Server"
-
-    def __init__(self, model: Q8Model, n_slots: int, max_rows=None, max_new_cap: int = 256, prefix_cache: int = 0, n_draft: int = 0,
-                 ngram: int = 3, hint_cap: int = 0):
-        serve_sizes(model.cfg, n_slots, max_rows, max_new_cap)      # (every size is checked before any library call, in this order)
-        self.n_draft, self.ngram, self.hint_cap = serve_spec_sizes(n_draft, ngram, hint_cap)
-        self.spec = self.n_draft > 0                      # n_draft == 0: the plain chain, rama_q8_serve_begin
+    def _start_caching(self, model, n_slots, max_rows, max_new_cap, prefix_cache, n_draft, ngram, hint_cap):
+        serve_sizes(model.cfg, n_slots, max_rows, max_new_cap, self.NAME)      # (every size is checked before any library call, in this order)
+        self.n_draft, self.ngram, self.hint_cap = serve_spec_sizes(n_draft, ngram, hint_cap, self.NAME)
+        self.spec = self.n_draft > 0                      # n_draft == 0: the plain chain, <ABI>_begin
         self.pool = PrefixPool(prefix_cache)              # (raises before any library call)
         self._cached = {}                                 # handle -> the n_cached it was admitted with
         self._drafts = {}                                 # handle -> (n_draft, ngram, hint tokens)
@@ -837,19 +824,13 @@ class Q8Server(ServeLoop):
         if not self.spec:
             return super()._begin()
         m = self.model
-        check(self.device.lib.rama_q8_serve_begin_spec(self.device.ctx, C.byref(m.ccfg), C.byref(m.weights), self.n_slots, self.max_rows,
-                                                       self.max_new_cap, self.n_draft, self.hint_cap), "rama_q8_serve_begin_spec")
-
-    def _new_engine(self):
-        e = Q8Engine(self.device, self.model)
-        self._mine.append(e)
-        return e
+        self._call("begin_spec", C.byref(m.ccfg), C.byref(m.weights), self.n_slots, self.max_rows, self.max_new_cap, self.n_draft, self.hint_cap)
 
     # -- requests
     def submit(self, context, max_new, temperature=0.0, topp=0.9, u=TOPP_U_CPU, stop_token=None, engine=None, n_cached=0,
                retain=False, n_draft=None, hint=None):
         """queue a request -> its handle.  It is admitted at once if a slot is free, else when one finishes (step / run).
-        engine: the Q8Engine whose run state the sequence uses (default: one the server owns for the slot).
+        engine: the engine whose run state the sequence uses (default: one the server owns for the slot).
         n_cached: rows 0..n_cached-1 of `engine` already hold context[0..n_cached) -- written by work enqueued earlier on the
         device's stream; the slot feeds the rest (at most n_context - 1: the final position is always fed).  Such a request is
         not matched against the prefix cache.
@@ -858,17 +839,17 @@ class Q8Server(ServeLoop):
         n_draft, hint: on a server made with n_draft > 0, the drafts per step of this request (default: the server's; 0: none)
         and a token list to look up in besides the request's own text (at most hint_cap tokens).  The tokens are the same
         whatever they are."""
-        ctx, plan = serve_plan(self.cfg, context, max_new, temperature, topp, u, stop_token, self.max_new_cap, n_cached)
-        draft = serve_spec_request(self.cfg, self.n_draft, self.ngram, self.hint_cap, n_draft, hint)
+        ctx, plan = serve_plan(self.cfg, context, max_new, temperature, topp, u, stop_token, self.max_new_cap, n_cached, self.NAME)
+        draft = serve_spec_request(self.cfg, self.n_draft, self.ngram, self.hint_cap, n_draft, hint, self.NAME)
         n_cached = int(n_cached)
         if n_cached and engine is None:
-            raise ValueError("Q8Server.submit: n_cached needs the engine that holds the rows")
+            raise ValueError(f"{self.NAME}.submit: n_cached needs the engine that holds the rows")
         if engine is not None and engine.model is not self.model:
-            raise ValueError("Q8Server.submit: the engine belongs to another Q8Model")
+            raise ValueError(f"{self.NAME}.submit: the engine belongs to another {type(self.model).__name__}")
         if engine is not None and any(e is engine for e in self._engines_in_use()):
-            raise ValueError("Q8Server.submit: the engine already serves a queued or running request")
+            raise ValueError(f"{self.NAME}.submit: the engine already serves a queued or running request")
         if engine is not None and engine in self.pool:
-            raise ValueError("Q8Server.submit: the engine is a donor of the prefix cache")
+            raise ValueError(f"{self.NAME}.submit: the engine is a donor of the prefix cache")
         h = self._submit(ctx, plan, engine, n_cached, retain)
         self._drafts[h] = draft
         self._admit()
@@ -889,10 +870,9 @@ class Q8Server(ServeLoop):
             K, N, hint = self._drafts[h]
             harr = _i32(hint)
             srec = rama_q8_serve_spec(K, N, harr if hint else None, len(hint))
-            check(L.rama_q8_serve_admit_spec(ctx, slot, C.byref(eng.state), arr, len(toks), n_cached, C.byref(rec), C.byref(srec)),
-                  "rama_q8_serve_admit_spec")
+            self._call("admit_spec", slot, C.byref(eng.state), arr, len(toks), n_cached, C.byref(rec), C.byref(srec))
         elif n_cached:
-            check(L.rama_q8_serve_admit_at(ctx, slot, C.byref(eng.state), arr, len(toks), n_cached, C.byref(rec)), "rama_q8_serve_admit_at")
+            self._call("admit_at", slot, C.byref(eng.state), arr, len(toks), n_cached, C.byref(rec))
         else:
             self._call("admit", slot, C.byref(eng.state), arr, len(toks), C.byref(rec))
         return n_cached
@@ -921,12 +901,12 @@ class Q8Server(ServeLoop):
     MIN_CACHED = 2     # a shorter match is not worth a launch: every context shares its first token (BOS) with every donor
 
     def run(self, on_token=None):
-        """ServeLoop.run; with drafts, _run_spec"""
-        return self._run_spec(on_token) if self.spec else super().run(on_token)
+        """ServeLoop.run; with drafts, _run_drafting"""
+        return self._run_drafting(on_token) if self.spec else super().run(on_token)
 
     SPEC_BLOCK = 4     # with drafts: at most this many steps between two looks at the device's slot table
 
-    def _run_spec(self, on_token=None):
+    def _run_drafting(self, on_token=None):
         """run() on a server with drafts.  A slot may finish earlier than the host plan foresees, so the plan -- one token per
         DECODE slot and step -- is an upper bound: the slot table is taken from the device before every block, the steps to the
         next finish by that plan -- SPEC_BLOCK at most -- are enqueued, and the finished words alone say who has finished.  A request that waits is
@@ -938,7 +918,7 @@ class Q8Server(ServeLoop):
             self._admit()
             if all(h is None for h in self._req):
                 if self._queue:
-                    raise RuntimeError("Q8Server.run: requests are waiting but no slot can take them")
+                    raise RuntimeError(f"{self.NAME}.run: requests are waiting but no slot can take them")
                 return
             self._count_and_enqueue(max(min(self._steps_to_next_finish(), self.SPEC_BLOCK), 1))
             while True:
@@ -948,17 +928,48 @@ class Q8Server(ServeLoop):
                     break
 
     def stats(self):
-        """rama_q8_serve_stats (synchronises): the device's counters, the slot table, the last step's row table; rows_cached is the
-        host's sum of n_cached over the admissions (context positions taken from cached rows instead of being fed)"""
+        """<ABI>_stats (synchronises): the device's counters, the slot table, the last step's row table; rows_cached is the
+        host's sum of n_cached over the admissions (context positions taken from cached rows instead of being fed); with drafts,
+        spec = <ABI>_spec_stats"""
         out = dict(super().stats(), rows_cached=self.rows_cached)
         if self.spec:
             q = rama_q8_serve_spec_report()
-            check(self.device.lib.rama_q8_serve_spec_stats(self.device.ctx, C.byref(q)), "rama_q8_serve_spec_stats")
+            self._call("spec_stats", C.byref(q))
             out["spec"] = serve_spec_report(q)
         return out
 
     def _closed(self):
         self.pool.clear()                             # (a caller's engine that was a donor is the caller's again)
+
+
+class Q8Server(CachingServeLoop):
+    """continuous batching over one Q8Model (rama_q8_serve_begin / _admit / _steps / _poll): n_slots sequence slots share weight
+    passes of max_rows rows; a finished sequence frees its slot for the next queued request while the others run on, and a new
+    request's context is ingested in chunks next to the decoding slots.  Every request's tokens are those Q8Engine.generate gives
+    it alone.  One serving chain per device context at a time.
+
+    Prompt caching (DESIGN.md 8.4).  submit(..., n_cached=n) admits over rows 0..n-1 that the caller's engine already holds
+    (a chat's next turn on the same engine).  prefix_cache=k keeps a pool of at most k donor engines: a request submitted with
+    retain=True leaves its engine there when it finishes, keyed by the tokens whose rows it holds; every later request is
+    matched against the pool at its admission, the longest shared prefix is forked into its engine (rama_q8_kv_fork) and the
+    slot starts at that cursor (rama_q8_serve_admit_at).  The tokens are the same with the cache on and off.
+
+    Drafts (DESIGN.md 8.6).  n_draft=K > 0 begins the chain with rama_q8_serve_begin_spec: a decoding request guesses up to K
+    tokens per step by looking its last <= ngram tokens up in its own text and in the hint it was submitted with (at most
+    hint_cap tokens), the guesses take the rows of the step that no slot wants -- prompts first -- and are verified in the same
+    weight pass.  The tokens are the same with drafts on and off; n_draft=0 (the default) is the plain chain."""
+
+    ABI = "rama_q8_serve"
+    NAME = "Q8Server"
+
+    def __init__(self, model: Q8Model, n_slots: int, max_rows=None, max_new_cap: int = 256, prefix_cache: int = 0, n_draft: int = 0,
+                 ngram: int = 3, hint_cap: int = 0):
+        self._start_caching(model, n_slots, max_rows, max_new_cap, prefix_cache, n_draft, ngram, hint_cap)
+
+    def _new_engine(self):
+        e = Q8Engine(self.device, self.model)
+        self._mine.append(e)
+        return e
 
 
 # ------------------------------------------------------------------ the speculative chain: n-gram lookup drafts (rama_q8_spec_*)

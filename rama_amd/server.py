@@ -1,32 +1,32 @@
-"""rama_amd.Server -- continuous batching over an fp32 Model in parity mode (rama_serve_*, DESIGN.md 8.7): the counterpart of
-Q8Server without prompt caching and drafts.  Both are rama_amd.q8.ServeLoop -- the queue, the mirror of the slot table, the steps to
-the next finish by the host plan, admissions behind the steps in flight, the rings -- over their own entries and engines."""
+"""rama_amd.Server -- continuous batching over an fp32 Model in parity mode (rama_serve_*, DESIGN.md 8.7 and 8.8): the counterpart of
+Q8Server.  Both are rama_amd.q8.CachingServeLoop -- the queue, the mirror of the slot table, the steps to the next finish by the host
+plan, admissions behind the steps in flight, the rings, the prefix cache and the run loop of a chain with drafts -- over their own
+entries and engines."""
 from __future__ import annotations
 
 from .engine import Engine, Model
-from .q8 import ServeLoop, TOPP_U_CPU, serve_plan
+from .q8 import CachingServeLoop
 
 
-class Server(ServeLoop):
+class Server(CachingServeLoop):
     """n_slots sequence slots share parity-mode weight passes of max_rows rows (tiles of 32).  Every request's tokens are those
     Engine.generate gives it alone in parity mode -- the reference's own.  The device context must be in parity mode
-    ("ref_order" = 1) and stay there.  One fp32 serving chain per device context; a Q8Server may be live next to it."""
+    ("ref_order" = 1) and stay there.  One fp32 serving chain per device context; a Q8Server may be live next to it.
+
+    Prompt caching and drafts are Q8Server's, argument for argument, and off by default: submit(..., n_cached=n)
+    admits over rows the caller's engine already holds (rama_serve_admit_at), prefix_cache=k keeps k donor engines whose shared
+    prefixes are forked into a new request's engine (rama_q8_kv_fork: the KV cache is fp32 in both stacks), and n_draft=K > 0 begins
+    the chain with rama_serve_begin_spec: a decoding request's n-gram guesses take the rows of a tile that no slot wants and are
+    verified in the same weight pass.  The tokens are the same whatever these are."""
 
     ABI = "rama_serve"
     NAME = "Server"
 
-    def __init__(self, model: Model, n_slots: int, max_rows=None, max_new_cap: int = 256):
-        self._start(model, n_slots, max_rows, max_new_cap)
+    def __init__(self, model: Model, n_slots: int, max_rows=None, max_new_cap: int = 256, n_draft: int = 0, ngram: int = 3,
+                 hint_cap: int = 0, prefix_cache: int = 0):
+        self._start_caching(model, n_slots, max_rows, max_new_cap, prefix_cache, n_draft, ngram, hint_cap)
 
     def _new_engine(self):
         e = Engine(self.device, self.model)
         self._mine.append(e)
         return e
-
-    def submit(self, context, max_new, temperature=0.0, topp=0.9, u=TOPP_U_CPU, stop_token=None, engine=None):
-        """queue a request -> its handle.  It is admitted at once if a slot is free, else when one finishes (step / run).
-        engine: the Engine whose run state the sequence uses (default: one the server owns for the slot)."""
-        ctx, plan = serve_plan(self.cfg, context, max_new, temperature, topp, u, stop_token, self.max_new_cap, 0, self.NAME)
-        h = self._submit(ctx, plan, engine)
-        self._admit()
-        return h
