@@ -8,6 +8,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
+from ._host import _per_seq, _stream_busy
 from ._lib import check, rama_config, rama_run_state, rama_seq_sampling, rama_stage, rama_weights
 from .sampler_const import TOPP_U_CPU
 from .transformer import Config, Hip
@@ -207,16 +208,6 @@ def decode_batch(engines: Sequence["Engine"], tokens: Sequence[int], positions: 
                                           states, toks, poss, len(engines)), "rama_decode_batch")
 
 
-def _per_seq(v, n: int, what: str) -> list:
-    """a scalar for every sequence, or one value per sequence"""
-    if np.ndim(v) == 0:
-        return [v] * n
-    v = list(v)
-    if len(v) != n:
-        raise ValueError(f"{what}: {len(v)} values for {n} sequences")
-    return v
-
-
 def sample_topp_batch(device: Hip, logits, temperature=1.0, topp=0.9, u=TOPP_U_CPU, n_rows: Optional[int] = None,
                       n: Optional[int] = None, ld: Optional[int] = None):
     """Device::sample for many rows at once on the device (rama_sample_topp_batch_dev) -> one token id per row (-1: nothing
@@ -233,9 +224,9 @@ def sample_topp_batch(device: Hip, logits, temperature=1.0, topp=0.9, u=TOPP_U_C
         if n_rows is None or n is None:
             raise ValueError("sample_topp_batch: a device pointer needs n_rows and n")
         ptr, ld = int(logits), ld if ld is not None else n
-    T = (C.c_float * n_rows)(*_per_seq(temperature, n_rows, "temperature"))
-    P = (C.c_float * n_rows)(*_per_seq(topp, n_rows, "topp"))
-    U = (C.c_float * n_rows)(*_per_seq(u, n_rows, "u"))
+    T = (C.c_float * n_rows)(*_per_seq(temperature, n_rows, "temperature: {} values"))
+    P = (C.c_float * n_rows)(*_per_seq(topp, n_rows, "topp: {} values"))
+    U = (C.c_float * n_rows)(*_per_seq(u, n_rows, "u: {} values"))
     res = device.alloc(n_rows)
     try:
         check(device.lib.rama_sample_topp_batch_dev(device.ctx, ptr, ld, n, n_rows, T, P, U, res.ptr), "rama_sample_topp_batch_dev")
@@ -262,7 +253,7 @@ def decode_batch_chained(engines: Sequence["Engine"], tokens: Sequence[int], pos
     states = (rama_run_state * ns)(*[e.state for e in engines])
     toks = (C.c_int32 * ns)(*tokens)
     poss = (C.c_int32 * ns)(*positions)
-    Ts, Ps, Us = _per_seq(temperature, ns, "temperature"), _per_seq(topp, ns, "topp"), _per_seq(u, ns, "u")
+    Ts, Ps, Us = _per_seq(temperature, ns, "temperature: {} values"), _per_seq(topp, ns, "topp: {} values"), _per_seq(u, ns, "u: {} values")
     prompts = [list(p) for p in prompts] if prompts is not None else [[] for _ in range(ns)]
     if len(prompts) != ns:
         raise ValueError(f"prompts: {len(prompts)} lists for {ns} sequences")
@@ -276,11 +267,10 @@ def decode_batch_chained(engines: Sequence["Engine"], tokens: Sequence[int], pos
                                                 poss, ns, max(n_steps, 1), per), "rama_decode_batch_begin_sampled")
     check(L.rama_decode_batch_steps(e0.device.ctx, n_steps), "rama_decode_batch_steps")
     if on_token is not None:
-        import time
         seen = [0] * len(engines)
         buf = (C.c_int32 * 64)()
         k = C.c_int()
-        idle_after_done = 0
+        ran = False                   # the stream has drained: one more sweep collects what is there
         while min(seen) < n_steps:
             progress = 0
             for s_ in range(len(engines)):
@@ -291,16 +281,9 @@ def decode_batch_chained(engines: Sequence["Engine"], tokens: Sequence[int], pos
                 progress += k.value
             if progress:
                 continue
-            # nothing new: is the stream still working on it?  (1 = yes; 0 = everything has run -- one more sweep collects what is there;
-            # anything else is a failed stream: the check raises instead of spinning for ever)
-            q = L.rama_stream_query(e0.device.ctx)
-            if q == 1:
-                time.sleep(0.0002)
-                continue
-            check(q, "rama_stream_query")
-            idle_after_done += 1
-            if idle_after_done > 1:
+            if ran:
                 raise RuntimeError(f"decode_batch_chained: the steps have run but only {min(seen)} of {n_steps} tokens appeared")
+            ran = not _stream_busy(e0.device, 0.0002)       # nothing new: still working on it, or (a failed stream raises) drained
     out = (C.c_int32 * (len(engines) * max(n_steps, 1)))()
     n = C.c_int()
     check(L.rama_decode_batch_tokens(e0.device.ctx, out, max(n_steps, 1), C.byref(n)), "rama_decode_batch_tokens")

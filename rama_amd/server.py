@@ -1,14 +1,14 @@
 """rama_amd.Server -- continuous batching over an fp32 Model in parity mode (rama_serve_*): the counterpart of
-Q8Server.  Both are rama_amd.q8.CachingServeLoop -- the queue, the mirror of the slot table, the steps to the next finish by the host
-plan, admissions behind the steps in flight, the rings, the prefix cache and the run loop of a chain with drafts -- over their own
-entries and engines."""
+Q8Server.  Both are rama_amd.serve.ServeLoop -- the queue, the mirror of the slot table, the steps to the next finish by the host plan,
+admissions behind the steps in flight, the rings, the prefix cache and the run loop of a chain with drafts -- over their own entries and
+engines."""
 from __future__ import annotations
 
 from .engine import Engine, Model
-from .q8 import CachingServeLoop
+from .serve import ServeLoop
 
 
-class Server(CachingServeLoop):
+class Server(ServeLoop):
     """n_slots sequence slots share parity-mode weight passes of max_rows rows (tiles of 32).  Every request's tokens are those
     Engine.generate gives it alone in parity mode -- the reference's own.  The device context must be in parity mode
     ("ref_order" = 1) and stay there.  One fp32 serving chain per device context; a Q8Server may be live next to it.
@@ -24,9 +24,7 @@ class Server(CachingServeLoop):
 
     def __init__(self, model: Model, n_slots: int, max_rows=None, max_new_cap: int = 256, n_draft: int = 0, ngram: int = 3,
                  hint_cap: int = 0, prefix_cache: int = 0):
-        self._start_caching(model, n_slots, max_rows, max_new_cap, prefix_cache, n_draft, ngram, hint_cap)
+        super().__init__(model, n_slots, max_rows, max_new_cap, prefix_cache, n_draft, ngram, hint_cap)
 
     def _new_engine(self):
-        e = Engine(self.device, self.model)
-        self._mine.append(e)
-        return e
+        return Engine(self.device, self.model)
