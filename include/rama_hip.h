@@ -739,6 +739,52 @@ int  rama_q8_spec_draft(const int32_t *hint, int n_hint, const int32_t *seq, int
                         int32_t *drafts_out);
 int  rama_q8_spec_accept(const int32_t *drafts, int n_d, const int32_t *picks, int stop_token, int remaining, int *finished);
 
+/* THE SPECULATIVE CHAIN WITH A DRAFT MODEL: the drafts come from a small Q8 model over the same vocabulary.
+ * rama_q8_spec_begin_model starts the chain above -- the same sequence record, ring and finished word, one captured graph for
+ * its life; rama_q8_spec_steps / _poll / _tokens / _stats / _end serve it unchanged, and it ends a previous speculative chain
+ * -- with one difference: where the drafts come from.  The pick is a deterministic function of the logits, so whatever the draft
+ * model proposes the output is, bit for bit, what rama_q8_spec_begin and rama_q8_generate give on the target alone.
+ *
+ * Notation as above, plus the DRAFT CURSOR Dc: rows 0..Dc-1 of the draft run state's cache hold the draft model's rows of
+ * s[0..Dc).  P - Dc is 0 or 1 when a step opens.
+ * STEP, one graph replay on one stream:
+ *   OPEN.   n_d = min(K, seq_len - 1 - P, remaining - 1), 0 on a finished sequence.  The first draft pass has two rows: the rows
+ *     at positions Dc..P carrying s[Dc..P] -- one live row, or two when the step before accepted all K of its drafts, whose last,
+ *     d[K-1], was never fed to the draft model (the CATCH-UP row).  n_d == 0: every draft row of the step is idle (position -1:
+ *     it writes nothing and nothing is read through it).
+ *   DRAFT.  For j = 0..K-1 a token-batch pass of the draft model (two rows for j = 0, one after that) and
+ *     d[j] = Device::sample(logits of the pass's last live row) with the plan's temperature, topp and u -- the target's own rule,
+ *     so a draft model equal to the target agrees with it everywhere.  Pass j + 1 feeds d[j] at position P + j + 1; passes
+ *     j >= n_d are idle.
+ *   VERIFY. The target's pass of K + 1 rows over s[L-1], d[0..n_d), the picks and the accept rule, exactly as above.
+ *   CLOSE.  Dc' = L + min(a, n_d - 1) for n_d >= 1 (L as the step opened; a budget or stop cut that emits fewer tokens than were
+ *     accepted ends the sequence, and Dc' stops at the new L).
+ * Rows of the DRAFT cache at and behind Dc' may hold the rows of rejected drafts, as rows of the target's cache behind its
+ * cursor may: the next step rewrites whatever it reads before it reads it.  Nothing at or beyond position
+ * n_context - 1 + max_new of either cache is ever written.
+ *
+ * rama_q8_spec_begin_model: the target side is rama_q8_spec_begin's contract -- rows 0..n_context-2 of `state` were written by
+ * work enqueued earlier on the context's stream -- and the same holds for `dstate` under the draft model (a rama_q8_prefill of
+ * context[:-1] with it).  The draft model may differ in dim, depth and group size; its passes run on a batch scratch of their
+ * own, sized here outside any capture.  plan->n_draft is in 1..15, plan->ngram is ignored, plan->hint must be NULL / 0: model
+ * drafts replace the n-gram lookup, they are not mixed with it.  Everything is checked first and a refusal leaves the previous
+ * chain as it was: RAMA_EINVAL for a NULL argument, dcfg->vocab_size != cfg->vocab_size, n_context + max_new > dcfg->seq_len,
+ * dstate sharing a cache with state, a hint, n_draft outside 1..15 and everything else rama_q8_spec_begin refuses; RAMA_EUNSUP
+ * where rama_q8_spec_begin gives it, and for rama_q8_batch_shape_ok(dcfg) == 0.
+ * rama_q8_spec_steps answers RAMA_EINVAL once either model (rama_q8_model_free) or either run state (rama_state_free) is gone.
+ * rama_q8_spec_stats keeps its meaning: drafts = sum n_d, accepted, accepted_hist, rows_fed = sum (n_d + 1), cursor = P.
+ * rama_q8_spec_model_stats synchronises; RAMA_EINVAL on a chain begun with rama_q8_spec_begin.  Over the steps before the
+ * finish: draft_passes = the live draft passes (sum n_d), draft_rows_fed = the live rows of those passes (catch-up rows
+ * included), catch_up_rows; draft_cursor = Dc. */
+typedef struct {
+    uint64_t draft_passes, draft_rows_fed, catch_up_rows;
+    int32_t draft_cursor;
+} rama_q8_spec_model_report;
+int  rama_q8_spec_begin_model(rama_ctx *ctx, const rama_config *cfg, const rama_q8_weights *w, const rama_run_state *state,
+                              const rama_config *dcfg, const rama_q8_weights *dw, const rama_run_state *dstate,
+                              const int32_t *context_host, int n_context, const rama_q8_spec_plan *plan);
+int  rama_q8_spec_model_stats(rama_ctx *ctx, rama_q8_spec_model_report *out);
+
 /* SPECULATION INSIDE THE SERVING CHAIN: a DECODE slot's drafts fill the rows no slot wants.  A step of the
  * serving chain costs its weight pass of max_rows rows whatever they hold, and rows at consecutive positions of one sequence
  * are exact (the speculative chain above); so a slot may put drafted tokens into rows that would otherwise be idle, and take

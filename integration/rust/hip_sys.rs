@@ -66,6 +66,9 @@ pub struct rama_q8_spec_report {
     pub accepted_hist: [u64; 16],
     pub finished: i32, pub n_out: i32, pub cursor: i32,
 }
+/// what rama_q8_spec_model_stats reports: the draft model's side of a chain begun with rama_q8_spec_begin_model
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct rama_q8_spec_model_report { pub draft_passes: u64, pub draft_rows_fed: u64, pub catch_up_rows: u64, pub draft_cursor: i32 }
 /// a slot's drafting fields on a serving chain begun with rama_q8_serve_begin_spec (hint may be null with n_hint 0) and what
 /// rama_q8_serve_spec_stats reports
 #[repr(C)] #[derive(Clone, Copy)]
@@ -292,6 +295,11 @@ extern "C" {
                               drafts_out: *mut i32) -> c_int;
     pub fn rama_q8_spec_accept(drafts: *const i32, n_d: c_int, picks: *const i32, stop_token: c_int, remaining: c_int,
                                finished: *mut c_int) -> c_int;
+    // ... with drafts from a small Q8 model over the same vocabulary instead of the lookup
+    pub fn rama_q8_spec_begin_model(ctx: *mut rama_ctx, cfg: *const rama_config, w: *const rama_q8_weights, state: *const rama_run_state,
+                                    dcfg: *const rama_config, dw: *const rama_q8_weights, dstate: *const rama_run_state,
+                                    context_host: *const i32, n_context: c_int, plan: *const rama_q8_spec_plan) -> c_int;
+    pub fn rama_q8_spec_model_stats(ctx: *mut rama_ctx, out: *mut rama_q8_spec_model_report) -> c_int;
     // speculation inside the serving chain: a DECODE slot's drafts in the rows no slot wants; _plan_step is host-only
     pub fn rama_q8_serve_begin_spec(ctx: *mut rama_ctx, cfg: *const rama_config, w: *const rama_q8_weights, n_slots: c_int, max_rows: c_int,
                                     max_new_cap: c_int, n_draft_cap: c_int, hint_cap: c_int) -> c_int;

@@ -103,6 +103,11 @@ class rama_q8_spec_report(C.Structure):
                 [("accepted_hist", C.c_uint64 * 16), ("finished", C.c_int32), ("n_out", C.c_int32), ("cursor", C.c_int32)])
 
 
+class rama_q8_spec_model_report(C.Structure):
+    """what rama_q8_spec_model_stats fills in: the draft model's side of a chain begun with rama_q8_spec_begin_model"""
+    _fields_ = [(n, C.c_uint64) for n in ("draft_passes", "draft_rows_fed", "catch_up_rows")] + [("draft_cursor", C.c_int32)]
+
+
 class rama_q8_serve_spec(C.Structure):
     """a slot's drafting fields on a serving chain begun with rama_q8_serve_begin_spec (rama_q8_serve_admit_spec)"""
     _fields_ = [("n_draft", C.c_int32), ("ngram", C.c_int32), ("hint", C.POINTER(C.c_int32)), ("n_hint", C.c_int32)]
@@ -249,6 +254,9 @@ SIGNATURES = {
     "rama_q8_spec_tokens": (_int, [_vp, i32p, _int, C.POINTER(_int)]),
     "rama_q8_spec_stats": (_int, [_vp, C.POINTER(rama_q8_spec_report)]),
     "rama_q8_spec_end": (_int, [_vp]),
+    "rama_q8_spec_begin_model": (_int, [_vp, _cfgp, C.POINTER(rama_q8_weights), _sp, _cfgp, C.POINTER(rama_q8_weights), _sp, i32p, _int,
+                                        C.POINTER(rama_q8_spec_plan)]),
+    "rama_q8_spec_model_stats": (_int, [_vp, C.POINTER(rama_q8_spec_model_report)]),
     "rama_q8_spec_draft": (_int, [i32p, _int, i32p, _int, _int, _int, _int, i32p]),
     "rama_q8_spec_accept": (_int, [i32p, _int, i32p, _int, _int, C.POINTER(_int)]),
     "rama_q8_serve_begin_spec": (_int, [_vp, _cfgp, C.POINTER(rama_q8_weights), _int, _int, _int, _int, _int]),

@@ -316,6 +316,11 @@ struct rama_ctx {
         int* ring = nullptr;               // [max_new] host-pinned and device-mapped: token + 1, 0 = not emitted yet
         int* words = nullptr;              // host-pinned and device-mapped: [0] tokens emitted, [1] 1 = the sequence has finished
         rama_run_state state{};
+        // a chain begun with rama_q8_spec_begin_model (q8_spec_model.hpp): the drafts are a second Q8 model's; all of it unused otherwise
+        bool model = false;
+        rama_config dcfg{}; rama_q8_weights dw{}; rama_run_state dstate{};      // the draft model and its run state: the chain dies with either
+        SpecModelTables mt{};              // the device tables (inside blob)
+        char* dblob = nullptr;             // the draft passes' batch scratch, a Q8BatchScratch of kSpecRows rows of the draft model's shape
     } q8p;
     // rama_serve_begin / _admit / _steps: the serving chain of an fp32 model in parity mode (batch_api.hip).  A state of its own: it
     // may be live next to q8s on the same context, and neither touches the other's graph or tables.

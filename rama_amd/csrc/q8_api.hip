@@ -1,6 +1,6 @@
 // q8_api.hip -- the Q8 part of the C ABI of include/rama_hip.h: rama_q8_quantize / _matmul, the Q8 forward and generate, the token
 // batches (prefill, decode batch), the chained batch, the serving chain (with and without drafts) and the speculative chain.  The kernels are q8.hpp,
-// q8_batch.hpp, q8_serve.hpp, q8_fork.hpp, q8_spec.hpp and q8_serve_spec.hpp; parity mode's norms and attention and the samplers are reached through the launchers of ctx.hpp, which chain_api.hip
+// q8_batch.hpp, q8_serve.hpp, q8_fork.hpp, q8_spec.hpp, q8_spec_model.hpp and q8_serve_spec.hpp; parity mode's norms and attention and the samplers are reached through the launchers of ctx.hpp, which chain_api.hip
 // defines -- this translation unit instantiates none of their kernels (DESIGN.md "Translation units").
 // The three device-chained loops are states of their own (rama_ctx::Q8Chain / Q8Serve / Q8Spec over Q8ChainBase) that share PROCEDURES, each
 // written once here (DESIGN.md "Q8 chains: shared pass, layout, pick and lookup"): q8_chains (graph and lifetime handling), q8_product (a layer's five
@@ -13,6 +13,7 @@
 #include "q8_serve.hpp"
 #include "q8_fork.hpp"
 #include "q8_spec.hpp"
+#include "q8_spec_model.hpp"
 #include "q8_serve_spec.hpp"
 
 #ifdef RAMA_CHAIN_HPP
@@ -33,7 +34,8 @@ void drop_q8_graphs(rama_ctx* c, const rama_run_state* s) {
     // a chain's step goes with all Q8 graphs (its next _steps call captures again), and with a run state the chain still uses -- after which the
     // chain is dead.  Which run states those are is each chain's own: a member's, a live slot's, the one sequence's.
     auto& sv = c->q8s;
-    bool uses[3] = {false, false, s && c->q8p.active && c->q8p.state.key_cache == s->key_cache};
+    const auto& sp = c->q8p;         // (a chain with a draft model uses two run states)
+    bool uses[3] = {false, false, s && sp.active && (sp.state.key_cache == s->key_cache || (sp.model && sp.dstate.key_cache == s->key_cache))};
     for (const auto& m : c->q8c.states) uses[0] = uses[0] || (s && m.key_cache == s->key_cache);
     // the serving chain's per-slot rule: the run state of a slot whose occupant the host cannot yet see DONE ends the chain -- a finished
     // occupant's is its owner's again
@@ -62,6 +64,7 @@ extern "C" void rama_internal_drop_q8_graphs(rama_ctx* c, const rama_q8_weights*
     drop_q8_graphs(c, nullptr);
     for (auto* ch : q8_chains(c))
         if (freed && ch->w.wq == freed->wq) ch->live = false;
+    if (freed && c->q8p.model && c->q8p.dw.wq == freed->wq) c->q8p.live = false;      // the speculative chain's draft model
 }
 
 // the serving chain's allocations (rama_q8_serve_begin / _end, release_q8); the stream is idle
@@ -92,7 +95,7 @@ static void q8_chain_release(rama_ctx* c) {
 static void spec_release(rama_ctx* c) {
     auto& sp = c->q8p;
     destroy_graph(sp.cg);
-    hipFree(sp.blob);
+    hipFree(sp.blob); hipFree(sp.dblob);
     if (sp.ring) hipHostFree(sp.ring);
     if (sp.words) hipHostFree(sp.words);
     sp = rama_ctx::Q8Spec();
@@ -191,12 +194,13 @@ static int q8_check(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* 
 
 // ---- The refusals several entries share, each in the calling entry's words: "<entry>: <what>" is the text that entry has always given.  An
 // entry calls them where its own REQUIREs of the same matter stood, so which error a bad call gets does not change.
-static int refuse(const char* entry, const char* what, int line) {
+static int refuse(const char* entry, const char* what, int line, int code = RAMA_EINVAL) {
     char msg[256];
     snprintf(msg, sizeof msg, "%s: %s", entry, what);
-    return fail(RAMA_EINVAL, msg, __FILE__, line);
+    return fail(code, msg, __FILE__, line);
 }
 #define REFUSE_UNLESS(cond, entry, what) do { if (!(cond)) return refuse((entry), (what), __LINE__); } while (0)
+#define UNSUPPORTED_UNLESS(cond, entry, what) do { if (!(cond)) return refuse((entry), (what), __LINE__, RAMA_EUNSUP); } while (0)
 
 // every token of a list is in the vocabulary
 static int check_tokens(const char* entry, const char* what, const int32_t* toks, int n, int V) {
@@ -500,16 +504,20 @@ int rama_q8_batch_shape_ok(const rama_config* cfg) {
     return q8_batch_ok(cfg) ? 1 : 0;
 }
 
-// (BlobCarver, ctx.hpp: the tables of one allocation in order)
+// (BlobCarver, ctx.hpp: the tables of one allocation in order)  A scratch of T rows over `base` (NULL: its size only), and the attention's geometry
+static size_t q8_batch_scratch_lay(const rama_config* cfg, int gs, size_t T, char* base, Q8BatchScratch* b) {
+    const size_t dim = (size_t)cfg->dim, hidden = (size_t)cfg->hidden_dim, mx = std::max(dim, hidden);
+    BlobCarver bc{base};
+    for (float** f : {&b->X, &b->XN, &b->Q, &b->Kr, &b->V, &b->XB}) bc.take(*f, T * dim);
+    bc.take(b->HB, T * hidden); bc.take(b->ATT, T * (size_t)cfg->n_heads * cfg->seq_len); bc.take(b->LG, T * (size_t)cfg->vocab_size);
+    bc.take(b->xq, T * mx); bc.take(b->xs, T * (mx / gs)); bc.take(b->toks, T); bc.take(b->seqs, T);
+    const int hs = cfg->dim / cfg->n_heads;
+    b->nw = attn_chain_waves(hs, false);
+    b->att_lds = attn_chain_lds_bytes(hs, cfg->seq_len, b->nw);
+    return bc.used;
+}
 static int ensure_q8_batch_scratch(rama_ctx* c, const rama_config* cfg, int gs, Q8BatchScratch* b) {
-    const size_t T = kQ8bMaxTok, dim = (size_t)cfg->dim, hidden = (size_t)cfg->hidden_dim, mx = std::max(dim, hidden);
-    auto lay = [&](char* base) {
-        BlobCarver bc{base};
-        for (float** f : {&b->X, &b->XN, &b->Q, &b->Kr, &b->V, &b->XB}) bc.take(*f, T * dim);
-        bc.take(b->HB, T * hidden); bc.take(b->ATT, T * (size_t)cfg->n_heads * cfg->seq_len); bc.take(b->LG, T * (size_t)cfg->vocab_size);
-        bc.take(b->xq, T * mx); bc.take(b->xs, T * (mx / gs)); bc.take(b->toks, T); bc.take(b->seqs, T);
-        return bc.used;
-    };
+    auto lay = [&](char* base) { return q8_batch_scratch_lay(cfg, gs, kQ8bMaxTok, base, b); };
     const size_t need = lay(nullptr);
     if (need > c->q8b_cap) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -523,9 +531,6 @@ static int ensure_q8_batch_scratch(rama_ctx* c, const rama_config* cfg, int gs, 
         c->q8b_cap = need;
     }
     lay(c->q8b_blob);
-    const int hs = cfg->dim / cfg->n_heads;
-    b->nw = attn_chain_waves(hs, false);
-    b->att_lds = attn_chain_lds_bytes(hs, cfg->seq_len, b->nw);
     return 0;
 }
 
@@ -1472,43 +1477,69 @@ int rama_q8_spec_end(rama_ctx* c) {
     return 0;
 }
 
-int rama_q8_spec_begin(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const rama_run_state* state, const int32_t* context_host,
-                       int n_context, const rama_q8_spec_plan* plan) {
-    RAMA_ENTER(c);
+// the draft model of rama_q8_spec_begin_model and its run state (NULL: rama_q8_spec_begin, the n-gram lookup)
+struct SpecDrafter { const rama_config* cfg; const rama_q8_weights* w; const rama_run_state* state; };
+
+// rama_q8_spec_begin (dm NULL) and rama_q8_spec_begin_model: one chain, begun the same way; the latter also sizes the draft passes' scratch and tables
+static int spec_begin(rama_ctx* c, const char* entry, const rama_config* cfg, const rama_q8_weights* w, const rama_run_state* state,
+                      const SpecDrafter* dm, const int32_t* context_host, int n_context, const rama_q8_spec_plan* plan) {
     // everything is checked before anything of a running chain is touched
-    REQUIRE(c && state && context_host && plan, RAMA_EINVAL, "q8_spec_begin: NULL argument");
+    REFUSE_UNLESS(c && state && context_host && plan && (!dm || dm->state), entry, "NULL argument");
     int rc = q8_check(c, cfg, w, state); if (rc) return rc;
+    if (dm) { rc = q8_check(c, dm->cfg, dm->w, dm->state); if (rc) return rc; }
     const int V = cfg->vocab_size;
-    CHECKED(check_sampler("q8_spec_begin", plan->temperature, plan->topp, plan->u));
-    CHECKED(check_stop_token("q8_spec_begin", plan->stop_token, V));
-    CHECKED(check_drafting("q8_spec_begin", *plan, kSpecMaxDraft, "n_draft outside 0..15", kSpecHintBit - 1, "bad hint", V));
-    REQUIRE(n_context >= 1, RAMA_EINVAL, "q8_spec_begin: n_context < 1");
-    REQUIRE(plan->max_new >= 1, RAMA_EINVAL, "q8_spec_begin: max_new < 1");
-    REQUIRE(plan->max_new <= cfg->seq_len && n_context <= cfg->seq_len - plan->max_new, RAMA_EINVAL, "q8_spec_begin: n_context + max_new beyond seq_len");
-    CHECKED(check_tokens("q8_spec_begin", "token outside the vocabulary", context_host, n_context, V));
-    REQUIRE(q8_batch_ok(cfg), RAMA_EUNSUP, "q8_spec_begin: a shape the Q8 token-batch pass does not take");
+    CHECKED(check_sampler(entry, plan->temperature, plan->topp, plan->u));
+    CHECKED(check_stop_token(entry, plan->stop_token, V));
+    if (!dm) CHECKED(check_drafting(entry, *plan, kSpecMaxDraft, "n_draft outside 0..15", kSpecHintBit - 1, "bad hint", V));
+    else {      // (ngram is ignored)
+        REFUSE_UNLESS(plan->n_draft >= 1 && plan->n_draft <= kSpecMaxDraft, entry, "n_draft outside 1..15");
+        REFUSE_UNLESS(!plan->hint && plan->n_hint == 0, entry, "a hint: model drafts replace the n-gram lookup");
+        REFUSE_UNLESS(dm->cfg->vocab_size == V, entry, "the draft model's vocabulary is not the target's");
+        REFUSE_UNLESS(dm->state->key_cache != state->key_cache && dm->state->value_cache != state->value_cache, entry,
+                      "the draft run state is the target's");
+    }
+    REFUSE_UNLESS(n_context >= 1, entry, "n_context < 1");
+    REFUSE_UNLESS(plan->max_new >= 1, entry, "max_new < 1");
+    REFUSE_UNLESS(plan->max_new <= cfg->seq_len && n_context <= cfg->seq_len - plan->max_new, entry, "n_context + max_new beyond seq_len");
+    if (dm) REFUSE_UNLESS(plan->max_new <= dm->cfg->seq_len && n_context <= dm->cfg->seq_len - plan->max_new, entry,
+                          "n_context + max_new beyond the draft model's seq_len");
+    CHECKED(check_tokens(entry, "token outside the vocabulary", context_host, n_context, V));
+    UNSUPPORTED_UNLESS(q8_batch_ok(cfg), entry, "a shape the Q8 token-batch pass does not take");
+    if (dm) UNSUPPORTED_UNLESS(q8_batch_ok(dm->cfg), entry, "a draft model of a shape the Q8 token-batch pass does not take");
     const bool sampled = plan->temperature != 0.0f;
-    REQUIRE(!sampled || (V > 1 && V <= kToppBlock * kToppMaxBlocks), RAMA_EUNSUP, "q8_spec_begin: a sampled plan needs vocab_size <= 32768");
+    UNSUPPORTED_UNLESS(!sampled || (V > 1 && V <= kToppBlock * kToppMaxBlocks), entry, "a sampled plan needs vocab_size <= 32768");
     if (set_device(c)) return 1;
     HIPCHK(hipStreamSynchronize(c->stream));
     spec_release(c);
     // the scratch and the chain's tables: sized here, outside any capture
-    const int R = plan->n_draft + 1;
+    const int R = plan->n_draft + 1;       // (a chain with a draft model has n_draft >= 1: its two-row draft pass fits the sampler's R slices)
     Q8BatchScratch b{};
     rc = q8_chain_scratch(c, cfg, w->group_size, sampled ? R : 0, &b); if (rc) return rc;
     auto& sp = c->q8p;
     SpecTables& t = sp.t;
+    SpecModelTables& mt = sp.mt;
     const size_t S = (size_t)cfg->seq_len, H = (size_t)plan->n_hint, cap = (size_t)plan->max_new;
     auto lay = [&](char* base) {
         BlobCarver bc{base};
         bc.take(t.st, 1); bc.take(t.text, H + S); bc.take(t.rows, kSpecRows); bc.take(t.row_tok, kSpecRows); bc.take(t.trow, kSpecRows);
         bc.take(t.out, cap);
+        if (dm) { bc.take(mt.ms, 1); bc.take(mt.rows, kSpecModelRows); bc.take(mt.row_tok, kSpecModelRows); bc.take(mt.trow, kSpecModelRows); }
         return bc.used;
     };
     const size_t need = lay(nullptr);
     HIPCHK(hipMalloc(&sp.blob, need));
     HIPCHK(hipMemset(sp.blob, 0, need));
     lay(sp.blob);
+    if (dm) {      // the draft passes' rows: a scratch of its own, in the draft model's shape -- one 16-token tile of the products
+        Q8BatchScratch db{};
+        const size_t dneed = q8_batch_scratch_lay(dm->cfg, dm->w->group_size, kSpecRows, nullptr, &db);
+        HIPCHK(hipMalloc(&sp.dblob, dneed));
+        HIPCHK(hipMemset(sp.dblob, 0, dneed));
+        SpecModelState mh{};
+        mh.kc = dm->state->key_cache; mh.vc = dm->state->value_cache;
+        mh.Dc = n_context - 1; mh.pick_row = -1;
+        HIPCHK(hipMemcpy(mt.ms, &mh, sizeof mh, hipMemcpyHostToDevice));
+    }
     HIPCHK(hipHostMalloc(&sp.ring, sizeof(int) * cap, hipHostMallocMapped));
     HIPCHK(hipHostMalloc(&sp.words, sizeof(int) * 2, hipHostMallocMapped));
     memset(sp.ring, 0, sizeof(int) * cap);
@@ -1528,6 +1559,41 @@ int rama_q8_spec_begin(rama_ctx* c, const rama_config* cfg, const rama_q8_weight
     HIPCHK(hipStreamSynchronize(c->stream));
     sp.cfg = *cfg; sp.w = *w; sp.state = *state; sp.sampled = sampled;
     sp.n_rows = R; sp.out_cap = plan->max_new; sp.captures = 0; sp.active = true; sp.live = true;
+    if (dm) { sp.model = true; sp.dcfg = *dm->cfg; sp.dw = *dm->w; sp.dstate = *dm->state; }
+    return 0;
+}
+
+int rama_q8_spec_begin(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const rama_run_state* state, const int32_t* context_host,
+                       int n_context, const rama_q8_spec_plan* plan) {
+    RAMA_ENTER(c);
+    return spec_begin(c, "q8_spec_begin", cfg, w, state, nullptr, context_host, n_context, plan);
+}
+
+int rama_q8_spec_begin_model(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const rama_run_state* state, const rama_config* dcfg,
+                             const rama_q8_weights* dw, const rama_run_state* dstate, const int32_t* context_host, int n_context,
+                             const rama_q8_spec_plan* plan) {
+    RAMA_ENTER(c);
+    const SpecDrafter dm{dcfg, dw, dstate};
+    return spec_begin(c, "q8_spec_begin_model", cfg, w, state, &dm, context_host, n_context, plan);
+}
+
+// the drafts of a chain begun with rama_q8_spec_begin_model (q8_spec_model.hpp): the step's opening launch, then n_draft passes of the draft model
+// over its own scratch -- two rows, then one -- each ended by the pick that stores d[j] and sets the next pass's row
+static int enqueue_q8_spec_model_drafts(rama_ctx* c) {
+    auto& sp = c->q8p;
+    Q8BatchScratch db{};
+    q8_batch_scratch_lay(&sp.dcfg, sp.dw.group_size, kSpecRows, sp.dblob, &db);
+    hipLaunchKernelGGL(spec_model_open_kernel, dim3(1), dim3(64), 0, c->stream, sp.t, sp.mt);
+    LAUNCHCHK();
+    for (int j = 0; j < sp.n_rows - 1; j++) {
+        const int n = j == 0 ? kSpecModelRows : 1;
+        int rc = enqueue_q8_batch_pass(c, &sp.dcfg, &sp.dw, db, sp.mt.row_tok, sp.mt.rows, n); if (rc) return rc;
+        SpecModelPickParams pk{};
+        pk.t = sp.t; pk.m = sp.mt; pk.j = j;
+        rc = enqueue_q8_pick_rows(c, db, sp.dcfg.vocab_size, sp.sampled, sp.mt.trow, n, &pk.r); if (rc) return rc;
+        hipLaunchKernelGGL(spec_model_pick_kernel, dim3(1), dim3(1024), 0, c->stream, pk);
+        LAUNCHCHK();
+    }
     return 0;
 }
 
@@ -1535,9 +1601,13 @@ int rama_q8_spec_begin(rama_ctx* c, const rama_config* cfg, const rama_q8_weight
 static int enqueue_q8_spec_step(rama_ctx* c, const Q8BatchScratch& b) {
     auto& sp = c->q8p;
     const int R = sp.n_rows;
-    hipLaunchKernelGGL(spec_draft_kernel, dim3(1), dim3(1024), 0, c->stream, sp.t);
-    LAUNCHCHK();
-    int rc = enqueue_q8_batch_pass(c, &sp.cfg, &sp.w, b, sp.t.row_tok, sp.t.rows, R); if (rc) return rc;
+    int rc = 0;
+    if (sp.model) { rc = enqueue_q8_spec_model_drafts(c); if (rc) return rc; }
+    else {
+        hipLaunchKernelGGL(spec_draft_kernel, dim3(1), dim3(1024), 0, c->stream, sp.t);
+        LAUNCHCHK();
+    }
+    rc = enqueue_q8_batch_pass(c, &sp.cfg, &sp.w, b, sp.t.row_tok, sp.t.rows, R); if (rc) return rc;
     SpecPickParams fin{};
     fin.t = sp.t;
     rc = enqueue_q8_pick_rows(c, b, sp.cfg.vocab_size, sp.sampled, sp.t.trow, R, &fin.r); if (rc) return rc;
@@ -1545,6 +1615,10 @@ static int enqueue_q8_spec_step(rama_ctx* c, const Q8BatchScratch& b) {
     LAUNCHCHK();
     hipLaunchKernelGGL(spec_accept_kernel, dim3(1), dim3(64), 0, c->stream, sp.t);
     LAUNCHCHK();
+    if (sp.model) {      // the draft cursor, from what the accept rule took
+        hipLaunchKernelGGL(spec_model_close_kernel, dim3(1), dim3(64), 0, c->stream, sp.t, sp.mt);
+        LAUNCHCHK();
+    }
     return 0;
 }
 
@@ -1552,7 +1626,7 @@ int rama_q8_spec_steps(rama_ctx* c, int n_steps) {
     RAMA_ENTER(c);
     REQUIRE(c && c->q8p.active, RAMA_EINVAL, "q8_spec_steps: call rama_q8_spec_begin first");
     auto& sp = c->q8p;
-    REQUIRE(sp.live, RAMA_EINVAL, "q8_spec_steps: the chain's model or its run state has been freed");
+    REQUIRE(sp.live, RAMA_EINVAL, "q8_spec_steps: the chain's model or its run state has been freed");      // (the target's or the draft's)
     REQUIRE(n_steps >= 0, RAMA_EINVAL, "q8_spec_steps: n_steps < 0");
     if (set_device(c)) return 1;
     int n_done = 0;
@@ -1594,5 +1668,17 @@ int rama_q8_spec_stats(rama_ctx* c, rama_q8_spec_report* out) {
     static_assert(sizeof out->accepted_hist == sizeof s.hist, "one histogram entry per accept count 0..15");
     memcpy(out->accepted_hist, s.hist, sizeof s.hist);
     out->finished = s.finished; out->n_out = s.n_out; out->cursor = s.L - 1;
+    return 0;
+}
+
+int rama_q8_spec_model_stats(rama_ctx* c, rama_q8_spec_model_report* out) {
+    RAMA_ENTER(c);
+    REQUIRE(c && out && c->q8p.active && c->q8p.model, RAMA_EINVAL, "q8_spec_model_stats: no chain begun with rama_q8_spec_begin_model");
+    { const int rh = q8_drain(c); if (rh) return rh; }
+    SpecModelState s{};
+    HIPCHK(hipMemcpy(&s, c->q8p.mt.ms, sizeof s, hipMemcpyDeviceToHost));
+    memset(out, 0, sizeof *out);
+    out->draft_passes = s.draft_passes; out->draft_rows_fed = s.draft_rows_fed; out->catch_up_rows = s.catch_up_rows;
+    out->draft_cursor = s.Dc;
     return 0;
 }

@@ -39,6 +39,25 @@ struct SpecTables {
     int* count; int* done;              // host-visible: tokens emitted, stored after their ring words; the finished word, stored after both
 };
 
+// a chain begun with rama_q8_spec_begin_model (q8_spec_model.hpp): the draft model's side of the sequence, next to the record above
+struct SpecModelState {
+    float* kc; float* vc;               // the draft run state's cache bases
+    int Dc;                             // the draft cursor: rows 0..Dc-1 of the draft cache belong to s
+    int pick_row;                       // the step under way: the row of the first draft pass whose logits give d[0] (-1: every draft row is idle)
+    int L0;                             // ... L when it opened
+    int open;                           // ... 1: it opened on an unfinished sequence
+    unsigned long long draft_passes, draft_rows_fed, catch_up_rows;
+};
+
+constexpr int kSpecModelRows = 2;       // rows of the first draft pass: the catch-up row and s[L - 1]; every later pass has one
+
+struct SpecModelTables {
+    SpecModelState* ms;
+    SeqSlot* rows;                      // [kSpecModelRows] the row table of the draft pass under way (idle: position -1)
+    int* row_tok;                       // [kSpecModelRows]
+    ToppRow* trow;                      // [kSpecModelRows] temperature 0 but for the row whose logits are picked from
+};
+
 // THE ACCEPT RULE (rama_q8_spec_accept on the host, spec_accept_kernel on the device: one statement for both).  *a: the drafts the picks
 // reproduce, from the front; pick_0 .. pick_a are emitted, cut at the budget (`remaining` >= 1 tokens) and after the first emitted token
 // equal to `stop`; either cut finishes the sequence.  Returns the tokens emitted (>= 1).

@@ -9,9 +9,10 @@ import numpy as np
 
 from ._host import (MAX_BATCH, MAX_DRAFT, MAX_NGRAM, _check_batch, _check_budget, _check_context, _check_drafting,  # noqa: F401  (the caps: re-exported)
                     _check_sampled_vocab, _check_sampler, _check_stop, _drain, _i32, _per_seq, _report, _ring_poll, _stream_busy, _tokens)
-from ._lib import Q8_TENSORS, check, load, rama_config, rama_q8_seq_plan, rama_q8_spec_plan, rama_q8_spec_report, rama_q8_weights, rama_run_state
+from ._lib import (Q8_TENSORS, check, load, rama_config, rama_q8_seq_plan, rama_q8_spec_model_report, rama_q8_spec_plan, rama_q8_spec_report,
+                   rama_q8_weights, rama_run_state)
 from .q8_replay import (SERVE_DECODE, SERVE_DONE, SERVE_FREE, SERVE_PROMPT,  # noqa: F401  (the restatements: re-exported)
-                        _accept_py, _draft_py, _spec_plan_py, serve_spec_replay, spec_replay)
+                        _accept_py, _draft_py, _spec_plan_py, serve_spec_replay, spec_model_replay, spec_replay)
 from .sampler_const import TOPP_U_CPU
 from .serve import (PrefixPool, ServeLoop, common_prefix, serve_plan, serve_plan_step, serve_sizes,  # noqa: F401  (the serving loop: re-exported)
                     serve_spec_plan_step, serve_spec_report, serve_spec_request, serve_spec_sizes)
@@ -131,22 +132,33 @@ class Q8Engine:
     spec_stats = None  # the last generate_spec's report (rama_q8_spec_stats)
 
     def generate_spec(self, context, max_new, temperature=0.0, topp=0.9, u=TOPP_U_CPU, stop_token=None, n_draft=7, ngram=3,
-                      hint=None, on_token=None):
+                      hint=None, on_token=None, draft=None):
         """speculative decode (rama_q8_spec_begin / _steps / _poll): context = the tokens fed at positions
         0..n-1 (the caller includes BOS) -> the up to max_new sampled tokens, those generate(context[1:], n - 1 + max_new,
         ...)[n-1:] gives, cut after stop_token.  Up to n_draft tokens per step are guessed by looking the last <= ngram
         tokens up in `hint` (a token list, optional) and in the sequence itself, and verified in one weight pass.
         context[:-1] is prefilled here; on_token(index, token), when given, is fed from the host-visible ring while the steps
-        run.  The report of the run stays behind as self.spec_stats."""
+        run.  The report of the run stays behind as self.spec_stats.
+        draft = a Q8Engine over a small model with the same vocabulary, on the same device (rama_q8_spec_begin_model, DESIGN.md
+        8.9): the guesses are that model's own next tokens under the same sampler instead of the lookup -- 1 <= n_draft, no hint,
+        ngram ignored; context[:-1] is prefilled on both engines, and spec_stats also has rama_q8_spec_model_stats' fields."""
         ctx_toks, hint_toks, (T, P, U, new, stop, K, N) = spec_plan(self.cfg, context, max_new, temperature, topp, u, stop_token,
                                                                     n_draft, ngram, hint)
+        if draft is not None:
+            spec_model_check(self, draft, len(ctx_toks), new, K, hint_toks)
         L, ctx = self.device.lib, self.device.ctx
         if len(ctx_toks) > 1:
             self.prefill(ctx_toks[:-1])
+            if draft is not None:
+                draft.prefill(ctx_toks[:-1])
         harr = _i32(hint_toks)
         rec = rama_q8_spec_plan(T, P, U, new, stop, K, N, harr if hint_toks else None, len(hint_toks))
-        check(L.rama_q8_spec_begin(ctx, C.byref(self.model.ccfg), C.byref(self.model.weights), C.byref(self.state),
-                                   _i32(ctx_toks), len(ctx_toks), C.byref(rec)), "rama_q8_spec_begin")
+        head = (ctx, C.byref(self.model.ccfg), C.byref(self.model.weights), C.byref(self.state))
+        if draft is None:
+            check(L.rama_q8_spec_begin(*head, _i32(ctx_toks), len(ctx_toks), C.byref(rec)), "rama_q8_spec_begin")
+        else:
+            check(L.rama_q8_spec_begin_model(*head, C.byref(draft.model.ccfg), C.byref(draft.model.weights), C.byref(draft.state),
+                                             _i32(ctx_toks), len(ctx_toks), C.byref(rec)), "rama_q8_spec_begin_model")
         out, poll = [], _ring_poll(L.rama_q8_spec_poll, "rama_q8_spec_poll", ctx)
 
         def sink(index, token):
@@ -173,6 +185,10 @@ class Q8Engine:
         r = rama_q8_spec_report()
         check(L.rama_q8_spec_stats(ctx, C.byref(r)), "rama_q8_spec_stats")
         self.spec_stats = spec_report(r)
+        if draft is not None:
+            q = rama_q8_spec_model_report()
+            check(L.rama_q8_spec_model_stats(ctx, C.byref(q)), "rama_q8_spec_model_stats")
+            self.spec_stats.update(_report(q))
         check(L.rama_q8_spec_end(ctx), "rama_q8_spec_end")
         return out
 
@@ -321,6 +337,23 @@ def spec_plan(cfg, context, max_new, temperature=0.0, topp=0.9, u=TOPP_U_CPU, st
     stop = _check_stop(what, stop_token, V)
     _check_sampled_vocab(what, T, V)
     return ctx, hint_toks, (T, P, U, new, stop, K, N)
+
+
+def spec_model_check(engine, draft, n_context, max_new, n_draft, hint_toks):
+    """ValueError for what rama_q8_spec_begin_model would refuse in a draft engine and can be seen from here.  No library call."""
+    what = "generate_spec"
+    if draft is engine or draft.state.key_cache == engine.state.key_cache:
+        raise ValueError(f"{what}: the draft engine is the target's own")
+    if draft.device is not engine.device:
+        raise ValueError(f"{what}: the draft engine is on another device context")
+    if hint_toks:
+        raise ValueError(f"{what}: a hint together with a draft model -- model drafts replace the lookup")
+    if draft.cfg.vocab_size != engine.cfg.vocab_size:
+        raise ValueError(f"{what}: the draft model's vocabulary {draft.cfg.vocab_size} is not the target's {engine.cfg.vocab_size}")
+    if n_context + max_new > draft.cfg.seq_len:
+        raise ValueError(f"{what}: n_context {n_context} + max_new {max_new} beyond the draft model's seq_len {draft.cfg.seq_len}")
+    if n_draft < 1:
+        raise ValueError(f"{what}: n_draft {n_draft} < 1 with a draft model")
 
 
 def spec_report(r) -> dict:

@@ -1,6 +1,6 @@
 """The Q8 chains' rules restated in plain Python, as oracles for the tests and the benchmarks: the drafting rule, the scheduling
-rule with drafts, the accept rule, and whole runs of the speculative chain and of a serving chain with drafts replayed from
-reference tokens.  No library call, nothing of rama_amd imported: rama_amd.q8 imports from here."""
+rule with drafts, the accept rule, and whole runs of the speculative chain (n-gram drafts, or a draft model's) and of a serving
+chain with drafts replayed from reference tokens.  No library call, nothing of rama_amd imported: rama_amd.q8 imports from here."""
 from __future__ import annotations
 
 SERVE_FREE, SERVE_PROMPT, SERVE_DECODE, SERVE_DONE = 0, 1, 2, 3
@@ -76,6 +76,37 @@ def spec_replay(ref_tokens, context, hint, n_draft, ngram, max_new, stop_token):
         e += emit
         out.append((len(d), a, emit))
     return out
+
+
+def spec_model_replay(ref_tokens, draft_fn, context, n_draft, max_new, stop_token):
+    """the steps of the speculative chain with a draft model (rama_q8_spec_begin_model) as a pure function of its inputs, no library
+    call: ref_tokens as spec_replay's; draft_fn(prefix, n) = the n tokens the draft model produces alone after the token list prefix,
+    under the plan's sampler -> (one (n_d, a, emitted, catch_up) per step up to the one that finishes the sequence, the final draft
+    cursor).  n_d = min(n_draft, remaining - 1) (n_context + max_new <= seq_len: the budget binds first); catch_up = the catch-up
+    rows the step feeds the draft model: 1 when the draft cursor is one behind the position fed next and the step drafts at all.
+    The draft cursor Dc: rows 0..Dc-1 of the draft cache belong to the sequence; P - Dc is 0 or 1 when a step opens."""
+    ref, s = [int(t) for t in ref_tokens], [int(t) for t in context]
+    stop = -1 if stop_token is None else int(stop_token)
+    if len(ref) < max_new:
+        raise ValueError(f"spec_model_replay: {len(ref)} reference tokens for max_new {max_new}")
+    out, e, fin, cursor = [], 0, False, len(s) - 1
+    while not fin:
+        L, remaining = len(s), max_new - e
+        n_d = max(min(n_draft, remaining - 1), 0)
+        gap = L - 1 - cursor
+        if gap not in (0, 1):
+            raise AssertionError(f"spec_model_replay: the draft cursor {cursor} is {gap} rows behind position {L - 1}")
+        d = [int(t) for t in draft_fn(list(s), n_d)] if n_d else []
+        if len(d) != n_d:
+            raise ValueError(f"spec_model_replay: draft_fn gave {len(d)} tokens for {n_d}")
+        picks = ref[e:e + n_d + 1]
+        a, emit, fin = _accept_py(d, picks, remaining, stop)
+        s += picks[:emit]
+        e += emit
+        if n_d:                                                    # rows P..P + n_d - 1 carry s[P], d[0..n_d - 1); d[0..a) are part of s now
+            cursor = min(L + min(a, n_d - 1), len(s))
+        out.append((n_d, a, emit, gap if n_d else 0))
+    return out, cursor
 
 
 def serve_spec_replay(requests, ref_tokens, n_slots, max_rows, use_slots=None):
