@@ -28,7 +28,11 @@ def dev():
 
 
 def open_model(dev, golden_dir, which):
+    """which = a fixture's name, "synth15m/<gs>", or the (configuration, group size, seed) of any synthetic model"""
     import rama_amd
+    if not isinstance(which, str):
+        cfg, gs, seed = which
+        return rama_amd.Q8Model.synth(dev, O.Config(**cfg), gs, seed)
     if which.startswith("synth15m/"):
         return rama_amd.Q8Model.synth(dev, O.Config(**STORIES15M), int(which.split("/")[1]), NEAR_SEED)
     return rama_amd.Q8Model.load(dev, golden_dir / f"{which}.bin")
