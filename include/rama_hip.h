@@ -855,6 +855,65 @@ int  rama_q8_serve_spec_plan_step(const rama_q8_serve_slot *slots, int n_slots, 
                                   rama_q8_serve_row *rows_out, int32_t *granted_out);
 int  rama_q8_serve_spec_stats(rama_ctx *ctx, rama_q8_serve_spec_report *out);
 
+/* MODEL DRAFTS INSIDE THE SERVING CHAIN: the chain above with the n-gram lookup replaced, per slot, by the next
+ * tokens of a SMALL Q8 MODEL over the same vocabulary -- the drafting of rama_q8_spec_begin_model, for many sequences at once.  A
+ * third, opt-in kind of Q8 serving chain: chains begun with rama_q8_serve_begin or rama_q8_serve_begin_spec are untouched.
+ * Every slot that drafts has a draft run state of its own and a draft cursor Dc: rows 0..Dc-1 of the draft cache belong to the
+ * slot's text s.  A step, one graph replay on one stream:
+ *   OPEN.  A DECODE slot with n_draft > 0 wants min(n_draft, seq_len - 1 - P, max_new - n_out - 1) drafts, every other slot 0.
+ *     No draft exists yet; the count is all the scheduler needs.  Such a slot feeds s[Dc..P] to the draft model in the first
+ *     draft pass -- one row, or two when the step before accepted all it was granted (the catch-up row) -- WHATEVER it is then
+ *     granted: the pass is in the graph anyway, and feeding keeps P - Dc in {0, 1} on steps where the prompts take every row.
+ *   SCHEDULE.  rama_q8_serve_spec_plan_step's rule over those wants, unchanged: prompts first, then g[i] = min(want, left) in
+ *     ascending slot index.  The draft rows' tokens are filled in by the passes below.
+ *   DRAFT.  n_draft_cap passes of the draft model, all drafting slots at once: 2 n_slots rows (slot i's rows 2i, 2i + 1), then
+ *     n_slots rows (slot i's row i).  After pass j, for j < g[i]: d[i][j] = Device::sample of slot i's last live row with the
+ *     slot's own temperature, topp and u -- the target's rule --, which becomes the token of the slot's target row j + 1, the
+ *     draft the accept rule compares, and the slot's row (d[j], P + j + 1) of pass j + 1, live only while j + 1 < g[i].  Idle
+ *     draft rows have position -1: they write nothing and nothing is read through them.
+ *   VERIFY.  The target's pass over max_rows rows, the picks per row and the accept rule per slot, as on a chain begun with
+ *     rama_q8_serve_begin_spec.
+ *   CLOSE.  Dc' = L + min(a, max(g - 1, 0)), L as the step opened; on a finishing step it stops at the new L.
+ * Slot i's tokens are still, bit for bit, rama_q8_generate's on that sequence alone: the drafts only choose which rows are
+ * verified.  The cache contract of the target's run states is rama_q8_serve_begin_spec's; the draft run states follow the same
+ * one under the draft model (rows below Dc are those of a rama_q8_prefill of the same tokens with it; nothing at or beyond row
+ * n_context - 1 + max_new is written).
+ *
+ * rama_q8_serve_begin_model: rama_q8_serve_begin_spec with hint_cap = 0, plus the draft model.  RAMA_EINVAL for
+ * dcfg->vocab_size != cfg->vocab_size, n_draft_cap outside 1..15 and 2 * n_slots > 128 (the first draft pass carries up to two
+ * rows per slot, and the token-batch pass takes 128); RAMA_EUNSUP where rama_q8_batch_shape_ok(dcfg) == 0 and wherever
+ * rama_q8_serve_begin_spec gives it.  Everything is sized here, outside any capture: a draft batch scratch of 2 * n_slots rows in
+ * the draft model's shape, separate from the context's own, and the context's scratches for the larger of the two shapes, so
+ * that a rama_q8_prefill with either model between two steps regrows nothing the captured step holds.
+ * rama_q8_serve_admit_model: rama_q8_serve_admit_at plus the slot's draft run state and its n_draft in 0..n_draft_cap.  THE
+ * CALLER'S CONTRACT: rows 0..n_context-1 of `dstate` hold the draft model's rows of the WHOLE context, written by work enqueued
+ * earlier on the context's stream (a rama_q8_prefill with the draft model).  RAMA_EINVAL, besides rama_q8_serve_admit_at's, for
+ * n_context + max_new > dcfg->seq_len, a dstate that shares a cache with `state`, and a dstate (or state) that a live slot
+ * already uses, as draft or as target state.  rama_q8_serve_admit and _admit_at on such a chain admit with n_draft = 0;
+ * rama_q8_serve_admit_spec is RAMA_EINVAL: model drafts replace the lookup.
+ * rama_q8_serve_model_plan_step is HOST-ONLY: the rule above as a pure function of the slot table, per slot n_draft (0..n_passes)
+ * and Dc, seq_len and n_passes = n_draft_cap -> rows_out[max_rows] (the target's table), want_out and granted_out [n_slots], and
+ * draft_rows_out[(n_passes + 1) * n_slots]: pass 0's 2 n_slots rows, then n_slots rows per later pass (`logits`: the row is
+ * picked from).
+ * rama_q8_serve_model_stats synchronises: the live draft passes (slot-steps that fed the draft model count max(g, 1) passes), the
+ * live draft rows fed (catch-up rows included), the catch-up rows, and every slot's draft cursor.  rama_q8_serve_spec_stats keeps
+ * its meaning on such a chain.  _steps, _poll, _tokens, _stats and _end are the existing entries; rama_q8_serve_steps answers
+ * RAMA_EINVAL once either model (rama_q8_model_free), or the target or draft run state of an occupied slot (rama_state_free), is
+ * gone. */
+typedef struct {
+    uint64_t draft_passes, draft_rows_fed, catch_up_rows;
+    int32_t n_slots, n_draft_cap;
+    int32_t draft_cursor[128];
+} rama_q8_serve_model_report;
+int  rama_q8_serve_begin_model(rama_ctx *ctx, const rama_config *cfg, const rama_q8_weights *w, const rama_config *dcfg,
+                               const rama_q8_weights *dw, int n_slots, int max_rows, int max_new_cap, int n_draft_cap);
+int  rama_q8_serve_admit_model(rama_ctx *ctx, int slot, const rama_run_state *state, const rama_run_state *dstate,
+                               const int32_t *context_host, int n_context, int n_cached, const rama_q8_serve_plan *plan, int n_draft);
+int  rama_q8_serve_model_plan_step(const rama_q8_serve_slot *slots, int n_slots, int max_rows, int seq_len, const int32_t *n_draft,
+                                   const int32_t *draft_cursor, int n_passes, rama_q8_serve_row *rows_out, int32_t *want_out,
+                                   int32_t *granted_out, rama_q8_serve_row *draft_rows_out);
+int  rama_q8_serve_model_stats(rama_ctx *ctx, rama_q8_serve_model_report *out);
+
 /* DRAFTS IN THE IDLE ROWS OF THE PARITY-MODE SERVING CHAIN: the three entries above for an fp32 model, argument
  * for argument, with rama_weights and the same plan, spec and report records.  A parity pass runs in tiles of 32 rows and a tile
  * costs its whole weight pass whatever its rows hold, so the rows of a live tile that no slot wants are paid for: a DECODE

@@ -69,6 +69,11 @@ pub struct rama_q8_spec_report {
 /// what rama_q8_spec_model_stats reports: the draft model's side of a chain begun with rama_q8_spec_begin_model
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct rama_q8_spec_model_report { pub draft_passes: u64, pub draft_rows_fed: u64, pub catch_up_rows: u64, pub draft_cursor: i32 }
+/// what rama_q8_serve_model_stats reports: the draft model's side of a serving chain begun with rama_q8_serve_begin_model
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct rama_q8_serve_model_report {
+    pub draft_passes: u64, pub draft_rows_fed: u64, pub catch_up_rows: u64, pub n_slots: i32, pub n_draft_cap: i32, pub draft_cursor: [i32; 128],
+}
 /// a slot's drafting fields on a serving chain begun with rama_q8_serve_begin_spec (hint may be null with n_hint 0) and what
 /// rama_q8_serve_spec_stats reports
 #[repr(C)] #[derive(Clone, Copy)]
@@ -308,6 +313,16 @@ extern "C" {
     pub fn rama_q8_serve_spec_plan_step(slots: *const rama_q8_serve_slot, n_slots: c_int, max_rows: c_int, want: *const i32,
                                         rows_out: *mut rama_q8_serve_row, granted_out: *mut i32) -> c_int;
     pub fn rama_q8_serve_spec_stats(ctx: *mut rama_ctx, out: *mut rama_q8_serve_spec_report) -> c_int;
+    // model drafts inside the serving chain: a small Q8 model drafts for every slot in the idle rows; _plan_step is host-only
+    pub fn rama_q8_serve_begin_model(ctx: *mut rama_ctx, cfg: *const rama_config, w: *const rama_q8_weights, dcfg: *const rama_config,
+                                     dw: *const rama_q8_weights, n_slots: c_int, max_rows: c_int, max_new_cap: c_int, n_draft_cap: c_int) -> c_int;
+    pub fn rama_q8_serve_admit_model(ctx: *mut rama_ctx, slot: c_int, state: *const rama_run_state, dstate: *const rama_run_state,
+                                     context_host: *const i32, n_context: c_int, n_cached: c_int, plan: *const rama_q8_serve_plan,
+                                     n_draft: c_int) -> c_int;
+    pub fn rama_q8_serve_model_plan_step(slots: *const rama_q8_serve_slot, n_slots: c_int, max_rows: c_int, seq_len: c_int, n_draft: *const i32,
+                                         draft_cursor: *const i32, n_passes: c_int, rows_out: *mut rama_q8_serve_row, want_out: *mut i32,
+                                         granted_out: *mut i32, draft_rows_out: *mut rama_q8_serve_row) -> c_int;
+    pub fn rama_q8_serve_model_stats(ctx: *mut rama_ctx, out: *mut rama_q8_serve_model_report) -> c_int;
 }
 
 #[repr(C)] pub struct rama_pipe { _p: [u8; 0] }

@@ -121,6 +121,12 @@ class rama_q8_serve_spec_report(C.Structure):
                 [("last_want", C.c_int32 * 128), ("last_granted", C.c_int32 * 128)])
 
 
+class rama_q8_serve_model_report(C.Structure):
+    """what rama_q8_serve_model_stats fills in: the draft model's side of a serving chain begun with rama_q8_serve_begin_model"""
+    _fields_ = ([(n, C.c_uint64) for n in ("draft_passes", "draft_rows_fed", "catch_up_rows")] +
+                [("n_slots", C.c_int32), ("n_draft_cap", C.c_int32), ("draft_cursor", C.c_int32 * 128)])
+
+
 class rama_pipe_plan(C.Structure):
     _fields_ = [("n_seq", C.c_int32), ("n_pos", C.c_int32), ("wrap", C.c_int32), ("prompt", C.POINTER(C.c_int32)), ("n_prompt", C.c_int32),
                 ("temperature", C.c_float), ("topp", C.c_float), ("u", C.c_float), ("out_tokens_dev", C.c_void_p)]
@@ -263,6 +269,11 @@ SIGNATURES = {
     "rama_q8_serve_admit_spec": (_int, [_vp, _int, _sp, i32p, _int, _int, C.POINTER(rama_q8_serve_plan), C.POINTER(rama_q8_serve_spec)]),
     "rama_q8_serve_spec_plan_step": (_int, [C.POINTER(rama_q8_serve_slot), _int, _int, i32p, C.POINTER(rama_q8_serve_row), i32p]),
     "rama_q8_serve_spec_stats": (_int, [_vp, C.POINTER(rama_q8_serve_spec_report)]),
+    "rama_q8_serve_begin_model": (_int, [_vp, _cfgp, C.POINTER(rama_q8_weights), _cfgp, C.POINTER(rama_q8_weights), _int, _int, _int, _int]),
+    "rama_q8_serve_admit_model": (_int, [_vp, _int, _sp, _sp, i32p, _int, _int, C.POINTER(rama_q8_serve_plan), _int]),
+    "rama_q8_serve_model_plan_step": (_int, [C.POINTER(rama_q8_serve_slot), _int, _int, _int, i32p, i32p, _int, C.POINTER(rama_q8_serve_row), i32p, i32p,
+                                             C.POINTER(rama_q8_serve_row)]),
+    "rama_q8_serve_model_stats": (_int, [_vp, C.POINTER(rama_q8_serve_model_report)]),
     "rama_serve_begin_spec": (_int, [_vp, _cfgp, C.POINTER(rama_weights), _int, _int, _int, _int, _int]),
     "rama_serve_admit_spec": (_int, [_vp, _int, _sp, i32p, _int, _int, C.POINTER(rama_q8_serve_plan), C.POINTER(rama_q8_serve_spec)]),
     "rama_serve_spec_stats": (_int, [_vp, C.POINTER(rama_q8_serve_spec_report)]),

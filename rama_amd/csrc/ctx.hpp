@@ -13,6 +13,7 @@
 #include "q8_serve_tables.hpp"  // ServeTables
 #include "q8_spec_tables.hpp"   // SpecTables
 #include "q8_serve_spec_tables.hpp"     // ServeSpecTables
+#include "q8_serve_model_tables.hpp"    // ServeModelTables
 
 #include <hip/hip_ext.h>   // hipExtLaunchKernelGGL: start/stop events carried by the dispatch itself
 
@@ -303,6 +304,14 @@ struct rama_ctx {
         char* sstage = nullptr;            // device: one spec admission record per slot (a ServeSpecSlot + hint_cap tokens)
         char* spinned = nullptr;           // host-pinned: the same
         size_t srec_bytes = 0;
+        // a chain begun with rama_q8_serve_begin_model (q8_serve_model.hpp): a slot's drafts are a second Q8 model's; all of it unused otherwise
+        bool model = false;
+        rama_config dcfg{}; rama_q8_weights dw{};      // the draft model: the chain dies with it
+        std::vector<rama_run_state> dstates;  // per slot, the occupant's draft run state (all NULL: admitted without drafts)
+        ServeModelTables mt{};             // the device tables (inside mblob)
+        char* mblob = nullptr;
+        char* dblob = nullptr;             // the draft passes' batch scratch, a Q8BatchScratch of draft_rows rows of the draft model's shape
+        int draft_rows = 0;                // 2 n_slots: the rows of the first draft pass
     };
     // rama_q8_serve_begin / _admit / _steps: the serving chain (q8_serve.hpp), a state of its own next to the chain above
     struct Q8Serve : Q8ChainBase, ServeState {} q8s;

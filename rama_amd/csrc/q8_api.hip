@@ -1,6 +1,6 @@
 // q8_api.hip -- the Q8 part of the C ABI of include/rama_hip.h: rama_q8_quantize / _matmul, the Q8 forward and generate, the token
 // batches (prefill, decode batch), the chained batch, the serving chain (with and without drafts) and the speculative chain.  The kernels are q8.hpp,
-// q8_batch.hpp, q8_serve.hpp, q8_fork.hpp, q8_spec.hpp, q8_spec_model.hpp and q8_serve_spec.hpp; parity mode's norms and attention and the samplers are reached through the launchers of ctx.hpp, which chain_api.hip
+// q8_batch.hpp, q8_serve.hpp, q8_fork.hpp, q8_spec.hpp, q8_spec_model.hpp, q8_serve_spec.hpp and q8_serve_model.hpp; parity mode's norms and attention and the samplers are reached through the launchers of ctx.hpp, which chain_api.hip
 // defines -- this translation unit instantiates none of their kernels (DESIGN.md "Translation units").
 // The three device-chained loops are states of their own (rama_ctx::Q8Chain / Q8Serve / Q8Spec over Q8ChainBase) that share PROCEDURES, each
 // written once here (DESIGN.md "Q8 chains: shared pass, layout, pick and lookup"): q8_chains (graph and lifetime handling), q8_product (a layer's five
@@ -15,6 +15,7 @@
 #include "q8_spec.hpp"
 #include "q8_spec_model.hpp"
 #include "q8_serve_spec.hpp"
+#include "q8_serve_model.hpp"
 
 #ifdef RAMA_CHAIN_HPP
 #error "q8_api.hip must not include chain.hpp: its kernels and g_pred_stats belong to chain_api.hip's code object"
@@ -65,6 +66,7 @@ extern "C" void rama_internal_drop_q8_graphs(rama_ctx* c, const rama_q8_weights*
     for (auto* ch : q8_chains(c))
         if (freed && ch->w.wq == freed->wq) ch->live = false;
     if (freed && c->q8p.model && c->q8p.dw.wq == freed->wq) c->q8p.live = false;      // the speculative chain's draft model
+    if (freed && c->q8s.model && c->q8s.dw.wq == freed->wq) c->q8s.live = false;      // ... and the serving chain's
 }
 
 // the serving chain's allocations (rama_q8_serve_begin / _end, release_q8); the stream is idle
@@ -75,6 +77,7 @@ void serve_state_free(rama_ctx::ServeState& sv) {
     if (sv.done) hipHostFree(sv.done);
     hipFree(sv.sstage);
     if (sv.spinned) hipHostFree(sv.spinned);
+    hipFree(sv.mblob); hipFree(sv.dblob);
 }
 static void serve_release(rama_ctx* c) {
     auto& sv = c->q8s;
@@ -961,8 +964,9 @@ int rama_q8_serve_end(rama_ctx* c) {
 }
 
 // rama_q8_serve_begin (spec false) and rama_q8_serve_begin_spec: the latter sizes the drafting tables as well, and its sampler for max_rows rows
+// draft_rows > 0 (rama_q8_serve_begin_model): the sampler is sized for the first draft pass's rows as well
 static int serve_begin(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, int n_slots, int max_rows, int max_new_cap, bool spec,
-                       int n_draft_cap, int hint_cap) {
+                       int n_draft_cap, int hint_cap, int draft_rows = 0) {
     RAMA_ENTER(c);
     REQUIRE(c, RAMA_EINVAL, "ctx is NULL");
     int rc = check_cfg(cfg); if (rc) return rc;
@@ -981,7 +985,7 @@ static int serve_begin(rama_ctx* c, const rama_config* cfg, const rama_q8_weight
     serve_release(c);
     // the scratch (a spec chain picks per row) and the chain's tables: sized here, outside any capture
     Q8BatchScratch b{};
-    rc = q8_chain_scratch(c, cfg, w->group_size, sampler ? (spec ? max_rows : n_slots) : 0, &b); if (rc) return rc;
+    rc = q8_chain_scratch(c, cfg, w->group_size, sampler ? std::max(spec ? max_rows : n_slots, draft_rows) : 0, &b); if (rc) return rc;
     auto& sv = c->q8s;
     rc = serve_state_alloc_spec(c, sv, cfg->seq_len, n_slots, max_rows, max_new_cap, spec, n_draft_cap, hint_cap); if (rc) return rc;
     sv.cfg = *cfg; sv.w = *w; sv.sampler = sampler;
@@ -1066,7 +1070,8 @@ bool serve_slot_live(const rama_ctx::ServeState& sv, int slot) {
 bool serve_state_uses(rama_ctx::ServeState& sv, const rama_run_state* s) {
     bool uses = false;
     for (int i = 0; i < sv.n_slots; i++) {
-        if (!sv.occupied[i] || sv.states[i].key_cache != s->key_cache) continue;
+        const bool drafts_on = sv.model && sv.dstates[i].key_cache && sv.dstates[i].key_cache == s->key_cache;      // (a slot's draft run state counts as its own)
+        if (!sv.occupied[i] || (sv.states[i].key_cache != s->key_cache && !drafts_on)) continue;
         if (__atomic_load_n(sv.done + i, __ATOMIC_ACQUIRE)) { sv.occupied[i] = 0; continue; }
         uses = true;
     }
@@ -1156,6 +1161,16 @@ int serve_admit_spec_install(rama_ctx* c, rama_ctx::ServeState& sv, int slot, co
     return 0;
 }
 
+// a chain begun with rama_q8_serve_begin_model: `s` shares a cache with the draft run state of a live slot other than `slot`
+static bool serve_model_state_clash(const rama_ctx::ServeState& sv, int slot, const rama_run_state* s) {
+    for (int j = 0; j < sv.n_slots; j++) {
+        const rama_run_state& d = sv.dstates[j];
+        if (j == slot || !serve_slot_live(sv, j) || !d.key_cache) continue;
+        if (d.key_cache == s->key_cache || d.value_cache == s->value_cache) return true;
+    }
+    return false;
+}
+
 // rama_q8_serve_admit (n_cached 0) and rama_q8_serve_admit_at: the slot starts PROMPT at cursor = n_cached, over rows 0 .. n_cached - 1 that
 // earlier work on the stream has put into the run state's caches
 // spec (rama_q8_serve_admit_spec; a chain begun with rama_q8_serve_begin_spec only): the slot's drafting fields and hint; without it a slot of
@@ -1169,10 +1184,15 @@ static int serve_admit(rama_ctx* c, int slot, const rama_run_state* state, const
     int rc = q8_check(c, &sv.cfg, &sv.w, state); if (rc) return rc;
     CHECKED(serve_admit_tail(kQ8ServeNames, sv, sv.cfg, slot, state, context_host, n_context, n_cached, plan));
     CHECKED(serve_admit_spec_check(kQ8ServeNames, sv, sv.cfg.vocab_size, spec));
+    if (sv.model) {      // a chain begun with rama_q8_serve_begin_model: no lookup drafts, and no run state that a live slot drafts on
+        REFUSE_UNLESS(!spec, "q8_serve_admit_spec", "the chain was begun with rama_q8_serve_begin_model: model drafts replace the lookup");
+        REFUSE_UNLESS(!serve_model_state_clash(sv, slot, state), "q8_serve_admit", "the run state is already in a live slot");
+    }
     if (set_device(c)) return 1;
     rc = serve_admit_install(c, sv, slot, state, context_host, n_context, n_cached, plan); if (rc) return rc;
     rc = serve_admit_spec_install(c, sv, slot, spec); if (rc) return rc;
     sv.states[slot] = *state; sv.occupied[slot] = 1; sv.gen[slot]++;
+    if (sv.model) sv.dstates[slot] = rama_run_state{};
     return 0;
 }
 
@@ -1189,6 +1209,137 @@ int rama_q8_serve_admit_spec(rama_ctx* c, int slot, const rama_run_state* state,
                              const rama_q8_serve_plan* plan, const rama_q8_serve_spec* spec) {
     REQUIRE(spec, RAMA_EINVAL, "q8_serve_admit_spec: NULL argument");
     return serve_admit(c, slot, state, context_host, n_context, n_cached, plan, spec);
+}
+
+// ---- MODEL DRAFTS INSIDE THE SERVING CHAIN (q8_serve_model.hpp): rama_q8_serve_begin_spec with hint_cap 0, plus a draft model
+// whose passes run on a batch scratch of their own; a slot is admitted with a draft run state and drafts with that model instead of the lookup
+
+int rama_q8_serve_begin_model(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const rama_config* dcfg, const rama_q8_weights* dw,
+                              int n_slots, int max_rows, int max_new_cap, int n_draft_cap) {
+    RAMA_ENTER(c);
+    REQUIRE(c, RAMA_EINVAL, "ctx is NULL");
+    int rc = check_cfg(cfg); if (rc) return rc;
+    rc = check_cfg(dcfg); if (rc) return rc;
+    REQUIRE(dw && dw->group_size > 0 && dcfg->dim % dw->group_size == 0 && dcfg->hidden_dim % dw->group_size == 0, RAMA_EINVAL,
+            "q8_serve_begin_model: the draft model's group_size must divide its dim and hidden_dim");
+    REQUIRE(q8_weights_complete(dw), RAMA_EINVAL, "q8_serve_begin_model: missing draft weights");
+    REQUIRE(dcfg->vocab_size == cfg->vocab_size, RAMA_EINVAL, "q8_serve_begin_model: the draft model's vocabulary is not the target's");
+    REQUIRE(n_draft_cap >= 1 && n_draft_cap <= kSpecMaxDraft, RAMA_EINVAL, "q8_serve_begin_model: n_draft_cap outside 1..15");
+    CHECKED(check_slots_rows("q8_serve_begin_model", n_slots, max_rows));
+    REQUIRE(2 * n_slots <= kQ8bMaxTok, RAMA_EINVAL, "q8_serve_begin_model: 2 n_slots > 128 (the first draft pass carries up to two rows per slot)");
+    REQUIRE(q8_batch_ok(dcfg), RAMA_EUNSUP, "q8_serve_begin_model: a draft model of a shape the Q8 token-batch pass does not take");
+    const int draft_rows = 2 * n_slots;
+    rc = serve_begin(c, cfg, w, n_slots, max_rows, max_new_cap, true, n_draft_cap, 0, draft_rows); if (rc) return rc;
+    auto& sv = c->q8s;
+    // everything a draft pass, and a draft-model prefill between two steps, runs on: sized here, outside any capture, so that neither regrows a
+    // buffer the captured step holds -- both scratches of the context for the larger of the two shapes, the draft passes' own for draft_rows rows
+    auto sized = [&]() -> int {
+        Q8BatchScratch b{};
+        int r = ensure_q8_scratch(c, dcfg); if (r) return r;
+        r = ensure_q8_batch_scratch(c, dcfg, dw->group_size, &b); if (r) return r;
+        r = q8_chain_scratch(c, cfg, w->group_size, 0, &b); if (r) return r;
+        Q8BatchScratch db{};
+        const size_t dneed = q8_batch_scratch_lay(dcfg, dw->group_size, (size_t)draft_rows, nullptr, &db);
+        HIPCHK(hipMalloc(&sv.dblob, dneed));
+        HIPCHK(hipMemset(sv.dblob, 0, dneed));
+        ServeModelTables& m = sv.mt;
+        const size_t N = (size_t)n_slots;
+        auto lay = [&](char* base) {
+            BlobCarver bc{base};
+            bc.take(m.ms, N); bc.take(m.rows0, 2 * N); bc.take(m.row_tok0, 2 * N); bc.take(m.trow0, 2 * N);
+            bc.take(m.rows, N); bc.take(m.row_tok, N); bc.take(m.trow, N);
+            return bc.used;
+        };
+        const size_t need = lay(nullptr);
+        HIPCHK(hipMalloc(&sv.mblob, need));
+        HIPCHK(hipMemset(sv.mblob, 0, need));
+        lay(sv.mblob);
+        return 0;
+    };
+    rc = sized();
+    if (rc) { serve_release(c); return rc; }
+    sv.model = true; sv.dcfg = *dcfg; sv.dw = *dw; sv.draft_rows = draft_rows;
+    sv.dstates.assign((size_t)n_slots, rama_run_state{});
+    return 0;
+}
+
+static const ServeNames kQ8ServeModelNames{"q8_serve_admit_model", "q8_serve_admit_model", "rama_q8_serve_begin_model", "q8_serve_admit_model",
+                                           "rama_q8_serve_begin_model"};
+
+int rama_q8_serve_admit_model(rama_ctx* c, int slot, const rama_run_state* state, const rama_run_state* dstate, const int32_t* context_host,
+                              int n_context, int n_cached, const rama_q8_serve_plan* plan, int n_draft) {
+    RAMA_ENTER(c);
+    const char* entry = "q8_serve_admit_model";
+    REQUIRE(c && c->q8s.n_slots > 0 && c->q8s.model, RAMA_EINVAL, "q8_serve_admit_model: call rama_q8_serve_begin_model first");
+    auto& sv = c->q8s;
+    CHECKED(serve_admit_head(kQ8ServeModelNames, sv, sv.live, slot, state, context_host, plan));
+    REFUSE_UNLESS(dstate, entry, "NULL argument");
+    int rc = q8_check(c, &sv.cfg, &sv.w, state); if (rc) return rc;
+    rc = q8_check(c, &sv.dcfg, &sv.dw, dstate); if (rc) return rc;
+    CHECKED(serve_admit_tail(kQ8ServeModelNames, sv, sv.cfg, slot, state, context_host, n_context, n_cached, plan));
+    REFUSE_UNLESS(n_draft >= 0 && n_draft <= sv.n_draft_cap, entry, "n_draft beyond rama_q8_serve_begin_model's n_draft_cap");
+    REFUSE_UNLESS(n_context <= sv.dcfg.seq_len - plan->max_new, entry, "n_context + max_new beyond the draft model's seq_len");
+    REFUSE_UNLESS(dstate->key_cache != state->key_cache && dstate->value_cache != state->value_cache, entry, "the draft run state is the target's");
+    for (int j = 0; j < sv.n_slots; j++)
+        REFUSE_UNLESS(j == slot || !serve_slot_live(sv, j) || (sv.states[j].key_cache != dstate->key_cache && sv.states[j].value_cache != dstate->value_cache),
+                      entry, "the draft run state is already in a live slot");
+    REFUSE_UNLESS(!serve_model_state_clash(sv, slot, dstate) && !serve_model_state_clash(sv, slot, state), entry, "a run state is already a live slot's draft state");
+    if (set_device(c)) return 1;
+    rc = serve_admit_install(c, sv, slot, state, context_host, n_context, n_cached, plan); if (rc) return rc;
+    const rama_q8_serve_spec spec{n_draft, 1, nullptr, 0};
+    rc = serve_admit_spec_install(c, sv, slot, &spec); if (rc) return rc;
+    // the draft cursor: rows 0 .. n_context - 1 of the draft cache hold the whole context (the caller's contract)
+    hipLaunchKernelGGL(serve_model_install_kernel, dim3(1), dim3(64), 0, c->stream, sv.mt, slot, dstate->key_cache, dstate->value_cache, n_context);
+    LAUNCHCHK();
+    sv.states[slot] = *state; sv.dstates[slot] = *dstate; sv.occupied[slot] = 1; sv.gen[slot]++;
+    return 0;
+}
+
+// the step's schedule on the host: the wants, rama_q8_serve_spec_plan_step's rule over them, and every draft pass's row table
+int rama_q8_serve_model_plan_step(const rama_q8_serve_slot* slots, int n_slots, int max_rows, int seq_len, const int32_t* n_draft,
+                                  const int32_t* draft_cursor, int n_passes, rama_q8_serve_row* rows_out, int32_t* want_out, int32_t* granted_out,
+                                  rama_q8_serve_row* draft_rows_out) {
+    REQUIRE(slots && n_draft && draft_cursor && rows_out && want_out && granted_out && draft_rows_out, RAMA_EINVAL, "q8_serve_model_plan_step: NULL argument");
+    CHECKED(check_slots_rows("q8_serve_model_plan_step", n_slots, max_rows));
+    REQUIRE(2 * n_slots <= kQ8bMaxTok && n_passes >= 1 && n_passes <= kSpecMaxDraft && seq_len >= 1, RAMA_EINVAL,
+            "q8_serve_model_plan_step: 2 n_slots <= 128, 1..15 passes");
+    for (int i = 0; i < n_slots; i++) {
+        const rama_q8_serve_slot& s = slots[i];
+        CHECKED(check_plan_slot("q8_serve_model_plan_step", s));
+        REQUIRE(n_draft[i] >= 0 && n_draft[i] <= n_passes, RAMA_EINVAL, "q8_serve_model_plan_step: a slot's n_draft outside 0..n_passes");
+        const bool dec = s.state == RAMA_SERVE_DECODE && n_draft[i] > 0;
+        REQUIRE(!dec || (s.cursor < seq_len && s.cursor - draft_cursor[i] >= 0 && s.cursor - draft_cursor[i] <= 1), RAMA_EINVAL,
+                "q8_serve_model_plan_step: a drafting slot's draft cursor is its cursor, or one row behind");
+        want_out[i] = dec ? std::max(std::min(n_draft[i], std::min(seq_len - 1 - s.cursor, s.max_new - s.n_out - 1)), 0) : 0;
+    }
+    CHECKED(rama_q8_serve_spec_plan_step(slots, n_slots, max_rows, want_out, rows_out, granted_out));
+    const rama_q8_serve_row idle{-1, -1, 0};
+    for (int i = 0; i < n_slots; i++) {
+        const rama_q8_serve_slot& s = slots[i];
+        const bool dec = s.state == RAMA_SERVE_DECODE && n_draft[i] > 0;
+        const int gap = dec ? s.cursor - draft_cursor[i] : -1, g = granted_out[i];
+        for (int k = 0; k < 2; k++)      // the first pass: s[Dc..P], fed whatever the grant; the last live row is picked from when g > 0
+            draft_rows_out[2 * i + k] = k <= gap ? rama_q8_serve_row{i, draft_cursor[i] + k, k == gap && g > 0 ? 1 : 0} : idle;
+        for (int j = 1; j < n_passes; j++)
+            draft_rows_out[(size_t)(j + 1) * n_slots + i] = j < g ? rama_q8_serve_row{i, s.cursor + j, 1} : idle;
+    }
+    return 0;
+}
+
+int rama_q8_serve_model_stats(rama_ctx* c, rama_q8_serve_model_report* out) {
+    RAMA_ENTER(c);
+    REQUIRE(c && out && c->q8s.n_slots > 0 && c->q8s.model, RAMA_EINVAL, "q8_serve_model_stats: no chain begun with rama_q8_serve_begin_model");
+    const auto& sv = c->q8s;
+    { const int rh = q8_drain(c); if (rh) return rh; }
+    std::vector<ServeModelSlot> ms(sv.n_slots);
+    HIPCHK(hipMemcpy(ms.data(), sv.mt.ms, sizeof(ServeModelSlot) * sv.n_slots, hipMemcpyDeviceToHost));
+    memset(out, 0, sizeof *out);
+    out->n_slots = sv.n_slots; out->n_draft_cap = sv.n_draft_cap;
+    for (int i = 0; i < sv.n_slots; i++) {
+        out->draft_passes += ms[i].draft_passes; out->draft_rows_fed += ms[i].draft_rows_fed; out->catch_up_rows += ms[i].catch_up_rows;
+        out->draft_cursor[i] = ms[i].Dc;
+    }
+    return 0;
 }
 
 // rows [0, n_rows) of every layer of src's caches into every destination's: one launch (q8_fork.hpp), stream-ordered
@@ -1322,6 +1473,35 @@ static int enqueue_q8_serve_spec_step(rama_ctx* c, const Q8BatchScratch& b) {
     return launch_serve_spec_accept(c, sv.t, sv.st);
 }
 
+// one step of a chain begun with rama_q8_serve_begin_model (q8_serve_model.hpp): the wants and the first draft pass's rows, the scheduler, n_draft_cap
+// passes of the draft model over its own scratch -- 2 n_slots rows, then n_slots -- each ended by the pick that stores every slot's d[j] and sets its
+// row of the next pass; then the spec step's pass, picks and accept rule, and the draft cursors
+static int enqueue_q8_serve_model_step(rama_ctx* c, const Q8BatchScratch& b) {
+    auto& sv = c->q8s;
+    Q8BatchScratch db{};
+    q8_batch_scratch_lay(&sv.dcfg, sv.dw.group_size, (size_t)sv.draft_rows, sv.dblob, &db);
+    hipLaunchKernelGGL(serve_model_open_kernel, dim3(1), dim3(kServeMaxSlots), 0, c->stream, sv.t, sv.st, sv.mt);
+    LAUNCHCHK();
+    int rc = launch_serve_spec_schedule(c, sv.t, sv.st); if (rc) return rc;
+    for (int j = 0; j < sv.n_draft_cap; j++) {
+        const int n = j == 0 ? sv.draft_rows : sv.n_slots;
+        const int* toks = j == 0 ? sv.mt.row_tok0 : sv.mt.row_tok;
+        const SeqSlot* rows = j == 0 ? sv.mt.rows0 : sv.mt.rows;
+        rc = enqueue_q8_batch_pass(c, &sv.dcfg, &sv.dw, db, toks, rows, n); if (rc) return rc;
+        ServeModelPickParams pk{};
+        pk.t = sv.t; pk.st = sv.st; pk.m = sv.mt; pk.j = j;
+        rc = enqueue_q8_pick_rows(c, db, sv.dcfg.vocab_size, sv.sampler, j == 0 ? sv.mt.trow0 : sv.mt.trow, n, &pk.r); if (rc) return rc;
+        hipLaunchKernelGGL(serve_model_pick_kernel, dim3(sv.n_slots), dim3(1024), 0, c->stream, pk);
+        LAUNCHCHK();
+    }
+    rc = enqueue_q8_batch_pass(c, &sv.cfg, &sv.w, b, sv.t.row_tok, sv.t.rows, sv.max_rows); if (rc) return rc;
+    rc = launch_serve_spec_pick(c, sv.t, sv.st, b.LG, sv.cfg.vocab_size, sv.sampler); if (rc) return rc;
+    rc = launch_serve_spec_accept(c, sv.t, sv.st); if (rc) return rc;
+    hipLaunchKernelGGL(serve_model_close_kernel, dim3(1), dim3(kServeMaxSlots), 0, c->stream, sv.t, sv.st, sv.mt);
+    LAUNCHCHK();
+    return 0;
+}
+
 int rama_q8_serve_steps(rama_ctx* c, int n_steps) {
     RAMA_ENTER(c);
     REQUIRE(c && c->q8s.n_slots > 0, RAMA_EINVAL, "q8_serve_steps: call rama_q8_serve_begin first");
@@ -1330,8 +1510,9 @@ int rama_q8_serve_steps(rama_ctx* c, int n_steps) {
     REQUIRE(n_steps >= 0, RAMA_EINVAL, "q8_serve_steps: n_steps < 0");
     if (set_device(c)) return 1;
     int n_done = 0;
-    const int rc = q8_chain_steps(c, sv, sv.sampler ? (sv.spec ? sv.max_rows : sv.n_slots) : 0, n_steps,
-                                  [&](const Q8BatchScratch& b) { return sv.spec ? enqueue_q8_serve_spec_step(c, b) : enqueue_q8_serve_step(c, b); }, &n_done);
+    const int rc = q8_chain_steps(c, sv, sv.sampler ? std::max(sv.spec ? sv.max_rows : sv.n_slots, sv.draft_rows) : 0, n_steps, [&](const Q8BatchScratch& b) {
+        return sv.model ? enqueue_q8_serve_model_step(c, b) : sv.spec ? enqueue_q8_serve_spec_step(c, b) : enqueue_q8_serve_step(c, b);
+    }, &n_done);
     sv.steps += (unsigned long long)n_done;
     return rc;
 }

@@ -12,10 +12,10 @@ from ._host import (MAX_BATCH, MAX_DRAFT, MAX_NGRAM, _check_batch, _check_budget
 from ._lib import (Q8_TENSORS, check, load, rama_config, rama_q8_seq_plan, rama_q8_spec_model_report, rama_q8_spec_plan, rama_q8_spec_report,
                    rama_q8_weights, rama_run_state)
 from .q8_replay import (SERVE_DECODE, SERVE_DONE, SERVE_FREE, SERVE_PROMPT,  # noqa: F401  (the restatements: re-exported)
-                        _accept_py, _draft_py, _spec_plan_py, serve_spec_replay, spec_model_replay, spec_replay)
+                        _accept_py, _draft_py, _spec_plan_py, serve_model_replay, serve_spec_replay, spec_model_replay, spec_replay)
 from .sampler_const import TOPP_U_CPU
-from .serve import (PrefixPool, ServeLoop, common_prefix, serve_plan, serve_plan_step, serve_sizes,  # noqa: F401  (the serving loop: re-exported)
-                    serve_spec_plan_step, serve_spec_report, serve_spec_request, serve_spec_sizes)
+from .serve import (PrefixPool, ServeLoop, common_prefix, serve_model_plan_step, serve_model_report, serve_model_sizes,  # noqa: F401  (the serving loop: re-exported)
+                    serve_plan, serve_plan_step, serve_sizes, serve_spec_plan_step, serve_spec_report, serve_spec_request, serve_spec_sizes)
 from .transformer import Config, Hip
 
 
@@ -308,17 +308,24 @@ class Q8Server(ServeLoop):
     Drafts.  n_draft=K > 0 begins the chain with rama_q8_serve_begin_spec: a decoding request guesses up to K
     tokens per step by looking its last <= ngram tokens up in its own text and in the hint it was submitted with (at most
     hint_cap tokens), the guesses take the rows of the step that no slot wants -- prompts first -- and are verified in the same
-    weight pass.  The tokens are the same with drafts on and off; n_draft=0 (the default) is the plain chain."""
+    weight pass.  The tokens are the same with drafts on and off; n_draft=0 (the default) is the plain chain.
+
+    Model drafts.  draft=Q8Model (a small model over the same vocabulary, on the same device) with n_draft=K in
+    1..15 begins the chain with rama_q8_serve_begin_model: the guesses are that model's own next tokens under the request's sampler
+    instead of the lookup -- no hint_cap, ngram ignored, at most 64 slots.  The server owns one draft engine per slot and prefills
+    it with the request's context before the admission.  The tokens are the same with and without the draft model."""
 
     ABI = "rama_q8_serve"
     NAME = "Q8Server"
 
     def __init__(self, model: Q8Model, n_slots: int, max_rows=None, max_new_cap: int = 256, prefix_cache: int = 0, n_draft: int = 0,
-                 ngram: int = 3, hint_cap: int = 0):
-        super().__init__(model, n_slots, max_rows, max_new_cap, prefix_cache, n_draft, ngram, hint_cap)
+                 ngram: int = 3, hint_cap: int = 0, draft: Q8Model = None):
+        if draft is not None and draft.device is not model.device:
+            raise ValueError("Q8Server: the draft model is on another device context")
+        super().__init__(model, n_slots, max_rows, max_new_cap, prefix_cache, n_draft, ngram, hint_cap, draft)
 
-    def _new_engine(self):
-        return Q8Engine(self.device, self.model)
+    def _new_engine(self, model=None):
+        return Q8Engine(self.device, model or self.model)
 
 
 # ------------------------------------------------------------------ the speculative chain: n-gram lookup drafts (rama_q8_spec_*)

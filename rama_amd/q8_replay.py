@@ -194,3 +194,102 @@ def serve_spec_replay(requests, ref_tokens, n_slots, max_rows, use_slots=None):
         steps.append(dict(admitted=admitted, rows=rows, want=want, granted=granted, accepted=accepted, emitted=emitted, finished=finished,
                           slots=[tuple(s) for s in slots]))
     return dict(steps=steps, counters=cnt, finish_step=finish, slot=slot_of, outputs=outputs)
+
+
+def serve_model_replay(requests, ref_tokens, draft_fn, n_slots, max_rows, use_slots=None):
+    """a whole workload of a serving chain with a draft model (rama_q8_serve_begin_model) as a pure function of its inputs, no library
+    call.  requests and ref_tokens as serve_spec_replay's (n_draft: the drafts per step of the request, 0: none; ngram and hint do not
+    exist here); draft_fn(prefix, n) = the n tokens the draft model produces alone after the token list prefix under the request's
+    sampler -- one callable, or one per request.  Admission as serve_spec_replay's.  Every step: a DECODE slot with n_draft > 0 wants
+    min(n_draft, max_new - n_out - 1) (n_context + max_new <= seq_len: the budget binds first) and feeds the draft model s[Dc..P]
+    whatever it is granted; the scheduling rule; the granted drafts d = draft_fn(s, g); the accept rule against the reference tokens;
+    Dc' = min(L + min(a, max(g - 1, 0)), new L).  -> serve_spec_replay's dict, and besides: per step `drafting` = {slot: (g, a,
+    emitted, catch_up)} for the slots that fed the draft model and `cursors` = every slot's draft cursor after the step; counters
+    also has draft_passes, draft_rows_fed and catch_up_rows (rama_q8_serve_model_stats); cursor = per request its final draft cursor."""
+    fns = list(draft_fn) if isinstance(draft_fn, (list, tuple)) else [draft_fn] * len(requests)
+    reqs = []
+    for r, ref in zip(requests, ref_tokens):
+        ctx, new = [int(t) for t in r["context"]], int(r["max_new"])
+        if len(ref) < new:
+            raise ValueError(f"serve_model_replay: {len(ref)} reference tokens for max_new {new}")
+        stop = r.get("stop_token")
+        reqs.append(dict(ctx=ctx, new=new, stop=-1 if stop is None else int(stop), K=int(r.get("n_draft", 0)), cached=int(r.get("n_cached", 0)),
+                         ref=[int(t) for t in ref]))
+    usable = list(range(n_slots)) if use_slots is None else sorted(use_slots)
+    slots = [[SERVE_FREE, 0, 0, 0, 0] for _ in range(n_slots)]      # state, n_context, cursor, n_out, max_new
+    who, text, Dc = [None] * n_slots, [None] * n_slots, [0] * n_slots
+    waiting = list(range(len(reqs)))
+    steps, finish, slot_of, outputs, final = [], [None] * len(reqs), [None] * len(reqs), [[] for _ in reqs], [None] * len(reqs)
+    cnt = dict(steps=0, rows_decode=0, rows_draft=0, rows_prompt=0, rows_idle=0, drafts_wanted=0, drafts_granted=0, drafts_accepted=0,
+               tokens_emitted=0, accepted_hist=[0] * 16, draft_passes=0, draft_rows_fed=0, catch_up_rows=0)
+    while waiting or any(s[0] in (SERVE_PROMPT, SERVE_DECODE) for s in slots):
+        admitted = []
+        for i in usable:
+            if waiting and slots[i][0] in (SERVE_FREE, SERVE_DONE):
+                q = waiting.pop(0)
+                r = reqs[q]
+                slots[i] = [SERVE_PROMPT, len(r["ctx"]), r["cached"], 0, r["new"]]
+                who[i], text[i], slot_of[q], Dc[i] = q, list(r["ctx"]), i, len(r["ctx"])
+                admitted.append((i, q))
+        if not any(s[0] in (SERVE_PROMPT, SERVE_DECODE) for s in slots):
+            raise ValueError("serve_model_replay: requests are waiting but no slot can take them")
+        want, gap = [0] * n_slots, {}
+        for i, s in enumerate(slots):
+            if s[0] == SERVE_DECODE and reqs[who[i]]["K"] > 0:
+                want[i] = max(min(reqs[who[i]]["K"], s[4] - s[3] - 1), 0)
+                gap[i] = s[2] - Dc[i]
+                if gap[i] not in (0, 1):
+                    raise AssertionError(f"serve_model_replay: slot {i}'s draft cursor {Dc[i]} is {gap[i]} rows behind position {s[2]}")
+        rows, granted = _spec_plan_py(slots, want, max_rows)
+        used = sum(1 for r in rows if r[0] >= 0)
+        n_dec = sum(1 for s in slots if s[0] == SERVE_DECODE)
+        cnt["steps"] += 1
+        cnt["rows_decode"] += n_dec
+        cnt["rows_draft"] += sum(granted)
+        cnt["rows_prompt"] += used - n_dec - sum(granted)
+        cnt["rows_idle"] += max_rows - used
+        cnt["drafts_wanted"] += sum(want)
+        accepted, emitted, finished, drafting = {}, {}, [], {}
+        for i, s in enumerate(slots):
+            n = sum(1 for r in rows if r[0] == i)
+            if n == 0:
+                continue
+            r = reqs[who[i]]
+            if s[0] == SERVE_PROMPT and s[2] + n < s[1]:
+                s[2] += n
+                continue
+            if s[0] == SERVE_PROMPT:
+                picks, emit = r["ref"][:1], 1
+                fin = s[4] <= 1 or picks[0] == r["stop"]
+                s[2] = s[1]
+            else:
+                g, L = granted[i], len(text[i])
+                d = [int(t) for t in fns[who[i]](list(text[i]), g)] if g else []
+                if len(d) != g:
+                    raise ValueError(f"serve_model_replay: draft_fn gave {len(d)} tokens for {g}")
+                picks = r["ref"][s[3]:s[3] + g + 1]
+                a, emit, fin = _accept_py(d, picks, s[4] - s[3], r["stop"])
+                accepted[i] = a
+                cnt["drafts_granted"] += g
+                cnt["drafts_accepted"] += a
+                cnt["accepted_hist"][a] += 1
+                s[2] += emit
+                if i in gap:
+                    Dc[i] = min(L + min(a, max(g - 1, 0)), L + emit)
+                    drafting[i] = (g, a, emit, gap[i])
+                    cnt["draft_passes"] += max(g, 1)
+                    cnt["draft_rows_fed"] += gap[i] + max(g, 1)
+                    cnt["catch_up_rows"] += gap[i]
+            emitted[i] = emit
+            cnt["tokens_emitted"] += emit
+            text[i] += picks[:emit]
+            outputs[who[i]] += picks[:emit]
+            s[3] += emit
+            s[0] = SERVE_DONE if fin else SERVE_DECODE
+            final[who[i]] = Dc[i]
+            if fin:
+                finished.append(i)
+                finish[who[i]] = len(steps)
+        steps.append(dict(admitted=admitted, rows=rows, want=want, granted=granted, accepted=accepted, emitted=emitted, finished=finished,
+                          slots=[tuple(s) for s in slots], drafting=drafting, cursors=list(Dc)))
+    return dict(steps=steps, counters=cnt, finish_step=finish, slot=slot_of, outputs=outputs, cursor=final)

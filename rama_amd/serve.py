@@ -8,8 +8,8 @@ import ctypes as C
 
 from ._host import (MAX_BATCH, _check_budget, _check_context, _check_drafting, _check_n_draft, _check_sampled_vocab, _check_sampler,
                     _check_stop, _drain, _i32, _report, _ring_poll, _row_table, _slot_table, _stream_busy, _tokens)
-from ._lib import (check, load, rama_q8_serve_plan, rama_q8_serve_report, rama_q8_serve_row, rama_q8_serve_slot, rama_q8_serve_spec,
-                   rama_q8_serve_spec_report)
+from ._lib import (check, load, rama_q8_serve_model_report, rama_q8_serve_plan, rama_q8_serve_report, rama_q8_serve_row, rama_q8_serve_slot,
+                   rama_q8_serve_spec, rama_q8_serve_spec_report)
 from .q8_replay import SERVE_DECODE, SERVE_DONE, SERVE_FREE, SERVE_PROMPT
 from .sampler_const import TOPP_U_CPU
 
@@ -106,6 +106,43 @@ def serve_spec_plan_step(slots, want, max_rows):
     return _row_table(rows, max_rows), granted[:n]
 
 
+def serve_model_sizes(cfg, draft, n_slots, n_draft, hint_cap, who="Q8Server"):
+    """ValueError for what rama_q8_serve_begin_model would refuse in a draft model and can be seen from here.  No library call."""
+    if hint_cap:
+        raise ValueError(f"{who}: hint_cap {hint_cap} together with a draft model -- model drafts replace the lookup")
+    if not 1 <= int(n_draft) <= 15:
+        raise ValueError(f"{who}: n_draft {n_draft} outside 1..15 with a draft model")
+    if draft.cfg.vocab_size != cfg.vocab_size:
+        raise ValueError(f"{who}: the draft model's vocabulary {draft.cfg.vocab_size} is not the target's {cfg.vocab_size}")
+    if 2 * int(n_slots) > MAX_BATCH:
+        raise ValueError(f"{who}: {n_slots} slots with a draft model, not 1..{MAX_BATCH // 2} (the first draft pass carries two rows per slot)")
+
+
+def serve_model_plan_step(slots, n_draft, draft_cursor, max_rows, seq_len, n_passes):
+    """rama_q8_serve_model_plan_step, the step's schedule of a chain with a draft model as a pure host function: slots = (state,
+    n_context, cursor, n_out, max_new) tuples, n_draft and draft_cursor per slot -> (rows [(slot, pos, logits)] * max_rows, want,
+    granted, the draft passes' row tables: [2 n_slots rows] then n_passes - 1 times [n_slots rows]).  No GPU."""
+    n = len(slots)
+    if len(n_draft) != n or len(draft_cursor) != n:
+        raise ValueError(f"serve_model_plan_step: {len(n_draft)} n_draft and {len(draft_cursor)} draft_cursor values for {n} slots")
+    table, max_rows, n_passes = _slot_table(slots), int(max_rows), int(n_passes)
+    rows = (rama_q8_serve_row * max(max_rows, 1))()
+    want, granted = (C.c_int32 * max(n, 1))(), (C.c_int32 * max(n, 1))()
+    drows = (rama_q8_serve_row * (max(n_passes + 1, 2) * max(n, 1)))()
+    check(load().rama_q8_serve_model_plan_step(table, n, max_rows, int(seq_len), _i32([int(v) for v in n_draft]), _i32([int(v) for v in draft_cursor]),
+                                               n_passes, rows, want, granted, drows), "rama_q8_serve_model_plan_step")
+    flat = [(r.slot, r.pos, r.logits) for r in drows[:(n_passes + 1) * n]]
+    passes = [flat[:2 * n]] + [flat[(j + 1) * n:(j + 2) * n] for j in range(1, n_passes)]
+    return _row_table(rows, max_rows), want[:n], granted[:n], passes
+
+
+def serve_model_report(r) -> dict:
+    """a rama_q8_serve_model_report as a dict: its counters, and the draft cursors of its n_slots slots"""
+    d = _report(r, skip=("n_slots",))
+    d["draft_cursor"] = d["draft_cursor"][:r.n_slots]
+    return d
+
+
 class PrefixPool:
     """the donors of a server's prefix cache: at most k engines, each keyed by the tokens whose cache rows it holds (row t is a
     function of tokens 0..t only, and its bits do not depend on who computed it).  Least recently used goes first.  Pure host
@@ -173,10 +210,14 @@ class ServeLoop:
     SPEC_BLOCK = 4     # with drafts: at most this many steps between two looks at the device's slot table
     MIN_CACHED = 2     # a shorter match is not worth a launch: every context shares its first token (BOS) with every donor
 
-    def __init__(self, model, n_slots, max_rows, max_new_cap, prefix_cache, n_draft, ngram, hint_cap):
+    def __init__(self, model, n_slots, max_rows, max_new_cap, prefix_cache, n_draft, ngram, hint_cap, draft=None):
         """the sizes (every one checked before any library call, in this order), the chain's begin, the loop's books"""
         self.n_slots, self.max_rows, self.max_new_cap = serve_sizes(model.cfg, n_slots, max_rows, max_new_cap, self.NAME)
         self.n_draft, self.ngram, self.hint_cap = serve_spec_sizes(n_draft, ngram, hint_cap, self.NAME)
+        self.draft = draft                                # a draft model (Q8Server only): <ABI>_begin_model / _admit_model
+        if draft is not None:
+            serve_model_sizes(model.cfg, draft, self.n_slots, self.n_draft, self.hint_cap, self.NAME)
+        self._down = [None] * self.n_slots                # the server's draft engine of a slot, made on first use and reused
         self.spec = self.n_draft > 0                      # n_draft == 0: the plain chain, <ABI>_begin
         self.pool = PrefixPool(prefix_cache)              # (raises before any library call)
         self.model, self.device, self.cfg = model, model.device, model.cfg
@@ -206,12 +247,17 @@ class ServeLoop:
     def _begin(self):
         m = self.model
         sizes = (C.byref(m.ccfg), C.byref(m.weights), self.n_slots, self.max_rows, self.max_new_cap)
-        if self.spec:
+        if self.draft is not None:
+            d = self.draft
+            self._call("begin_model", C.byref(m.ccfg), C.byref(m.weights), C.byref(d.ccfg), C.byref(d.weights), self.n_slots, self.max_rows,
+                       self.max_new_cap, self.n_draft)
+        elif self.spec:
             self._call("begin_spec", *sizes, self.n_draft, self.hint_cap)
         else:
             self._call("begin", *sizes)
 
-    def _new_engine(self):
+    def _new_engine(self, model=None):
+        """an engine over the server's model, or -- a server with a draft model -- over `model`"""
         raise NotImplementedError
 
     # -- requests
@@ -229,6 +275,8 @@ class ServeLoop:
         whatever they are."""
         ctx, plan = serve_plan(self.cfg, context, max_new, temperature, topp, u, stop_token, self.max_new_cap, n_cached, self.NAME)
         draft = serve_spec_request(self.cfg, self.n_draft, self.ngram, self.hint_cap, n_draft, hint, self.NAME)
+        if self.draft is not None and len(ctx) + plan[3] > self.draft.cfg.seq_len:
+            raise ValueError(f"{self.NAME}.submit: n_context {len(ctx)} + max_new {plan[3]} beyond the draft model's seq_len {self.draft.cfg.seq_len}")
         n_cached = int(n_cached)
         if n_cached and engine is None:
             raise ValueError(f"{self.NAME}.submit: n_cached needs the engine that holds the rows")
@@ -278,7 +326,16 @@ class ServeLoop:
                     check(L.rama_q8_kv_fork(ctx, C.byref(self.model.ccfg), C.byref(donor.state), C.byref(eng.state), 1, n_cached),
                           "rama_q8_kv_fork")
             arr, rec = _i32(toks), rama_q8_serve_plan(T, P, U, new, stop)
-            if self.spec:
+            if self.draft is not None:
+                # the draft model's rows of the whole context: a prefill enqueued before the admission, stream-ordered between two steps (the
+                # chain's begin sized every buffer it runs on, so the captured step holds none that it could regrow)
+                if self._down[slot] is None:
+                    self._down[slot] = self._new_engine(self.draft)
+                    self._mine.append(self._down[slot])
+                self._down[slot].prefill(toks)
+                self._call("admit_model", slot, C.byref(eng.state), C.byref(self._down[slot].state), arr, len(toks), n_cached, C.byref(rec),
+                           self._drafts[h][0])
+            elif self.spec:
                 K, N, hint = self._drafts[h]
                 harr = _i32(hint)
                 srec = rama_q8_serve_spec(K, N, harr if hint else None, len(hint))
@@ -457,6 +514,10 @@ class ServeLoop:
             q = rama_q8_serve_spec_report()
             self._call("spec_stats", C.byref(q))
             out["spec"] = serve_spec_report(q)
+        if self.draft is not None:
+            q = rama_q8_serve_model_report()
+            self._call("model_stats", C.byref(q))
+            out["model"] = serve_model_report(q)
         return out
 
     def close(self):
@@ -467,4 +528,4 @@ class ServeLoop:
             for e in self._mine:
                 e.free()
             self._mine, self._spare = [], []
-            self._own, self._eng = [None] * self.n_slots, [None] * self.n_slots
+            self._own, self._eng, self._down = [None] * self.n_slots, [None] * self.n_slots, [None] * self.n_slots
