@@ -437,6 +437,16 @@ int  rama_q8_model_load(rama_ctx *ctx, const char *path, rama_q8_model **out);
  * quantized by export.py quantize_q80's rule (scale = max|w| / 127, torch.round: halves to even).  RoPE tables as
  * rama_model_synth computes them without given tables. */
 int  rama_q8_model_synth(rama_ctx *ctx, const rama_config *cfg, int group_size, uint64_t seed, rama_q8_model **out);
+/* A resident fp32 weight set -- rama_model_weights of a loaded or synthetic model, or tensors uploaded one by one -- quantized on the
+ * device: the rama_q8_model that rama_q8_model_load gives from the version-2 file export.py writes for those weights.  tok, wq, wk,
+ * wv, wo, w1, w2, w3 and (unless shared: wcls == token_embedding_table, whatever cfg->shared_weight says) wcls by quantize_q80's rule in groups
+ * of group_size, every layer's matrix on its own; the fp32 norms copied; RoPE tables and the dequantized token table as
+ * rama_q8_model_synth makes them.  The quantizer reads the resident tensors where they lie (no scratch); the source is only read
+ * and stays valid.  Synchronises.  RAMA_EINVAL for a NULL argument, an incomplete weight set (a pipeline stage's), cfg->shared_weight
+ * set over a wcls of its own, group_size <= 0
+ * or one that does not divide dim and hidden_dim (the Python wrapper backs it off as version2_export does; this entry does not);
+ * RAMA_EUNSUP for n_kv_heads != n_heads. */
+int  rama_q8_model_from_f32(rama_ctx *ctx, const rama_config *cfg, const rama_weights *w, int group_size, rama_q8_model **out);
 int  rama_q8_model_config(const rama_q8_model *m, rama_config *cfg);
 int  rama_q8_model_weights(const rama_q8_model *m, rama_q8_weights *w);
 size_t rama_q8_model_bytes(const rama_q8_model *m);     /* bytes streamed per token: int8 values + scales + fp32 norms */
@@ -941,6 +951,34 @@ int  rama_serve_begin_spec(rama_ctx *ctx, const rama_config *cfg, const rama_wei
 int  rama_serve_admit_spec(rama_ctx *ctx, int slot, const rama_run_state *state, const int32_t *context_host, int n_context,
                            int n_cached, const rama_q8_serve_plan *plan, const rama_q8_serve_spec *spec);
 int  rama_serve_spec_stats(rama_ctx *ctx, rama_q8_serve_spec_report *out);
+
+/* MODEL DRAFTS IN THE IDLE ROWS OF THE PARITY-MODE SERVING CHAIN: rama_q8_serve_begin_model / _admit_model /
+ * _model_stats argument for argument, for an fp32 TARGET in parity mode (rama_weights) and a Q8 DRAFT model (dcfg, dw) over the
+ * same vocabulary -- rama_q8_model_from_f32 makes one from an fp32 model.  The same plan and report records;
+ * rama_q8_serve_model_plan_step is the host plan of both stacks.  A step is the Q8 chain's OPEN, SCHEDULE and DRAFT PASSES (the
+ * same kernels, the draft passes on the chain's own batch scratch), then the verify half of rama_serve_begin_spec's step -- the
+ * tiles' guard entries, the pass tile by tile, the final norm and classifier where the rows sit, the picks, the accept rule --,
+ * then CLOSE.  One graph replay on one stream, one captured graph for the chain's life.  Slot i's tokens and target cache rows
+ * are, bit for bit, parity-mode rama_generate's on that sequence alone; the draft cache contract is rama_q8_serve_begin_model's.
+ * rama_serve_begin_model: rama_serve_begin_spec's checks with hint_cap = 0 (parity mode only: RAMA_EUNSUP otherwise, at _steps
+ *   too), and rama_q8_serve_begin_model's of the draft model, n_draft_cap in 1..15 and 2 * n_slots <= 128.  Sized here, outside
+ *   any capture: the drafting tables, logits for max_rows rows, sampler slices for max(max_rows, 2 * n_slots) rows, the draft
+ *   batch scratch for 2 * n_slots rows, and the context's Q8 scratches for the draft's shape (what a rama_q8_prefill of the draft
+ *   cache runs on).  THE CAPTURED STEP HOLDS NONE OF THE CONTEXT'S Q8 SCRATCHES: a Q8 chain or a prefill with a larger Q8 model
+ *   on the same context may regrow them between two steps.  (The sampler's slices are shared: whoever regrows them drops every
+ *   captured step, this one included, and it is captured again.)
+ * rama_serve_admit_model: rama_q8_serve_admit_model's contract and refusals in this entry's words; `state` is an fp32 run state
+ *   of the target, `dstate` a run state of the draft model.  rama_serve_admit and _admit_at on such a chain admit with
+ *   n_draft = 0; rama_serve_admit_spec is RAMA_EINVAL.
+ * rama_serve_steps answers RAMA_EINVAL once the target (rama_model_free), the draft model (rama_q8_model_free), or the target or
+ *   draft run state of an occupied slot (rama_state_free) is gone.  rama_q8_kv_fork refuses a destination that is a live slot's
+ *   draft run state, on either chain.
+ * rama_serve_model_stats: as rama_q8_serve_model_stats; RAMA_EINVAL on a chain not begun with rama_serve_begin_model. */
+int  rama_serve_begin_model(rama_ctx *ctx, const rama_config *cfg, const rama_weights *w, const rama_config *dcfg,
+                            const rama_q8_weights *dw, int n_slots, int max_rows, int max_new_cap, int n_draft_cap);
+int  rama_serve_admit_model(rama_ctx *ctx, int slot, const rama_run_state *state, const rama_run_state *dstate,
+                            const int32_t *context_host, int n_context, int n_cached, const rama_q8_serve_plan *plan, int n_draft);
+int  rama_serve_model_stats(rama_ctx *ctx, rama_q8_serve_model_report *out);
 
 /* ---------------------------------------------------------------- measurement
  * HIP events on the context's stream (the stream the kernels are launched on). */

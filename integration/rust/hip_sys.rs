@@ -224,6 +224,8 @@ extern "C" {
     pub fn rama_q8_model_load(ctx: *mut rama_ctx, path: *const c_char, out: *mut *mut rama_q8_model) -> c_int;
     pub fn rama_q8_model_synth(ctx: *mut rama_ctx, cfg: *const rama_config, group_size: c_int, seed: u64,
                                out: *mut *mut rama_q8_model) -> c_int;
+    pub fn rama_q8_model_from_f32(ctx: *mut rama_ctx, cfg: *const rama_config, w: *const rama_weights, group_size: c_int,
+                                  out: *mut *mut rama_q8_model) -> c_int;
     pub fn rama_q8_model_config(m: *const rama_q8_model, cfg: *mut rama_config) -> c_int;
     pub fn rama_q8_model_weights(m: *const rama_q8_model, w: *mut rama_q8_weights) -> c_int;
     pub fn rama_q8_model_bytes(m: *const rama_q8_model) -> usize;
@@ -323,6 +325,12 @@ extern "C" {
                                          draft_cursor: *const i32, n_passes: c_int, rows_out: *mut rama_q8_serve_row, want_out: *mut i32,
                                          granted_out: *mut i32, draft_rows_out: *mut rama_q8_serve_row) -> c_int;
     pub fn rama_q8_serve_model_stats(ctx: *mut rama_ctx, out: *mut rama_q8_serve_model_report) -> c_int;
+    pub fn rama_serve_begin_model(ctx: *mut rama_ctx, cfg: *const rama_config, w: *const rama_weights, dcfg: *const rama_config,
+                                  dw: *const rama_q8_weights, n_slots: c_int, max_rows: c_int, max_new_cap: c_int, n_draft_cap: c_int) -> c_int;
+    pub fn rama_serve_admit_model(ctx: *mut rama_ctx, slot: c_int, state: *const rama_run_state, dstate: *const rama_run_state,
+                                  context_host: *const i32, n_context: c_int, n_cached: c_int, plan: *const rama_q8_serve_plan,
+                                  n_draft: c_int) -> c_int;
+    pub fn rama_serve_model_stats(ctx: *mut rama_ctx, out: *mut rama_q8_serve_model_report) -> c_int;
 }
 
 #[repr(C)] pub struct rama_pipe { _p: [u8; 0] }

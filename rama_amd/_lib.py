@@ -218,6 +218,7 @@ SIGNATURES = {
     "rama_kprof_read": (_int, [_vp, C.POINTER(_int), C.POINTER(C.c_double)]),
     "rama_q8_model_load": (_int, [_vp, C.c_char_p, C.POINTER(_vp)]),
     "rama_q8_model_synth": (_int, [_vp, _cfgp, _int, C.c_uint64, C.POINTER(_vp)]),
+    "rama_q8_model_from_f32": (_int, [_vp, _cfgp, _wp, _int, C.POINTER(_vp)]),
     "rama_q8_model_config": (_int, [_vp, _cfgp]),
     "rama_q8_model_weights": (_int, [_vp, C.POINTER(rama_q8_weights)]),
     "rama_q8_model_bytes": (_sz, [_vp]),
@@ -277,6 +278,9 @@ SIGNATURES = {
     "rama_serve_begin_spec": (_int, [_vp, _cfgp, C.POINTER(rama_weights), _int, _int, _int, _int, _int]),
     "rama_serve_admit_spec": (_int, [_vp, _int, _sp, i32p, _int, _int, C.POINTER(rama_q8_serve_plan), C.POINTER(rama_q8_serve_spec)]),
     "rama_serve_spec_stats": (_int, [_vp, C.POINTER(rama_q8_serve_spec_report)]),
+    "rama_serve_begin_model": (_int, [_vp, _cfgp, C.POINTER(rama_weights), _cfgp, C.POINTER(rama_q8_weights), _int, _int, _int, _int]),
+    "rama_serve_admit_model": (_int, [_vp, _int, _sp, _sp, i32p, _int, _int, C.POINTER(rama_q8_serve_plan), _int]),
+    "rama_serve_model_stats": (_int, [_vp, C.POINTER(rama_q8_serve_model_report)]),
 }
 
 # exported but not in the header (the rama_internal_* accessors tests read; most declare their own types where they call them): here

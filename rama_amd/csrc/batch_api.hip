@@ -767,12 +767,19 @@ int rama_serve_end(rama_ctx* c) {
 }
 
 // rama_serve_begin (spec false) and rama_serve_begin_spec: the latter sizes the drafting tables as well, and its sampler and logits for max_rows rows
-static int serve_begin(rama_ctx* c, const rama_config* cfg, const rama_weights* w, int n_slots, int max_rows, int max_new_cap, bool spec, int n_draft_cap, int hint_cap) {
+// dcfg, dw (rama_serve_begin_model): a chain with drafts whose drafts are that Q8 model's -- the sampler for the first draft pass's 2 n_slots rows as
+// well, and the draft side's allocations (serve_model_alloc)
+static int serve_begin(rama_ctx* c, const rama_config* cfg, const rama_weights* w, int n_slots, int max_rows, int max_new_cap, bool spec, int n_draft_cap, int hint_cap,
+                       const rama_config* dcfg = nullptr, const rama_q8_weights* dw = nullptr) {
     RAMA_ENTER(c);
     REQUIRE(c, RAMA_EINVAL, "ctx is NULL");
     int rc = check_cfg(cfg); if (rc) return rc;
+    if (dcfg) {
+        rc = check_cfg(dcfg); if (rc) return rc;
+        rc = serve_model_begin_check("serve_begin_model", cfg, dcfg, dw, n_slots, max_rows, n_draft_cap); if (rc) return rc;
+    }
     REQUIRE(w && w->token_embedding_table && w->rms_final_weight && w->wq && w->wcls, RAMA_EINVAL, "serve_begin: missing weights");
-    rc = check_slots_rows("serve_begin", n_slots, max_rows); if (rc) return rc;
+    if (!dcfg) { rc = check_slots_rows("serve_begin", n_slots, max_rows); if (rc) return rc; }      // (with a draft model: serve_model_begin_check has looked)
     REQUIRE(max_new_cap >= 1 && max_new_cap <= cfg->seq_len - 1, RAMA_EINVAL, "serve_begin: max_new_cap outside [1, seq_len - 1]");
     REQUIRE(c->tune_ref_order == 1 && !c->tune_tol && !c->tune_bar, RAMA_EUNSUP, "serve_begin: parity mode only (\"ref_order\" = 1): no fast mode, no bar mode");
     const int V = cfg->vocab_size;
@@ -786,7 +793,7 @@ static int serve_begin(rama_ctx* c, const rama_config* cfg, const rama_weights* 
     bool ok = false;
     rc = chain_batch_copies(c, cfg, w, true, &copies, &ccls, &ok); if (rc) return rc;
     REQUIRE(ok, RAMA_EUNSUP, "serve_begin: a shape or weights the parity-mode token batch does not take (dim, hidden_dim multiples of 16; chain-order copies)");
-    if (sampler) { rc = ensure_topp_batch(c, spec ? max_rows : n_slots, V); if (rc) return rc; }      // sized here, outside any capture (a chain with drafts picks per row)
+    if (sampler) { rc = ensure_topp_batch(c, spec ? std::max(max_rows, dcfg ? 2 * n_slots : 0) : n_slots, V); if (rc) return rc; }      // sized here, outside any capture (a chain with drafts picks per row)
     // the new chain is made beside the running one, which goes only when nothing can fail any more
     rama_ctx::Serve fresh;
     auto make = [&]() -> int {
@@ -797,7 +804,7 @@ static int serve_begin(rama_ctx* c, const rama_config* cfg, const rama_weights* 
         HIPCHK(hipMalloc(&fresh.scratch, floats * sizeof(float)));
         HIPCHK(hipMemsetAsync(fresh.scratch, 0, floats * sizeof(float), c->stream));      // (an idle row is computed along in a live tile: finite values, never read by anyone)
         HIPCHK(hipStreamSynchronize(c->stream));      // (also: nothing of the previous chain is still running)
-        return 0;
+        return dcfg ? serve_model_alloc(c, fresh, dcfg, dw) : 0;
     };
     rc = make();
     if (rc) { serve_state_free(fresh); hipFree(fresh.scratch); hipFree(fresh.tguard); return rc; }
@@ -815,6 +822,16 @@ int rama_serve_begin_spec(rama_ctx* c, const rama_config* cfg, const rama_weight
     return serve_begin(c, cfg, w, n_slots, max_rows, max_new_cap, true, n_draft_cap, hint_cap);
 }
 
+// ---- MODEL DRAFTS INSIDE THE FP32 SERVING CHAIN: rama_serve_begin_spec with hint_cap 0, plus a Q8 draft model over the same vocabulary.
+// The tables, the draft passes and the serve_model_* kernels are the Q8 chain's (q8_serve_model.hpp in q8_api.hip's code object, reached through ctx.hpp);
+// the verify half is the step of rama_serve_begin_spec.
+int rama_serve_begin_model(rama_ctx* c, const rama_config* cfg, const rama_weights* w, const rama_config* dcfg, const rama_q8_weights* dw,
+                           int n_slots, int max_rows, int max_new_cap, int n_draft_cap) {
+    RAMA_ENTER(c);
+    REQUIRE(c && dcfg && dw, RAMA_EINVAL, "serve_begin_model: NULL argument");
+    return serve_begin(c, cfg, w, n_slots, max_rows, max_new_cap, true, n_draft_cap, 0, dcfg, dw);
+}
+
 // rama_serve_admit (n_cached 0), rama_serve_admit_at and -- spec != NULL -- rama_serve_admit_spec: one body, rama_q8_serve_admit*'s checks in their order.
 // The slot starts PROMPT at cursor = n_cached, over rows 0 .. n_cached - 1 that earlier work on the stream has put into the run state's caches
 static const ServeNames kServeNames{"serve_admit", "serve_admit_at", "rama_serve_begin", "serve_admit_spec", "rama_serve_begin_spec"};
@@ -828,10 +845,15 @@ static int serve_admit(rama_ctx* c, int slot, const rama_run_state* state, const
     rc = check_stage(&sv.cfg, &sv.w, state, &st); if (rc) return rc;
     rc = serve_admit_tail(kServeNames, sv, sv.cfg, slot, state, context_host, n_context, n_cached, plan); if (rc) return rc;
     rc = serve_admit_spec_check(kServeNames, sv, sv.cfg.vocab_size, spec); if (rc) return rc;
+    if (sv.model) {      // a chain begun with rama_serve_begin_model: no lookup drafts, and no run state that a live slot drafts on
+        REQUIRE(!spec, RAMA_EINVAL, "serve_admit_spec: the chain was begun with rama_serve_begin_model: model drafts replace the lookup");
+        REQUIRE(!serve_model_state_clash(sv, slot, state), RAMA_EINVAL, "serve_admit: the run state is already in a live slot");
+    }
     if (set_device(c)) return 1;
     rc = serve_admit_install(c, sv, slot, state, context_host, n_context, n_cached, plan); if (rc) return rc;
     rc = serve_admit_spec_install(c, sv, slot, spec); if (rc) return rc;
     sv.states[slot] = *state; sv.occupied[slot] = 1; sv.gen[slot]++;
+    if (sv.model) sv.dstates[slot] = rama_run_state{};
     return 0;
 }
 
@@ -848,6 +870,27 @@ int rama_serve_admit_spec(rama_ctx* c, int slot, const rama_run_state* state, co
                           const rama_q8_serve_plan* plan, const rama_q8_serve_spec* spec) {
     REQUIRE(spec, RAMA_EINVAL, "serve_admit_spec: NULL argument");
     return serve_admit(c, slot, state, context_host, n_context, n_cached, plan, spec);
+}
+
+static const ServeNames kServeModelNames{"serve_admit_model", "serve_admit_model", "rama_serve_begin_model", "serve_admit_model", "rama_serve_begin_model"};
+// rama_q8_serve_admit_model's checks in their order, in this entry's words; the draft run state is a Q8 stack's, the target's an fp32 model's
+int rama_serve_admit_model(rama_ctx* c, int slot, const rama_run_state* state, const rama_run_state* dstate, const int32_t* context_host, int n_context,
+                           int n_cached, const rama_q8_serve_plan* plan, int n_draft) {
+    RAMA_ENTER(c);
+    REQUIRE(c && c->sv.n_slots > 0 && c->sv.model, RAMA_EINVAL, "serve_admit_model: call rama_serve_begin_model first");
+    auto& sv = c->sv;
+    int rc = serve_admit_head(kServeModelNames, sv, sv.live, slot, state, context_host, plan); if (rc) return rc;
+    REQUIRE(dstate, RAMA_EINVAL, "serve_admit_model: NULL argument");
+    rama_stage st{0, sv.cfg.n_layers, 1, 1};
+    rc = check_stage(&sv.cfg, &sv.w, state, &st); if (rc) return rc;
+    rc = serve_admit_model_dstate(c, sv, dstate); if (rc) return rc;
+    rc = serve_admit_tail(kServeModelNames, sv, sv.cfg, slot, state, context_host, n_context, n_cached, plan); if (rc) return rc;
+    rc = serve_admit_model_check(kServeModelNames, sv, slot, state, dstate, n_context, plan, n_draft); if (rc) return rc;
+    if (set_device(c)) return 1;
+    rc = serve_admit_install(c, sv, slot, state, context_host, n_context, n_cached, plan); if (rc) return rc;
+    rc = serve_admit_model_install(c, sv, slot, dstate, n_context, n_draft); if (rc) return rc;
+    sv.states[slot] = *state; sv.dstates[slot] = *dstate; sv.occupied[slot] = 1; sv.gen[slot]++;
+    return 0;
 }
 
 // the pass over the step's row table, tile by tile in ascending order
@@ -874,13 +917,11 @@ static int enqueue_serve_step(rama_ctx* c, const ServeScratch& s) {
     return launch_serve_pick(c, sv.t, s.LG, V, sv.sampler);
 }
 
-// one step of a chain begun with rama_serve_begin_spec: the drafts, the scheduler, the tiles' guard entries, the wanted rows' embeddings, the pass, then --
-// tile by tile, where the rows sit -- the final norm and the classifier of the tiles that hold a logits row, every flagged row's pick, the accept rule
-static int enqueue_serve_spec_step(rama_ctx* c, const ServeScratch& s) {
+// the verify half of a step with drafts, behind the scheduler: from the tiles' guard entries to the accept rule
+static int enqueue_serve_verify(rama_ctx* c, const ServeScratch& s) {
     auto& sv = c->sv;
     const int dim = sv.cfg.dim, V = sv.cfg.vocab_size, R = sv.max_rows;
-    int rc = launch_serve_draft(c, sv.t, sv.st); if (rc) return rc;
-    rc = launch_serve_spec_schedule(c, sv.t, sv.st); if (rc) return rc;
+    int rc;
     hipLaunchKernelGGL(serve_tile_guard_kernel, dim3(1), dim3(kTileGuardThreads), 0, c->stream, (const int*)sv.st.lflag, R, sv.tguard);
     LAUNCHCHK();
     rc = launch_serve_embed(c, s.b.X, sv.w.token_embedding_table, sv.t, dim); if (rc) return rc;
@@ -898,6 +939,21 @@ static int enqueue_serve_spec_step(rama_ctx* c, const ServeScratch& s) {
     return launch_serve_spec_accept(c, sv.t, sv.st);
 }
 
+// one step of a chain begun with rama_serve_begin_spec: the drafts, the scheduler, the tiles' guard entries, the wanted rows' embeddings, the pass, then --
+// tile by tile, where the rows sit -- the final norm and the classifier of the tiles that hold a logits row, every flagged row's pick, the accept rule
+static int enqueue_serve_spec_step(rama_ctx* c, const ServeScratch& s) {
+    auto& sv = c->sv;
+    int rc = launch_serve_draft(c, sv.t, sv.st); if (rc) return rc;
+    rc = launch_serve_spec_schedule(c, sv.t, sv.st); if (rc) return rc;
+    return enqueue_serve_verify(c, s);
+}
+// one step of a chain begun with rama_serve_begin_model: the drafting half is the Q8 chain's (the wants, the scheduler, n_draft_cap passes of the draft
+// model with their picks), the verify half the step's above, then the draft cursors
+static int enqueue_serve_model_step(rama_ctx* c, const ServeScratch& s) {
+    int rc = launch_serve_model_drafts(c, c->sv); if (rc) return rc;
+    rc = enqueue_serve_verify(c, s); if (rc) return rc;
+    return launch_serve_model_close(c, c->sv);
+}
 int rama_serve_steps(rama_ctx* c, int n_steps) {
     RAMA_ENTER(c);
     REQUIRE(c && c->sv.n_slots > 0, RAMA_EINVAL, "serve_steps: call rama_serve_begin first");
@@ -914,9 +970,9 @@ int rama_serve_steps(rama_ctx* c, int n_steps) {
     REQUIRE(ok, RAMA_EUNSUP, "serve_steps: the chain-order copies are gone and cannot be made (\"chain\" / \"prefill_chain\" = 0?)");
     const float* now[7] = {copies.cq, copies.ck, copies.cv, copies.co, copies.c13, copies.c2, ccls};
     if (memcmp(now, sv.copies, sizeof now)) { if (sv.cg.exec) HIPCHK(hipStreamSynchronize(c->stream)); destroy_graph(sv.cg); memcpy(sv.copies, now, sizeof now); }
-    if (sv.sampler) { rc = ensure_topp_batch(c, sv.spec ? sv.max_rows : sv.n_slots, sv.cfg.vocab_size); if (rc) return rc; }
+    if (sv.sampler) { rc = ensure_topp_batch(c, sv.spec ? std::max(sv.max_rows, sv.draft_rows) : sv.n_slots, sv.cfg.vocab_size); if (rc) return rc; }
     const ServeScratch s = serve_scratch(sv, copies, ccls);
-    auto step = [&] { return sv.spec ? enqueue_serve_spec_step(c, s) : enqueue_serve_step(c, s); };
+    auto step = [&] { return sv.model ? enqueue_serve_model_step(c, s) : sv.spec ? enqueue_serve_spec_step(c, s) : enqueue_serve_step(c, s); };
     c->embedded_x = nullptr; c->host_pos = -1;
     const bool graphs = c->graph_mode && c->kp.kernel_id < 0;
     for (int i = 0; i < n_steps; i++, sv.steps++) {
@@ -954,3 +1010,8 @@ int rama_serve_spec_stats(rama_ctx* c, rama_q8_serve_spec_report* out) {
     return serve_spec_report(c, c->sv, out);
 }
 
+int rama_serve_model_stats(rama_ctx* c, rama_q8_serve_model_report* out) {
+    RAMA_ENTER(c);
+    REQUIRE(c && out && c->sv.n_slots > 0 && c->sv.model, RAMA_EINVAL, "serve_model_stats: no chain begun with rama_serve_begin_model");
+    return serve_model_report(c, c->sv, out);
+}

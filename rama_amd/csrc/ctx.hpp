@@ -460,6 +460,20 @@ int launch_serve_spec_schedule(rama_ctx* c, const ServeTables& t, const ServeSpe
 int launch_serve_spec_pick(rama_ctx* c, const ServeTables& t, const ServeSpecTables& st, const float* logits, int V, bool sampled);
 int launch_serve_spec_accept(rama_ctx* c, const ServeTables& t, const ServeSpecTables& st);
 int serve_spec_report(rama_ctx* c, const rama_ctx::ServeState& sv, rama_q8_serve_spec_report* out);
+// ... and what a chain with a DRAFT MODEL (rama_q8_serve_begin_model, rama_serve_begin_model; q8_serve_model.hpp) does alike whatever its target: the
+// begin's refusals in the entry's words, the draft side's allocations behind serve_state_alloc_spec (the chain's own draft batch scratch and tables; the
+// context's Q8 scratches sized for the draft's shape), an _admit_model entry's checks (names.admit_spec: the entry, names.begin_spec: its begin) and
+// install, the report, and the two halves of the step around the verify pass -- the draft passes hold the chain's own buffers and the sampler's slices only
+int serve_model_begin_check(const char* entry, const rama_config* cfg, const rama_config* dcfg, const rama_q8_weights* dw, int n_slots, int max_rows, int n_draft_cap);
+int serve_model_alloc(rama_ctx* c, rama_ctx::ServeState& sv, const rama_config* dcfg, const rama_q8_weights* dw);
+bool serve_model_state_clash(const rama_ctx::ServeState& sv, int slot, const rama_run_state* s);
+int serve_admit_model_dstate(rama_ctx* c, const rama_ctx::ServeState& sv, const rama_run_state* dstate);
+int serve_admit_model_check(const ServeNames& names, const rama_ctx::ServeState& sv, int slot, const rama_run_state* state, const rama_run_state* dstate,
+                            int n_context, const rama_q8_serve_plan* plan, int n_draft);
+int serve_admit_model_install(rama_ctx* c, rama_ctx::ServeState& sv, int slot, const rama_run_state* dstate, int n_context, int n_draft);
+int serve_model_report(rama_ctx* c, const rama_ctx::ServeState& sv, rama_q8_serve_model_report* out);
+int launch_serve_model_drafts(rama_ctx* c, const rama_ctx::ServeState& sv);
+int launch_serve_model_close(rama_ctx* c, const rama_ctx::ServeState& sv);
 
 // the pending run of recorded 1:1 ops is issued by whatever enters the library next: first statement of every entry point
 // that enqueues, synchronises or changes a setting

@@ -67,6 +67,8 @@ extern "C" void rama_internal_drop_q8_graphs(rama_ctx* c, const rama_q8_weights*
         if (freed && ch->w.wq == freed->wq) ch->live = false;
     if (freed && c->q8p.model && c->q8p.dw.wq == freed->wq) c->q8p.live = false;      // the speculative chain's draft model
     if (freed && c->q8s.model && c->q8s.dw.wq == freed->wq) c->q8s.live = false;      // ... and the serving chain's
+    // ... and the fp32 serving chain's (rama_serve_begin_model): its captured step is no Q8 graph, and goes only with its own draft model
+    if (freed && c->sv.model && c->sv.dw.wq == freed->wq) { destroy_graph(c->sv.cg); c->sv.live = false; }
 }
 
 // the serving chain's allocations (rama_q8_serve_begin / _end, release_q8); the stream is idle
@@ -1161,8 +1163,8 @@ int serve_admit_spec_install(rama_ctx* c, rama_ctx::ServeState& sv, int slot, co
     return 0;
 }
 
-// a chain begun with rama_q8_serve_begin_model: `s` shares a cache with the draft run state of a live slot other than `slot`
-static bool serve_model_state_clash(const rama_ctx::ServeState& sv, int slot, const rama_run_state* s) {
+// a chain begun with an _begin_model entry: `s` shares a cache with the draft run state of a live slot other than `slot`
+bool serve_model_state_clash(const rama_ctx::ServeState& sv, int slot, const rama_run_state* s) {
     for (int j = 0; j < sv.n_slots; j++) {
         const rama_run_state& d = sv.dstates[j];
         if (j == slot || !serve_slot_live(sv, j) || !d.key_cache) continue;
@@ -1214,57 +1216,94 @@ int rama_q8_serve_admit_spec(rama_ctx* c, int slot, const rama_run_state* state,
 // ---- MODEL DRAFTS INSIDE THE SERVING CHAIN (q8_serve_model.hpp): rama_q8_serve_begin_spec with hint_cap 0, plus a draft model
 // whose passes run on a batch scratch of their own; a slot is admitted with a draft run state and drafts with that model instead of the lookup
 
+// what an _begin_model entry refuses of the draft model and the geometry, in the entry's words (before anything is allocated)
+int serve_model_begin_check(const char* entry, const rama_config* cfg, const rama_config* dcfg, const rama_q8_weights* dw, int n_slots, int max_rows, int n_draft_cap) {
+    REFUSE_UNLESS(dw && dw->group_size > 0 && dcfg->dim % dw->group_size == 0 && dcfg->hidden_dim % dw->group_size == 0, entry,
+                  "the draft model's group_size must divide its dim and hidden_dim");
+    REFUSE_UNLESS(q8_weights_complete(dw), entry, "missing draft weights");
+    REFUSE_UNLESS(dcfg->vocab_size == cfg->vocab_size, entry, "the draft model's vocabulary is not the target's");
+    REFUSE_UNLESS(n_draft_cap >= 1 && n_draft_cap <= kSpecMaxDraft, entry, "n_draft_cap outside 1..15");
+    CHECKED(check_slots_rows(entry, n_slots, max_rows));
+    REFUSE_UNLESS(2 * n_slots <= kQ8bMaxTok, entry, "2 n_slots > 128 (the first draft pass carries up to two rows per slot)");
+    UNSUPPORTED_UNLESS(q8_batch_ok(dcfg), entry, "a draft model of a shape the Q8 token-batch pass does not take");
+    return 0;
+}
+
+// The draft side of a chain whose tables serve_state_alloc_spec has made: the context's two Q8 scratches for the draft's shape (what a draft-model
+// prefill between two steps runs on: sized here, outside any capture), then what the draft passes themselves run on -- a batch scratch of 2 n_slots rows
+// and the draft tables, both the chain's own.  The caller frees a half-made state (serve_state_free).
+int serve_model_alloc(rama_ctx* c, rama_ctx::ServeState& sv, const rama_config* dcfg, const rama_q8_weights* dw) {
+    const int n_slots = sv.n_slots, draft_rows = 2 * n_slots;
+    Q8BatchScratch b{};
+    int r = ensure_q8_scratch(c, dcfg); if (r) return r;
+    r = ensure_q8_batch_scratch(c, dcfg, dw->group_size, &b); if (r) return r;
+    Q8BatchScratch db{};
+    const size_t dneed = q8_batch_scratch_lay(dcfg, dw->group_size, (size_t)draft_rows, nullptr, &db);
+    HIPCHK(hipMalloc(&sv.dblob, dneed));
+    HIPCHK(hipMemset(sv.dblob, 0, dneed));
+    ServeModelTables& m = sv.mt;
+    const size_t N = (size_t)n_slots;
+    auto lay = [&](char* base) {
+        BlobCarver bc{base};
+        bc.take(m.ms, N); bc.take(m.rows0, 2 * N); bc.take(m.row_tok0, 2 * N); bc.take(m.trow0, 2 * N);
+        bc.take(m.rows, N); bc.take(m.row_tok, N); bc.take(m.trow, N);
+        return bc.used;
+    };
+    const size_t need = lay(nullptr);
+    HIPCHK(hipMalloc(&sv.mblob, need));
+    HIPCHK(hipMemset(sv.mblob, 0, need));
+    lay(sv.mblob);
+    sv.model = true; sv.dcfg = *dcfg; sv.dw = *dw; sv.draft_rows = draft_rows;
+    sv.dstates.assign(N, rama_run_state{});
+    return 0;
+}
+
 int rama_q8_serve_begin_model(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const rama_config* dcfg, const rama_q8_weights* dw,
                               int n_slots, int max_rows, int max_new_cap, int n_draft_cap) {
     RAMA_ENTER(c);
     REQUIRE(c, RAMA_EINVAL, "ctx is NULL");
     int rc = check_cfg(cfg); if (rc) return rc;
     rc = check_cfg(dcfg); if (rc) return rc;
-    REQUIRE(dw && dw->group_size > 0 && dcfg->dim % dw->group_size == 0 && dcfg->hidden_dim % dw->group_size == 0, RAMA_EINVAL,
-            "q8_serve_begin_model: the draft model's group_size must divide its dim and hidden_dim");
-    REQUIRE(q8_weights_complete(dw), RAMA_EINVAL, "q8_serve_begin_model: missing draft weights");
-    REQUIRE(dcfg->vocab_size == cfg->vocab_size, RAMA_EINVAL, "q8_serve_begin_model: the draft model's vocabulary is not the target's");
-    REQUIRE(n_draft_cap >= 1 && n_draft_cap <= kSpecMaxDraft, RAMA_EINVAL, "q8_serve_begin_model: n_draft_cap outside 1..15");
-    CHECKED(check_slots_rows("q8_serve_begin_model", n_slots, max_rows));
-    REQUIRE(2 * n_slots <= kQ8bMaxTok, RAMA_EINVAL, "q8_serve_begin_model: 2 n_slots > 128 (the first draft pass carries up to two rows per slot)");
-    REQUIRE(q8_batch_ok(dcfg), RAMA_EUNSUP, "q8_serve_begin_model: a draft model of a shape the Q8 token-batch pass does not take");
-    const int draft_rows = 2 * n_slots;
-    rc = serve_begin(c, cfg, w, n_slots, max_rows, max_new_cap, true, n_draft_cap, 0, draft_rows); if (rc) return rc;
-    auto& sv = c->q8s;
+    CHECKED(serve_model_begin_check("q8_serve_begin_model", cfg, dcfg, dw, n_slots, max_rows, n_draft_cap));
+    rc = serve_begin(c, cfg, w, n_slots, max_rows, max_new_cap, true, n_draft_cap, 0, 2 * n_slots); if (rc) return rc;
     // everything a draft pass, and a draft-model prefill between two steps, runs on: sized here, outside any capture, so that neither regrows a
-    // buffer the captured step holds -- both scratches of the context for the larger of the two shapes, the draft passes' own for draft_rows rows
-    auto sized = [&]() -> int {
-        Q8BatchScratch b{};
-        int r = ensure_q8_scratch(c, dcfg); if (r) return r;
-        r = ensure_q8_batch_scratch(c, dcfg, dw->group_size, &b); if (r) return r;
-        r = q8_chain_scratch(c, cfg, w->group_size, 0, &b); if (r) return r;
-        Q8BatchScratch db{};
-        const size_t dneed = q8_batch_scratch_lay(dcfg, dw->group_size, (size_t)draft_rows, nullptr, &db);
-        HIPCHK(hipMalloc(&sv.dblob, dneed));
-        HIPCHK(hipMemset(sv.dblob, 0, dneed));
-        ServeModelTables& m = sv.mt;
-        const size_t N = (size_t)n_slots;
-        auto lay = [&](char* base) {
-            BlobCarver bc{base};
-            bc.take(m.ms, N); bc.take(m.rows0, 2 * N); bc.take(m.row_tok0, 2 * N); bc.take(m.trow0, 2 * N);
-            bc.take(m.rows, N); bc.take(m.row_tok, N); bc.take(m.trow, N);
-            return bc.used;
-        };
-        const size_t need = lay(nullptr);
-        HIPCHK(hipMalloc(&sv.mblob, need));
-        HIPCHK(hipMemset(sv.mblob, 0, need));
-        lay(sv.mblob);
-        return 0;
-    };
-    rc = sized();
+    // buffer the captured step holds -- both scratches of the context for the larger of the two shapes, the draft passes' own for 2 n_slots rows
+    rc = serve_model_alloc(c, c->q8s, dcfg, dw);
+    Q8BatchScratch b{};
+    if (!rc) rc = q8_chain_scratch(c, cfg, w->group_size, 0, &b);
     if (rc) { serve_release(c); return rc; }
-    sv.model = true; sv.dcfg = *dcfg; sv.dw = *dw; sv.draft_rows = draft_rows;
-    sv.dstates.assign((size_t)n_slots, rama_run_state{});
     return 0;
 }
 
 static const ServeNames kQ8ServeModelNames{"q8_serve_admit_model", "q8_serve_admit_model", "rama_q8_serve_begin_model", "q8_serve_admit_model",
                                            "rama_q8_serve_begin_model"};
+
+// an _admit_model entry's refusals behind serve_admit_tail, in its words (names.admit_spec; names.begin_spec is its _begin_model entry) ...
+int serve_admit_model_check(const ServeNames& names, const rama_ctx::ServeState& sv, int slot, const rama_run_state* state, const rama_run_state* dstate,
+                            int n_context, const rama_q8_serve_plan* plan, int n_draft) {
+    const char* entry = names.admit_spec;
+    char what[2][112];
+    snprintf(what[0], sizeof what[0], "n_draft beyond %s's n_draft_cap", names.begin_spec);
+    REFUSE_UNLESS(n_draft >= 0 && n_draft <= sv.n_draft_cap, entry, what[0]);
+    REFUSE_UNLESS(n_context <= sv.dcfg.seq_len - plan->max_new, entry, "n_context + max_new beyond the draft model's seq_len");
+    REFUSE_UNLESS(dstate->key_cache != state->key_cache && dstate->value_cache != state->value_cache, entry, "the draft run state is the target's");
+    for (int j = 0; j < sv.n_slots; j++)
+        REFUSE_UNLESS(j == slot || !serve_slot_live(sv, j) || (sv.states[j].key_cache != dstate->key_cache && sv.states[j].value_cache != dstate->value_cache),
+                      entry, "the draft run state is already in a live slot");
+    REFUSE_UNLESS(!serve_model_state_clash(sv, slot, dstate) && !serve_model_state_clash(sv, slot, state), entry, "a run state is already a live slot's draft state");
+    return 0;
+}
+// ... the draft run state against the draft model (where the entry checks the target's against its own) ...
+int serve_admit_model_dstate(rama_ctx* c, const rama_ctx::ServeState& sv, const rama_run_state* dstate) { return q8_check(c, &sv.dcfg, &sv.dw, dstate); }
+// ... and the drafting half of the install, behind serve_admit_install: the slot's n_draft, and its draft cursor -- rows 0 .. n_context - 1 of the draft
+// cache hold the whole context (the caller's contract)
+int serve_admit_model_install(rama_ctx* c, rama_ctx::ServeState& sv, int slot, const rama_run_state* dstate, int n_context, int n_draft) {
+    const rama_q8_serve_spec spec{n_draft, 1, nullptr, 0};
+    const int rc = serve_admit_spec_install(c, sv, slot, &spec); if (rc) return rc;
+    hipLaunchKernelGGL(serve_model_install_kernel, dim3(1), dim3(64), 0, c->stream, sv.mt, slot, dstate->key_cache, dstate->value_cache, n_context);
+    LAUNCHCHK();
+    return 0;
+}
 
 int rama_q8_serve_admit_model(rama_ctx* c, int slot, const rama_run_state* state, const rama_run_state* dstate, const int32_t* context_host,
                               int n_context, int n_cached, const rama_q8_serve_plan* plan, int n_draft) {
@@ -1275,22 +1314,12 @@ int rama_q8_serve_admit_model(rama_ctx* c, int slot, const rama_run_state* state
     CHECKED(serve_admit_head(kQ8ServeModelNames, sv, sv.live, slot, state, context_host, plan));
     REFUSE_UNLESS(dstate, entry, "NULL argument");
     int rc = q8_check(c, &sv.cfg, &sv.w, state); if (rc) return rc;
-    rc = q8_check(c, &sv.dcfg, &sv.dw, dstate); if (rc) return rc;
+    rc = serve_admit_model_dstate(c, sv, dstate); if (rc) return rc;
     CHECKED(serve_admit_tail(kQ8ServeModelNames, sv, sv.cfg, slot, state, context_host, n_context, n_cached, plan));
-    REFUSE_UNLESS(n_draft >= 0 && n_draft <= sv.n_draft_cap, entry, "n_draft beyond rama_q8_serve_begin_model's n_draft_cap");
-    REFUSE_UNLESS(n_context <= sv.dcfg.seq_len - plan->max_new, entry, "n_context + max_new beyond the draft model's seq_len");
-    REFUSE_UNLESS(dstate->key_cache != state->key_cache && dstate->value_cache != state->value_cache, entry, "the draft run state is the target's");
-    for (int j = 0; j < sv.n_slots; j++)
-        REFUSE_UNLESS(j == slot || !serve_slot_live(sv, j) || (sv.states[j].key_cache != dstate->key_cache && sv.states[j].value_cache != dstate->value_cache),
-                      entry, "the draft run state is already in a live slot");
-    REFUSE_UNLESS(!serve_model_state_clash(sv, slot, dstate) && !serve_model_state_clash(sv, slot, state), entry, "a run state is already a live slot's draft state");
+    CHECKED(serve_admit_model_check(kQ8ServeModelNames, sv, slot, state, dstate, n_context, plan, n_draft));
     if (set_device(c)) return 1;
     rc = serve_admit_install(c, sv, slot, state, context_host, n_context, n_cached, plan); if (rc) return rc;
-    const rama_q8_serve_spec spec{n_draft, 1, nullptr, 0};
-    rc = serve_admit_spec_install(c, sv, slot, &spec); if (rc) return rc;
-    // the draft cursor: rows 0 .. n_context - 1 of the draft cache hold the whole context (the caller's contract)
-    hipLaunchKernelGGL(serve_model_install_kernel, dim3(1), dim3(64), 0, c->stream, sv.mt, slot, dstate->key_cache, dstate->value_cache, n_context);
-    LAUNCHCHK();
+    rc = serve_admit_model_install(c, sv, slot, dstate, n_context, n_draft); if (rc) return rc;
     sv.states[slot] = *state; sv.dstates[slot] = *dstate; sv.occupied[slot] = 1; sv.gen[slot]++;
     return 0;
 }
@@ -1326,10 +1355,7 @@ int rama_q8_serve_model_plan_step(const rama_q8_serve_slot* slots, int n_slots, 
     return 0;
 }
 
-int rama_q8_serve_model_stats(rama_ctx* c, rama_q8_serve_model_report* out) {
-    RAMA_ENTER(c);
-    REQUIRE(c && out && c->q8s.n_slots > 0 && c->q8s.model, RAMA_EINVAL, "q8_serve_model_stats: no chain begun with rama_q8_serve_begin_model");
-    const auto& sv = c->q8s;
+int serve_model_report(rama_ctx* c, const rama_ctx::ServeState& sv, rama_q8_serve_model_report* out) {
     { const int rh = q8_drain(c); if (rh) return rh; }
     std::vector<ServeModelSlot> ms(sv.n_slots);
     HIPCHK(hipMemcpy(ms.data(), sv.mt.ms, sizeof(ServeModelSlot) * sv.n_slots, hipMemcpyDeviceToHost));
@@ -1340,6 +1366,20 @@ int rama_q8_serve_model_stats(rama_ctx* c, rama_q8_serve_model_report* out) {
         out->draft_cursor[i] = ms[i].Dc;
     }
     return 0;
+}
+
+int rama_q8_serve_model_stats(rama_ctx* c, rama_q8_serve_model_report* out) {
+    RAMA_ENTER(c);
+    REQUIRE(c && out && c->q8s.n_slots > 0 && c->q8s.model, RAMA_EINVAL, "q8_serve_model_stats: no chain begun with rama_q8_serve_begin_model");
+    return serve_model_report(c, c->q8s, out);
+}
+
+// slot j's occupant runs on a cache of `s`: its target run state, or -- a chain with a draft model -- its draft run state
+static bool serve_slot_holds(const rama_ctx::ServeState& sv, int j, const rama_run_state& s) {
+    const rama_run_state& t = sv.states[j];
+    if (t.key_cache == s.key_cache || t.value_cache == s.value_cache) return true;
+    if (!sv.model || !sv.dstates[j].key_cache) return false;
+    return sv.dstates[j].key_cache == s.key_cache || sv.dstates[j].value_cache == s.value_cache;
 }
 
 // rows [0, n_rows) of every layer of src's caches into every destination's: one launch (q8_fork.hpp), stream-ordered
@@ -1369,8 +1409,7 @@ int rama_q8_kv_fork(rama_ctx* c, const rama_config* cfg, const rama_run_state* s
     for (const auto& ch : chains)
         for (int d = 0; d < n_dst; d++)
             for (int j = 0; j < ch.sv->n_slots; j++)
-                REQUIRE(!serve_slot_live(*ch.sv, j) || (ch.sv->states[j].key_cache != dsts[d].key_cache && ch.sv->states[j].value_cache != dsts[d].value_cache),
-                        RAMA_EINVAL, ch.what);
+                REQUIRE(!serve_slot_live(*ch.sv, j) || !serve_slot_holds(*ch.sv, j, dsts[d]), RAMA_EINVAL, ch.what);
     if (n_rows == 0) return 0;
     const size_t span = (size_t)n_rows * (size_t)cfg->dim, reach = layer * (size_t)(cfg->n_layers - 1) + span;
     for (int d = 0; d < n_dst; d++) { RAMA_WRITES(c, dsts[d].key_cache, reach); RAMA_WRITES(c, dsts[d].value_cache, reach); }
@@ -1478,6 +1517,17 @@ static int enqueue_q8_serve_spec_step(rama_ctx* c, const Q8BatchScratch& b) {
 // row of the next pass; then the spec step's pass, picks and accept rule, and the draft cursors
 static int enqueue_q8_serve_model_step(rama_ctx* c, const Q8BatchScratch& b) {
     auto& sv = c->q8s;
+    int rc = launch_serve_model_drafts(c, sv); if (rc) return rc;
+    rc = enqueue_q8_batch_pass(c, &sv.cfg, &sv.w, b, sv.t.row_tok, sv.t.rows, sv.max_rows); if (rc) return rc;
+    rc = launch_serve_spec_pick(c, sv.t, sv.st, b.LG, sv.cfg.vocab_size, sv.sampler); if (rc) return rc;
+    rc = launch_serve_spec_accept(c, sv.t, sv.st); if (rc) return rc;
+    return launch_serve_model_close(c, sv);
+}
+// q8_serve_model.hpp's kernels and the draft passes for either chain with a draft model (ctx.hpp).  The drafting half of a step: the wants and the first
+// draft pass's rows, the scheduler, then n_draft_cap token-batch passes of the draft model over the chain's own scratch (sv.dblob: nothing of the
+// context's Q8 scratches, so whoever regrows those moves nothing a captured step holds) -- 2 n_slots rows, then n_slots -- each ended by the sampler's
+// ordering launches and the pick that stores every slot's d[j] and sets its row of the next pass
+int launch_serve_model_drafts(rama_ctx* c, const rama_ctx::ServeState& sv) {
     Q8BatchScratch db{};
     q8_batch_scratch_lay(&sv.dcfg, sv.dw.group_size, (size_t)sv.draft_rows, sv.dblob, &db);
     hipLaunchKernelGGL(serve_model_open_kernel, dim3(1), dim3(kServeMaxSlots), 0, c->stream, sv.t, sv.st, sv.mt);
@@ -1494,9 +1544,10 @@ static int enqueue_q8_serve_model_step(rama_ctx* c, const Q8BatchScratch& b) {
         hipLaunchKernelGGL(serve_model_pick_kernel, dim3(sv.n_slots), dim3(1024), 0, c->stream, pk);
         LAUNCHCHK();
     }
-    rc = enqueue_q8_batch_pass(c, &sv.cfg, &sv.w, b, sv.t.row_tok, sv.t.rows, sv.max_rows); if (rc) return rc;
-    rc = launch_serve_spec_pick(c, sv.t, sv.st, b.LG, sv.cfg.vocab_size, sv.sampler); if (rc) return rc;
-    rc = launch_serve_spec_accept(c, sv.t, sv.st); if (rc) return rc;
+    return 0;
+}
+// ... and what ends the step, behind the accept rule: the draft cursors
+int launch_serve_model_close(rama_ctx* c, const rama_ctx::ServeState& sv) {
     hipLaunchKernelGGL(serve_model_close_kernel, dim3(1), dim3(kServeMaxSlots), 0, c->stream, sv.t, sv.st, sv.mt);
     LAUNCHCHK();
     return 0;

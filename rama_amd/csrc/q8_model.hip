@@ -233,6 +233,51 @@ extern "C" int rama_q8_model_synth(rama_ctx* ctx, const rama_config* cfg, int gr
     return 0;
 }
 
+// A resident fp32 weight set quantized where it lies: rama_weights keeps every layered tensor stacked over the layers, and group_size divides a
+// layer's matrix (dim and hidden_dim are multiples of it), so no group spans two layers and one launch over the stacked tensor quantizes every layer's
+// matrix on its own, as export.py does.  The quantizer is q8_quantize_weights_kernel as it stands: its group index is a size_t and it walks
+// a grid of 2048 x 256 threads in strides, so a tensor of 2^31 groups takes 4096 rounds of it.
+extern "C" int rama_q8_model_from_f32(rama_ctx* ctx, const rama_config* cfg, const rama_weights* w, int group_size, rama_q8_model** out) {
+    if (!ctx || !cfg || !w || !out) return bad(RAMA_EINVAL, "rama_q8_model_from_f32: NULL argument");
+    const rama_config& c = *cfg;
+    if (c.dim <= 0 || c.hidden_dim <= 0 || c.n_layers <= 0 || c.n_heads <= 0 || c.vocab_size <= 0 || c.seq_len <= 0 || c.dim % c.n_heads)
+        return bad(RAMA_EINVAL, "rama_q8_model_from_f32: implausible config");
+    if (!w->token_embedding_table || !w->rms_att_weight || !w->rms_ffn_weight || !w->wq || !w->wk || !w->wv || !w->wo || !w->w1 || !w->w2 || !w->w3 ||
+        !w->rms_final_weight || !w->wcls)
+        return bad(RAMA_EINVAL, "rama_q8_model_from_f32: incomplete weights (a pipeline stage's, or tensors still missing)");
+    if (c.n_kv_heads != c.n_heads) return bad(RAMA_EUNSUP, "n_kv_heads != n_heads (the reference indexes the cache with stride dim)");
+    if (group_size <= 0) return bad(RAMA_EINVAL, "rama_q8_model_from_f32: group_size <= 0");
+    if (c.dim % group_size || c.hidden_dim % group_size) return bad(RAMA_EINVAL, "rama_q8_model_from_f32: group_size does not divide dim and hidden_dim");
+    rama_config qc = c;
+    const bool one_tensor = w->wcls == w->token_embedding_table;
+    if (c.shared_weight && !one_tensor) return bad(RAMA_EINVAL, "rama_q8_model_from_f32: shared_weight is set but wcls is a tensor of its own");
+    qc.shared_weight = one_tensor;      // (one tensor behind both names is shared whatever the config says)
+    rama_q8_model* m = nullptr;
+    std::vector<std::pair<int8_t*, float*>> qt;
+    int rc = q8_alloc(ctx, qc, group_size, &m, &qt);
+    if (rc) return rc;
+    const size_t L = qc.n_layers, d = qc.dim;
+    rc = rama_sync(ctx);       // the source's tensors may still be being written by the context's stream or a copy
+    if (!rc && hipSetDevice(rama_internal_device(ctx)) != hipSuccess) rc = bad(RAMA_EIO, "hipSetDevice failed");
+    hipStream_t st = (hipStream_t)rama_internal_stream(ctx);
+    const struct { const float* dst; const float* src; size_t n; } norms[] = {
+        {m->w.rms_att_weight, w->rms_att_weight, L * d}, {m->w.rms_ffn_weight, w->rms_ffn_weight, L * d}, {m->w.rms_final_weight, w->rms_final_weight, d}};
+    for (auto& n : norms)
+        if (!rc && hipMemcpyAsync((float*)n.dst, n.src, n.n * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) rc = bad(RAMA_EIO, "copying the norms failed");
+    const float* src[] = {w->token_embedding_table, w->wq, w->wk, w->wv, w->wo, w->w1, w->w2, w->w3, w->wcls};      // q8_layout's order
+    auto lay = q8_layout(qc);
+    for (size_t i = 0; i < lay.size() && !rc; i++) {
+        hipLaunchKernelGGL(q8_quantize_weights_kernel, dim3(2048), dim3(256), 0, st, src[i], lay[i].n / (size_t)group_size, group_size, qt[i].first,
+                           qt[i].second);
+        if (hipGetLastError() != hipSuccess) rc = bad(RAMA_EIO, "quantize launch failed");
+    }
+    if (!rc) rc = rama_sync(ctx);
+    if (!rc) rc = q8_finish(ctx, m);
+    if (rc) { rama_q8_model_free(ctx, m); return rc; }
+    *out = m;
+    return 0;
+}
+
 extern "C" int rama_q8_model_config(const rama_q8_model* m, rama_config* cfg) {
     if (!m || !cfg) return RAMA_EINVAL;
     *cfg = m->cfg;

@@ -46,6 +46,17 @@ class Q8Model:
         check(device.lib.rama_q8_model_synth(device.ctx, C.byref(c), group_size, seed, C.byref(h)), "rama_q8_model_synth")
         return Q8Model(device, h)
 
+    @staticmethod
+    def from_model(model, group_size: int = 64) -> "Q8Model":
+        """a resident fp32 Model (loaded, synthetic, any whole weight set) quantized in HBM by export.py's quantize_q80 rule
+        (rama_q8_model_from_f32): the Q8Model that load() gives from the version-2 file export.py writes for those weights.  The
+        group size is halved until it fits, as version2_export does (from_f32_group_size); the source model is only read."""
+        gs = from_f32_group_size(model.cfg, group_size)
+        h = C.c_void_p()
+        check(model.device.lib.rama_q8_model_from_f32(model.device.ctx, C.byref(model.ccfg), C.byref(model.weights), gs, C.byref(h)),
+              "rama_q8_model_from_f32")
+        return Q8Model(model.device, h)
+
     @property
     def bytes(self) -> int:
         """bytes a decode step streams: int8 values, scales and fp32 norms"""
@@ -78,6 +89,18 @@ class Q8Model:
         if self.handle:
             check(self.device.lib.rama_q8_model_free(self.device.ctx, self.handle))
             self.handle = None
+
+
+def from_f32_group_size(cfg, group_size: int = 64) -> int:
+    """the group size Q8Model.from_model quantizes with: version2_export's back-off -- halve the wanted size while it does not
+    divide dim -- carried on while it does not divide hidden_dim either, which the Q8 products need as well (every row of W2 is
+    whole groups).  ValueError for a size below 1.  No library call."""
+    gs = int(group_size)
+    if gs < 1:
+        raise ValueError(f"from_model: group_size {gs} < 1")
+    while gs > 1 and (cfg.dim % gs or cfg.hidden_dim % gs):
+        gs //= 2
+    return gs
 
 
 class Q8Engine:

@@ -214,7 +214,7 @@ class ServeLoop:
         """the sizes (every one checked before any library call, in this order), the chain's begin, the loop's books"""
         self.n_slots, self.max_rows, self.max_new_cap = serve_sizes(model.cfg, n_slots, max_rows, max_new_cap, self.NAME)
         self.n_draft, self.ngram, self.hint_cap = serve_spec_sizes(n_draft, ngram, hint_cap, self.NAME)
-        self.draft = draft                                # a draft model (Q8Server only): <ABI>_begin_model / _admit_model
+        self.draft = draft                                # a Q8 draft model: <ABI>_begin_model / _admit_model
         if draft is not None:
             serve_model_sizes(model.cfg, draft, self.n_slots, self.n_draft, self.hint_cap, self.NAME)
         self._down = [None] * self.n_slots                # the server's draft engine of a slot, made on first use and reused
@@ -328,7 +328,7 @@ class ServeLoop:
             arr, rec = _i32(toks), rama_q8_serve_plan(T, P, U, new, stop)
             if self.draft is not None:
                 # the draft model's rows of the whole context: a prefill enqueued before the admission, stream-ordered between two steps (the
-                # chain's begin sized every buffer it runs on, so the captured step holds none that it could regrow)
+                # chain's begin sized every buffer it runs on, and the captured step holds none that it could regrow)
                 if self._down[slot] is None:
                     self._down[slot] = self._new_engine(self.draft)
                     self._mine.append(self._down[slot])

@@ -5,6 +5,7 @@ engines."""
 from __future__ import annotations
 
 from .engine import Engine, Model
+from .q8 import Q8Engine, Q8Model
 from .serve import ServeLoop
 
 
@@ -17,14 +18,21 @@ class Server(ServeLoop):
     admits over rows the caller's engine already holds (rama_serve_admit_at), prefix_cache=k keeps k donor engines whose shared
     prefixes are forked into a new request's engine (rama_q8_kv_fork: the KV cache is fp32 in both stacks), and n_draft=K > 0 begins
     the chain with rama_serve_begin_spec: a decoding request's n-gram guesses take the rows of a tile that no slot wants and are
-    verified in the same weight pass.  The tokens are the same whatever these are."""
+    verified in the same weight pass.  The tokens are the same whatever these are.
+
+    Model drafts.  draft=Q8Model (a small Q8 model over the same vocabulary on the same device --
+    Q8Model.from_model makes one from an fp32 Model) with n_draft=K in 1..15 begins the chain with rama_serve_begin_model: the
+    guesses are that model's own next tokens under the request's sampler instead of the lookup -- no hint_cap, ngram ignored, at
+    most 64 slots.  The server owns one draft engine per slot and prefills it with the request's context before the admission."""
 
     ABI = "rama_serve"
     NAME = "Server"
 
     def __init__(self, model: Model, n_slots: int, max_rows=None, max_new_cap: int = 256, n_draft: int = 0, ngram: int = 3,
-                 hint_cap: int = 0, prefix_cache: int = 0):
-        super().__init__(model, n_slots, max_rows, max_new_cap, prefix_cache, n_draft, ngram, hint_cap)
+                 hint_cap: int = 0, prefix_cache: int = 0, draft: Q8Model = None):
+        if draft is not None and draft.device is not model.device:
+            raise ValueError("Server: the draft model is on another device context")
+        super().__init__(model, n_slots, max_rows, max_new_cap, prefix_cache, n_draft, ngram, hint_cap, draft)
 
-    def _new_engine(self):
-        return Engine(self.device, self.model)
+    def _new_engine(self, model=None):
+        return Q8Engine(self.device, model) if model is not None else Engine(self.device, self.model)
