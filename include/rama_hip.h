@@ -566,7 +566,8 @@ int  rama_q8_decode_batch_stream_poll(rama_ctx *ctx, int seq, int from, int32_t 
  * rama_q8_serve_steps: no overall limit.  RAMA_EINVAL once the model (rama_q8_model_free) or the run state of an occupied slot
  * (rama_state_free before the host could see the slot DONE) is gone.
  * rama_q8_serve_poll never touches the stream: tokens from.. of the slot's occupant, *finished, and *generation (each may be
- * NULL).  rama_q8_serve_tokens synchronises.  rama_q8_serve_stats synchronises: the counters the scheduler launch keeps on the
+ * NULL).  *finished is the slot's finished WORD, not a boolean: 0 while the occupant runs, 1 once it has finished by itself, and
+ * RAMA_SERVE_CANCELLED (2) once a rama_q8_serve_cancel has ended it (below) -- test it against 0, not against 1.  rama_q8_serve_tokens synchronises.  rama_q8_serve_stats synchronises: the counters the scheduler launch keeps on the
  * device, the captures so far, the slot table, and the last step's row table.
  * rama_q8_serve_plan_step is HOST-ONLY (no context, no GPU): the rule above as a pure function, rows_out[max_rows] and --
  * slots_after may be NULL -- the successor states when no stop token is sampled.  The device scheduler produces exactly
@@ -664,6 +665,7 @@ int  rama_q8_kv_fork(rama_ctx *ctx, const rama_config *cfg, const rama_run_state
  * rama_serve_steps: no overall limit.  RAMA_EINVAL once the model (rama_model_free) or the run state of an occupied slot
  *   (rama_state_free before the host could see the slot DONE) is gone; RAMA_EUNSUP once the context has left parity mode.
  * rama_serve_poll never touches the stream: tokens from.. of the slot's occupant, *finished, *generation (each may be NULL).
+ *   *finished is the finished word as rama_q8_serve_poll gives it: 0, 1, or RAMA_SERVE_CANCELLED (2) after a rama_serve_cancel.
  * rama_serve_tokens synchronises and copies the slot's tokens.
  * rama_serve_stats synchronises: the device's counters, the captures so far, the slot table, the last step's row table.
  * rama_serve_end synchronises and frees the chain; nothing to end is success. */
@@ -979,6 +981,24 @@ int  rama_serve_begin_model(rama_ctx *ctx, const rama_config *cfg, const rama_we
 int  rama_serve_admit_model(rama_ctx *ctx, int slot, const rama_run_state *state, const rama_run_state *dstate,
                             const int32_t *context_host, int n_context, int n_cached, const rama_q8_serve_plan *plan, int n_draft);
 int  rama_serve_model_stats(rama_ctx *ctx, rama_q8_serve_model_report *out);
+
+/* CANCEL in both serving chains: end requests from outside.  One entry per stack, one body; chains begun with
+ * _begin, _begin_spec and _begin_model alike.  A slot of the list that is PROMPT or DECODE when the launch runs becomes DONE
+ * with the finished word RAMA_SERVE_CANCELLED; to every kernel of a step it is a slot that ran out of budget at that point.  Its
+ * cursor, n_out, tokens, ring row and cache rows stay as they are, so the tokens polled until the word shows are the request's,
+ * and the sequence can be continued later on the same run state with the bits of an uninterrupted run: _admit_at with the old
+ * context plus the tokens produced, n_cached = the slot's cursor (rama_*_serve_stats; at most n_context - 1) and the budget that
+ * is left.  A slot whose occupant finishes by itself before the launch runs keeps the word 1 and all its tokens.
+ * Like an admission: stream-ordered on the context's stream, never synchronises, leaves the captured step alone, legal between
+ * any two _steps calls.  The set travels as launch arguments: no copy is staged.  Everything is checked first and a refusal
+ * leaves the chain as it was: RAMA_EINVAL for no chain, a NULL list with n > 0, n < 0 or n > 128, a slot index outside the
+ * table.  Duplicates are fine.  A slot the host can already see is not live -- never admitted, or its finished word set -- is
+ * skipped without error; if nothing is left, nothing is launched.  The host's books do not change at the cancel: the slot is
+ * admissible once the host sees the word (_poll reports it as it is: 0, 1 or RAMA_SERVE_CANCELLED), and rama_state_free on the
+ * occupant's run state before that still ends the chain. */
+#define RAMA_SERVE_CANCELLED 2      /* the finished word of a slot ended by a cancel */
+int  rama_q8_serve_cancel(rama_ctx *ctx, const int32_t *slots, int n);
+int  rama_serve_cancel(rama_ctx *ctx, const int32_t *slots, int n);
 
 /* ---------------------------------------------------------------- measurement
  * HIP events on the context's stream (the stream the kernels are launched on). */

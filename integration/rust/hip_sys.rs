@@ -331,6 +331,9 @@ extern "C" {
                                   context_host: *const i32, n_context: c_int, n_cached: c_int, plan: *const rama_q8_serve_plan,
                                   n_draft: c_int) -> c_int;
     pub fn rama_serve_model_stats(ctx: *mut rama_ctx, out: *mut rama_q8_serve_model_report) -> c_int;
+    // cancel in both serving chains: the slots of the list that are still live end with the finished word RAMA_SERVE_CANCELLED (2)
+    pub fn rama_q8_serve_cancel(ctx: *mut rama_ctx, slots: *const i32, n: c_int) -> c_int;
+    pub fn rama_serve_cancel(ctx: *mut rama_ctx, slots: *const i32, n: c_int) -> c_int;
 }
 
 #[repr(C)] pub struct rama_pipe { _p: [u8; 0] }

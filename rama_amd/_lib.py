@@ -281,6 +281,8 @@ SIGNATURES = {
     "rama_serve_begin_model": (_int, [_vp, _cfgp, C.POINTER(rama_weights), _cfgp, C.POINTER(rama_q8_weights), _int, _int, _int, _int]),
     "rama_serve_admit_model": (_int, [_vp, _int, _sp, _sp, i32p, _int, _int, C.POINTER(rama_q8_serve_plan), _int]),
     "rama_serve_model_stats": (_int, [_vp, C.POINTER(rama_q8_serve_model_report)]),
+    "rama_q8_serve_cancel": (_int, [_vp, i32p, _int]),
+    "rama_serve_cancel": (_int, [_vp, i32p, _int]),
 }
 
 # exported but not in the header (the rama_internal_* accessors tests read; most declare their own types where they call them): here

@@ -893,6 +893,12 @@ int rama_serve_admit_model(rama_ctx* c, int slot, const rama_run_state* state, c
     return 0;
 }
 
+int rama_serve_cancel(rama_ctx* c, const int32_t* slots, int n) {
+    RAMA_ENTER(c);
+    REQUIRE(c, RAMA_EINVAL, "serve_cancel: ctx is NULL");
+    return serve_cancel(c, "serve_cancel", c->sv, slots, n);
+}
+
 // the pass over the step's row table, tile by tile in ascending order
 static int serve_pass(rama_ctx* c, const ServeScratch& s) {
     auto& sv = c->sv;

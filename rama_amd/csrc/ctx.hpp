@@ -298,6 +298,7 @@ struct rama_ctx {
         unsigned long long steps = 0;
         // a chain begun with rama_q8_serve_begin_spec / rama_serve_begin_spec (q8_serve_spec.hpp): drafts in the rows no slot wants; all of it unused on
         // a chain begun without it
+        unsigned long long cancel_launches = 0;   // serve_cancel_kernel launches since the chain began (rama_internal_serve_cancel_launches)
         bool spec = false;
         int n_draft_cap = 0, hint_cap = 0;
         ServeSpecTables st{};              // the device tables (inside blob)
@@ -440,6 +441,8 @@ int serve_admit_tail(const ServeNames& names, const rama_ctx::ServeState& sv, co
                      int n_cached, const rama_q8_serve_plan* plan);
 int serve_admit_install(rama_ctx* c, rama_ctx::ServeState& sv, int slot, const rama_run_state* state, const int32_t* context_host, int n_context, int n_cached,
                         const rama_q8_serve_plan* plan);
+// a cancel, for either chain of any kind: the refusals in the calling entry's words, then serve_cancel_kernel for the slots of the list still live
+int serve_cancel(rama_ctx* c, const char* entry, rama_ctx::ServeState& sv, const int32_t* slots, int n);
 // the drafting half of an admission, behind the tail: spec != NULL is an _admit_spec entry's record -- refused on a chain begun without drafts --, and
 // the install puts the slot's drafting fields and hint in (spec == NULL: n_draft = 0); nothing to do on a chain begun without drafts
 int serve_admit_spec_check(const ServeNames& names, const rama_ctx::ServeState& sv, int vocab_size, const rama_q8_serve_spec* spec);

@@ -1139,6 +1139,38 @@ int serve_admit_install(rama_ctx* c, rama_ctx::ServeState& sv, int slot, const r
     LAUNCHCHK();
     return 0;
 }
+// rama_q8_serve_cancel and rama_serve_cancel behind RAMA_ENTER: everything is checked first, then one launch of serve_cancel_kernel for the slots
+// still on the device's hands -- stream-ordered, no synchronisation, no staging copy (the set travels as launch arguments), the captured step
+// untouched.  A slot never admitted, or one whose finished word the host can see, is skipped; nothing left: nothing launched.  The host's books
+// (occupied, gen) do not change: as with any finish, the slot is admissible once the host sees the word.  A drafting chain needs no more than this:
+// the draft, open, schedule, accept and close kernels key on the slot's state.
+int serve_cancel(rama_ctx* c, const char* entry, rama_ctx::ServeState& sv, const int32_t* slots, int n) {
+    REFUSE_UNLESS(sv.n_slots > 0, entry, "no serving chain");
+    REFUSE_UNLESS(n >= 0 && n <= kServeMaxSlots, entry, "n outside [0, 128]");
+    REFUSE_UNLESS(n == 0 || slots, entry, "NULL argument");
+    for (int k = 0; k < n; k++) REFUSE_UNLESS(slots[k] >= 0 && slots[k] < sv.n_slots, entry, "no such slot");
+    unsigned long long mask[2] = {0ull, 0ull};
+    for (int k = 0; k < n; k++)
+        if (serve_slot_live(sv, slots[k])) mask[slots[k] >> 6] |= 1ull << (slots[k] & 63);
+    if (!(mask[0] | mask[1])) return 0;
+    if (set_device(c)) return 1;
+    hipLaunchKernelGGL(serve_cancel_kernel, dim3(1), dim3(kServeMaxSlots), 0, c->stream, sv.t, mask[0], mask[1]);
+    LAUNCHCHK();
+    sv.cancel_launches++;
+    return 0;
+}
+// A hook for the tests, exported like the other rama_internal_* accessors and not in the header: the serve_cancel_kernel launches since the chain began, of the
+// context's Q8 chain (fp32 == 0) or fp32 chain -- tests/test_hip_serve_cancel.py sees that a cancel with nothing left to cancel launches nothing
+extern "C" long long rama_internal_serve_cancel_launches(rama_ctx* c, int fp32) {
+    if (!c) return -1;
+    return (long long)(fp32 ? static_cast<const rama_ctx::ServeState&>(c->sv) : static_cast<const rama_ctx::ServeState&>(c->q8s)).cancel_launches;
+}
+int rama_q8_serve_cancel(rama_ctx* c, const int32_t* slots, int n) {
+    RAMA_ENTER(c);
+    REQUIRE(c, RAMA_EINVAL, "q8_serve_cancel: ctx is NULL");
+    return serve_cancel(c, "q8_serve_cancel", c->q8s, slots, n);
+}
+
 int serve_admit_spec_check(const ServeNames& names, const rama_ctx::ServeState& sv, int vocab_size, const rama_q8_serve_spec* spec) {
     if (!spec) return 0;
     char what[3][112];
@@ -1575,7 +1607,7 @@ int serve_poll_ring(const char* entry, const rama_ctx::ServeState& sv, int slot,
     // the finished word first: it is stored after the occupant's last ring word, so a set word means every token is there to be read
     const int fin = __atomic_load_n(sv.done + slot, __ATOMIC_ACQUIRE);
     *n_ready = read_ring(sv.ring + (size_t)slot * sv.out_cap, sv.out_cap, from, out_host, max_tokens);
-    if (finished) *finished = fin != 0;
+    if (finished) *finished = fin;                                 // 0, 1, or RAMA_SERVE_CANCELLED
     if (generation) *generation = sv.gen[slot];
     return 0;
 }

@@ -7,7 +7,8 @@
 //   serve_gather_kernel     the <= n_slots rows that carry logits -> a compact buffer; final norm, quantizer, classifier on those
 //   the batched sampler's ordering launches (topp_sort.hpp; a slot without logits or at temperature 0 leaves them at once)
 //   serve_pick_kernel       one workgroup per slot: argmax / top-p pick, then the slot's state machine
-// and between any two steps serve_install_kernel puts a new sequence into a slot (stream-ordered, the captured step untouched).
+// and between any two steps serve_install_kernel puts a new sequence into a slot and serve_cancel_kernel ends the occupants of a set of
+// slots (both stream-ordered, the captured step untouched).
 //
 // The scheduling rule (rama_q8_serve_plan_step is the same rule on the host; the two tables must be identical):
 //   every DECODE slot one row (its token at its position); every PROMPT slot one row (its next context position); the rows left
@@ -114,6 +115,23 @@ __global__ void serve_install_kernel(ServeTables t, int slot, const ServeSlot* r
     const int n = rec->n_ctx;
     for (int k = threadIdx.x; k < n; k += blockDim.x) t.ctx[(size_t)slot * t.seq_len + k] = toks[k];
     if (threadIdx.x == 0) t.slots[slot] = *rec;
+}
+
+// a cancel (rama_q8_serve_cancel / rama_serve_cancel): one workgroup of kServeMaxSlots threads, thread i is slot i; the set is a
+// 128-bit mask in two launch arguments (nothing to stage).  A PROMPT or DECODE slot of the set becomes DONE -- to every kernel of a step what a
+// slot is that ran out of budget here -- and its finished word RAMA_SERVE_CANCELLED; cursor, n_out, tok, out, the ring and the caches stay.
+// A slot in any other state is left alone: an occupant that finished by itself keeps its word 1.
+constexpr int kServeCancelled = 2;
+__global__ __launch_bounds__(kServeMaxSlots) void serve_cancel_kernel(ServeTables t, unsigned long long lo, unsigned long long hi) {
+    const int i = threadIdx.x;
+    if (i >= t.n_slots) return;
+    if (!(((i < 64 ? lo : hi) >> (i & 63)) & 1ull)) return;
+    ServeSlot* d = t.slots + i;
+    const int state = d->state;
+    if (state != kServePrompt && state != kServeDecode) return;
+    d->state = kServeDone;
+    // (the ring words of the steps before are this stream's earlier kernels' stores: who sees the word set finds every token)
+    __hip_atomic_store(t.done + i, kServeCancelled, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // What ends a step, one workgroup per slot.  A PROMPT slot still inside its context moves its cursor on; a slot with logits takes

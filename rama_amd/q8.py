@@ -342,10 +342,10 @@ class Q8Server(ServeLoop):
     NAME = "Q8Server"
 
     def __init__(self, model: Q8Model, n_slots: int, max_rows=None, max_new_cap: int = 256, prefix_cache: int = 0, n_draft: int = 0,
-                 ngram: int = 3, hint_cap: int = 0, draft: Q8Model = None):
+                 ngram: int = 3, hint_cap: int = 0, draft: Q8Model = None, preempt: bool = False):
         if draft is not None and draft.device is not model.device:
             raise ValueError("Q8Server: the draft model is on another device context")
-        super().__init__(model, n_slots, max_rows, max_new_cap, prefix_cache, n_draft, ngram, hint_cap, draft)
+        super().__init__(model, n_slots, max_rows, max_new_cap, prefix_cache, n_draft, ngram, hint_cap, draft, preempt)
 
     def _new_engine(self, model=None):
         return Q8Engine(self.device, model or self.model)

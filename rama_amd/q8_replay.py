@@ -56,6 +56,26 @@ def _spec_plan_py(slots, want, max_rows):
     return rows + [(-1, -1, 0)] * (max_rows - len(rows)), granted
 
 
+def _cancel_py(cancels, t, slots):
+    """the cancel rule: the slots of cancels[t] that are PROMPT or DECODE become DONE before step t, and nothing else changes -> them"""
+    hit = []
+    for i in sorted(set(int(i) for i in (cancels or {}).get(t, ()))):
+        if not 0 <= i < len(slots):
+            raise ValueError(f"serve replay: cancels[{t}] names slot {i} of {len(slots)}")
+        if slots[i][0] in (SERVE_PROMPT, SERVE_DECODE):
+            slots[i][0] = SERVE_DONE
+            hit.append(i)
+    return hit
+
+
+def _next_waiting(waiting, reqs, t):
+    """the first waiting request that may be admitted before step t (a request's `after_step`, default 0: at once); None: none yet"""
+    for q in waiting:
+        if reqs[q]["after"] <= t:
+            return q
+    return None
+
+
 def spec_replay(ref_tokens, context, hint, n_draft, ngram, max_new, stop_token):
     """the speculative chain's steps as a pure function of its inputs, no library call: ref_tokens = the max_new tokens the
     sequence produces alone (Q8Engine.generate(context[1:], ...)[len(context) - 1:], not cut at the stop token) -> one
@@ -109,7 +129,7 @@ def spec_model_replay(ref_tokens, draft_fn, context, n_draft, max_new, stop_toke
     return out, cursor
 
 
-def serve_spec_replay(requests, ref_tokens, n_slots, max_rows, use_slots=None):
+def serve_spec_replay(requests, ref_tokens, n_slots, max_rows, use_slots=None, cancels=None):
     """a whole workload of a serving chain with drafts as a pure function of its inputs, no library call.  requests = dicts with
     context and max_new, and optionally stop_token, n_draft (0), ngram (3), hint and n_cached (0); ref_tokens[i] = the max_new
     tokens request i produces alone (Q8Engine.generate(context[1:], ...)[len(context) - 1:], not cut at the stop token).
@@ -118,7 +138,13 @@ def serve_spec_replay(requests, ref_tokens, n_slots, max_rows, use_slots=None):
     comparison with the reference tokens: row j's pick is ref[n_out + j] as long as the drafts before it were right, which is
     all the accept rule looks at.  -> dict(steps = one dict per step: admitted [(slot, request)], rows, want, granted, accepted
     {slot: a} for the DECODE slots, emitted {slot: n}, finished [slots]; counters = what rama_q8_serve_spec_stats reports;
-    finish_step = per request the step it finishes in; slot = per request its slot; outputs = per request its tokens)."""
+    finish_step = per request the step it finishes in; slot = per request its slot; outputs = per request its tokens).
+    cancels = {step: [slots]}: before step `step` (and before its admissions) the slots named that are PROMPT or DECODE become
+    DONE, and nothing else changes -- the rule of rama_q8_serve_cancel.  A request may carry after_step: it is not admitted
+    before that step (a continuation of a cancelled request: context ++ outputs, n_cached = the cursor, the budget left, the
+    reference tokens from there on).  With cancels given, each step dict has cancelled = the slots a cancel ended before it, the result
+    cancelled_at = per request the step before which it was cancelled (None: it was not); a cancelled request has no
+    finish_step."""
     reqs = []
     for r, ref in zip(requests, ref_tokens):
         ctx, new = [int(t) for t in r["context"]], int(r["max_new"])
@@ -126,25 +152,35 @@ def serve_spec_replay(requests, ref_tokens, n_slots, max_rows, use_slots=None):
             raise ValueError(f"serve_spec_replay: {len(ref)} reference tokens for max_new {new}")
         stop = r.get("stop_token")
         reqs.append(dict(ctx=ctx, new=new, stop=-1 if stop is None else int(stop), K=int(r.get("n_draft", 0)), N=int(r.get("ngram", 3)),
-                         hint=[int(t) for t in (r.get("hint") or [])], cached=int(r.get("n_cached", 0)), ref=[int(t) for t in ref]))
+                         hint=[int(t) for t in (r.get("hint") or [])], cached=int(r.get("n_cached", 0)), ref=[int(t) for t in ref],
+                         after=int(r.get("after_step", 0))))
     usable = list(range(n_slots)) if use_slots is None else sorted(use_slots)
     slots = [[SERVE_FREE, 0, 0, 0, 0] for _ in range(n_slots)]      # state, n_context, cursor, n_out, max_new
     who, text = [None] * n_slots, [None] * n_slots
     waiting = list(range(len(reqs)))
     steps, finish, slot_of, outputs = [], [None] * len(reqs), [None] * len(reqs), [[] for _ in reqs]
+    cancelled_at = [None] * len(reqs)
     cnt = dict(steps=0, rows_decode=0, rows_draft=0, rows_prompt=0, rows_idle=0, drafts_wanted=0, drafts_granted=0, drafts_accepted=0,
                tokens_emitted=0, accepted_hist=[0] * 16)
     while waiting or any(s[0] in (SERVE_PROMPT, SERVE_DECODE) for s in slots):
+        t = len(steps)
+        cancelled = _cancel_py(cancels, t, slots)
+        for i in cancelled:
+            cancelled_at[who[i]] = t
         admitted = []
         for i in usable:
-            if waiting and slots[i][0] in (SERVE_FREE, SERVE_DONE):
-                q = waiting.pop(0)
+            q = _next_waiting(waiting, reqs, t)
+            if q is not None and slots[i][0] in (SERVE_FREE, SERVE_DONE):
+                waiting.remove(q)
                 r = reqs[q]
                 slots[i] = [SERVE_PROMPT, len(r["ctx"]), r["cached"], 0, r["new"]]
                 who[i], text[i], slot_of[q] = q, list(r["ctx"]), i
                 admitted.append((i, q))
         if not any(s[0] in (SERVE_PROMPT, SERVE_DECODE) for s in slots):
-            raise ValueError("serve_spec_replay: requests are waiting but no slot can take them")
+            if not waiting:
+                break                                              # (a cancel ended the last live slot)
+            if all(reqs[q]["after"] <= t for q in waiting):
+                raise ValueError("serve_spec_replay: requests are waiting but no slot can take them")
         want, drafts = [0] * n_slots, [[] for _ in range(n_slots)]
         for i, s in enumerate(slots):
             if s[0] == SERVE_DECODE and reqs[who[i]]["K"] > 0:
@@ -193,10 +229,29 @@ def serve_spec_replay(requests, ref_tokens, n_slots, max_rows, use_slots=None):
                 finish[who[i]] = len(steps)
         steps.append(dict(admitted=admitted, rows=rows, want=want, granted=granted, accepted=accepted, emitted=emitted, finished=finished,
                           slots=[tuple(s) for s in slots]))
-    return dict(steps=steps, counters=cnt, finish_step=finish, slot=slot_of, outputs=outputs)
+        if cancels is not None:
+            steps[-1]["cancelled"] = cancelled
+    out = dict(steps=steps, counters=cnt, finish_step=finish, slot=slot_of, outputs=outputs)
+    if cancels is not None:
+        out["cancelled_at"] = cancelled_at
+    return out
 
 
-def serve_model_replay(requests, ref_tokens, draft_fn, n_slots, max_rows, use_slots=None):
+def serve_replay(requests, ref_tokens, n_slots, max_rows, use_slots=None, cancels=None):
+    """a whole workload of a serving chain WITHOUT drafts (rama_q8_serve_begin, rama_serve_begin) as a pure function of its inputs:
+    serve_spec_replay with no slot drafting -- the scheduling rule with drafts is the plain rule when nobody wants one --, so one
+    cancel schedule replays on all three kinds of chain.  -> serve_spec_replay's dict without the drafting entries: counters =
+    what rama_q8_serve_stats reports (steps, rows_decode, rows_prompt, rows_idle)."""
+    plain = [{k: v for k, v in r.items() if k not in ("n_draft", "ngram", "hint")} for r in requests]
+    out = serve_spec_replay(plain, ref_tokens, n_slots, max_rows, use_slots, cancels or {})
+    out["counters"] = {k: out["counters"][k] for k in ("steps", "rows_decode", "rows_prompt", "rows_idle")}
+    for st in out["steps"]:
+        for k in ("want", "granted", "accepted"):
+            del st[k]
+    return out
+
+
+def serve_model_replay(requests, ref_tokens, draft_fn, n_slots, max_rows, use_slots=None, cancels=None):
     """a whole workload of a serving chain with a draft model (rama_q8_serve_begin_model) as a pure function of its inputs, no library
     call.  requests and ref_tokens as serve_spec_replay's (n_draft: the drafts per step of the request, 0: none; ngram and hint do not
     exist here); draft_fn(prefix, n) = the n tokens the draft model produces alone after the token list prefix under the request's
@@ -205,7 +260,8 @@ def serve_model_replay(requests, ref_tokens, draft_fn, n_slots, max_rows, use_sl
     whatever it is granted; the scheduling rule; the granted drafts d = draft_fn(s, g); the accept rule against the reference tokens;
     Dc' = min(L + min(a, max(g - 1, 0)), new L).  -> serve_spec_replay's dict, and besides: per step `drafting` = {slot: (g, a,
     emitted, catch_up)} for the slots that fed the draft model and `cursors` = every slot's draft cursor after the step; counters
-    also has draft_passes, draft_rows_fed and catch_up_rows (rama_q8_serve_model_stats); cursor = per request its final draft cursor."""
+    also has draft_passes, draft_rows_fed and catch_up_rows (rama_q8_serve_model_stats); cursor = per request its final draft cursor.
+    cancels and a request's after_step: as serve_spec_replay's; a cancelled slot's draft cursor stays where it is."""
     fns = list(draft_fn) if isinstance(draft_fn, (list, tuple)) else [draft_fn] * len(requests)
     reqs = []
     for r, ref in zip(requests, ref_tokens):
@@ -214,25 +270,34 @@ def serve_model_replay(requests, ref_tokens, draft_fn, n_slots, max_rows, use_sl
             raise ValueError(f"serve_model_replay: {len(ref)} reference tokens for max_new {new}")
         stop = r.get("stop_token")
         reqs.append(dict(ctx=ctx, new=new, stop=-1 if stop is None else int(stop), K=int(r.get("n_draft", 0)), cached=int(r.get("n_cached", 0)),
-                         ref=[int(t) for t in ref]))
+                         ref=[int(t) for t in ref], after=int(r.get("after_step", 0))))
     usable = list(range(n_slots)) if use_slots is None else sorted(use_slots)
     slots = [[SERVE_FREE, 0, 0, 0, 0] for _ in range(n_slots)]      # state, n_context, cursor, n_out, max_new
     who, text, Dc = [None] * n_slots, [None] * n_slots, [0] * n_slots
     waiting = list(range(len(reqs)))
     steps, finish, slot_of, outputs, final = [], [None] * len(reqs), [None] * len(reqs), [[] for _ in reqs], [None] * len(reqs)
+    cancelled_at = [None] * len(reqs)
     cnt = dict(steps=0, rows_decode=0, rows_draft=0, rows_prompt=0, rows_idle=0, drafts_wanted=0, drafts_granted=0, drafts_accepted=0,
                tokens_emitted=0, accepted_hist=[0] * 16, draft_passes=0, draft_rows_fed=0, catch_up_rows=0)
     while waiting or any(s[0] in (SERVE_PROMPT, SERVE_DECODE) for s in slots):
+        t = len(steps)
+        cancelled = _cancel_py(cancels, t, slots)
+        for i in cancelled:
+            cancelled_at[who[i]] = t
         admitted = []
         for i in usable:
-            if waiting and slots[i][0] in (SERVE_FREE, SERVE_DONE):
-                q = waiting.pop(0)
+            q = _next_waiting(waiting, reqs, t)
+            if q is not None and slots[i][0] in (SERVE_FREE, SERVE_DONE):
+                waiting.remove(q)
                 r = reqs[q]
                 slots[i] = [SERVE_PROMPT, len(r["ctx"]), r["cached"], 0, r["new"]]
                 who[i], text[i], slot_of[q], Dc[i] = q, list(r["ctx"]), i, len(r["ctx"])
                 admitted.append((i, q))
         if not any(s[0] in (SERVE_PROMPT, SERVE_DECODE) for s in slots):
-            raise ValueError("serve_model_replay: requests are waiting but no slot can take them")
+            if not waiting:
+                break                                              # (a cancel ended the last live slot)
+            if all(reqs[q]["after"] <= t for q in waiting):
+                raise ValueError("serve_model_replay: requests are waiting but no slot can take them")
         want, gap = [0] * n_slots, {}
         for i, s in enumerate(slots):
             if s[0] == SERVE_DECODE and reqs[who[i]]["K"] > 0:
@@ -292,4 +357,9 @@ def serve_model_replay(requests, ref_tokens, draft_fn, n_slots, max_rows, use_sl
                 finish[who[i]] = len(steps)
         steps.append(dict(admitted=admitted, rows=rows, want=want, granted=granted, accepted=accepted, emitted=emitted, finished=finished,
                           slots=[tuple(s) for s in slots], drafting=drafting, cursors=list(Dc)))
-    return dict(steps=steps, counters=cnt, finish_step=finish, slot=slot_of, outputs=outputs, cursor=final)
+        if cancels is not None:
+            steps[-1]["cancelled"] = cancelled
+    out = dict(steps=steps, counters=cnt, finish_step=finish, slot=slot_of, outputs=outputs, cursor=final)
+    if cancels is not None:
+        out["cancelled_at"] = cancelled_at
+    return out

@@ -13,6 +13,8 @@ from ._lib import (check, load, rama_q8_serve_model_report, rama_q8_serve_plan, 
 from .q8_replay import SERVE_DECODE, SERVE_DONE, SERVE_FREE, SERVE_PROMPT
 from .sampler_const import TOPP_U_CPU
 
+SERVE_CANCELLED = 2      # RAMA_SERVE_CANCELLED: the finished word of a slot ended by a cancel
+
 
 def serve_sizes(cfg, n_slots, max_rows, max_new_cap, who="Q8Server"):
     """the checked sizes of a serving chain; ValueError for what rama_q8_serve_begin would refuse as a bad size.  No library call."""
@@ -201,17 +203,22 @@ class ServeLoop:
     host plan (rama_q8_serve_plan_step), the steps to the next finish, admissions behind the steps in flight, the host-visible rings --
     and what both chains offer on request: prompt caching (submit(n_cached=), the donor pool of prefix_cache=k, the fork --
     rama_q8_kv_fork: the KV cache is fp32 in both stacks -- and <ABI>_admit_at) and drafts (<ABI>_begin_spec / _admit_spec / _spec_stats
-    and the run loop of a chain whose steps the host cannot foresee).  Q8Server (rama_q8_serve_*) and rama_amd.Server (rama_serve_*,
-    parity mode) are this loop over their entries' family: a subclass states ABI, NAME and the engine a slot gets (_new_engine)."""
+    and the run loop of a chain whose steps the host cannot foresee), and ending a request from outside: cancel /
+    cancelled, submit(priority=), preempt=True -- a waiting request that outranks a running one takes its slot, and the request that
+    left continues later on its engine over its own rows with the tokens of an uninterrupted run -- and suspend / resume.  Q8Server
+    (rama_q8_serve_*) and rama_amd.Server (rama_serve_*, parity mode) are this loop over their entries' family: a subclass states ABI,
+    NAME and the engine a slot gets (_new_engine)."""
 
     ABI = None         # the C entries' family: <ABI>_begin / _admit / _steps / _poll / _stats / _end
     NAME = "ServeLoop"
     LOOKAHEAD = 2      # steps enqueued past a foreseen finish while requests wait: the admission then goes in behind running steps
     SPEC_BLOCK = 4     # with drafts: at most this many steps between two looks at the device's slot table
+    PREEMPT_BLOCK = 4  # with preempt: at most this many steps enqueued at once, so that a cancel lands no further behind an urgent arrival
     MIN_CACHED = 2     # a shorter match is not worth a launch: every context shares its first token (BOS) with every donor
 
-    def __init__(self, model, n_slots, max_rows, max_new_cap, prefix_cache, n_draft, ngram, hint_cap, draft=None):
+    def __init__(self, model, n_slots, max_rows, max_new_cap, prefix_cache, n_draft, ngram, hint_cap, draft=None, preempt=False):
         """the sizes (every one checked before any library call, in this order), the chain's begin, the loop's books"""
+        self.preempt = bool(preempt)                      # a waiting request that outranks a running one takes its slot (DESIGN.md 8.12)
         self.n_slots, self.max_rows, self.max_new_cap = serve_sizes(model.cfg, n_slots, max_rows, max_new_cap, self.NAME)
         self.n_draft, self.ngram, self.hint_cap = serve_spec_sizes(n_draft, ngram, hint_cap, self.NAME)
         self.draft = draft                                # a Q8 draft model: <ABI>_begin_model / _admit_model
@@ -237,6 +244,15 @@ class ServeLoop:
         self._cached = {}                                 # handle -> the n_cached it was admitted with
         self._drafts = {}                                 # handle -> (n_draft, ngram, hint tokens)
         self.rows_cached = 0                              # ... summed over the admissions
+        self._prio = {}                                   # handle -> priority (the queue: highest first, FIFO within one)
+        self._serial = [0] * self.n_slots                 # admissions a slot has seen: tells an occupant from its successor
+        self._admitted = {}                               # handle -> the count of admissions at its (last) own: the victim among equals is the latest
+        self._n_admitted = 0
+        self._off = [0] * self.n_slots                    # tokens the occupant had produced before this admission (a continuation's on_token indices run on)
+        self._ending = {}                                 # handle of a running request with a cancel enqueued -> "cancel" / "preempt" / "suspend" / "resume"
+        self._cancelled = set()                           # handles ended by cancel()
+        self._suspended = set()                           # handles whose continuation waits for resume()
+        self.preemptions = 0
         self.planned = dict(steps=0, rows_decode=0, rows_prompt=0, rows_idle=0)      # the host plan's sums over the steps enqueued (none with drafts: no host plan)
         self.last_rows = []                               # ... and its row table of the last one
 
@@ -262,7 +278,7 @@ class ServeLoop:
 
     # -- requests
     def submit(self, context, max_new, temperature=0.0, topp=0.9, u=TOPP_U_CPU, stop_token=None, engine=None, n_cached=0,
-               retain=False, n_draft=None, hint=None):
+               retain=False, n_draft=None, hint=None, priority=0):
         """queue a request -> its handle.  It is admitted at once if a slot is free, else when one finishes (step / run).
         engine: the engine whose run state the sequence uses (default: one the server owns for the slot).
         n_cached: rows 0..n_cached-1 of `engine` already hold context[0..n_cached) -- written by work enqueued earlier on the
@@ -272,12 +288,15 @@ class ServeLoop:
         is the pool's until it is evicted).
         n_draft, hint: on a server made with n_draft > 0, the drafts per step of this request (default: the server's; 0: none)
         and a token list to look up in besides the request's own text (at most hint_cap tokens).  The tokens are the same
-        whatever they are."""
+        whatever they are.
+        priority: the queue serves the highest first, FIFO within one; on a server made with preempt=True a waiting request that
+        outranks a running one takes its slot (the lowest priority, among equals the most recently admitted, is cancelled and
+        continues later on its engine with the tokens of an uninterrupted run)."""
         ctx, plan = serve_plan(self.cfg, context, max_new, temperature, topp, u, stop_token, self.max_new_cap, n_cached, self.NAME)
         draft = serve_spec_request(self.cfg, self.n_draft, self.ngram, self.hint_cap, n_draft, hint, self.NAME)
         if self.draft is not None and len(ctx) + plan[3] > self.draft.cfg.seq_len:
             raise ValueError(f"{self.NAME}.submit: n_context {len(ctx)} + max_new {plan[3]} beyond the draft model's seq_len {self.draft.cfg.seq_len}")
-        n_cached = int(n_cached)
+        n_cached, priority = int(n_cached), int(priority)
         if n_cached and engine is None:
             raise ValueError(f"{self.NAME}.submit: n_cached needs the engine that holds the rows")
         if engine is not None and engine.model is not self.model:
@@ -291,12 +310,21 @@ class ServeLoop:
         self._plans[h] = (ctx, plan, engine, n_cached, bool(retain))
         self._results[h] = []
         self._drafts[h] = draft
-        self._queue.append(h)
+        self._prio[h] = priority
+        self._enqueue(h)
         self._admit()
         return h
 
+    def _enqueue(self, h, front=False):
+        """into the queue behind every request of its priority or a higher one (front: before its equals -- a continuation was
+        there before them)"""
+        p, k = self._prio[h], 0
+        while k < len(self._queue) and (self._prio[self._queue[k]] > p or (not front and self._prio[self._queue[k]] == p)):
+            k += 1
+        self._queue.insert(k, h)
+
     def _engines_in_use(self):
-        waiting = [self._plans[h][2] for h in self._queue]
+        waiting = [self._plans[h][2] for h in list(self._queue) + sorted(self._suspended)]
         running = [self._eng[i] for i, h in enumerate(self._req) if h is not None]
         return [e for e in waiting + running if e is not None]
 
@@ -305,7 +333,7 @@ class ServeLoop:
         L, ctx = self.device.lib, self.device.ctx
         for slot in range(self.n_slots):
             if not self._queue:
-                return
+                break
             if self._req[slot] is not None:
                 continue
             h = self._queue[0]                             # (it leaves the queue once the library has taken it)
@@ -346,9 +374,116 @@ class ServeLoop:
                 self._call("admit", slot, C.byref(eng.state), arr, len(toks), C.byref(rec))
             self._queue.pop(0)
             self._req[slot], self._seen[slot], self._eng[slot] = h, 0, eng
+            self._off[slot] = len(self._results[h])
+            self._serial[slot] += 1
+            self._n_admitted += 1
+            self._admitted[h] = self._n_admitted
             self._cached[h] = n_cached
             self.rows_cached += n_cached
             self._mirror[slot] = (SERVE_PROMPT, len(toks), n_cached, 0, new)
+        if self.preempt:
+            self._preempt()
+
+    # -- ending a request from outside
+    def _slot_of(self, handle):
+        for slot, h in enumerate(self._req):
+            if h == handle:
+                return slot
+        return None
+
+    def _end_running(self, slot, why):
+        """<ABI>_cancel behind the steps enqueued -- where the host's mirror stands --, and the slot DONE in the mirror"""
+        self._call("cancel", _i32([slot]), 1)
+        self._ending[self._req[slot]] = why
+        self._mirror[slot] = (SERVE_DONE,) + tuple(self._mirror[slot][1:])
+
+    def _preempt(self):
+        """while no slot is free and a waiting request outranks a running one: the running request of the lowest priority, among
+        equals the most recently admitted, is cancelled.  The k-th cancel under way serves the k-th request of the queue.  A
+        preemption may turn out needless: if another slot finishes by itself before the victim's word shows, the urgent request
+        takes that slot, and the victim is still requeued as a continuation (and counted) -- exact, one row fed again."""
+        while all(h is not None for h in self._req):
+            under_way = sum(1 for why in self._ending.values() if why == "preempt")
+            if under_way >= len(self._queue):
+                return
+            running = [h for h in self._req if h not in self._ending]
+            if not running:
+                return
+            victim = min(running, key=lambda h: (self._prio[h], -self._admitted[h]))
+            if self._prio[victim] >= self._prio[self._queue[under_way]]:
+                return
+            self._end_running(self._slot_of(victim), "preempt")
+
+    def _known(self, what, handle):
+        if handle not in self._plans:
+            raise ValueError(f"{self.NAME}.{what}: no request {handle!r}")
+
+    def _leave(self, h):
+        """a request that waits (queued or suspended) ends here: an engine of the server's that stayed with it is spare again"""
+        eng = self._plans[h][2]
+        if eng is not None and any(eng is m for m in self._mine) and not any(eng is o for o in self._own):
+            self._spare.append(eng)
+        self._finished.add(h)
+        self._cancelled.add(h)
+
+    def cancel(self, handle):
+        """end request `handle` now.  Queued (or suspended): it leaves the queue.  Running: <ABI>_cancel, stream-ordered behind the
+        steps enqueued; the tokens drained until its finished word shows are its result, and cancelled(handle) says whether the
+        cancel ended it -- a request that finishes by itself first is not cancelled.  Finished already: nothing.  May be called
+        from an on_token callback inside run()."""
+        self._known("cancel", handle)
+        if handle in self._finished:
+            return
+        if handle in self._queue or handle in self._suspended:
+            if handle in self._queue:
+                self._queue.remove(handle)
+            self._suspended.discard(handle)
+            self._leave(handle)
+        elif handle in self._ending:
+            self._ending[handle] = "cancel"
+        else:
+            self._end_running(self._slot_of(handle), "cancel")
+
+    def cancelled(self, handle) -> bool:
+        """request `handle` was ended by cancel() (False while it runs, and for one that finished by itself)"""
+        self._known("cancelled", handle)
+        return handle in self._cancelled
+
+    def suspend(self, handle):
+        """the first half of a preemption, for callers who schedule themselves: a running request is cancelled and, once its
+        finished word shows, waits -- with its engine -- as a continuation until resume(handle); a queued one leaves the queue
+        and waits the same way.  One that finishes by itself first has simply finished."""
+        self._known("suspend", handle)
+        if handle in self._finished or handle in self._suspended or self._ending.get(handle) in ("cancel", "suspend"):
+            raise ValueError(f"{self.NAME}.suspend: request {handle!r} has finished, is being cancelled or is suspended already")
+        if handle in self._queue:
+            self._queue.remove(handle)
+            self._suspended.add(handle)
+        elif handle in self._ending:
+            self._ending[handle] = "suspend"
+        else:
+            self._end_running(self._slot_of(handle), "suspend")
+
+    def resume(self, handle):
+        """the second half: the continuation of a suspended request goes back into the queue, before its equals"""
+        self._known("resume", handle)
+        if handle in self._suspended:
+            self._suspended.discard(handle)
+            self._enqueue(handle, front=True)
+            self._admit()
+        elif self._ending.get(handle) == "suspend":
+            self._ending[handle] = "resume"                # (its finished word has not shown yet: queued when it does)
+        else:
+            raise ValueError(f"{self.NAME}.resume: request {handle!r} is not suspended")
+
+    def _continuation(self, slot, h, produced):
+        """the request a cancel ended in `slot` as one that can be admitted again on its engine: the context plus the tokens
+        it produced since its admission, n_cached = the slot's cursor (every row below it is the uninterrupted run's; the final
+        position is always fed), the budget that is left; sampler, stop token and drafts as they were"""
+        toks, (T, P, U, new, stop), _, _, retain = self._plans[h]
+        cursor = self.stats()["slots"][slot][2]            # (synchronises: once per preemption)
+        toks = toks + produced
+        self._plans[h] = (toks, (T, P, U, new - len(produced), stop), self._eng[slot], min(cursor, len(toks) - 1), retain)
 
     def cached(self, handle) -> int:
         """the n_cached request `handle` was admitted with (None while it waits)"""
@@ -356,33 +491,63 @@ class ServeLoop:
 
     def _collect(self, on_token=None):
         """what the rings hold: new tokens of every occupied slot; a finished occupant frees its slot and leaves its engine -- with
-        retain and a prefix cache the engine becomes a donor, keyed by the tokens it was fed (the context and every output but the
-        last); whoever leaves the pool for it serves requests again if the server made it"""
+        retain and a prefix cache the engine becomes a donor, keyed by the tokens whose rows it holds (the context and every output
+        but the last); whoever leaves the pool for it serves requests again if the server made it.  A finished word of
+        RAMA_SERVE_CANCELLED: the request ends as cancelled, or -- preempted or suspended -- becomes a continuation that keeps its
+        engine; a request that finished by itself before the cancel ran has simply finished."""
         early = False
         for slot in range(self.n_slots):
             h = self._req[slot]
             if h is None:
                 continue
-            got = self._results[h]
+            got, off, word = self._results[h], self._off[slot], [0]
 
             def sink(index, token):
                 if on_token is not None:
-                    on_token(h, index, token)
+                    on_token(h, off + index, token)
                 got.append(token)
-            n, fin = _drain(self._poll[slot], self._seen[slot], sink)
+
+            def poll(start):
+                toks, word[0] = self._poll[slot](start)
+                return toks, word[0]
+            n, fin = _drain(poll, self._seen[slot], sink)
             self._seen[slot] += n
-            if fin:
-                self._finished.add(h)
-                self._req[slot] = None
-                eng, self._eng[slot] = self._eng[slot], None
-                if self._plans[h][4] and self.pool.k:      # retain
-                    if self._own[slot] is eng:
-                        self._own[slot] = None
-                    for e in self.pool.put(self._plans[h][0] + got[:-1], eng):
-                        if any(e is m for m in self._mine):
-                            self._spare.append(e)
-                early = early or self._mirror[slot][0] != SERVE_DONE
-                self._mirror[slot] = (SERVE_DONE,) + tuple(self._mirror[slot][1:])
+            if not fin:
+                continue
+            why = self._ending.pop(h, None)
+            if word[0] != SERVE_CANCELLED:
+                why = None                                 # (it finished by itself, whatever was enqueued behind)
+            elif why is None:
+                why = "cancel"                             # (a cancel past this loop, through the entry itself)
+            early = early or self._mirror[slot][0] != SERVE_DONE
+            self._mirror[slot] = (SERVE_DONE,) + tuple(self._mirror[slot][1:])
+            eng = self._eng[slot]
+            if why in ("preempt", "suspend", "resume"):
+                self._continuation(slot, h, got[off:])
+                if self._own[slot] is eng:                 # (the engine stays with the handle; the slot gets another from the spares)
+                    self._own[slot] = None
+                self._req[slot], self._eng[slot] = None, None
+                if why == "suspend":
+                    self._suspended.add(h)
+                else:
+                    self.preemptions += why == "preempt"
+                    self._enqueue(h, front=True)
+                continue
+            self._finished.add(h)
+            if why == "cancel":
+                self._cancelled.add(h)
+            self._req[slot], self._eng[slot] = None, None
+            if self._plans[h][4] and self.pool.k:          # retain
+                if self._own[slot] is eng:
+                    self._own[slot] = None
+                held = self._plans[h][0] + got[off:][:-1]
+                if why == "cancel" and len(got) == off:    # cancelled inside its context: the rows below the cursor
+                    held = self._plans[h][0][:self.stats()["slots"][slot][2]]
+                for e in self.pool.put(held, eng):
+                    if any(e is m for m in self._mine):
+                        self._spare.append(e)
+            elif any(eng is m for m in self._mine) and self._own[slot] is not eng:
+                self._spare.append(eng)                    # (a continuation's engine: no slot's own any more)
         return early
 
     def step(self, n: int = 1, on_token=None):
@@ -439,6 +604,8 @@ class ServeLoop:
             self._admit()
             expect = done_in(self._mirror)                # finished by the plan, not yet seen
             k = self._steps_to_next_finish()
+            cut = self.preempt and k > self.PREEMPT_BLOCK  # (the block is run to its end before the next look)
+            k = min(k, self.PREEMPT_BLOCK) if cut else k
             if k == 0 and not expect:
                 if self._queue:
                     raise RuntimeError(f"{self.NAME}.run: requests are waiting but no slot can take them")
@@ -447,17 +614,19 @@ class ServeLoop:
                 after = self._after(k)
                 expect |= done_in(after)
                 live_on = any(s[0] in (SERVE_PROMPT, SERVE_DECODE) for s in after)
-                self._count_and_enqueue(k + (self.LOOKAHEAD if self._queue and live_on else 0))
-            while True:                       # until the slots the plan ends here have set their finished words
+                self._count_and_enqueue(k + (self.LOOKAHEAD if self._queue and live_on and not cut else 0))
+            serial = {i: self._serial[i] for i in expect}
+            still = lambda: [i for i in expect if self._req[i] is not None and self._serial[i] == serial[i]]     # (not its successor, admitted from a callback)
+            while True:                       # until the slots the plan -- or a cancel -- ends here have set their finished words
                 if self._collect(on_token):
                     self._resync()
-                if all(self._req[i] is None for i in expect):
+                if not still() and not cut:
                     break
                 if _stream_busy(self.device, 0.0001):
                     continue
                 self._collect(on_token)
-                if not all(self._req[i] is None for i in expect):
-                    raise RuntimeError(f"{self.NAME}.run: the steps have run but slots {[i for i in expect if self._req[i] is not None]} have not finished")
+                if still():
+                    raise RuntimeError(f"{self.NAME}.run: the steps have run but slots {still()} have not finished")
                 break
 
     def _after(self, k):
@@ -509,7 +678,7 @@ class ServeLoop:
                    rows_idle=int(r.rows_idle), n_slots=int(r.n_slots), max_rows=int(r.max_rows),
                    last_rows=_row_table(r.last_rows, r.max_rows),
                    slots=[(s.state, s.n_context, s.cursor, s.n_out, s.max_new) for s in r.slots[:r.n_slots]],
-                   generation=[int(g) for g in r.generation[:r.n_slots]], rows_cached=self.rows_cached)
+                   generation=[int(g) for g in r.generation[:r.n_slots]], rows_cached=self.rows_cached, preemptions=self.preemptions)
         if self.spec:
             q = rama_q8_serve_spec_report()
             self._call("spec_stats", C.byref(q))

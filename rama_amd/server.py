@@ -29,10 +29,10 @@ class Server(ServeLoop):
     NAME = "Server"
 
     def __init__(self, model: Model, n_slots: int, max_rows=None, max_new_cap: int = 256, n_draft: int = 0, ngram: int = 3,
-                 hint_cap: int = 0, prefix_cache: int = 0, draft: Q8Model = None):
+                 hint_cap: int = 0, prefix_cache: int = 0, draft: Q8Model = None, preempt: bool = False):
         if draft is not None and draft.device is not model.device:
             raise ValueError("Server: the draft model is on another device context")
-        super().__init__(model, n_slots, max_rows, max_new_cap, prefix_cache, n_draft, ngram, hint_cap, draft)
+        super().__init__(model, n_slots, max_rows, max_new_cap, prefix_cache, n_draft, ngram, hint_cap, draft, preempt)
 
     def _new_engine(self, model=None):
         return Q8Engine(self.device, model) if model is not None else Engine(self.device, self.model)
