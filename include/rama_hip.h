@@ -281,8 +281,9 @@ int  rama_pipe_item(const rama_pipe_plan *plan, int world, int rank, int tick, i
 int  rama_pipe_total_ticks(const rama_pipe *pipe, const rama_pipe_plan *plan);   /* S * n_pos + world - 1 */
 int  rama_pipe_plan_ticks(const rama_pipe_plan *plan, int world);                 /* the same without a communicator */
 /* [r6] EVERYTHING one tick of one rank consists of, as pure arithmetic (no GPU, no communicator): rama_pipe_run_ticks is a loop over this function
- * and executes exactly what it says -- so a CPU test that lets gloo ranks compute and exchange by it (tests/test_pipeline_gloo.py) validates the
- * native loop's own bookkeeping.  kinds: RAMA_PIPE_NONE | RAMA_PIPE_X (float[dim]) | RAMA_PIPE_TOKEN (one int32).
+ * and executes exactly what it says -- so a CPU test that lets gloo ranks compute and exchange by it (tests/test_pipeline_gloo.py
+ * test_native_tick_plan_drives_gloo_ranks) validates the native loop's own bookkeeping; tests/test_pipe_tick_plan_host.py checks the legs, the
+ * dataflow and every field for every rank and tick, also with fewer sequences than stages and with wrap.  kinds: RAMA_PIPE_NONE | RAMA_PIPE_X (float[dim]) | RAMA_PIPE_TOKEN (one int32).
  * token_kind: 0 = BOS (mod.rs:182), 1 = forced prompt token `token` (mod.rs:190-191), 2 = the sequence's device token word (rank 0: what the last
  * rank sampled; other ranks take no token).  recv_pos: the position the received token was sampled AFTER (rank 0's history row). */
 enum { RAMA_PIPE_NONE = 0, RAMA_PIPE_X = 1, RAMA_PIPE_TOKEN = 2 };

@@ -197,7 +197,9 @@ extern "C" int rama_pipe_plan_ticks(const rama_pipe_plan* plan, int world) {
 }
 
 // one tick of one rank, decided: what it computes, with which token, whether it samples, what it sends and what it receives.  The ONLY place the
-// native loop's decisions are made -- rama_pipe_run_ticks below executes this, tests/test_pipeline_gloo.py lets gloo ranks execute it on the CPU.
+// native loop's decisions are made -- rama_pipe_run_ticks below executes this, tests/test_pipeline_gloo.py lets gloo ranks execute it on the CPU
+// (test_native_tick_plan_drives_gloo_ranks), tests/test_pipe_tick_plan_host.py checks every field for every rank and tick of 675 plans, and
+// tests/test_hip_pipe_stages.py executes it for N stages on one GPU.
 extern "C" int rama_pipe_tick_plan(const rama_pipe_plan* plan, int world, int rank, int tick, rama_pipe_tick* out) {
     if (!plan || !out || world < 1 || rank < 0 || rank >= world || plan->n_seq < 1 || plan->n_pos < 1 || plan->n_prompt < 0 || (plan->n_prompt && !plan->prompt)) return -1;
     const int last = world - 1;

@@ -11,7 +11,7 @@ import pytest
 from oracle import oracle as O
 from oracle import synth as S
 
-from .helpers import GOLDEN, load_case, to_rama_cfg
+from .helpers import GOLDEN, LOGIT_ATOL, load_case, to_rama_cfg
 
 pytestmark = pytest.mark.gpu
 
@@ -101,6 +101,77 @@ def test_native_tick_loop_equals_generate(dev, pipe, n_seq, temperature, graph, 
     for e in engines:
         e.free()
     model.free()
+
+
+WRAP, WRAP_POS, WRAP_SEQ = 8, 20, 2
+
+
+def _run_wrapped_plan(dev, pipe, graph, parity, splits):
+    """rama_pipe_run_ticks over the wrapped plan (wrap 8, 20 positions, 2 sequences, the 3-token prompt), one call per range that
+    `splits(total)` yields -> (history [n_seq, n_pos] by UNWRAPPED position, the reference's history)"""
+    import rama_amd
+    from rama_amd._lib import check, rama_run_state, rama_stage
+    from . import pipe_plan_cases as P
+    check(dev.lib.rama_set_tuning(dev.ctx, b"ref_order", parity))
+    cfg, w, g = load_case("synth_d288_h6")
+    prompt = g["tokens"].tolist()[1:4]
+    ref = P.reference(cfg, w, prompt, WRAP_POS, WRAP)
+    want = ref.history
+    assert parity or min(ref.gaps) > 2 * LOGIT_ATOL, ref.gaps      # fast mode's tokens are comparable where the oracle is decisive
+    model = rama_amd.Model.synth(dev, to_rama_cfg(cfg), int(g["seed"]), rope=(g["freq_cis_real"], g["freq_cis_imag"]))
+    engines = [rama_amd.Engine(dev, model) for _ in range(WRAP_SEQ)]
+    states = (rama_run_state * WRAP_SEQ)(*[e.state for e in engines])
+    toks = [dev.alloc(1) for _ in range(WRAP_SEQ)]
+    tok_ptrs = (C.c_void_p * WRAP_SEQ)(*[t.ptr for t in toks])
+    out = dev.allocate(np.full(WRAP_SEQ * WRAP_POS, -1, np.int32).view(np.float32))
+    plan = P.make_plan(WRAP_SEQ, WRAP_POS, WRAP, prompt, out=out.ptr)
+    stage = rama_stage(0, cfg.n_layers, 1, 1)
+    total = dev.lib.rama_pipe_total_ticks(pipe, C.byref(plan))
+    assert total == WRAP_SEQ * WRAP_POS
+    dev.lib.rama_set_graph_mode(dev.ctx, graph)
+    try:
+        for a, b in splits(total):
+            check(dev.lib.rama_pipe_run_ticks(pipe, C.byref(model.ccfg), C.byref(model.weights), states, tok_ptrs, C.byref(stage),
+                                              C.byref(plan), a, b), "rama_pipe_run_ticks")
+        hist = dev.download(out).view(np.int32).reshape(WRAP_SEQ, WRAP_POS)
+    finally:
+        dev.lib.rama_set_graph_mode(dev.ctx, 0)
+        check(dev.lib.rama_set_tuning(dev.ctx, b"ref_order", 0))
+        for e in engines:
+            e.free()
+        for t in toks + [out]:
+            t.free()
+        model.free()
+    return hist, want
+
+
+def _two_calls(total):
+    return [(0, total // 2), (total // 2, total)]
+
+
+def _one_tick_per_call(total):
+    return [(t, t + 1) for t in range(total)]
+
+
+@pytest.mark.parametrize("graph,parity", [(0, 0), (1, 0), (1, 1)])
+def test_native_tick_loop_wraps(dev, pipe, graph, parity):
+    """wrap = 8 through the native loop: a sequence that reaches position 8 starts over at position 0 with BOS and the prompt -- the
+    stage is given the wrapped position (20 positions would otherwise leave no trace of it: the model's seq_len is 64), the history is
+    filed by the unwrapped one and equals the reference's wrapped generate() at all 20 positions"""
+    hist, want = _run_wrapped_plan(dev, pipe, graph, parity, _two_calls)
+    assert want[WRAP:2 * WRAP] == want[:WRAP] and want[2 * WRAP:] == want[:WRAP_POS - 2 * WRAP]      # three generations of the same prompt
+    for s in range(WRAP_SEQ):
+        assert hist[s].tolist() == want, (s, hist[s].tolist(), want)
+
+
+@pytest.mark.parametrize("graph", [0, 1])
+def test_native_tick_loop_one_tick_per_call(dev, pipe, graph):
+    """the same plan run as [t, t + 1) for every t: the tick is the loop's only state, so the history is the two-call split's"""
+    single, want = _run_wrapped_plan(dev, pipe, graph, 0, _one_tick_per_call)
+    halves, _ = _run_wrapped_plan(dev, pipe, graph, 0, _two_calls)
+    assert np.array_equal(single, halves), (single.tolist(), halves.tolist())
+    for s in range(WRAP_SEQ):
+        assert single[s].tolist() == want, (s, single[s].tolist(), want)
 
 
 @pytest.mark.parametrize("name,parity", [("ckpt_tied", 0), ("ckpt_untied", 0), ("ckpt_untied", 1)])

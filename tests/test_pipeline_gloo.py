@@ -185,3 +185,107 @@ def test_native_schedule_matches_python_schedule():
             if lib.rama_pipe_item(C.byref(plan), 4, rank, tick, C.byref(seq), C.byref(pos)) == 1:
                 busy.append((tick, seq.value, pos.value))
         assert busy == [(4 * p + rank, 0, p) for p in range(3)]
+
+
+# ------------------------------------------------------------------ the NATIVE tick plan (csrc/pipe.hip rama_pipe_tick_plan) between real ranks
+
+PLAN_PROMPT_LEN = 3
+
+
+class PlanStage(OracleStage):
+    """an OracleStage for tests/pipe_plan_cases.py execute_tick: the stage pass and the sampler are separate calls, as in
+    rama_pipe_run_ticks, and the sampler is Device::sample (O.sample: the argmax at temperature 0)"""
+
+    def __init__(self, cfg, w, rank, world, n_seq, temperature, topp, u):
+        super().__init__(cfg, w, rank, world, n_seq)
+        self.sampler = (temperature, topp, u)
+
+    def compute(self, seq, pos, token):
+        if self.rank == 0 and token is None:
+            token = int(self.tok_buffers[seq][0])
+        self.orcs[seq].forward_range(int(token or 0), pos, self.lo, self.hi, self.rank == 0, self.rank == self.world - 1)
+
+    def sample(self, seq):
+        nxt = int(O.sample(self.orcs[seq].s["logits"].copy(), *self.sampler))
+        self.tok_buffers[seq][0] = nxt
+        self.produced[seq].append(nxt)
+
+
+def _plan_worker(rank, world, port, n_seq, n_pos, wrap, sampler, q):
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    O.lib().oracle_set_threads(1)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        import rama_amd
+        from tests import pipe_plan_cases as P
+        lib = rama_amd.load()
+        cfg, w, g = load_case(CASE)
+        prompt = g["tokens"].tolist()[1:1 + PLAN_PROMPT_LEN]
+        plan = P.make_plan(n_seq, n_pos, wrap, prompt, *sampler)
+        be = PlanStage(cfg, w, rank, world, n_seq, *sampler)
+        history = np.full((n_seq, n_pos), -1, dtype=np.int64)
+        both = 0      # ticks whose ONE batch held this rank's send and its receive
+        for t in range(P.plan_ticks(lib, plan, world)):
+            send, recv = P.execute_tick(P.tick(lib, plan, world, rank, t), rank, be)
+            ops = []
+            if send is not None:
+                kind, seq, peer = send
+                ops.append(dist.P2POp(dist.isend, be.x_buffers[seq] if kind == P.X else be.tok_buffers[seq], peer))
+            if recv is not None:
+                kind, seq, peer, recv_pos = recv
+                ops.append(dist.P2POp(dist.irecv, be.x_buffers[seq] if kind == P.X else be.tok_buffers[seq], peer))
+            both += len(ops) == 2
+            if ops:
+                for req in dist.batch_isend_irecv(ops):
+                    req.wait()
+            if recv is not None and recv[0] == P.TOKEN:      # rank 0 keeps the history, as rama_pipe_run_ticks does in out_tokens_dev
+                history[recv[1], recv[3]] = int(be.tok_buffers[recv[1]][0])
+        dist.barrier()
+        q.put((rank, history.tolist(), be.produced, both))
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("world,n_seq,n_pos,wrap,sampler", [
+    (2, 2, 9, 0, (0.0, 0.9, 0.0)),
+    (2, 3, 9, 0, (0.0, 0.9, 0.0)),
+    (3, 3, 9, 0, (0.0, 0.9, 0.0)),
+    (2, 1, 6, 0, (0.0, 0.9, 0.0)),       # fewer sequences than stages: Schedule refuses these, the native plan idles the extra slots
+    (3, 2, 6, 0, (0.0, 0.9, 0.0)),
+    (2, 2, 11, 4, (0.0, 0.9, 0.0)),      # every slot starts a new generation every 4 positions
+    (3, 3, 7, 0, (1.0, 0.9, 0.2721174359321594)),
+])
+def test_native_tick_plan_drives_gloo_ranks(world, n_seq, n_pos, wrap, sampler):
+    """world-2 and world-3 gloo ranks compute and exchange by rama_pipe_tick_plan alone (tests/pipe_plan_cases.py execute_tick, one
+    batch_isend_irecv per tick; Schedule is not consulted): the history rank 0 collects -- every position of every sequence, the
+    forced ones included -- and the ids the last rank sampled equal a single-process generate() of the whole model."""
+    from tests import pipe_plan_cases as P
+    cfg, w, g = load_case(CASE)
+    if world > cfg.n_layers + 1:
+        pytest.skip("more stages than layers")
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_plan_worker, args=(r, world, port, n_seq, n_pos, wrap, sampler, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    reports = {}
+    for _ in range(world):
+        rank, history, produced, both = q.get(timeout=120)
+        reports[rank] = (history, produced, both)
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    assert sorted(reports) == list(range(world))
+    want = P.reference(cfg, w, g["tokens"].tolist()[1:1 + PLAN_PROMPT_LEN], n_pos, wrap, *sampler).history
+    assert len(want) == n_pos
+    for s in range(n_seq):
+        assert reports[0][0][s] == want, (s, reports[0][0][s], want)              # rank 0's history, by unwrapped position
+        assert reports[world - 1][1][s] == want, (s, reports[world - 1][1][s], want)   # the last rank's own samples, in order
+    for r in range(1, world):
+        assert all(v == -1 for row in reports[r][0] for v in row), r               # nobody else receives a token
+    for r in range(world - 1):
+        assert reports[r][1] == [[] for _ in range(n_seq)], r                      # nobody else samples
+    if n_seq >= world:      # a full pipe: in steady state a rank's one batch holds both legs (world 2: both with the same peer)
+        assert all(reports[r][2] > 0 for r in range(world)), [reports[r][2] for r in range(world)]
