@@ -798,6 +798,62 @@ int  rama_q8_spec_begin_model(rama_ctx *ctx, const rama_config *cfg, const rama_
                               const int32_t *context_host, int n_context, const rama_q8_spec_plan *plan);
 int  rama_q8_spec_model_stats(rama_ctx *ctx, rama_q8_spec_model_report *out);
 
+/* THE SPECULATIVE CHAIN WITH TREE DRAFTS: several continuations of the tail n-gram, verified in one weight pass.
+ * rama_q8_spec_begin_tree starts the speculative chain above -- the same sequence record, ring and finished word, one captured
+ * graph for its life; rama_q8_spec_steps / _poll / _tokens / _stats / _end serve it unchanged, and it ends a previous speculative
+ * chain.  Notation as rama_q8_spec_begin's, plus B = n_branch in 1..4 and R = n_rows in 2..16.
+ * DRAFT (rama_q8_spec_tree_draft).  cap = min(K, room); cap <= 0: only the root.  n as above.  The occurrences of the tail at that
+ *   n, ordered hint before sequence and larger end first; the first B are the branches (there may be fewer), branch b the
+ *   min(cap, text_end - e_b) tokens behind occurrence b in its own text.  The branches are inserted in order into a trie whose root
+ *   (node 0) carries s[L-1]: walk from the root, follow a child with the same token, else create node m + 1 with parent = the
+ *   current node and depth = depth(parent) + 1; once R - 1 nodes exist everything stops.  Children of a node have distinct tokens,
+ *   parent < index, and branch 0 is rama_q8_spec_draft's draft: its nodes have index == depth.  A node with index != depth is OFF
+ *   THE TRUNK.
+ * STEP.  Row j carries tok[j] at position P + depth[j]; rows m+1..R-1 are idle.  All R rows are classified and
+ *   pick_j = Device::sample(logits_j).  Only the root writes its cache row (at P) during the pass: two nodes of one depth share a
+ *   position.  A row's attention reads timestep t <= P from the cache and timestep P + k from its ancestor of depth k in the pass.
+ * ACCEPT (rama_q8_spec_tree_accept).  cur = 0, emit pick_0; while the token just emitted is not the stop token, the budget is not
+ *   used up and cur has a child c with tok[c] == that token: cur = c, emit pick_c.  a = depth(cur); the path is the rows visited.
+ *   The sequence finishes at the budget or on an emitted stop token.  (a counts the rows walked: a stop token ends the walk, where
+ *   rama_q8_spec_accept's a goes on counting the drafts its picks reproduce behind it.)
+ * COMMIT.  The path's rows 1..a are copied to cache positions P+1..P+a in every layer.  UNLIKE rama_q8_spec_begin's chain, nothing
+ *   at or behind the new P is ever written.
+ * The output is rama_q8_generate's, bit for bit, whatever B, R, K, N, the hint and the graph mode; with B = 1 and R = K + 1 the
+ * drafts, the steps and the tokens are rama_q8_spec_begin's.
+ * rama_q8_spec_begin_tree: rama_q8_spec_begin's contract and refusals, plus RAMA_EINVAL for n_branch outside 1..4, n_rows
+ * outside 2..16 and n_draft < 1.  It also sizes the tree store, [n_layers][R-1][dim] floats twice, outside any capture.
+ * rama_q8_spec_stats keeps its meanings: drafts = sum m, rows_fed = sum (m + 1), accepted = sum a, accepted_hist[a].
+ * rama_q8_spec_tree_stats synchronises; RAMA_EINVAL on a chain begun any other way.  off_trunk_accepted = accepted nodes with
+ * index != depth, off_trunk_steps = steps that accepted one, nodes_hist[m] = steps whose tree had m nodes besides the root.
+ * rama_q8_spec_tree_draft and rama_q8_spec_tree_accept are HOST-ONLY.  _draft returns m and fills tok_out / parent_out /
+ * depth_out[0..m) with nodes 1..m.  _accept takes nodes 1..m the same way (tok[j-1], parent[j-1]) and picks[0..m]; it returns the
+ * tokens emitted and fills path_out[0..a] (>= 16 entries; may be NULL), *a_out and *finished (may be NULL).  Both answer
+ * RAMA_EINVAL (negative) for a bad argument.
+ *
+ * THE BUILDING BLOCKS, for host-driven speculators.  rama_q8_tree_forward: an eager pass over a caller's tree -- parent[0] = -1,
+ * parent[j] in [0, j), depth at most 15, n_rows in 1..16, pos0 + the deepest depth < seq_len; rows 0..pos0-1 of `state` were
+ * written by work enqueued earlier on the context's stream.  It writes logits_dev [n_rows, vocab_size] (device memory), the root's
+ * cache row at pos0 and nothing else of the cache.  rama_q8_tree_commit copies a root-to-node path (path[0] = 0, each row a child
+ * of the one before) of the LAST tree pass on that state to cache positions pos0+1..pos0+n_path-1.  Stream-ordered.  RAMA_EINVAL
+ * for every bad argument (a path that is none, another state, model or pos0 than the last pass's, a state freed since);
+ * RAMA_EUNSUP where rama_q8_batch_shape_ok == 0. */
+typedef struct {
+    uint64_t off_trunk_accepted, off_trunk_steps;
+    uint64_t nodes_hist[16];
+    int32_t n_branch, n_rows;
+} rama_q8_spec_tree_report;
+int  rama_q8_spec_begin_tree(rama_ctx *ctx, const rama_config *cfg, const rama_q8_weights *w, const rama_run_state *state,
+                             const int32_t *context_host, int n_context, const rama_q8_spec_plan *plan, int n_branch, int n_rows);
+int  rama_q8_spec_tree_stats(rama_ctx *ctx, rama_q8_spec_tree_report *out);
+int  rama_q8_spec_tree_draft(const int32_t *hint, int n_hint, const int32_t *seq, int L, int n_draft, int ngram, int room,
+                             int n_branch, int n_rows, int32_t *tok_out, int32_t *parent_out, int32_t *depth_out);
+int  rama_q8_spec_tree_accept(const int32_t *tok, const int32_t *parent, int m, const int32_t *picks, int stop_token, int remaining,
+                              int32_t *path_out, int *a_out, int *finished);
+int  rama_q8_tree_forward(rama_ctx *ctx, const rama_config *cfg, const rama_q8_weights *w, const rama_run_state *state,
+                          const int32_t *tokens_host, const int32_t *parent_host, int n_rows, int pos0, float *logits_dev);
+int  rama_q8_tree_commit(rama_ctx *ctx, const rama_config *cfg, const rama_run_state *state, const int32_t *path_host, int n_path,
+                         int pos0);
+
 /* SPECULATION INSIDE THE SERVING CHAIN: a DECODE slot's drafts fill the rows no slot wants.  A step of the
  * serving chain costs its weight pass of max_rows rows whatever they hold, and rows at consecutive positions of one sequence
  * are exact (the speculative chain above); so a slot may put drafted tokens into rows that would otherwise be idle, and take

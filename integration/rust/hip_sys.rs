@@ -69,6 +69,9 @@ pub struct rama_q8_spec_report {
 /// what rama_q8_spec_model_stats reports: the draft model's side of a chain begun with rama_q8_spec_begin_model
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct rama_q8_spec_model_report { pub draft_passes: u64, pub draft_rows_fed: u64, pub catch_up_rows: u64, pub draft_cursor: i32 }
+/// what rama_q8_spec_tree_stats reports: the tree side of a chain begun with rama_q8_spec_begin_tree
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct rama_q8_spec_tree_report { pub off_trunk_accepted: u64, pub off_trunk_steps: u64, pub nodes_hist: [u64; 16], pub n_branch: i32, pub n_rows: i32 }
 /// what rama_q8_serve_model_stats reports: the draft model's side of a serving chain begun with rama_q8_serve_begin_model
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct rama_q8_serve_model_report {
@@ -307,6 +310,18 @@ extern "C" {
                                     dcfg: *const rama_config, dw: *const rama_q8_weights, dstate: *const rama_run_state,
                                     context_host: *const i32, n_context: c_int, plan: *const rama_q8_spec_plan) -> c_int;
     pub fn rama_q8_spec_model_stats(ctx: *mut rama_ctx, out: *mut rama_q8_spec_model_report) -> c_int;
+    // ... with tree drafts: up to four continuations of the tail n-gram in one pass; _tree_draft and _tree_accept are host-only
+    pub fn rama_q8_spec_begin_tree(ctx: *mut rama_ctx, cfg: *const rama_config, w: *const rama_q8_weights, state: *const rama_run_state,
+                                   context_host: *const i32, n_context: c_int, plan: *const rama_q8_spec_plan, n_branch: c_int, n_rows: c_int) -> c_int;
+    pub fn rama_q8_spec_tree_stats(ctx: *mut rama_ctx, out: *mut rama_q8_spec_tree_report) -> c_int;
+    pub fn rama_q8_spec_tree_draft(hint: *const i32, n_hint: c_int, seq: *const i32, l: c_int, n_draft: c_int, ngram: c_int, room: c_int,
+                                   n_branch: c_int, n_rows: c_int, tok_out: *mut i32, parent_out: *mut i32, depth_out: *mut i32) -> c_int;
+    pub fn rama_q8_spec_tree_accept(tok: *const i32, parent: *const i32, m: c_int, picks: *const i32, stop_token: c_int, remaining: c_int,
+                                    path_out: *mut i32, a_out: *mut c_int, finished: *mut c_int) -> c_int;
+    pub fn rama_q8_tree_forward(ctx: *mut rama_ctx, cfg: *const rama_config, w: *const rama_q8_weights, state: *const rama_run_state,
+                                tokens_host: *const i32, parent_host: *const i32, n_rows: c_int, pos0: c_int, logits_dev: *mut f32) -> c_int;
+    pub fn rama_q8_tree_commit(ctx: *mut rama_ctx, cfg: *const rama_config, state: *const rama_run_state, path_host: *const i32, n_path: c_int,
+                               pos0: c_int) -> c_int;
     // speculation inside the serving chain: a DECODE slot's drafts in the rows no slot wants; _plan_step is host-only
     pub fn rama_q8_serve_begin_spec(ctx: *mut rama_ctx, cfg: *const rama_config, w: *const rama_q8_weights, n_slots: c_int, max_rows: c_int,
                                     max_new_cap: c_int, n_draft_cap: c_int, hint_cap: c_int) -> c_int;

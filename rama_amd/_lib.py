@@ -108,6 +108,12 @@ class rama_q8_spec_model_report(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("draft_passes", "draft_rows_fed", "catch_up_rows")] + [("draft_cursor", C.c_int32)]
 
 
+class rama_q8_spec_tree_report(C.Structure):
+    """what rama_q8_spec_tree_stats fills in: the tree side of a chain begun with rama_q8_spec_begin_tree"""
+    _fields_ = ([(n, C.c_uint64) for n in ("off_trunk_accepted", "off_trunk_steps")] + [("nodes_hist", C.c_uint64 * 16)] +
+                [("n_branch", C.c_int32), ("n_rows", C.c_int32)])
+
+
 class rama_q8_serve_spec(C.Structure):
     """a slot's drafting fields on a serving chain begun with rama_q8_serve_begin_spec (rama_q8_serve_admit_spec)"""
     _fields_ = [("n_draft", C.c_int32), ("ngram", C.c_int32), ("hint", C.POINTER(C.c_int32)), ("n_hint", C.c_int32)]
@@ -266,6 +272,12 @@ SIGNATURES = {
     "rama_q8_spec_model_stats": (_int, [_vp, C.POINTER(rama_q8_spec_model_report)]),
     "rama_q8_spec_draft": (_int, [i32p, _int, i32p, _int, _int, _int, _int, i32p]),
     "rama_q8_spec_accept": (_int, [i32p, _int, i32p, _int, _int, C.POINTER(_int)]),
+    "rama_q8_spec_begin_tree": (_int, [_vp, _cfgp, C.POINTER(rama_q8_weights), _sp, i32p, _int, C.POINTER(rama_q8_spec_plan), _int, _int]),
+    "rama_q8_spec_tree_stats": (_int, [_vp, C.POINTER(rama_q8_spec_tree_report)]),
+    "rama_q8_spec_tree_draft": (_int, [i32p, _int, i32p, _int, _int, _int, _int, _int, _int, i32p, i32p, i32p]),
+    "rama_q8_spec_tree_accept": (_int, [i32p, i32p, _int, i32p, _int, _int, i32p, C.POINTER(_int), C.POINTER(_int)]),
+    "rama_q8_tree_forward": (_int, [_vp, _cfgp, C.POINTER(rama_q8_weights), _sp, i32p, i32p, _int, _int, _vp]),
+    "rama_q8_tree_commit": (_int, [_vp, _cfgp, _sp, i32p, _int, _int]),
     "rama_q8_serve_begin_spec": (_int, [_vp, _cfgp, C.POINTER(rama_q8_weights), _int, _int, _int, _int, _int]),
     "rama_q8_serve_admit_spec": (_int, [_vp, _int, _sp, i32p, _int, _int, C.POINTER(rama_q8_serve_plan), C.POINTER(rama_q8_serve_spec)]),
     "rama_q8_serve_spec_plan_step": (_int, [C.POINTER(rama_q8_serve_slot), _int, _int, i32p, C.POINTER(rama_q8_serve_row), i32p]),

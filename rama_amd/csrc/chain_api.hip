@@ -4,6 +4,7 @@
 // translation units fill in chain_params.hpp's parameter blocks and call the launchers that ctx.hpp declares (DESIGN.md "Translation units").
 #include "ctx.hpp"
 #include "chain.hpp"
+#include "q8_tree.hpp"          // attention_tree_kernel (after chain.hpp: its attention half)
 #include "topp_pick.hpp"
 #include "topp_kernels.hpp"
 
@@ -16,6 +17,9 @@ int chain_api_init(rama_ctx*) {
     HIPCHK(hipFuncSetAttribute((const void*)attention_chain_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAttnChainMaxLds));
     HIPCHK(hipFuncSetAttribute((const void*)attention_chain_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAttnChainMaxLds));
     HIPCHK(hipFuncSetAttribute((const void*)attention_chain_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAttnChainMaxLds));
+    HIPCHK(hipFuncSetAttribute((const void*)attention_tree_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAttnChainMaxLds));
+    HIPCHK(hipFuncSetAttribute((const void*)attention_tree_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAttnChainMaxLds));
+    HIPCHK(hipFuncSetAttribute((const void*)attention_tree_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAttnChainMaxLds));
 #define RAMA_GC_ATTR(TPW_) \
     HIPCHK(hipFuncSetAttribute((const void*)gemm_chain_kernel<TPW_, CEPI_STORE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm_chain_lds_bytes(TPW_))); \
     HIPCHK(hipFuncSetAttribute((const void*)gemm_chain_kernel<TPW_, CEPI_RESID>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm_chain_lds_bytes(TPW_))); \
@@ -272,6 +276,16 @@ int launch_attention_chain_tokens(rama_ctx* c, const RefAttnParams& a, int n_hea
     if (nw == 4) hipLaunchKernelGGL((attention_chain_kernel<4>), grid, dim3(4 * 64), lds, c->stream, a);
     else if (nw == 8) hipLaunchKernelGGL((attention_chain_kernel<8>), grid, dim3(8 * 64), lds, c->stream, a);
     else hipLaunchKernelGGL((attention_chain_kernel<16>), grid, dim3(16 * 64), lds, c->stream, a);
+    LAUNCHCHK();
+    return 0;
+}
+
+// the same grid for the rows of a tree pass (q8_tree.hpp): a timestep behind the root's position is read from an ancestor's row of the pass
+int launch_attention_tree(rama_ctx* c, const TreeAttnParams& a, int n_heads, int nt, int nw, size_t lds) {
+    const dim3 grid(n_heads, nt);
+    if (nw == 4) hipLaunchKernelGGL((attention_tree_kernel<4>), grid, dim3(4 * 64), lds, c->stream, a);
+    else if (nw == 8) hipLaunchKernelGGL((attention_tree_kernel<8>), grid, dim3(8 * 64), lds, c->stream, a);
+    else hipLaunchKernelGGL((attention_tree_kernel<16>), grid, dim3(16 * 64), lds, c->stream, a);
     LAUNCHCHK();
     return 0;
 }

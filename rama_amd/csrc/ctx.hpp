@@ -12,6 +12,7 @@
 #include "chain_params.hpp"     // ChainParams, GemmChainParams, CEPI_* / CNORM_*
 #include "q8_serve_tables.hpp"  // ServeTables
 #include "q8_spec_tables.hpp"   // SpecTables
+#include "q8_tree_tables.hpp"   // TreeTables, TreeAttnParams
 #include "q8_serve_spec_tables.hpp"     // ServeSpecTables
 #include "q8_serve_model_tables.hpp"    // ServeModelTables
 
@@ -331,7 +332,20 @@ struct rama_ctx {
         rama_config dcfg{}; rama_q8_weights dw{}; rama_run_state dstate{};      // the draft model and its run state: the chain dies with either
         SpecModelTables mt{};              // the device tables (inside blob)
         char* dblob = nullptr;             // the draft passes' batch scratch, a Q8BatchScratch of kSpecRows rows of the draft model's shape
+        // a chain begun with rama_q8_spec_begin_tree (q8_tree.hpp): the drafts form a tree; all of it unused otherwise
+        bool tree = false;
+        TreeTables tt{};                   // the tree record and the ancestor records (inside blob), the tree store (tblob)
+        char* tblob = nullptr;
     } q8p;
+    // rama_q8_tree_forward / _commit (q8_tree.hpp): the tables of an eager tree pass and what its commit checks a path against
+    struct Q8Tree {
+        char* blob = nullptr; char* store = nullptr; size_t store_cap = 0;
+        SeqSlot* rows = nullptr; int* row_tok = nullptr;
+        TreeTables tt{};
+        float* kc = nullptr;               // the run state of the last pass (NULL: none, or its state is gone)
+        int n_rows = 0, pos0 = 0, n_layers = 0, dim = 0, seq_len = 0;
+        int parent[kSpecRows] = {};
+    } q8t;
     // rama_serve_begin / _admit / _steps: the serving chain of an fp32 model in parity mode (batch_api.hip).  A state of its own: it
     // may be live next to q8s on the same context, and neither touches the other's graph or tables.
     struct Serve : ServeState {
@@ -399,6 +413,7 @@ int ensure_attn_scores(rama_ctx* c, int n_heads, int seq_len);
 int launch_attention_chain(rama_ctx* c, float* xb, float* att, const float* q, const float* kc_layer, const float* vc_layer,
                            const Ctl* ctl, int pos, int dim, int head_size, int seq_len, int n_heads, bool long_ctx = false, bool spread_wanted = false);
 int launch_attention_chain_tokens(rama_ctx* c, const RefAttnParams& a, int n_heads, int nt, int nw, size_t lds);
+int launch_attention_tree(rama_ctx* c, const TreeAttnParams& a, int n_heads, int nt, int nw, size_t lds);      // q8_tree.hpp's attention_tree_kernel
 
 int topp_dist_check(rama_ctx* c);     // handoff_check: the distributed pick's error word
 int enqueue_sample(rama_ctx* c, ArgmaxParams fin, float temperature, float topp, float u);

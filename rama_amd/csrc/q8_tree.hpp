@@ -1,0 +1,401 @@
+// q8_tree.hpp -- TREE DRAFTS for the speculative chain of a Q8 model (rama_q8_spec_begin_tree, rama_q8_tree_forward / _commit, DESIGN.md
+// section 8.13): up to four continuations of the tail n-gram share their common prefix in one pass of up to 16 rows.  Two nodes at one depth
+// sit at one position, so only the root writes its cache row during the pass; every other row's k and v stay in the pass's own rows, and a row's
+// attention takes each timestep behind the root from the ancestor of that depth.  Every step
+//   spec_tree_draft_kernel   spec_draft_kernel's scan n_branch times (round b: the largest key below round b - 1's), the trie, the row table,
+//                            the ancestor records, the row tokens, the sampler records
+//   the batched pass         q8_batch_layers with q8_rope_tree_kernel and attention_tree_kernel in place of the two launches that touch the cache
+//   spec_pick_kernel         (q8_spec.hpp, unchanged: rows 0..m)
+//   spec_tree_accept_kernel  the accept rule over the tree, the ring / count / finished words as spec_accept_kernel stores them, the path
+//   tree_commit_kernel       the path's rows from the tree store to cache positions P + 1 .. P + a, every layer
+// This header serves two translation units (DESIGN.md "Translation units"): attention_tree_kernel is built from chain.hpp's pieces and lives
+// with them in chain_api.hip (the half under RAMA_CHAIN_HPP); everything else lives in q8_api.hip, which must not see chain.hpp.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "kernels.hpp"
+#include "q8_tree_tables.hpp"
+
+namespace rama {
+
+#ifdef RAMA_CHAIN_HPP
+// ---------------------------------------------------------------- cpu.rs:23-52 multi_head_attention over a tree row
+// attention_chain_body's operations in its order per output -- the score chains in index order, / sqrtf(hs); max, expf_glibc_tab,
+// seq_sum_cascade over pos + 1 terms, divide; the products a * v rounded, added in ascending t -- with one difference: where a timestep's
+// row comes from.  t <= P (the root's position) is cache row t; t = P + k is row path[k] of the pass.  Both addresses are formed, one is
+// selected, the load is issued: no branch around a load, and both bases are global address space.
+template <int NW>
+__global__ __launch_bounds__(NW * 64) void attention_tree_kernel(TreeAttnParams tp) {
+    RAMA_NO_CONTRACT
+    RefAttnParams p = tp.a;
+    const int y = blockIdx.y, h = blockIdx.x;
+    const int pos = p.seqs[y].pos;
+    if (pos < 0) return;                                          // an idle row (uniform: the whole workgroup)
+    constexpr int T = NW * 64;
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    __shared__ SeqSumShared<NW> sh;
+    __shared__ PredShared<NW> ps;
+    __shared__ FastSumShared<NW> fsn;
+    __shared__ float red[16];
+    __shared__ unsigned long long s_tab[32];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    exp_tab_fill(s_tab);
+    const int lds_seq = p.seq_len;
+    const unsigned long long path = tp.anc[y].path;
+    const int P = pos - tp.anc[y].depth;                          // the root's position: rows 0..P come from the cache
+    const float* kcl = p.seqs[y].kc + p.layer_off;
+    const float* vcl = p.seqs[y].vc + p.layer_off;
+    p.q += (size_t)y * p.tok_stride; p.xb += (size_t)y * p.tok_stride;
+    if (p.att) p.att += (size_t)y * p.att_stride;
+    const int hs = p.head_size, hs4 = hs >> 2;
+    const size_t col = (size_t)h * hs;
+    // timestep t <= pos of this row, as a 16-byte pointer to its head columns: the cache's row or an ancestor's
+    auto row_of = [&](const float* cache, const float* rows, int t) -> gf4p {
+        const int k = max(t - P, 0);                              // 0..depth <= 15
+        const int r = (int)((path >> (4 * k)) & 15ull);
+        const gf4p c = gptr4(cache + (size_t)min(t, P) * p.dim + col);
+        const gf4p s = gptr4(rows + (size_t)r * p.dim + col);
+        return t <= P ? c : s;
+    };
+    float* s_q = sm;                                              // [hs]
+    float* s_p = sm + ((hs + 3) & ~3);                            // [lds_seq] the probabilities
+    float* s_att = s_p + ((lds_seq + 3) & ~3);                    // [scan_slot(lds_seq)] scores -> exponentials
+    const int region_off = (((hs + 3) & ~3) + ((lds_seq + 3) & ~3) + lds_seq + (lds_seq >> 5) + 4 + 3) & ~3;      // (an offset, not a rounded pointer)
+    float* region = sm + region_off;
+    for (int i = tid; i < hs; i += T) s_q[i] = p.q[col + i];
+    constexpr int U = NW >= 16 ? 4 : 8;
+    const int tile4 = kAttTile * hs4;
+    int er[U], ec[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) { const int e = tid + u * T; er[u] = e / hs4; ec[u] = e - er[u] * hs4; }
+    auto vissue = [&](int t0, f4 (&vr)[U]) {
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const int tr = min(t0 + er[u], pos), c4 = ec[u];      // (rows behind pos are clamped: their products are written, never added)
+            vr[u] = __builtin_nontemporal_load(row_of(vcl, tp.v, tr) + c4);
+        }
+    };
+    f4 va[U], vb[U];
+    __syncthreads();
+    const float scale_div = sqrtf((float)hs);
+    const f4* q4 = reinterpret_cast<const f4*>(s_q);
+    if (hs % kAttPiece == 0 && pos >= 1024) {       // long contexts: staged pieces; a group of 64 timesteps may hold cache rows and ancestors
+        float* stage = region + wave * (64 * kAttStride);
+        const int npiece = hs / kAttPiece;
+        const int lrow = lane >> 3, lc4 = lane & 7;
+        const int ngroup = (pos + 64) >> 6;
+        const int nstep = ((ngroup - wave + NW - 1) / NW) * npiece;
+        auto load_step = [&](int st, f4 (&d)[8]) {
+            const int sc = min(st, max(nstep - 1, 0));
+            const int g = wave + (sc / npiece) * NW, pc = sc % npiece;
+#pragma unroll
+            for (int u = 0; u < 8; u++) {
+                const int t = min(g * 64 + u * 8 + lrow, pos);
+                d[u] = __builtin_nontemporal_load(row_of(kcl, tp.kr, t) + pc * (kAttPiece / 4) + lc4);
+            }
+        };
+        constexpr int NB = NW >= 16 ? 1 : 2;
+        f4 na[8], nb[NB == 2 ? 8 : 1];
+        load_step(0, na);
+        if constexpr (NB == 2) load_step(1, nb);
+        float acc = 0.0f;
+        auto consume = [&](int st, f4 (&d)[8]) {
+#pragma unroll
+            for (int u = 0; u < 8; u++) *reinterpret_cast<f4*>(stage + (u * 8 + lrow) * kAttStride + 4 * lc4) = d[u];
+            load_step(st + NB, d);
+            __builtin_amdgcn_wave_barrier();
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            const int pc = st % npiece;
+            const f4* row = reinterpret_cast<const f4*>(stage + lane * kAttStride);
+            f4 kk[8];
+#pragma unroll
+            for (int i = 0; i < 8; i++) kk[i] = row[i];
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                const f4 qq = q4[pc * 8 + i];
+                acc = acc + qq.x * kk[i].x; acc = acc + qq.y * kk[i].y; acc = acc + qq.z * kk[i].z; acc = acc + qq.w * kk[i].w;
+            }
+            if (pc + 1 == npiece) {
+                const int t = (wave + (st / npiece) * NW) * 64 + lane;
+                if (t <= pos) s_att[scan_slot(t)] = acc / scale_div;
+                acc = 0.0f;
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_wave_barrier();
+        };
+        for (int st = 0; st < nstep; st += NB) {                  // uniform per wave
+            consume(st, na);
+            if constexpr (NB == 2) { if (st + 1 < nstep) consume(st + 1, nb); }
+        }
+    } else {
+        for (int t = tid; t <= pos; t += T) {
+            const gf4p k4 = row_of(kcl, tp.kr, t);
+            float acc = 0.0f;
+            int i = 0;
+            auto batch = [&](auto nb) {
+                constexpr int NB = decltype(nb)::value;
+                for (; i + NB <= hs4; i += NB) {
+                    f4 kk[NB];
+#pragma unroll
+                    for (int u = 0; u < NB; u++) kk[u] = k4[i + u];
+#pragma unroll
+                    for (int u = 0; u < NB; u++) {
+                        const f4 qq = q4[i + u];
+                        acc = acc + qq.x * kk[u].x; acc = acc + qq.y * kk[u].y; acc = acc + qq.z * kk[u].z; acc = acc + qq.w * kk[u].w;
+                    }
+                }
+            };
+            if constexpr (NW < 16) batch(std::integral_constant<int, 32>{});
+            batch(std::integral_constant<int, 16>{});
+            batch(std::integral_constant<int, 8>{});
+            batch(std::integral_constant<int, 4>{});
+            for (; i < hs4; i++) {
+                const f4 kk = k4[i], qq = q4[i];
+                acc = acc + qq.x * kk.x; acc = acc + qq.y * kk.y; acc = acc + qq.z * kk.z; acc = acc + qq.w * kk.w;
+            }
+            s_att[scan_slot(t)] = acc / scale_div;
+        }
+    }
+    __syncthreads();
+    // softmax_num (cpu.rs:187-192)
+    float mx = -INFINITY;
+    for (int t = tid; t <= pos; t += T) mx = fmaxf(mx, s_att[scan_slot(t)]);
+    mx = block_max(mx, red);
+    for (int t = tid; t <= pos; t += T) s_att[scan_slot(t)] = expf_glibc_tab(s_att[scan_slot(t)] - mx, s_tab);
+    __syncthreads();
+    const float sum = seq_sum_cascade<NW>(s_att, pos + 1, fsn, ps, sh);
+    for (int t = tid; t <= pos; t += T) {
+        const float a = s_att[scan_slot(t)] / sum;
+        s_p[t] = a;
+        if (p.att) p.att[(size_t)h * p.seq_len + t] = a;
+    }
+    float acc = 0.0f;
+    vissue(0, va);
+    if (pos >= kAttTile) vissue(kAttTile, vb);                   // (uniform)
+    __syncthreads();                                              // the probabilities are final; the staging region is free
+    auto vtile = [&](int t0, int buf, f4 (&vr)[U]) {
+        float* tile = region + buf * (kAttTile * hs);
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const int e = tid + u * T;
+            if (e < tile4) {
+                const float a = s_p[min(t0 + er[u], pos)];
+                const f4 vv = vr[u];
+                f4 pr;
+                pr.x = a * vv.x; pr.y = a * vv.y; pr.z = a * vv.z; pr.w = a * vv.w;     // cpu.rs:48 `a * vi`, rounded
+                *reinterpret_cast<f4*>(tile + 4 * e) = pr;
+            }
+        }
+        if (t0 + 2 * kAttTile <= pos) vissue(t0 + 2 * kAttTile, vr);      // (uniform)
+        __syncthreads();
+        if (tid < hs) {
+            const int nt = min(kAttTile, pos + 1 - t0);
+            int r = 0;
+            for (; r + 16 <= nt; r += 16) {
+                float v16[16];
+#pragma unroll
+                for (int u = 0; u < 16; u++) v16[u] = tile[(r + u) * hs + tid];
+#pragma unroll
+                for (int u = 0; u < 16; u++) acc = acc + v16[u];
+            }
+            for (; r < nt; r++) acc = acc + tile[r * hs + tid];
+        }
+    };
+    for (int t0 = 0; t0 <= pos; t0 += 2 * kAttTile) {
+        vtile(t0, 0, va);
+        if (t0 + kAttTile <= pos) vtile(t0 + kAttTile, 1, vb);    // uniform
+    }
+    if (tid < hs) p.xb[col + tid] = acc;
+}
+
+#else  // ---------------------------------------------------------------- everything but the attention: q8_api.hip's half
+
+// infer.rs:25-33 for the rows of a tree: q8_rope_batch_kernel's arithmetic.  The root (row 0) writes its cache row; every other live row
+// writes its rotated k and its v into the tree store instead (two rows of one depth share a position).  Kr / V keep the layer's rows.
+__global__ void q8_rope_tree_kernel(float* Q, float* Kr, const float* V, const float* fr, const float* fi, int dim, int head_size,
+                                    const SeqSlot* seqs, size_t layer_off, float* ks, float* vs) {
+    RAMA_NO_CONTRACT
+    const int j = blockIdx.x * blockDim.x + threadIdx.x, t = blockIdx.y;
+    if (j >= dim / 2) return;
+    const int pos = seqs[t].pos;
+    if (pos < 0) return;                   // an idle row: nothing rotated, nothing stored
+    // (row 0 is never idle when any row is live; its bases are the sequence's)
+    float* kd = t == 0 ? seqs[t].kc + layer_off + (size_t)pos * dim : ks + (size_t)(t - 1) * dim;
+    float* vd = t == 0 ? seqs[t].vc + layer_off + (size_t)pos * dim : vs + (size_t)(t - 1) * dim;
+    float* q = Q + (size_t)t * dim;
+    float* k = Kr + (size_t)t * dim;
+    const float* v = V + (size_t)t * dim;
+    const int i = j % (head_size / 2);
+    const float fcr = fr[(size_t)pos * (head_size / 2) + i], fci = fi[(size_t)pos * (head_size / 2) + i];
+    const float q0 = q[2 * j], q1 = q[2 * j + 1];
+    const float a0 = q0 * fcr - q1 * fci, a1 = q0 * fci + q1 * fcr;
+    q[2 * j] = a0; q[2 * j + 1] = a1;
+    const float k0 = k[2 * j], k1 = k[2 * j + 1];
+    const float b0 = k0 * fcr - k1 * fci, b1 = k0 * fci + k1 * fcr;
+    k[2 * j] = b0; k[2 * j + 1] = b1;
+    kd[2 * j] = b0; kd[2 * j + 1] = b1;                           // infer.rs:32
+    vd[2 * j] = v[2 * j]; vd[2 * j + 1] = v[2 * j + 1];           // infer.rs:33
+}
+
+// The commit: row path[k] of the store -> cache position pos0 + k for k = 1..a, every layer.  Grid (n_layers, 15): the path and a are read from
+// the chain state, so the launch is the same whatever was accepted.
+struct TreeCommitParams {
+    const TreeState* ts;
+    float* kc; float* vc;               // the sequence's cache bases
+    const float* ks; const float* vs;
+    int dim, seq_len, store_rows;
+};
+__global__ __launch_bounds__(256) void tree_commit_kernel(TreeCommitParams p) {
+    const int l = blockIdx.x, k = blockIdx.y + 1;
+    const TreeState* ts = p.ts;
+    if (k > ts->a) return;                                        // (uniform: the whole workgroup)
+    const int r = ts->path[k];                                    // 1..store_rows
+    const size_t src = ((size_t)l * p.store_rows + (size_t)(r - 1)) * p.dim;
+    const size_t dst = ((size_t)l * p.seq_len + (size_t)(ts->pos0 + k)) * p.dim;
+    for (int i = threadIdx.x; i < p.dim / 4; i += blockDim.x) {
+        reinterpret_cast<f4*>(p.kc + dst)[i] = reinterpret_cast<const f4*>(p.ks + src)[i];
+        reinterpret_cast<f4*>(p.vc + dst)[i] = reinterpret_cast<const f4*>(p.vs + src)[i];
+    }
+}
+
+// spec_scan_text (q8_spec.hpp) with a ceiling: the largest key below `limit` among this thread's candidates
+__device__ __forceinline__ int spec_tree_scan_text(const int* text, int hi, int n, const int (&tail)[kSpecMaxNgram], int key_bit, int limit, int best) {
+    for (int e = n + (int)threadIdx.x; e <= hi; e += (int)blockDim.x) {
+        bool ok = true;
+#pragma unroll
+        for (int i = 0; i < kSpecMaxNgram; i++) {
+            const int v = text[min(e - n + i, e - 1)];            // e >= n >= 1: [e - n, e - 1] is inside the text
+            ok = ok && (i >= n || v == tail[i]);
+        }
+        const int key = key_bit | e;
+        best = ok && key < limit ? max(best, key) : best;
+    }
+    return best;
+}
+
+__global__ __launch_bounds__(1024) void spec_tree_draft_kernel(SpecTables t, TreeTables tt) {
+    __shared__ int s_best[16];
+    __shared__ int s_keys[kTreeMaxBranch], s_br[kTreeMaxBranch][kSpecMaxDraft], s_tok[kSpecRows], s_par[kSpecRows], s_dep[kSpecRows], s_m;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    SpecState* st = t.st;
+    TreeState* ts = tt.ts;
+    const int L = st->L, n_hint = st->n_hint, K = st->n_draft, fin = st->finished;
+    const int B = ts->n_branch, R = ts->n_rows;
+    const int P = L - 1;
+    const int* hint = t.text;
+    const int* s = t.text + n_hint;
+    const int room = min(st->seq_len - 1 - P, st->max_new - st->n_out - 1);
+    const int cap = fin ? 0 : max(min(K, room), 0);
+    int nb = 0;
+    if (cap > 0) {                                                 // (uniform, as everything that decides a barrier below)
+        for (int n = min(st->ngram, L); n >= 1 && nb == 0; n--) {
+            int tail[kSpecMaxNgram];
+#pragma unroll
+            for (int i = 0; i < kSpecMaxNgram; i++) tail[i] = s[min(L - n + i, L - 1)];
+            int limit = 0x7fffffff;
+            for (int b = 0; b < B; b++) {                          // round b: the largest key strictly below round b - 1's
+                int best = spec_tree_scan_text(hint, n_hint, n, tail, kSpecHintBit, limit, -1);
+                best = spec_tree_scan_text(s, L - 1, n, tail, 0, limit, best);
+                best = wave_max_i(best);
+                if (lane == 0) s_best[wave] = best;
+                __syncthreads();
+                int key = s_best[0];
+                for (int w = 1; w < (int)(blockDim.x >> 6); w++) key = max(key, s_best[w]);
+                __syncthreads();
+                if (key < 0) break;                                // (uniform) fewer occurrences than branches
+                if (tid == 0) s_keys[nb] = key;
+                nb++; limit = key;
+            }
+        }
+    }
+    __syncthreads();
+    // the branches' tokens, one per thread (index clamped into the text, the value selected afterwards), then the trie in LDS by one thread:
+    // at most 4 x 15 insertions, one statement with the host's
+    if (tid < kTreeMaxBranch * kSpecMaxDraft) {
+        const int b = tid / kSpecMaxDraft, i = tid - b * kSpecMaxDraft;
+        const int key = s_keys[min(b, max(nb - 1, 0))];
+        const bool in_hint = (key & kSpecHintBit) != 0;
+        const int e = key & (kSpecHintBit - 1), len_text = in_hint ? n_hint : L;
+        const bool on = b < nb && i < min(cap, len_text - e);
+        const int v = (in_hint ? hint : s)[on ? e + i : 0];       // (s[0] exists: L >= 1)
+        s_br[b][i] = on ? v : -1;
+    }
+    if (tid == 0) { s_tok[0] = s[L - 1]; s_par[0] = -1; s_dep[0] = 0; }
+    __syncthreads();
+    if (tid == 0) {
+        int m = 0;
+        for (int b = 0; b < nb; b++) {
+            int len = 0;
+            while (len < kSpecMaxDraft && s_br[b][len] >= 0) len++;
+            if (!spec_tree_insert(s_tok, s_par, s_dep, &m, s_br[b], len, R)) break;
+        }
+        s_m = m;
+        ts->m = m;
+        ts->a = 0;                                                 // an idle step commits nothing
+        ts->pos0 = P;
+        st->n_d = m;                                               // spec_pick_kernel picks rows 0..n_d
+        st->steps += 1ull;
+        if (!fin) { st->rows_fed += (unsigned long long)(m + 1); st->drafts += (unsigned long long)m; }
+    }
+    __syncthreads();
+    if (tid < kSpecRows) {
+        const int m = s_m;
+        const bool on = !fin && tid <= m;
+        const int d = on ? s_dep[tid] : 0;
+        unsigned long long path = 0ull;
+        for (int c = on ? tid : 0, k = d; k >= 0; k--) {           // from the node up to the root: nibble k = the ancestor at depth k
+            path |= (unsigned long long)c << (4 * k);
+            c = max(s_par[c], 0);
+        }
+        const int tok = on ? s_tok[tid] : 0;
+        if (on) { ts->tok[tid] = tok; ts->parent[tid] = s_par[tid]; ts->depth[tid] = d; }
+        if (tid < R) {                                             // R <= kSpecRows rows
+            t.rows[tid] = on ? SeqSlot{st->kc, st->vc, P + d, 0} : SeqSlot{nullptr, nullptr, -1, -1};
+            tt.anc[tid] = TreeAnc{path, d, 0};
+            t.row_tok[tid] = tok;
+            t.trow[tid] = ToppRow{on ? st->temperature : 0.0f, st->topp, st->u, 0, nullptr};
+        }
+        if (tid >= 1) st->d[tid - 1] = on ? tok : -1;
+    }
+}
+
+// What ends a step: spec_accept_kernel's stores in its order and at its scopes, over the tree rule; the path stays behind for the commit.
+__global__ void spec_tree_accept_kernel(SpecTables t, TreeTables tt) {
+    if (threadIdx.x != 0) return;
+    SpecState* st = t.st;
+    TreeState* ts = tt.ts;
+    if (st->finished) return;
+    const int n_out = st->n_out, L = st->L, m = ts->m;
+    int a, fin, toks[kSpecRows], path[kSpecRows];
+    const int emit = spec_tree_accept_rule(ts->tok, ts->parent, m, st->picks, st->stop, st->max_new - n_out, path, toks, &a, &fin);
+    int* s = t.text + st->n_hint;
+    for (int i = 0; i < emit; i++) {                               // L + emit <= n_context + max_new <= seq_len; n_out + emit <= max_new
+        const int tok = toks[i];
+        s[L + i] = tok;
+        t.out[n_out + i] = tok;
+        __hip_atomic_store(t.ring + n_out + i, tok + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    st->L = L + emit;
+    st->n_out = n_out + emit;
+    __hip_atomic_store(t.count, n_out + emit, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);      // (after the ring words)
+    if (fin) {
+        st->finished = 1;
+        __hip_atomic_store(t.done, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);              // (after the count)
+    }
+    st->accepted += (unsigned long long)a;
+    st->emitted += (unsigned long long)emit;
+    st->hist[a] += 1ull;
+    int off = 0;
+    for (int k = 0; k <= a; k++) { ts->path[k] = path[k]; off += path[k] != k; }      // a node with index != depth is off the trunk
+    ts->a = a;
+    ts->off_trunk_accepted += (unsigned long long)off;
+    ts->off_trunk_steps += off ? 1ull : 0ull;
+    ts->nodes_hist[m] += 1ull;
+}
+
+#endif  // RAMA_CHAIN_HPP
+
+}  // namespace rama

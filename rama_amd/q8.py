@@ -10,9 +10,10 @@ import numpy as np
 from ._host import (MAX_BATCH, MAX_DRAFT, MAX_NGRAM, _check_batch, _check_budget, _check_context, _check_drafting,  # noqa: F401  (the caps: re-exported)
                     _check_sampled_vocab, _check_sampler, _check_stop, _drain, _i32, _per_seq, _report, _ring_poll, _stream_busy, _tokens)
 from ._lib import (Q8_TENSORS, check, load, rama_config, rama_q8_seq_plan, rama_q8_spec_model_report, rama_q8_spec_plan, rama_q8_spec_report,
+                   rama_q8_spec_tree_report,
                    rama_q8_weights, rama_run_state)
 from .q8_replay import (SERVE_DECODE, SERVE_DONE, SERVE_FREE, SERVE_PROMPT,  # noqa: F401  (the restatements: re-exported)
-                        _accept_py, _draft_py, _spec_plan_py, serve_model_replay, serve_spec_replay, spec_model_replay, spec_replay)
+                        _accept_py, _draft_py, _spec_plan_py, serve_model_replay, serve_spec_replay, spec_model_replay, spec_replay, spec_tree_replay)
 from .sampler_const import TOPP_U_CPU
 from .serve import (PrefixPool, ServeLoop, common_prefix, serve_model_plan_step, serve_model_report, serve_model_sizes,  # noqa: F401  (the serving loop: re-exported)
                     serve_plan, serve_plan_step, serve_sizes, serve_spec_plan_step, serve_spec_report, serve_spec_request, serve_spec_sizes)
@@ -155,7 +156,7 @@ class Q8Engine:
     spec_stats = None  # the last generate_spec's report (rama_q8_spec_stats)
 
     def generate_spec(self, context, max_new, temperature=0.0, topp=0.9, u=TOPP_U_CPU, stop_token=None, n_draft=7, ngram=3,
-                      hint=None, on_token=None, draft=None):
+                      hint=None, on_token=None, draft=None, n_branch=None, tree_rows=None):
         """speculative decode (rama_q8_spec_begin / _steps / _poll): context = the tokens fed at positions
         0..n-1 (the caller includes BOS) -> the up to max_new sampled tokens, those generate(context[1:], n - 1 + max_new,
         ...)[n-1:] gives, cut after stop_token.  Up to n_draft tokens per step are guessed by looking the last <= ngram
@@ -164,11 +165,17 @@ class Q8Engine:
         run.  The report of the run stays behind as self.spec_stats.
         draft = a Q8Engine over a small model with the same vocabulary, on the same device (rama_q8_spec_begin_model, DESIGN.md
         8.9): the guesses are that model's own next tokens under the same sampler instead of the lookup -- 1 <= n_draft, no hint,
-        ngram ignored; context[:-1] is prefilled on both engines, and spec_stats also has rama_q8_spec_model_stats' fields."""
+        ngram ignored; context[:-1] is prefilled on both engines, and spec_stats also has rama_q8_spec_model_stats' fields.
+        n_branch = B in 1..4 (with tree_rows = R in 2..16, default 16): tree drafts (rama_q8_spec_begin_tree) --
+        the continuations of the B latest occurrences share one pass of R rows; 1 <= n_draft, no draft model; spec_stats also
+        has rama_q8_spec_tree_stats' fields.  The default (None) stays the linear chain."""
         ctx_toks, hint_toks, (T, P, U, new, stop, K, N) = spec_plan(self.cfg, context, max_new, temperature, topp, u, stop_token,
                                                                     n_draft, ngram, hint)
         if draft is not None:
             spec_model_check(self, draft, len(ctx_toks), new, K, hint_toks)
+        tree = n_branch is not None or tree_rows is not None
+        if tree:
+            B, R = spec_tree_check(draft, K, 1 if n_branch is None else n_branch, 16 if tree_rows is None else tree_rows)
         L, ctx = self.device.lib, self.device.ctx
         if len(ctx_toks) > 1:
             self.prefill(ctx_toks[:-1])
@@ -177,7 +184,9 @@ class Q8Engine:
         harr = _i32(hint_toks)
         rec = rama_q8_spec_plan(T, P, U, new, stop, K, N, harr if hint_toks else None, len(hint_toks))
         head = (ctx, C.byref(self.model.ccfg), C.byref(self.model.weights), C.byref(self.state))
-        if draft is None:
+        if tree:
+            check(L.rama_q8_spec_begin_tree(*head, _i32(ctx_toks), len(ctx_toks), C.byref(rec), B, R), "rama_q8_spec_begin_tree")
+        elif draft is None:
             check(L.rama_q8_spec_begin(*head, _i32(ctx_toks), len(ctx_toks), C.byref(rec)), "rama_q8_spec_begin")
         else:
             check(L.rama_q8_spec_begin_model(*head, C.byref(draft.model.ccfg), C.byref(draft.model.weights), C.byref(draft.state),
@@ -212,8 +221,39 @@ class Q8Engine:
             q = rama_q8_spec_model_report()
             check(L.rama_q8_spec_model_stats(ctx, C.byref(q)), "rama_q8_spec_model_stats")
             self.spec_stats.update(_report(q))
+        if tree:
+            q = rama_q8_spec_tree_report()
+            check(L.rama_q8_spec_tree_stats(ctx, C.byref(q)), "rama_q8_spec_tree_stats")
+            self.spec_stats.update(_report(q))
         check(L.rama_q8_spec_end(ctx), "rama_q8_spec_end")
         return out
+
+    def tree_forward(self, tokens, parent, pos0: int) -> np.ndarray:
+        """an eager pass over a tree of up to 16 rows (rama_q8_tree_forward): row j carries tokens[j] below row parent[j]
+        (parent[0] = -1, parent[j] < j), the root at position pos0 -> the logits [len(tokens), vocab_size], each row's those of
+        forward() after the prefix and the row's path.  Only the root's cache row is written."""
+        toks = _tokens(tokens, self.cfg.vocab_size, "tree_forward")
+        par = [int(p) for p in parent]
+        if len(par) != len(toks):
+            raise ValueError(f"tree_forward: {len(par)} parents for {len(toks)} tokens")
+        n, V = len(toks), self.cfg.vocab_size
+        L, ctx = self.device.lib, self.device.ctx
+        buf = C.c_void_p()
+        check(L.rama_alloc_f32(ctx, max(n, 1) * V, C.byref(buf)), "rama_alloc_f32")
+        try:
+            check(L.rama_q8_tree_forward(ctx, C.byref(self.model.ccfg), C.byref(self.model.weights), C.byref(self.state), _i32(toks), _i32(par),
+                                         n, int(pos0), buf), "rama_q8_tree_forward")
+            out = np.empty((n, V), dtype=np.float32)
+            check(L.rama_download_f32(ctx, buf, n * V, out.ctypes.data))
+        finally:
+            check(L.rama_free(ctx, buf))
+        return out
+
+    def tree_commit(self, path, pos0: int):
+        """the rows of a root-to-node path of the last tree_forward into cache positions pos0 + 1 .. (rama_q8_tree_commit)"""
+        path = [int(p) for p in path]
+        check(self.device.lib.rama_q8_tree_commit(self.device.ctx, C.byref(self.model.ccfg), C.byref(self.state), _i32(path), len(path), int(pos0)),
+              "rama_q8_tree_commit")
 
     def set_graph_mode(self, on: bool):
         check(self.device.lib.rama_set_graph_mode(self.device.ctx, int(bool(on))), "rama_set_graph_mode")
@@ -386,6 +426,21 @@ def spec_model_check(engine, draft, n_context, max_new, n_draft, hint_toks):
         raise ValueError(f"{what}: n_draft {n_draft} < 1 with a draft model")
 
 
+def spec_tree_check(draft, n_draft, n_branch, tree_rows):
+    """ValueError for what rama_q8_spec_begin_tree would refuse in its own arguments -> (n_branch, n_rows).  No library call."""
+    what = "generate_spec"
+    B, R = int(n_branch), int(tree_rows)
+    if draft is not None:
+        raise ValueError(f"{what}: tree drafts together with a draft model")
+    if not 1 <= B <= 4:
+        raise ValueError(f"{what}: n_branch {B} outside 1..4")
+    if not 2 <= R <= 16:
+        raise ValueError(f"{what}: tree_rows {R} outside 2..16")
+    if n_draft < 1:
+        raise ValueError(f"{what}: n_draft {n_draft} < 1 with tree drafts")
+    return B, R
+
+
 def spec_report(r) -> dict:
     """a rama_q8_spec_report as a dict"""
     return _report(r)
@@ -413,3 +468,28 @@ def spec_accept(drafts, picks, stop_token, remaining):
     if n < 0:
         check(n, "rama_q8_spec_accept")
     return n, bool(fin.value)
+
+
+def spec_tree_draft(hint, seq, n_draft, ngram, room, n_branch, n_rows):
+    """rama_q8_spec_tree_draft, the tree drafting rule as a pure host function -> (tok, parent, depth) of nodes 1..m.  No GPU."""
+    hint, seq = [int(t) for t in (hint or [])], [int(t) for t in seq]
+    tok, par, dep = ((C.c_int32 * 16)() for _ in range(3))
+    m = load().rama_q8_spec_tree_draft(_i32(hint) if hint else None, len(hint), _i32(seq), len(seq), int(n_draft), int(ngram), int(room),
+                                       int(n_branch), int(n_rows), tok, par, dep)
+    if m < 0:
+        check(m, "rama_q8_spec_tree_draft")
+    return tok[:m], par[:m], dep[:m]
+
+
+def spec_tree_accept(tok, parent, picks, stop_token, remaining):
+    """rama_q8_spec_tree_accept, the tree accept rule as a pure host function: tok / parent of nodes 1..m, picks of rows 0..m ->
+    (path, tokens emitted, finished).  No GPU."""
+    tok, parent, picks = [int(t) for t in tok], [int(t) for t in parent], [int(t) for t in picks]
+    if len(parent) != len(tok) or len(picks) != len(tok) + 1:
+        raise ValueError(f"spec_tree_accept: {len(tok)} tokens, {len(parent)} parents, {len(picks)} picks")
+    path, a, fin = (C.c_int32 * 16)(), C.c_int(), C.c_int()
+    n = load().rama_q8_spec_tree_accept(_i32(tok) if tok else None, _i32(parent) if parent else None, len(tok), _i32(picks),
+                                        -1 if stop_token is None else int(stop_token), int(remaining), path, C.byref(a), C.byref(fin))
+    if n < 0:
+        check(n, "rama_q8_spec_tree_accept")
+    return path[:a.value + 1], n, bool(fin.value)

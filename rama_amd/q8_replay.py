@@ -1,5 +1,5 @@
 """The Q8 chains' rules restated in plain Python, as oracles for the tests and the benchmarks: the drafting rule, the scheduling
-rule with drafts, the accept rule, and whole runs of the speculative chain (n-gram drafts, or a draft model's) and of a serving
+rule with drafts, the accept rule, the tree rules, and whole runs of the speculative chain (n-gram drafts, a tree of them, or a draft model's) and of a serving
 chain with drafts replayed from reference tokens.  No library call, nothing of rama_amd imported: rama_amd.q8 imports from here."""
 from __future__ import annotations
 
@@ -95,6 +95,83 @@ def spec_replay(ref_tokens, context, hint, n_draft, ngram, max_new, stop_token):
         s += picks[:emit]
         e += emit
         out.append((len(d), a, emit))
+    return out
+
+
+def spec_tree_draft(hint, seq, n_draft, ngram, room, n_branch, n_rows):
+    """the drafting rule over a tree (rama_q8_spec_tree_draft): the continuations of the first n_branch occurrences of the tail
+    n-gram -- hint before sequence, larger end first, at the largest n that has any -- inserted in order into a trie whose root
+    (node 0) carries seq[-1], until n_rows - 1 nodes exist -> (tok, parent, depth) of nodes 1..m."""
+    hint, seq = [int(t) for t in (hint or [])], [int(t) for t in seq]
+    cap, L = min(n_draft, room), len(seq)
+    tok, parent, depth = [seq[-1]], [-1], [0]
+    if cap <= 0:
+        return [], [], []
+    for n in range(min(ngram, L), 0, -1):
+        tail = seq[L - n:]
+        occ = [(hint, e) for e in range(len(hint), n - 1, -1) if hint[e - n:e] == tail]
+        occ += [(seq, e) for e in range(L - 1, n - 1, -1) if seq[e - n:e] == tail]
+        if not occ:
+            continue
+        full = False
+        for text, e in occ[:n_branch]:
+            cur = 0
+            for t in text[e:e + cap]:
+                kids = [j for j in range(1, len(tok)) if parent[j] == cur and tok[j] == t]
+                if kids:
+                    cur = kids[0]
+                    continue
+                if len(tok) - 1 >= n_rows - 1:
+                    full = True
+                    break
+                tok.append(t); parent.append(cur); depth.append(depth[cur] + 1)
+                cur = len(tok) - 1
+            if full:
+                break
+        break
+    return tok[1:], parent[1:], depth[1:]
+
+
+def spec_tree_accept(tok, parent, picks, remaining, stop):
+    """the accept rule over a tree (rama_q8_spec_tree_accept): tok / parent of nodes 1..m, picks of rows 0..m -> (path = the rows
+    visited from the root, tokens emitted, finished); a = len(path) - 1."""
+    tok, parent = [None] + [int(t) for t in tok], [-1] + [int(t) for t in parent]
+    stop = -1 if stop is None else int(stop)
+    cur, path, out = 0, [0], [int(picks[0])]
+    while out[-1] != stop and len(out) < remaining:
+        kids = [j for j in range(1, len(tok)) if parent[j] == cur and tok[j] == out[-1]]
+        if not kids:
+            break
+        cur = kids[0]
+        path.append(cur)
+        out.append(int(picks[cur]))
+    return path, out, len(out) >= remaining or out[-1] == stop
+
+
+def spec_tree_replay(ref_tokens, context, hint, n_draft, ngram, n_branch, n_rows, max_new, stop_token):
+    """the tree chain's steps (rama_q8_spec_begin_tree) as a pure function of its inputs, no library call: ref_tokens as
+    spec_replay's -> one (m, a, emitted, off_trunk, off_trunk_deep) per step up to the one that finishes the sequence; off_trunk =
+    the accepted nodes with index != depth, off_trunk_deep those of them at depth >= 2.  A node's pick is the reference token
+    behind its path as long as the path is right, which is all the accept rule looks at; any other node's pick is never read."""
+    ref, s = [int(t) for t in ref_tokens], [int(t) for t in context]
+    hint = [int(t) for t in (hint or [])]
+    if len(ref) < max_new:
+        raise ValueError(f"spec_tree_replay: {len(ref)} reference tokens for max_new {max_new}")
+    out, e, fin = [], 0, False
+    while not fin:
+        remaining = max_new - e
+        tok, parent, depth = spec_tree_draft(hint, s, n_draft, ngram, remaining - 1, n_branch, n_rows)
+        # a node on the reference's path at depth d is picked ref[e + d]; off it the pick is never compared: -2 matches nothing
+        right, picks = [True], [ref[e]]
+        for j in range(1, len(tok) + 1):
+            ok = right[parent[j - 1]] and e + depth[j - 1] - 1 < len(ref) and tok[j - 1] == ref[e + depth[j - 1] - 1]
+            right.append(ok)
+            picks.append(ref[e + depth[j - 1]] if ok and e + depth[j - 1] < len(ref) else -2)
+        path, emitted, fin = spec_tree_accept(tok, parent, picks, remaining, stop_token)
+        off = [j for k, j in enumerate(path) if j != k]
+        s += emitted
+        e += len(emitted)
+        out.append((len(tok), len(path) - 1, len(emitted), len(off), sum(1 for j in off if depth[j - 1] >= 2)))
     return out
 
 
