@@ -51,7 +51,7 @@ def _per_seq(v, n: int, counted: str) -> list:
     return v
 
 
-# ------------------------------------------------------------------ the refusals the entry points share (as check_* in q8_api.hip:
+# ------------------------------------------------------------------ the refusals the entry points share (as check_* in q8_host.hpp / q8_api.hip:
 # each takes the caller's prefix and, where two callers word a cap differently, that text)
 
 def _tokens(tokens, vocab_size: int, what: str) -> list:

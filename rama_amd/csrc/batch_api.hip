@@ -680,7 +680,7 @@ int rama_decode_batch_stream_poll(rama_ctx* c, int seq, int from, int32_t* out_h
 
 // ---- THE SERVING CHAIN IN PARITY MODE (rama_serve_*): continuous batching for an fp32 model in the reference's rounding order.  The
 // tables, the scheduler, the gather, the admission and the pick are the Q8 serving chain's (q8_serve.hpp, reached through ctx.hpp's launchers and the
-// shared host layer of q8_api.hip); the pass is chain_batch_layers over the step's row table in TILES of kGcMaxTok rows, in ascending order -- a slot's
+// shared host layer of q8_serve_api.hip); the pass is chain_batch_layers over the step's row table in TILES of kGcMaxTok rows, in ascending order -- a slot's
 // prompt rows may straddle a tile boundary, and the later tile's attention reads the cache rows the earlier tile's pass wrote.  Idle rows come last in
 // the table: a tile whose first row is idle costs its launches and no weight pass (chain.hpp).
 
@@ -823,7 +823,7 @@ int rama_serve_begin_spec(rama_ctx* c, const rama_config* cfg, const rama_weight
 }
 
 // ---- MODEL DRAFTS INSIDE THE FP32 SERVING CHAIN: rama_serve_begin_spec with hint_cap 0, plus a Q8 draft model over the same vocabulary.
-// The tables, the draft passes and the serve_model_* kernels are the Q8 chain's (q8_serve_model.hpp in q8_api.hip's code object, reached through ctx.hpp);
+// The tables, the draft passes and the serve_model_* kernels are the Q8 chain's (q8_serve_model.hpp in q8_serve_api.hip's code object, reached through ctx.hpp);
 // the verify half is the step of rama_serve_begin_spec.
 int rama_serve_begin_model(rama_ctx* c, const rama_config* cfg, const rama_weights* w, const rama_config* dcfg, const rama_q8_weights* dw,
                            int n_slots, int max_rows, int max_new_cap, int n_draft_cap) {

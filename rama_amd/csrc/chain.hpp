@@ -28,7 +28,7 @@
 // Results are bit-identical to ref_order.hpp's and to the oracle's (tests/test_hip_ref_order.py,
 // tests/test_hip_parity_7b.py).
 #pragma once
-#define RAMA_CHAIN_HPP 1      // (rama_api.hip, batch_api.hip and q8_api.hip refuse to be compiled with this header: its kernels are chain_api.hip's)
+#define RAMA_CHAIN_HPP 1      // (rama_api.hip, batch_api.hip and the three q8_*api.hip refuse to be compiled with this header: its kernels are chain_api.hip's)
 #include "kernels.hpp"
 #include "chain_params.hpp"     // ChainParams, GemmChainParams, CEPI_* / CNORM_*, the LDS sizes: what the launchers' callers see
 #include "ref_order.hpp"

@@ -1,4 +1,4 @@
-// ctx.hpp -- what the library's C-ABI translation units (rama_api.hip, batch_api.hip, chain_api.hip, q8_api.hip) share: the context, the error plumbing, graph
+// ctx.hpp -- what the library's C-ABI translation units (rama_api.hip, batch_api.hip, chain_api.hip, q8_api.hip, q8_serve_api.hip, q8_spec_api.hip) share: the context, the error plumbing, graph
 // capture, the launch macros, and declarations of what each defines for the others.  Internal: not installed, not part of the C ABI.
 //
 // The library is built WITHOUT relocatable device code, so a kernel or a __device__ global lives in the code object of the translation
@@ -257,7 +257,7 @@ struct rama_ctx {
         int* forced = nullptr; size_t forced_cap = 0;      // the forced lists, one after the other
     } bc;
     // what the three Q8 chains below share, and all that drop_q8_graphs, rama_internal_drop_q8_graphs and the _steps entries need of one (q8_api.hip
-    // q8_chains, q8_chain_steps): the model it was begun on, whether it may still run, its one captured step.  The chains share procedures, not state.
+    // q8_chains, q8_host.hpp q8_chain_steps): the model it was begun on, whether it may still run, its one captured step.  The chains share procedures, not state.
     struct Q8ChainBase {
         bool live = false;                 // false once the model or a run state the chain still uses has been freed: its _steps entry refuses
         rama_config cfg{}; rama_q8_weights w{};
@@ -281,7 +281,7 @@ struct rama_ctx {
         int* forced = nullptr; size_t forced_cap = 0;
         std::vector<rama_run_state> states;
     } q8c;
-    // What a serving chain keeps whatever its model (q8_api.hip serve_state_* / serve_admit_*): the geometry, the device tables, the admission records,
+    // What a serving chain keeps whatever its model (q8_serve_api.hip serve_state_* / serve_admit_*): the geometry, the device tables, the admission records,
     // the host-visible rings and the host's view of the slots.  The Q8 chain and the fp32 chain below each have one; they share procedures, not state.
     struct ServeState {
         int n_slots = 0, max_rows = 0, out_cap = 0;       // n_slots 0: no serving chain
@@ -428,7 +428,9 @@ int enqueue_topp_batch_order(rama_ctx* c, const ToppRow* rows, int n_rows, const
 void drop_q8_graphs(rama_ctx* c, const rama_run_state* s);      // drop_graph, rama_state_free: the captured Q8 steps, all of them (s == NULL) or those over one run state
 void release_q8(rama_ctx* c);                                   // rama_ctx_destroy: the Q8 stack's allocations; the stream is idle
 
-// the serving chains' shared host layer: what rama_q8_serve_* and rama_serve_* do alike is written once in q8_api.hip, which also
+// ---------------------------------------------------------------- defined in q8_serve_api.hip (check_slots_rows .. launch_serve_model_close)
+
+// the serving chains' shared host layer: what rama_q8_serve_* and rama_serve_* do alike is written once in q8_serve_api.hip, which also
 // owns q8_serve.hpp's kernels -- batch_api.hip reaches them through the launchers
 // The tables of one allocation in order, each rounded up to 256 bytes.  The same code lays a blob out twice: over no base for its size
 // (`used`), then over the allocation for the typed pointers.

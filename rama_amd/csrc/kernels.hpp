@@ -728,7 +728,7 @@ __global__ void attention_combine_kernel(const float* part, float* xb, int head_
 
 // ---------------------------------------------------------------- small ops
 
-// The kernels here that are no templates are the six that more than one translation unit sees (rama_api.hip and q8_api.hip launch them: embed_kernel, embed_rows_kernel, set_ctl_kernel,
+// The kernels here that are no templates are the six that more than one translation unit sees (rama_api.hip and q8_api.hip launch them, and every translation unit that includes this header emits them: embed_kernel, embed_rows_kernel, set_ctl_kernel,
 // copy_kernel, argmax_batch_kernel; rope_ref_cursor_kernel in ref_order.hpp).  Such a kernel is emitted by every translation unit that sees it, so they
 // are `inline` -- one host stub after linking, a copy of the device function per code object -- and must stay free of launch attributes and
 // __device__ globals.  Every other non-template kernel lives in ops_kernels.hpp, which rama_api.hip alone includes.

@@ -1,6 +1,6 @@
 // ops_kernels.hpp -- the kernels of kernels.hpp that are no templates and that rama_api.hip alone launches: the 1:1 ops, the synthetic fill.
 // A kernel that is no template is emitted by every translation unit that sees its definition, so these live
-// apart from the types, device functions and template kernels of kernels.hpp, which q8_api.hip sees too.
+// apart from the types, device functions and template kernels of kernels.hpp, which the other translation units see too.
 #pragma once
 #include "kernels.hpp"
 

@@ -8,6 +8,7 @@
 //     int32), val = val + ((float)ival * Ws[i][g]) * xs[g] -- three separately rounded fp32 operations, no contraction.
 // Everything else in the forward (norms, RoPE, attention, SiLU, residual adds) is parity mode's exact kernels.
 #pragma once
+#define RAMA_Q8_HPP 1           // (q8_serve_api.hip and q8_spec_api.hip refuse to be compiled with this header or q8_batch.hpp: their kernels are q8_api.hip's)
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>

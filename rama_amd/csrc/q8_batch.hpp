@@ -24,7 +24,7 @@
 namespace rama {
 
 constexpr int kQ8bWaves = 1;       // waves (row tiles) per workgroup: one, so that the few row tiles of Wo / W2 spread over every CU
-constexpr int kQ8bMaxTok = 128;    // token rows per launch (8 tiles of 16)
+// (kQ8bMaxTok, the token rows per launch -- 8 tiles of 16 --, is q8_host.hpp's: the launcher's constant, which the other Q8 translation units check against)
 
 struct Q8BatchParams {
     const int8_t* w[3]; const float* ws[3]; float* o[3];   // up to three matrices [rows, K] over the same activations
@@ -349,6 +349,33 @@ __global__ void q8_rope_batch_kernel(float* Q, float* Kr, const float* V, const 
     k[2 * j] = b0; k[2 * j + 1] = b1;
     kcb[(size_t)pos * dim + 2 * j] = b0; kcb[(size_t)pos * dim + 2 * j + 1] = b1;           // infer.rs:32
     vcb[(size_t)pos * dim + 2 * j] = v[2 * j]; vcb[(size_t)pos * dim + 2 * j + 1] = v[2 * j + 1];   // infer.rs:33
+}
+
+// infer.rs:25-33 for the rows of a tree (q8_tree.hpp): q8_rope_batch_kernel's arithmetic.  The root (row 0) writes its cache row; every
+// other live row writes its rotated k and its v into the tree store instead (two rows of one depth share a position).  Kr / V keep the layer's rows.
+__global__ void q8_rope_tree_kernel(float* Q, float* Kr, const float* V, const float* fr, const float* fi, int dim, int head_size,
+                                    const SeqSlot* seqs, size_t layer_off, float* ks, float* vs) {
+    RAMA_NO_CONTRACT
+    const int j = blockIdx.x * blockDim.x + threadIdx.x, t = blockIdx.y;
+    if (j >= dim / 2) return;
+    const int pos = seqs[t].pos;
+    if (pos < 0) return;                   // an idle row: nothing rotated, nothing stored
+    // (row 0 is never idle when any row is live; its bases are the sequence's)
+    float* kd = t == 0 ? seqs[t].kc + layer_off + (size_t)pos * dim : ks + (size_t)(t - 1) * dim;
+    float* vd = t == 0 ? seqs[t].vc + layer_off + (size_t)pos * dim : vs + (size_t)(t - 1) * dim;
+    float* q = Q + (size_t)t * dim;
+    float* k = Kr + (size_t)t * dim;
+    const float* v = V + (size_t)t * dim;
+    const int i = j % (head_size / 2);
+    const float fcr = fr[(size_t)pos * (head_size / 2) + i], fci = fi[(size_t)pos * (head_size / 2) + i];
+    const float q0 = q[2 * j], q1 = q[2 * j + 1];
+    const float a0 = q0 * fcr - q1 * fci, a1 = q0 * fci + q1 * fcr;
+    q[2 * j] = a0; q[2 * j + 1] = a1;
+    const float k0 = k[2 * j], k1 = k[2 * j + 1];
+    const float b0 = k0 * fcr - k1 * fci, b1 = k0 * fci + k1 * fcr;
+    k[2 * j] = b0; k[2 * j + 1] = b1;
+    kd[2 * j] = b0; kd[2 * j + 1] = b1;                           // infer.rs:32
+    vd[2 * j] = v[2 * j]; vd[2 * j + 1] = v[2 * j + 1];           // infer.rs:33
 }
 
 }  // namespace rama

@@ -17,6 +17,7 @@
 // Several rows of one slot in one step: the RoPE launch writes their cache rows before the attention launch reads them, and a
 // (head, row) workgroup at position p reads rows 0..p of its own slot only -- what rama_q8_prefill's passes rely on.
 #pragma once
+#define RAMA_Q8_SERVE_HPP 1     // (q8_api.hip and q8_spec_api.hip refuse to be compiled with this header: its kernels are q8_serve_api.hip's)
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -10,16 +10,15 @@
 //   serve_spec_pick_kernel       one workgroup per row: Device::sample of a flagged row's logits, nothing else
 //   serve_spec_accept_kernel     one workgroup per slot: the cursor of a slot inside its context, the one token of a final context row,
 //                                spec_accept_rule for a DECODE slot; the tokens go to out, the ring and the text, then the finished word
-// The rules are rama_q8_spec_draft's, rama_q8_serve_spec_plan_step's and rama_q8_spec_accept's (q8_api.hip), which the kernels must reproduce
-// exactly.
+// The rules are rama_q8_spec_draft's and rama_q8_spec_accept's (q8_spec_api.hip) and rama_q8_serve_spec_plan_step's (q8_serve_api.hip), which the
+// kernels must reproduce exactly.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "q8_serve.hpp"         // the chain it extends
-#include "q8_spec.hpp"          // spec_scan_text
-#include "q8_serve_spec_tables.hpp"
+#include "q8_serve_spec_tables.hpp"     // (and q8_spec_tables.hpp: spec_scan_text, spec_accept_rule -- not q8_spec.hpp, whose kernels are q8_spec_api.hip's)
 
 namespace rama {
 

@@ -9,32 +9,18 @@
 //   spec_accept_kernel   the accept rule (q8_spec_tables.hpp), the emitted tokens appended to s, to `out` and to the host-visible ring,
 //                        the count and the finished word, the counters
 // Nothing in a step's launch geometry depends on the sequence, so one captured graph serves the chain for its whole life.
-// The drafting rule is rama_q8_spec_draft's (q8_api.hip), which the kernel must reproduce exactly.
+// The drafting rule is rama_q8_spec_draft's (q8_spec_api.hip), which the kernel must reproduce exactly.
 #pragma once
+#define RAMA_Q8_SPEC_HPP 1      // (q8_api.hip and q8_serve_api.hip refuse to be compiled with this header: its kernels are q8_spec_api.hip's)
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "kernels.hpp"
 #include "topp_sort.hpp"
-#include "q8_spec_tables.hpp"
+#include "q8_spec_tables.hpp"   // the tables, spec_scan_text, spec_accept_rule
 
 namespace rama {
-
-// the latest end e in [n, hi] (exclusive end: text[e - n .. e) equals the tail) among this thread's candidates, as a key; -1: none.
-// Every load is made -- index clamped into the text -- and the comparison selected afterwards: no branch around a load.
-__device__ __forceinline__ int spec_scan_text(const int* text, int hi, int n, const int (&tail)[kSpecMaxNgram], int key_bit, int best) {
-    for (int e = n + (int)threadIdx.x; e <= hi; e += (int)blockDim.x) {
-        bool ok = true;
-#pragma unroll
-        for (int i = 0; i < kSpecMaxNgram; i++) {
-            const int v = text[min(e - n + i, e - 1)];            // e >= n >= 1: [e - n, e - 1] is inside the text
-            ok = ok && (i >= n || v == tail[i]);
-        }
-        best = ok ? max(best, key_bit | e) : best;
-    }
-    return best;
-}
 
 __global__ __launch_bounds__(1024) void spec_draft_kernel(SpecTables t) {
     __shared__ int s_best[16];

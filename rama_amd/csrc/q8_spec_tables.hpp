@@ -1,5 +1,5 @@
-// q8_spec_tables.hpp -- the speculative chain's device tables and its accept rule (q8_spec.hpp has the kernels that work on them): what
-// the host's context (ctx.hpp) keeps a copy of, so it holds no kernel
+// q8_spec_tables.hpp -- the speculative chain's device tables, its accept rule and the lookup's scan (q8_spec.hpp has the kernels that work on
+// them; the serving chain's drafting kernel of q8_serve_spec.hpp scans the same way): what the host's context (ctx.hpp) keeps a copy of, so it holds no kernel
 #pragma once
 
 #include "kernels.hpp"          // SeqSlot
@@ -71,6 +71,22 @@ __host__ __device__ inline int spec_accept_rule(const int* drafts, int n_d, cons
         if (picks[j] == stop) { emit = j + 1; fin = 1; break; }
     *finished = fin;
     return emit;
+}
+
+// THE LOOKUP'S SCAN (spec_draft_kernel, serve_draft_kernel): the latest end e in [n, hi] (exclusive end: text[e - n .. e) equals the tail) among
+// this thread's candidates, as a key; -1: none.
+// Every load is made -- index clamped into the text -- and the comparison selected afterwards: no branch around a load.
+__device__ __forceinline__ int spec_scan_text(const int* text, int hi, int n, const int (&tail)[kSpecMaxNgram], int key_bit, int best) {
+    for (int e = n + (int)threadIdx.x; e <= hi; e += (int)blockDim.x) {
+        bool ok = true;
+#pragma unroll
+        for (int i = 0; i < kSpecMaxNgram; i++) {
+            const int v = text[min(e - n + i, e - 1)];            // e >= n >= 1: [e - n, e - 1] is inside the text
+            ok = ok && (i >= n || v == tail[i]);
+        }
+        best = ok ? max(best, key_bit | e) : best;
+    }
+    return best;
 }
 
 }  // namespace rama

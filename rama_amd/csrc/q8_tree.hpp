@@ -4,12 +4,12 @@
 // attention takes each timestep behind the root from the ancestor of that depth.  Every step
 //   spec_tree_draft_kernel   spec_draft_kernel's scan n_branch times (round b: the largest key below round b - 1's), the trie, the row table,
 //                            the ancestor records, the row tokens, the sampler records
-//   the batched pass         q8_batch_layers with q8_rope_tree_kernel and attention_tree_kernel in place of the two launches that touch the cache
+//   the batched pass         q8_batch_layers with q8_rope_tree_kernel (q8_batch.hpp) and attention_tree_kernel in place of the two launches that touch the cache
 //   spec_pick_kernel         (q8_spec.hpp, unchanged: rows 0..m)
 //   spec_tree_accept_kernel  the accept rule over the tree, the ring / count / finished words as spec_accept_kernel stores them, the path
 //   tree_commit_kernel       the path's rows from the tree store to cache positions P + 1 .. P + a, every layer
 // This header serves two translation units (DESIGN.md "Translation units"): attention_tree_kernel is built from chain.hpp's pieces and lives
-// with them in chain_api.hip (the half under RAMA_CHAIN_HPP); everything else lives in q8_api.hip, which must not see chain.hpp.
+// with them in chain_api.hip (the half under RAMA_CHAIN_HPP); the drafts, the accept rule and the commit live in q8_spec_api.hip, which must not see chain.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -211,34 +211,10 @@ __global__ __launch_bounds__(NW * 64) void attention_tree_kernel(TreeAttnParams 
     if (tid < hs) p.xb[col + tid] = acc;
 }
 
-#else  // ---------------------------------------------------------------- everything but the attention: q8_api.hip's half
+#else  // ---------------------------------------------------------------- the drafts, the accept rule and the commit: q8_spec_api.hip's half
+#define RAMA_Q8_TREE_HPP 1      // (q8_api.hip and q8_serve_api.hip refuse to be compiled with this half: its kernels are q8_spec_api.hip's)
 
-// infer.rs:25-33 for the rows of a tree: q8_rope_batch_kernel's arithmetic.  The root (row 0) writes its cache row; every other live row
-// writes its rotated k and its v into the tree store instead (two rows of one depth share a position).  Kr / V keep the layer's rows.
-__global__ void q8_rope_tree_kernel(float* Q, float* Kr, const float* V, const float* fr, const float* fi, int dim, int head_size,
-                                    const SeqSlot* seqs, size_t layer_off, float* ks, float* vs) {
-    RAMA_NO_CONTRACT
-    const int j = blockIdx.x * blockDim.x + threadIdx.x, t = blockIdx.y;
-    if (j >= dim / 2) return;
-    const int pos = seqs[t].pos;
-    if (pos < 0) return;                   // an idle row: nothing rotated, nothing stored
-    // (row 0 is never idle when any row is live; its bases are the sequence's)
-    float* kd = t == 0 ? seqs[t].kc + layer_off + (size_t)pos * dim : ks + (size_t)(t - 1) * dim;
-    float* vd = t == 0 ? seqs[t].vc + layer_off + (size_t)pos * dim : vs + (size_t)(t - 1) * dim;
-    float* q = Q + (size_t)t * dim;
-    float* k = Kr + (size_t)t * dim;
-    const float* v = V + (size_t)t * dim;
-    const int i = j % (head_size / 2);
-    const float fcr = fr[(size_t)pos * (head_size / 2) + i], fci = fi[(size_t)pos * (head_size / 2) + i];
-    const float q0 = q[2 * j], q1 = q[2 * j + 1];
-    const float a0 = q0 * fcr - q1 * fci, a1 = q0 * fci + q1 * fcr;
-    q[2 * j] = a0; q[2 * j + 1] = a1;
-    const float k0 = k[2 * j], k1 = k[2 * j + 1];
-    const float b0 = k0 * fcr - k1 * fci, b1 = k0 * fci + k1 * fcr;
-    k[2 * j] = b0; k[2 * j + 1] = b1;
-    kd[2 * j] = b0; kd[2 * j + 1] = b1;                           // infer.rs:32
-    vd[2 * j] = v[2 * j]; vd[2 * j + 1] = v[2 * j + 1];           // infer.rs:33
-}
+// (q8_rope_tree_kernel is the pass's kernel, launched from q8_batch_layers: q8_batch.hpp, beside q8_rope_batch_kernel)
 
 // The commit: row path[k] of the store -> cache position pos0 + k for k = 1..a, every layer.  Grid (n_layers, 15): the path and a are read from
 // the chain state, so the launch is the same whatever was accepted.
@@ -261,7 +237,7 @@ __global__ __launch_bounds__(256) void tree_commit_kernel(TreeCommitParams p) {
     }
 }
 
-// spec_scan_text (q8_spec.hpp) with a ceiling: the largest key below `limit` among this thread's candidates
+// spec_scan_text (q8_spec_tables.hpp) with a ceiling: the largest key below `limit` among this thread's candidates
 __device__ __forceinline__ int spec_tree_scan_text(const int* text, int hi, int n, const int (&tail)[kSpecMaxNgram], int key_bit, int limit, int best) {
     for (int e = n + (int)threadIdx.x; e <= hi; e += (int)blockDim.x) {
         bool ok = true;

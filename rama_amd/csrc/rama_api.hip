@@ -1,7 +1,7 @@
 // rama_api.hip -- the C ABI of include/rama_hip.h: context, memory, the 1:1 Device<T>
 // ops, the fused decode path, the chained decode and generate, the tuning table, measurement.  Kernels are in kernels.hpp.  Parity mode's
-// kernels and the samplers are chain_api.hip's, the token batches and the fp32 serving chain batch_api.hip's, the Q8 entry points q8_api.hip's;
-// ctx.hpp is what the four share.
+// kernels and the samplers are chain_api.hip's, the token batches and the fp32 serving chain batch_api.hip's, the Q8 entry points q8_api.hip's, q8_serve_api.hip's and
+// q8_spec_api.hip's; ctx.hpp is what the six share.
 #include "../../include/rama_hip.h"
 #include "kernels.hpp"
 #include "ops_kernels.hpp"

@@ -1,6 +1,6 @@
 // ref_kernels.hpp -- the kernels of ref_order.hpp (none is a template) but rope_ref_cursor_kernel: rama_api.hip alone launches them.
 // A kernel that is no template is emitted by every translation unit that sees its definition, so these live
-// apart from the types, device functions and template kernels of ref_order.hpp, which q8_api.hip sees too.
+// apart from the types, device functions and template kernels of ref_order.hpp, which the Q8 translation units see too.
 #pragma once
 #include "ref_order.hpp"
 

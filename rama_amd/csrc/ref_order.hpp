@@ -87,7 +87,7 @@ struct RefMatParams { const float* w[3]; float* o[3]; const float* x; int K, row
 // ---------------------------------------------------------------- cpu.rs:74-97 apply_position, all heads
 
 // cpu.rs:74-97 apply_position over all heads + the two cache appends of infer.rs:31-33, the position taken from the device cursor: table row pos,
-// cache row pos (rope_ref_kernel, with the position given: ref_kernels.hpp).  Shared with q8_api.hip, hence `inline`: see kernels.hpp "small ops"
+// cache row pos (rope_ref_kernel, with the position given: ref_kernels.hpp).  Shared with q8_api.hip (rama_q8_forward's launch), hence `inline`: see kernels.hpp "small ops"
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wcuda-compat"      // ("another compiler ignores `inline` on a kernel": this one does not)
 inline __global__ void rope_ref_cursor_kernel(float* q, float* k, const float* v, const float* fr, const float* fi, int dim, int head_size,

@@ -1,6 +1,6 @@
 // topp_kernels.hpp -- the samplers' kernels that are no templates (five of topp_sort.hpp, argmax_kernel, topp_pick_kernel): chain_api.hip alone launches them.
 // A kernel that is no template is emitted by every translation unit that sees its definition, so these live
-// apart from the types, device functions and template kernels of topp_sort.hpp, which q8_api.hip sees too.
+// apart from the types, device functions and template kernels of topp_sort.hpp, which the Q8 translation units see too (q8_serve_api.hip and q8_spec_api.hip for their pick kernels).
 #pragma once
 #include "topp_sort.hpp"
 

@@ -1,4 +1,4 @@
-"""What the Q8 entries share on the host (q8_api.hip: the check_* refusals, q8_chains): every entry that goes through a shared check
+"""What the Q8 entries share on the host (q8_host.hpp / q8_api.hip: the check_* refusals, q8_chains): every entry that goes through a shared check
 refuses with RAMA_EINVAL in its OWN words -- rama_last_error starts with that entry's prefix and the text it has always had --, and
 freeing the model ends all three chains begun on one context, each _steps entry refusing with its own text.  The two plan functions
 are pure host functions; everything else needs a context, hence a GPU."""
