@@ -854,6 +854,53 @@ int  rama_q8_tree_forward(rama_ctx *ctx, const rama_config *cfg, const rama_q8_w
 int  rama_q8_tree_commit(rama_ctx *ctx, const rama_config *cfg, const rama_run_state *state, const int32_t *path_host, int n_path,
                          int pos0);
 
+/* THE SPECULATIVE CHAIN WITH TREE DRAFTS FROM A DRAFT MODEL: the draft model's second and third choices as branches.
+ * rama_q8_spec_begin_model_tree starts the speculative chain above with rama_q8_spec_begin_model's drafter and
+ * rama_q8_spec_begin_tree's verification; rama_q8_spec_steps / _poll / _tokens / _stats / _end serve it unchanged, and it ends a
+ * previous speculative chain.  Notation as above: K = plan->n_draft, B = n_branch in 1..4, R = n_rows in 2..16, P = L - 1, Dc the
+ * draft cursor, cap = min(K, seq_len - 1 - P, remaining - 1), at least 0, and 0 on a finished sequence.
+ * SHAPE (rama_q8_spec_model_tree_shape).  Static: a pure function of (cap, B, R), no data in it.  Node 0 is the root and carries
+ *   s[L-1].  Trunk first: nodes 1..min(cap, R-1), node d with parent d - 1, depth d, rank 0.  Then the sides, level by level: for
+ *   depth d = 1..cap and every node p of depth d - 1 in ascending index, each new node taking the next free index -- p on the trunk
+ *   (index == depth, the root included): side children of ranks 1..B-1; otherwise one child of rank 0.  Everything stops once R - 1
+ *   nodes exist; m = the nodes besides the root.  parent < index, and OFF THE TRUNK is index != depth as above.  B = 1: the line
+ *   1..cap.  B = 2, K = 4, R = 16: 14 nodes.
+ * CANDIDATES (rama_q8_spec_model_tree_candidates).  A node's token comes from the draft model's logits after the prefix and the
+ *   path to the node's PARENT.  Rank 0 is Device::sample of that row under the plan's (temperature, topp, u): rama_q8_spec_begin_model's
+ *   draft.  Ranks 1..B-1: order all tokens by a 64-bit key, descending -- high word the logit's bits mapped monotonically to
+ *   unsigned (bits ^ 0x80000000 for a clear sign bit, ~bits for a set one; a NaN lands where its bits put it), low word the token
+ *   index: the larger logit first, on ties the higher index, the argmax's own rule --, drop rank 0's token, take the first B - 1.
+ *   Children of one node have distinct tokens.
+ * STEP.  One graph replay on one stream.  OPEN: cap, the shape, the target's row table.  K DRAFT LEVELS: pass d feeds every node of
+ *   depth d - 1 at position P + d - 1 (pass 1: the root, behind rama_q8_spec_begin_model's catch-up row at P - 1 when P - Dc == 1);
+ *   only the root and the catch-up row write the draft cache, every other fed node leaves its rotated k and its v in row node - 1
+ *   of a draft tree store, and a fed row's attention takes timestep t <= P from the draft cache and timestep P + k from the store
+ *   row of its ancestor of depth k.  Each pass ends with its rows' picks: every child's token.  Passes d > cap are idle: position
+ *   -1, nothing written, nothing read.  VERIFY: the target's tree pass over rows 0..m, the picks, ACCEPT and COMMIT as
+ *   rama_q8_spec_begin_tree runs them.  CLOSE: the accepted path's fed nodes, depths 1..min(a, cap - 1), go from the draft store to
+ *   draft cache positions P+1..; Dc' = L + min(a, cap - 1) for cap >= 1 (L as the step opened; a budget or stop cut stops it at
+ *   the new L).  P - Dc stays in {0, 1}.  Nothing at or behind Dc', or behind the new P, is written in either cache.
+ * The output is rama_q8_generate's, bit for bit, whatever the drafter proposes.  Draft cache rows below Dc are those of a fresh
+ * rama_q8_prefill of the draft model, and every node's draft logits those of rama_q8_forward after the prefix and the node's path.
+ * rama_q8_spec_begin_model_tree: rama_q8_spec_begin_model's contract and refusals, plus RAMA_EINVAL for n_branch outside 1..4,
+ * n_rows outside 2..16 and n_branch > vocab_size.  Checks come first: a refusal leaves a running chain as it was.  It also sizes
+ * the tree store and the draft tree store, [dn_layers][R-1][ddim] floats twice, outside any capture.  rama_q8_spec_steps answers
+ * RAMA_EINVAL once either model or either run state is freed.
+ * rama_q8_spec_model_stats and rama_q8_spec_tree_stats both answer on this chain: draft_passes = sum cap, draft_rows_fed = the live
+ * draft rows (catch-up rows included), drafts = sum m, rows_fed = sum (m + 1), accepted = sum a; off_trunk_* and nodes_hist as above.
+ * rama_q8_spec_model_tree_shape and _candidates are HOST-ONLY pure functions, RAMA_EINVAL (negative) on a bad argument.  _shape
+ * (cap in 0..15) returns m and fills parent_out / depth_out / rank_out[0..m) with nodes 1..m.  _candidates (n in 0..3, n <
+ * vocab_size, rank0_token in the vocabulary) fills out[0..n) with ranks 1..n and returns n.
+ * rama_q8_spec_model_tree_last synchronises and reports the last step's tree as the device built it: tok / parent / depth / picks
+ * [0..m] (>= 16 entries each; node 0 the root), path[0..a] (>= 16 entries), *m and *a.  RAMA_EINVAL on a chain begun any other way. */
+int  rama_q8_spec_begin_model_tree(rama_ctx *ctx, const rama_config *cfg, const rama_q8_weights *w, const rama_run_state *state,
+                                   const rama_config *dcfg, const rama_q8_weights *dw, const rama_run_state *dstate,
+                                   const int32_t *context_host, int n_context, const rama_q8_spec_plan *plan, int n_branch, int n_rows);
+int  rama_q8_spec_model_tree_shape(int cap, int n_branch, int n_rows, int32_t *parent_out, int32_t *depth_out, int32_t *rank_out);
+int  rama_q8_spec_model_tree_candidates(const float *logits_host, int vocab_size, int rank0_token, int n, int32_t *out);
+int  rama_q8_spec_model_tree_last(rama_ctx *ctx, int32_t *tok, int32_t *parent, int32_t *depth, int32_t *picks, int32_t *path,
+                                  int *m, int *a);
+
 /* SPECULATION INSIDE THE SERVING CHAIN: a DECODE slot's drafts fill the rows no slot wants.  A step of the
  * serving chain costs its weight pass of max_rows rows whatever they hold, and rows at consecutive positions of one sequence
  * are exact (the speculative chain above); so a slot may put drafted tokens into rows that would otherwise be idle, and take

@@ -322,6 +322,16 @@ extern "C" {
                                 tokens_host: *const i32, parent_host: *const i32, n_rows: c_int, pos0: c_int, logits_dev: *mut f32) -> c_int;
     pub fn rama_q8_tree_commit(ctx: *mut rama_ctx, cfg: *const rama_config, state: *const rama_run_state, path_host: *const i32, n_path: c_int,
                                pos0: c_int) -> c_int;
+    // ... with a tree whose branches are the draft model's second and third choices; _shape and _candidates are host-only
+    pub fn rama_q8_spec_begin_model_tree(ctx: *mut rama_ctx, cfg: *const rama_config, w: *const rama_q8_weights, state: *const rama_run_state,
+                                         dcfg: *const rama_config, dw: *const rama_q8_weights, dstate: *const rama_run_state,
+                                         context_host: *const i32, n_context: c_int, plan: *const rama_q8_spec_plan, n_branch: c_int,
+                                         n_rows: c_int) -> c_int;
+    pub fn rama_q8_spec_model_tree_shape(cap: c_int, n_branch: c_int, n_rows: c_int, parent_out: *mut i32, depth_out: *mut i32,
+                                         rank_out: *mut i32) -> c_int;
+    pub fn rama_q8_spec_model_tree_candidates(logits_host: *const f32, vocab_size: c_int, rank0_token: c_int, n: c_int, out: *mut i32) -> c_int;
+    pub fn rama_q8_spec_model_tree_last(ctx: *mut rama_ctx, tok: *mut i32, parent: *mut i32, depth: *mut i32, picks: *mut i32, path: *mut i32,
+                                        m: *mut c_int, a: *mut c_int) -> c_int;
     // speculation inside the serving chain: a DECODE slot's drafts in the rows no slot wants; _plan_step is host-only
     pub fn rama_q8_serve_begin_spec(ctx: *mut rama_ctx, cfg: *const rama_config, w: *const rama_q8_weights, n_slots: c_int, max_rows: c_int,
                                     max_new_cap: c_int, n_draft_cap: c_int, hint_cap: c_int) -> c_int;

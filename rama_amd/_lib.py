@@ -278,6 +278,11 @@ SIGNATURES = {
     "rama_q8_spec_tree_accept": (_int, [i32p, i32p, _int, i32p, _int, _int, i32p, C.POINTER(_int), C.POINTER(_int)]),
     "rama_q8_tree_forward": (_int, [_vp, _cfgp, C.POINTER(rama_q8_weights), _sp, i32p, i32p, _int, _int, _vp]),
     "rama_q8_tree_commit": (_int, [_vp, _cfgp, _sp, i32p, _int, _int]),
+    "rama_q8_spec_begin_model_tree": (_int, [_vp, _cfgp, C.POINTER(rama_q8_weights), _sp, _cfgp, C.POINTER(rama_q8_weights), _sp, i32p, _int,
+                                             C.POINTER(rama_q8_spec_plan), _int, _int]),
+    "rama_q8_spec_model_tree_shape": (_int, [_int, _int, _int, i32p, i32p, i32p]),
+    "rama_q8_spec_model_tree_candidates": (_int, [C.POINTER(C.c_float), _int, _int, _int, i32p]),
+    "rama_q8_spec_model_tree_last": (_int, [_vp, i32p, i32p, i32p, i32p, i32p, C.POINTER(_int), C.POINTER(_int)]),
     "rama_q8_serve_begin_spec": (_int, [_vp, _cfgp, C.POINTER(rama_q8_weights), _int, _int, _int, _int, _int]),
     "rama_q8_serve_admit_spec": (_int, [_vp, _int, _sp, i32p, _int, _int, C.POINTER(rama_q8_serve_plan), C.POINTER(rama_q8_serve_spec)]),
     "rama_q8_serve_spec_plan_step": (_int, [C.POINTER(rama_q8_serve_slot), _int, _int, i32p, C.POINTER(rama_q8_serve_row), i32p]),

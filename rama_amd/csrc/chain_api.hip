@@ -20,6 +20,9 @@ int chain_api_init(rama_ctx*) {
     HIPCHK(hipFuncSetAttribute((const void*)attention_tree_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAttnChainMaxLds));
     HIPCHK(hipFuncSetAttribute((const void*)attention_tree_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAttnChainMaxLds));
     HIPCHK(hipFuncSetAttribute((const void*)attention_tree_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAttnChainMaxLds));
+    HIPCHK(hipFuncSetAttribute((const void*)attention_draft_tree_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAttnChainMaxLds));
+    HIPCHK(hipFuncSetAttribute((const void*)attention_draft_tree_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAttnChainMaxLds));
+    HIPCHK(hipFuncSetAttribute((const void*)attention_draft_tree_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAttnChainMaxLds));
 #define RAMA_GC_ATTR(TPW_) \
     HIPCHK(hipFuncSetAttribute((const void*)gemm_chain_kernel<TPW_, CEPI_STORE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm_chain_lds_bytes(TPW_))); \
     HIPCHK(hipFuncSetAttribute((const void*)gemm_chain_kernel<TPW_, CEPI_RESID>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm_chain_lds_bytes(TPW_))); \
@@ -281,8 +284,16 @@ int launch_attention_chain_tokens(rama_ctx* c, const RefAttnParams& a, int n_hea
 }
 
 // the same grid for the rows of a tree pass (q8_tree.hpp): a timestep behind the root's position is read from an ancestor's row of the pass
-int launch_attention_tree(rama_ctx* c, const TreeAttnParams& a, int n_heads, int nt, int nw, size_t lds) {
+// (by_node: a level of a draft model's tree, q8_spec_model_tree.hpp -- a.kr / a.v are the layer's slice of the draft tree store, the path's nibbles nodes)
+int launch_attention_tree(rama_ctx* c, const TreeAttnParams& a, int n_heads, int nt, int nw, size_t lds, bool by_node) {
     const dim3 grid(n_heads, nt);
+    if (by_node) {
+        if (nw == 4) hipLaunchKernelGGL((attention_draft_tree_kernel<4>), grid, dim3(4 * 64), lds, c->stream, a);
+        else if (nw == 8) hipLaunchKernelGGL((attention_draft_tree_kernel<8>), grid, dim3(8 * 64), lds, c->stream, a);
+        else hipLaunchKernelGGL((attention_draft_tree_kernel<16>), grid, dim3(16 * 64), lds, c->stream, a);
+        LAUNCHCHK();
+        return 0;
+    }
     if (nw == 4) hipLaunchKernelGGL((attention_tree_kernel<4>), grid, dim3(4 * 64), lds, c->stream, a);
     else if (nw == 8) hipLaunchKernelGGL((attention_tree_kernel<8>), grid, dim3(8 * 64), lds, c->stream, a);
     else hipLaunchKernelGGL((attention_tree_kernel<16>), grid, dim3(16 * 64), lds, c->stream, a);

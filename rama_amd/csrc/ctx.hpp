@@ -336,6 +336,12 @@ struct rama_ctx {
         bool tree = false;
         TreeTables tt{};                   // the tree record and the ancestor records (inside blob), the tree store (tblob)
         char* tblob = nullptr;
+        // a chain begun with rama_q8_spec_begin_model_tree (q8_spec_model_tree.hpp): model and tree both set, and the draft model runs over the
+        // tree level by level; all of it unused otherwise
+        SpecModelTreeTables xt{};          // the levels' row tables (inside blob), the draft tree store (xblob)
+        char* xblob = nullptr;
+        int n_levels = 0;                  // n_draft: the draft passes of a step
+        int level_rows[kSpecMaxDraft] = {};   // the rows of draft pass d at [d - 1]: the widest that level gets at any cap
     } q8p;
     // rama_q8_tree_forward / _commit (q8_tree.hpp): the tables of an eager tree pass and what its commit checks a path against
     struct Q8Tree {
@@ -413,7 +419,7 @@ int ensure_attn_scores(rama_ctx* c, int n_heads, int seq_len);
 int launch_attention_chain(rama_ctx* c, float* xb, float* att, const float* q, const float* kc_layer, const float* vc_layer,
                            const Ctl* ctl, int pos, int dim, int head_size, int seq_len, int n_heads, bool long_ctx = false, bool spread_wanted = false);
 int launch_attention_chain_tokens(rama_ctx* c, const RefAttnParams& a, int n_heads, int nt, int nw, size_t lds);
-int launch_attention_tree(rama_ctx* c, const TreeAttnParams& a, int n_heads, int nt, int nw, size_t lds);      // q8_tree.hpp's attention_tree_kernel
+int launch_attention_tree(rama_ctx* c, const TreeAttnParams& a, int n_heads, int nt, int nw, size_t lds, bool by_node = false);      // q8_tree.hpp's attention_tree_kernel / attention_draft_tree_kernel
 
 int topp_dist_check(rama_ctx* c);     // handoff_check: the distributed pick's error word
 int enqueue_sample(rama_ctx* c, ArgmaxParams fin, float temperature, float topp, float u);

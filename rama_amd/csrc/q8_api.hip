@@ -487,7 +487,7 @@ int ensure_q8_batch_scratch(rama_ctx* c, const rama_config* cfg, int gs, Q8Batch
 // row table): the two launches that touch the cache are swapped for the tree's -- only row 0 writes its cache row, the others' k and v go to
 // the tree store, and a row's attention reads the timesteps behind row 0's position from its ancestors' rows of this pass
 static int q8_batch_layers(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const Q8BatchScratch& b, int nt, int p0,
-                           float* key_cache, float* value_cache, const SeqSlot* seqs, const TreeTables* tree = nullptr) {
+                           float* key_cache, float* value_cache, const SeqSlot* seqs, const TreeTables* tree = nullptr, bool tree_by_node = false) {
     const int dim = cfg->dim, hidden = cfg->hidden_dim, hs = dim / cfg->n_heads, H = cfg->n_heads, seq = cfg->seq_len, gs = w->group_size;
     int rc;
     for (int l = 0; l < cfg->n_layers; l++) {
@@ -503,7 +503,19 @@ static int q8_batch_layers(rama_ctx* c, const rama_config* cfg, const rama_q8_we
         rc = launch_rmsnorm_chain(c, b.XN, b.X, w->rms_att_weight + (size_t)l * dim, dim, nullptr, nt, dim); if (rc) return rc;    // infer.rs:19
         rc = launch_q8_quantize(c, b.XN, nt * dim, gs, b.xq, b.xs); if (rc) return rc;
         rc = launch_q8_gemm<Q8EPI_STORE>(c, product(Q8P_QKV, dim, b.Q, b.Kr, b.V)); if (rc) return rc;                             // :20-23
-        if (tree) {
+        if (tree && tree_by_node) {      // a level of a draft model's tree: a fed node's k and v go to the store row of the NODE
+            const size_t store_off = (size_t)l * tree->store_rows * dim;
+            hipLaunchKernelGGL(q8_rope_tree_node_kernel, dim3((dim / 2 + 255) / 256, nt), dim3(256), 0, c->stream, b.Q, b.Kr, (const float*)b.V,
+                               w->freq_cis_real, w->freq_cis_imag, dim, hs, seqs, layer_off, tree->ks + store_off, tree->vs + store_off,
+                               (const TreeAnc*)tree->anc);
+            LAUNCHCHK();
+            TreeAttnParams ta{};
+            RefAttnParams& a = ta.a;
+            a.q = b.Q; a.att = b.ATT; a.xb = b.XB; a.dim = dim; a.head_size = hs; a.seq_len = seq; a.tok_stride = dim; a.att_stride = H * seq;
+            a.seqs = seqs; a.layer_off = layer_off;
+            ta.anc = tree->anc; ta.kr = tree->ks + store_off; ta.v = tree->vs + store_off;
+            rc = launch_attention_tree(c, ta, H, nt, b.nw, b.att_lds, true); if (rc) return rc;
+        } else if (tree) {
             const size_t store_off = (size_t)l * tree->store_rows * dim;
             hipLaunchKernelGGL(q8_rope_tree_kernel, dim3((dim / 2 + 255) / 256, nt), dim3(256), 0, c->stream, b.Q, b.Kr, (const float*)b.V,
                                w->freq_cis_real, w->freq_cis_imag, dim, hs, seqs, layer_off, tree->ks + store_off, tree->vs + store_off);
@@ -577,17 +589,17 @@ int enqueue_q8_classifier(rama_ctx* c, const rama_config* cfg, const rama_q8_wei
 
 // A pass over a device row table: the embedding rows of row_tok and every layer over `rows` (n_rows of them; an idle row has position -1) ...
 int enqueue_q8_row_layers(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const Q8BatchScratch& b, const int* row_tok,
-                          const SeqSlot* rows, int n_rows, const TreeTables* tree) {
+                          const SeqSlot* rows, int n_rows, const TreeTables* tree, bool tree_by_node) {
     const int dim = cfg->dim;
     hipLaunchKernelGGL(embed_rows_kernel, dim3((dim + 255) / 256, n_rows), dim3(256), 0, c->stream, b.X, w->token_embedding_table, row_tok, n_rows, dim);
     LAUNCHCHK();
-    return q8_batch_layers(c, cfg, w, b, n_rows, 0, nullptr, nullptr, rows, tree);
+    return q8_batch_layers(c, cfg, w, b, n_rows, 0, nullptr, nullptr, rows, tree, tree_by_node);
 }
 // ... and the classifier tail over every row: rama_q8_decode_batch's pass, and that of every chain's step but the serving chain's without
 // drafts, which classifies the rows it has gathered
 int enqueue_q8_batch_pass(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const Q8BatchScratch& b, const int* row_tok,
-                          const SeqSlot* rows, int n_rows, const TreeTables* tree) {
-    const int rc = enqueue_q8_row_layers(c, cfg, w, b, row_tok, rows, n_rows, tree); if (rc) return rc;
+                          const SeqSlot* rows, int n_rows, const TreeTables* tree, bool tree_by_node) {
+    const int rc = enqueue_q8_row_layers(c, cfg, w, b, row_tok, rows, n_rows, tree, tree_by_node); if (rc) return rc;
     return enqueue_q8_classifier(c, cfg, w, b, b.X, n_rows);
 }
 

@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "q8.hpp"
+#include "q8_tree_tables.hpp"      // TreeAnc (q8_rope_tree_node_kernel)
 
 namespace rama {
 
@@ -363,6 +364,35 @@ __global__ void q8_rope_tree_kernel(float* Q, float* Kr, const float* V, const f
     // (row 0 is never idle when any row is live; its bases are the sequence's)
     float* kd = t == 0 ? seqs[t].kc + layer_off + (size_t)pos * dim : ks + (size_t)(t - 1) * dim;
     float* vd = t == 0 ? seqs[t].vc + layer_off + (size_t)pos * dim : vs + (size_t)(t - 1) * dim;
+    float* q = Q + (size_t)t * dim;
+    float* k = Kr + (size_t)t * dim;
+    const float* v = V + (size_t)t * dim;
+    const int i = j % (head_size / 2);
+    const float fcr = fr[(size_t)pos * (head_size / 2) + i], fci = fi[(size_t)pos * (head_size / 2) + i];
+    const float q0 = q[2 * j], q1 = q[2 * j + 1];
+    const float a0 = q0 * fcr - q1 * fci, a1 = q0 * fci + q1 * fcr;
+    q[2 * j] = a0; q[2 * j + 1] = a1;
+    const float k0 = k[2 * j], k1 = k[2 * j + 1];
+    const float b0 = k0 * fcr - k1 * fci, b1 = k0 * fci + k1 * fcr;
+    k[2 * j] = b0; k[2 * j + 1] = b1;
+    kd[2 * j] = b0; kd[2 * j + 1] = b1;                           // infer.rs:32
+    vd[2 * j] = v[2 * j]; vd[2 * j + 1] = v[2 * j + 1];           // infer.rs:33
+}
+
+// The same for one level of a DRAFT MODEL's tree (q8_spec_model_tree.hpp): the rows of a pass are the nodes of one depth, so the store
+// row is the NODE's -- nibble `depth` of the row's path, row node - 1 --, not the pass row's.  A row of depth 0 (the root, the catch-up row in
+// front of it) writes its cache row.  ks / vs: the layer's slice of the draft tree store, n_rows - 1 rows; a node is at most n_rows - 1.
+__global__ void q8_rope_tree_node_kernel(float* Q, float* Kr, const float* V, const float* fr, const float* fi, int dim, int head_size,
+                                         const SeqSlot* seqs, size_t layer_off, float* ks, float* vs, const TreeAnc* anc) {
+    RAMA_NO_CONTRACT
+    const int j = blockIdx.x * blockDim.x + threadIdx.x, t = blockIdx.y;
+    if (j >= dim / 2) return;
+    const int pos = seqs[t].pos;
+    if (pos < 0) return;                   // an idle row: nothing rotated, nothing stored
+    const int depth = anc[t].depth;
+    const int node = (int)((anc[t].path >> (4 * depth)) & 15ull);
+    float* kd = depth == 0 ? seqs[t].kc + layer_off + (size_t)pos * dim : ks + (size_t)(node - 1) * dim;
+    float* vd = depth == 0 ? seqs[t].vc + layer_off + (size_t)pos * dim : vs + (size_t)(node - 1) * dim;
     float* q = Q + (size_t)t * dim;
     float* k = Kr + (size_t)t * dim;
     const float* v = V + (size_t)t * dim;

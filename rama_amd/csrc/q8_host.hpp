@@ -54,10 +54,11 @@ int q8_chain_scratch(rama_ctx* c, const rama_config* cfg, int group_size, int sa
 
 // a pass over a device row table: the embedding rows and every layer; the same with the classifier tail over every row; the classifier over
 // n_rows rows of src_rows into b.LG; what a sampled step does behind the classifier
+// (tree_by_node: `tree` is a level of a draft model's tree, q8_spec_model_tree.hpp -- its store holds row node - 1 of every node fed so far)
 int enqueue_q8_row_layers(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const Q8BatchScratch& b, const int* row_tok,
-                          const SeqSlot* rows, int n_rows, const TreeTables* tree = nullptr);
+                          const SeqSlot* rows, int n_rows, const TreeTables* tree = nullptr, bool tree_by_node = false);
 int enqueue_q8_batch_pass(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const Q8BatchScratch& b, const int* row_tok,
-                          const SeqSlot* rows, int n_rows, const TreeTables* tree = nullptr);
+                          const SeqSlot* rows, int n_rows, const TreeTables* tree = nullptr, bool tree_by_node = false);
 int enqueue_q8_classifier(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const Q8BatchScratch& b, const float* src_rows, int n_rows);
 int enqueue_q8_pick_rows(rama_ctx* c, const Q8BatchScratch& b, int V, bool sampled, const ToppRow* trow, int n_rows, PickRows* r);
 

@@ -11,6 +11,7 @@
 #include "q8_spec.hpp"
 #include "q8_spec_model.hpp"
 #include "q8_tree.hpp"
+#include "q8_spec_model_tree.hpp"
 
 #if defined(RAMA_CHAIN_HPP) || defined(RAMA_Q8_HPP) || defined(RAMA_Q8_SERVE_HPP)
 #error "q8_spec_api.hip must not include chain.hpp, q8.hpp / q8_batch.hpp or q8_serve.hpp: their kernels belong to other code objects"
@@ -24,7 +25,7 @@
 void spec_release(rama_ctx* c) {
     auto& sp = c->q8p;
     destroy_graph(sp.cg);
-    hipFree(sp.blob); hipFree(sp.dblob); hipFree(sp.tblob);
+    hipFree(sp.blob); hipFree(sp.dblob); hipFree(sp.tblob); hipFree(sp.xblob);
     if (sp.ring) hipHostFree(sp.ring);
     if (sp.words) hipHostFree(sp.words);
     sp = rama_ctx::Q8Spec();
@@ -100,6 +101,7 @@ static int spec_begin(rama_ctx* c, const char* entry, const rama_config* cfg, co
         REFUSE_UNLESS(plan->n_draft >= 1, entry, "n_draft outside 1..15");
         REFUSE_UNLESS(n_branch >= 1 && n_branch <= kTreeMaxBranch, entry, "n_branch outside 1..4");
         REFUSE_UNLESS(n_rows >= 2 && n_rows <= kSpecRows, entry, "n_rows outside 2..16");
+        if (dm) REFUSE_UNLESS(n_branch <= V, entry, "n_branch beyond vocab_size");
     }
     REFUSE_UNLESS(n_context >= 1, entry, "n_context < 1");
     REFUSE_UNLESS(plan->max_new >= 1, entry, "max_new < 1");
@@ -117,8 +119,10 @@ static int spec_begin(rama_ctx* c, const char* entry, const rama_config* cfg, co
     // the scratch and the chain's tables: sized here, outside any capture
     const int R = tree ? n_rows : plan->n_draft + 1;       // (a chain with a draft model has n_draft >= 1: its two-row draft pass fits the sampler's R slices)
     Q8BatchScratch b{};
-    rc = q8_chain_scratch(c, cfg, w->group_size, sampled ? R : 0, &b); if (rc) return rc;
+    // (a draft model's tree: a draft level has up to 15 rows -- two at least --, whatever R is)
+    rc = q8_chain_scratch(c, cfg, w->group_size, sampled ? (dm && tree ? kSpecRows : R) : 0, &b); if (rc) return rc;
     auto& sp = c->q8p;
+    SpecModelTreeTables& xt = sp.xt;
     SpecTables& t = sp.t;
     SpecModelTables& mt = sp.mt;
     TreeTables& tt = sp.tt;
@@ -129,6 +133,10 @@ static int spec_begin(rama_ctx* c, const char* entry, const rama_config* cfg, co
         bc.take(t.out, cap);
         if (dm) { bc.take(mt.ms, 1); bc.take(mt.rows, kSpecModelRows); bc.take(mt.row_tok, kSpecModelRows); bc.take(mt.trow, kSpecModelRows); }
         if (tree) { bc.take(tt.ts, 1); bc.take(tt.anc, kSpecRows); }
+        if (dm && tree) {
+            constexpr size_t n = (size_t)kSpecMaxDraft * kSpecRows;
+            bc.take(xt.xs, 1); bc.take(xt.dts, 1); bc.take(xt.rows, n); bc.take(xt.row_tok, n); bc.take(xt.trow, n); bc.take(xt.anc, n);
+        }
         return bc.used;
     };
     const size_t need = lay(nullptr);
@@ -154,6 +162,18 @@ static int spec_begin(rama_ctx* c, const char* entry, const rama_config* cfg, co
         th.n_branch = n_branch; th.n_rows = R;
         HIPCHK(hipMemcpy(tt.ts, &th, sizeof th, hipMemcpyHostToDevice));
     }
+    if (dm && tree) {      // the draft tree store, and every level's row count: the widest that depth gets at any cap
+        const size_t n = (size_t)dm->cfg->n_layers * (size_t)(R - 1) * (size_t)dm->cfg->dim;
+        HIPCHK(hipMalloc(&sp.xblob, 2 * n * sizeof(float)));
+        HIPCHK(hipMemset(sp.xblob, 0, 2 * n * sizeof(float)));
+        xt.ks = reinterpret_cast<float*>(sp.xblob); xt.vs = xt.ks + n; xt.store_rows = R - 1;
+        for (int d = 0; d < kSpecMaxDraft; d++) sp.level_rows[d] = d == 0 ? kSpecModelRows : 1;
+        for (int k = 1; k <= plan->n_draft; k++) {
+            int par[kSpecRows], dep[kSpecRows], rank[kSpecRows], width[kSpecRows] = {0};
+            const int m = spec_model_tree_shape(k, n_branch, R, par, dep, rank);
+            for (int j = 1; j <= m; j++) if (dep[j] < k) sp.level_rows[dep[j]] = std::max(sp.level_rows[dep[j]], ++width[dep[j]]);
+        }
+    }
     HIPCHK(hipHostMalloc(&sp.ring, sizeof(int) * cap, hipHostMallocMapped));
     HIPCHK(hipHostMalloc(&sp.words, sizeof(int) * 2, hipHostMallocMapped));
     memset(sp.ring, 0, sizeof(int) * cap);
@@ -175,6 +195,7 @@ static int spec_begin(rama_ctx* c, const char* entry, const rama_config* cfg, co
     sp.n_rows = R; sp.out_cap = plan->max_new; sp.captures = 0; sp.active = true; sp.live = true;
     if (dm) { sp.model = true; sp.dcfg = *dm->cfg; sp.dw = *dm->w; sp.dstate = *dm->state; }
     sp.tree = tree;
+    sp.n_levels = dm && tree ? plan->n_draft : 0;
     return 0;
 }
 
@@ -198,6 +219,14 @@ int rama_q8_spec_begin_tree(rama_ctx* c, const rama_config* cfg, const rama_q8_w
     return spec_begin(c, "q8_spec_begin_tree", cfg, w, state, nullptr, context_host, n_context, plan, n_branch, n_rows, true);
 }
 
+int rama_q8_spec_begin_model_tree(rama_ctx* c, const rama_config* cfg, const rama_q8_weights* w, const rama_run_state* state, const rama_config* dcfg,
+                                  const rama_q8_weights* dw, const rama_run_state* dstate, const int32_t* context_host, int n_context,
+                                  const rama_q8_spec_plan* plan, int n_branch, int n_rows) {
+    RAMA_ENTER(c);
+    const SpecDrafter dm{dcfg, dw, dstate};
+    return spec_begin(c, "q8_spec_begin_model_tree", cfg, w, state, &dm, context_host, n_context, plan, n_branch, n_rows, true);
+}
+
 // the commit of a tree pass: the path recorded in tt.ts, from the tree store into the caches at kc / vc (q8_tree.hpp tree_commit_kernel)
 static int launch_tree_commit(rama_ctx* c, const TreeTables& tt, float* kc, float* vc, int n_layers, int dim, int seq_len) {
     TreeCommitParams p{tt.ts, kc, vc, tt.ks, tt.vs, dim, seq_len, tt.store_rows};
@@ -208,12 +237,17 @@ static int launch_tree_commit(rama_ctx* c, const TreeTables& tt, float* kc, floa
 
 // one step of a chain begun with rama_q8_spec_begin_tree: the tree and its row table, the pass over it, every row's pick, the accept rule
 // over the tree, the accepted path's rows into the cache
+static int enqueue_q8_spec_model_tree_drafts(rama_ctx* c);
 static int enqueue_q8_spec_tree_step(rama_ctx* c, const Q8BatchScratch& b) {
     auto& sp = c->q8p;
     const int R = sp.n_rows;
-    hipLaunchKernelGGL(spec_tree_draft_kernel, dim3(1), dim3(1024), 0, c->stream, sp.t, sp.tt);
-    LAUNCHCHK();
-    int rc = enqueue_q8_batch_pass(c, &sp.cfg, &sp.w, b, sp.t.row_tok, sp.t.rows, R, &sp.tt); if (rc) return rc;
+    int rc = 0;
+    if (sp.model) { rc = enqueue_q8_spec_model_tree_drafts(c); if (rc) return rc; }      // (rama_q8_spec_begin_model_tree: the tree is the draft model's)
+    else {
+        hipLaunchKernelGGL(spec_tree_draft_kernel, dim3(1), dim3(1024), 0, c->stream, sp.t, sp.tt);
+        LAUNCHCHK();
+    }
+    rc = enqueue_q8_batch_pass(c, &sp.cfg, &sp.w, b, sp.t.row_tok, sp.t.rows, R, &sp.tt); if (rc) return rc;
     SpecPickParams fin{};
     fin.t = sp.t;
     rc = enqueue_q8_pick_rows(c, b, sp.cfg.vocab_size, sp.sampled, sp.t.trow, R, &fin.r); if (rc) return rc;
@@ -221,7 +255,34 @@ static int enqueue_q8_spec_tree_step(rama_ctx* c, const Q8BatchScratch& b) {
     LAUNCHCHK();
     hipLaunchKernelGGL(spec_tree_accept_kernel, dim3(1), dim3(64), 0, c->stream, sp.t, sp.tt);
     LAUNCHCHK();
-    return launch_tree_commit(c, sp.tt, sp.state.key_cache, sp.state.value_cache, sp.cfg.n_layers, sp.cfg.dim, sp.cfg.seq_len);
+    rc = launch_tree_commit(c, sp.tt, sp.state.key_cache, sp.state.value_cache, sp.cfg.n_layers, sp.cfg.dim, sp.cfg.seq_len); if (rc) return rc;
+    if (!sp.model) return 0;
+    // the draft cursor and the draft commit's record from what the accept rule took; then the same commit over the draft's caches and store
+    hipLaunchKernelGGL(spec_model_tree_close_kernel, dim3(1), dim3(64), 0, c->stream, sp.t, sp.mt, sp.tt, sp.xt);
+    LAUNCHCHK();
+    const TreeTables dt{sp.xt.dts, nullptr, sp.xt.ks, sp.xt.vs, sp.xt.store_rows};
+    return launch_tree_commit(c, dt, sp.dstate.key_cache, sp.dstate.value_cache, sp.dcfg.n_layers, sp.dcfg.dim, sp.dcfg.seq_len);
+}
+
+// the drafts of a chain begun with rama_q8_spec_begin_model_tree (q8_spec_model_tree.hpp): the step's opening launch, then n_draft passes of the draft
+// model over its own scratch, one per level of the tree, each ended by the pick that gives the level's children their tokens
+static int enqueue_q8_spec_model_tree_drafts(rama_ctx* c) {
+    auto& sp = c->q8p;
+    Q8BatchScratch db{};
+    q8_batch_scratch_lay(&sp.dcfg, sp.dw.group_size, kSpecRows, sp.dblob, &db);
+    hipLaunchKernelGGL(spec_model_tree_open_kernel, dim3(1), dim3(256), 0, c->stream, sp.t, sp.mt, sp.tt, sp.xt);
+    LAUNCHCHK();
+    for (int d = 1; d <= sp.n_levels; d++) {
+        const int n = sp.level_rows[d - 1], at = (d - 1) * kSpecRows;
+        const TreeTables lt{nullptr, sp.xt.anc + at, sp.xt.ks, sp.xt.vs, sp.xt.store_rows};
+        int rc = enqueue_q8_batch_pass(c, &sp.dcfg, &sp.dw, db, sp.xt.row_tok + at, sp.xt.rows + at, n, &lt, true); if (rc) return rc;
+        SpecModelTreePickParams pk{};
+        pk.t = sp.t; pk.tt = sp.tt; pk.x = sp.xt; pk.d = d;
+        rc = enqueue_q8_pick_rows(c, db, sp.dcfg.vocab_size, sp.sampled, sp.xt.trow + at, n, &pk.r); if (rc) return rc;
+        hipLaunchKernelGGL(spec_model_tree_pick_kernel, dim3(n), dim3(1024), 0, c->stream, pk);
+        LAUNCHCHK();
+    }
+    return 0;
 }
 
 // the drafts of a chain begun with rama_q8_spec_begin_model (q8_spec_model.hpp): the step's opening launch, then n_draft passes of the draft model
@@ -278,7 +339,8 @@ int rama_q8_spec_steps(rama_ctx* c, int n_steps) {
     REQUIRE(n_steps >= 0, RAMA_EINVAL, "q8_spec_steps: n_steps < 0");
     if (set_device(c)) return 1;
     int n_done = 0;
-    return q8_chain_steps(c, sp, sp.sampled ? sp.n_rows : 0, n_steps, [&](const Q8BatchScratch& b) { return enqueue_q8_spec_step(c, b); }, &n_done);
+    const int sampler_rows = sp.model && sp.tree ? kSpecRows : sp.n_rows;
+    return q8_chain_steps(c, sp, sp.sampled ? sampler_rows : 0, n_steps, [&](const Q8BatchScratch& b) { return enqueue_q8_spec_step(c, b); }, &n_done);
 }
 
 int rama_q8_spec_poll(rama_ctx* c, int from, int32_t* out_host, int max_tokens, int* n_ready, int* finished) {
@@ -375,6 +437,55 @@ int rama_q8_spec_tree_draft(const int32_t* hint, int n_hint, const int32_t* seq,
     }
     for (int j = 1; j <= m; j++) { tok_out[j - 1] = tok[j]; parent_out[j - 1] = parent[j]; depth_out[j - 1] = depth[j]; }
     return m;
+}
+
+// ---- TREES FROM A DRAFT MODEL (q8_spec_model_tree.hpp): the shape and the candidate order as host-only pure functions
+
+int rama_q8_spec_model_tree_shape(int cap, int n_branch, int n_rows, int32_t* parent_out, int32_t* depth_out, int32_t* rank_out) {
+    REQUIRE(cap >= 0 && cap <= kSpecMaxDraft && n_branch >= 1 && n_branch <= kTreeMaxBranch && n_rows >= 2 && n_rows <= kSpecRows, RAMA_EINVAL,
+            "q8_spec_model_tree_shape: cap in 0..15, n_branch in 1..4, n_rows in 2..16");
+    REQUIRE(parent_out && depth_out && rank_out, RAMA_EINVAL, "q8_spec_model_tree_shape: NULL argument");
+    int parent[kSpecRows], depth[kSpecRows], rank[kSpecRows];
+    const int m = spec_model_tree_shape(cap, n_branch, n_rows, parent, depth, rank);
+    for (int j = 1; j <= m; j++) { parent_out[j - 1] = parent[j]; depth_out[j - 1] = depth[j]; rank_out[j - 1] = rank[j]; }
+    return m;
+}
+
+// (spec_model_tree_pick_kernel finds the same tokens by n rounds of a workgroup-wide maximum below the round before's)
+int rama_q8_spec_model_tree_candidates(const float* logits_host, int vocab_size, int rank0_token, int n, int32_t* out) {
+    REQUIRE(logits_host && vocab_size >= 1 && rank0_token >= 0 && rank0_token < vocab_size, RAMA_EINVAL,
+            "q8_spec_model_tree_candidates: a logits row and a rank-0 token inside it");
+    REQUIRE(n >= 0 && n < kTreeMaxBranch && n < vocab_size && (n == 0 || out), RAMA_EINVAL,
+            "q8_spec_model_tree_candidates: n in 0..3, below vocab_size");
+    unsigned long long limit = ~0ull;
+    for (int r = 0; r < n; r++) {
+        unsigned long long best = 0ull;
+        for (int i = 0; i < vocab_size; i++) {
+            unsigned bits;
+            memcpy(&bits, logits_host + i, sizeof bits);
+            const unsigned long long k1 = spec_model_tree_key1(bits, i);
+            if (i != rank0_token && k1 < limit && k1 > best) best = k1;
+        }
+        out[r] = (int32_t)(unsigned)((best - 1ull) & 0xffffffffull);
+        limit = best;
+    }
+    return n;
+}
+
+int rama_q8_spec_model_tree_last(rama_ctx* c, int32_t* tok, int32_t* parent, int32_t* depth, int32_t* picks, int32_t* path, int* m, int* a) {
+    RAMA_ENTER(c);
+    REQUIRE(c && tok && parent && depth && picks && path && m && a && c->q8p.active && c->q8p.model && c->q8p.tree, RAMA_EINVAL,
+            "q8_spec_model_tree_last: no chain begun with rama_q8_spec_begin_model_tree");
+    { const int rh = q8_drain(c); if (rh) return rh; }
+    TreeState ts{};
+    SpecState s{};
+    HIPCHK(hipMemcpy(&ts, c->q8p.tt.ts, sizeof ts, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&s, c->q8p.t.st, sizeof s, hipMemcpyDeviceToHost));
+    REQUIRE(ts.m >= 0 && ts.m < kSpecRows && ts.a >= 0 && ts.a <= ts.m, RAMA_EINVAL, "q8_spec_model_tree_last: no step has run");
+    for (int j = 0; j <= ts.m; j++) { tok[j] = ts.tok[j]; parent[j] = ts.parent[j]; depth[j] = ts.depth[j]; picks[j] = s.picks[j]; }
+    for (int k = 0; k <= ts.a; k++) path[k] = ts.path[k];
+    *m = ts.m; *a = ts.a;
+    return 0;
 }
 
 // a caller's tree: parent[0] = -1, parent[j] in [0, j), depth at most 15 -> its depths; false for anything else

@@ -80,4 +80,53 @@ __host__ __device__ inline int spec_tree_accept_rule(const int* tok, const int* 
     return emit;
 }
 
+// ---------------------------------------------------------------- trees from a draft model (q8_spec_model_tree.hpp)
+
+// THE SHAPE (rama_q8_spec_model_tree_shape on the host, spec_model_tree_open_kernel on the device: one statement for both), a pure function of
+// (cap, n_branch, n_rows): the trunk 1..min(cap, n_rows - 1) first, then level by level every node of the level above in ascending index -- a
+// trunk node (index == depth, the root included) gets side children of ranks 1..n_branch - 1, any other node one child of rank 0 -- until
+// n_rows - 1 nodes exist.  parent / depth / rank: nodes 0..m (node 0 the root).  Returns m.
+__host__ __device__ inline int spec_model_tree_shape(int cap, int n_branch, int n_rows, int* parent, int* depth, int* rank) {
+    int m = 0;
+    parent[0] = -1; depth[0] = 0; rank[0] = 0;
+    for (int d = 1; d <= cap && m < n_rows - 1; d++) { m = d; parent[d] = d - 1; depth[d] = d; rank[d] = 0; }
+    for (int d = 1; d <= cap && m < n_rows - 1; d++) {
+        const int have = m;                                       // (the nodes of depth d - 1 all exist: the trunk's, or made one level up)
+        for (int p = 0; p <= have && m < n_rows - 1; p++) {
+            if (depth[p] != d - 1) continue;
+            if (p == depth[p]) {
+                for (int r = 1; r < n_branch && m < n_rows - 1; r++) { ++m; parent[m] = p; depth[m] = d; rank[m] = r; }
+            } else { ++m; parent[m] = p; depth[m] = d; rank[m] = 0; }
+        }
+    }
+    return m;
+}
+
+// THE CANDIDATE ORDER of ranks 1..: a token's 64-bit key -- the logit's bits mapped monotonically to unsigned (the sign-flip map; a NaN lands
+// where its bits put it) above the token index --, PLUS ONE so that 0 means "none".  Descending: the larger logit first, on ties the higher
+// index, the argmax's own tie rule.
+__host__ __device__ inline unsigned long long spec_model_tree_key1(unsigned bits, int index) {
+    const unsigned hi = bits ^ ((bits >> 31) ? 0xffffffffu : 0x80000000u);
+    return (((unsigned long long)hi << 32) | (unsigned long long)(unsigned)index) + 1ull;
+}
+
+// the step under way on the draft model's side, next to SpecModelState (Dc, L0, open and the counters are that record's)
+struct SpecModelTreeState {
+    int cap;                            // the step's depth bound (0: every draft row idle)
+    int pad_;
+    int child[kSpecRows][kTreeMaxBranch];      // node p's child of rank r (-1: none)
+    int row_of[kSpecRows];              // the row of the draft pass that feeds the node (-1: a node that is not fed)
+};
+
+struct SpecModelTreeTables {
+    SpecModelTreeState* xs;
+    SeqSlot* rows;                      // [kSpecMaxDraft][kSpecRows] level d's row table at (d - 1) kSpecRows (idle: position -1)
+    int* row_tok;                       // [kSpecMaxDraft][kSpecRows]
+    ToppRow* trow;                      // [kSpecMaxDraft][kSpecRows] temperature 0 but for a row that feeds a node
+    TreeAnc* anc;                       // [kSpecMaxDraft][kSpecRows] nibbles are NODES; pad = the node the row feeds (-1: the catch-up row, an idle row)
+    TreeState* dts;                     // the draft commit's record: a = min(a, cap - 1), the path, pos0
+    float* ks; float* vs;               // the draft tree store [dn_layers][n_rows - 1][ddim]: row node - 1
+    int store_rows;
+};
+
 }  // namespace rama

@@ -13,7 +13,8 @@ from ._lib import (Q8_TENSORS, check, load, rama_config, rama_q8_seq_plan, rama_
                    rama_q8_spec_tree_report,
                    rama_q8_weights, rama_run_state)
 from .q8_replay import (SERVE_DECODE, SERVE_DONE, SERVE_FREE, SERVE_PROMPT,  # noqa: F401  (the restatements: re-exported)
-                        _accept_py, _draft_py, _spec_plan_py, serve_model_replay, serve_spec_replay, spec_model_replay, spec_replay, spec_tree_replay)
+                        _accept_py, _draft_py, _spec_plan_py, serve_model_replay, serve_spec_replay, spec_model_replay, spec_model_tree_replay, spec_replay,
+                        spec_tree_replay)
 from .sampler_const import TOPP_U_CPU
 from .serve import (PrefixPool, ServeLoop, common_prefix, serve_model_plan_step, serve_model_report, serve_model_sizes,  # noqa: F401  (the serving loop: re-exported)
                     serve_plan, serve_plan_step, serve_sizes, serve_spec_plan_step, serve_spec_report, serve_spec_request, serve_spec_sizes)
@@ -168,13 +169,17 @@ class Q8Engine:
         ngram ignored; context[:-1] is prefilled on both engines, and spec_stats also has rama_q8_spec_model_stats' fields.
         n_branch = B in 1..4 (with tree_rows = R in 2..16, default 16): tree drafts (rama_q8_spec_begin_tree) --
         the continuations of the B latest occurrences share one pass of R rows; 1 <= n_draft, no draft model; spec_stats also
-        has rama_q8_spec_tree_stats' fields.  The default (None) stays the linear chain."""
+        has rama_q8_spec_tree_stats' fields.  The default (None) stays the linear chain.
+        draft together with n_branch / tree_rows: the tree is the draft model's (rama_q8_spec_begin_model_tree) -- its
+        first choice below every node, its next B - 1 choices below the trunk's; spec_stats carries all three reports."""
         ctx_toks, hint_toks, (T, P, U, new, stop, K, N) = spec_plan(self.cfg, context, max_new, temperature, topp, u, stop_token,
                                                                     n_draft, ngram, hint)
         if draft is not None:
             spec_model_check(self, draft, len(ctx_toks), new, K, hint_toks)
         tree = n_branch is not None or tree_rows is not None
-        if tree:
+        if tree and draft is not None:
+            B, R = spec_model_tree_check(self.cfg, K, 1 if n_branch is None else n_branch, 16 if tree_rows is None else tree_rows)
+        elif tree:
             B, R = spec_tree_check(draft, K, 1 if n_branch is None else n_branch, 16 if tree_rows is None else tree_rows)
         L, ctx = self.device.lib, self.device.ctx
         if len(ctx_toks) > 1:
@@ -184,7 +189,10 @@ class Q8Engine:
         harr = _i32(hint_toks)
         rec = rama_q8_spec_plan(T, P, U, new, stop, K, N, harr if hint_toks else None, len(hint_toks))
         head = (ctx, C.byref(self.model.ccfg), C.byref(self.model.weights), C.byref(self.state))
-        if tree:
+        if tree and draft is not None:
+            check(L.rama_q8_spec_begin_model_tree(*head, C.byref(draft.model.ccfg), C.byref(draft.model.weights), C.byref(draft.state),
+                                                  _i32(ctx_toks), len(ctx_toks), C.byref(rec), B, R), "rama_q8_spec_begin_model_tree")
+        elif tree:
             check(L.rama_q8_spec_begin_tree(*head, _i32(ctx_toks), len(ctx_toks), C.byref(rec), B, R), "rama_q8_spec_begin_tree")
         elif draft is None:
             check(L.rama_q8_spec_begin(*head, _i32(ctx_toks), len(ctx_toks), C.byref(rec)), "rama_q8_spec_begin")
@@ -441,6 +449,22 @@ def spec_tree_check(draft, n_draft, n_branch, tree_rows):
     return B, R
 
 
+def spec_model_tree_check(cfg, n_draft, n_branch, tree_rows):
+    """ValueError for what rama_q8_spec_begin_model_tree would refuse in its own arguments, beyond spec_model_check's -> (n_branch,
+    n_rows).  No library call."""
+    what = "generate_spec"
+    B, R = int(n_branch), int(tree_rows)
+    if not 1 <= B <= 4:
+        raise ValueError(f"{what}: n_branch {B} outside 1..4")
+    if not 2 <= R <= 16:
+        raise ValueError(f"{what}: tree_rows {R} outside 2..16")
+    if B > cfg.vocab_size:
+        raise ValueError(f"{what}: n_branch {B} beyond the vocabulary {cfg.vocab_size}")
+    if n_draft < 1:
+        raise ValueError(f"{what}: n_draft {n_draft} < 1 with a draft model")
+    return B, R
+
+
 def spec_report(r) -> dict:
     """a rama_q8_spec_report as a dict"""
     return _report(r)
@@ -493,3 +517,35 @@ def spec_tree_accept(tok, parent, picks, stop_token, remaining):
     if n < 0:
         check(n, "rama_q8_spec_tree_accept")
     return path[:a.value + 1], n, bool(fin.value)
+
+
+
+def spec_model_tree_shape(cap, n_branch, n_rows):
+    """rama_q8_spec_model_tree_shape, the static shape of a draft model's tree as a pure host function -> (parent, depth, rank) of
+    nodes 1..m.  No GPU."""
+    par, dep, rank = ((C.c_int32 * 16)() for _ in range(3))
+    m = load().rama_q8_spec_model_tree_shape(int(cap), int(n_branch), int(n_rows), par, dep, rank)
+    if m < 0:
+        check(m, "rama_q8_spec_model_tree_shape")
+    return par[:m], dep[:m], rank[:m]
+
+
+def spec_model_tree_candidates(logits, rank0_token, n):
+    """rama_q8_spec_model_tree_candidates, the tokens of ranks 1..n of a logits row as a pure host function: descending by (logit
+    bits mapped to unsigned, token index), rank 0's token dropped.  No GPU."""
+    row = np.ascontiguousarray(logits, dtype=np.float32).reshape(-1)
+    out = (C.c_int32 * 4)()
+    k = load().rama_q8_spec_model_tree_candidates(row.ctypes.data_as(C.POINTER(C.c_float)), int(row.size), int(rank0_token), int(n), out)
+    if k < 0:
+        check(k, "rama_q8_spec_model_tree_candidates")
+    return out[:k]
+
+
+def spec_model_tree_last(device):
+    """rama_q8_spec_model_tree_last: the last step's tree as the device built it -> dict(tok, parent, depth, picks of nodes 0..m,
+    path = the accepted rows, m, a).  Synchronises."""
+    tok, par, dep, picks, path = ((C.c_int32 * 16)() for _ in range(5))
+    m, a = C.c_int(), C.c_int()
+    check(device.lib.rama_q8_spec_model_tree_last(device.ctx, tok, par, dep, picks, path, C.byref(m), C.byref(a)), "rama_q8_spec_model_tree_last")
+    n = m.value + 1
+    return dict(tok=tok[:n], parent=par[:n], depth=dep[:n], picks=picks[:n], path=path[:a.value + 1], m=m.value, a=a.value)

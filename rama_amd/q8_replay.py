@@ -206,6 +206,89 @@ def spec_model_replay(ref_tokens, draft_fn, context, n_draft, max_new, stop_toke
     return out, cursor
 
 
+def spec_model_tree_shape(cap, n_branch, n_rows):
+    """the static shape of a draft model's tree (rama_q8_spec_model_tree_shape): the trunk 1..min(cap, n_rows - 1) first, then level
+    by level every node of the level above in ascending index -- a trunk node (index == depth, the root included) gets side children
+    of ranks 1..n_branch - 1, any other node one child of rank 0 -- until n_rows - 1 nodes exist -> (parent, depth, rank) of nodes 1..m."""
+    parent, depth, rank = [-1], [0], [0]
+    for d in range(1, cap + 1):
+        if len(parent) - 1 >= n_rows - 1:
+            break
+        parent.append(d - 1); depth.append(d); rank.append(0)
+    for d in range(1, cap + 1):
+        for p in range(len(parent)):
+            if depth[p] != d - 1:
+                continue
+            kids = range(1, n_branch) if p == depth[p] else (0,)
+            for r in kids:
+                if len(parent) - 1 >= n_rows - 1:
+                    break
+                parent.append(p); depth.append(d); rank.append(r)
+    return parent[1:], depth[1:], rank[1:]
+
+
+def spec_model_tree_candidates(logits, rank0_token, n):
+    """the tokens of ranks 1..n of a logits row (rama_q8_spec_model_tree_candidates): all tokens by descending 64-bit key -- high word
+    the float32's bits mapped monotonically to unsigned (a NaN where its bits put it), low word the token index --, rank 0's token
+    dropped, the first n."""
+    import struct
+    keys = []
+    for i, v in enumerate(logits):
+        bits = struct.unpack("<I", struct.pack("<f", v))[0]
+        hi = bits ^ (0xFFFFFFFF if bits >> 31 else 0x80000000)
+        if i != int(rank0_token):
+            keys.append((hi << 32) | i)
+    keys.sort(reverse=True)
+    return [k & 0xFFFFFFFF for k in keys[:n]]
+
+
+def spec_model_tree_replay(ref_tokens, logits_fn, context, n_draft, n_branch, n_rows, max_new, stop_token, sampler):
+    """the steps of the speculative chain with a draft model's tree (rama_q8_spec_begin_model_tree) as a pure function of its inputs,
+    no library call: ref_tokens as spec_replay's; logits_fn(prefix) = the draft model's logits row after the token list prefix;
+    sampler(row) = Device::sample of a logits row under the plan's sampler (rank 0) -> (one (cap, tok, parent, depth, picks, a, path,
+    emitted, catch_up) per step up to the one that finishes the sequence -- tok / parent / depth / picks of nodes 0..m, a pick that is
+    never compared given as -2 --, (the final cursor, the final draft cursor)).  cap = min(n_draft, remaining - 1) (n_context +
+    max_new <= seq_len: the budget binds first).  A node's token: rank 0 = sampler of the row after the prefix and the path to its
+    parent, rank r >= 1 = spec_model_tree_candidates of that row behind rank 0's token."""
+    ref, s = [int(t) for t in ref_tokens], [int(t) for t in context]
+    if len(ref) < max_new:
+        raise ValueError(f"spec_model_tree_replay: {len(ref)} reference tokens for max_new {max_new}")
+    out, e, fin, cursor = [], 0, False, len(s) - 1
+    while not fin:
+        L, remaining = len(s), max_new - e
+        cap = max(min(n_draft, remaining - 1), 0)
+        gap = L - 1 - cursor
+        if gap not in (0, 1):
+            raise AssertionError(f"spec_model_tree_replay: the draft cursor {cursor} is {gap} rows behind position {L - 1}")
+        par, dep, rank = spec_model_tree_shape(cap, n_branch, n_rows)
+        parent, depth, rank = [-1] + par, [0] + dep, [0] + rank
+        tok, rows = [s[-1]], {}
+        for j in range(1, len(parent)):
+            p = parent[j]
+            if p not in rows:                                      # the row of the pass that feeds p: its first choice, then the next ones
+                chain, c = [], p
+                while c > 0:
+                    chain.append(tok[c])
+                    c = parent[c]
+                row = logits_fn(list(s) + chain[::-1])
+                first = int(sampler(row))
+                rows[p] = [first] + spec_model_tree_candidates(row, first, n_branch - 1)
+            tok.append(int(rows[p][rank[j]]))
+        right, picks = [True], [ref[e]]
+        for j in range(1, len(tok)):
+            ok = right[parent[j]] and e + depth[j] - 1 < len(ref) and tok[j] == ref[e + depth[j] - 1]
+            right.append(ok)
+            picks.append(ref[e + depth[j]] if ok and e + depth[j] < len(ref) else -2)
+        path, emitted, fin = spec_tree_accept(tok[1:], parent[1:], picks, remaining, stop_token)
+        a = len(path) - 1
+        s += emitted
+        e += len(emitted)
+        if cap:                                                    # the fed nodes of the path, depths 1..min(a, cap - 1), are part of s now
+            cursor = min(L + min(a, cap - 1), len(s))
+        out.append((cap, tok, parent, depth, picks, a, path, emitted, gap if cap else 0))
+    return out, (len(s) - 1, cursor)
+
+
 def serve_spec_replay(requests, ref_tokens, n_slots, max_rows, use_slots=None, cancels=None):
     """a whole workload of a serving chain with drafts as a pure function of its inputs, no library call.  requests = dicts with
     context and max_new, and optionally stop_token, n_draft (0), ngram (3), hint and n_cached (0); ref_tokens[i] = the max_new
